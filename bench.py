@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoise-steps/sec of the HIP engine on BASELINE.json configs[1].
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--full] [--dump-outputs DIR]
                   [--image-size 64|128 --batch B --frames T --respacing ddim250 --executor eager|graph]
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` also writes what the
+last timed step returned (DIR/sample.npy, float32; inputs and noise are seeded, so the same arguments give the same inputs).
+Everything else the benchmark measures (the extra objects below) runs only with `--full`.
 
 N > 1 with no WORLD_SIZE in the environment: this process starts N children (one per GPU, RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* set) BEFORE it touches a GPU and exits with the worst child's code; under
@@ -17,7 +21,7 @@ video_sample.py:577-582, no collective inside the step; `--scaling weak` (defaul
 window, `--scaling strong` splits ONE B-clip window into B/N clips per rank.  The weights reach ranks > 0 through ONE
 RCCL broadcast of the packed buffer.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects of a `--full` run (each `--no-*` option below leaves one out):
   roofline      dominant kernel class: algorithmic FLOPs of its launches / their HIP-event durations, measured live in a
                 separate profiled step on the launch stream; `traffic` comes from the committed rocprofv3 PMC passes
                 (PMC cannot be read from inside the process) and says so in `traffic_source`
@@ -58,25 +62,65 @@ def parse_args():
     ap.add_argument("--respacing", default="ddim250")
     ap.add_argument("--num-res-blocks", type=int, default=2)
     ap.add_argument("--sampler", choices=["p_sample", "ddim"], default="p_sample",
-                    help="ddim: ddim_sample with eta = 0 (SURVEY 8d config 2 asks for it beside the p_sample headline; the default run reports it as `ddim_sample_eta0`)")
+                    help="ddim: ddim_sample with eta = 0 (SURVEY 8d config 2 asks for it beside the p_sample headline; a --full run reports it as `ddim_sample_eta0`)")
     ap.add_argument("--executor", choices=["eager", "graph"], default="eager",
                     help="graph: the window executor (one captured hipGraph per window shape, device-resident step counter)")
     ap.add_argument("--prefix-cache", action="store_true",
                     help="with --executor graph: the observed frames' activations before the first attention layer once per "
-                         "window (vd_set_window_prefix_cache); never the headline -- the default run reports it as an extra object")
+                         "window (vd_set_window_prefix_cache); never the headline -- a --full run reports it as an extra object")
     ap.add_argument("--suffix-skip", action="store_true",
                     help="with --executor graph: everything behind the last attention layer without the purely observed frames "
-                         "(vd_set_window_suffix_skip); never the headline -- the default run reports it as an extra object")
+                         "(vd_set_window_suffix_skip); never the headline -- a --full run reports it as an extra object")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: CPU baseline, roofline + kernel classes, parity margin, the other arithmetic "
+                         "modes, executor opt-ins and window shapes (child processes), drop-in, ddim_sample and whole-window legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/sample.npy (float32; a fixed seeded sample "
+                         "of it beyond 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-fp32-ref", action="store_true")
     ap.add_argument("--no-dropin", action="store_true")
     ap.add_argument("--parity-margin", action="store_true",
-                    help="also report max |eps - reference eps| of the headline window against tests/golden/unet_full64_b8.npz (the default run "
+                    help="also report max |eps - reference eps| of the headline window against tests/golden/unet_full64_b8.npz (a --full run "
                          "does, for its own arithmetic and, through its VD_MATH children, for the other two)")
     ap.add_argument("--no-full-window", action="store_true",
                     help="skip the whole-window leg (one 250-step window through video_sample.infer_video, ~6 s)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                     # a plain run: the headline steps only
+        args.no_cpu_baseline = args.no_roofline = args.no_fp32_ref = args.no_dropin = args.no_full_window = True
+    return args
+
+
+DUMP_BYTES = 64 << 20
+
+
+def child_argv(argv):
+    """The command line of a side-leg child: this run's own, without --dump-outputs (the dump is the parent's timed path only)."""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif not a.startswith("--dump-outputs="):
+            out.append(a)
+    return out
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """arrays: name -> tensor.  Each is written as out_dir/<name>.npy in float32; when the lot would pass `budget` bytes, every array
+    is replaced by the same fixed, seeded subset of its flattened elements (sorted indices, seed 0), scaled to fit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > budget:
+            a = a.reshape(-1)
+            keep = max(1, a.size * budget // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def rank_env(base, rank, world, port):
@@ -367,7 +411,7 @@ def main():
 
     def child(extra, env=None):
         """The same benchmark in a child process (started before this process touches the GPU); its JSON line, or {'error': ...}."""
-        c = subprocess.run([sys.executable, os.path.abspath(__file__), *sys.argv[1:], *SIDE_OFF, *extra], env={**os.environ, **(env or {})},
+        c = subprocess.run([sys.executable, os.path.abspath(__file__), *child_argv(sys.argv[1:]), *SIDE_OFF, *extra], env={**os.environ, **(env or {})},
                            capture_output=True, text=True)
         try:
             return json.loads([l for l in c.stdout.splitlines() if l.startswith("{")][-1])
@@ -481,6 +525,9 @@ def main():
     elapsed = timed(stepper, order, args.warmup, args.steps, vdist, device)
     assert torch.isfinite(stepper.result()).all()
     model.check_device_errors()                                    # a non-finite network output inside the timed steps (vd_device_errors bit 1) fails the run
+    if args.dump_outputs:
+        # x_{t-1} of the last timed step: the sample p_sample / ddim_sample hand back (rank r > 0 of a weak / strong job: its own window)
+        dump_outputs(args.dump_outputs, {"sample" if rank == 0 else f"sample_rank{rank}": stepper.result()}, budget=DUMP_BYTES // world)
 
     # SURVEY 8d config 2 asks for the p_sample number AND, separately, ddim_sample with eta = 0 (gaussian_diffusion.py:597-634): the same
     # window, the same network forward, the deterministic update -- timed here in the same process (never `value`)

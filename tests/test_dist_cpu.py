@@ -245,6 +245,36 @@ def test_bench_rank_environment_is_well_formed():
         bench.rank_env({}, 2, 2, 29500)
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path, monkeypatch):
+    """A plain bench run is the headline steps only (every side leg behind --full); --dump-outputs never reaches a side-leg child;
+    the dump is float32, whole when it fits and otherwise the same seeded subset of every array, within the byte budget."""
+    import importlib.util
+    import sys
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = ("no_cpu_baseline", "no_roofline", "no_fp32_ref", "no_dropin", "no_full_window")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None and all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-roofline", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "d" and a.no_roofline and not any(getattr(a, k) for k in legs if k != "no_roofline")
+    assert bench.child_argv(["--steps", "5", "--dump-outputs", "d", "--full", "--dump-outputs=e", "--frames", "20"]) == \
+        ["--steps", "5", "--full", "--frames", "20"]
+    x = torch.randn(2, 3, 4, 5, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"sample": x})
+    got = np.load(tmp_path / "whole" / "sample.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    y = torch.arange(1000.0)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"sample": y, "other": y + 1}, budget=800)
+    a1, b1, o1 = (np.load(tmp_path / d / f"{n}.npy") for d, n in (("a", "sample"), ("b", "sample"), ("a", "other")))
+    assert a1.size == o1.size == 100 and np.array_equal(a1, b1) and np.array_equal(o1, a1 + 1)       # fixed indices, 4 bytes each
+    assert np.all(np.diff(a1) > 0) and a1.dtype == np.float32
+
+
 def test_dist_init_picks_the_gpu_before_the_group_exists(monkeypatch):
     """RCCL: torch.cuda.set_device(local_rank) FIRST, then init_process_group(device_id=that device) -- the order of the
     reference's dist_util.py:100-110; a group without device_id guesses its GPU at the first collective."""

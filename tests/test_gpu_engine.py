@@ -1612,11 +1612,12 @@ def test_full_sampler_adaptive_autoreg_vs_oracle(monkeypatch):
     assert every.shape == (B, 5, T, 3, 32, 32) and np.array_equal(every[:, -1], got)       # the last horizontal pass is the result
 
 
-def test_bench_two_rank_launch_path_runs_on_the_box():
+def test_bench_two_rank_launch_path_runs_on_the_box(tmp_path):
     """The N > 1 path of `bench.py --gpus N` as the driver starts it on the 8-GPU node -- self-launch of one process per rank,
     rendezvous on 127.0.0.1, the layout-id all-reduce, the ONE packed-weight broadcast, barrier + max-over-ranks timing -- executed
     on this one-GPU box every round: two ranks over gloo, both on device 0 (RCCL refuses two ranks on one GPU; the 8-GPU run is the
-    driver's).  No scaling number is read off this.  Reference fan-out: improved_diffusion/command_launchers.py:32-62."""
+    driver's).  No scaling number is read off this.  Reference fan-out: improved_diffusion/command_launchers.py:32-62.
+    --dump-outputs: each rank writes the sample its last timed step returned."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1624,13 +1625,16 @@ def test_bench_two_rank_launch_path_runs_on_the_box():
     if os.path.exists(err1):
         os.remove(err1)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-fp32-ref", "--no-dropin", "--no-full-window", "--no-roofline"],
+                        "--no-fp32-ref", "--no-dropin", "--no-full-window", "--no-roofline", "--dump-outputs", str(tmp_path)],
                        env={**os.environ, "VD_BENCH_BACKEND": "gloo", "VD_BENCH_ALL_ON_DEVICE0": "1"}, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["rccl_ranks"] == 2 and line["scaling"] == "weak", line
     assert line["steps"] == 2 and line["warmup"] == 1 and np.isfinite(line["value"]) and line["value"] > 0
     assert abs(line["value"] - 2 * 1000.0 / line["ms_per_step"]) < 1e-2 * line["value"]      # whole-job steps/s = ranks x steps / slowest rank's time
+    s0, s1 = np.load(tmp_path / "sample.npy"), np.load(tmp_path / "sample_rank1.npy")
+    assert s0.dtype == s1.dtype == np.float32 and s0.shape == s1.shape == (8, 16, 3, 64, 64)
+    assert np.isfinite(s0).all() and np.isfinite(s1).all() and not np.array_equal(s0, s1)     # weak: each rank its own seeded window
     rank1 = open(err1).read() if os.path.exists(err1) else ""
     # (c10d's "[W...] hostname of the client socket cannot be retrieved" and libdrm's amdgpu.ids line are this pool's noise)
     assert not any(w in rank1 for w in ("Traceback", "Error", "error:", "FAILED", "Aborted")), rank1[-2000:]

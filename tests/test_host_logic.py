@@ -427,12 +427,6 @@ def test_integration_import_block_resolves_every_name_the_script_uses(tmp_path):
     data = ns["dist_util"].load_state_dict(str(ck), map_location="cpu")
     assert data["step"] == 5 and torch.equal(data["state_dict"]["w"], torch.arange(3.0))
     assert ns["dist_util"].dev().type in ("cpu", "cuda") and ns["dist_util"].get_world_size() == 1
-    ref = "/root/reference/scripts"
-    if os.path.isdir(ref):                               # in the build container: the fixture still says what the scripts say
-        for script, mods in used.items():
-            src = open(os.path.join(ref, script)).read()
-            for mod in ("dist_util", "inference_util", "test_util"):
-                assert sorted(set(re.findall(rf"\b{mod}\.([A-Za-z_][A-Za-z0-9_]*)", src))) == mods.get(mod, []), (script, mod)
 
 
 def test_timing_only_kernel_builds_still_compile(tmp_path):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of library builds, alternating, three rounds:   tools/ab.sh <tag> <script + args, quoted> <lib|product> [<lib|product> ...]
 #   e.g. (via gpurun)  bash tools/ab.sh r04c "tools/conv_bench.py --quick" product tools/_timing/abl1.so tools/_timing/abl2.so
-#        bash tools/ab.sh r04d "bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-ref --no-dropin" product tools/_timing/x.so
+#        bash tools/ab.sh r04d "bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-ref --no-dropin" product tools/_timing/x.so
 # Environment switches of the product library are A/B'd the same way: VD_MATH=bf16x6:product as a lib name sets the variable.
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=$1; CMD=$2; shift; shift; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 for rep in 1 2 3; do

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-fp32-ref", "--no-dropin",
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-fp32-ref", "--no-dropin",
                     "--no-full-window", *sys.argv[1:]], capture_output=True, text=True)
 if r.returncode:
     sys.exit(r.stderr[-2000:])

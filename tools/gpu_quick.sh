@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-quick}; shift; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 timeout -k 10 900 python -m pytest ${@:-tests/test_gpu_ops.py} -q -x > $O/tests.log 2>&1; rc=$?; tail -15 $O/tests.log
 [ $rc -ge 124 ] && exit $rc
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-ref --no-dropin > $O/bench.json 2> $O/bench.err; rc2=$?
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-ref --no-dropin > $O/bench.json 2> $O/bench.err; rc2=$?
 [ $rc2 -ne 0 ] && { tail -20 $O/bench.err; exit $rc2; }
 python - <<PY
 import json
