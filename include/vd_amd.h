@@ -386,6 +386,30 @@ int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, cons
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
 
+/* ---- LPIPS frame distance of the adaptive-* frame schedulers (csrc/lpips.hip).
+ * Replaces LpipsEmbedder (improved_diffusion/inference_util.py:15-31: lpips.LPIPS(net='alex', spatial=False), AlexNet features
+ * with per-layer unit normalisation, lin-weight scaling, flattened) as AdaptiveInferenceStrategyBase.embed uses it (:142-150), and
+ * the farthest-point loop of select_obs_indices (:157-185).  fp32 operands and accumulation whatever VD_MATH says; deterministic.
+ * A handle belongs to the device current at vd_lpips_create. */
+typedef struct vd_lpips vd_lpips;
+int vd_lpips_create(vd_lpips** out);
+void vd_lpips_destroy(vd_lpips* h);
+/* Host fp32 tensors, blocking H2D copy; packing happens here, once.  Names: "conv1.weight" .. "conv5.weight" (OIHW, torchvision
+ * alexnet.features.{0,3,6,8,10}), "conv1.bias" .. "conv5.bias", "lin1" .. "lin5" ((C,) lin-layer weights, non-negative), and optional
+ * "shift" / "scale" (3 values each; default: the lpips ScalingLayer constants). */
+int vd_lpips_load_weight(vd_lpips* h, const char* name, const float* host, long long bytes);
+/* Embedding length D of an H x W frame, or -1 when some layer of the feature stack would be empty. */
+long long vd_lpips_dim(int H, int W);
+/* frames [N][3][H][W] in the model's [-1, 1] space (no remapping, as LpipsEmbedder.forward) -> out [N][D].  Workspace owned by
+ * the handle (grown on demand, bounded: frames are processed in chunks). */
+int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float* out, void* stream);
+/* Farthest-point selection on embs [B][n_cand][D] (inference_util.py:157-185): out [B*n + 1] ints receives per item the n picked
+ * CANDIDATE indices (pick 0 and every pick i < n_always is always_host[i]; the others the argmax of the squared distance to the
+ * nearest earlier pick, lowest index on ties; repicks possible), and out[B*n] an error word (bit 0: a distance was not finite).
+ * work: B*n_cand floats.  Enqueued only: the caller reads `out` back once. */
+int vd_fps_select(int B, int n_cand, long long D, const float* embs, int n, const int* always_host, int n_always, float* work,
+                  int* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,8 +9,9 @@ drives it with `iter()` / `next()`.
 The goal-directed, visualisation and frameskip ("google") strategies (:534-776) are
 pinned by tests/golden/schedulers_more.json.  The adaptive strategies (:137-229, :421-531) choose the
 observed frames per batch item by farthest-point selection on frame embeddings; with distance='l2' (raw
-frames) they are pinned by tests/golden/schedulers_adaptive.json, distance='lpips' needs the pretrained
-LPIPS network, which does not ship: register one with `set_lpips_embedder`.
+frames) they are pinned by tests/golden/schedulers_adaptive.json, distance='lpips' needs the LPIPS network, whose pretrained
+weights do not ship: `load_lpips_weights(paths)` builds the HIP one (lpips.py: embedding and selection on the GPU) from the user's
+files, or register any callable with `set_lpips_embedder`.
 """
 import numpy as np
 
@@ -19,9 +20,28 @@ _lpips_embedder = None
 
 def set_lpips_embedder(fn):
     """`fn(frames (B,C,H,W)) -> embedding tensor`: what `LpipsEmbedder(net='alex', spatial=False)` is to the reference
-    (inference_util.py:14-31,146-148).  The pretrained network is not available offline, so none is built in."""
+    (inference_util.py:14-31,146-148).  A plain callable runs the host loop of select_obs_indices; an lpips.LpipsAlex
+    (`load_lpips_weights`) embeds and selects on the GPU.  None unregisters."""
     global _lpips_embedder
     _lpips_embedder = fn
+
+
+def load_lpips_weights(paths, device=None):
+    """Build the GPU LPIPS (AlexNet) embedder from the user's weight files (lpips.LpipsAlex.from_files: one lpips.LPIPS(net='alex')
+    state dict, or torchvision's AlexNet checkpoint plus lpips' weights/v0.1/alex.pth) and register it for distance='lpips'.
+    The adaptive strategies then embed and select on the device (LpipsAlex.embed / select)."""
+    from .lpips import LpipsAlex
+    emb = LpipsAlex.from_files(paths, device)
+    set_lpips_embedder(emb)
+    return emb
+
+
+def _device_lpips():
+    """The registered embedder when it is the HIP LpipsAlex (batched embedding + device selection), else None."""
+    if _lpips_embedder is None:
+        return None
+    from .lpips import LpipsAlex
+    return _lpips_embedder if isinstance(_lpips_embedder, LpipsAlex) else None
 
 
 class InferenceStrategyBase:
@@ -250,6 +270,10 @@ class AdaptiveInferenceStrategyBase(InferenceStrategyBase):
         return torch.stack(embs, dim=1)
 
     def select_obs_indices(self, possible_next_indices, n, always_selected=(0,)):
+        dev = _device_lpips() if self.distance == "lpips" else None
+        if dev is not None:            # the same loop on the device: one batched embedding, one read-back of the picks
+            picks = dev.select(dev.embed(self.videos, possible_next_indices), n, always_selected)
+            return [[possible_next_indices[i] for i in row] for row in picks]
         embs = self.embed(possible_next_indices)
         picked_per_item = []
         for b in range(len(self.videos)):

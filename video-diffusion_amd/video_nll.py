@@ -104,6 +104,8 @@ def run(args, create=None, device=None):
         torch.cuda.set_device(device)
     torch.manual_seed(getattr(args, "seed", 0) + rank)
     adaptive = args.adaptive = "adaptive" in args.inference_mode
+    from .video_sample import load_lpips_for
+    load_lpips_for(args, device)
     model, diffusion = load_model(args, device, rank, world, create=create)
     if args.max_frames is None:                                         # video_nll.py:288-290: BEFORE the run directory is named
         args.max_frames = model.config.get("max_frames") or model.config["T"]
@@ -165,12 +167,13 @@ def run(args, create=None, device=None):
 def main(argv=None):
     import argparse
     from .script_util import str2bool
-    from .video_sample import add_job_arguments
+    from .video_sample import add_job_arguments, add_lpips_arguments, parse_with_lpips
     ap = add_job_arguments(argparse.ArgumentParser())
     ap.add_argument("--indices_path", default=None, help="saved (obs_indices, lat_indices); default <eval_dir>/frame_indices.pt")
     ap.add_argument("--clip_denoised", type=str2bool, default=True)
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"])
-    return run(ap.parse_args(argv))
+    add_lpips_arguments(ap)
+    return run(parse_with_lpips(ap, argv))
 
 
 if __name__ == "__main__":

@@ -51,7 +51,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
 
     'adaptive-*' modes (:74,94-95,104-118,176-183): the strategy sees the current samples before every window and hands
     back one index list per batch item.  `adaptive_distance` is the reference's `distance` ('lpips' is what its script
-    passes and needs `inference_util.set_lpips_embedder`; 'l2' works on the frames themselves).
+    passes and needs `inference_util.load_lpips_weights` or `set_lpips_embedder`; 'l2' works on the frames themselves).
 
     executor='eager' (default): one `diffusion.p_sample` call per step from the host with `th.randn_like` noise, the
     reference's own loop.  executor='graph': each window's step loop runs on the window executor -- one captured hipGraph
@@ -317,10 +317,45 @@ def add_job_arguments(ap):
     return ap
 
 
+def add_lpips_arguments(ap):
+    """--lpips_weights of the three CLIs (next to their --adaptive_distance)."""
+    ap.add_argument("--lpips_weights", default=None, metavar="PATH[,PATH]",
+                    help="with --adaptive_distance lpips: an lpips.LPIPS(net='alex') state dict, or torchvision's AlexNet "
+                         "checkpoint and lpips' weights/v0.1/alex.pth, comma-separated (lpips.py)")
+    return ap
+
+
+def parse_with_lpips(ap, argv):
+    """parse_args + the refusal of --adaptive_distance lpips without weights (unless an embedder is registered already)."""
+    args = ap.parse_args(argv)
+    if (getattr(args, "adaptive_distance", "l2") == "lpips" and not getattr(args, "lpips_weights", None)
+            and inference_util._lpips_embedder is None):
+        ap.error("--adaptive_distance lpips needs --lpips_weights PATH[,PATH] (the LPIPS AlexNet weights do not ship)")
+    return args
+
+
+_lpips_loaded = {}
+
+
+def load_lpips_for(args, device):
+    """Adaptive mode with --adaptive_distance lpips and --lpips_weights: build the GPU embedder on this rank's device and
+    register it -- once per process and (weights, device)."""
+    paths = getattr(args, "lpips_weights", None)
+    if not paths or getattr(args, "adaptive_distance", "l2") != "lpips" or "adaptive" not in args.inference_mode:
+        return None
+    key = (str(paths), str(device))
+    if key not in _lpips_loaded:
+        _lpips_loaded[key] = inference_util.load_lpips_weights(paths, device)
+    else:
+        inference_util.set_lpips_embedder(_lpips_loaded[key])
+    return _lpips_loaded[key]
+
+
 def main(argv=None):
     ap = add_job_arguments(argparse.ArgumentParser())
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
-                    help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs set_lpips_embedder)")
+                    help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
+    add_lpips_arguments(ap)
     ap.add_argument("--executor", default="eager", choices=["graph", "eager"],
                     help="eager: one p_sample call per step (default); graph: one captured hipGraph per window shape (executor.py)")
     ap.add_argument("--suffix_skip", type=str2bool, nargs="?", const=True, default=False,
@@ -328,7 +363,7 @@ def main(argv=None):
                          "on the non-observed frames only")
     ap.add_argument("--prefix_cache", type=str2bool, nargs="?", const=True, default=False,
                     help="with --executor graph and observed_frames x_0: compute the observed frames' encoder prefix once per window")
-    args = ap.parse_args(argv)
+    args = parse_with_lpips(ap, argv)
     return run(args)
 
 
@@ -360,6 +395,7 @@ def run(args, create=None, device=None, infer=None):
         device = torch.device("cuda", local_rank)
         torch.cuda.set_device(device)
     torch.manual_seed(args.seed + rank)
+    load_lpips_for(args, device)
     infer = infer or _default_infer
     # the run identifier is formed from the options AS GIVEN, before --max_frames / --T take their defaults from the model and
     # the dataset (video_sample.py:530-533 precedes :568-570,612-615: an unset one reads 'None' in the directory name)

@@ -16,7 +16,7 @@ Results land where video_eval.py of the reference looks for them (test_util.py n
 uint8); the job around the sampler -- dataset items, sample indices, the skip-before-sampling of finished batches -- is
 `video_sample.run`, shared with the windowed CLI.  `adaptive-*` modes (:78,103-113,187,223-234,306 of the reference) pick
 their observed frames per batch item from the current samples before every window; `adaptive_distance='l2'` works on the
-frames themselves, 'lpips' needs `inference_util.set_lpips_embedder`.
+frames themselves, 'lpips' needs --lpips_weights (or `inference_util.set_lpips_embedder`).
 """
 import argparse
 import json
@@ -28,7 +28,7 @@ import torch
 
 from . import inference_util, test_util
 from .script_util import str2bool
-from .video_sample import add_job_arguments, get_masks, run
+from .video_sample import add_job_arguments, add_lpips_arguments, get_masks, parse_with_lpips, run
 
 logger = logging.getLogger("video_sample_full")
 
@@ -156,7 +156,8 @@ def main(argv=None):
     ap = add_job_arguments(argparse.ArgumentParser())
     ap.add_argument("--vertical_steps", type=int, default=0)
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"])
-    args = ap.parse_args(argv)
+    add_lpips_arguments(ap)
+    args = parse_with_lpips(ap, argv)
     return run(args, infer=_infer)
 
 
