@@ -1434,23 +1434,6 @@ def test_use_gradient_method_with_tiny_gradients_vs_oracle_autograd(shrink):
     assert torch.isfinite(got["sample"]).all()
 
 
-def test_round5_fusions_leave_the_bits_alone():
-    """The round-5 changes that claim the SAME arithmetic per element -- the relative-position nets of all blocks in two launches per width
-    (VD_NO_RPE_ALL undoes it), the GroupNorm affine + SiLU inside conv_wino_z128.hip's patch staging (VD_NO_CONV_ACT) -- against the forms they
-    replace: eps of the tiny model and of the default 116 M model (one 64 x 64 clip), byte for byte.  The switches are read once per process:
-    tools/switch_check.py runs as child processes."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    shas = {}
-    for name, env in (("default", {}), ("per_block_rpe", {"VD_NO_RPE_ALL": "1"}), ("materialised_activations", {"VD_NO_CONV_ACT": "1"})):
-        r = subprocess.run([sys.executable, os.path.join(root, "tools", "switch_check.py")], env={**os.environ, **env}, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-1500:]
-        shas[name] = json.loads(r.stdout.strip().splitlines()[-1])
-    for name in ("per_block_rpe", "materialised_activations"):
-        assert shas[name]["tiny"] == shas["default"]["tiny"] and shas[name]["full64"] == shas["default"]["full64"], (name, shas)
-
-
 # ------------------------------------------------------------------------------------------------------------------
 # Round 6: the sampling job end to end (SURVEY 8 f2), the adaptive vertical / horizontal sampler
 def test_sampling_cli_from_a_checkpoint_file_writes_the_oracles_videos_and_resumes_without_a_step(tmp_path, monkeypatch):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""SHA-1 of the network output under the process' A/B switches (VD_NO_RPE_ALL, VD_NO_CONV_ACT, VD_HEAD_GENERIC, ...: read once per process, so a
-test compares child processes).  Prints one JSON line: {"tiny": sha, "full64": sha, "version": ...}.
+"""SHA-1 of the network output of whichever library this process loads (VD_LIB selects another build, VD_MATH the arithmetic mode), so
+that two builds can be compared by running this once against each.  Prints one JSON line: {"tiny": sha, "full64": sha, "version": ...}.
   tiny    tests/golden/unet_tiny.npz case 0 (32 base channels: generic kernels, RPE nets)
   full64  the default 116 M model, one 16-frame 64 x 64 clip, seeded (conv_wino_z128.hip's activating form serves its 64 x 64 and 32 x 32 levels)"""
 import hashlib

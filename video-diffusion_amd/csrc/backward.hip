@@ -641,7 +641,7 @@ int launch_grad_rescale(float* deps, size_t n, float* gs, hipStream_t st) {
 // g = dxd + dx_net / s;  mean' = mean - 10 * alpha_t * g / 2  (alpha_t = 1 - beta_t);  sample = mean' + nz*sigma*z2
 __global__ __launch_bounds__(256) void guided_final_kernel(GuidedArgs a, const float* __restrict__ dx_net, const float* __restrict__ noise2,
                                                            float* __restrict__ grad, float* __restrict__ mean_out, float* __restrict__ sample) {
-    const float inv_s = a.gscale ? a.gscale[1] : 1.f;
+    const float inv_s = a.gscale[1];
     const size_t total = (size_t)a.B * a.per;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int b = (int)(i / a.per);

@@ -74,9 +74,6 @@ extern "C" int vd_debug_r64_stamps(unsigned long long* host_out) {
 #else
 #define R64_STAMP(i)
 #endif
-#ifndef VD_R64_B2REG
-#define VD_R64_B2REG 1     // f16x3: the third weight piece 2^-12 b0 formed in registers (conv_wino_z128.hip) instead of loaded (A/B: 0)
-#endif
 // Variants that were built, measured and taken out again (the code lives in the history, commit aa1331c): the a1 piece by v_fma_mixlo/hi_f16 (10.31
 // instead of 10.98 instructions per MFMA, same bits: 0 .. 5 % slower per layer, r05b); the patch staged through registers instead of LDS-DMA (worth 8 % in
 // conv_wino_z128.hip, 2 .. 9 % SLOWER here, r05t: this loop has no issue slot left for twelve more requests per chunk pair); a uniform branch around the
@@ -305,7 +302,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     u32x4 bfr[4][2][3];
     // (n, piece) offsets 0 .. 3072 ride in the instruction's 12-bit immediate, the last two behind a second scalar base: two
     // scalar adds per position instead of six (every instruction of a one-wave-per-SIMD stream is an issue slot)
-    constexpr bool B2R = F16 && VD_R64_B2REG;                        // piece 2 = 2^-12 x piece 0: four v_pk_mul_f16 instead of a 1 KiB load
+    constexpr bool B2R = F16;                                        // f16x3: piece 2 = 2^-12 x piece 0, formed in registers: four v_pk_mul_f16 instead of a 1 KiB load
     const unsigned two_m12 = 0x0c000c00u;
     auto b_third = [&](int j, int n) {
         asm("v_pk_mul_f16 %0, %4, %8\n\tv_pk_mul_f16 %1, %5, %8\n\tv_pk_mul_f16 %2, %6, %8\n\tv_pk_mul_f16 %3, %7, %8"
@@ -714,10 +711,8 @@ int launch_conv_wino_r64(const IgemmArgs& a, hipStream_t s) {
     g.ncb = a.Cout / 64;
     g.nitems = g.nbx * g.ncb;
     g.xcd_order = g.nbx % 8 == 0;
-    // (the grouped cout walk of the sub-pixel form changes nothing here: 2 .. 8 cout blocks per patch, headline 27.55 ms with groups of 0 / 2 / 4;
-    // re-measured in round 6 on the f16x3 kernel through VD_R64_CGROUP, LAB_NOTES R6)
-    static const int env_cgroup = getenv("VD_R64_CGROUP") ? atoi(getenv("VD_R64_CGROUP")) : 0;
-    if (env_cgroup > 0 && g.xcd_order && g.ncb % env_cgroup == 0) g.cgroup = env_cgroup;
+    // (no grouped cout walk here, unlike the sub-pixel form: 2 .. 8 cout blocks per patch, headline 27.55 ms with groups of 0 / 2 / 4;
+    // re-measured in round 6 on the f16x3 kernel, LAB_NOTES R6)
     // split-K only with scratch from the caller (the engine's arena; the single-operator entry points run one slice)
     g.ksplit = a.ksplit_ws && a.ksplit_ws_floats >= conv_wino_r64_ksplit_floats(a.nfr, Hl, a.Cin, a.Cout, a.nfr_sel)
                    ? conv_wino_r64_ksplit(a.nfr_sel ? a.nfr_sel : a.nfr, Hl, a.Cin, a.Cout) : 1;

@@ -519,23 +519,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
 // 16^2, 128 frames: 384 items = 1.5 rounds of 256 CUs against 3.0; 200 | 161 us): decided by the fill of the last round.
 static double z128_fill(int items, int cus) { return (double)items / ((double)cus * ((items + cus - 1) / cus)); }
 
-static bool z128_shape(int nfr, int H, int Cin, int Cout, int max_cin);
-bool conv_wino_z128_shape(int nfr, int H, int Cin, int Cout) {
-#ifndef VD_Z128_MAX_CIN
-#define VD_Z128_MAX_CIN 320
-#endif
-    return z128_shape(nfr, H, Cin, Cout, VD_Z128_MAX_CIN);
-}
+// Longest channel loop the kernel takes (Cin); a later A/B at 384 edits this constant.
+constexpr int kZ128MaxCin = 320;
 
-static bool z128_shape(int nfr, int H, int Cin, int Cout, int max_cin) {
-#ifdef VD_Z128_OFF                                   // kernel-experiment builds (tools/build_variant.sh): every shape on conv_wino_r64.hip
-    return false;
-#endif
+bool conv_wino_z128_shape(int nfr, int H, int Cin, int Cout) {
     if (!f16_math() || H < 16 || (H & (H - 1)) || Cout % 128 || Cin % 32 || conv_wino_r64_ksplit(nfr, H, Cin, Cout) != 1) return false;
     // 1.5 x the MFMAs for half the per-item overhead and half the vector work: pays while the channel loop is short.  Same box,
     // us per launch, this kernel | conv_wino_r64.hip (r04q, after the latter stopped loading the third weight piece):
     // 128 -> 128 @ 64^2 411 - 428 | 432 - 451, 256 -> 256 @ 32^2 344 - 356 | 361 - 370, 640 -> 256 @ 32^2 805 | 758 - 774
-    if (Cin > max_cin) return false;
+    if (Cin > kZ128MaxCin) return false;
     // CU count of the CURRENT device (cached per device id: a process that drives several devices must not inherit the first one's)
     static int cu_of[64] = {};
     int dev = 0;
@@ -558,15 +550,9 @@ bool conv_wino_z128_supported(const IgemmArgs& a) {
 // takes, with at most two cout blocks per patch (each of them activates it).  The shape half is what the engine asks before it decides
 // not to materialise the activation image (engine.hip: res_block).
 bool conv_wino_z128_act_shape(int nfr, int H, int Cin, int Cout) {
-#ifdef VD_Z128_NO_ACT
-    return false;
-#endif
-    static const bool off = getenv("VD_NO_CONV_ACT") != nullptr;       // A/B switch: the activation pass + the plain kernel
-    static const int max_cout = getenv("VD_CONV_ACT_MAX_COUT") ? atoi(getenv("VD_CONV_ACT_MAX_COUT")) : 256;
-    // (longer channel loops than the plain kernel takes -- the decoder's 384 .. 640 -> 128 | 256 convs, whose image the skip convolution writes --
+    // (no longer channel loops than the plain kernel takes: the decoder's 384 .. 640 -> 128 | 256 convs, whose image the skip convolution writes --
     // measured in the step, r05q: 320 | 384 | 640 -> 20.155 | 20.148 | 20.22 ms: what the image costs is what conv_wino_r64.hip's lead there is worth)
-    static const int max_cin = getenv("VD_CONV_ACT_MAX_CIN") ? atoi(getenv("VD_CONV_ACT_MAX_CIN")) : VD_Z128_MAX_CIN;
-    return !off && Cout <= max_cout && z128_shape(nfr, H, Cin, Cout, max_cin);
+    return Cout <= 256 && conv_wino_z128_shape(nfr, H, Cin, Cout);
 }
 
 bool conv_wino_z128_act_supported(const IgemmArgs& a) {

@@ -155,10 +155,7 @@ struct ProfScope {
 // call as built (weight image, piece count, strides, size limits).  If the two ever disagree the conv would get a raw tensor plus
 // (A, B) that no other kernel applies: say so here, by name, instead of failing later with the generic "no kernel covers" error.
 static bool act_conv_will_dispatch(const IgemmArgs& g) {
-    IgemmArgs one = g;
-    one.nfr = std::max(1, std::min(g.nfr, igemm_frames_per_launch(g)));
-    one.M = one.nfr * g.Ho * g.Wo;
-    return conv_wino_z128_act_supported(one);
+    return g.affA && igemm_kernel(igemm_first_launch(g)) == IK_Z128;     // (the plain z128 kernel takes no affine)
 }
 
 static int igemm_p(const IgemmArgs& g, hipStream_t st, int cin_alg = 0) {
@@ -169,20 +166,23 @@ static int igemm_p(const IgemmArgs& g, hipStream_t st, int cin_alg = 0) {
     // GroupNorm + SiLU image from the A rows it stages (IgemmArgs::side: one more tensor of the input's size written by this launch, the
     // pass affine_act would otherwise be), that image: counted since r05 (round 4's figure omitted it and read as 2x traffic waste)
     const double bytes = nz * 4.0 * (in_pix * cin + (double)g.M * g.Cout * (g.res ? 2 : 1) + taps * cin * g.Cout + (g.side ? in_pix * cin : 0.0));
-    IgemmArgs one = g;                         // a big window goes out as several launches over frame ranges (igemm.hip)
-    one.nfr = std::max(1, std::min(g.nfr, igemm_frames_per_launch(g)));
-    one.M = one.nfr * g.Ho * g.Wo;
-    const bool zact = conv_wino_z128_act_supported(one);              // conv_wino_z128.hip with the activation in its patch staging
-    const bool wino = zact || conv_wino_supported(one) || conv_wino_r64_supported(one);
-    const bool split_gemm = gemm_split_supported(one) || conv_split_supported(one);
-    const int cls = wino ? (int)(g.ups_phase ? PC_CONV_WINO_R64_UPS : zact || conv_wino_z128_supported(one) ? PC_CONV_WINO_Z128
-                                                               : conv_wino_r64_supported(one) ? PC_CONV_WINO_R64 : PC_CONV_WINO)
-                    : split_gemm && gemm_split_tile_class(igemm_sel_M(one), g.Cout) == 4 ? (int)PC_IGEMM_128x192
-                    : igemm_tile_class(igemm_sel_M(one), g.Cout) + (g.ksz == 3 && !split_gemm ? (int)PC_CONV_128x128 : 0);   // 3x3 on the generic kernel
+    const IgemmArgs one = igemm_first_launch(g);      // a big window goes out as several launches over frame ranges (igemm.hip)
+    const IgemmKernel k = igemm_kernel(one);
+    const bool wino = k == IK_R64_UPS || k == IK_Z128 || k == IK_R64 || k == IK_WINO;
+    const int tile = igemm_tile_class(igemm_sel_M(one), g.Cout);
+    int cls;
+    switch (k) {
+        case IK_R64_UPS: cls = PC_CONV_WINO_R64_UPS; break;
+        case IK_Z128: cls = PC_CONV_WINO_Z128; break;
+        case IK_R64: cls = PC_CONV_WINO_R64; break;
+        case IK_WINO: cls = PC_CONV_WINO; break;
+        case IK_SPLIT: cls = gemm_split_tile_class(igemm_sel_M(one), g.Cout) == 4 ? (int)PC_IGEMM_128x192 : tile; break;
+        default: cls = tile + (g.ksz == 3 ? (int)PC_CONV_128x128 : 0);        // gemm_frag (1x1) | the generic kernel
+    }
     char tag[56];
     snprintf(tag, sizeof(tag), "M=%d N=%d K=%d k%d s%d%s%s%s", g.M, g.Cout, g.Cin, g.ksz, g.stride, g.ups ? " ups" : "",
              g.affA ? " pro" : (g.act ? " act" : ""), g.res ? " res" : "");
-    VD_REQUIRE(g.stats == nullptr || wino || (split_gemm && g.stats_hw > 0),
+    VD_REQUIRE(g.stats == nullptr || wino || (k == IK_SPLIT && g.stats_hw > 0),
                "GroupNorm partial sums requested from a kernel that has no such epilogue");
     ProfScope ps(cls, nz * 2.0 * g.M * g.Cout * cin * taps, bytes, st, tag);
     return launch_igemm(g, st);
@@ -266,6 +266,7 @@ struct vd_engine {
     std::vector<float*> rpe_R;        // [attention block][3]: R of the running forward (k, q, v order of attn_block), or empty
     int rpe_all(const float* te, const int64_t* fidx, int B, int T, hipStream_t st, Arena& ar);
     int rpe_tables();
+    void rpe_group_blocks();
     // small device tables
     float* d_freq_time = nullptr; int n_freq_time = 0;
     float* d_freq_frame = nullptr; int n_freq_frame = 0;
@@ -382,7 +383,7 @@ struct vd_engine {
     int ensure_ws(int B, int T);
     int res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, const float* emb_unused,
                   hipStream_t st, Arena& ar, Tens* out);
-    int attn_block(const AttnP& a, Tens x, int B, int T, const float* te_all, const int64_t* fidx, const float* amask,
+    int attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* fidx, const float* amask,
                    hipStream_t st, Arena& ar, Tens* out);
     int gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb, const float* film,
                 int film_ld, hipStream_t st, Arena& ar, float** A, float** B, float** mr = nullptr);
@@ -696,9 +697,9 @@ int vd_engine::gn_act(const Tens& x0, const Tens* x1, int N, int gw, int gb, con
     // gn_final_affine, then the pass on many short blocks -- 5.95 TB/s against the 5.2 of the long blocks the in-kernel fold needs
     // (tools/probes/stream_probe.hip); the 7 us of the extra launch are repaid from ~64 MB on.  Same formulas and fp64 sums; the ORDER of the
     // sums differs (gn_final_affine deals a group's pairs to eight lanes, the folding pass walks them in sequence), so (A, B) agree to fp64
-    // rounding -- after the cast to fp32 in practice to the bit (tools/switch_check.py), by construction to 1 ulp.  The 64 MB switch is by the
+    // rounding -- after the cast to fp32 in practice to the bit, by construction to 1 ulp.  The 64 MB switch is by the
     // size of the whole layer call (g_sel_nfr): a full window and the compact suffix batch of the same layer take the same form.
-    static const size_t big = getenv("VD_AA_BIG_MB") ? (size_t)atol(getenv("VD_AA_BIG_MB")) << 20 : (size_t)64 << 20;
+    constexpr size_t big = (size_t)64 << 20;
     const bool two = (size_t)(g_sel_nfr > N ? g_sel_nfr : N) * HW * C * 4 >= big;      // by the size of the whole layer call: the compact suffix batch takes the full window's form
     float* Aab = two ? ar.get<float>((size_t)N * C) : nullptr;
     float* Bab = two ? ar.get<float>((size_t)N * C) : nullptr;
@@ -856,7 +857,7 @@ int vd_engine::res_block(const ResP& r, Tens x0, const Tens* x1, int N, const fl
     return 0;
 }
 
-int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const float* te_all, const int64_t* fidx,
+int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* fidx,
                           const float* amask, hipStream_t st, Arena& ar, Tens* out) {
     const int C = a.C, H = x.H, HW = H * H, N = B * T;
     const size_t tok = (size_t)N * HW;
@@ -865,15 +866,13 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const float* te_
     // ---- temporal attention over the T frames of each (batch, pixel)      (unet.py:246-255)
     float* xn = ar.get<float>(tok * C);
     float* qkv = ar.get<float>(tok * 3 * C);
-    // relative-position terms in memory order q, k, v: the three nets of a block have identical shapes and sit at a
-    // constant stride in the packed weights, so each of their two layers is ONE launch (blockIdx.y / .z = net)
+    // relative-position terms in memory order q, k, v: the RPE nets' come from rpe_all (start of the forward), the bucket tables' are built here
     const RpeP* rp[3] = {&a.rq, &a.rk, &a.rv};
     const size_t rrows = (size_t)B * T * T;
     const int blk = (int)(&a - attn.data());
-    const bool pre = !rpe_R.empty();                                        // rpe_all has produced this forward's R tensors already
-    float* Ehid = cfg.use_rpe_net && !pre ? ar.get<float>(3 * rrows * C) : nullptr;
-    float* Rall = pre ? rpe_R[3 * blk] : ar.get<float>(3 * rrows * C);     // (memory order q, k, v)
-    float* R[3] = {Rall + rrows * C, Rall, Rall + 2 * rrows * C};          // k, q, v as the attention kernel takes them
+    VD_REQUIRE(!cfg.use_rpe_net || !rpe_R.empty(), "attn_block: rpe_all has not run");
+    float* Rall = cfg.use_rpe_net ? rpe_R[3 * blk] : ar.get<float>(3 * rrows * C);     // (memory order q, k, v)
+    float* R[3] = {Rall + rrows * C, Rall, Rall + 2 * rrows * C};                      // k, q, v as the attention kernel takes them
     float* o = ar.get<float>(tok * C);
     float* xt = ar.get<float>(tok * C);
     Tens xt_t{xt, C, H};                               // the spatial attention's GroupNorm reads it: statistics from the proj_out GEMM
@@ -883,25 +882,10 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const float* te_
           rc = launch_gn_temporal(x.p, W(a.tp.normw), W(a.tp.normb), B, T, HW, C, xn, st); }
         if (rc) return rc;
         if ((rc = linear(xn, (int)tok, C, 0, 0, 3 * C, W(a.tp.qkvw), W(a.tp.qkvb), 0, nullptr, qkv, st))) return rc;
-        if (pre) {
-        } else if (cfg.use_rpe_net) {
-            const int zs_dw = (int)(W(rp[1]->dw) - W(rp[0]->dw)), zs_db = (int)(W(rp[1]->db) - W(rp[0]->db));
-            const int zs_ow = (int)(W(rp[1]->ow) - W(rp[0]->ow)), zs_ob = (int)(W(rp[1]->ob) - W(rp[0]->ob));
-            VD_REQUIRE(W(rp[2]->dw) - W(rp[1]->dw) == zs_dw && W(rp[2]->db) - W(rp[1]->db) == zs_db &&
-                       W(rp[2]->ow) - W(rp[1]->ow) == zs_ow && W(rp[2]->ob) - W(rp[1]->ob) == zs_ob &&
-                       rp[1]->te_off - rp[0]->te_off == C && rp[2]->te_off - rp[1]->te_off == C, "RPE nets: constant stride");
-            if ((rc = launch_rpe_hidden(te_all + rp[0]->te_off, te_total, W(rp[0]->dw), W(rp[0]->db), fidx, B, T, C, Ehid, 3, C,
-                                        zs_dw, zs_db, rrows * C, st))) return rc;
-            IgemmArgs g{};
-            g.src0 = Ehid; g.C0 = C; g.Cin = C; g.nfr = (int)rrows; g.Hs = g.Ws = g.Ho = g.Wo = 1; g.stride = 1; g.ksz = 1;
-            g.wfrag = W(rp[0]->ow); g.wsplit = split_math(); g.bias = W(rp[0]->ob); g.out = Rall; g.ldo = C; g.Cout = C; g.M = (int)rrows;
-            g.zcount = 3; g.zs_a = g.zs_out = (int)(rrows * C); g.zs_w = zs_ow; g.zs_bias = zs_ob;
-            if ((rc = igemm_p(g, st))) return rc;
-        } else {
+        if (!cfg.use_rpe_net)
             for (int i = 0; i < 3; ++i)
                 if ((rc = launch_rpe_table(W(rp[i]->table), fidx, B, T, C, cfg.rp_alpha, cfg.rp_beta, cfg.rp_gamma,
                                            Rall + i * rrows * C, st))) return rc;
-        }
         AttnTemporalArgs ta{qkv, R[0], R[1], R[2], amask, o, B, T, HW, C, cfg.num_heads,
                             cfg.allow_interactions_between_padding, scale};
         { const double Fd = C / cfg.num_heads;
@@ -948,21 +932,23 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const float* te_
 // timestep embedding and the frame indices only -- nothing a block computes.  Per block they were two small dependent launches (the three
 // nets of a block batched): 22 of the ~210 launches of a step, each paying the ~5 us of a dependent dispatch on top of 5 - 15 us of work
 // that leaves most CUs idle.  Here: per channel width ONE hidden-layer launch and ONE output-layer GEMM over all nets of that width (the
-// 3 x 5 nets of 384 channels, the 3 x 6 of 512), at the start of the forward.  Same kernels, same arithmetic per net: bit-identical R.
-// the attention blocks by channel width, and per width the device tables of offsets the two launches read (never inside a stream capture:
-// ensure_ws calls this)
-static bool rpe_all_on() { static const bool on = getenv("VD_NO_RPE_ALL") == nullptr; return on; }     // (A/B switch: the per-block launches of rounds 1-4)
-
-int vd_engine::rpe_tables() {
-    if (!cfg.use_rpe_net || !split_math() || attn.empty() || !te_total || !rpe_all_on()) return 0;
-    if (rpe_groups.empty()) {
-        for (size_t b = 0; b < attn.size(); ++b) {
-            size_t gi = 0;
-            while (gi < rpe_groups.size() && rpe_groups[gi].C != attn[b].C) ++gi;
-            if (gi == rpe_groups.size()) rpe_groups.push_back(RpeGroup{attn[b].C, {}});
-            rpe_groups[gi].blocks.push_back((int)b);
-        }
+// 3 x 5 nets of 384 channels, the 3 x 6 of 512), at the start of the forward, in every arithmetic mode (the GEMM is gemm_split.hip's or,
+// under VD_MATH=fp32, gemm_frag.hip's; both read the weights of problem z through IgemmArgs::ztab).  Same arithmetic per net: bit-identical R.
+// The attention blocks by channel width (the dry run sizes the arena before any table exists: it needs the widths only)
+void vd_engine::rpe_group_blocks() {
+    if (!rpe_groups.empty()) return;
+    for (size_t b = 0; b < attn.size(); ++b) {
+        size_t gi = 0;
+        while (gi < rpe_groups.size() && rpe_groups[gi].C != attn[b].C) ++gi;
+        if (gi == rpe_groups.size()) rpe_groups.push_back(RpeGroup{attn[b].C, {}});
+        rpe_groups[gi].blocks.push_back((int)b);
     }
+}
+
+// per width the device tables of offsets the two launches read (never inside a stream capture: ensure_ws calls this)
+int vd_engine::rpe_tables() {
+    if (!cfg.use_rpe_net || attn.empty() || !te_total) return 0;
+    rpe_group_blocks();
     for (auto& g : rpe_groups) {
         if (g.d_hid) continue;
         const int nn = 3 * (int)g.blocks.size();
@@ -986,16 +972,8 @@ int vd_engine::rpe_tables() {
 
 int vd_engine::rpe_all(const float* te, const int64_t* fidx, int B, int T, hipStream_t st, Arena& ar) {
     rpe_R.clear();
-    if (!cfg.use_rpe_net || !split_math() || attn.empty() || !te_total || !rpe_all_on()) return 0;
-    if (ar.dry && rpe_groups.empty()) {                                // (the dry run sizes the arena before any table exists: widths only)
-        for (size_t b = 0; b < attn.size(); ++b) {
-            size_t gi = 0;
-            while (gi < rpe_groups.size() && rpe_groups[gi].C != attn[b].C) ++gi;
-            if (gi == rpe_groups.size()) rpe_groups.push_back(RpeGroup{attn[b].C, {}});
-            rpe_groups[gi].blocks.push_back((int)b);
-        }
-    }
-    VD_REQUIRE(!rpe_groups.empty(), "rpe_all: ensure_ws has not run");
+    if (!cfg.use_rpe_net || attn.empty() || !te_total) return 0;
+    rpe_group_blocks();
     const size_t rrows = (size_t)B * T * T;
     rpe_R.assign(3 * attn.size(), nullptr);
     int rc = 0;
@@ -1084,7 +1062,7 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
             if (L.type == 1) {
                 if ((rc = res_block(res[L.idx], cur, second, N, film, nullptr, st, ar, &nxt))) return rc;
             } else if (L.type == 2) {
-                if ((rc = attn_block(attn[L.idx], cur, B, T, te, in.fidx, amask, st, ar, &nxt))) return rc;
+                if ((rc = attn_block(attn[L.idx], cur, B, T, in.fidx, amask, st, ar, &nxt))) return rc;
             } else if (L.type == 0) {                                 // stem: im2col (assemble_kernel) x [64][mc] GEMM
                 const ConvP& c = convs[L.idx];
                 float* o = ar.get<float>((size_t)N * S * S * c.c);
@@ -1214,11 +1192,11 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
     if (!ar.dry) {
         VD_REQUIRE(h.H == S && h.C == final_ch, "output head shape");
         { // out = conv3x3(silu(gn(h))) with 3 | 6 outputs (unet.py:744-749,838): T[pixel][cout * 9 + tap] = silu(A h + B) . w[cout][:][tap] as ONE
-          // 1x1 GEMM over the 27 | 54 (cout, tap) columns (the generic kernel: GroupNorm affine + SiLU in its operand load), then
+          // 1x1 GEMM over the 27 | 54 (cout, tap) columns (head_gemm_kernel, or the generic kernel for shapes it does not take: GroupNorm
+          // affine + SiLU in the operand load), then
           // eps[cout][y][x] = bias + sum over the 9 taps of T at the neighbour the tap points to (out_gather_kernel)
           ProfScope ps(PC_OUT_CONV, 2.0 * Nrun * S * S * h.C * 27.0, 4.0 * Nrun * S * S * (h.C + 3.0), st);
-          static const bool old_head = getenv("VD_HEAD_GENERIC") != nullptr;      // A/B switch: the generic fp32 kernel (rounds 4)
-          if (!old_head && head_gemm_supported(S * S, h.C, out_t_cols(oc))) {
+          if (head_gemm_supported(S * S, h.C, out_t_cols(oc))) {
               rc = launch_head_gemm(h.p, A, Bf, W(p_outw) + (size_t)9 * oc * h.C, Nrun, S * S, h.C, out_t_cols(oc), head_t, st);
           } else {
               IgemmArgs g = conv_args(h, nullptr, Nrun, 1, 1, 0);
@@ -2242,9 +2220,8 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs,
                       deps, dxd, mean0, xstart ? xstart : xs0};
         ga.err = e->d_err;
         rc = launch_guided_grad(ga, st);
-        static const bool no_gs = getenv("VD_NO_GRAD_SCALE") != nullptr;      // (A/B switch: the un-scaled backward pass of rounds 3-4)
         float* gs = lat_net + 256;                                            // 4 floats of the tail's spare kilobyte
-        if (!rc && !no_gs) { rc = launch_grad_rescale(deps, tot, gs, st); ga.gscale = gs; }
+        if (!rc) { rc = launch_grad_rescale(deps, tot, gs, st); ga.gscale = gs; }
         if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
         if (!rc) rc = launch_guided_final(ga, dxn, noise2, grad, mean, sample, st);
     }

@@ -43,10 +43,11 @@ __global__ __launch_bounds__(256, 3) void gemm_frag_kernel(IgemmArgs a) {
     const int nchunk = a.Cin >> 5, ncoblk = a.Cout >> 5;
     const int C1 = a.Cin - a.C0;
     GEMM_STAMP(0);
-    if (a.zcount > 1) {                          // batched problems of one shape
+    if (a.zcount > 1) {                          // batched problems of one shape, weights / bias from a table of offsets (IgemmArgs::ztab)
         const int z = blockIdx.z;
-        a.src0 += (size_t)z * a.zs_a; a.wfrag += (size_t)z * a.zs_w; a.out += (size_t)z * a.zs_out;
-        if (a.bias) a.bias += (size_t)z * a.zs_bias;
+        a.src0 += (size_t)z * a.zs_a; a.out += (size_t)z * a.zs_out;
+        a.wfrag = a.zbase + a.ztab[2 * z];
+        a.bias = a.zbase + a.ztab[2 * z + 1];
     }
 
     // A rows: byte offsets into either source (rows past M: duplicates of the last row, dropped at the store)

@@ -35,24 +35,6 @@ __device__ __forceinline__ f32x16 mfma_piece(u32x4 a, u32x4 b, f32x16 c) {
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-#ifndef VD_GS_PF3
-#define VD_GS_PF3 1        // 0: the A operand one chunk ahead for every tile (A/B)
-#endif
-#ifndef VD_GS_PF3_ALL
-#define VD_GS_PF3_ALL 0    // 1: three chunks of the A operand in flight for the 128-row tiles too (A/B)
-#endif
-#ifndef VD_GS_RING6
-#define VD_GS_RING6 1      // 0: three weight slots for the 64x64 tile too (A/B)
-#endif
-#ifndef VD_GS_B2REG
-#define VD_GS_B2REG 1      // f16x3: the third weight piece 2^-12 b0 formed in registers (four v_pk_mul_f16 per fragment) instead of loaded (A/B: 0)
-#endif
-#ifndef VD_GS_RING3_192
-#define VD_GS_RING3_192 0  // 1: 128x192 tile with two k-steps of weights ahead (the registers the un-fetched third piece freed).  Measured r04v,
-#endif                     // same box: qkv 8192 x 512 x 1536 41.4 -> 43.3 us, 32768 x 384 x 1152 95.5 -> 97.6, class 4.03 -> 4.08 ms: not a latency problem
-#ifndef VD_GS_XCD
-#define VD_GS_XCD 1        // XCD-aware block -> tile mapping (A/B: 0)
-#endif
 #ifndef VD_GS_SKIP
 #define VD_GS_SKIP 0       // kernel-experiment builds: bit 0 no weight loads, 1 no A staging, 2 no split + LDS stores, 3 stores of unsplit bits (timing only)
 #endif
@@ -95,16 +77,19 @@ template <int BM, int BN, bool ACT, bool CONV, bool F16 = true, bool SIDE = fals
 __global__ __launch_bounds__(256, 2) void gemm_split_kernel(IgemmArgs a) {
     constexpr int MI = BM / 64, NI = BN / 64, AR = BM / 32;
     // weight ring slots (k-steps ahead = RING - 1): 2 for the 128x192 tile (256 registers per wave; 3 under f16x3, whose ring holds two
-    // pieces per fragment), 3 for the others -- and 6
+    // pieces per fragment, was slower -- r04v, same box: qkv 8192 x 512 x 1536 41.4 -> 43.3 us, 32768 x 384 x 1152 95.5 -> 97.6, class
+    // 4.03 -> 4.08 ms: not a latency problem), 3 for the others -- and 6
     // for the 64x64 tile: its k-step is 6 MFMAs (0.1 us), its launches are the small-M ones (one block per CU, nothing else
     // to hide behind), and two steps ahead left every weight fragment a full L2 round trip short
-    constexpr bool B2R = F16 && VD_GS_B2REG;                           // the third weight piece lives in ONE register set (b2), not in the ring
-    constexpr int RING = NI >= 3 ? (B2R && VD_GS_RING3_192 ? 3 : 2) : (BM == 64 && BN == 64 && VD_GS_RING6) ? 6 : 3;
+    // f16x3: the third weight piece 2^-12 b0 is formed in registers (four v_pk_mul_f16 per fragment) instead of loaded, and lives in ONE
+    // register set (b2), not in the ring
+    constexpr bool B2R = F16;
+    constexpr int RING = NI >= 3 ? 2 : (BM == 64 && BN == 64) ? 6 : 3;
     constexpr int BP = B2R ? 2 : 3;                                     // fetched pieces per fragment
     // A-operand prefetch distance in chunks.  A chunk of a 64-row tile is 12 .. 24 MFMAs (0.2 .. 0.4 us): one chunk ahead, the
     // split + store of the next chunk waits a full memory round trip every chunk, and a small-M launch (a B = 1 shard: 60 of
     // them per step) costs ~1 us per chunk whatever its size.  The small tiles have the registers for three chunks in flight.
-    constexpr int PF = ((BM == 64 && VD_GS_PF3) || VD_GS_PF3_ALL) ? 3 : 1;      // (three chunks in flight for the HBM-bound 128x128 SIDE launches too: measured, no gain -- r04i)
+    constexpr int PF = BM == 64 ? 3 : 1;      // (three chunks in flight for the HBM-bound 128x128 SIDE launches too: measured, no gain -- r04i)
     constexpr int NPL = F16 ? 2 : 3;                                      // planes of the A tile
     constexpr int PLANE = BM * SROW, ABUF = NPL * PLANE;                  // bytes
     extern __shared__ __attribute__((aligned(16))) char smem_c[];         // [2][3 planes][BM][SROW]
@@ -119,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(IgemmArgs a) {
     // Same box (r04w): 32768 x 384 x 1152 95.5 -> 90 us, 131072 x 640 x 256 205 -> 180, 131072 x 512 x 256 160 -> 148; launches whose
     // row tiles all fit the chip at once (8192 rows: 64 tiles) lose 5 % and keep the plain mapping.
     int bxi = blockIdx.x, byi = blockIdx.y;
-    if (VD_GS_XCD && gridDim.y > 1 && (gridDim.x & 7) == 0 && gridDim.x >= 128) {
+    if (gridDim.y > 1 && (gridDim.x & 7) == 0 && gridDim.x >= 128) {
         const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y, xcd = lin & 7, loc = lin >> 3;
         byi = loc % gridDim.y;
         bxi = (loc / gridDim.y) * 8 + xcd;
@@ -133,16 +118,11 @@ __global__ __launch_bounds__(256, 2) void gemm_split_kernel(IgemmArgs a) {
     const int cpt = a.Cin >> 5;                                            // chunks per tap
     const int nchunk = CONV ? 9 * cpt : cpt, ncoblk = a.Cout >> 5;
     const int C1 = a.Cin - a.C0;
-    if (a.zcount > 1) {                          // batched problems of one shape
+    if (a.zcount > 1) {                          // batched problems of one shape, weights / bias from a table of offsets (IgemmArgs::ztab)
         const int z = blockIdx.z;
         a.src0 += (size_t)z * a.zs_a; a.out += (size_t)z * a.zs_out;
-        if (a.ztab) {                            // weights / bias of problem z from a table of offsets (IgemmArgs::ztab)
-            a.wfrag = a.zbase + a.ztab[2 * z];
-            a.bias = a.zbase + a.ztab[2 * z + 1];
-        } else {
-            a.wfrag += (size_t)z * a.zs_w;
-            if (a.bias) a.bias += (size_t)z * a.zs_bias;
-        }
+        a.wfrag = a.zbase + a.ztab[2 * z];
+        a.bias = a.zbase + a.ztab[2 * z + 1];
     }
 
     const auto asrc0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0,

@@ -195,20 +195,35 @@ static int launch_t(const IgemmArgs& a, hipStream_t s) {
     return 0;
 }
 
+// The ONE place that decides which kernel serves an IgemmArgs (the engine's profiler classes and its planning read the same answer)
+IgemmKernel igemm_kernel(const IgemmArgs& a) {
+    if (a.ups_phase) return IK_R64_UPS;                                 // sub-pixel weight image: only conv_wino_r64.hip reads it
+    if (gemm_split_supported(a) || conv_split_supported(a)) return IK_SPLIT;
+    if (conv_wino_z128_act_supported(a) || conv_wino_z128_supported(a)) return IK_Z128;
+    if (conv_wino_r64_supported(a)) return IK_R64;
+    if (gemm_frag_supported(a)) return IK_FRAG;
+    if (conv_wino_supported(a)) return IK_WINO;
+    return IK_GENERIC;
+}
+
 // One launch: every operand of `a` is small enough for the 32-bit byte offsets the kernels address with.
 static int launch_igemm_one(const IgemmArgs& a, hipStream_t s) {
-    if (a.ups_phase) {                                                  // sub-pixel weight image: only conv_wino_r64.hip reads it
-        VD_REQUIRE(conv_wino_r64_supported(a), "sub-pixel Upsample conv: shape not covered by conv_wino_r64.hip");
-        return launch_conv_wino_r64(a, s);
+    const IgemmKernel k = igemm_kernel(a);
+    const int tile = igemm_tile_class(igemm_sel_M(a), a.Cout);
+    switch (k) {
+        case IK_R64_UPS:
+            VD_REQUIRE(conv_wino_r64_supported(a), "sub-pixel Upsample conv: shape not covered by conv_wino_r64.hip");
+            return launch_conv_wino_r64(a, s);
+        case IK_SPLIT: return launch_gemm_split(a, tile, s);
+        case IK_Z128: return launch_conv_wino_z128(a, s);
+        case IK_R64: return launch_conv_wino_r64(a, s);
+        case IK_FRAG: return launch_gemm_frag(a, tile, s);
+        case IK_WINO: return launch_conv_wino(a, s);
+        case IK_GENERIC: break;
     }
-    if (gemm_split_supported(a) || conv_split_supported(a)) return launch_gemm_split(a, igemm_tile_class(igemm_sel_M(a), a.Cout), s);
-    if (conv_wino_z128_act_supported(a) || conv_wino_z128_supported(a)) return launch_conv_wino_z128(a, s);
-    if (conv_wino_r64_supported(a)) return launch_conv_wino_r64(a, s);
     VD_REQUIRE(!a.wsplit, "split weight image given for a shape the split kernels do not cover");
-    if (gemm_frag_supported(a)) return launch_gemm_frag(a, igemm_tile_class(igemm_sel_M(a), a.Cout), s);
-    if (conv_wino_supported(a)) return launch_conv_wino(a, s);
     VD_REQUIRE(a.w != nullptr, "this shape runs on the generic kernel and needs [tap][Cout][Cin] weights");
-    switch (igemm_tile_class(igemm_sel_M(a), a.Cout)) {
+    switch (tile) {
         case 0: return launch_t<128, 128>(a, s);
         case 1: return launch_t<128, 64>(a, s);
         case 2: return launch_t<64, 128>(a, s);
@@ -236,6 +251,30 @@ int igemm_frames_per_launch(const IgemmArgs& a) {
     return (int)std::min(per, maxfr);
 }
 
+// The launch of frames [f0, f0 + n) of a call that is cut along the frame dimension: base pointers advanced, kernel variants still
+// chosen for the whole call (nfr_sel)
+static IgemmArgs frame_range(const IgemmArgs& a, int f0, int n) {
+    const size_t HWi = (size_t)a.Hs * a.Ws, HWo = (size_t)a.Ho * a.Wo;
+    IgemmArgs b = a;
+    b.nfr = n;
+    b.nfr_sel = a.nfr_sel ? a.nfr_sel : a.nfr;
+    b.M = b.nfr * a.Ho * a.Wo;
+    b.src0 = a.src0 + (size_t)f0 * HWi * a.C0;
+    if (a.src1) b.src1 = a.src1 + (size_t)f0 * HWi * (a.Cin - a.C0);
+    if (a.res) b.res = a.res + (size_t)f0 * HWo * a.res_ld;
+    b.out = a.out + (size_t)f0 * HWo * a.ldo;
+    if (a.affA) { b.affA = a.affA + (size_t)f0 * a.Cin; b.affB = a.affB + (size_t)f0 * a.Cin; }
+    if (a.fbias) b.fbias = a.fbias + (size_t)f0 * a.fbias_ld;
+    if (a.stats) b.stats = a.stats + (size_t)f0 * a.stats_split * a.Cout * 2;
+    if (a.side) { b.side = a.side + (size_t)f0 * HWo * a.Cin; b.sideA = a.sideA + (size_t)f0 * a.Cin; b.sideB = a.sideB + (size_t)f0 * a.Cin; }
+    return b;
+}
+
+IgemmArgs igemm_first_launch(const IgemmArgs& a) {
+    const int per = igemm_frames_per_launch(a);
+    return per > 0 && per < a.nfr ? frame_range(a, 0, per) : a;
+}
+
 int launch_igemm(const IgemmArgs& a, hipStream_t s) {
     VD_REQUIRE(a.Cin % BK == 0, "Cin must be a multiple of 32 (pad the operand)");
     VD_REQUIRE(a.C0 % BK == 0 && a.C0 <= a.Cin, "concat split must be a multiple of 32");
@@ -247,21 +286,8 @@ int launch_igemm(const IgemmArgs& a, hipStream_t s) {
     VD_REQUIRE(per > 0, "one frame of this layer exceeds 2^28 elements");
     if (per >= a.nfr) return launch_igemm_one(a, s);
     VD_REQUIRE(!(a.stats && a.stats_hw > 0), "GroupNorm partial sums from the split GEMM: one launch only (the tile choice, and with it the table, depends on M)");
-    const size_t HWi = (size_t)a.Hs * a.Ws, HWo = (size_t)a.Ho * a.Wo;
     for (int f0 = 0; f0 < a.nfr; f0 += per) {
-        IgemmArgs b = a;
-        b.nfr = std::min(per, a.nfr - f0);
-        b.nfr_sel = a.nfr_sel ? a.nfr_sel : a.nfr;
-        b.M = b.nfr * a.Ho * a.Wo;
-        b.src0 = a.src0 + (size_t)f0 * HWi * a.C0;
-        if (a.src1) b.src1 = a.src1 + (size_t)f0 * HWi * (a.Cin - a.C0);
-        if (a.res) b.res = a.res + (size_t)f0 * HWo * a.res_ld;
-        b.out = a.out + (size_t)f0 * HWo * a.ldo;
-        if (a.affA) { b.affA = a.affA + (size_t)f0 * a.Cin; b.affB = a.affB + (size_t)f0 * a.Cin; }
-        if (a.fbias) b.fbias = a.fbias + (size_t)f0 * a.fbias_ld;
-        if (a.stats) b.stats = a.stats + (size_t)f0 * a.stats_split * a.Cout * 2;
-        if (a.side) { b.side = a.side + (size_t)f0 * HWo * a.Cin; b.sideA = a.sideA + (size_t)f0 * a.Cin; b.sideB = a.sideB + (size_t)f0 * a.Cin; }
-        const int rc = launch_igemm_one(b, s);
+        const int rc = launch_igemm_one(frame_range(a, f0, std::min(per, a.nfr - f0)), s);
         if (rc) return rc;
     }
     return 0;

@@ -178,28 +178,24 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
         if (act) { r.x = silu_f(r.x); r.y = silu_f(r.y); r.z = silu_f(r.z); r.w = silu_f(r.w); }
         return r;
     };
-#ifndef VD_AA_NT
-#define VD_AA_NT 1          // bit 0 nontemporal loads (the source is read once: 5.41 -> 5.79 TB/s), bit 1 nontemporal stores (4.93)
-#endif
-    auto ld4 = [&](const float* q) { return (VD_AA_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)) : *reinterpret_cast<const f32x4*>(q); };
-    auto st4 = [&](float* q, f32x4 v) { if (VD_AA_NT & 2) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(q)); else *reinterpret_cast<f32x4*>(q) = v; };
+    // nontemporal loads (the source is read once: 5.41 -> 5.79 TB/s), plain stores (nontemporal ones: 4.93)
+    auto ld4 = [&](const float* q) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)); };
     int p = p_begin + pl;
     for (; p + 3 * ppi < p_end; p += 4 * ppi) {           // four loads in flight
         f32x4 v[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = ld4(src + (size_t)(p + u * ppi) * ld);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) st4(dst + (size_t)(p + u * ppi) * C, one(v[u]));
+        for (int u = 0; u < 4; ++u) *reinterpret_cast<f32x4*>(dst + (size_t)(p + u * ppi) * C) = one(v[u]);
     }
     for (; p < p_end; p += ppi) *reinterpret_cast<f32x4*>(dst + (size_t)p * C) = one(*reinterpret_cast<const f32x4*>(src + (size_t)p * ld));
 }
 
-// Blocks of the activation pass: pixel ranges of a frame, at least `aa_min_iters` trips of four 16-byte loads per thread, until the grid has
-// `aa_target_blocks` blocks.  tools/probes/stream_probe.hip (r05f, 128 ch x 64 x 64 x 128 frames, read + write): 2048 blocks of 8 trips
+// Blocks of the activation pass: pixel ranges of a frame, at least `kAaMinIters` trips of four 16-byte loads per thread, until the grid has
+// `kAaTargetBlocks` blocks.  tools/probes/stream_probe.hip (r05f, 128 ch x 64 x 64 x 128 frames, read + write): 2048 blocks of 8 trips
 // 5.24 TB/s, 8192 blocks of 2 trips 5.95 TB/s (a flat one-trip mapping 6.16; hipMemcpy 5.43) -- many short blocks keep more requests in
-// flight across the tail of each wave than few long ones.  (VD_AA_BLOCKS / VD_AA_ITERS: A/B knobs, read once.)
-static int aa_target_blocks() { static const int v = getenv("VD_AA_BLOCKS") ? atoi(getenv("VD_AA_BLOCKS")) : 8192; return v; }
-static int aa_min_iters() { static const int v = getenv("VD_AA_ITERS") ? atoi(getenv("VD_AA_ITERS")) : 1; return v; }
+// flight across the tail of each wave than few long ones.
+constexpr int kAaTargetBlocks = 8192, kAaMinIters = 1;
 
 int launch_affine_act(const float* src0, const float* src1, int C0, int C, const float* affA, const float* affB, int nfr,
                       int HW, int act, float* y, hipStream_t s) {
@@ -207,15 +203,14 @@ int launch_affine_act(const float* src0, const float* src1, int C0, int C, const
     const int tpp = C / 4, ppi = 256 / tpp, threads = ppi * tpp;
     // pixel ranges: enough blocks to fill the chip (>= 2048), at least 4 iterations of 4 loads per block where the frame allows
     int split = 1;
-    while (nfr * split < aa_target_blocks() && HW / (split * 2) >= ppi * aa_min_iters() * 4) split *= 2;
+    while (nfr * split < kAaTargetBlocks && HW / (split * 2) >= ppi * kAaMinIters * 4) split *= 2;
     const int per = (HW + split - 1) / split;
     hipLaunchKernelGGL(affine_act_kernel, dim3(split, nfr), dim3(threads), 0, s, src0, src1, C0, C, affA, affB, HW, per, act, y);
     VD_HIP(hipGetLastError());
     return 0;
 }
 
-static int fold_target_blocks() { static const int v = getenv("VD_FOLD_BLOCKS") ? atoi(getenv("VD_FOLD_BLOCKS")) : 2048; return v; }   // A/B knobs, read once
-static int fold_min_rows() { static const int v = getenv("VD_FOLD_ROWS") ? atoi(getenv("VD_FOLD_ROWS")) : 16; return v; }
+constexpr int kFoldTargetBlocks = 2048, kFoldMinRows = 16;      // blocks of the folding pass: see launch_affine_act_fold
 
 // ------------------------------------------------------------------ the fold inside the pass
 // gn_final_affine_kernel is 7.5 us of dependent round trips per launch whatever the size (56 launches per step, 0.42 ms: the
@@ -253,7 +248,7 @@ __global__ __launch_bounds__(256) void affine_act_fold_kernel(const float* __res
     const float* src; int ld;
     if (c < C0) { src = src0 + (size_t)n * HW * C0 + c; ld = C0; } else { src = src1 + (size_t)n * HW * C1 + (c - C0); ld = C1; }
     float* dst = y + (size_t)n * HW * C + c;
-    auto ld4 = [&](const float* q) { return (VD_AA_NT & 1) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)) : *reinterpret_cast<const f32x4*>(q); };
+    auto ld4 = [&](const float* q) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q)); };
     int p = p_begin + pl;
     const bool head = p + 3 * ppi < p_end;
     f32x4 v0[4] = {};
@@ -335,7 +330,7 @@ int launch_affine_act_fold(const float* src0, const float* src1, int C0, int C, 
     VD_REQUIRE(f.part0 && (C0 == C || f.part1), "affine_act_fold: GroupNorm partial tables");
     const int tpp = C / 4, ppi = 256 / tpp, threads = ppi * tpp;
     int split = 1;                                  // (coarse blocks: every block folds its frame's table first -- 8192 blocks: 1.74 -> 2.58 ms per step, r05h)
-    while (nfr * split < fold_target_blocks() && HW / (split * 2) >= ppi * fold_min_rows()) split *= 2;
+    while (nfr * split < kFoldTargetBlocks && HW / (split * 2) >= ppi * kFoldMinRows) split *= 2;
     const int per = (HW + split - 1) / split;
     const size_t lds = (size_t)(8 * threads + 2 * C) * sizeof(double) + 64 * sizeof(float);
     hipLaunchKernelGGL(affine_act_fold_kernel, dim3(split, nfr), dim3(threads), lds, s, src0, src1, C0, C, f, HW, per, act, y);

@@ -90,16 +90,14 @@ struct IgemmArgs {
     // gemm_split.hip (linear layers whose rows are the pixels of consecutive frames): rows per frame; the table is then
     // [frame][stats_split = stats_hw / rows of a wave tile][Cout][2] (gemm_split_stats_rows)
     int stats_hw;
-    // gemm_frag.hip only: zcount > 1 runs zcount independent problems of identical shape in one launch (blockIdx.z);
-    // problem z reads src0 + z*zs_a, wfrag + z*zs_w, bias + z*zs_bias and writes out + z*zs_out (element strides).
-    // The three RPE-net output layers of an attention block (unet.py:283-298) go out this way.
-    int zcount, zs_a, zs_w, zs_bias, zs_out;
-    // gemm_split.hip: problems whose weights do not sit at a constant stride (the RPE nets of ALL attention blocks of one width in one
-    // launch, engine.hip: rpe_all): problem z takes wfrag = zbase + ztab[2z], bias = zbase + ztab[2z + 1] (float offsets, device table)
+    // gemm_frag.hip, gemm_split.hip: zcount > 1 runs zcount independent problems of identical shape in one launch (blockIdx.z), the
+    // relative-position nets of ALL attention blocks of one width (engine.hip: rpe_all).  Problem z reads src0 + z*zs_a and writes
+    // out + z*zs_out (element strides); its weights and bias sit at no constant stride: wfrag = zbase + ztab[2z], bias = zbase + ztab[2z + 1]
+    // (float offsets, device table).  wfrag / bias themselves hold problem 0's (the shape checks read them).
+    int zcount, zs_a, zs_out;
     const long long* ztab = nullptr; const float* zbase = nullptr;
     // wsplit == 2: wwino is the image of pack_conv3_wino_split (conv_wino_r64.hip).  Otherwise:
-    // wfrag is the bf16-split image of the weights (gemm_split.hip: fp32 accuracy from six bf16 piece products);
-    // zs_w then counts floats of that image as well
+    // wfrag is the bf16-split image of the weights (gemm_split.hip: fp32 accuracy from six bf16 piece products)
     int wsplit;
     // conv_wino_r64.hip, small grids only: scratch for split-K partial outputs (conv_wino_r64_ksplit_floats), or null
     float* ksplit_ws;
@@ -127,6 +125,12 @@ struct AttnTemporalArgs {
 
 int launch_igemm(const IgemmArgs& a, hipStream_t s);
 int igemm_frames_per_launch(const IgemmArgs& a);   // frames (rows) per launch: big windows are cut along the frame dimension
+IgemmArgs igemm_first_launch(const IgemmArgs& a);  // the args of the first launch launch_igemm makes for `a` (`a` itself when not cut)
+// the kernel launch_igemm takes for ONE launch's args: the sub-pixel form of conv_wino_r64.hip, the split GEMM (gemm_split.hip, 1x1 or
+// implicit-im2col 3x3), conv_wino_z128.hip (plain or activating), conv_wino_r64.hip, gemm_frag.hip, the fp32 Winograd kernel
+// (conv_wino.hip), the generic kernel (igemm.hip)
+enum IgemmKernel { IK_R64_UPS, IK_SPLIT, IK_Z128, IK_R64, IK_FRAG, IK_WINO, IK_GENERIC };
+IgemmKernel igemm_kernel(const IgemmArgs& a);
 int igemm_tile_class(int M, int Cout);   // 0: 128x128, 1: 128x64, 2: 64x128, 3: 64x64
 // linear / 1x1 path with fragment-major weights (gemm_frag.hip); wfrag = [K/32][N/32][4][64][4]
 bool gemm_frag_supported(const IgemmArgs& a);
@@ -303,10 +307,7 @@ int launch_scatter_stats(const double* src, int split, int C, const int* list, i
 // out[n] = [cos(t*f) | sin(t*f)] with the frequency table built on the host (nn.py:89-107)
 int launch_sinus_embed(const float* t, int n, int dim, const float* freqs, float* out, hipStream_t s);
 // RPENet hidden: E[b,t,s,c] = silu(te[b*T+t][c] + Wd[c][:]*feat(d) + bd[c]), d = fi[b,t]-fi[b,s]  (unet.py:283-296)
-// nz nets at once (blockIdx.y): net z reads te + z*zs_te, Wd + z*zs_w, bd + z*zs_b and writes E + z*zs_e
-int launch_rpe_hidden(const float* te, int te_ld, const float* Wd, const float* bd, const int64_t* fidx, int B, int T,
-                      int C, float* E, int nz, int zs_te, int zs_w, int zs_b, size_t zs_e, hipStream_t s);
-// the same for nets at arbitrary places: net z reads te + tab[3z], wbase + tab[3z + 1] (Wd), wbase + tab[3z + 2] (bd)
+// nz nets at once (blockIdx.y): net z reads te + tab[3z], wbase + tab[3z + 1] (Wd), wbase + tab[3z + 2] (bd) and writes E + z*zs_e
 int launch_rpe_hidden_tab(const float* te, int te_ld, const float* wbase, const long long* tab, const int64_t* fidx, int B, int T, int C,
                           float* E, int nz, size_t zs_e, hipStream_t s);
 // bucket-table path (unet.py:330-347): R[b,t,s,:] = table[bucket(d)]
@@ -396,7 +397,7 @@ struct GuidedArgs {
     float* deps; float* dxd;            // d loss / d eps, and the direct part of d loss / d x
     float* mean; float* xstart;         // the unguided posterior mean and the x_0 prediction
     int* err = nullptr;                 // sticky error word (bit 1: eps not finite)
-    const float* gscale = nullptr;      // {s, 1 / s}: the backward pass ran on s * d loss / d eps (backward.hip: launch_grad_rescale); null: 1
+    const float* gscale = nullptr;      // {s, 1 / s}: the backward pass ran on s * d loss / d eps (backward.hip: launch_grad_rescale); set before launch_guided_final
 };
 int launch_grad_rescale(float* deps, size_t n, float* gs, hipStream_t st);
 int launch_guided_grad(const GuidedArgs& a, hipStream_t s);
