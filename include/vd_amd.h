@@ -117,7 +117,14 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * The host mirror raises FloatingPointError. */
 int vd_device_errors(vd_engine* e, int* flags);
 
-/* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call. */
+/* Longest window, in frames per batch item, that every forward / step / window entry point accepts: 128.  A window is any
+ * T in 1..vd_max_window_frames() (the reference's UNet takes any T; --max_frames picks it at sampling time).  T <= 32 runs
+ * on the original temporal attention / GroupNorm kernels, 33..128 on their long-window forms (key tiles with an online
+ * softmax).  vd_guided_step (use_gradient_method) is limited to T <= 32.  Larger T fails with a message naming the limit. */
+int vd_max_window_frames(void);
+
+/* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
+ * grow with B*T^2 (about 60 KB per (b, t, s) pair for the default 64x64 model: ~1 GB at B = 1, T = 128). */
 int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes);
 
 /* observed_frames: 0 'x_0', 1 'x_t', 2 'x_t_minus_1' (unet.py:958-974,991-1013). */
@@ -241,6 +248,8 @@ int vd_attn_block_info(vd_engine* e, int i, int* resolution, int* channels);
 int vd_set_attn_capture(vd_engine* e, float* const* temporal, float* const* spatial, int n);
 
 /* use_gradient_method (gaussian_diffusion.py:264-271,350-364; scripts/video_sample.py:429 `--use_gradient_method`).
+ * Windows of at most 32 frames (the backward kernels of temporal attention and GroupNorm); a longer T fails with a message
+ * that names use_gradient_method and the limit.
  * The guidance needs d(loss)/d(x_t) through the whole UNet: backward-DATA only, no weight gradients.  Its matrix products
  * run on the forward kernels over a second packed image -- transposed linear weights, 180-degree-rotated transposed 3x3
  * kernels -- that exists only when asked for: vd_bwd_weights_bytes -> vd_set_bwd_weight_storage (device memory, or host

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "misc.hip", "engine.hip", "lpips.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # per-source flags on top of the common ones.  conv_wino_z128.hip: its main loop is ONE fully unrolled body of 288 MFMA slots; past
 # LLVM's default size limit for `#pragma unroll` (16 k IR instructions) hipcc silently keeps the loops and indexes the register
@@ -142,6 +142,7 @@ SIGNATURES = {
     "vd_last_error": (ctypes.c_char_p, []),
     "vd_version": (ctypes.c_char_p, []),
     "vd_source_sha": (ctypes.c_char_p, []),
+    "vd_max_window_frames": (_I, []),
     "vd_create": (_I, [ctypes.POINTER(VdConfig), ctypes.POINTER(_P)]),
     "vd_destroy": (None, [_P]),
     "vd_param_count": (_I, [_P]),

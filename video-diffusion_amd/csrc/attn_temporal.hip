@@ -4,6 +4,7 @@
 //   w[t,s] = q't.ks + q't.Rk[t,s] + (ks*scale).Rq[s,t]      q' = q*scale
 //   w -= inf where the frame mask forbids (t,s)               (unet.py:511-524)
 //   a = softmax_s(w);  o[t] = sum_s a[t,s] * (vs + Rv[t,s])
+// (Windows of 33..128 frames: attn_temporal_long.hip.)
 //
 // One block = PB pixels of one (batch, head).  q' and k of those pixels are staged in LDS once
 // (coalesced 4F-byte rows; rows padded by 4 floats so the 16 distinct key rows of a ds_read_b128 lane
@@ -489,9 +490,10 @@ static int launch_tt(const AttnTemporalArgs& a, size_t lds, hipStream_t s) {
 }
 
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.T >= 1 && a.T <= 32, "temporal window of 1..32 frames");
+    VD_REQUIRE(a.T >= 1 && a.T <= kMaxWindowFrames, "temporal window of 1..128 frames");
     VD_REQUIRE(a.C % a.heads == 0 && (a.C / a.heads) % 8 == 0, "head dim multiple of 8");
     VD_REQUIRE((a.Rk == nullptr) == (a.Rq == nullptr) && (a.Rk == nullptr) == (a.Rv == nullptr), "all or no RPE terms");
+    if (a.T > 32) return launch_attn_temporal_long(a, s);     // key tiles + online softmax (attn_temporal_long.hip)
     const int F = a.C / a.heads;
     // The kernel is chosen by the per-item shape alone (pixels, heads, head dim, T), never by the batch: a clip gives the same
     // bits whether it is sampled alone (a strong-scaling shard) or inside a batch.  (At B = 1 the 4-pixel blocks of the

@@ -727,8 +727,85 @@ __global__ __launch_bounds__(256) void attn_temporal_weights_kernel(AttnTemporal
     for (int i = tid; i < T * T; i += 256) out[((size_t)b * HW + p) * T * T + i] = fabsf(M[(i / T) * TS + (i % T)] * ih);
 }
 
+// Long windows (33..kMaxWindowFrames frames): the same maps with the query rows cut into chunks of QC, one block per (pixel, batch
+// element, chunk), so that q of the chunk, k, and the chunk's score / mean rows fit LDS (117 KB at T = 128, F = 128).
+template <bool RPE>
+__global__ __launch_bounds__(256) void attn_temporal_weights_long_kernel(AttnTemporalArgs a, float* __restrict__ out) {
+    constexpr int QC = 32;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int T = a.T, C = a.C, HW = a.HW, C3 = 3 * C, F = C / a.heads, FP = F + 4, TS = T + 1;
+    const int p = blockIdx.x, b = blockIdx.y, r0 = QC * blockIdx.z, nr = min(QC, T - r0), tid = threadIdx.x;
+    float* qs = smem;                    // [QC][FP]  rows r0 ..
+    float* ks = qs + QC * FP;            // [T][FP]
+    float* P = ks + T * FP;              // [QC][TS] one head
+    float* M = P + QC * TS;              // [QC][TS] mean over heads
+    const size_t tok0 = (size_t)b * T * HW + p;
+    for (int i = tid; i < QC * TS; i += 256) M[i] = 0.f;
+    for (int h = 0; h < a.heads; ++h) {
+        __syncthreads();
+        for (int i = tid; i < T * F; i += 256) {
+            const int t = i / F, f = i - t * F;
+            const float* r = a.qkv + (tok0 + (size_t)t * HW) * C3 + h * F + f;
+            if (t >= r0 && t < r0 + nr) qs[(t - r0) * FP + f] = r[0] * a.scale;
+            ks[t * FP + f] = r[C];
+        }
+        __syncthreads();
+        for (int pr = tid; pr < nr * T; pr += 256) {
+            const int tl = pr / T, s_ = pr - tl * T, t = r0 + tl;
+            const float* rk = RPE ? a.Rk + (((size_t)b * T + t) * T + s_) * C + h * F : nullptr;
+            const float* rq = RPE ? a.Rq + (((size_t)b * T + s_) * T + t) * C + h * F : nullptr;
+            float w = 0.f;
+            for (int f = 0; f < F; ++f) {
+                const float k = ks[s_ * FP + f];
+                w += qs[tl * FP + f] * (k + (RPE ? rk[f] : 0.f)) + (RPE ? a.scale * k * rq[f] : 0.f);
+            }
+            bool masked = false;
+            if (a.mask) {
+                const float mt = a.mask[b * T + t], ms = a.mask[b * T + s_];
+                float allowed = mt * ms;
+                if (a.allow_pad) allowed += (1.f - mt) * (1.f - ms);
+                else if (t == s_) allowed = 1.f;
+                masked = allowed == 0.f;
+            }
+            P[tl * TS + s_] = masked ? -INFINITY : w;
+        }
+        __syncthreads();
+        if (tid < nr) {
+            float* r = P + tid * TS;
+            float mx = -INFINITY;
+            for (int s_ = 0; s_ < T; ++s_) mx = fmaxf(mx, r[s_]);
+            float sum = 0.f;
+            for (int s_ = 0; s_ < T; ++s_) { const float e = __expf(r[s_] - mx); r[s_] = e; sum += e; }
+            const float inv = 1.0f / sum;
+            for (int s_ = 0; s_ < T; ++s_) M[tid * TS + s_] += r[s_] * inv;
+        }
+    }
+    __syncthreads();
+    const float ih = 1.0f / (float)a.heads;
+    float* o = out + (((size_t)b * HW + p) * T + r0) * T;
+    for (int i = tid; i < nr * T; i += 256) o[i] = fabsf(M[(i / T) * TS + (i % T)] * ih);
+}
+
+static int launch_attn_temporal_weights_long(const AttnTemporalArgs& a, float* out, hipStream_t s) {
+    constexpr int QC = 32;
+    const int F = a.C / a.heads;
+    const size_t lds = ((size_t)(QC + a.T) * (F + 4) + (size_t)2 * QC * (a.T + 1)) * sizeof(float);
+    VD_REQUIRE(lds <= 150 * 1024, "temporal attention weights: head dim too large");
+    const dim3 grid(a.HW, a.B, (a.T + QC - 1) / QC);
+    if (a.Rk) {
+        VD_RAISE_LDS((&attn_temporal_weights_long_kernel<true>), lds);
+        hipLaunchKernelGGL(attn_temporal_weights_long_kernel<true>, grid, dim3(256), lds, s, a, out);
+    } else {
+        VD_RAISE_LDS((&attn_temporal_weights_long_kernel<false>), lds);
+        hipLaunchKernelGGL(attn_temporal_weights_long_kernel<false>, grid, dim3(256), lds, s, a, out);
+    }
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_attn_temporal_weights(const AttnTemporalArgs& a, float* out, hipStream_t s) {
-    VD_REQUIRE(a.T >= 1 && a.T <= 32 && a.C % a.heads == 0, "temporal attention weights: shape");
+    VD_REQUIRE(a.T >= 1 && a.T <= kMaxWindowFrames && a.C % a.heads == 0, "temporal attention weights: shape");
+    if (a.T > 32) return launch_attn_temporal_weights_long(a, out, s);
     const int F = a.C / a.heads;
     const size_t lds = ((size_t)2 * a.T * (F + 4) + (size_t)2 * a.T * (a.T + 1)) * sizeof(float);
     VD_REQUIRE(lds <= 150 * 1024, "temporal attention weights: head dim too large");

@@ -1709,7 +1709,7 @@ int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes) {
 
 static int check_ready(vd_engine* e, int B, int T) {
     VD_REQUIRE(e, "null engine");
-    VD_REQUIRE(B > 0 && T > 0 && T <= 32, "window of 1..32 frames");
+    VD_REQUIRE(B > 0 && T > 0 && T <= kMaxWindowFrames, "window of 1.." + std::to_string(kMaxWindowFrames) + " frames (vd_max_window_frames)");
     VD_REQUIRE(e->wbuf && !e->wbuf_on_host, "weights not set (the packed image must live in device memory: vd_set_weight_storage)");
     int miss = vd_weights_missing(e);
     if (miss) {
@@ -1718,6 +1718,8 @@ static int check_ready(vd_engine* e, int B, int T) {
     }
     return 0;
 }
+
+int vd_max_window_frames(void) { return kMaxWindowFrames; }
 
 int vd_unet_forward(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs,
                     const float* lat, const float* km, const long long* fidx, const float* t_model, int obs_mode,
@@ -2192,6 +2194,8 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs,
                    const float* noise2, float* mean, float* xstart, float* grad, float* sample, void* stream) {
     int rc = check_ready(e, B, T);
     if (rc) return rc;
+    VD_REQUIRE(T <= kMaxGuidedWindowFrames, "use_gradient_method: windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
+                                            " frames (its temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
     VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283)");
     VD_REQUIRE(e->mean_type == 0, "use_gradient_method: epsilon-prediction models only");

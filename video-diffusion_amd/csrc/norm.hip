@@ -451,10 +451,112 @@ __global__ __launch_bounds__(256) void gn_temporal_generic_kernel(const float* _
         if (t < T) *reinterpret_cast<f32x4*>(y + (((size_t)b * T + t) * HW + p) * C + q * 4) = v[t] * A + Bv;
 }
 
+// Long windows (33..kMaxWindowFrames frames): a pixel's T rows are cut into slices of 16 frames, one thread per (slice, channel
+// quad), so that a thread still keeps its rows in registers between the statistics and the normalisation (each element read
+// and written once).  Thread -> (pixel slot, frame slice, channel quad); a block holds whole pixels (up to 1024 threads).  The
+// partial sums are fp64 per thread; the group total sums them over the group's quads of every slice.  QUAD: a thread's quad
+// lies in one group (one partial pair per thread); else one pair per channel (the tiny test models' 2 channels per group).
+template <bool QUAD>
+__global__ __launch_bounds__(1024) void gn_temporal_long_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                const float* __restrict__ beta, int T, int HW, int C,
+                                                                float* __restrict__ y) {
+    constexpr int TR = 16;
+    extern __shared__ __attribute__((aligned(16))) double sred[];   // QUAD: [thread][2]; else [thread][4 channels][2]
+    const int tpp = C >> 2, ns = (T + TR - 1) / TR, tpx = tpp * ns, ppb = blockDim.x / tpx;
+    const int tid = threadIdx.x;
+    const int pl = tid / tpx, rem = tid - pl * tpx, sl = rem / tpp, q = rem - sl * tpp;
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * ppb + pl;
+    const bool active = pl < ppb && p < HW;
+    const int tb = sl * TR;
+    f32x4 v[TR];
+    double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+    if (active) {
+#pragma unroll
+        for (int t = 0; t < TR; ++t)
+            if (tb + t < T) {
+                v[t] = *reinterpret_cast<const f32x4*>(x + (((size_t)b * T + tb + t) * HW + p) * C + q * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const double d = (double)v[t][e]; s[e] += d; ss[e] += d * d; }
+            }
+        if constexpr (QUAD) {
+            sred[(size_t)tid * 2] = (s[0] + s[1]) + (s[2] + s[3]);
+            sred[(size_t)tid * 2 + 1] = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { sred[((size_t)tid * 4 + e) * 2] = s[e]; sred[((size_t)tid * 4 + e) * 2 + 1] = ss[e]; }
+        }
+    }
+    __syncthreads();
+    if (!active) return;
+    const int cg = C / 32;
+    const double cnt = (double)cg * T;
+    const int px0 = pl * tpx;                    // first thread of this pixel slot
+    f32x4 A, Bv;
+    if constexpr (QUAD) {
+        const int tpg = cg >> 2, q0 = q - (q % tpg);
+        double gs = 0, gss = 0;
+        for (int j = 0; j < ns; ++j)
+            for (int k = 0; k < tpg; ++k) {
+                const size_t o = (size_t)(px0 + j * tpp + q0 + k) * 2;
+                gs += sred[o]; gss += sred[o + 1];
+            }
+        const double mean = gs / cnt;
+        double var = gss / cnt - mean * mean;
+        if (var < 0) var = 0;
+        const float rstd = (float)(1.0 / sqrt(var + 1e-5));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = q * 4 + e;
+            A[e] = rstd * gamma[c];
+            Bv[e] = beta[c] - (float)mean * A[e];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int c = q * 4 + e, g = c / cg;
+            double gs = 0, gss = 0;
+            for (int j = 0; j < ns; ++j)
+                for (int k = g * cg; k < (g + 1) * cg; ++k) {
+                    const size_t o = ((size_t)(px0 + j * tpp + (k >> 2)) * 4 + (k & 3)) * 2;
+                    gs += sred[o]; gss += sred[o + 1];
+                }
+            const double mean = gs / cnt;
+            double var = gss / cnt - mean * mean;
+            if (var < 0) var = 0;
+            const float rstd = (float)(1.0 / sqrt(var + 1e-5));
+            A[e] = rstd * gamma[c];
+            Bv[e] = beta[c] - (float)mean * A[e];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < TR; ++t)
+        if (tb + t < T) *reinterpret_cast<f32x4*>(y + (((size_t)b * T + tb + t) * HW + p) * C + q * 4) = v[t] * A + Bv;
+}
+
+static int launch_gn_temporal_long(const float* x, const float* gamma, const float* beta, int B, int T, int HW, int C, float* y,
+                                   hipStream_t s) {
+    const int tpx = (C / 4) * ((T + 15) / 16);                        // threads per pixel
+    VD_REQUIRE(tpx <= 1024, "temporal GroupNorm: C/4 * ceil(T/16) <= 1024 (C <= 512 at 128 frames)");
+    const int ppb = std::max(1, 256 / tpx), threads = ppb * tpx;
+    dim3 grid((HW + ppb - 1) / ppb, B);
+    if ((C / 32) % 4 == 0) {
+        const size_t lds = (size_t)threads * 2 * sizeof(double);
+        hipLaunchKernelGGL(gn_temporal_long_kernel<true>, grid, dim3(threads), lds, s, x, gamma, beta, T, HW, C, y);
+    } else {
+        const size_t lds = (size_t)threads * 8 * sizeof(double);
+        VD_RAISE_LDS((&gn_temporal_long_kernel<false>), lds);
+        hipLaunchKernelGGL(gn_temporal_long_kernel<false>, grid, dim3(threads), lds, s, x, gamma, beta, T, HW, C, y);
+    }
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_gn_temporal(const float* x, const float* gamma, const float* beta, int B, int T, int HW, int C, float* y,
                        hipStream_t s) {
     VD_REQUIRE(C % 32 == 0 && C <= 1024, "GroupNorm32 channel constraints");
-    VD_REQUIRE(T >= 1 && T <= 32, "temporal window of 1..32 frames");
+    VD_REQUIRE(T >= 1 && T <= kMaxWindowFrames, "temporal window of 1..128 frames");
+    if (T > 32) return launch_gn_temporal_long(x, gamma, beta, B, T, HW, C, y, s);
     const int ppb = 256 / (C / 4);
     dim3 grid((HW + ppb - 1) / ppb, B);
     if ((C / 32) % 4 == 0) {                      // a thread's channel quad lies in one group: the fast kernel

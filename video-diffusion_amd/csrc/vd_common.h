@@ -10,6 +10,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace vd {
 
+// Longest window the forward serves (frames per item): the temporal attention and GroupNorm kernels are built for 1..32 frames
+// (attn_temporal.hip, norm.hip) and for 33..128 (attn_temporal_long.hip, norm.hip's long form).  The guided step's backward
+// kernels (use_gradient_method, backward.hip) stay at kMaxGuidedWindowFrames.
+constexpr int kMaxWindowFrames = 128;
+constexpr int kMaxGuidedWindowFrames = 32;
+
 // Error plumbing: every C-ABI entry returns 0 or a negative code; text via vd_last_error().
 void set_error(const std::string& msg);
 extern thread_local std::string g_last_error;
@@ -254,6 +260,7 @@ int launch_conv_wino(const IgemmArgs& a, hipStream_t s);
 void pack_conv3_wino(const float* oihw, float* out, int O, int I);      // out: 16*O*I floats
 int launch_attn_spatial(const AttnSpatialArgs& a, hipStream_t s);
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s);
+int launch_attn_temporal_long(const AttnTemporalArgs& a, hipStream_t s);   // 33 <= T <= kMaxWindowFrames (attn_temporal_long.hip)
 
 // GroupNorm statistics over (pixels x channels-of-group) of one frame, 32 groups, virtual concat.
 // part: workspace of nfr*split*C*2 doubles (per-channel fp64 sum / sum of squares per pixel range).
