@@ -394,6 +394,24 @@ int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, cons
                         int T, int HW, int C, int heads, int allow_pad, float* out, void* stream);
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
+/* Backward-data operators of use_gradient_method (csrc/backward.hip); each one synchronises its stream before it returns. */
+/* GroupNorm32(+FiLM)(+SiLU) backward over a virtual concat; mr [nfr][32][2] (mean, rstd); dx0 / dx1 assigned or accumulated (acc0 / acc1), plus extra if given. */
+int vd_op_gn_bwd(const float* x0, const float* x1, int C0, int C, const float* affA, const float* affB, const float* mr,
+                 const float* dy, int act, int nfr, int HW, const float* extra, float* dx0, int acc0, float* dx1, int acc1,
+                 void* stream);
+/* Backward of vd_op_gn_temporal without its affine shift (the statistics are recomputed from x); T <= 32. */
+int vd_op_gn_temporal_bwd(const float* x, const float* gamma, const float* dy, int B, int T, int HW, int C, int accumulate,
+                          float* dx, void* stream);
+/* Backward of vd_op_attn_temporal: dout [B*T*HW][C] -> dqkv [B*T*HW][3C]; T <= 32. */
+int vd_op_attn_temporal_bwd(const float* qkv, const float* Rk, const float* Rq, const float* Rv, const float* mask, int B,
+                            int T, int HW, int C, int heads, int allow_pad, const float* dout, float* dqkv, void* stream);
+/* Backward of vd_op_attn_spatial: dout [nfr*L][C] -> dqkv [nfr*L][3C]; L <= 1024, head dim <= 128 and a multiple of 4. */
+int vd_op_attn_spatial_bwd(const float* qkv, int nfr, int L, int C, int heads, const float* dout, float* dqkv, void* stream);
+/* Output head conv backward, data part: deps [nfr][Cout][H][W] -> da [nfr][H][W][C]; w as vd_op_out_conv's w_packed [tap][Cout][C]. */
+int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W, int C, int Cout, float* da, void* stream);
+/* Stem backward: dcols [nfr][H*W][64] (k = tap * stem channels + channel) -> dx [nfr][3][H][W]; cond_mode 0 channel, 1 duplicate / all, 2 t=0. */
+int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, const float* km, int nfr, int H, int W,
+                      int cond_mode, float* dx, void* stream);
 
 /* ---- LPIPS frame distance of the adaptive-* frame schedulers (csrc/lpips.hip).
  * Replaces LpipsEmbedder (improved_diffusion/inference_util.py:15-31: lpips.LPIPS(net='alex', spatial=False), AlexNet features

@@ -219,6 +219,12 @@ SIGNATURES = {
     "vd_op_attn_spatial": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "vd_op_attn_temporal": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_out_conv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_gn_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "vd_op_gn_temporal_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_attn_temporal_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "vd_op_attn_spatial_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "vd_op_out_conv_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_stem_col2im": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "vd_lpips_create": (_I, [ctypes.POINTER(_P)]),
     "vd_lpips_destroy": (None, [_P]),
     "vd_lpips_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),

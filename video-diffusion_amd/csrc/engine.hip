@@ -2474,4 +2474,58 @@ int vd_op_out_conv(const float* x, const float* affA, const float* affB, const f
     return launch_out_conv(x, affA, affB, w, bias, nfr, H, W, C, Cout, out, static_cast<hipStream_t>(stream));
 }
 
+// ---- backward-data operators of use_gradient_method (backward.hip)
+int vd_op_gn_bwd(const float* x0, const float* x1, int C0, int C, const float* affA, const float* affB, const float* mr,
+                 const float* dy, int act, int nfr, int HW, const float* extra, float* dx0, int acc0, float* dx1, int acc1,
+                 void* stream) {
+    VD_REQUIRE(nfr > 0 && HW > 0 && C > 0 && C % 32 == 0 && C <= 1024, "vd_op_gn_bwd: shape");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int split = gn_bwd_split(nfr, HW, C);
+    double* part = nullptr;
+    float* K = nullptr;
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(&part), (size_t)nfr * split * C * 2 * sizeof(double)));
+    if (hipMalloc(reinterpret_cast<void**>(&K), (size_t)nfr * 32 * 2 * sizeof(float)) != hipSuccess) {
+        (void)hipFree(part);
+        VD_REQUIRE(false, "vd_op_gn_bwd: workspace allocation");
+    }
+    GnBwdArgs a{x0, x1, C0, C, affA, affB, mr, dy, act, nfr, HW, dx0, dx1, acc0, acc1, extra, part, K};
+    int rc = launch_gn_bwd(a, st);
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(part);
+    (void)hipFree(K);
+    return rc;
+}
+
+int vd_op_gn_temporal_bwd(const float* x, const float* gamma, const float* dy, int B, int T, int HW, int C, int accumulate,
+                          float* dx, void* stream) {
+    return launch_gn_temporal_bwd(x, gamma, dy, B, T, HW, C, accumulate, dx, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_attn_temporal_bwd(const float* qkv, const float* Rk, const float* Rq, const float* Rv, const float* mask, int B,
+                            int T, int HW, int C, int heads, int allow_pad, const float* dout, float* dqkv, void* stream) {
+    AttnTemporalArgs a{qkv, Rk, Rq, Rv, mask, nullptr, B, T, HW, C, heads, allow_pad, 1.0f / sqrtf((float)(C / heads))};
+    return launch_attn_temporal_bwd(a, dout, dqkv, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_attn_spatial_bwd(const float* qkv, int nfr, int L, int C, int heads, const float* dout, float* dqkv, void* stream) {
+    VD_REQUIRE(nfr > 0 && L > 0 && heads > 0 && C % heads == 0, "vd_op_attn_spatial_bwd: shape");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AttnSpatialArgs a{qkv, nullptr, nfr, L, C, heads, 1.0f / sqrtf((float)(C / heads))};
+    float* ws = nullptr;
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(&ws), attn_spatial_bwd_ws_floats(a) * sizeof(float)));
+    int rc = launch_attn_spatial_bwd(a, dout, dqkv, ws, st);
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(ws);
+    return rc;
+}
+
+int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W, int C, int Cout, float* da, void* stream) {
+    return launch_out_conv_bwd(deps, w, nfr, H, W, C, Cout, da, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, const float* km, int nfr, int H, int W,
+                      int cond_mode, float* dx, void* stream) {
+    return launch_stem_col2im(dcols, obs, lat, km, nfr, H, W, STEM_KPAD, cond_mode, dx, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"
