@@ -82,7 +82,6 @@ static const int CH_MULT_32[] = {1, 2, 2, 2};
 // VD_MATH (vd_common.h): f16x3 (default) and bf16x6 run every matrix product on the split kernels (gemm_split.hip,
 // conv_wino_r64.hip) over 16-bit piece images; fp32 keeps them on the fp32 MFMA (gemm_frag.hip, conv_wino.hip).
 static bool split_math() { return math_mode() != MATH_FP32; }
-static bool split_conv() { return split_math(); }
 
 constexpr int STEM_KPAD = 64;          // im2col width of the 5-channel 3x3 stem (45 real columns)
 
@@ -134,7 +133,7 @@ struct Profiler {
 static Profiler g_prof;
 static const char* prof_name(int i) {
     if (i < 0 || i >= PC_COUNT) return "";
-    return kProfNames[i][i == PC_CONV_WINO || i == PC_CONV_WINO_R64 ? !split_conv() : !split_math()];
+    return kProfNames[i][!split_math()];
 }
 
 struct ProfScope {
@@ -148,6 +147,12 @@ struct ProfScope {
         g_prof.recs.push_back(r);
     }
     ~ProfScope() { if (live) (void)hipEventRecord(g_prof.recs.back().b, st); }
+};
+// no event records for a scope (a stream capture, the window prefix build pass): the switch is restored on every way out
+struct ProfPause {
+    bool was = g_prof.on;
+    ProfPause() { g_prof.on = false; }
+    ~ProfPause() { g_prof.on = was; }
 };
 
 // res_block decides from the SHAPE alone (conv_wino_z128_act_shape) that a conv activates in its own patch staging and then never
@@ -272,11 +277,16 @@ struct vd_engine {
     float* d_freq_frame = nullptr; int n_freq_frame = 0;
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
-    // workspace: activations of one (B, T) window [0, ws_tail), then t_model [B] and the eps scratch
+    // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded) and the eps scratch
     char* ws = nullptr; size_t ws_cap = 0;
     bool ws_suf = false;
     int ws_B = 0, ws_T = 0; size_t ws_tail = 0;      // the window shape ws_tail was computed for (dry run of the topology)
     std::unordered_map<long long, size_t> ws_peaks;  // (B << 32 | T) -> arena peak
+    static size_t tm_bytes(int B) { return ((size_t)B * sizeof(float) + 255) & ~(size_t)255; }
+    size_t step_tail_bytes(int B, int T) const { return tm_bytes(B) + (size_t)B * T * (cfg.learn_sigma ? 6 : 3) * cfg.image_size * cfg.image_size * sizeof(float); }
+    float* step_tm() const { return reinterpret_cast<float*>(ws + ws_tail); }
+    float* step_eps(int B) const { return reinterpret_cast<float*>(ws + ws_tail + tm_bytes(B)); }
+    Arena step_arena() const { Arena a; a.base = ws; a.cap = ws_tail; return a; }     // the activations end where the tail begins
     // ---- use_gradient_method: second packed image (backward-data weights) + the tape of the guided step's forward
     float* wbuf_bwd = nullptr; bool wbuf_bwd_on_host = false; size_t packed_bwd_total = 0;
     Tape* tape = nullptr;
@@ -288,32 +298,34 @@ struct vd_engine {
     int device = -1;
     double* d_part = nullptr; size_t part_cap = 0;   // NLL partial sums
     // ---- window executor (vd_window_*): device-resident step state + one captured graph per window signature
-    struct WinKey {
+    struct WinKey {                  // the arguments of vd_window_begin a captured step depends on (zero-filled: compared bytewise)
         int B, T, obs_mode, sampler, clip, flags; float eta;      // flags: 1 prefix cache, 2 suffix skip
-        const void *x, *obs_src, *obs, *lat, *km, *fidx;
+        float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
-        WinKey key; hipGraph_t graph; hipGraphExec_t exec;
+        WinKey key; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         // window prefix cache: which frames are step-invariant (part of the signature: the compact batch size is baked into the
         // captured launches), the two device lists and the persistent tensors the captured step reads and writes
         std::vector<unsigned char> inv; int n_inv = 0, n_suf = 0;   // n_suf: frames the suffix runs on (0: all of them)
         int* d_lists = nullptr;                  // [n_act active frames | n_inv invariant frames]
         PrefixStore* store = nullptr;
+        void release() {             // everything the graph owns; a graph the executor's stream may still run is drained first by the caller
+            if (exec) (void)hipGraphExecDestroy(exec);
+            if (graph) (void)hipGraphDestroy(graph);
+            if (d_lists) (void)hipFree(d_lists);
+            if (store) { for (float* p : store->tens) if (p) (void)hipFree(p); for (double* p : store->parts) if (p) (void)hipFree(p); delete store; }
+            exec = nullptr; graph = nullptr; d_lists = nullptr; store = nullptr;
+        }
     };
     bool prefix_cache_on = false;                // vd_set_window_prefix_cache
     bool suffix_skip_on = false;                 // vd_set_window_suffix_skip
-    static void free_graph(WinGraph& g) {
-        (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph);
-        if (g.d_lists) (void)hipFree(g.d_lists);
-        if (g.store) { for (float* p : g.store->tens) if (p) (void)hipFree(p); for (double* p : g.store->parts) if (p) (void)hipFree(p); delete g.store; }
-    }
     std::vector<WinGraph> win_graphs;
     int win_cur = -1;
     bool win_lost = false;                               // the armed window's graph was dropped (workspace growth / new schedule)
     unsigned long long win_gen = 0;                      // bumped by every vd_window_begin: a run must name the window it continues
     long long win_left = 0;                              // steps the current window still has (t + 1)
-    long long* d_win_t = nullptr; int win_t_cap = 0;     // [B] current respaced index of the window
+    long long* d_win_t = nullptr; size_t win_t_cap = 0;  // [B] current respaced index of the window
     float* d_win_xtm1 = nullptr; size_t win_xtm1_cap = 0; // 'x_t_minus_1' windows: the observed frames re-noised to t - 1, redrawn every step
     unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset}
 
@@ -329,7 +341,7 @@ struct vd_engine {
         if (d_win_t) (void)hipFree(d_win_t);
         if (d_win_rng) (void)hipFree(d_win_rng);
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
-        for (auto& g : win_graphs) free_graph(g);
+        for (auto& g : win_graphs) g.release();
     }
 
     // Captured window graphs bake addresses (workspace, schedule tables, step counters) and values (num_timesteps, rescale)
@@ -338,16 +350,40 @@ struct vd_engine {
     void drop_window_graphs() {
         if (win_graphs.empty()) { win_cur = -1; return; }
         (void)hipDeviceSynchronize();
-        for (auto& g : win_graphs) free_graph(g);
+        for (auto& g : win_graphs) g.release();
         win_graphs.clear();
         win_cur = -1;
+    }
+    // Grow the device buffer p to at least n elements (contents not kept).  With held_by_graphs, captured window graphs point into
+    // it: they are dropped before it moves (a window in flight is lost: vd_window_run then reports "window graphs invalidated").
+    template <class Tp> int grow(Tp*& p, size_t& cap, size_t n, bool held_by_graphs) {
+        if (n <= cap) return 0;
+        if (held_by_graphs && p) { if (win_cur >= 0) win_lost = true; drop_window_graphs(); }
+        if (p) VD_HIP(hipFree(p));
+        p = nullptr; cap = 0;
+        VD_HIP(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(Tp)));
+        cap = n;
+        return 0;
+    }
+    // The workspace of a window shape: the arena peak of its dry run (cached under `key`: the run walks the whole topology),
+    // 256-byte rounded into *tail, plus `extra` bytes of the caller's own buffers behind it
+    template <class DryRun> int grow_ws(long long key, size_t extra, DryRun dry_run, size_t* tail) {
+        if (int rc = rpe_tables()) return rc;
+        auto it = ws_peaks.find(key);
+        if (it == ws_peaks.end()) {
+            size_t peak = 0;
+            if (int rc = dry_run(&peak)) return rc;
+            it = ws_peaks.emplace(key, peak).first;
+        }
+        *tail = (it->second + 255) & ~(size_t)255;
+        return grow(ws, ws_cap, *tail + extra, true);
     }
 
     const float* W(int p) const { return wbuf + params[p].off; }
     void set_w(vd::IgemmArgs& g, int p) const {
         const int k = params[p].kind;
         g.w = g.wfrag = g.wwino = nullptr;
-        if (k == PK_CONV3W) { g.wwino = W(p); g.wsplit = split_conv() ? 2 : 0; }
+        if (k == PK_CONV3W) { g.wwino = W(p); g.wsplit = split_math() ? 2 : 0; }
         else if (k == PK_CONV3WU) { g.wwino = W(p); g.wsplit = 2; g.ups_phase = 1; }
         else if (k == PK_CONV3S) { g.wfrag = W(p); g.wsplit = 1; }
         else if (k == PK_LINF) { g.wfrag = W(p); g.wsplit = split_math(); }
@@ -368,7 +404,7 @@ struct vd_engine {
         if (kind == PK_STEM) p.packed = O * STEM_KPAD;
         if ((kind == PK_STEM || kind == PK_LINF) && split_math()) p.packed = p.packed * 3 / 2 + 2 * O;
         if (kind == PK_CONV3S) p.packed = p.numel * 3 / 2 + 2 * O;
-        if (kind == PK_CONV3W) p.packed = split_conv() ? (size_t)16 * O * p.shape[1] * 3 / 2 + 2 * O : (size_t)16 * O * p.shape[1];
+        if (kind == PK_CONV3W) p.packed = split_math() ? (size_t)16 * O * p.shape[1] * 3 / 2 + 2 * O : (size_t)16 * O * p.shape[1];
         if (kind == PK_CONV3WU) p.packed = (size_t)4 * 16 * O * p.shape[1] * 3 / 2 + 8 * O;
         // output head: [tap][O][I] (out_conv_bwd, the op entry point) + [out_t_cols(O)][I], rows co * 9 + tap: the head as a 1x1 GEMM over
         // (cout, tap) columns followed by a 9-tap gather (misc.hip: out_gather_kernel)
@@ -381,8 +417,7 @@ struct vd_engine {
     int build();
     int forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr);
     int ensure_ws(int B, int T);
-    int res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, const float* emb_unused,
-                  hipStream_t st, Arena& ar, Tens* out);
+    int res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, hipStream_t st, Arena& ar, Tens* out);
     int attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* fidx, const float* amask,
                    hipStream_t st, Arena& ar, Tens* out);
     int gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb, const float* film,
@@ -394,7 +429,7 @@ struct vd_engine {
     int bwd_conv3(Tens dy, int N, int pw, int cout_bwd, const float* res, float* out, hipStream_t st, Arena& ar);
     int ensure_ws_guided(int B, int T);
     const float* WB(int p) const { return wbuf_bwd + params[p].off_bwd; }
-    int linear(const float* a, int M, int K, int pw, int pb, int Nout, const float* wptr, const float* bptr, int act,
+    int linear(const float* a, int M, int K, int Nout, const float* wptr, const float* bptr, int act,
                const float* res, float* out, hipStream_t st, const Tens* stats_of = nullptr);
     void gemm_stats_table(Arena& ar, int M, int K, int Nout, Tens* t);
     void conv_split_stats_table(Arena& ar, const IgemmArgs& conv, int Cout, Tens* t);
@@ -426,7 +461,7 @@ int vd_engine::build() {
     auto k3 = [&](int res_out, int cout) { return res_out >= 8 && cout % 64 == 0 ? (int)PK_CONV3W : (int)PK_CONV3; };
     // backward-data image of a 3x3 stride-1 conv with `co` outputs (= the forward's inputs) and `ci` inputs at resolution rs
     auto k3b = [&](int rs, int co, int ci) {
-        return rs >= 8 && (rs & (rs - 1)) == 0 && co % 64 == 0 && ci % 32 == 0 && split_conv() ? (int)PK_CONV3W : (int)PK_CONV3;
+        return rs >= 8 && (rs & (rs - 1)) == 0 && co % 64 == 0 && ci % 32 == 0 && split_math() ? (int)PK_CONV3W : (int)PK_CONV3;
     };
     auto bwd3 = [&](int p, int rs) { params[p].kind_bwd = k3b(rs, (int)params[p].shape[1], (int)params[p].shape[0]); };
     auto bwdl = [&](int p) { params[p].kind_bwd = PK_LINF; };
@@ -538,7 +573,7 @@ int vd_engine::build() {
                 // Upsample + conv: the sub-pixel form where the split Winograd kernel serves the SOURCE map
                 const int rs_src = cfg.image_size / ds;
                 int kup = k3(2 * rs_src, ch);
-                if (kup == PK_CONV3W && split_conv() && rs_src >= 8 && (rs_src & (rs_src - 1)) == 0 && ch % 64 == 0) kup = PK_CONV3WU;
+                if (kup == PK_CONV3W && split_math() && rs_src >= 8 && (rs_src & (rs_src - 1)) == 0 && ch % 64 == 0) kup = PK_CONV3WU;
                 blk.push_back(Layer{4, add_conv(pre + "." + std::to_string(li++) + ".conv", ch, ch, kup, 2 * rs_src)});
                 ds /= 2;
             }
@@ -631,28 +666,22 @@ void vd_engine::conv_split_stats_table(Arena& ar, const IgemmArgs& conv, int Cou
     t->part = ar.get<double>((size_t)g.nfr * t->split * Cout * 2);
 }
 
-int vd_engine::linear(const float* a, int M, int K, int, int, int Nout, const float* wptr, const float* bptr, int act,
+int vd_engine::linear(const float* a, int M, int K, int Nout, const float* wptr, const float* bptr, int act,
                       const float* resid, float* out, hipStream_t st, const Tens* stats_of) {
-    IgemmArgs g{};
-    g.src0 = a; g.src1 = nullptr; g.C0 = K; g.Cin = K;
-    g.nfr = M; g.Hs = 1; g.Ws = 1; g.ups = 0; g.stride = 1; g.pad = 0; g.ksz = 1; g.Ho = 1; g.Wo = 1;
-    g.w = nullptr; g.wfrag = wptr;           // every nn.Linear weight is stored fragment-major (PK_LINF)
-    g.wsplit = split_math();
-    g.bias = bptr; g.affA = nullptr; g.affB = nullptr; g.act = act;
-    g.res = resid; g.res_ld = Nout; g.fbias = nullptr; g.fbias_ld = 0;
-    g.out = out; g.ldo = Nout; g.Cout = Nout; g.M = M;
+    IgemmArgs g = linear_args(M, K, Nout);
+    g.src0 = a; g.wfrag = wptr;              // every nn.Linear weight is stored fragment-major (PK_LINF)
+    g.bias = bptr; g.act = act; g.res = resid; g.out = out;
     if (stats_of && stats_of->part) { g.stats = stats_of->part; g.stats_split = stats_of->split; g.stats_hw = stats_of->H * stats_of->H; }
     return igemm_p(g, st);
 }
 
-int vd_engine::gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb,
-                       const float* film, int film_ld, hipStream_t st, Arena& ar, float** A, float** Bp, float** mr) {
-    const int HW = x0.H * x0.H, C = x0.C + (x1 ? x1->C : 0);
-    // per-channel partial sums of each source: the table its producer wrote, or one statistics pass over it
+// GroupNorm input of gn_fold / gn_act (x1: the second half of a virtual concat, or null): per-channel partial sums of each source --
+// the table its producer wrote, or one statistics pass over it
+static int gn_partials(const Tens& x0, const Tens* x1, int N, hipStream_t st, Arena& ar, const double* part[2], int split[2]) {
+    const int HW = x0.H * x0.H;
     const Tens* src[2] = {&x0, x1};
-    const double* part[2] = {nullptr, nullptr};
-    int split[2] = {0, 0};
     for (int i = 0; i < 2; ++i) {
+        part[i] = nullptr; split[i] = 0;
         if (!src[i]) continue;
         if (src[i]->part) { part[i] = src[i]->part; split[i] = src[i]->split; continue; }
         split[i] = gn_stats_split(N, HW, src[i]->C);
@@ -663,6 +692,14 @@ int vd_engine::gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb,
         int rc = launch_gn_stats(src[i]->p, nullptr, src[i]->C, src[i]->C, N, HW, pt, split[i], st);
         if (rc) return rc;
     }
+    return 0;
+}
+
+int vd_engine::gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb,
+                       const float* film, int film_ld, hipStream_t st, Arena& ar, float** A, float** Bp, float** mr) {
+    const int HW = x0.H * x0.H, C = x0.C + (x1 ? x1->C : 0);
+    const double* part[2]; int split[2];
+    if (int rc = gn_partials(x0, x1, N, st, ar, part, split)) return rc;
     *A = ar.get<float>((size_t)N * C);
     *Bp = ar.get<float>((size_t)N * C);
     float* mrp = tape && mr ? ar.get<float>((size_t)N * 64) : nullptr;      // group mean / rstd for the backward pass
@@ -675,24 +712,11 @@ int vd_engine::gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb,
 // GroupNorm(+FiLM) + SiLU of a (virtually concatenated) tensor into y in ONE launch: the activation pass folds the statistics
 // itself (norm.hip: affine_act_fold_kernel).  For consumers that need nothing but y; not with a tape (the backward pass reads
 // A, B and mean / rstd).
-static bool gn_fold_fused() { return true; }
 int vd_engine::gn_act(const Tens& x0, const Tens* x1, int N, int gw, int gb, const float* film, int film_ld, int act, float* y,
                       hipStream_t st, Arena& ar) {
     const int HW = x0.H * x0.H, C = x0.C + (x1 ? x1->C : 0);
-    const Tens* src[2] = {&x0, x1};
-    const double* part[2] = {nullptr, nullptr};
-    int split[2] = {0, 0};
-    for (int i = 0; i < 2; ++i) {
-        if (!src[i]) continue;
-        if (src[i]->part) { part[i] = src[i]->part; split[i] = src[i]->split; continue; }
-        split[i] = gn_stats_split(N, HW, src[i]->C);
-        double* pt = ar.get<double>((size_t)N * split[i] * src[i]->C * 2);
-        part[i] = pt;
-        if (ar.dry) continue;
-        ProfScope ps(PC_GN_STATS, 0.0, 4.0 * N * HW * src[i]->C, st);
-        int rc = launch_gn_stats(src[i]->p, nullptr, src[i]->C, src[i]->C, N, HW, pt, split[i], st);
-        if (rc) return rc;
-    }
+    const double* part[2]; int split[2];
+    if (int rc = gn_partials(x0, x1, N, st, ar, part, split)) return rc;
     // Big tensors (the 64 x 64 and 32 x 32 levels of a full window) take the two-launch form: (A, B) per (frame, channel) by
     // gn_final_affine, then the pass on many short blocks -- 5.95 TB/s against the 5.2 of the long blocks the in-kernel fold needs
     // (tools/probes/stream_probe.hip); the 7 us of the extra launch are repaid from ~64 MB on.  Same formulas and fp64 sums; the ORDER of the
@@ -733,20 +757,26 @@ static size_t ksplit_scratch(const Arena& ar, int N, int H, int cin, int cout) {
     return m;
 }
 
-static IgemmArgs conv_args(Tens x0, const Tens* x1, int N, int ksz, int stride, int ups) {
+// the source side of a convolution: nfr frames of Hs x Ws pixels, C0 channels of src0 (+ Cin - C0 of src1, a virtual concat),
+// read through a nearest x2 upsample when ups = 1; the output size and M follow
+static IgemmArgs conv_args(const float* src0, const float* src1, int C0, int Cin, int nfr, int Hs, int Ws, int ups, int stride,
+                           int pad, int ksz) {
     IgemmArgs g{};
-    g.src0 = x0.p; g.C0 = x0.C; g.Cin = x0.C;
-    if (x1) { g.src1 = x1->p; g.Cin += x1->C; }
-    g.nfr = N; g.Hs = x0.H; g.Ws = x0.H; g.ups = ups; g.stride = stride; g.pad = ksz == 3 ? 1 : 0; g.ksz = ksz;
-    g.nfr_sel = g_sel_nfr;
-    const int Hl = x0.H << ups;
-    g.Ho = g.Wo = (Hl + 2 * g.pad - ksz) / stride + 1;
-    g.M = N * g.Ho * g.Wo;
+    g.src0 = src0; g.src1 = src1; g.C0 = C0; g.Cin = Cin;
+    g.nfr = nfr; g.Hs = Hs; g.Ws = Ws; g.ups = ups; g.stride = stride; g.pad = pad; g.ksz = ksz;
+    g.Ho = ((Hs << ups) + 2 * pad - ksz) / stride + 1;
+    g.Wo = ((Ws << ups) + 2 * pad - ksz) / stride + 1;
+    g.M = nfr * g.Ho * g.Wo;
     return g;
 }
 
-int vd_engine::res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, const float*,
-                         hipStream_t st, Arena& ar, Tens* out) {
+static IgemmArgs conv_args(Tens x0, const Tens* x1, int N, int ksz, int stride, int ups) {
+    IgemmArgs g = conv_args(x0.p, x1 ? x1->p : nullptr, x0.C, x0.C + (x1 ? x1->C : 0), N, x0.H, x0.H, ups, stride, ksz == 3 ? 1 : 0, ksz);
+    g.nfr_sel = g_sel_nfr;
+    return g;
+}
+
+int vd_engine::res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, hipStream_t st, Arena& ar, Tens* out) {
     const int H = x0.H, HW = H * H;
     const int cin = x0.C + (x1 ? x1->C : 0);
     VD_REQUIRE(cin == r.cin, "ResBlock input channels");
@@ -770,7 +800,7 @@ int vd_engine::res_block(const ResP& r, Tens x0, const Tens* x1, int N, const fl
     }
     // the statistics folded by the activation pass itself (gn_act) wherever nothing else reads (A, B): not for the skip
     // convolution that writes the image (it takes the pair as arrays), not with a tape
-    const bool fold = !tape && gn_fold_fused();
+    const bool fold = !tape;
     // Where conv_wino_z128.hip takes the convolution and one or two cout blocks share a patch, the GroupNorm(+FiLM) affine + SiLU runs in
     // the kernel's patch staging and the activation image is never written (conv_wino_z128_act_shape): the pair goes in as arrays.  The
     // dry run lays the arena out for both forms (a compact batch may decide differently).
@@ -881,7 +911,7 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* f
         { ProfScope ps(PC_GN_TEMPORAL, 0.0, 8.0 * tok * C, st);
           rc = launch_gn_temporal(x.p, W(a.tp.normw), W(a.tp.normb), B, T, HW, C, xn, st); }
         if (rc) return rc;
-        if ((rc = linear(xn, (int)tok, C, 0, 0, 3 * C, W(a.tp.qkvw), W(a.tp.qkvb), 0, nullptr, qkv, st))) return rc;
+        if ((rc = linear(xn, (int)tok, C, 3 * C, W(a.tp.qkvw), W(a.tp.qkvb), 0, nullptr, qkv, st))) return rc;
         if (!cfg.use_rpe_net)
             for (int i = 0; i < 3; ++i)
                 if ((rc = launch_rpe_table(W(rp[i]->table), fidx, B, T, C, cfg.rp_alpha, cfg.rp_beta, cfg.rp_gamma,
@@ -895,11 +925,11 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* f
         if (!attn_cap_t.empty() && attn_seq < (int)attn_cap_t.size() && attn_cap_t[attn_seq] &&
             (rc = launch_attn_temporal_weights(ta, attn_cap_t[attn_seq], st))) return rc;
         // proj_out + residual on the NORMALISED activations (unet.py:537-538)
-        if ((rc = linear(o, (int)tok, C, 0, 0, C, W(a.tp.projw), W(a.tp.projb), 0, xn, xt, st, &xt_t))) return rc;
+        if ((rc = linear(o, (int)tok, C, C, W(a.tp.projw), W(a.tp.projb), 0, xn, xt, st, &xt_t))) return rc;
     }
     // ---- spatial attention over the HW pixels of each frame               (unet.py:258-267)
     float *A = nullptr, *Bf = nullptr, *mrs = nullptr;
-    const bool fold = !tape && gn_fold_fused();
+    const bool fold = !tape;
     if (!fold && (rc = gn_fold(xt_t, nullptr, N, a.sp.normw, a.sp.normb, nullptr, 0, st, ar, &A, &Bf, &mrs))) return rc;
     float* xn2 = ar.get<float>(tok * C);
     float* qkv2 = ar.get<float>(tok * 3 * C);
@@ -911,13 +941,13 @@ int vd_engine::attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* f
     if (!ar.dry) {
         if (!fold) { ProfScope ps(PC_ELEMENTWISE, 0.0, 8.0 * tok * C, st); rc = launch_affine_apply(xt, A, Bf, N, HW, C, xn2, st); }
         if (rc) return rc;
-        if ((rc = linear(xn2, (int)tok, C, 0, 0, 3 * C, W(a.sp.qkvw), W(a.sp.qkvb), 0, nullptr, qkv2, st))) return rc;
+        if ((rc = linear(xn2, (int)tok, C, 3 * C, W(a.sp.qkvw), W(a.sp.qkvb), 0, nullptr, qkv2, st))) return rc;
         AttnSpatialArgs sa{qkv2, o2, N, HW, C, cfg.num_heads, scale};
         { ProfScope ps(PC_ATTN_SPATIAL, 4.0 * N * (double)HW * HW * C, 16.0 * tok * C, st); rc = launch_attn_spatial(sa, st); }
         if (rc) return rc;
         if (!attn_cap_s.empty() && attn_seq < (int)attn_cap_s.size() && attn_cap_s[attn_seq] &&
             (rc = launch_attn_spatial_weights(sa, attn_cap_s[attn_seq], st))) return rc;
-        if ((rc = linear(o2, (int)tok, C, 0, 0, C, W(a.sp.projw), W(a.sp.projb), 0, xn2, xs, st, &xs_t))) return rc;
+        if ((rc = linear(o2, (int)tok, C, C, W(a.sp.projw), W(a.sp.projb), 0, xn2, xs, st, &xs_t))) return rc;
     }
     *out = xs_t;
     if (!ar.dry) ++attn_seq;
@@ -988,10 +1018,9 @@ int vd_engine::rpe_all(const float* te, const int64_t* fidx, int B, int T, hipSt
         if (ar.dry) continue;
         VD_REQUIRE(g.d_hid && g.d_out, "rpe_all: offset tables missing (ensure_ws builds them)");
         if ((rc = launch_rpe_hidden_tab(te, te_total, wbuf, g.d_hid, fidx, B, T, C, Eh, nn, rrows * C, st))) return rc;
-        IgemmArgs q{};
-        q.src0 = Eh; q.C0 = C; q.Cin = C; q.nfr = (int)rrows; q.Hs = q.Ws = q.Ho = q.Wo = 1; q.stride = 1; q.ksz = 1;
+        IgemmArgs q = linear_args((int)rrows, C, C);
+        q.src0 = Eh; q.out = Rg;
         q.wfrag = wbuf + params[attn[g.blocks[0]].rq.ow].off; q.bias = wbuf + params[attn[g.blocks[0]].rq.ob].off;   // (problem 0's: the shape checks read them)
-        q.wsplit = split_math(); q.out = Rg; q.ldo = C; q.Cout = C; q.M = (int)rrows;
         q.zcount = nn; q.zs_a = q.zs_out = (int)(rrows * C); q.ztab = g.d_out; q.zbase = wbuf;
         if ((rc = igemm_p(q, st))) return rc;
     }
@@ -1026,12 +1055,12 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
         }
         if ((rc = launch_assemble(aa, st))) return rc;
         if ((rc = launch_sinus_embed(tfr, N, mc, d_freq_time, tsin, st))) return rc;
-        if ((rc = linear(tsin, N, mc, 0, 0, E, W(p_te0w), W(p_te0b), 0, nullptr, e1, st))) return rc;
-        if ((rc = linear(e1, N, E, 0, 0, E, W(p_te2w), W(p_te2b), 1, nullptr, emb, st))) return rc;
+        if ((rc = linear(tsin, N, mc, E, W(p_te0w), W(p_te0b), 0, nullptr, e1, st))) return rc;
+        if ((rc = linear(e1, N, E, E, W(p_te2w), W(p_te2b), 1, nullptr, emb, st))) return rc;
         // every ResBlock's emb_layers (SiLU -> Linear, unet.py:143-150) in ONE GEMM; same for RPENet's
         // embed_diffusion_time (no SiLU, unet.py:294)
-        if ((rc = linear(emb, N, E, 0, 0, film_total, wbuf + film_w_off, wbuf + film_b_off, 1, nullptr, film, st))) return rc;
-        if (te_total && (rc = linear(emb, N, E, 0, 0, te_total, wbuf + te_w_off, wbuf + te_b_off, 0, nullptr, te, st))) return rc;
+        if ((rc = linear(emb, N, E, film_total, wbuf + film_w_off, wbuf + film_b_off, 1, nullptr, film, st))) return rc;
+        if (te_total && (rc = linear(emb, N, E, te_total, wbuf + te_w_off, wbuf + te_b_off, 0, nullptr, te, st))) return rc;
         if (cfg.use_frame_encoding) {
             VD_REQUIRE(d_freq_frame && n_freq_frame == pos_ch / 2, "vd_set_freqs not called (frame frequencies)");
             if ((rc = launch_frame_t(in.fidx, B, T, cfg.enforce_position_invariance, ftv, st))) return rc;
@@ -1060,7 +1089,7 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
             const Layer& L = blk[li];
             Tens nxt{};
             if (L.type == 1) {
-                if ((rc = res_block(res[L.idx], cur, second, N, film, nullptr, st, ar, &nxt))) return rc;
+                if ((rc = res_block(res[L.idx], cur, second, N, film, st, ar, &nxt))) return rc;
             } else if (L.type == 2) {
                 if ((rc = attn_block(attn[L.idx], cur, B, T, in.fidx, amask, st, ar, &nxt))) return rc;
             } else if (L.type == 0) {                                 // stem: im2col (assemble_kernel) x [64][mc] GEMM
@@ -1068,7 +1097,7 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
                 float* o = ar.get<float>((size_t)N * S * S * c.c);
                 nxt = Tens{o, c.c, S};
                 gemm_stats_table(ar, N * S * S, STEM_KPAD, c.c, &nxt);
-                if (!ar.dry && (rc = linear(cur.p, N * S * S, STEM_KPAD, 0, 0, c.c, W(c.w), W(c.b), 0, nullptr, o, st, &nxt))) return rc;
+                if (!ar.dry && (rc = linear(cur.p, N * S * S, STEM_KPAD, c.c, W(c.w), W(c.b), 0, nullptr, o, st, &nxt))) return rc;
                 if (tape) { tape->ops.push_back(TapeOp{0, (int)tape->conv.size()}); tape->conv.push_back(TapeConv{0, L.idx, cur, nxt}); }
             } else {
                 const ConvP& c = convs[L.idx];
@@ -1217,36 +1246,23 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
 
 int vd_engine::ensure_ws(int B, int T) {
     if (B == ws_B && T == ws_T && ws && ws_suf == suffix_skip_on) return 0;      // the common case: every step of a window
-    { const int trc = rpe_tables(); if (trc) return trc; }
     // with the window suffix skip enabled the arena also holds the gathered skip tensors: sized for the worst list (every frame)
     const long long key = ((long long)B << 32) | (unsigned)T | (suffix_skip_on ? 1ll << 61 : 0);
-    auto it = ws_peaks.find(key);
-    if (it == ws_peaks.end()) {
+    size_t tail = 0;
+    int rc = grow_ws(key, step_tail_bytes(B, T), [&](size_t* peak) {
         Arena dry; dry.dry = true;
         FwdIn fi{}; fi.B = B; fi.T = T;
-        int rc = forward(fi, nullptr, dry);
-        if (!rc && suffix_skip_on) {
+        int frc = forward(fi, nullptr, dry);
+        if (!frc && suffix_skip_on) {
             Arena dry2; dry2.dry = true;
             SuffixPlan wp; wp.n = B * T;
-            rc = forward(fi, nullptr, dry2, nullptr, &wp);
+            frc = forward(fi, nullptr, dry2, nullptr, &wp);
             dry.peak = std::max(dry.peak, dry2.peak);
         }
-        if (rc) return rc;
-        it = ws_peaks.emplace(key, dry.peak).first;
-    }
-    const size_t tail = (it->second + 255) & ~(size_t)255;
-    const size_t tm_bytes = ((size_t)B * sizeof(float) + 255) & ~(size_t)255;
-    const size_t need = tail + tm_bytes + (size_t)B * T * (cfg.learn_sigma ? 6 : 3) * cfg.image_size * cfg.image_size * sizeof(float);
-    if (need > ws_cap) {
-        // captured window graphs hold addresses inside the old workspace: they die with it (a window in flight is lost:
-        // vd_window_run then reports "window graphs invalidated")
-        if (win_cur >= 0) win_lost = true;
-        drop_window_graphs();
-        if (ws) VD_HIP(hipFree(ws));
-        ws = nullptr; ws_cap = 0; ws_B = ws_T = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&ws), need));
-        ws_cap = need;
-    }
+        *peak = dry.peak;
+        return frc;
+    }, &tail);
+    if (rc) return rc;
     ws_B = B; ws_T = T; ws_tail = tail; ws_suf = suffix_skip_on;
     return 0;
 }
@@ -1274,7 +1290,7 @@ struct GradMap {
 // out[M][K_fwd] = dy[M][N_fwd] * W  (+ res): the forward's split GEMM over the transposed image of parameter pw
 int vd_engine::bwd_linear(const float* dy, int M, int pw, const float* resid, float* out, hipStream_t st) {
     const Param& p = params[pw];
-    const int Kb = p.kind == PK_STEM ? (int)p.shape[0] : (int)p.shape[0], Nb = p.kind == PK_STEM ? STEM_KPAD : (int)p.shape[1];
+    const int Kb = (int)p.shape[0], Nb = p.kind == PK_STEM ? STEM_KPAD : (int)p.shape[1];
     IgemmArgs g = linear_args(M, Kb, Nb);
     g.src0 = dy; g.wfrag = WB(pw); g.wsplit = 1; g.res = resid; g.out = out;
     VD_REQUIRE(gemm_split_supported(g), "backward linear layer: shape not covered by gemm_split.hip");
@@ -1425,32 +1441,32 @@ int vd_engine::backward(const FwdIn& in, const float* deps, float* dx, hipStream
 
 // workspace of a guided step: forward (taped, nothing released that the backward reads) + backward + the step's own buffers
 int vd_engine::ensure_ws_guided(int B, int T) {
-    { const int trc = rpe_tables(); if (trc) return trc; }
     const long long key = ((long long)B << 32) | (unsigned)T | (1ll << 62);
-    auto it = ws_peaks.find(key);
-    if (it == ws_peaks.end()) {
+    const size_t per = (size_t)B * T * 3 * cfg.image_size * cfg.image_size * sizeof(float);
+    size_t tail = 0;
+    int rc = grow_ws(key, 4096 + 8 * per, [&](size_t* peak) {
         Arena dry; dry.dry = true;
         Tape tp; tape = &tp;
         FwdIn fi{}; fi.B = B; fi.T = T;
-        int rc = forward(fi, nullptr, dry);
-        if (!rc) rc = backward(fi, nullptr, nullptr, nullptr, dry);
+        int frc = forward(fi, nullptr, dry);
+        if (!frc) frc = backward(fi, nullptr, nullptr, nullptr, dry);
         tape = nullptr;
-        if (rc) return rc;
-        it = ws_peaks.emplace(key, dry.peak).first;
-    }
-    const size_t per = (size_t)B * T * 3 * cfg.image_size * cfg.image_size * sizeof(float);
-    const size_t need = ((it->second + 255) & ~(size_t)255) + 4096 + 8 * per;
-    if (need > ws_cap) {
-        if (win_cur >= 0) win_lost = true;
-        drop_window_graphs();
-        if (ws) VD_HIP(hipFree(ws));
-        ws = nullptr; ws_cap = 0; ws_B = ws_T = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&ws), need));
-        ws_cap = need;
-    }
+        *peak = dry.peak;
+        return frc;
+    }, &tail);
+    if (rc) return rc;
     ws_B = ws_T = 0;                       // the plain step recomputes its tail offsets on its next call
     return 0;
 }
+
+// device workspace of one operator call: released once the call's launches have run
+struct OpScratch {
+    hipStream_t st;
+    std::vector<void*> bufs;
+    explicit OpScratch(void* stream) : st(static_cast<hipStream_t>(stream)) {}
+    template <class Tp> int get(Tp** p, size_t n) { VD_HIP(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(Tp))); bufs.push_back(*p); return 0; }
+    ~OpScratch() { if (!bufs.empty()) (void)hipStreamSynchronize(st); for (void* p : bufs) (void)hipFree(p); }
+};
 
 // ------------------------------------------------------------------------------------------ C ABI
 extern "C" {
@@ -1569,7 +1585,7 @@ int vd_load_weight(vd_engine* e, const char* name, const float* host, long long 
         p.loaded = true;
         return 0;
     }
-    if (p.kind == PK_CONV3W && split_conv()) {
+    if (p.kind == PK_CONV3W && split_math()) {
         tmp.resize(p.packed);
         pack_conv3_wino_split(host, reinterpret_cast<unsigned short*>(tmp.data()), (int)p.shape[0], (int)p.shape[1]);
         src = tmp.data();
@@ -1719,6 +1735,18 @@ static int check_ready(vd_engine* e, int B, int T) {
     return 0;
 }
 
+// the opening checks of the sampler entry points (vd_p_sample / vd_ddim_sample / vd_p_mean_variance / vd_window_begin): their
+// steps end in the 3-channel posterior kernel, which a 6-channel network output must never reach
+static int check_sampler(vd_engine* e, int B, int T, int obs_mode, int max_obs_mode, const char* obs_modes) {
+    int rc = check_ready(e, B, T);
+    if (rc) return rc;
+    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(obs_mode >= 0 && obs_mode <= max_obs_mode, obs_modes);
+    VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283: model_output.shape == (B, 2*T, ...)); only the network forward is served");
+    return 0;
+}
+static const char* const kObsModes = "observed_frames must be x_0 / x_t / x_t_minus_1";
+
 int vd_max_window_frames(void) { return kMaxWindowFrames; }
 
 int vd_unet_forward(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs,
@@ -1727,9 +1755,9 @@ int vd_unet_forward(vd_engine* e, int B, int T, const float* x, const float* obs
     int rc = check_ready(e, B, T);
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t_model && eps, "null tensor");
-    VD_REQUIRE(obs_mode >= 0 && obs_mode <= 2, "observed_frames must be x_0 / x_t / x_t_minus_1");
+    VD_REQUIRE(obs_mode >= 0 && obs_mode <= 2, kObsModes);
     if ((rc = e->ensure_ws(B, T))) return rc;
-    Arena ar; ar.base = e->ws; ar.cap = e->ws_tail;                   // the activations end where t_model and the eps scratch begin
+    Arena ar = e->step_arena();
     FwdIn fi{B, T, x, obs_src, obs, lat, km, t_model, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
     return e->forward(fi, static_cast<hipStream_t>(stream), ar);
 }
@@ -1750,6 +1778,11 @@ __global__ void map_t_kernel(const int64_t* t, const float* tmap, float rescale,
     }
 }
 
+static void map_t(const vd_engine* e, const long long* t, int B, float* tm, hipStream_t st) {
+    hipLaunchKernelGGL(map_t_kernel, dim3((B + 63) / 64), dim3(64), 0, st, reinterpret_cast<const int64_t*>(t), e->d_tmap,
+                       e->rescale, B, e->num_timesteps, tm, e->d_err);
+}
+
 // One denoise step on `st`: t -> t_model, UNet forward, posterior update.  `t` and (when rng != null) the Philox
 // {seed, offset} are read from device memory, so the same launch sequence serves every step of a window (executor).
 static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
@@ -1758,16 +1791,11 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
                          const unsigned long long* rng, float* sample, float* xstart, float* mean, float* eps_out,
                          hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr) {
     int rc;
-    // every sampler entry point comes through here (vd_p_sample / vd_ddim_sample / vd_p_mean_variance / the window executor): a
-    // 6-channel network output must never reach the 3-channel posterior kernel
-    VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283: model_output.shape == (B, 2*T, ...)); only the network forward is served");
     const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
-    // tail of the workspace: t_model [B] + eps scratch (sized by ensure_ws for this B)
-    float* tm = reinterpret_cast<float*>(e->ws + e->ws_tail);
-    float* eps = eps_out ? eps_out : reinterpret_cast<float*>(e->ws + e->ws_tail + (((size_t)B * sizeof(float) + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(map_t_kernel, dim3((B + 63) / 64), dim3(64), 0, st, reinterpret_cast<const int64_t*>(t), e->d_tmap,
-                       e->rescale, B, e->num_timesteps, tm, e->d_err);
-    Arena ar; ar.base = e->ws; ar.cap = e->ws_tail;                   // the activations end where t_model and the eps scratch begin
+    float* tm = e->step_tm();
+    float* eps = eps_out ? eps_out : e->step_eps(B);
+    map_t(e, t, B, tm, st);
+    Arena ar = e->step_arena();
     FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
     if ((rc = e->forward(fi, st, ar, pp, sp))) return rc;
     PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
@@ -1782,13 +1810,10 @@ static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, con
                        const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
                        int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
                        float* sample, float* xstart, float* eps_out, void* stream) {
-    int rc = check_ready(e, B, T);
+    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
     if (rc) return rc;
-    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && sample, "null tensor");
-    VD_REQUIRE(obs_mode >= 0 && obs_mode <= 2, "observed_frames must be x_0 / x_t / x_t_minus_1");
     VD_REQUIRE(mode == 0 || eta >= 0.f, "eta");
-    VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283: model_output.shape == (B, 2*T, ...)); only the network forward is served");
     if ((rc = e->ensure_ws(B, T))) return rc;
     return step_launches(e, mode, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, nullptr,
                          sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream));
@@ -1797,23 +1822,12 @@ static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, con
 int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                        const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float* mean,
                        float* xstart, float* eps, void* stream) {
-    int rc = check_ready(e, B, T);
+    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
     if (rc) return rc;
-    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && (mean || xstart || eps), "null tensor");
-    VD_REQUIRE(obs_mode >= 0 && obs_mode <= 2, "observed_frames must be x_0 / x_t / x_t_minus_1");
     if ((rc = e->ensure_ws(B, T))) return rc;
     return step_launches(e, 0, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, nullptr, nullptr,
                          xstart, mean, eps, static_cast<hipStream_t>(stream));
-}
-
-static int ensure_part(vd_engine* e, size_t doubles) {
-    if (doubles <= e->part_cap) return 0;
-    if (e->d_part) VD_HIP(hipFree(e->d_part));
-    e->d_part = nullptr; e->part_cap = 0;
-    VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_part), doubles * sizeof(double)));
-    e->part_cap = doubles;
-    return 0;
 }
 
 int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x_t, const float* eps, const float* noise,
@@ -1824,7 +1838,7 @@ int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x
     VD_REQUIRE(mse == nullptr || noise != nullptr, "mse needs the noise x_t was drawn with");
     const long per = (long)T * 3 * e->cfg.image_size * e->cfg.image_size;
     const int nblk = vb_terms_blocks(per);
-    int rc = ensure_part(e, (size_t)B * nblk * 3);
+    int rc = e->grow(e->d_part, e->part_cap, (size_t)B * nblk * 3, false);
     if (rc) return rc;
     VbArgs a{x_start, x_t, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, latent_mask, B, T, per,
              clip, pred_xstart, e->d_part, nblk, vb, xstart_mse, mse};
@@ -1838,7 +1852,7 @@ int vd_prior_bpd(vd_engine* e, int B, int T, const float* x_start, const float* 
     VD_REQUIRE(B > 0 && T > 0 && x_start && out, "arguments");
     const long per = (long)T * 3 * e->cfg.image_size * e->cfg.image_size;
     const int nblk = vb_terms_blocks(per);
-    int rc = ensure_part(e, (size_t)B * nblk * 3);
+    int rc = e->grow(e->d_part, e->part_cap, (size_t)B * nblk * 3, false);
     if (rc) return rc;
     return launch_prior_bpd(x_start, latent_mask, e->d_tab, e->num_timesteps, B, T, per, e->d_part, nblk, out,
                             static_cast<hipStream_t>(stream));
@@ -1862,43 +1876,147 @@ __global__ void win_advance_kernel(long long* t, unsigned long long* rng, int B,
     if (b == 0) rng[1] += draws;
 }
 
+// ---- the steps of vd_window_begin
+// the executor's device state for a window of B entries: the step counters, the Philox pair and, in 'x_t_minus_1' mode, the
+// observed frames re-noised to t - 1 (per: floats of one entry)
+static int window_buffers(vd_engine* e, int B, int obs_mode, size_t per) {
+    int rc = e->grow(e->d_win_t, e->win_t_cap, (size_t)B, true);
+    if (rc) return rc;
+    if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 2 * sizeof(unsigned long long)));
+    return obs_mode == 2 ? e->grow(e->d_win_xtm1, e->win_xtm1_cap, (size_t)B * per, true) : 0;
+}
+
+// the frames whose network input cannot change during the window: pure observations (obs = 1, lat = 0); inv stays empty if none is
+static int invariant_frames(const float* obs, const float* lat, int N, hipStream_t st, std::vector<unsigned char>* inv, int* n_inv) {
+    std::vector<float> hm(2 * (size_t)N);
+    VD_HIP(hipMemcpyAsync(hm.data(), obs, N * sizeof(float), hipMemcpyDeviceToHost, st));
+    VD_HIP(hipMemcpyAsync(hm.data() + N, lat, N * sizeof(float), hipMemcpyDeviceToHost, st));
+    VD_HIP(hipStreamSynchronize(st));
+    inv->resize(N);
+    for (int n = 0; n < N; ++n) { (*inv)[n] = hm[n] == 1.f && hm[N + n] == 0.f; *n_inv += (*inv)[n]; }
+    if (*n_inv == 0) inv->clear();
+    return 0;
+}
+
+static int find_window_graph(const vd_engine* e, const vd_engine::WinKey& key, const std::vector<unsigned char>& inv) {
+    for (size_t i = 0; i < e->win_graphs.size(); ++i)
+        if (e->win_graphs[i].key == key && e->win_graphs[i].inv == inv) return (int)i;
+    return -1;
+}
+
+// 'x_t_minus_1' (gaussian_diffusion.py:565-568): obs_src holds the CLEAN observed frames x0; every step first draws
+// x_t_minus_1 = q_sample(x0, t - 1) into the engine's buffer (the second half of the step's Philox range), the network reads that
+static int renoise_observed(const vd_engine* e, const vd_engine::WinKey& k, hipStream_t st) {
+    if (k.obs_mode != 2) return 0;
+    const size_t per = (size_t)k.T * 3 * e->cfg.image_size * e->cfg.image_size;
+    return launch_q_sample_prev(k.obs_src, reinterpret_cast<const int64_t*>(e->d_win_t), e->d_tab, e->num_timesteps, k.B, (long)per,
+                                e->d_win_rng, (unsigned long long)k.B * per / 2, e->d_win_xtm1, st);
+}
+
+// the invariant frames' prefix, eagerly, into the graph's store (the window prefix cache is per window: its first pass, and again on
+// every window that reuses the graph -- same buffers, possibly new contents)
+static int prefix_build_pass(vd_engine* e, const vd_engine::WinKey& k, const vd_engine::WinGraph& g, hipStream_t st) {
+    float* tm = e->step_tm();
+    map_t(e, e->d_win_t, k.B, tm, st);
+    Arena ar = e->step_arena();
+    FwdIn fi{k.B, k.T, k.x, k.obs_src, k.obs, k.lat, k.km, tm, reinterpret_cast<const int64_t*>(k.fidx), k.obs_mode, e->step_eps(k.B)};
+    PrefixPlan bp; bp.n = g.n_inv; bp.list = g.d_lists + (k.B * k.T - g.n_inv); bp.build_only = true; bp.store = g.store;
+    ProfPause pause;
+    return e->forward(fi, st, ar, &bp);
+}
+
+// A new signature.  Everything a launch needs lazily (kernel attributes, CU count, the workspace) is set up by one eager forward
+// into the eps scratch before the capture; x is not touched by it.
+static int warmup_forward(vd_engine* e, const vd_engine::WinKey& k, const float* net_obs_src, int net_mode, hipStream_t st) {
+    float* tm = e->step_tm();
+    map_t(e, e->d_win_t, k.B, tm, st);
+    Arena ar = e->step_arena();
+    int rc = renoise_observed(e, k, st);
+    if (rc) return rc;
+    FwdIn fi{k.B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, tm, reinterpret_cast<const int64_t*>(k.fidx), net_mode, e->step_eps(k.B)};
+    if ((rc = e->forward(fi, st, ar))) return rc;
+    VD_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// One step of the window as a new graph (prefix cache: after the first pass over the invariant frames), cached as the current window.
+// The graph under construction owns its device lists and prefix store: every error return releases them.
+static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::vector<unsigned char>& inv, int n_inv,
+                          const float* net_obs_src, int net_mode, hipStream_t st) {
+    const int B = k.B, N = B * k.T;
+    const bool pre_on = k.flags & 1, suf_on = k.flags & 2;
+    const size_t per = (size_t)k.T * 3 * e->cfg.image_size * e->cfg.image_size;
+    ProfPause pause;                                            // no event records inside a capture
+    vd_engine::WinGraph wg{};
+    struct Owner { vd_engine::WinGraph* g; ~Owner() { if (g) g->release(); } } owner{&wg};
+    wg.key = k; wg.inv = inv; wg.n_inv = n_inv;
+    PrefixPlan plan;
+    SuffixPlan splan;
+    if (pre_on || suf_on) {
+        std::vector<int> lists;
+        for (int n = 0; n < N; ++n) if (!inv[n]) lists.push_back(n);
+        for (int n = 0; n < N; ++n) if (inv[n]) lists.push_back(n);
+        VD_HIP(hipMalloc(reinterpret_cast<void**>(&wg.d_lists), N * sizeof(int)));
+        VD_HIP(hipMemcpy(wg.d_lists, lists.data(), N * sizeof(int), hipMemcpyHostToDevice));
+        wg.n_suf = suf_on ? N - n_inv : 0;
+        splan.n = N - n_inv; splan.list = wg.d_lists;
+    }
+    int rc;
+    if (pre_on) {
+        wg.store = new PrefixStore();
+        rc = prefix_build_pass(e, k, wg, st);
+        if (!rc && hipStreamSynchronize(st) != hipSuccess) { set_error("prefix cache: first pass"); rc = -2; }
+        if (rc) return rc;
+        plan.n = N - n_inv; plan.list = wg.d_lists; plan.store = wg.store;
+    }
+    VD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    rc = renoise_observed(e, k, st);
+    if (!rc) rc = step_launches(e, k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta,
+                                nullptr, 0, 0, e->d_win_rng, k.x, nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
+                                suf_on ? &splan : nullptr);
+    if (!rc) {
+        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B,
+                           (unsigned long long)B * per);
+        if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
+    }
+    const hipError_t ce = hipStreamEndCapture(st, &wg.graph);
+    if (rc) return rc;
+    if (ce != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce)); return -2; }
+    hipGraphExec_t exec = nullptr;
+    if (hipGraphInstantiate(&exec, wg.graph, nullptr, nullptr, 0) != hipSuccess) { set_error("hipGraphInstantiate"); return -2; }
+    wg.exec = exec;
+    if (wg.store) {
+        // a prefix store holds full-size copies of every tensor before the first attention layer (over 1 GB per block at 128x128,
+        // N = 160): sampling modes whose observed-frame pattern changes from window to window (hierarchy, adaptive, mixed) would
+        // grow device memory without bound (ADVICE r3).  At most four graphs keep a store; the oldest one goes first.
+        int cnt = 0, oldest = -1;
+        for (size_t i = 0; i < e->win_graphs.size(); ++i) if (e->win_graphs[i].store) { ++cnt; if (oldest < 0) oldest = (int)i; }
+        if (cnt >= 4) {
+            (void)hipDeviceSynchronize();                       // its graph may still be queued on the executor's stream
+            e->win_graphs[oldest].release();
+            e->win_graphs.erase(e->win_graphs.begin() + oldest);
+        }
+    }
+    e->win_graphs.push_back(wg);
+    owner.g = nullptr;
+    e->win_cur = (int)e->win_graphs.size() - 1;
+    return 0;
+}
+
 int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, const float* obs, const float* lat,
                     const float* km, const long long* fidx, int obs_mode, int sampler, int clip, float eta,
                     unsigned long long seed, unsigned long long offset, long long t_start, void* stream) {
-    int rc = check_ready(e, B, T);
-    if (rc) return rc;
-    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(obs_mode >= 0 && obs_mode <= 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     // 3 = 'x_t_minus_1' with the caller's tensor read as it is at every step -- what scripts/video_sample.py:149-166 does (it hands x0 as a
     // clean placeholder); 2 = p_sample_loop's form, which re-noises the clean frames to t - 1 before each step (gaussian_diffusion.py:565-568)
-    const int net_mode = obs_mode == 3 ? 2 : obs_mode;
+    int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
+    if (rc) return rc;
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
     VD_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 p_sample, 1 ddim_sample");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = e->ensure_ws(B, T))) return rc;
-    if (B > e->win_t_cap) {
-        e->drop_window_graphs();                                // captured graphs hold the old counter address
-        if (e->d_win_t) VD_HIP(hipFree(e->d_win_t));
-        e->d_win_t = nullptr; e->win_t_cap = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_t), (size_t)B * sizeof(long long)));
-        e->win_t_cap = B;
-    }
-    if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 2 * sizeof(unsigned long long)));
-    const size_t per_w = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
-    if (obs_mode == 2 && (size_t)B * per_w > e->win_xtm1_cap) {
-        if (e->d_win_xtm1) {                                    // captured graphs hold the old buffer's address
-            e->drop_window_graphs();
-            VD_HIP(hipFree(e->d_win_xtm1));
-        }
-        e->d_win_xtm1 = nullptr; e->win_xtm1_cap = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_xtm1), (size_t)B * per_w * sizeof(float)));
-        e->win_xtm1_cap = (size_t)B * per_w;
-    }
-    // 'x_t_minus_1' (gaussian_diffusion.py:565-568): obs_src holds the CLEAN observed frames x0; every step first draws
-    // x_t_minus_1 = q_sample(x0, t - 1) into the engine's buffer (the second half of the step's Philox range), the network reads that
-    const float* net_obs_src = obs_mode == 2 ? e->d_win_xtm1 : obs_src;
+    if ((rc = window_buffers(e, B, obs_mode, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
     hipLaunchKernelGGL(win_set_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, t_start, seed, offset);
     VD_HIP(hipGetLastError());
     vd_engine::WinKey key;
@@ -1911,120 +2029,27 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     e->win_left = t_start + 1;
     // window prefix cache (opt-in): the frames whose network input cannot change during the window -- observed (obs = 1,
     // lat = 0) in 'x_0' mode with the default 'channel' conditioning (assemble_kernel: v = obs_src, indicator channels,
-    // timestep 0) -- run the blocks before the first attention layer ONCE, now; the captured step runs them on the others
-    const int N = B * T;
-    std::vector<unsigned char> inv;
-    int n_inv = 0;
-    // window suffix skip (opt-in): the same frames -- pure observations -- are not read back by the caller and re-enter the
+    // timestep 0) -- run the blocks before the first attention layer ONCE, now; the captured step runs them on the others.
+    // Window suffix skip (opt-in): the same frames -- pure observations -- are not read back by the caller and re-enter the
     // network as the observation ('x_0', 'x_t_minus_1'; NOT 'x_t', where an observed frame's input is its own running sample):
     // everything behind the last attention layer runs without them
+    const int N = B * T;
     const bool use_pre = e->prefix_cache_on && obs_mode == 0 && e->cfg.cond_emb_type == 0 && e->n_before_attn > 0;
     const bool want_suf = e->suffix_skip_on && obs_mode != 1 && e->cfg.cond_emb_type == 0 && e->suf_blk >= -1 && !e->attn.empty();
-    if (use_pre || want_suf) {
-        std::vector<float> hm(2 * (size_t)N);
-        VD_HIP(hipMemcpyAsync(hm.data(), obs, N * sizeof(float), hipMemcpyDeviceToHost, st));
-        VD_HIP(hipMemcpyAsync(hm.data() + N, lat, N * sizeof(float), hipMemcpyDeviceToHost, st));
-        VD_HIP(hipStreamSynchronize(st));
-        inv.resize(N);
-        for (int n = 0; n < N; ++n) { inv[n] = hm[n] == 1.f && hm[N + n] == 0.f; n_inv += inv[n]; }
-        if (n_inv == 0) inv.clear();
-    }
+    std::vector<unsigned char> inv;
+    int n_inv = 0;
+    if ((use_pre || want_suf) && (rc = invariant_frames(obs, lat, N, st, &inv, &n_inv))) return rc;
     const bool pre_on = use_pre && n_inv > 0, suf_on = want_suf && n_inv > 0 && n_inv < N;
     key.flags = (pre_on ? 1 : 0) | (suf_on ? 2 : 0);
-    auto build_pass = [&](vd_engine::WinGraph& g) -> int {               // the invariant frames' prefix, eagerly, into the store
-        float* tm = reinterpret_cast<float*>(e->ws + e->ws_tail);
-        float* eps = reinterpret_cast<float*>(e->ws + e->ws_tail + (((size_t)B * sizeof(float) + 255) & ~(size_t)255));
-        hipLaunchKernelGGL(map_t_kernel, dim3((B + 63) / 64), dim3(64), 0, st, reinterpret_cast<const int64_t*>(e->d_win_t),
-                           e->d_tmap, e->rescale, B, e->num_timesteps, tm, e->d_err);
-        Arena ar; ar.base = e->ws; ar.cap = e->ws_tail;                   // the activations end where t_model and the eps scratch begin
-        FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
-        PrefixPlan bp; bp.n = g.n_inv; bp.list = g.d_lists + (N - g.n_inv); bp.build_only = true; bp.store = g.store;
-        const bool prof = g_prof.on;
-        g_prof.on = false;
-        const int brc = e->forward(fi, st, ar, &bp);
-        g_prof.on = prof;
-        return brc;
-    };
-    for (size_t i = 0; i < e->win_graphs.size(); ++i)
-        if (e->win_graphs[i].key == key && e->win_graphs[i].inv == inv) {
-            e->win_cur = (int)i;
-            return pre_on ? build_pass(e->win_graphs[i]) : 0;          // same buffers, possibly new contents: the cache is per window
-        }
-    // A new signature.  Everything a launch needs lazily (kernel attributes, CU count, the workspace) is set up by one
-    // eager forward into the eps scratch before the capture; x is not touched by it.
-    {
-        float* tm = reinterpret_cast<float*>(e->ws + e->ws_tail);
-        float* eps = reinterpret_cast<float*>(e->ws + e->ws_tail + (((size_t)B * sizeof(float) + 255) & ~(size_t)255));
-        hipLaunchKernelGGL(map_t_kernel, dim3((B + 63) / 64), dim3(64), 0, st, reinterpret_cast<const int64_t*>(e->d_win_t),
-                           e->d_tmap, e->rescale, B, e->num_timesteps, tm, e->d_err);
-        Arena ar; ar.base = e->ws; ar.cap = e->ws_tail;                   // the activations end where t_model and the eps scratch begin
-        if (obs_mode == 2 && (rc = launch_q_sample_prev(obs_src, reinterpret_cast<const int64_t*>(e->d_win_t), e->d_tab, e->num_timesteps, B, (long)per_w,
-                                                        e->d_win_rng, (unsigned long long)B * per_w / 2, e->d_win_xtm1, st))) return rc;
-        FwdIn fi{B, T, x, net_obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), net_mode, eps};
-        if ((rc = e->forward(fi, st, ar))) return rc;
-        VD_HIP(hipStreamSynchronize(st));
+    const int hit = find_window_graph(e, key, inv);
+    if (hit >= 0) {
+        e->win_cur = hit;
+        return pre_on ? prefix_build_pass(e, key, e->win_graphs[hit], st) : 0;
     }
-    const bool prof = g_prof.on;
-    g_prof.on = false;                                          // no event records inside a capture
-    const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
-    vd_engine::WinGraph wg{};
-    wg.key = key; wg.inv = inv; wg.n_inv = n_inv;
-    PrefixPlan plan;
-    SuffixPlan splan;
-    if (pre_on || suf_on) {
-        std::vector<int> lists;
-        for (int n = 0; n < N; ++n) if (!inv[n]) lists.push_back(n);
-        for (int n = 0; n < N; ++n) if (inv[n]) lists.push_back(n);
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&wg.d_lists), N * sizeof(int)));
-        VD_HIP(hipMemcpy(wg.d_lists, lists.data(), N * sizeof(int), hipMemcpyHostToDevice));
-        wg.n_suf = suf_on ? N - n_inv : 0;
-        splan.n = N - n_inv; splan.list = wg.d_lists;
-    }
-    if (pre_on) {
-        wg.store = new PrefixStore();
-        rc = build_pass(wg);
-        if (!rc && hipStreamSynchronize(st) != hipSuccess) { set_error("prefix cache: first pass"); rc = -2; }
-        if (rc) { g_prof.on = prof; wg.graph = nullptr; wg.exec = nullptr; if (wg.d_lists) (void)hipFree(wg.d_lists);
-                  for (float* p : wg.store->tens) if (p) (void)hipFree(p); for (double* p : wg.store->parts) if (p) (void)hipFree(p); delete wg.store; return rc; }
-        plan.n = N - n_inv; plan.list = wg.d_lists; plan.store = wg.store;
-    }
-    VD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    rc = obs_mode == 2 ? launch_q_sample_prev(obs_src, reinterpret_cast<const int64_t*>(e->d_win_t), e->d_tab, e->num_timesteps, B, (long)per,
-                                              e->d_win_rng, (unsigned long long)B * per / 2, e->d_win_xtm1, st) : 0;
-    if (!rc) rc = step_launches(e, sampler, B, T, x, net_obs_src, obs, lat, km, fidx, e->d_win_t, net_mode, clip, eta, nullptr, 0, 0,
-                                e->d_win_rng, x, nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr, suf_on ? &splan : nullptr);
-    if (!rc) {
-        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B,
-                           (unsigned long long)B * per);
-        if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
-    }
-    hipGraph_t graph = nullptr;
-    const hipError_t ce = hipStreamEndCapture(st, &graph);
-    g_prof.on = prof;
-    auto drop_store = [&]() {
-        if (wg.d_lists) (void)hipFree(wg.d_lists);
-        if (wg.store) { for (float* p : wg.store->tens) if (p) (void)hipFree(p); for (double* p : wg.store->parts) if (p) (void)hipFree(p); delete wg.store; }
-    };
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); drop_store(); return rc; }
-    if (ce != hipSuccess) { set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce)); drop_store(); return -2; }
-    hipGraphExec_t exec = nullptr;
-    if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) { set_error("hipGraphInstantiate"); (void)hipGraphDestroy(graph); drop_store(); return -2; }
-    wg.graph = graph; wg.exec = exec;
-    if (wg.store) {
-        // a prefix store holds full-size copies of every tensor before the first attention layer (over 1 GB per block at 128x128,
-        // N = 160): sampling modes whose observed-frame pattern changes from window to window (hierarchy, adaptive, mixed) would
-        // grow device memory without bound (ADVICE r3).  At most four graphs keep a store; the oldest one goes first.
-        int cnt = 0, oldest = -1;
-        for (size_t i = 0; i < e->win_graphs.size(); ++i) if (e->win_graphs[i].store) { ++cnt; if (oldest < 0) oldest = (int)i; }
-        if (cnt >= 4) {
-            (void)hipDeviceSynchronize();                       // its graph may still be queued on the executor's stream
-            vd_engine::free_graph(e->win_graphs[oldest]);
-            e->win_graphs.erase(e->win_graphs.begin() + oldest);
-        }
-    }
-    e->win_graphs.push_back(wg);
-    e->win_cur = (int)e->win_graphs.size() - 1;
-    return 0;
+    const float* net_obs_src = obs_mode == 2 ? e->d_win_xtm1 : obs_src;
+    const int net_mode = obs_mode == 3 ? 2 : obs_mode;
+    if ((rc = warmup_forward(e, key, net_obs_src, net_mode, st))) return rc;
+    return capture_window(e, key, inv, n_inv, net_obs_src, net_mode, st);
 }
 
 int vd_set_window_prefix_cache(vd_engine* e, int on) {
@@ -2132,7 +2157,7 @@ long long vd_bwd_weights_bytes(vd_engine* e) { return e ? (long long)(e->packed_
 
 int vd_set_bwd_weight_storage(vd_engine* e, void* buf, long long bytes, int on_host) {
     VD_REQUIRE(e && buf, "null argument");
-    VD_REQUIRE(split_conv(), "use_gradient_method runs on the split arithmetic only (VD_MATH=f16x3 | bf16x6)");
+    VD_REQUIRE(split_math(), "use_gradient_method runs on the split arithmetic only (VD_MATH=f16x3 | bf16x6)");
     VD_REQUIRE(bytes >= (long long)(e->packed_bwd_total * sizeof(float)), "backward weight buffer too small");
     e->wbuf_bwd = static_cast<float*>(buf);
     e->wbuf_bwd_on_host = on_host != 0;
@@ -2212,8 +2237,7 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs,
     VD_REQUIRE(N <= 256 && B <= 256, "window of at most 256 frames");
     float* buf = reinterpret_cast<float*>(tail + 4096);
     float *eps = buf, *deps = buf + tot, *dxd = buf + 2 * tot, *mean0 = buf + 3 * tot, *dxn = buf + 4 * tot, *xs0 = buf + 5 * tot;
-    hipLaunchKernelGGL(map_t_kernel, dim3((B + 63) / 64), dim3(64), 0, st, reinterpret_cast<const int64_t*>(t), e->d_tmap,
-                       e->rescale, B, e->num_timesteps, tm, e->d_err);
+    map_t(e, t, B, tm, st);
     hipLaunchKernelGGL(guided_masks_kernel, dim3((N + 63) / 64), dim3(64), 0, st, obs, lat, N, obs_net, lat_net);
     Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);       // forward + backward live below the step's own buffers
     Tape tp; e->tape = &tp;
@@ -2258,12 +2282,9 @@ int vd_pack_conv3_wino_split(const float* host_oihw, unsigned short* host_out, i
 int vd_op_conv_wino_split(const float* src0, int Cin, int nfr, int Hs, int Ws, int ups, const void* w_split, const float* bias,
                           const float* res, const float* fbias, int fbias_ld, float* out, int Cout, double* gn_part,
                           void* stream) {
-    IgemmArgs g{};
-    g.src0 = src0; g.C0 = Cin; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Ws; g.ups = ups;
-    g.stride = 1; g.pad = 1; g.ksz = 3;
-    g.Ho = Hs << ups; g.Wo = Ws << ups;
+    IgemmArgs g = conv_args(src0, nullptr, Cin, Cin, nfr, Hs, Ws, ups, 1, 1, 3);
     g.wwino = static_cast<const float*>(w_split); g.wsplit = 2; g.bias = bias; g.res = res; g.res_ld = Cout;
-    g.fbias = fbias; g.fbias_ld = fbias_ld; g.out = out; g.ldo = Cout; g.Cout = Cout; g.M = nfr * g.Ho * g.Wo;
+    g.fbias = fbias; g.fbias_ld = fbias_ld; g.out = out; g.ldo = Cout; g.Cout = Cout;
     g.stats = gn_part; g.stats_split = conv_wino_stats_split(g.Ho);
     VD_REQUIRE(conv_wino_r64_supported(g), "vd_op_conv_wino_split: shape not covered by conv_wino_r64.hip");
     return launch_igemm(g, static_cast<hipStream_t>(stream));            // cuts big windows along frames like the engine
@@ -2271,13 +2292,11 @@ int vd_op_conv_wino_split(const float* src0, int Cin, int nfr, int Hs, int Ws, i
 
 int vd_op_conv_wino_act(const float* src0, const float* src1, int C0, int Cin, int nfr, int Hs, int Ws, const void* w_split, const float* bias,
                         const float* affA, const float* affB, const float* res, float* out, int Cout, double* gn_part, void* stream) {
-    IgemmArgs g{};
     VD_REQUIRE(src0 && (src1 ? C0 > 0 && C0 < Cin : C0 == Cin), "vd_op_conv_wino_act: one source of Cin channels, or two of C0 and Cin - C0");
-    g.src0 = src0; g.src1 = src1; g.C0 = C0; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Ws;
-    g.stride = 1; g.pad = 1; g.ksz = 3; g.Ho = Hs; g.Wo = Ws;
+    IgemmArgs g = conv_args(src0, src1, C0, Cin, nfr, Hs, Ws, 0, 1, 1, 3);
     g.wwino = static_cast<const float*>(w_split); g.wsplit = 2; g.bias = bias; g.res = res; g.res_ld = Cout;
     g.affA = affA; g.affB = affB; g.act = 1;
-    g.out = out; g.ldo = Cout; g.Cout = Cout; g.M = nfr * g.Ho * g.Wo;
+    g.out = out; g.ldo = Cout; g.Cout = Cout;
     g.stats = gn_part; g.stats_split = conv_wino_stats_split(g.Ho);
     VD_REQUIRE(conv_wino_z128_act_supported(g), "vd_op_conv_wino_act: shape not covered by conv_wino_z128.hip's activating form (vd_conv_wino_act_ok)");
     return launch_igemm(g, static_cast<hipStream_t>(stream));
@@ -2295,12 +2314,9 @@ int vd_conv_ups_stats_split(int Hs) { return conv_wino_ups_stats_split(Hs); }
 
 int vd_op_conv_wino_ups(const float* src0, int Cin, int nfr, int Hs, const void* w_ups, const float* bias, float* out, int Cout,
                         double* gn_part, void* stream) {
-    IgemmArgs g{};
-    g.src0 = src0; g.C0 = Cin; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Hs; g.ups = 1; g.ups_phase = 1;
-    g.stride = 1; g.pad = 1; g.ksz = 3;
-    g.Ho = 2 * Hs; g.Wo = 2 * Hs;
+    IgemmArgs g = conv_args(src0, nullptr, Cin, Cin, nfr, Hs, Hs, 1, 1, 1, 3);
+    g.ups_phase = 1;
     g.wwino = static_cast<const float*>(w_ups); g.wsplit = 2; g.bias = bias; g.out = out; g.ldo = Cout; g.Cout = Cout;
-    g.M = nfr * g.Ho * g.Wo;
     g.stats = gn_part; g.stats_split = conv_wino_ups_stats_split(Hs);
     VD_REQUIRE(conv_wino_r64_supported(g), "vd_op_conv_wino_ups: shape not covered (square power-of-two source map >= 8, Cout % 64, Cin % 32)");
     return launch_igemm(g, static_cast<hipStream_t>(stream));            // cuts big windows along frames like the engine
@@ -2314,12 +2330,9 @@ int vd_pack_conv3_split(const float* host_oihw, unsigned short* host_out, int O,
 
 int vd_op_conv_split(const float* src0, int Cin, int nfr, int Hs, int Ws, int stride, const void* w_split, const float* bias,
                      const float* res, float* out, int Cout, void* stream) {
-    IgemmArgs g{};
-    g.src0 = src0; g.C0 = Cin; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Ws;
-    g.stride = stride; g.pad = 1; g.ksz = 3;
-    g.Ho = (Hs + 2 - 3) / stride + 1; g.Wo = (Ws + 2 - 3) / stride + 1;
+    IgemmArgs g = conv_args(src0, nullptr, Cin, Cin, nfr, Hs, Ws, 0, stride, 1, 3);
     g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.res = res; g.res_ld = Cout;
-    g.out = out; g.ldo = Cout; g.Cout = Cout; g.M = nfr * g.Ho * g.Wo;
+    g.out = out; g.ldo = Cout; g.Cout = Cout;
     VD_REQUIRE(conv_split_supported(g), "vd_op_conv_split: shape not covered by the kernel");
     return launch_igemm(g, static_cast<hipStream_t>(stream));
 }
@@ -2332,19 +2345,15 @@ int vd_pack_linear_split(const float* host_w, unsigned short* host_out, int N, i
 
 int vd_op_linear_split(const float* a, int M, int K, const void* w_split, const float* bias, const float* res, int act,
                        float* out, int N, void* stream) {
-    IgemmArgs g{};
-    g.src0 = a; g.C0 = K; g.Cin = K; g.nfr = M; g.Hs = g.Ws = g.Ho = g.Wo = 1; g.stride = 1; g.ksz = 1;
-    g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.act = act; g.res = res; g.res_ld = N;
-    g.out = out; g.ldo = N; g.Cout = N; g.M = M;
+    IgemmArgs g = linear_args(M, K, N);
+    g.src0 = a; g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.act = act; g.res = res; g.out = out;
     return launch_igemm(g, static_cast<hipStream_t>(stream));
 }
 
 int vd_op_linear_split_stats(const float* a, int M, int K, const void* w_split, const float* bias, const float* res, int act,
                              float* out, int N, int HW, double* gn_part, void* stream) {
-    IgemmArgs g{};
-    g.src0 = a; g.C0 = K; g.Cin = K; g.nfr = M; g.Hs = g.Ws = g.Ho = g.Wo = 1; g.stride = 1; g.ksz = 1;
-    g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.act = act; g.res = res; g.res_ld = N;
-    g.out = out; g.ldo = N; g.Cout = N; g.M = M;
+    IgemmArgs g = linear_args(M, K, N);
+    g.src0 = a; g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.act = act; g.res = res; g.out = out;
     VD_REQUIRE(gn_part && HW > 0 && gemm_split_supported(g), "vd_op_linear_split_stats: shape not covered by gemm_split.hip");
     g.stats = gn_part; g.stats_hw = HW; g.stats_split = HW / gemm_split_stats_rows(M, N);
     return launch_igemm(g, static_cast<hipStream_t>(stream));
@@ -2397,13 +2406,9 @@ int vd_op_conv(const float* src0, const float* src1, int C0, int Cin, int nfr, i
                int pad, int ksz, const float* w, const float* w_frag, const float* w_wino, const float* bias, const float* affA,
                const float* affB, int act,
                const float* res, const float* fbias, int fbias_ld, float* out, int Cout, void* stream) {
-    IgemmArgs g{};
-    g.src0 = src0; g.src1 = src1; g.C0 = C0; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Ws; g.ups = ups;
-    g.stride = stride; g.pad = pad; g.ksz = ksz;
-    g.Ho = ((Hs << ups) + 2 * pad - ksz) / stride + 1;
-    g.Wo = ((Ws << ups) + 2 * pad - ksz) / stride + 1;
+    IgemmArgs g = conv_args(src0, src1, C0, Cin, nfr, Hs, Ws, ups, stride, pad, ksz);
     g.w = w; g.wfrag = w_frag; g.wwino = w_wino; g.bias = bias; g.affA = affA; g.affB = affB; g.act = act; g.res = res; g.res_ld = Cout;
-    g.fbias = fbias; g.fbias_ld = fbias_ld; g.out = out; g.ldo = Cout; g.Cout = Cout; g.M = nfr * g.Ho * g.Wo;
+    g.fbias = fbias; g.fbias_ld = fbias_ld; g.out = out; g.ldo = Cout; g.Cout = Cout;
     return launch_igemm(g, static_cast<hipStream_t>(stream));
 }
 
@@ -2413,12 +2418,9 @@ int vd_conv_wino_block_couts(int nfr, int H, int Cin, int Cout) { return conv_wi
 int vd_op_conv_stats(const float* src0, int Cin, int nfr, int Hs, int Ws, int ups, const float* w_wino, const float* bias,
                      const float* res, const float* fbias, int fbias_ld, float* out, int Cout, double* gn_part,
                      void* stream) {
-    IgemmArgs g{};
-    g.src0 = src0; g.C0 = Cin; g.Cin = Cin; g.nfr = nfr; g.Hs = Hs; g.Ws = Ws; g.ups = ups;
-    g.stride = 1; g.pad = 1; g.ksz = 3;
-    g.Ho = Hs << ups; g.Wo = Ws << ups;
+    IgemmArgs g = conv_args(src0, nullptr, Cin, Cin, nfr, Hs, Ws, ups, 1, 1, 3);
     g.wwino = w_wino; g.bias = bias; g.res = res; g.res_ld = Cout; g.fbias = fbias; g.fbias_ld = fbias_ld;
-    g.out = out; g.ldo = Cout; g.Cout = Cout; g.M = nfr * g.Ho * g.Wo;
+    g.out = out; g.ldo = Cout; g.Cout = Cout;
     g.stats = gn_part; g.stats_split = conv_wino_stats_split(g.Ho);
     VD_REQUIRE(conv_wino_supported(g), "vd_op_conv_stats: shape not covered by the Winograd kernel");
     return launch_igemm(g, static_cast<hipStream_t>(stream));
@@ -2433,14 +2435,12 @@ int vd_op_gn_affine(const double* part0, int split0, int C0, const double* part1
 
 int vd_op_gn_fold(const float* src0, const float* src1, int C0, int C, int nfr, int HW, const float* gamma,
                   const float* beta, const float* film, int film_ld, float* affA, float* affB, void* stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    OpScratch ws(stream);
     const int split = gn_stats_split(nfr, HW, C);
     double* part;
-    VD_HIP(hipMalloc(reinterpret_cast<void**>(&part), (size_t)nfr * split * C * 2 * sizeof(double)));
-    int rc = launch_gn_stats(src0, src1, C0, C, nfr, HW, part, split, st);
-    if (!rc) rc = launch_gn_affine(part, split, C, nullptr, 0, (double)HW * (C / 32), gamma, beta, film, film_ld, nfr, C, affA, affB, st);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(part);
+    int rc = ws.get(&part, (size_t)nfr * split * C * 2);
+    if (!rc) rc = launch_gn_stats(src0, src1, C0, C, nfr, HW, part, split, ws.st);
+    if (!rc) rc = launch_gn_affine(part, split, C, nullptr, 0, (double)HW * (C / 32), gamma, beta, film, film_ld, nfr, C, affA, affB, ws.st);
     return rc;
 }
 
@@ -2479,21 +2479,14 @@ int vd_op_gn_bwd(const float* x0, const float* x1, int C0, int C, const float* a
                  const float* dy, int act, int nfr, int HW, const float* extra, float* dx0, int acc0, float* dx1, int acc1,
                  void* stream) {
     VD_REQUIRE(nfr > 0 && HW > 0 && C > 0 && C % 32 == 0 && C <= 1024, "vd_op_gn_bwd: shape");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int split = gn_bwd_split(nfr, HW, C);
+    OpScratch ws(stream);
     double* part = nullptr;
     float* K = nullptr;
-    VD_HIP(hipMalloc(reinterpret_cast<void**>(&part), (size_t)nfr * split * C * 2 * sizeof(double)));
-    if (hipMalloc(reinterpret_cast<void**>(&K), (size_t)nfr * 32 * 2 * sizeof(float)) != hipSuccess) {
-        (void)hipFree(part);
-        VD_REQUIRE(false, "vd_op_gn_bwd: workspace allocation");
-    }
+    int rc = ws.get(&part, (size_t)nfr * gn_bwd_split(nfr, HW, C) * C * 2);
+    if (!rc) rc = ws.get(&K, (size_t)nfr * 32 * 2);
+    if (rc) return rc;
     GnBwdArgs a{x0, x1, C0, C, affA, affB, mr, dy, act, nfr, HW, dx0, dx1, acc0, acc1, extra, part, K};
-    int rc = launch_gn_bwd(a, st);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(part);
-    (void)hipFree(K);
-    return rc;
+    return launch_gn_bwd(a, ws.st);
 }
 
 int vd_op_gn_temporal_bwd(const float* x, const float* gamma, const float* dy, int B, int T, int HW, int C, int accumulate,
@@ -2509,14 +2502,11 @@ int vd_op_attn_temporal_bwd(const float* qkv, const float* Rk, const float* Rq, 
 
 int vd_op_attn_spatial_bwd(const float* qkv, int nfr, int L, int C, int heads, const float* dout, float* dqkv, void* stream) {
     VD_REQUIRE(nfr > 0 && L > 0 && heads > 0 && C % heads == 0, "vd_op_attn_spatial_bwd: shape");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     AttnSpatialArgs a{qkv, nullptr, nfr, L, C, heads, 1.0f / sqrtf((float)(C / heads))};
-    float* ws = nullptr;
-    VD_HIP(hipMalloc(reinterpret_cast<void**>(&ws), attn_spatial_bwd_ws_floats(a) * sizeof(float)));
-    int rc = launch_attn_spatial_bwd(a, dout, dqkv, ws, st);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(ws);
-    return rc;
+    OpScratch ws(stream);
+    float* buf = nullptr;
+    int rc = ws.get(&buf, attn_spatial_bwd_ws_floats(a));
+    return rc ? rc : launch_attn_spatial_bwd(a, dout, dqkv, buf, ws.st);
 }
 
 int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W, int C, int Cout, float* da, void* stream) {

@@ -149,6 +149,18 @@ class GaussianDiffusion:
         return t
 
     # -- per-step entry points ---------------------------------------------------------------------
+    def _prepare(self, model, x, t, model_kwargs):
+        """What every step hands the engine: the bound model, x as float32 and t as int64 on its device, model_kwargs packed
+        (_pack_kwargs).  A host t is range-checked like the reference's table lookup; a device-resident t is range-checked
+        by the kernels (NaN output + model.check_device_errors())."""
+        model = self._bind(model)
+        B = x.shape[0]
+        assert t.shape == (B,)                                   # gaussian_diffusion.py:273
+        if t.device.type == "cpu" and B and (int(t.min()) < 0 or int(t.max()) >= self.num_timesteps):
+            raise IndexError(f"index {int(t.max())} is out of bounds for dimension 0 with size {self.num_timesteps}")
+        xs = _f32(x, model.device)
+        return model, xs, t.to(device=model.device, dtype=th.int64).contiguous(), model._pack_kwargs(xs, model_kwargs)
+
     def _step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
               return_attn_weights=False, use_gradient_method=False):
         if model_kwargs is None:
@@ -163,29 +175,20 @@ class GaussianDiffusion:
             out = self._guided(model, x, t, clip_denoised, model_kwargs, noise2=noise, want_sample=True)
             return out["sample"], out["pred_xstart"]
         if denoised_fn is not None:
-            return self._step_denoised_fn(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights)
-        model = self._bind(model)
-        B = x.shape[0]
-        assert t.shape == (B,)                                   # gaussian_diffusion.py:273
-        if t.device.type == "cpu" and B and (int(t.min()) < 0 or int(t.max()) >= self.num_timesteps):
-            raise IndexError(f"index {int(t.max())} is out of bounds for dimension 0 with size {self.num_timesteps}")
-        # (a device-resident t is range-checked by the kernels: NaN output + model.check_device_errors())
-        dev = model.device
-        xs = _f32(x, dev)
-        kw = model._pack_kwargs(xs, model_kwargs)
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise)
+            self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
+            return out["sample"], out["pred_xstart"]
+        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
         if noise is None:
             noise = th.randn_like(xs)                            # gaussian_diffusion.py:438 / :628 (drawn even for eta=0)
         else:
-            noise = _f32(noise, dev)
+            noise = _f32(noise, model.device)
         assert noise.shape == xs.shape
-        tt = t.to(device=dev, dtype=th.int64).contiguous()
         sample = th.empty_like(xs)
         xstart = th.empty_like(xs)
-        T = xs.shape[1]
+        B, T = xs.shape[:2]
         L = _lib.lib()
-        common = (model._handle, B, T, _lib.ptr(xs), _lib.ptr(kw["obs_src"]), _lib.ptr(kw["obs_mask"]),
-                  _lib.ptr(kw["latent_mask"]), _lib.ptr(kw["kinda_marg_mask"]), _lib.ptr(kw["frame_indices"]),
-                  _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0)
+        common = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0)
         self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
             if mode == 0:
@@ -206,20 +209,14 @@ class GaussianDiffusion:
         the noise of the x_{t-1} sample inside p_mean_variance first, p_sample's own noise second."""
         if self.model_mean_type != ModelMeanType.EPSILON:
             raise NotImplementedError("use_gradient_method with predict_xstart=True")
-        base = self._bind(model)
+        base, xs, tt, kw = self._prepare(model, x, t, dict(model_kwargs, observed_frames="x_t"))   # obs_src is unused: every frame is latent
         base._require_guidance()
         dev = base.device
-        xs = _f32(x, dev)
         B, T = xs.shape[:2]
-        assert t.shape == (B,)
-        if t.device.type == "cpu" and B and (int(t.min()) < 0 or int(t.max()) >= self.num_timesteps):
-            raise IndexError(f"index {int(t.max())} is out of bounds for dimension 0 with size {self.num_timesteps}")
-        kw = base._pack_kwargs(xs, dict(model_kwargs, observed_frames="x_t"))      # obs_src is unused: every frame is latent
         xtm1 = _f32(model_kwargs["x_t_minus_1"], dev)
         noise = th.randn_like(xs) if _noise is None else _f32(_noise, dev)         # gaussian_diffusion.py:351
         if want_sample:
             noise2 = th.randn_like(xs) if noise2 is None else _f32(noise2, dev)     # gaussian_diffusion.py:438
-        tt = t.to(device=dev, dtype=th.int64).contiguous()
         mean, xstart, grad = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
         sample = th.empty_like(xs) if want_sample else None
         _lib.check(_lib.lib().vd_guided_step(
@@ -229,25 +226,32 @@ class GaussianDiffusion:
             _lib.ptr(sample) if want_sample else None, _lib.current_stream()))
         return {"mean": mean, "pred_xstart": xstart, "grad": grad, "sample": sample}
 
-    def _step_denoised_fn(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights=False):
+    def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None):
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
-        the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart."""
+        the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
+        (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample."""
         out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
-        self._last_attn = out["attn"]                              # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
         base = self._bind(model)
         dev = base.device
         xs = _f32(x, dev)
-        B = xs.shape[0]
         x0 = _f32(denoised_fn(out["pred_xstart"]), dev)
         assert x0.shape == xs.shape
-        noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
+        if mode is not None:
+            noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
         tt = t.to(device=dev, dtype=th.int64).contiguous()
-        sample, xstart = th.empty_like(xs), th.empty_like(xs)
+        out.update({"sample" if mode is not None else "mean": th.empty_like(xs), "pred_xstart": th.empty_like(xs)})
         _lib.check(_lib.lib().vd_posterior_from_xstart(
-            base._handle, mode, B, xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
-            float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None, _lib.current_stream()))
-        return sample, xstart
+            base._handle, mode or 0, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
+            float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(out.get("sample")), _lib.ptr(out["pred_xstart"]),
+            _lib.ptr(out["mean"] if mode is None else None), _lib.current_stream()))
+        return out
+
+    def _variance(self, t, shape):
+        """p_mean_variance's fixed variance rows at t (gaussian_diffusion.py:299-317)."""
+        variance = self.posterior_variance if self.model_var_type == ModelVarType.FIXED_SMALL \
+            else np.append(self.posterior_variance[1], self.betas[1:])
+        return {"variance": self._extract(variance, t, shape), "log_variance": self._extract(self._model_log_variance(), t, shape)}
 
     def _extract(self, arr, t, shape):
         """_extract_into_tensor (gaussian_diffusion.py:1019-1031): float64 table gathered at t, cast to float32,
@@ -269,48 +273,23 @@ class GaussianDiffusion:
                 raise NotImplementedError("use_gradient_method with denoised_fn")
             g = self._guided(model, x, t, clip_denoised, model_kwargs or {}, _noise=getattr(self, "_guidance_noise", None))
             tt = t.to(device=g["mean"].device, dtype=th.int64)
-            variance = self.posterior_variance if self.model_var_type == ModelVarType.FIXED_SMALL \
-                else np.append(self.posterior_variance[1], self.betas[1:])
-            return {"mean": g["mean"], "variance": self._extract(variance, tt, g["mean"].shape),
-                    "log_variance": self._extract(self._model_log_variance(), tt, g["mean"].shape),
-                    "pred_xstart": g["pred_xstart"], "attn": None, "grad": g["grad"]}
+            return {"mean": g["mean"], **self._variance(tt, g["mean"].shape), "pred_xstart": g["pred_xstart"], "attn": None,
+                    "grad": g["grad"]}
         if denoised_fn is not None:
-            out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
-            base = self._bind(model)
-            xs = _f32(x, base.device)
-            x0 = _f32(denoised_fn(out["pred_xstart"]), base.device)
-            tt = t.to(device=base.device, dtype=th.int64).contiguous()
-            mean, xstart = th.empty_like(xs), th.empty_like(xs)
-            _lib.check(_lib.lib().vd_posterior_from_xstart(
-                base._handle, 0, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt),
-                1 if clip_denoised else 0, 0.0, None, 0, 0, None, _lib.ptr(xstart), _lib.ptr(mean), _lib.current_stream()))
-            out.update(mean=mean, pred_xstart=xstart)
-            return out
-        model = self._bind(model)
-        B = x.shape[0]
-        assert t.shape == (B,)
-        if t.device.type == "cpu" and B and (int(t.min()) < 0 or int(t.max()) >= self.num_timesteps):
-            raise IndexError(f"index {int(t.max())} is out of bounds for dimension 0 with size {self.num_timesteps}")
-        dev = model.device
-        xs = _f32(x, dev)
-        kw = model._pack_kwargs(xs, model_kwargs or {})
-        tt = t.to(device=dev, dtype=th.int64).contiguous()
+            return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights)
+        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs or {})
+        B, T = xs.shape[:2]
         mean, xstart, eps = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
-        attn = model._attn_capture(B, xs.shape[1]) if return_attn_weights else None
+        attn = model._attn_capture(B, T) if return_attn_weights else None
         try:
-            rc = _lib.lib().vd_p_mean_variance(
-                model._handle, B, xs.shape[1], _lib.ptr(xs), _lib.ptr(kw["obs_src"]), _lib.ptr(kw["obs_mask"]),
-                _lib.ptr(kw["latent_mask"]), _lib.ptr(kw["kinda_marg_mask"]), _lib.ptr(kw["frame_indices"]), _lib.ptr(tt),
-                kw["obs_mode"], 1 if clip_denoised else 0, _lib.ptr(mean), _lib.ptr(xstart), _lib.ptr(eps), _lib.current_stream())
+            rc = _lib.lib().vd_p_mean_variance(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
+                                               1 if clip_denoised else 0, _lib.ptr(mean), _lib.ptr(xstart), _lib.ptr(eps),
+                                               _lib.current_stream())
         finally:
             if attn is not None:
                 model._attn_release()
         _lib.check(rc)
-        logvar = self._model_log_variance()
-        variance = self.posterior_variance if self.model_var_type == ModelVarType.FIXED_SMALL \
-            else np.append(self.posterior_variance[1], self.betas[1:])             # gaussian_diffusion.py:299-317
-        return {"mean": mean, "variance": self._extract(variance, tt, xs.shape),
-                "log_variance": self._extract(logvar, tt, xs.shape), "pred_xstart": xstart, "attn": attn, "eps": eps}
+        return {"mean": mean, **self._variance(tt, xs.shape), "pred_xstart": xstart, "attn": attn, "eps": eps}
 
     def q_posterior_mean_variance(self, x_start, x_t, t):
         """gaussian_diffusion.py:208-227 (host composition of schedule rows; the samplers fuse it in posterior_kernel)."""

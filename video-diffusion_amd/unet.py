@@ -317,6 +317,12 @@ class CondMargVideoModel:
                     kinda_marg_mask=f32(kw["kinda_marg_mask"]).reshape(B * T),
                     frame_indices=fi.to(device=dev, dtype=th.int64).contiguous(), obs_mode=_OBS_MODES[mode])
 
+    @staticmethod
+    def _window_ptrs(x, kw):
+        """The six window tensors as the C ABI takes them (x, obs_src, obs_mask, latent_mask, kinda_marg_mask, frame_indices);
+        kw as _pack_kwargs returns it."""
+        return (_lib.ptr(x),) + tuple(_lib.ptr(kw[k]) for k in ("obs_src", "obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"))
+
     # -- return_attn_weights ---------------------------------------------------------------------------
     def _attn_capture(self, B, T):
         """Arm the engine's attention-weight capture for the next forward and return the reference's dict
@@ -350,10 +356,8 @@ class CondMargVideoModel:
         eps = th.empty(B, T, self.out_channels, H, W, dtype=th.float32, device=self.device)
         attn = self._attn_capture(B, T) if return_attn_weights else None
         try:
-            _lib.check(_lib.lib().vd_unet_forward(self._handle, B, T, _lib.ptr(xs), _lib.ptr(kw["obs_src"]),
-                                                  _lib.ptr(kw["obs_mask"]), _lib.ptr(kw["latent_mask"]),
-                                                  _lib.ptr(kw["kinda_marg_mask"]), _lib.ptr(kw["frame_indices"]),
-                                                  _lib.ptr(tm), kw["obs_mode"], _lib.ptr(eps), _lib.current_stream()))
+            _lib.check(_lib.lib().vd_unet_forward(self._handle, B, T, *self._window_ptrs(xs, kw), _lib.ptr(tm), kw["obs_mode"],
+                                                  _lib.ptr(eps), _lib.current_stream()))
         finally:
             if attn is not None:
                 self._attn_release()
