@@ -437,6 +437,24 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
 int vd_fps_select(int B, int n_cand, long long D, const float* embs, int n, const int* always_host, int n_always, float* work,
                   int* out, void* stream);
 
+/* ---- Evaluation metrics of sampled videos (csrc/metrics.hip).
+ * Replaces the per-frame, per-channel host loops of scripts/video_eval.py: compute_metrics_lazy (:205-225; scikit-image 0.19.3
+ * structural_similarity and peak_signal_noise_ratio on float32 planes) and the distance half of compute_lpips_lazy (:228-252;
+ * lpips.LPIPS(net='alex', spatial=False) of two frames = the squared L2 distance of their vd_lpips_embed embeddings).
+ *
+ * Frame metrics: gt [N][C][H][W] float32 in [0, 1]; pred the same shape, uint8 (read as u / 255) when pred_is_u8, else float32.  Per frame the
+ * mean over its C planes of
+ *   SSIM: 7 x 7 uniform window, sample covariance (49/48), K1 = 0.01, K2 = 0.03, data range ssim_data_range (2.0 is what the
+ *         reference's scikit-image takes for float images when none is passed, 1.0 the true range), mean over the windows that lie
+ *         inside the plane (the crop of 3 pixels per side);
+ *   PSNR: 10 log10(1 / mse), mse the float64 mean of the squared float32 differences; +inf for identical planes.
+ * Sums in float64, fixed order: a frame's values do not depend on the other frames of the call.  Limits: H, W >= 7, W <= 1024, C >= 1.
+ * Device pointers; enqueued only.  The partial-sum table is owned by the library (per device, grown on demand). */
+int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pred, int pred_is_u8, double ssim_data_range,
+                     double* ssim_out, double* psnr_out, void* stream);
+/* out[n] = sum over d of (a[n][d] - b[n][d])^2 for rows of D floats, differences and sum in float64, fixed order. */
+int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,298 @@
+"""GPU: per-frame SSIM / PSNR (csrc/metrics.hip: vd_frame_metrics), the paired embedding distance (vd_pair_sqdist,
+LpipsAlex.distance) and the video_eval job, against the restatement of the reference's arithmetic in tests/metrics_restated.py and
+tests/lpips_restated.py (scikit-image and lpips are not installed, so the restatement is the yardstick).
+
+SSIM bound.  The yardstick is the restatement in float64.  The reference itself runs scikit-image 0.19.3 on float32 images, i.e. the
+same lines in float32; the gap between the two, taken over ALL inputs of this file (computed here, GAP below), is the error the
+reference's own numbers carry.  The kernel accumulates its window sums in float64 and evaluates S in float64, so it has no reason to be
+further from the float64 value than that: |kernel - float64| <= max(GAP_ssim, SSIM_FLOOR).  SSIM_FLOOR stands for the kernel's own
+rounding where the float32 gap happens to vanish (an identical pair gives exactly 1 in either precision): 3 x the largest error measured
+on the MI355X.  PSNR: the same scheme on |kernel - float64| / |float64| in dB; a +inf must be +inf.
+
+Measured on the MI355X over all inputs of this file (MEASURED below): SSIM, kernel against float64, 8.6e-14 absolute at R = 2 and 2.7e-13 at
+R = 1, where the float32 gap of the restatement is 7.08e-7 and 8.45e-7; PSNR 2.27e-8 relative, which IS the float32 gap (2.27e-8): the
+kernel squares float32 differences as the reference does.  Every run prints these figures.  LPIPS distance against the restatement:
+relative error <= 1.9e-7 for the regular pairs; the near-identical pair (d = 1.9e-6 at 128 x 128) is off by 2.3e-11 = 1.2e-5 d, inside
+its ATOL of 3.9e-8.
+
+LPIPS bound.  tests/test_gpu_lpips.py holds every pairwise squared distance of embeddings to DIST_RTOL = 1e-5 relative (measured there
+<= 1.9e-7) and every embedding element to |err_i| <= 2e-5 max|e_tap| + 1e-5 |e_i|.  The same embedding kernels feed LpipsAlex.distance and
+vd_pair_sqdist adds no rounding of its own beyond float64 (its differences are exact, its sum is in float64), so the same relative
+bound applies.  It cannot hold as d -> 0: with ea' = ea + ua, eb' = eb + ub, d' - d = 2 (ea - eb).(ua - ub) + ||ua - ub||^2.  The first term scales
+with sqrt(d) and is what the relative bound covers for well-separated pairs; the second does not shrink with d.  Its size from the
+per-element bound: |ua_i - ub_i| <= e_i := (2e-5 max|ea_tap| + 1e-5 |ea_i|) + (2e-5 max|eb_tap| + 1e-5 |eb_i|), so ||ua - ub||^2 <= sum_i e_i^2 =: ATOL
+(about 1e-7 at 64 x 64), computed per pair from the restated embeddings.  Tolerance: DIST_RTOL * d + ATOL.  The regular pairs are asserted
+to lie at least 1000 x above ATOL; one pair is deliberately near-identical."""
+import functools
+import os
+import pickle
+
+import numpy as np
+import pytest
+import torch
+
+import metrics_restated as mr
+from lpips_restated import embed_parts_restated, synth_weights
+from video_diffusion_amd import _lib
+from video_diffusion_amd import video_eval as ve
+from video_diffusion_amd.lpips import LpipsAlex, embedding_dim
+from video_diffusion_amd.metrics import frame_ssim_psnr
+from video_diffusion_amd.video_sample import to_uint8
+
+pytestmark = pytest.mark.gpu
+DIST_RTOL = 1e-5                              # tests/test_gpu_lpips.py
+# largest errors of the kernel against the float64 restatement measured on the MI355X over all inputs of this file
+MEASURED = {"ssim_abs": 2.7e-13, "psnr_rel": 2.27e-8}
+SSIM_FLOOR = 3 * MEASURED["ssim_abs"]
+PSNR_FLOOR = 3 * MEASURED["psnr_rel"]
+
+SHAPES = [(7, 7), (9, 33), (64, 64), (100, 70), (128, 128), (200, 160)]     # 200 x 160: several row strips per plane
+KINDS = ["noise", "outliers", "ramp", "quantised", "identical"]
+N_FRAMES = 2
+
+
+def _case(kind, C, H, W, u8):
+    """(gt float32 in [0, 1], pred float32 or uint8), N_FRAMES frames of C planes."""
+    g = np.random.default_rng(KINDS.index(kind) * 7919 + C * 104729 + H * 1301 + W)
+    shape = (N_FRAMES, C, H, W)
+    if kind == "noise":
+        gt = g.random(shape)
+        pred = g.random(shape)
+    elif kind == "outliers":                     # a constant image with sparse outliers: windows of zero variance next to large ones
+        gt = np.full(shape, 0.25)
+        gt[g.random(shape) < 0.02] = 1.0
+        pred = np.full(shape, 0.25)
+        pred[g.random(shape) < 0.02] = 0.0
+    elif kind == "ramp":
+        yy = np.linspace(0, 1, H).reshape(1, 1, H, 1)
+        xx = np.linspace(0, 1, W).reshape(1, 1, 1, W)
+        gt = np.broadcast_to(0.5 * (yy + xx), shape).copy()
+        pred = np.clip(gt + 0.02 * g.standard_normal(shape), 0, 1)
+    elif kind == "quantised":                    # the prediction is the ground truth as a sample file stores it
+        gt = g.random(shape)
+        pred = None
+    elif kind == "identical":
+        gt = mr.u8_to_float((g.random(shape) * 255).astype(np.uint8)) if u8 else g.random(shape)
+        pred = None
+    gt = gt.astype(np.float32)
+    if kind == "quantised":
+        q = (gt * 255).astype(np.uint8)
+        pred = q if u8 else mr.u8_to_float(q)
+    elif kind == "identical":
+        pred = (np.rint(gt * 255).astype(np.uint8)) if u8 else gt.copy()
+        if u8:
+            assert np.array_equal(mr.u8_to_float(pred), gt)
+    else:
+        pred = (pred * 255).astype(np.uint8) if u8 else pred.astype(np.float32)
+    return gt, pred
+
+
+def _all_cases():
+    for (H, W) in SHAPES:
+        for C in (1, 3):
+            for kind in KINDS:
+                for u8 in (False, True):
+                    yield (H, W, C, kind, u8)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(R):
+    """{case: (ssim64, psnr64, ssim32, psnr32)} for every input of this file, and the float32-against-float64 gaps of the restatement."""
+    out, gap_s, gap_p = {}, 0.0, 0.0
+    for key in _all_cases():
+        H, W, C, kind, u8 = key
+        gt, pred = _case(kind, C, H, W, u8)
+        s64, p64 = mr.frame_ssim_psnr(gt, pred, R, np.float64)
+        s32, p32 = mr.frame_ssim_psnr(gt, pred, R, np.float32)
+        out[key] = (s64, p64, s32, p32)
+        gap_s = max(gap_s, float(np.abs(s32 - s64).max()))
+        fin = np.isfinite(p64)
+        assert np.array_equal(fin, np.isfinite(p32))
+        if fin.any():
+            gap_p = max(gap_p, float((np.abs(p32 - p64)[fin] / np.abs(p64[fin])).max()))
+    return out, gap_s, gap_p
+
+
+@pytest.mark.parametrize("R", [2.0, 1.0])
+def test_frame_metrics_vs_restated(R):
+    want, gap_s, gap_p = _restated(R)
+    tol_s, tol_p = max(gap_s, SSIM_FLOOR), max(gap_p, PSNR_FLOOR)
+    worst_s, worst_p, n_inf = 0.0, 0.0, 0
+    failures = []
+    for key in _all_cases():
+        H, W, C, kind, u8 = key
+        gt, pred = _case(kind, C, H, W, u8)
+        ssim, psnr = frame_ssim_psnr(gt, pred, R, device="cuda:0")
+        assert ssim.shape == (N_FRAMES,) and ssim.dtype == np.float64 and psnr.dtype == np.float64
+        s64, p64, _, _ = want[key]
+        es = float(np.abs(ssim - s64).max())
+        fin = np.isfinite(p64)
+        if not np.array_equal(psnr[~fin], p64[~fin]):                        # +inf stays +inf
+            failures.append((key, "psnr inf", psnr, p64))
+        n_inf += int((~fin).sum())
+        ep = float((np.abs(psnr - p64)[fin] / np.abs(p64[fin])).max()) if fin.any() else 0.0
+        worst_s, worst_p = max(worst_s, es), max(worst_p, ep)
+        if es > tol_s or ep > tol_p:
+            failures.append((key, es, ep))
+        if kind == "identical":
+            assert np.abs(ssim - 1.0).max() <= tol_s and not fin.any()
+    print(f"frame metrics R={R}: float32 gap of the restatement ssim {gap_s:.3e} abs, psnr {gap_p:.3e} rel; "
+          f"kernel vs float64: ssim {worst_s:.3e} abs, psnr {worst_p:.3e} rel; {n_inf} +inf frames")
+    assert n_inf > 0
+    assert not failures, failures[:5]
+    # a finding about the kernel, not a reason to widen the bound: it must not be 10 x worse than the reference's own arithmetic
+    assert worst_s <= 10 * gap_s and worst_p <= 10 * gap_p
+
+
+@pytest.mark.parametrize("H,W,u8", [(64, 64, True), (200, 160, False), (9, 33, True)])
+def test_batched_call_is_bit_equal_to_single_frames(H, W, u8):
+    g = np.random.default_rng(5)
+    gt = g.random((5, 3, H, W)).astype(np.float32)
+    pred = (g.random((5, 3, H, W)) * 255).astype(np.uint8) if u8 else g.random((5, 3, H, W)).astype(np.float32)
+    s, p = frame_ssim_psnr(gt, pred, device="cuda:0")
+    for n in range(5):
+        s1, p1 = frame_ssim_psnr(gt[n:n + 1], pred[n:n + 1], device="cuda:0")
+        assert s1[0] == s[n] and p1[0] == p[n]
+    s2, p2 = frame_ssim_psnr(torch.from_numpy(gt).cuda(), torch.from_numpy(pred).cuda())      # device tensors, run to run
+    assert np.array_equal(s2, s) and np.array_equal(p2, p)
+
+
+def test_c_entry_refuses_small_and_wide_frames():
+    gt = torch.zeros(1, 1, 6, 2048, device="cuda:0")
+    out = torch.zeros(2, dtype=torch.float64, device="cuda:0")
+    L = _lib.lib()
+
+    def call(H, W):
+        return L.vd_frame_metrics(1, 1, H, W, _lib.ptr(gt), _lib.ptr(gt), 0, 2.0, _lib.ptr(out), _lib.ptr(out[1:]), _lib.current_stream())
+    with pytest.raises(_lib.VdError, match="H >= 7"):
+        _lib.check(call(6, 20))
+    with pytest.raises(_lib.VdError, match="H >= 7"):
+        _lib.check(call(20, 6))
+    with pytest.raises(_lib.VdError, match="1024"):
+        _lib.check(call(7, 2048))
+    with pytest.raises(ValueError, match="win_size exceeds image extent"):       # the wrapper, before any launch
+        frame_ssim_psnr(gt, gt)
+    with pytest.raises(_lib.VdError, match="positive"):
+        _lib.check(L.vd_frame_metrics(1, 1, 8, 8, _lib.ptr(gt), _lib.ptr(gt), 0, 0.0, _lib.ptr(out), _lib.ptr(out[1:]), _lib.current_stream()))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("D", [31872, 148608, 1001])
+def test_pair_sqdist(D):
+    g = torch.Generator().manual_seed(D)
+    a = torch.randn(5, D, generator=g)
+    b = torch.randn(5, D, generator=g)
+    b[3] = a[3]
+    out = torch.empty(5, dtype=torch.float64, device="cuda:0")
+    ad, bd = a.cuda(), b.cuda()
+    _lib.check(_lib.lib().vd_pair_sqdist(5, D, _lib.ptr(ad), _lib.ptr(bd), _lib.ptr(out), _lib.current_stream()))
+    want = ((a.double() - b.double()) ** 2).sum(1)
+    got = out.cpu()
+    assert got[3] == 0.0
+    assert ((got - want).abs() <= 1e-12 * want).all(), (got, want)
+    # rows that do not start 16-byte aligned (odd D): the scalar path
+    if D % 4:
+        _lib.check(_lib.lib().vd_pair_sqdist(4, D, _lib.ptr(ad[1:]), _lib.ptr(bd[1:]), _lib.ptr(out), _lib.current_stream()))
+        assert ((out.cpu()[:4] - want[1:]).abs() <= 1e-12 * want[1:]).all()
+
+
+_emb = {}
+
+
+def _embedder():
+    if not _emb:
+        from test_gpu_lpips import _state_dict
+        _emb[0] = LpipsAlex.from_state_dict(_state_dict(synth_weights(0)), "cuda:0")
+    return _emb[0], synth_weights(0)
+
+
+def _frames(N, H, W, seed):
+    from test_gpu_lpips import _frames as frames
+    return frames(N, H, W, seed)
+
+
+def _lpips_want(a, b, w):
+    """(restated distances, ATOL per pair) -- the module docstring's derivation."""
+    pa, pb = embed_parts_restated(a, w), embed_parts_restated(b, w)
+    d = sum(((x - y) ** 2).sum(1) for x, y in zip(pa, pb))
+    atol = sum((((2e-5 * x.abs().amax(1, keepdim=True) + 1e-5 * x.abs()) + (2e-5 * y.abs().amax(1, keepdim=True) + 1e-5 * y.abs())) ** 2).sum(1)
+               for x, y in zip(pa, pb))
+    return d.numpy(), atol.numpy()
+
+
+@pytest.mark.parametrize("H,W", [(64, 64), (128, 128)])
+def test_lpips_distance_vs_restated(H, W):
+    emb, w = _embedder()
+    N = 5
+    a = _frames(N, H, W, seed=3 * H)
+    b = _frames(N, H, W, seed=3 * H + 1)
+    b[N - 1] = (a[N - 1] + 1e-3 * torch.randn(3, H, W, generator=torch.Generator().manual_seed(2))).clamp(-1, 1)    # near-identical
+    got = emb.distance(a, b)
+    assert got.shape == (N,) and got.dtype == np.float64
+    want, atol = _lpips_want(a, b, w)
+    err = np.abs(got - want)
+    print(f"LPIPS distance {H}x{W}: d {want}, ATOL {atol}, rel err {err / want}")
+    assert (want[:N - 1] > 1000 * atol[:N - 1]).all()                       # regular pairs: far above the absolute term
+    assert want[N - 1] < 1e-2 * want[:N - 1].min()                           # the near-identical one is
+    assert (err <= DIST_RTOL * want + atol).all(), (err, DIST_RTOL * want + atol)
+    assert (err[:N - 1] <= DIST_RTOL * want[:N - 1]).all()
+    # identical frames: exactly zero; chunked = unchunked, bit for bit; device inputs
+    assert np.array_equal(emb.distance(a, a.clone()), np.zeros(N))
+    assert np.array_equal(emb.distance(a, b, chunk=2), got)
+    assert np.array_equal(emb.distance(a.cuda(), b.cuda(), chunk=N + 3), got)
+    # vd_pair_sqdist of the embeddings is the same number
+    ea, eb = emb(a).reshape(N, -1), emb(b).reshape(N, -1)
+    assert ea.shape[1] == embedding_dim(H, W)
+    d64 = ((ea.double() - eb.double()) ** 2).sum(1).cpu().numpy()
+    assert (np.abs(got - d64) <= 1e-12 * d64).all()
+
+
+def test_video_eval_cli_end_to_end(tmp_path, capsys):
+    """Two ground-truth videos, two samples each (to_uint8 of noised copies), `video_eval.main` with --modes all: the pickle's three arrays
+    against the restatement at the tolerances above; a rerun has nothing to compute."""
+    _, w = _embedder()
+    T, OBS, S = 5, 2, 64
+    vids = _frames(2 * T, S, S, seed=50).reshape(2, T, 3, S, S)
+    np.save(tmp_path / "videos.npy", vids.numpy())
+    (tmp_path / "run" / "samples").mkdir(parents=True)
+    gen = torch.Generator().manual_seed(51)
+    samples = {}
+    for v in range(2):
+        for k in range(2):
+            noisy = (vids[v] + 0.1 * (k + 1) * torch.randn(vids[v].shape, generator=gen)).clamp(-1, 1)
+            samples[v, k] = to_uint8(noisy.numpy())
+            np.save(tmp_path / "run" / "samples" / f"sample_{v:04d}-{k}.npy", samples[v, k])
+    feat = (0, 3, 6, 8, 10)
+    tv = {f"features.{feat[k]}.{p}": w[f"conv{k + 1}.{p}"] for k in range(5) for p in ("weight", "bias")}
+    lin = {f"lin{k}.model.1.weight": w[f"lin{k + 1}"].view(1, -1, 1, 1) for k in range(5)}
+    torch.save(tv, tmp_path / "alexnet.pth")
+    torch.save(lin, tmp_path / "alex.pth")
+    argv = ["--eval_dir", str(tmp_path / "run"), "--videos", str(tmp_path / "videos.npy"), "--obs_length", str(OBS), "--modes", "all",
+            "--lpips_weights", f"{tmp_path / 'alexnet.pth'},{tmp_path / 'alex.pth'}"]
+    path = ve.main(argv)
+    out = capsys.readouterr().out
+    assert "fvd is not computed here" in out and "Saved metrics to" in out
+    assert path == tmp_path / "run" / f"metrics_2-2-{T}.pkl"
+    with open(path, "rb") as f:
+        got = pickle.load(f)
+    assert sorted(got) == ["lpips", "psnr", "ssim"]
+    found = ve.discover_samples(tmp_path / "run")
+    _, gap_s, gap_p = _restated(2.0)
+    for v in range(2):
+        gt01 = ((vids[v].numpy() - (-1)) / 2).astype(np.float32)[OBS:]
+        for k, p in enumerate(found[v]):
+            pred = np.load(p)[OBS:]
+            s64, p64 = mr.frame_ssim_psnr(gt01, pred, 2.0, np.float64)
+            assert np.abs(got["ssim"][v, k] - s64).max() <= max(gap_s, SSIM_FLOOR)
+            assert (np.abs(got["psnr"][v, k] - p64) / np.abs(p64)).max() <= max(gap_p, PSNR_FLOOR)
+            a = torch.from_numpy(gt01) * 2 - 1
+            b = torch.from_numpy(mr.u8_to_float(pred)) * 2 - 1
+            want, atol = _lpips_want(a, b, w)
+            assert (want > 1000 * atol).all()
+            assert (np.abs(got["lpips"][v, k] - want) <= DIST_RTOL * want).all()
+    for m in got.values():
+        assert m.shape == (2, 2, T - OBS) and m.dtype == np.float64
+    before = os.path.getmtime(path)
+    assert ve.main(argv) == path
+    assert "No metrics to compute." in capsys.readouterr().out
+    assert os.path.getmtime(path) == before

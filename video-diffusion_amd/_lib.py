@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # per-source flags on top of the common ones.  conv_wino_z128.hip: its main loop is ONE fully unrolled body of 288 MFMA slots; past
 # LLVM's default size limit for `#pragma unroll` (16 k IR instructions) hipcc silently keeps the loops and indexes the register
@@ -136,6 +136,7 @@ _I = ctypes.c_int
 _L = ctypes.c_longlong
 _U = ctypes.c_ulonglong
 _F = ctypes.c_float
+_D = ctypes.c_double
 
 # name -> (restype, argtypes); every symbol declared in include/vd_amd.h
 SIGNATURES = {
@@ -231,6 +232,8 @@ SIGNATURES = {
     "vd_lpips_dim": (_L, [_I, _I]),
     "vd_lpips_embed": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "vd_fps_select": (_I, [_I, _I, _L, _P, _I, _P, _I, _P, _P, _P]),
+    "vd_frame_metrics": (_I, [_I, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P]),
+    "vd_pair_sqdist": (_I, [_I, _L, _P, _P, _P, _P]),
 }
 
 _lib = None

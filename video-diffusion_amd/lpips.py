@@ -176,6 +176,28 @@ class LpipsAlex:
         x = frames.to(device=self.device, dtype=torch.float32)
         return self._embed_device(x).reshape(x.shape[0], -1, 1, 1)
 
+    def distance(self, a, b, chunk=32):
+        """LPIPS of frame pairs: a, b (N, 3, H, W) in [-1, 1] (any device) -> (N,) float64 numpy, `lpips.LPIPS(net='alex',
+        spatial=False)(a, b)` of the reference's compute_lpips_lazy (scripts/video_eval.py:228-252).  The distance of two frames is the
+        squared L2 distance of their embeddings: each tap of the embedding is the channel-normalised feature times sqrt(lin weight) and
+        1 / sqrt(h w), so ||e(a) - e(b)||^2 = sum over taps of the spatial mean of sum_c w_c (n_a - n_b)^2.  Both sets are embedded `chunk`
+        frames at a time (a 500-frame 128 x 128 video never holds 2 x 500 x 148 608 floats); a frame's embedding does not depend on
+        its chunk, so neither does the result."""
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"LPIPS distance: shapes differ, {tuple(a.shape)} and {tuple(b.shape)}")
+        if chunk < 1:
+            raise ValueError("LPIPS distance: chunk >= 1")
+        a = a.to(device=self.device, dtype=torch.float32)
+        b = b.to(device=self.device, dtype=torch.float32)
+        N = a.shape[0]
+        out = torch.empty(N, dtype=torch.float64, device=self.device)
+        for k in range(0, N, chunk):
+            ea, eb = self._embed_device(a[k:k + chunk]), self._embed_device(b[k:k + chunk])
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().vd_pair_sqdist(ea.shape[0], ea.shape[1], _lib.ptr(ea), _lib.ptr(eb), _lib.ptr(out[k:k + chunk]),
+                                                     _lib.current_stream()))
+        return out.cpu().numpy()
+
     def embed(self, videos, indices):
         """videos (B, T, 3, H, W), indices: list of frame indices -> (B, len(indices), D) on self.device; the frames are gathered
         where the videos live and cross to the device in one copy."""

@@ -325,12 +325,15 @@ def add_lpips_arguments(ap):
     return ap
 
 
+LPIPS_WEIGHTS_NEEDED = "needs --lpips_weights PATH[,PATH] (the LPIPS AlexNet weights do not ship)"
+
+
 def parse_with_lpips(ap, argv):
     """parse_args + the refusal of --adaptive_distance lpips without weights (unless an embedder is registered already)."""
     args = ap.parse_args(argv)
     if (getattr(args, "adaptive_distance", "l2") == "lpips" and not getattr(args, "lpips_weights", None)
             and inference_util._lpips_embedder is None):
-        ap.error("--adaptive_distance lpips needs --lpips_weights PATH[,PATH] (the LPIPS AlexNet weights do not ship)")
+        ap.error(f"--adaptive_distance lpips {LPIPS_WEIGHTS_NEEDED}")
     return args
 
 
