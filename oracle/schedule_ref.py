@@ -6,7 +6,7 @@ import this file; the shipped path lives in `video-diffusion_amd/` and never
 touches `oracle/`.
 
 Pinned by: tests/golden/schedule_*.json + tests/golden/space_timesteps.json,
-generated from the imported reference by tools/gen_golden.py.
+generated from the imported reference by tools/golden/schedules.py.
 
 Follows (reference file:line, relative to /root/reference):
   - get_named_beta_schedule      improved_diffusion/gaussian_diffusion.py:20-52

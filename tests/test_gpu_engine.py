@@ -75,7 +75,7 @@ def test_p_sample_and_ddim_match_reference_golden():
 
 
 def _denoised_fn(x):
-    """tools/gen_golden_r3.py: the function the reference was run with."""
+    """tools/golden/_common.py: denoised_fn: the function the reference was run with."""
     return 1.3 * torch.tanh(1.5 * x) + 0.05
 
 
@@ -241,7 +241,7 @@ def test_full_size_model_one_clip_vs_oracle():
 @pytest.mark.parametrize("name", ["unet_full64.npz", "unet_full128.npz"])
 def test_full_size_models_vs_reference_golden(name):
     """The DEFAULT models (116 M parameters at 64x64, 119 M at 128x128) against eps the IMPORTED REFERENCE produced for one
-    clip (tools/gen_golden_r3.py full; 0.8 / 1.5 MB fixtures): full-size parity pinned on reference output, not only on the
+    clip (tools/golden/full_size.py: full; 0.8 / 1.5 MB fixtures): full-size parity pinned on reference output, not only on the
     oracle.  The window is rebuilt from its seed; the fixture carries checksums of the inputs it was made from."""
     rec = load_npz(name)
     cfg = json.loads(str(rec["cfg_json"]))
@@ -257,7 +257,7 @@ def test_full_size_models_vs_reference_golden(name):
 
 def test_headline_window_vs_reference_golden():
     """The HEADLINE window itself -- default 116 M model, B = 8 x T = 16 x 64 x 64, 4 observed frames, bench.py's make_window --
-    against eps the IMPORTED REFERENCE produced for it (tools/gen_golden_r4.py b8, 31 s on the build box): every 4th pixel of
+    against eps the IMPORTED REFERENCE produced for it (tools/golden/full_size.py: b8, 31 s on the build box): every 4th pixel of
     every frame at the tier's tolerance, and per-frame fp64 sums / sums of squares of the FULL output (a wrong pixel anywhere
     moves them: 12 288 values per frame, bound = tolerance x sqrt(n) x 8 for the sum).  Then the same eps from the oracle
     (12 s per step on 16 cores) where the box is fast enough."""
@@ -287,7 +287,7 @@ def test_headline_window_vs_reference_golden():
 def test_predict_xstart_matches_reference_golden():
     """predict_xstart=True (ModelMeanType.START_X; script_util.py:429-431, gaussian_diffusion.py:326-341): the network's output IS
     the x_0 prediction -- process_xstart(model_output), the posterior mean from it, DDIM's eps derived from it -- against dicts
-    the imported reference produced (tools/gen_golden_r4.py xstart): p_mean_variance, p_sample, ddim_sample (eta 0, 1) at
+    the imported reference produced (tools/golden/steps.py: xstart): p_mean_variance, p_sample, ddim_sample (eta 0, 1) at
     t = 249, 120, 1, 0, clip on and off, recorded noise."""
     rec = load_npz("xstart_tiny.npz")
     cfg = json.loads(str(rec["cfg_json"]))
@@ -455,7 +455,7 @@ def test_p_sample_loop_and_ddim_loop_contracts():
 @pytest.mark.parametrize("tag,vertical,obs_frames", [("v2_xtm1", 2, "x_t_minus_1"), ("v0_x0", 0, "x_0"), ("v5_x0", 5, "x_0")])
 def test_full_sampler_matches_reference_golden(monkeypatch, tag, vertical, obs_frames):
     """the vertical + horizontal sampler (scripts/video_sample_full.py:50-323) on the HIP engine against
-    the samples the reference itself produced on CPU (tools/gen_golden_full.py), replaying its randn_like sequence:
+    the samples the reference itself produced on CPU (tools/golden/jobs.py: full_sampler), replaying its randn_like sequence:
     4 autoreg windows x (2 vertical + 3 horizontal) steps with observed_frames = x_t_minus_1, the all-horizontal and
     the all-vertical split."""
     from video_diffusion_amd import gaussian_diffusion as gdm
@@ -614,7 +614,7 @@ def test_out_of_range_timestep_is_loud():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# a10 / a12: the two loops against what the imported reference produced (tools/gen_golden_loops.py)
+# a10 / a12: the two loops against what the imported reference produced (tools/golden/loops_nll.py: loops)
 def _cpu_draws(monkeypatch):
     """The reference draws everything from torch's global CPU generator; route the mirror's draws there too (the engine
     lives on the GPU, whose generator is a different stream)."""
@@ -1137,7 +1137,7 @@ def test_256_topology_miniature_vs_oracle():
 @pytest.mark.parametrize("case", ["c32", "c64", "c64tab"])
 def test_use_gradient_method_matches_reference_golden(case):
     """p_mean_variance / p_sample with use_gradient_method=True (gaussian_diffusion.py:264-271,350-364) against what the
-    imported reference's autograd produced (tools/gen_golden_r3.py grad): x.grad itself, the shifted mean, p_sample's draw.
+    imported reference's autograd produced (tools/golden/guidance.py: grad): x.grad itself, the shifted mean, p_sample's draw.
     c32: 32 base channels (generic conv / split GEMM kernels), c64: 64 (Winograd backward-data on the rotated transposed
     image, split-K on the small grids), c64tab: bucket-table RPE, no scale-shift norm.  Tolerance: the gradient is O(10)
     and passes through ~60 layers twice; 2e-4 of its largest entry + 1e-3 relative (observed: a few 1e-5 of the scale)."""
@@ -1352,7 +1352,7 @@ def test_configs0_shapes_default_model_short_windows_vs_oracle(Tw, n_obs):
 def test_nll_path_with_predict_xstart_matches_reference_golden(monkeypatch):
     """The NLL path with predict_xstart=True (ModelMeanType.START_X; gaussian_diffusion.py:750-790 on top of :326-341): the
     reference runs it, rounds 2-4 raised NotImplementedError.  _vb_terms_bpd at t = 4, 2, 0 (clip on / off, masked / unmasked) and
-    calc_bpd_loop_subsampled against tests/golden/nll_xstart_tiny.npz (tools/gen_golden_r5.py, imported reference)."""
+    calc_bpd_loop_subsampled against tests/golden/nll_xstart_tiny.npz (tools/golden/loops_nll.py: nll_xstart, imported reference)."""
     rec = load_npz("nll_xstart_tiny.npz")
     cfg = json.loads(str(rec["cfg_json"]))
     assert cfg["predict_xstart"] is True
@@ -1382,7 +1382,7 @@ def test_nll_path_with_predict_xstart_matches_reference_golden(monkeypatch):
 def test_return_attn_weights_with_denoised_fn_matches_reference_golden():
     """return_attn_weights TOGETHER with denoised_fn (gaussian_diffusion.py:274-324 allows it; rounds 3-4 raised): the maps of the
     step's one forward, the sample / pred_xstart of the callback path, and p_mean_variance's dict, against
-    tests/golden/attn_denoised_tiny.npz (tools/gen_golden_r5.py)."""
+    tests/golden/attn_denoised_tiny.npz (tools/golden/steps.py: attn_denoised)."""
     rec = load_npz("attn_denoised_tiny.npz")
     cfg = json.loads(str(rec["cfg_json"]))
     model, diff = engine(cfg)

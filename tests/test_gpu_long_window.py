@@ -200,7 +200,7 @@ def golden_window(rec):
 
 @pytest.mark.parametrize("case", ["rpe", "nopad", "table"])
 def test_eps_matches_reference_golden_long(case):
-    """unet_tiny_long.npz (tools/gen_golden_long_window.py): T = 48, B = 2, 8 padding frames in no mask; RPE nets with both
+    """unet_tiny_long.npz (tools/golden/long_window.py: unet_tiny_long): T = 48, B = 2, 8 padding frames in no mask; RPE nets with both
     padding rules, and the bucket tables."""
     rec = load_npz("unet_tiny_long.npz")
     cfg = json.loads(str(rec[f"{case}_cfg_json"]))

@@ -129,7 +129,7 @@ def test_factory_error_behaviour():
     with pytest.raises(ValueError, match="cannot create exactly"):
         vda.create_video_model_and_diffusion(**{**d, "timestep_respacing": "ddim300"})
     # do_cond_marg=False: the reference hands cond_emb_type to UNetVideoModel -> UNetModel.__init__, which does not take it
-    # (script_util.py:275-300; probed on the imported reference by tools/gen_golden_r4.py): same exception, same text
+    # (script_util.py:275-300; probed on the imported reference by tools/golden/steps.py: probe_no_cond_marg): same exception, same text
     with pytest.raises(TypeError, match=r"UNetModel.__init__\(\) got an unexpected keyword argument 'cond_emb_type'"):
         vda.create_video_model_and_diffusion(**{**d, "do_cond_marg": False})
     from video_diffusion_amd import gaussian_diffusion as gd
@@ -167,7 +167,7 @@ def test_engine_reports_errors_not_crashes():
 
 def test_eval_dir_naming_matches_reference(tmp_path):
     """improved_diffusion/test_util.py:65-132 naming rules against strings produced by the reference
-    (tools/gen_golden_full.py): results/<subpath>/<stem>[_ddim][_respace<X>] and the run identifier."""
+    (tools/golden/jobs.py: eval_paths): results/<subpath>/<stem>[_ddim][_respace<X>] and the run identifier."""
     from argparse import Namespace
 
     from helpers import load_json
@@ -198,7 +198,7 @@ def test_eval_dir_naming_matches_reference(tmp_path):
 
 def test_remaining_schedulers_match_reference():
     """goal-directed / visualisation / frameskip schedules (inference_util.py:534-776) against the
-    sequences -- and the failures -- of the reference itself (tools/gen_golden_full.py)."""
+    sequences -- and the failures -- of the reference itself (tools/golden/schedules.py: schedulers_more)."""
     import contextlib
     import io
 
@@ -228,7 +228,7 @@ def test_remaining_schedulers_match_reference():
 def test_adaptive_schedulers_match_reference_sequences():
     """adaptive-autoreg / adaptive-hierarchy-N with distance='l2' (inference_util.py:137-229,421-531): per-item observed
     lists picked by farthest-point selection on the frames themselves, against what the imported reference produced on
-    the same seeded videos (tools/gen_golden_adaptive.py).  Where the reference never terminates (hierarchy with no
+    the same seeded videos (tools/golden/schedules.py: schedulers_adaptive).  Where the reference never terminates (hierarchy with no
     observed frames: its backwards search for a finished frame runs below index 0 forever) the mirror raises."""
     import torch
     rec = load_json("schedulers_adaptive.json")
@@ -406,7 +406,7 @@ def test_nll_window_table_equals_the_per_item_construction():
 def test_integration_import_block_resolves_every_name_the_script_uses(tmp_path):
     """INTEGRATION.md A shows the import swap a maintainer makes in scripts/video_sample.py:12-19.  The 'after' half is executed
     as written, and every attribute the reference's scripts take from the swapped modules (tests/golden/script_imports.json,
-    tools/gen_script_imports.py) must resolve in the mirror -- a block that leaves `dist_util` or `test_util` unbound is a NameError
+    tools/golden/jobs.py: script_imports) must resolve in the mirror -- a block that leaves `dist_util` or `test_util` unbound is a NameError
     at the script's first use of them.  `dist_util.load_state_dict` must open a checkpoint file like `torch.load`."""
     import torch
     text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -664,3 +664,87 @@ def test_windowed_sampler_host_loop_and_all_timestep_record_against_a_plain_rest
         assert np.array_equal(every, rec.numpy()), mode
         plain, placeholder = infer_video(mode, Model(), Diff(), batch, mf, obs, step, adaptive_distance="l2")
         assert np.array_equal(plain, got) and placeholder.shape == (1,)
+
+
+def test_golden_manifest_names_exactly_the_committed_fixtures():
+    """tools/golden/__init__.py: MANIFEST -- no orphan fixture under tests/golden/, no producer without a file; every entry is
+    (producer, rough seconds, needs a full-size model?)."""
+    from tools.golden import MANIFEST, SKIPPED_KEYS
+    assert set(MANIFEST) == set(os.listdir(os.path.join(ROOT, "tests", "golden")))
+    for name, (producer, seconds, full_size) in MANIFEST.items():
+        assert callable(producer) and seconds > 0 and isinstance(full_size, bool), name
+    assert set(SKIPPED_KEYS) <= set(MANIFEST)
+
+
+def test_golden_command_works_without_the_reference(tmp_path):
+    """`python -m tools.golden` in a child interpreter with --reference pointing at a directory that does not exist: `list` prints
+    every fixture, `check` exits non-zero with one line that names the missing directory (no traceback from inside an import)."""
+    import subprocess
+    import sys
+    from tools.golden import MANIFEST
+    missing = str(tmp_path / "no_such_reference")
+
+    def run(*argv):
+        return subprocess.run([sys.executable, "-m", "tools.golden", *argv, "--reference", missing], cwd=ROOT, capture_output=True, text=True)
+
+    r = run("list")
+    assert r.returncode == 0, r.stderr
+    assert [line.split()[0] for line in r.stdout.splitlines()] == list(MANIFEST)
+    r = run("check")
+    assert r.returncode != 0 and missing in r.stderr and "Traceback" not in r.stderr and "ImportError" not in r.stderr, r.stderr
+    r = run("check", "space_timesteps.json")
+    assert r.returncode != 0 and missing in r.stderr and "Traceback" not in r.stderr, r.stderr
+    assert not os.path.exists(missing)
+
+
+def test_golden_compare_is_on_content_and_names_what_differs(tmp_path):
+    """tools/golden/_compare.py: compare -- what `check` reports.  Equal content in a differently ordered, re-compressed archive
+    passes; one flipped mantissa bit, a changed dtype, a missing key and a changed string each fail and are named."""
+    from tools.golden._compare import compare
+    rng = np.random.RandomState(3)
+    base = dict(eps=rng.randn(2, 3, 4).astype(np.float32), t=np.array([200, 200]), cfg_json=np.array('{"T": 4}'), n=np.array(7),
+                nan=np.array([np.nan, 1.0], np.float32))
+    a = str(tmp_path / "a.npz")
+    np.savez_compressed(a, **base)
+
+    def other(**change):
+        d = {k: base[k] for k in reversed(list(base))}
+        d.update(change)
+        d = {k: v for k, v in d.items() if v is not None}
+        p = str(tmp_path / f"b{len(os.listdir(tmp_path))}.npz")
+        np.savez(p, **d)                                       # uncompressed, keys in the opposite order
+        return p
+
+    assert compare(a, other()) is None
+    flipped = base["eps"].copy()
+    flipped.view(np.uint32)[1, 2, 3] ^= 1
+    msg = compare(a, other(eps=flipped))
+    assert "'eps'" in msg and "1 of 24 elements" in msg and "max |delta|" in msg
+    msg = compare(a, other(eps=base["eps"].astype(np.float64)))
+    assert "'eps'" in msg and "float32" in msg and "float64" in msg
+    msg = compare(a, other(t=base["t"].reshape(2, 1)))
+    assert "'t'" in msg and "shape" in msg
+    msg = compare(a, other(n=None))
+    assert "'n'" in msg and "key sets differ" in msg
+    msg = compare(a, other(extra=np.zeros(1)))
+    assert "'extra'" in msg
+    msg = compare(a, other(cfg_json=np.array('{"T": 5}')))
+    assert "'cfg_json'" in msg and "strings differ" in msg
+    msg = compare(a, other(nan=np.array([np.nan, np.float32(1.0) + np.float32(2.0 ** -23)], np.float32)))
+    assert "'nan'" in msg and "1 of 2 elements" in msg
+
+    def js(name, obj):
+        p = str(tmp_path / name)
+        json.dump(obj, open(p, "w"), indent=len(name) % 3)
+        return p
+
+    rec = {"f.npz": dict(params=116, reference_s_per_step=1.86, oracle_s_per_step=1.89, shape=[1, 16, 3, 64, 64])}
+    ja = js("a.json", rec)
+    assert compare(ja, js("b.json", {"f.npz": dict(reversed(list(rec["f.npz"].items())))})) is None
+    slower = {"f.npz": {**rec["f.npz"], "reference_s_per_step": 15.4}}
+    assert "reference_s_per_step" in compare(ja, js("c.json", slower))
+    assert compare(ja, js("d.json", slower), skip_keys=("reference_s_per_step", "oracle_s_per_step")) is None
+    msg = compare(ja, js("e.json", {"f.npz": {**rec["f.npz"], "shape": [1, 16, 3, 64, 32]}}), skip_keys=("reference_s_per_step",))
+    assert "f.npz.shape[4]" in msg and "64" in msg and "32" in msg
+    assert "keys differ" in compare(ja, js("f.json", {"f.npz": {k: v for k, v in rec["f.npz"].items() if k != "params"}}))
+    assert compare(ja, js("g.json", {"f.npz": {**rec["f.npz"], "params": 116.0}})) is not None      # int vs float: a changed type

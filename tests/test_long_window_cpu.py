@@ -1,4 +1,4 @@
-"""CPU: the oracle (oracle/unet_ref.py) against the long-window golden vectors (tools/gen_golden_long_window.py: the imported
+"""CPU: the oracle (oracle/unet_ref.py) against the long-window golden vectors (tools/golden/long_window.py: unet_tiny_long; the imported
 reference at T = 48, B = 2, with padding frames, both padding rules and the bucket tables).  The GPU tests of windows above
 32 frames (tests/test_gpu_long_window.py) use this oracle as their checker."""
 import json

@@ -1,6 +1,6 @@
 """CPU: pin the oracle (oracle/*.py) against golden vectors minted from the imported reference.
 
-tools/gen_golden.py wrote tests/golden/ by running /root/reference on CPU; these
+The producers of tools/golden/ wrote tests/golden/ by running /root/reference on CPU; these
 tests never read the reference.  An oracle that fails here may not be used as a checker.
 """
 import json
@@ -143,7 +143,7 @@ def test_window_loop_matches_reference():
 @pytest.mark.parametrize("tag,vertical,obs_frames", [("v2_xtm1", 2, "x_t_minus_1"), ("v0_x0", 0, "x_0"), ("v5_x0", 5, "x_0")])
 def test_full_sampler_matches_reference(tag, vertical, obs_frames):
     """scripts/video_sample_full.py infer_video (vertical + horizontal loop nest) run by the reference itself
-    (tools/gen_golden_full.py) against the oracle's restatement, same global-generator noise sequence."""
+    (tools/golden/jobs.py: full_sampler) against the oracle's restatement, same global-generator noise sequence."""
     from video_diffusion_amd import inference_util as iu
     rec = load_npz("full_sampler_tiny.npz")
     cfg = json.loads(str(rec["cfg_json"]))
@@ -174,7 +174,7 @@ def _loops_setup(name):
 
 @pytest.mark.parametrize("obsf", ["x_0", "x_t_minus_1", "x_t"])
 def test_p_sample_loop_matches_reference(obsf):
-    """gaussian_diffusion.py:450-595 run by the reference from a seeded global generator (tools/gen_golden_loops.py):
+    """gaussian_diffusion.py:450-595 run by the reference from a seeded global generator (tools/golden/loops_nll.py: loops):
     the restatement must consume the generator in the same order (initial image; per step x_t_minus_1's noise, random_t's
     uniform, x_random's noise, p_sample's noise) to land on the same trajectory."""
     rec, s, kw = _loops_setup("loops_tiny.npz")
@@ -235,7 +235,7 @@ def test_nll_terms_match_reference():
 
 def test_full_size_oracle_matches_reference_golden():
     """The oracle at FULL size (default 64x64 model, 116 M parameters, one 16-frame clip) against eps of the imported
-    reference (tools/gen_golden_r3.py full).  The same script timed both on this container's 8 cores -- reference 1.86 s,
+    reference (tools/golden/full_size.py: full).  The same script timed both on this container's 8 cores -- reference 1.86 s,
     oracle 1.89 s per step, max |d eps| 1.9e-6 (tests/golden/full_size_reference_vs_oracle.json) -- which is what backs
     bench.py's `cpu_baseline.kind: "port"`: the restatement is the same workload as the reference."""
     rec = load_npz("unet_full64.npz")
@@ -263,7 +263,7 @@ def test_full_size_oracle_matches_reference_golden():
 @pytest.mark.parametrize("case", ["c32", "c64", "c64tab"])
 def test_guidance_gradient_matches_reference(case):
     """use_gradient_method (gaussian_diffusion.py:264-271,350-364): x.grad, the shifted mean and p_sample's draw of the
-    imported reference (tools/gen_golden_r3.py grad) against autograd through the oracle's own network."""
+    imported reference (tools/golden/guidance.py: grad) against autograd through the oracle's own network."""
     rec = load_npz("grad_tiny.npz")
     cfg = json.loads(str(rec[f"{case}_cfg_json"]))
     import video_diffusion_amd as vda
@@ -289,7 +289,7 @@ def test_guidance_gradient_matches_reference(case):
 def test_cond_emb_variants_and_learn_sigma_forward_match_reference(name):
     """cond_emb_type duplicate / all-initzero / t=0 (unet.py:932-947,1014-1019 -- 't=0' with the reference's write through an
     expanded tensor: a whole batch item gets timestep -1 once one of its frames is observed) and the 6-channel network of
-    learn_sigma=True at Boundary A (tools/gen_golden_r3.py variants)."""
+    learn_sigma=True at Boundary A (tools/golden/steps.py: variants)."""
     rec = load_npz("variants_tiny.npz")
     cfg = json.loads(str(rec[f"{name}_cfg_json"]))
     import video_diffusion_amd as vda

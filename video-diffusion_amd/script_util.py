@@ -44,7 +44,7 @@ def create_video_model(T, image_size, num_channels, num_res_blocks, learn_sigma,
         raise NotImplementedError("class_cond is not supported by the HIP engine")
     if not do_cond_marg:
         # script_util.py:275-300: ModelClass = UNetVideoModel, which is handed cond_emb_type=... and passes it on to
-        # UNetModel.__init__, which does not take it -- the reference cannot construct this model (tools/gen_golden_r4.py
+        # UNetModel.__init__, which does not take it -- the reference cannot construct this model (tools/golden/steps.py: probe_no_cond_marg
         # records the probe); same exception, same message
         raise TypeError("UNetModel.__init__() got an unexpected keyword argument 'cond_emb_type'")
     attention_ds = tuple(image_size // int(res) for res in attention_resolutions.split(","))
