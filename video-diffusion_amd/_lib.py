@@ -12,6 +12,8 @@ _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
 SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
+# every header a source may include: part of the library's identity and of each object's build stamp
+HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), HEADER]
 # per-source flags on top of the common ones.  conv_wino_z128.hip: its main loop is ONE fully unrolled body of 288 MFMA slots; past
 # LLVM's default size limit for `#pragma unroll` (16 k IR instructions) hipcc silently keeps the loops and indexes the register
 # arrays through scratch
@@ -42,11 +44,10 @@ def _read(path):
 
 def source_sha():
     """Identity of the library the sources beside this file would build: SHA-1 over the compiler flags, every csrc/*.hip in
-    SOURCES, vd_common.h and include/vd_amd.h -- by CONTENT, so a checkout / rsync / snapshot with arbitrary mtimes can
+    SOURCES and every header in HEADERS -- by CONTENT, so a checkout / rsync / snapshot with arbitrary mtimes can
     neither hide a stale binary nor force a rebuild of a fresh one.  The built library carries it (vd_source_sha())."""
     hipcc, flags = _toolchain()
-    return _sha("\0".join(flags), repr(sorted(SOURCE_FLAGS.items())), *[_read(os.path.join(_CSRC, s)) for s in SOURCES], _read(os.path.join(_CSRC, "vd_common.h")),
-                _read(HEADER))[:16]
+    return _sha("\0".join(flags), repr(sorted(SOURCE_FLAGS.items())), *[_read(os.path.join(_CSRC, s)) for s in SOURCES], *[_read(h) for h in HEADERS])[:16]
 
 
 def _stale():
@@ -77,7 +78,7 @@ def build(force=False, verbose=False):
             sha = source_sha()
             objdir = os.path.join(_CSRC, ".obj")
             os.makedirs(objdir, exist_ok=True)
-            hdr_bytes = [_read(os.path.join(_CSRC, "vd_common.h")), _read(HEADER)]
+            hdr_bytes = [_read(h) for h in HEADERS]
             # the library's identity as a translation unit of its own (generated: not part of the hash it states)
             idsrc = os.path.join(objdir, "build_id.cpp")
             with open(idsrc, "w") as f:

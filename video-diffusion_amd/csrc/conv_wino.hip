@@ -18,7 +18,7 @@
 //   * one barrier per chunk (128 MFMAs per wave).
 //   Output: Z[i][q] = sum_j M[i][j] A[j][q] is wave-local; the sum over i crosses waves through LDS once per block;
 //   wave (p,q) then owns output pixel (p,q) of every tile and adds bias + residual.
-#include "vd_common.h"
+#include "wino_common.h"
 
 namespace vd {
 
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(IgemmArgs a, WinoG
                 for (int h = 0; h < (TF4 ? 2 : 1); ++h) {            // TF4: rows 0..7 / 8..15 are two frames
                     float s = 0.f, ss = 0.f;
 #pragma unroll
-                    for (int r = h * (TF4 ? 8 : 0); r < (TF4 ? 8 * h + 8 : 16); ++r) { s += y[r]; ss = __builtin_fmaf(y[r], y[r], ss); }     // (explicit: see conv_wino_r64.hip)
+                    for (int r = h * (TF4 ? 8 : 0); r < (TF4 ? 8 * h + 8 : 16); ++r) wino_stat_add(s, ss, y[r]);
                     const int fs = TF4 ? 2 * m + h : 0;              // frame slot of the block
                     gsum[fs][n][0] += s; gsum[fs][n][1] += ss;
                 }
@@ -420,8 +420,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_kernel(IgemmArgs a, WinoG
     }
     WINO_STAMP(3);
 }
-
-static bool wino_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 bool conv_wino_supported(const IgemmArgs& a) {
     const int Hl = a.Hs << a.ups, Wl = a.Ws << a.ups;

@@ -9,21 +9,15 @@
 // chunk, straight from the raw patch -- and forms t = d[X] + s*d[S], the four column combinations and their split in its own
 // registers: the result IS the A fragment.  No V image in LDS, ONE barrier per TWO chunks (patch hand-over), four patch
 // buffers: a patch is requested three or four chunks ahead.
-//
-// Patch image (LDS-DMA: buffer_load_dwordx4 ... lds, lane l of a request writes 16 bytes at M0 + 16 l whatever address it
-// gathers from, zeros where that address fails the descriptor's range check): [row 18][x parity 2][slot 10][64 B = 16
-// channels of one pixel]; the four 16-byte quads of a pixel are stored at quad ^ ((row >> 1) & 3), so that the 16 lanes of
-// a ds_read_b128 group (four tile rows x four tile columns) fall on 16 different bank quads.
+// (Patch image, block map, output transform: wino_common.h.)
 #include <cstdlib>
 #include <cstring>
 
-#include "vd_common.h"
-
+#include "wino_common.h"
 
 namespace vd {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool F16>
 __device__ __forceinline__ f32x16 r64_mfma(u32x4 a, u32x4 b, f32x16 c) {
@@ -31,43 +25,18 @@ __device__ __forceinline__ f32x16 r64_mfma(u32x4 a, u32x4 b, f32x16 c) {
     else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-struct WinoR64Geom { int tiles_x, tiles_y, nbx, ncb, nitems, xcd_order, ksplit; int phase_cb = 0; int cgroup = 0; };   // ksplit > 1: blockIdx.y = the block's slice of the channel chunks
-// phase_cb > 0 (= real Cout / 32): the sub-pixel form of Upsample + conv (see conv3x3_wino_r64_ups_kernel)
-
-// Geometry of an item's patch image.  TF4 = false: one frame, 8 x 8 tiles (maps >= 16 x 16).  TF4 = true: FOUR frames of an
-// 8 x 8 map, 4 x 4 tiles each, a 10 x 10 patch per frame at a frame stride of FSB bytes (every stride a multiple of 256 bytes,
-// so the bank argument for the swizzle holds across tile rows and frames alike).
-template <bool TF4> struct R64G {
-    static constexpr int P = TF4 ? 10 : 18;                 // patch width
-    static constexpr int SPP = TF4 ? 6 : 10;                // 64-byte pixel slots per plane row (P / 2 pixels + 1 pad)
-    static constexpr int PLB = SPP * 64, RSB = 2 * PLB;
-    static constexpr int FSB = TF4 ? P * RSB : 0;           // frame stride
-    static constexpr int NX = TF4 ? 8 : 6;                  // DMA instructions per thread and patch (256 threads x 16 B each)
-    static constexpr int XBUF = NX * 4096;
-    static constexpr int MOFF = TF4 ? 2 * FSB : 8 * RSB;    // second M-tile: two frames / four tile rows further
-};
 #ifndef VD_R64_ABL
 #define VD_R64_ABL 0       // timing-only builds of the main loop, see below
 #endif
 namespace r64 {
-constexpr int NB = 4;                       // patch buffers
-// 4 patch buffers (98304 | 131072 bytes; the Z image, 64 KB, overlays them) + one more that only ever receives the requests
-// past the item's last chunk (see x_dma): 122880 | 163840
-template <bool TF4> constexpr int lds_bytes() { return (VD_R64_ABL & 32) ? 163840 : (NB + 1) * R64G<TF4>::XBUF; }
+template <bool TF4> constexpr int lds_bytes() { return (VD_R64_ABL & 32) ? 163840 : R64G<TF4>::LDS_BYTES; }
 }  // namespace r64
 
 #ifdef VD_WINO_TIMING
 // cycle stamps of ONE work item (wave 0 of block 7): 0 start, 1 loop start, 2 loop end; per cout tile n (3 + 4n ..): Z image
 // written, past the exchange barrier, output stored, statistics done; 14 / 15: the 100 MHz clock at start / end
 __device__ unsigned long long g_r64_stamp[16];
-#define R64_STAMP(i)                                                                                  \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x == 7) {                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                        \
-            g_r64_stamp[i] = (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_readcyclecounter(); \
-            __builtin_amdgcn_sched_barrier(0);                                                        \
-        }                                                                                             \
-    } while (0)
+#define R64_STAMP(i) VD_WINO_STAMP(g_r64_stamp, i)
 extern "C" int vd_debug_r64_stamps(unsigned long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_r64_stamp), sizeof(g_r64_stamp));
 }
@@ -86,28 +55,6 @@ extern "C" int vd_debug_r64_stamps(unsigned long long* host_out) {
 // patch: 16 - NX more LDS-DMA requests per thread and chunk, one per slot, read from the output buffer (one 4 KB line per request, the same
 // lines for the cout blocks of a patch, as V would be shared) into LDS beyond the patch buffers.  A best case: no pre-pass is timed.
 
-// block -> (tile group, first cout tile): blocks are dealt to the 8 XCDs round-robin; inside an XCD the cout blocks of one
-// patch are neighbours
-__device__ __forceinline__ void r64_item(const WinoR64Geom& g, int& bx, int& cob0) {
-    if (g.xcd_order && g.cgroup > 0) {
-        // sub-pixel form: 4 x the cout blocks (16 .. 32 weight slices of 1 - 2 MB against 4 MB of L2 per XCD).  With the cout
-        // block as the fast index every slice had two concurrent readers per XCD (one at 512 couts) and the loop waited on
-        // weights from beyond the L2: 1452 -> 1252 us only for a quarter fewer MFMAs, 338 -> 351 at 512 couts.  Here an XCD
-        // walks ALL its patches with four cout blocks before it takes the next four.
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3, px = g.nbx >> 3;
-        const int c_lo = loc % g.cgroup, rest = loc / g.cgroup;
-        cob0 = ((rest / px) * g.cgroup + c_lo) * 2;
-        bx = (rest % px) * 8 + xcd;
-    } else if (g.xcd_order) {
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        cob0 = (loc % g.ncb) * 2;
-        bx = (loc / g.ncb) * 8 + xcd;
-    } else {
-        bx = blockIdx.x % g.nbx;
-        cob0 = (blockIdx.x / g.nbx) * 2;
-    }
-}
-
 // JS >= 0: the sub-pixel form of nearest-x2 Upsample + conv3x3 (unet.py:70-77).  Output pixel (2y + a, 2x + b) only sees a 2 x 2
 // neighbourhood of the SOURCE map: rows (y-1, y) with weights (w0, w1 + w2) for a = 0, (y, y+1) with (w0 + w1, w2) for a = 1,
 // the same along x -- four 3x3 kernels with one zero row and one zero column each, convolved with the low-resolution map
@@ -117,15 +64,14 @@ __device__ __forceinline__ void r64_item(const WinoR64Geom& g, int& bx, int& cob
 // per group instead of four, three patch columns transformed instead of four; the zero row costs nothing to keep.  Same
 // products as F(2x2,3x3) on the upsampled map would form, a quarter of them skipped.
 template <bool TF4, bool F16, int JS>
-__device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& g) {
-    using namespace r64;
+__device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoItemGeom& g) {
     constexpr int NP = JS < 0 ? 4 : 3;                               // positions of a group
     constexpr int JLa[4] = {JS == 0 ? 1 : 0, JS == 0 ? 2 : 1, JS == 0 ? 3 : 2, 3};     // position li of a group -> column j of the row
     constexpr int ORDa[4] = {JS == 0 ? 2 : 0, JS == 0 ? 1 : 2, JS == 0 ? 3 : 1, 3};    // the patch column position li recomputes for the next group
     constexpr bool PH = JS >= 0;
     constexpr int NSLOT = F16 ? 6 : 12;                              // MFMAs of a position: piece products x 2 cout tiles
     using G = R64G<TF4>;
-    constexpr int P = G::P, SPP = G::SPP, PLB = G::PLB, RSB = G::RSB, NX = G::NX, XBUF = G::XBUF;
+    constexpr int PLB = G::PLB, RSB = G::RSB, NX = G::NX, XBUF = G::XBUF, NB = G::NB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* const lds = reinterpret_cast<char*>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -141,7 +87,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     const int c_begin = ks * nchunk;
 
     int bx, cob0;
-    r64_item(g, bx, cob0);
+    wino_item<2, true>(g, bx, cob0);
     const int bxx = bx % g.tiles_x; bx /= g.tiles_x;
     const int byy = bx % g.tiles_y; bx /= g.tiles_y;
     const int f0 = TF4 ? bx * 4 : bx;                                 // first frame of the item
@@ -150,34 +96,18 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     const int patch_id = (f0 * g.tiles_y + byy) * g.tiles_x + bxx;
 #endif
 
-    // ---- patch staging: thread -> 16-byte LDS slots e*256 + tid; the slot at quad position lq of patch row py holds the
-    // pixel's quad lq ^ ((py >> 1) & 3)
+    // ---- patch staging: thread -> 16-byte LDS slots e*256 + tid
     unsigned xo[NX];
 #pragma unroll
     for (int e = 0; e < NX; ++e) {
-        const int gs = e * 256 + tid, lq = gs & 3, ps0 = gs >> 2;
-        const int fl = TF4 ? ps0 / (P * 2 * SPP) : 0, ps = TF4 ? ps0 % (P * 2 * SPP) : ps0;   // frame of the item, slot inside its image
-        const int py = ps / (2 * SPP), r = ps % (2 * SPP), pxh = r % SPP, px = 2 * pxh + r / SPP;
-        const int ly = oy0 + py - 1, lx = ox0 + px - 1;
-        const bool in = fl < (TF4 ? 4 : 1) && f0 + fl < a.nfr && py < P && pxh < P / 2 && ly >= 0 && ly < Hl && lx >= 0 && lx < Wl;
-        xo[e] = in ? (unsigned)(((f0 + fl) * a.Hs + (ly >> a.ups)) * a.Ws + (lx >> a.ups)) * (unsigned)(a.Cin * 4) + (unsigned)((lq ^ ((py >> 1) & 3)) * 16) +
-                         (unsigned)(c_begin * 64)
-                   : 0x80000000u;
+        const WinoPatchSlot ps = wino_patch_slot<TF4>(e * 256 + tid, oy0, ox0, Hl, Wl);
+        xo[e] = ps.in && f0 + ps.fl < a.nfr
+                    ? (unsigned)(((f0 + ps.fl) * a.Hs + (ps.ly >> a.ups)) * a.Ws + (ps.lx >> a.ups)) * (unsigned)(a.Cin * 4) + (unsigned)(ps.quad * 16) + (unsigned)(c_begin * 64)
+                    : 0x80000000u;
     }
     const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, a.nfr * a.Hs * a.Ws * a.Cin * 4, 0x00020000);
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    // A request past the item's last chunk must not land in the output transform's Z image.  It is NOT skipped by a branch:
-    // hipcc's s_waitcnt insertion merges the two paths of a conditional request to the one with FEWER loads in flight, i.e.
-    // every wait for a weight fragment behind it becomes a wait for the patch itself.  The request always issues; when it is
-    // late it goes through a descriptor of zero records (no memory access, zeros) into the spare fifth buffer.
-    const auto xnull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, 0, 0x00020000);
-    auto x_dma_one = [&](int chunk, int e) {
-#if defined(__HIP_DEVICE_COMPILE__)      // (hipcc's host pass drops a kernel whose body names this builtin)
-        const bool live = chunk < nchunk;
-        const int bufi = live ? (chunk & (NB - 1)) : NB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(live ? xsrc : xnull, (lds_ptr)(lds + bufi * XBUF + e * 4096 + wi * 1024), 16, xo[e], chunk * 64, 0, 0);
-#endif
-    };
+    const auto xnull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, 0, 0x00020000);      // requests past the last chunk
+    auto x_dma_one = [&](int chunk, int e) { wino_patch_dma<G>(xsrc, xnull, lds, wi, chunk, nchunk, e, xo[e]); };
     auto x_dma = [&](int chunk) {
 #pragma unroll
         for (int e = 0; e < NX; ++e) x_dma_one(chunk, e);
@@ -189,7 +119,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     const unsigned xtra_base = ((unsigned)patch_id * xtra_span) % (xtra_bytes - xtra_span) + (unsigned)(tid * 16);
     auto x_extra = [&](int chunk, int i) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(xtra_src, (lds_ptr)(lds + NB * XBUF + i * 4096 + wi * 1024), 16, xtra_base, (chunk * (16 - NX) + i) * 4096, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(xtra_src, (wino_lds_ptr)(lds + NB * XBUF + i * 4096 + wi * 1024), 16, xtra_base, (chunk * (16 - NX) + i) * 4096, 0, 0);
 #endif
     };
 #endif
@@ -260,8 +190,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     // r * 2^12, round -- and channels 2k, 2k+1 of the NEXT position's V (column combination X -/+ Y).  `early`: the piece is read
     // by the MFMA of the next slot, and a VALU write needs two wait states before an MFMA reads it as A / B: the combination
     // goes behind the conversion.
-#define VD_R64_A1 "v_fma_mix_f32 %3, %5, -1.0, %6 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %4, %5, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t" \
-                  "v_ldexp_f32 %3, %3, 12\n\tv_ldexp_f32 %4, %4, 12\n\t"
+#define VD_R64_A1 VD_WINO_A1(3, 4, 5, 6, 7)
 #define VD_R64_A1_OPS : "=&v"(af[cur][1][k]), "=&v"(tv[nxt][2 * k]), "=&v"(tv[nxt][2 * k + 1]), "=&v"(r0), "=&v"(r1) \
                       : "v"(af[cur][0][k]), "v"(tv[cur][2 * k]), "v"(tv[cur][2 * k + 1]), "v"(t[cx][2 * k]), "v"(t[cy][2 * k]), "v"(t[cx][2 * k + 1]), "v"(t[cy][2 * k + 1])
     auto f16_slot_a = [&](int cur, int nxt, int k, int jn, bool early) {
@@ -303,12 +232,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     // (n, piece) offsets 0 .. 3072 ride in the instruction's 12-bit immediate, the last two behind a second scalar base: two
     // scalar adds per position instead of six (every instruction of a one-wave-per-SIMD stream is an issue slot)
     constexpr bool B2R = F16;                                        // f16x3: piece 2 = 2^-12 x piece 0, formed in registers: four v_pk_mul_f16 instead of a 1 KiB load
-    const unsigned two_m12 = 0x0c000c00u;
-    auto b_third = [&](int j, int n) {
-        asm("v_pk_mul_f16 %0, %4, %8\n\tv_pk_mul_f16 %1, %5, %8\n\tv_pk_mul_f16 %2, %6, %8\n\tv_pk_mul_f16 %3, %7, %8"
-            : "=&v"(bfr[j][n][2][0]), "=&v"(bfr[j][n][2][1]), "=&v"(bfr[j][n][2][2]), "=&v"(bfr[j][n][2][3])
-            : "v"(bfr[j][n][0][0]), "v"(bfr[j][n][0][1]), "v"(bfr[j][n][0][2]), "v"(bfr[j][n][0][3]), "s"(two_m12));
-    };
+    auto b_third = [&](int j, int n) { wino_b_third(bfr[j][n][2], bfr[j][n][0]); };
     auto b_load_one = [&](int chunk, int j, int n, int p) {
         if (B2R && p == 2) return;
         const int idx = n * 3 + p, so = chunk * ustride + bsb + j * bstep;
@@ -474,9 +398,7 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
     R64_STAMP(2);
-    // ---- output transform, one cout tile at a time: Z[q] = sum_j M[wi][j] A[j][q] is wave-local, the sum over the rows
-    // crosses the waves through LDS; wave (p, q) = (wi >> 1, wi & 1) then owns output pixel (p, q) of every tile.
-    // Z image: [plane 2*i + q 8][m 2][c4 4][lane 64][4 floats] = 64 KB over the patch buffers.
+    // ---- output transform (wino_common.h), one cout tile at a time
     const int p = wi >> 1, q = wi & 1;
     // sub-pixel form: block blk = cob0 / 2 = pb * phase_cb + cb; cout tile n is phase (n, pb) of real couts 32*cb .. 32*cb + 31, its
     // pixel (y, x) of the low-resolution map goes to (2y + n, 2x + pb) of the output
@@ -486,24 +408,14 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
     const auto osrc = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)ks * (obytes >> 2), 0, obytes, 0x00020000);
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.out), 0, a.res ? obytes : 0, 0x00020000);
     const float sgn = p ? -1.f : 1.f;
-    float* Zs = smem;
     unsigned oo[2][16];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int tt = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int tx = TF4 ? tt & 3 : tt & 7, ty = TF4 ? (tt >> 2) & 3 : tt >> 3, nf = f0 + (TF4 ? tt >> 4 : 0);
-            const unsigned o = PH ? (unsigned)(((nf * Ho + 2 * (oy0 + 2 * ty + p)) * Wo + 2 * (ox0 + 2 * tx + q) + ppb) * a.ldo + pcb * 32 + lr) * 4u
-                                  : (unsigned)(((nf * Hl + oy0 + 2 * ty + p) * Wl + ox0 + 2 * tx + q) * a.ldo + cob0 * 32 + lr) * 4u;
-            oo[m][r] = nf < a.nfr ? o : 0x80000000u;                 // TF4: a frame past the end is neither read nor stored
-        }
+    wino_out_offsets<TF4, PH>(oo, lh, p, q, f0, a.nfr, oy0, ox0, Ho, Wo, a.ldo, (PH ? pcb : cob0) * 32 + lr, ppb);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         const int co = PH ? pcb * 32 + lr : (cob0 + n) * 32 + lr;
         const int nso = PH ? n * Wo * a.ldo * 4 : n * 128;             // byte offset of cout tile n: one output row down | 32 channels on
         const float bias = a.bias ? a.bias[co] : 0.f;
-        // F16: the weight row's power-of-two scale leaves here (image trailer: [Cout] s, [Cout] 1 / s; Cout = the image's 4 x real in the sub-pixel form)
+        // F16: the weight row's power-of-two scale (image trailer: [Cout] s, [Cout] 1 / s; Cout = the image's 4 x real in the sub-pixel form)
         const float winv = F16 ? (a.wwino + (size_t)24 * a.Cout * a.Cin)[a.Cout + (cob0 + n) * 32 + lr] : 1.f;
         // per-frame bias: TF1 one frame; TF4 registers 0..7 of M-tile m belong to frame 2m, 8..15 to frame 2m + 1
         float bvf[2][2];
@@ -521,97 +433,51 @@ __device__ __forceinline__ void r64_body(const IgemmArgs& a, const WinoR64Geom& 
             // Z = M A: columns (1, 1, 1, 0) and (0, 1, -1, -1); the column the sub-pixel form never computed is zero
             const f32x16 z0 = JS == 0 ? acc[m][1][n] + acc[m][2][n] : acc[m][0][n] + acc[m][1][n] + acc[m][2][n];
             const f32x16 z1 = JS == 3 ? acc[m][1][n] - acc[m][2][n] : acc[m][1][n] - acc[m][2][n] - acc[m][3][n];
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                *reinterpret_cast<f32x4*>(Zs + ((((wi * 2 + 0) * 2 + m) * 4 + c4) * 64 + lane) * 4) = f32x4{z0[4 * c4], z0[4 * c4 + 1], z0[4 * c4 + 2], z0[4 * c4 + 3]};
-                *reinterpret_cast<f32x4*>(Zs + ((((wi * 2 + 1) * 2 + m) * 4 + c4) * 64 + lane) * 4) = f32x4{z1[4 * c4], z1[4 * c4 + 1], z1[4 * c4 + 2], z1[4 * c4 + 3]};
-            }
+            wino_z_write(smem, wi, lane, m, z0, z1);
         }
         R64_STAMP(3 + 4 * n);
         __syncthreads();
         R64_STAMP(4 + 4 * n);
-        const float* zw = Zs + wi * 2048 + lane * 4;                 // Z[p + k][q] is plane wi + 2k
-        float gsum[TF4 ? 4 : 1][2] = {};
+        constexpr int NFS = TF4 ? 4 : 1;
+        float gsum[NFS][2] = {};
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            f32x16 y;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const float* zp = zw + (m * 4 + c4) * 256;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(zp) +
-                                (*reinterpret_cast<const f32x4*>(zp + 2 * 2048) + *reinterpret_cast<const f32x4*>(zp + 4 * 2048)) * sgn;
-                y[4 * c4] = v.x; y[4 * c4 + 1] = v.y; y[4 * c4 + 2] = v.z; y[4 * c4 + 3] = v.w;
-            }
-            if constexpr (F16) y = y * winv + rv[m];
-            else y += rv[m];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[r] += bvf[m][r >> 3];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)y[r]), osrc, oo[m][r], nso, 0);
-            if (a.stats) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int fs = TF4 ? 2 * m + (r >> 3) : 0;
-                    // explicit fma: left to -ffp-contract, hipcc fused the square into the sum in one unrolled copy of this loop
-                    // and not in the other -- a frame's statistics then depended on its place in a four-frame item (r04m)
-                    gsum[fs][0] += y[r]; gsum[fs][1] = __builtin_fmaf(y[r], y[r], gsum[fs][1]);
-                }
-            }
-        }
+        for (int m = 0; m < 2; ++m) wino_out_rows<F16, TF4>(smem, wi, lane, m, sgn, winv, rv[m], bvf[m], osrc, oo[m], nso, a.stats != nullptr, gsum);
         R64_STAMP(5 + 4 * n);
-        if (a.stats) {                                               // GroupNorm partial sums of the output
-            constexpr int NFS = TF4 ? 4 : 1;
-            __syncthreads();
-            double* red = reinterpret_cast<double*>(smem);           // [wave 4][lh 2][frame NFS][lr 32][2]
-#pragma unroll
-            for (int fs = 0; fs < NFS; ++fs) {
-                double* d = red + ((((wi * 2 + lh) * NFS + fs) * 32 + lr) * 2);
-                d[0] = (double)gsum[fs][0]; d[1] = (double)gsum[fs][1];
-            }
-            __syncthreads();
-            if (tid < NFS * 32) {
-                const int fs = tid >> 5, c = tid & 31;
-                double s = 0.0, ss = 0.0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { s += red[((k * NFS + fs) * 32 + c) * 2]; ss += red[((k * NFS + fs) * 32 + c) * 2 + 1]; }
+        if (a.stats)
+            wino_stats_reduce<NFS>(smem, tid, wi, lh, lr, gsum, [&](int fs, int c) -> double* {
                 const int nf = f0 + fs, sp = TF4 ? 0 : byy * g.tiles_x + bxx;
-                if (nf < a.nfr) {
-                    // sub-pixel form: four table entries per tile group, one per phase, over the real couts
-                    double* o = PH ? a.stats + (((size_t)nf * a.stats_split + sp * 4 + 2 * n + ppb) * (g.phase_cb * 32) + pcb * 32 + c) * 2
-                                   : a.stats + (((size_t)nf * a.stats_split + sp) * a.Cout + (cob0 + n) * 32 + c) * 2;
-                    o[0] = s; o[1] = ss;
-                }
-            }
-        }
+                if (nf >= a.nfr) return nullptr;
+                // sub-pixel form: four table entries per tile group, one per phase, over the real couts
+                return PH ? a.stats + (((size_t)nf * a.stats_split + sp * 4 + 2 * n + ppb) * (g.phase_cb * 32) + pcb * 32 + c) * 2
+                          : a.stats + (((size_t)nf * a.stats_split + sp) * a.Cout + (cob0 + n) * 32 + c) * 2;
+            });
         R64_STAMP(6 + 4 * n);
     }
     R64_STAMP(15);
 }
 
 template <bool TF4, bool F16>
-__global__ __launch_bounds__(256, 1) void conv3x3_wino_r64_kernel(IgemmArgs a, WinoR64Geom g) { r64_body<TF4, F16, -1>(a, g); }
+__global__ __launch_bounds__(256, 1) void conv3x3_wino_r64_kernel(IgemmArgs a, WinoItemGeom g) { r64_body<TF4, F16, -1>(a, g); }
 
 template <bool TF4, bool F16>
-__global__ __launch_bounds__(256, 1) void conv3x3_wino_r64_ups_kernel(IgemmArgs a, WinoR64Geom g) {
+__global__ __launch_bounds__(256, 1) void conv3x3_wino_r64_ups_kernel(IgemmArgs a, WinoItemGeom g) {
     int bx, cob0;
-    r64_item(g, bx, cob0);
+    wino_item<2, true>(g, bx, cob0);
     if ((cob0 >> 1) < g.phase_cb) r64_body<TF4, F16, 3>(a, g);       // phases (., 0): column 3 of U is zero
     else r64_body<TF4, F16, 0>(a, g);                                // phases (., 1): column 0
 }
 
 template <auto KERN>
-static int r64_launch(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& k, const WinoR64Geom& g) {
+static int r64_launch(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& k, const WinoItemGeom& g) {
     VD_RAISE_LDS(KERN, (size_t)160 * 1024);      // per kernel and device: each one that runs raises its own LDS limit once
     hipLaunchKernelGGL(KERN, grid, dim3(256), lds, s, k, g);
     VD_HIP(hipGetLastError());
     return 0;
 }
 
-static bool r64_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
 bool conv_wino_r64_supported(const IgemmArgs& a) {
     const int Hl = a.Hs << a.ups, Wl = a.Ws << a.ups;
-    return a.wsplit == 2 && a.wwino != nullptr && a.ksz == 3 && a.stride == 1 && a.pad == 1 && Hl == Wl && r64_pow2(Hl) && Hl >= 8 &&
+    return a.wsplit == 2 && a.wwino != nullptr && a.ksz == 3 && a.stride == 1 && a.pad == 1 && Hl == Wl && wino_pow2(Hl) && Hl >= 8 &&
            a.Cout % 64 == 0 && a.Cin % 32 == 0 && a.src1 == nullptr && a.C0 == a.Cin && a.affA == nullptr && a.act == 0 &&
            (size_t)a.nfr * a.Hs * a.Ws * a.Cin < (1u << 29) && (size_t)a.Cin * a.Cout * 96 < (1u << 31) &&
            (size_t)a.nfr * Hl * Wl * a.ldo < (1u << 29) && (a.res == nullptr || a.res_ld == a.ldo);
@@ -679,15 +545,9 @@ static int launch_conv_wino_r64_ups(const IgemmArgs& a, hipStream_t s) {
     VD_REQUIRE(a.ups == 1 && a.res == nullptr && a.fbias == nullptr && a.Cout % 64 == 0, "sub-pixel Upsample conv: no residual, no per-frame bias");
     VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_ups_stats_split(a.Hs), "GroupNorm partial table: split (sub-pixel form)");
     VD_REQUIRE((size_t)a.Cin * a.Cout * 4 * 96 < ((size_t)1 << 31), "sub-pixel weight image beyond 2 GiB");
-    WinoR64Geom g;
     const int Hl = a.Hs;
     const bool tf4 = Hl == 8;
-    g.tiles_x = tf4 ? 1 : Hl / 16; g.tiles_y = g.tiles_x;
-    g.nbx = g.tiles_x * g.tiles_y * (tf4 ? (a.nfr + 3) / 4 : a.nfr);
-    g.ncb = 4 * a.Cout / 64;
-    g.nitems = g.nbx * g.ncb;
-    g.xcd_order = g.nbx % 8 == 0;
-    g.ksplit = 1;
+    WinoItemGeom g = wino_item_geom(Hl, a.nfr, 4 * a.Cout, 64, tf4);
     g.phase_cb = a.Cout / 32;
     g.cgroup = g.ncb % 4 == 0 ? 4 : 2;                                // groups of 1 / 2 / 4 / 8 measured: 1 loses the patch reuse (1347 us at 256 couts), 2 .. 8 within noise
     IgemmArgs k = a;
@@ -704,13 +564,8 @@ int launch_conv_wino_r64(const IgemmArgs& a, hipStream_t s) {
     if (a.ups_phase) return launch_conv_wino_r64_ups(a, s);
     const int Hl = a.Hs << a.ups;
     VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl), "GroupNorm partial table: split");
-    WinoR64Geom g;
     const bool tf4 = Hl == 8;                       // four frames of 4 x 4 tiles per item
-    g.tiles_x = tf4 ? 1 : Hl / 16; g.tiles_y = g.tiles_x;
-    g.nbx = g.tiles_x * g.tiles_y * (tf4 ? (a.nfr + 3) / 4 : a.nfr);
-    g.ncb = a.Cout / 64;
-    g.nitems = g.nbx * g.ncb;
-    g.xcd_order = g.nbx % 8 == 0;
+    WinoItemGeom g = wino_item_geom(Hl, a.nfr, a.Cout, 64, tf4);
     // (no grouped cout walk here, unlike the sub-pixel form: 2 .. 8 cout blocks per patch, headline 27.55 ms with groups of 0 / 2 / 4;
     // re-measured in round 6 on the f16x3 kernel, LAB_NOTES R6)
     // split-K only with scratch from the caller (the engine's arena; the single-operator entry points run one slice)

@@ -14,40 +14,23 @@
 // per 128 couts, and the epilogue no longer sums position tiles.  The minus signs cost nothing for V3 (its column combination is
 // taken with swapped operands) and sixteen v_xor for V2 (the fragment is negated in place between its two uses).
 //
-// Everything else is conv_wino_r64.hip's: the LDS-DMA patch image and its swizzle, wave i = Winograd row i, the weight image
-// (split_pack.hip), one barrier per two chunks, requests one per MFMA slot.  A position is 24 or 48 slots here, so the weight
+// Everything else is as in conv_wino_r64.hip: the LDS-DMA patch image and its swizzle, the block map and the output transform
+// (wino_common.h), wave i = Winograd row i, the weight image (split_pack.hip), one barrier per two chunks, requests one per MFMA slot.  A position is 24 or 48 slots here, so the weight
 // fragments of the NEXT position (12 KiB per wave: 4 cout tiles x 3 pieces) have a whole position to arrive in a two-slot
 // register ring, and the vector work of the next position's two fragments (8 blocks of 12 instructions) is 2 - 4 per slot.
 // Served: f16x3, maps >= 16 x 16, Cout % 128 == 0, no split-K, not the sub-pixel Upsample form (conv_wino_r64.hip keeps those).
 #include <cstdlib>
 #include <cstring>
 
-#include "vd_common.h"
+#include "wino_common.h"
 
 namespace vd {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct WinoZ128Geom { int tiles_x, tiles_y, nbx, ncb, nitems, xcd_order; };
-
-namespace z128 {
-constexpr int NB = 4;                                          // patch buffers
-constexpr int P = 18, SPP = 10, PLB = SPP * 64, RSB = 2 * PLB, NX = 6, XBUF = NX * 4096, MOFF = 8 * RSB;
-constexpr int LDS_BYTES = (NB + 1) * XBUF;                     // + the spare buffer for requests past the last chunk
-}  // namespace z128
 
 // Variants built, measured and taken out (history: commit aa1331c): v_fma_mixlo/hi_f16 for the a1 piece (no faster, r05b), a uniform branch around
 // the residual requests (slower, r05u), register staging without the activation as a timing build (r05s: what the staging method alone is worth).
 #ifdef VD_WINO_TIMING
 __device__ unsigned long long g_z128_stamp[16];
-#define Z128_STAMP(i)                                                                                 \
-    do {                                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x == 7) {                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                        \
-            g_z128_stamp[i] = (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_readcyclecounter(); \
-            __builtin_amdgcn_sched_barrier(0);                                                        \
-        }                                                                                             \
-    } while (0)
+#define Z128_STAMP(i) VD_WINO_STAMP(g_z128_stamp, i)
 extern "C" int vd_debug_z128_stamps(unsigned long long* host_out) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_z128_stamp), sizeof(g_z128_stamp));
 }
@@ -65,8 +48,9 @@ extern "C" int vd_debug_z128_stamps(unsigned long long* host_out) {
 // carry nothing else, 6 ds_write_b128; the patch of chunk c + 2 is activated during chunk c from registers loaded at the end of chunk
 // c - 1, published by the barrier that stands in front of its first reader anyway.
 template <bool ACT>
-__global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, WinoZ128Geom g) {
-    using namespace z128;
+__global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, WinoItemGeom g) {
+    using G = R64G<false>;                                           // one frame, 8 x 8 tiles
+    constexpr int PLB = G::PLB, RSB = G::RSB, NX = G::NX, XBUF = G::XBUF, MOFF = G::MOFF, NB = G::NB, LDS_BYTES = G::LDS_BYTES;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* const lds = reinterpret_cast<char*>(smem);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -75,53 +59,35 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
     const int Hl = a.Hs, Wl = a.Ws;
     const int ncoblk = a.Cout >> 5, nchunk = a.Cin >> 4;
 
-    // block -> (tile group, first cout tile): dealt to the 8 XCDs round-robin, the cout blocks of one patch neighbours inside an XCD
     int bx, cob0;
-    if (g.xcd_order) {
-        const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-        cob0 = (loc % g.ncb) * 4;
-        bx = (loc / g.ncb) * 8 + xcd;
-    } else {
-        bx = blockIdx.x % g.nbx;
-        cob0 = (blockIdx.x / g.nbx) * 4;
-    }
+    wino_item<4>(g, bx, cob0);
     const int bxx = bx % g.tiles_x; bx /= g.tiles_x;
     const int byy = bx % g.tiles_y; bx /= g.tiles_y;
     const int f0 = bx;                                               // the item's frame
     const int ox0 = bxx * 16, oy0 = byy * 16;
 
-    // ---- patch staging (conv_wino_r64.hip): thread -> 16-byte LDS slots e*256 + tid; the slot at quad position lq of patch row py
-    // holds the pixel's quad lq ^ ((py >> 1) & 3)
+    // ---- patch staging: thread -> 16-byte LDS slots e*256 + tid
     unsigned xo[NX];
     unsigned ldo[ACT ? NX : 1];                                       // ACT: byte offset of the thread's slot e inside a patch buffer
     unsigned long long inm[ACT ? NX : 1];                             // ACT: lanes whose slot e lies inside the picture
 #pragma unroll
     for (int e = 0; e < NX; ++e) {
-        const int gs = e * 256 + tid, lq = gs & 3, ps = gs >> 2;
-        const int py = ps / (2 * SPP), r = ps % (2 * SPP), pxh = r % SPP, px = 2 * pxh + r / SPP;
-        const int ly = oy0 + py - 1, lx = ox0 + px - 1;
-        const bool in = py < P && pxh < P / 2 && ly >= 0 && ly < Hl && lx >= 0 && lx < Wl;
+        const int gs = e * 256 + tid;
+        const WinoPatchSlot ps = wino_patch_slot<false>(gs, oy0, ox0, Hl, Wl);
         if constexpr (ACT) {
-            // the thread keeps ONE channel quad (lq = tid & 3: its (A, B) are four registers per chunk) and writes it to the place the
-            // DMA image gives that quad: position lq ^ ((py >> 1) & 3) of the pixel's four 16-byte slots.  xo = the PIXEL index: the
-            // input may be a virtual concat of two tensors of different widths (unet.py:826-828), the byte offset is formed per source
-            xo[e] = in ? (unsigned)((f0 * a.Hs + ly) * a.Ws + lx) : 0x80000000u;
-            ldo[e] = (unsigned)(((gs & ~3) | (lq ^ ((py >> 1) & 3))) * 16);
-            inm[e] = __ballot(in);
+            // the thread keeps ONE channel quad (tid & 3: its (A, B) are four registers per chunk) and writes it to the place the DMA
+            // image gives that quad.  xo = the PIXEL index: the input may be a virtual concat of two tensors of different widths
+            // (unet.py:826-828), the byte offset is formed per source
+            xo[e] = ps.in ? (unsigned)((f0 * a.Hs + ps.ly) * a.Ws + ps.lx) : 0x80000000u;
+            ldo[e] = (unsigned)(((gs & ~3) | ps.quad) * 16);
+            inm[e] = __ballot(ps.in);
         } else {
-            xo[e] = in ? (unsigned)((f0 * a.Hs + ly) * a.Ws + lx) * (unsigned)(a.Cin * 4) + (unsigned)((lq ^ ((py >> 1) & 3)) * 16) : 0x80000000u;
+            xo[e] = ps.in ? (unsigned)((f0 * a.Hs + ps.ly) * a.Ws + ps.lx) * (unsigned)(a.Cin * 4) + (unsigned)(ps.quad * 16) : 0x80000000u;
         }
     }
     const auto xsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, a.nfr * a.Hs * a.Ws * (ACT ? a.C0 : a.Cin) * 4, 0x00020000);
-    const auto xnull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, 0, 0x00020000);
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    auto x_dma_one = [&](int chunk, int e) {                          // (a request past the last chunk always issues: conv_wino_r64.hip)
-#if defined(__HIP_DEVICE_COMPILE__)
-        const bool live = chunk < nchunk;
-        const int bufi = live ? (chunk & (NB - 1)) : NB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(live ? xsrc : xnull, (lds_ptr)(lds + bufi * XBUF + e * 4096 + wi * 1024), 16, xo[e], chunk * 64, 0, 0);
-#endif
-    };
+    const auto xnull = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.src0), 0, 0, 0x00020000);      // requests past the last chunk
+    auto x_dma_one = [&](int chunk, int e) { wino_patch_dma<G>(xsrc, xnull, lds, wi, chunk, nchunk, e, xo[e]); };
 
     // ---- ACT: register staging.  (A, B) of the item's frame sit in LDS behind the patch buffers: [Cin] A, [Cin] B.
     float* const sab = reinterpret_cast<float*>(lds + LDS_BYTES);
@@ -222,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
     // different MFMA slots (4 - 6 vector instructions hide behind an MFMA, a seventh and later do not: tools/probes/mfma_f16_coissue.hip):
     //   0: row combination of both columns (4 v_fma_f32)   1: column combination, a0 = f16 (3)   2: a1 = f16((x - a0) * 2^12) (5)
     // Each part is ONE asm statement: hipcc pads every asm output that the next instruction reads with an s_nop, and an s_nop is
-    // an issue slot like any other (conv_wino_r64.hip).
+    // an issue slot like any other.
     float pa0, pa1, pb0, pb1, pv0, pv1;                              // in flight between the parts of one block
     auto frag_part = [&](int nxt, int jn, int b, int part) {         // block b of 8: m = b >> 2, pair b & 3
         const int m = b >> 2, pr = b & 3, h = pr >> 1, e0 = 2 * (pr & 1);
@@ -250,8 +216,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
 #undef VD_Z128_P01
         } else {
             float r0, r1;
-            asm("v_fma_mix_f32 %1, %3, -1.0, %4 op_sel_hi:[1,0,0]\n\tv_fma_mix_f32 %2, %3, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-                "v_ldexp_f32 %1, %1, 12\n\tv_ldexp_f32 %2, %2, 12\n\tv_cvt_pk_f16_f32 %0, %1, %2"
+            asm(VD_WINO_A1(1, 2, 3, 4, 5) "v_cvt_pk_f16_f32 %0, %1, %2"
                 : "=&v"(af[nxt][m][1][pr]), "=&v"(r0), "=&v"(r1) : "v"(af[nxt][m][0][pr]), "v"(pv0), "v"(pv1));
         }
     };
@@ -265,21 +230,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
     const int bsb = (wi * 4 * ncoblk + cob0) * 3072;
     const unsigned blane = lane * 16u;
     u32x4 bfr[2][4][3];                                               // [ring slot = position & 1][cout tile][piece]
-    // Pieces 0 and 1 only: piece 2 = 2^-12 b0 (split_pack.hip) is formed here, four v_pk_mul_f16 per fragment (exact: a power of two,
-    // fp16 subnormals honoured like the host's conversion) -- a third less weight traffic from the L2 for 16 vector instructions per
-    // position, in slots that carry none
+    // Pieces 0 and 1 only: piece 2 is formed here (wino_b_third) -- a third less weight traffic from the L2 for 16 vector instructions
+    // per position, in slots that carry none
     auto b_load_one = [&](int chunk, int j, int k) {                 // k-th load of a position (8), in the order the MFMAs want them: piece k >> 2 of cout tile k & 3
         const int idx = (k & 3) * 3 + (k >> 2);
         const int so = chunk * ustride + bsb + j * bstep + (idx >> 2) * 4096;
         bfr[j & 1][idx / 3][idx % 3] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(usrc, blane + (idx & 3) * 1024u, so, 0));
     };
 
-    const unsigned two_m12 = 0x0c000c00u;                             // (2^-12, 2^-12) in fp16
-    auto b_third = [&](int slot, int n) {
-        asm("v_pk_mul_f16 %0, %4, %8\n\tv_pk_mul_f16 %1, %5, %8\n\tv_pk_mul_f16 %2, %6, %8\n\tv_pk_mul_f16 %3, %7, %8"
-            : "=&v"(bfr[slot][n][2][0]), "=&v"(bfr[slot][n][2][1]), "=&v"(bfr[slot][n][2][2]), "=&v"(bfr[slot][n][2][3])
-            : "v"(bfr[slot][n][0][0]), "v"(bfr[slot][n][0][1]), "v"(bfr[slot][n][0][2]), "v"(bfr[slot][n][0][3]), "s"(two_m12));
-    };
+    auto b_third = [&](int slot, int n) { wino_b_third(bfr[slot][n][2], bfr[slot][n][0]); };
 
     f32x16 acc[2][2][4];                                              // [z][m][n]
     Z128_STAMP(0); Z128_STAMP(14);
@@ -431,83 +390,39 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino_z128_kernel(IgemmArgs a, 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
     Z128_STAMP(2);
-    // ---- output transform, one cout tile at a time: the accumulators are Z[q] = sum_j M[wi][j] A[j][q] already; the sum over the
-    // rows crosses the waves through LDS; wave (p, q) = (wi >> 1, wi & 1) then owns output pixel (p, q) of every tile.
-    // Z image: [plane 2*i + q 8][m 2][c4 4][lane 64][4 floats] = 64 KB over the patch buffers.
+    // ---- output transform (wino_common.h), one cout tile at a time: the accumulators are Z[q] = sum_j M[wi][j] A[j][q] already
     const int p = wi >> 1, q = wi & 1;
     const int obytes = a.nfr * Hl * Wl * a.ldo * 4;
     const auto osrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, obytes, 0x00020000);
     const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.res ? a.res : a.out), 0, a.res ? obytes : 0, 0x00020000);
     const float sgn = p ? -1.f : 1.f;
-    float* Zs = smem;
     unsigned oo[2][16];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int tt = m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int tx = tt & 7, ty = tt >> 3;
-            oo[m][r] = (unsigned)(((f0 * Hl + oy0 + 2 * ty + p) * Wl + ox0 + 2 * tx + q) * a.ldo + cob0 * 32 + lr) * 4u;
-        }
+    wino_out_offsets<false, false>(oo, lh, p, q, f0, a.nfr, oy0, ox0, Hl, Wl, a.ldo, cob0 * 32 + lr, 0);
     const float* trailer = a.wwino + (size_t)24 * a.Cout * a.Cin;     // [Cout] s, [Cout] 1 / s (split_pack.hip)
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
         const int co = (cob0 + n) * 32 + lr;
         const int nso = n * 128;                                       // byte offset of cout tile n
         const float winv = trailer[a.Cout + co];
-        const float bvf = (a.bias ? a.bias[co] : 0.f) + (a.fbias ? a.fbias[(size_t)f0 * a.fbias_ld + co] : 0.f);
+        const float bv = (a.bias ? a.bias[co] : 0.f) + (a.fbias ? a.fbias[(size_t)f0 * a.fbias_ld + co] : 0.f);
+        const float bvf[2] = {bv, bv};
         f32x16 rv[2];
         if (n) __syncthreads();                                      // the previous Z is no longer read
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) rv[m][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, oo[m][r], nso, 0));
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                *reinterpret_cast<f32x4*>(Zs + ((((wi * 2 + 0) * 2 + m) * 4 + c4) * 64 + lane) * 4) =
-                    f32x4{acc[0][m][n][4 * c4], acc[0][m][n][4 * c4 + 1], acc[0][m][n][4 * c4 + 2], acc[0][m][n][4 * c4 + 3]};
-                *reinterpret_cast<f32x4*>(Zs + ((((wi * 2 + 1) * 2 + m) * 4 + c4) * 64 + lane) * 4) =
-                    f32x4{acc[1][m][n][4 * c4], acc[1][m][n][4 * c4 + 1], acc[1][m][n][4 * c4 + 2], acc[1][m][n][4 * c4 + 3]};
-            }
+            wino_z_write(smem, wi, lane, m, acc[0][m][n], acc[1][m][n]);
         }
         Z128_STAMP(3 + 2 * n);
         __syncthreads();
-        const float* zw = Zs + wi * 2048 + lane * 4;                 // Z[p + k][q] is plane wi + 2k
-        float gsum[2] = {0.f, 0.f};
+        float gsum[1][2] = {};
 #pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            f32x16 y;
-#pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const float* zp = zw + (m * 4 + c4) * 256;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(zp) +
-                                (*reinterpret_cast<const f32x4*>(zp + 2 * 2048) + *reinterpret_cast<const f32x4*>(zp + 4 * 2048)) * sgn;
-                y[4 * c4] = v.x; y[4 * c4 + 1] = v.y; y[4 * c4 + 2] = v.z; y[4 * c4 + 3] = v.w;
-            }
-            y = y * winv + rv[m];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[r] += bvf;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)y[r]), osrc, oo[m][r], nso, 0);
-            if (a.stats) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { gsum[0] += y[r]; gsum[1] = __builtin_fmaf(y[r], y[r], gsum[1]); }
-            }
-        }
-        if (a.stats) {                                               // GroupNorm partial sums of the output (conv_wino_r64.hip)
-            __syncthreads();
-            double* red = reinterpret_cast<double*>(smem);           // [wave 4][lh 2][lr 32][2]
-            double* d = red + (((wi * 2 + lh) * 32 + lr) * 2);
-            d[0] = (double)gsum[0]; d[1] = (double)gsum[1];
-            __syncthreads();
-            if (tid < 32) {
-                double s = 0.0, ss = 0.0;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { s += red[(k * 32 + tid) * 2]; ss += red[(k * 32 + tid) * 2 + 1]; }
-                double* o = a.stats + (((size_t)f0 * a.stats_split + byy * g.tiles_x + bxx) * a.Cout + (cob0 + n) * 32 + tid) * 2;
-                o[0] = s; o[1] = ss;
-            }
-        }
+        for (int m = 0; m < 2; ++m) wino_out_rows<true, false>(smem, wi, lane, m, sgn, winv, rv[m], bvf, osrc, oo[m], nso, a.stats != nullptr, gsum);
+        if (a.stats)
+            wino_stats_reduce<1>(smem, tid, wi, lh, lr, gsum, [&](int, int c) -> double* {
+                return a.stats + (((size_t)f0 * a.stats_split + byy * g.tiles_x + bxx) * a.Cout + (cob0 + n) * 32 + c) * 2;
+            });
         Z128_STAMP(4 + 2 * n);
     }
     Z128_STAMP(15);
@@ -564,19 +479,14 @@ bool conv_wino_z128_act_supported(const IgemmArgs& a) {
 int launch_conv_wino_z128(const IgemmArgs& a, hipStream_t s) {
     const int Hl = a.Hs;
     VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl), "GroupNorm partial table: split");
-    WinoZ128Geom g;
-    g.tiles_x = Hl / 16; g.tiles_y = g.tiles_x;
-    g.nbx = g.tiles_x * g.tiles_y * a.nfr;
-    g.ncb = a.Cout / 128;
-    g.nitems = g.nbx * g.ncb;
-    g.xcd_order = g.nbx % 8 == 0;
+    const WinoItemGeom g = wino_item_geom(Hl, a.nfr, a.Cout, 128, false);
     VD_RAISE_LDS((&conv3x3_wino_z128_kernel<false>), (size_t)160 * 1024);
     VD_RAISE_LDS((&conv3x3_wino_z128_kernel<true>), (size_t)160 * 1024);
     if (a.affA) {
         VD_REQUIRE(conv_wino_z128_act_supported(a), "conv_wino_z128 with the activation in its patch staging: shape not covered");
-        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<true>, dim3(g.nitems), dim3(256), z128::LDS_BYTES + 2 * a.Cin * sizeof(float), s, a, g);
+        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<true>, dim3(g.nitems), dim3(256), R64G<false>::LDS_BYTES + 2 * a.Cin * sizeof(float), s, a, g);
     } else {
-        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<false>, dim3(g.nitems), dim3(256), z128::LDS_BYTES, s, a, g);
+        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<false>, dim3(g.nitems), dim3(256), R64G<false>::LDS_BYTES, s, a, g);
     }
     VD_HIP(hipGetLastError());
     return 0;
