@@ -455,6 +455,35 @@ int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pr
 /* out[n] = sum over d of (a[n][d] - b[n][d])^2 for rows of D floats, differences and sum in float64, fixed order. */
 int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream);
 
+/* ---- I3D video embedding of the Frechet video distance (csrc/i3d.hip).
+ * Replaces create_id3_embedding(preprocess(videos, (224, 224))) (improved_diffusion/frechet_video_distance.py:38-133; the TF-Hub
+ * module deepmind/i3d-kinetics-400/1, output RGB/inception_i3d/Mean:0): TF1 bilinear resize to 224 x 224 and 2 x / 255 - 1, the
+ * 57 Unit3D convolutions of Inception-v1 inflated to 3-D with TF's SAME padding, the logits layer, the mean over time.  fp32 operands
+ * and accumulation whatever VD_MATH says; deterministic; a video's feature does not depend on the other videos of the call.
+ * A handle belongs to the device current at vd_i3d_create. */
+typedef struct vd_i3d vd_i3d;
+int vd_i3d_create(vd_i3d** out);
+void vd_i3d_destroy(vd_i3d* h);
+/* Host fp32 tensors, blocking H2D copy; packing happens here, once.  Names: "<unit>.weight" ([Cout][Cin][kt][kh][kw], the BatchNorm
+ * already folded in) and "<unit>.bias" ([Cout]) for <unit> = Conv3d_1a_7x7, Conv3d_2b_1x1, Conv3d_2c_3x3 and
+ * Mixed_{3b,3c,4b,4c,4d,4e,4f,5b,5c}.{b0,b1a,b1b,b2a,b2b,b3b}; "logits.weight" ([400][1024]) and "logits.bias". */
+int vd_i3d_load_weight(vd_i3d* h, const char* name, const float* host, long long bytes);
+/* Longest video vd_i3d_embed takes (1024 frames); the shortest has 9. */
+int vd_i3d_max_frames(void);
+/* videos [N][T][3][H][W] uint8 (device) -> out [N][400] (device).  Workspace owned by the handle, grown on demand for T; the videos
+ * are processed one after another on `stream`.  A T outside 9 .. vd_i3d_max_frames() is refused before anything is allocated. */
+int vd_i3d_embed(vd_i3d* h, int N, int T, int H, int W, const unsigned char* videos, float* out, void* stream);
+/* One convolution of that network on its own: x [T][H][W][Cin] channels-last, w [Cout][Cin][kt][kh][kw] and bias [Cout] (or NULL) on
+ * the device, SAME padding, optional ReLU; output row (ot, oy, ox) at out + ((ot*Ho + oy)*Wo + ox) * out_stride, Cout floats
+ * (out may point into a wider tensor).  Packs w on every call and waits for the stream: an entry for tests. */
+int vd_op_conv3d_same(const float* x, const float* w, const float* bias, int T, int H, int W, int Cin, int Cout, int kt, int kh,
+                      int kw, int st, int sh, int sw, int relu, float* out, long long out_stride, void* stream);
+/* Max pool with SAME padding (the padding never wins): x [T][H][W][C] -> out [To][Ho][Wo][C], sizes ceil(size / stride); C % 4 == 0. */
+int vd_op_maxpool3d_same(const float* x, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw, float* out,
+                         void* stream);
+/* The preprocessing: frames [T][3][H][W] uint8 -> out [T][224][224][3] float32 in [-1, 1]. */
+int vd_op_resize_bilinear_tf1(const unsigned char* frames, int T, int H, int W, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

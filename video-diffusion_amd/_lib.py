@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # every header a source may include: part of the library's identity and of each object's build stamp
 HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), HEADER]
@@ -235,6 +235,14 @@ SIGNATURES = {
     "vd_fps_select": (_I, [_I, _I, _L, _P, _I, _P, _I, _P, _P, _P]),
     "vd_frame_metrics": (_I, [_I, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P]),
     "vd_pair_sqdist": (_I, [_I, _L, _P, _P, _P, _P]),
+    "vd_i3d_create": (_I, [ctypes.POINTER(_P)]),
+    "vd_i3d_destroy": (None, [_P]),
+    "vd_i3d_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),
+    "vd_i3d_max_frames": (_I, []),
+    "vd_i3d_embed": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "vd_op_conv3d_same": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "vd_op_maxpool3d_same": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_resize_bilinear_tf1": (_I, [_P, _I, _I, _I, _P, _P]),
 }
 
 _lib = None
