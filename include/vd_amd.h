@@ -6,7 +6,8 @@
  * arguments are DEVICE pointers owned by the caller unless the name says `host`; `stream` is a
  * hipStream_t passed as void*.  Every function returns 0 on success or a negative code
  * (-1 bad argument / unsupported configuration, -2 HIP runtime error); text via vd_last_error().
- * No entry point synchronises the stream except vd_load_weight (a blocking H2D copy) and vd_device_errors.
+ * No entry point synchronises the stream except vd_load_weight (a blocking H2D copy), vd_device_errors, and the two that read a
+ * B*T mask back to shape their launches (vd_window_begin with the prefix cache / suffix skip on, vd_score_windows with suffix_skip = 1).
  * Contract: ONE device per process (the reference launches one process per GPU, command_launchers.py:32-62) and one
  * stream at a time per engine: kernel attributes are cached process-wide and an engine owns a single workspace.
  * vd_set_weight_storage binds the process to the current device and refuses a second one.
@@ -173,6 +174,31 @@ int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x
                 const long long* t, int clip_denoised, const float* latent_mask, float* vb, float* xstart_mse, float* mse,
                 float* pred_xstart, void* stream);
 int vd_prior_bpd(vd_engine* e, int B, int T, const float* x_start, const float* latent_mask, float* out, void* stream);
+
+/* The observed-frame search of scripts/video_optimal_schedule.py (:142-206,222-354).  One candidate evaluation there is
+ * run_bpd_evaluation at ONE timestep per batch item, of which the search reads `mse` only.  vd_score_windows is that evaluation:
+ *   noise    element j of item b = element j of vd_randn(out, per, seed, item_offset[b]) (per = T*3*H*W; item_offset: B Philox
+ *            block offsets in DEVICE memory), or `noise` [B][per] when it is non-NULL (the form tests use);
+ *   x_t      q_sample(x_start, t[b], noise), into engine-owned step memory;
+ *   forward  one UNet forward at x_t in observed_frames = 'x_0' mode with obs_src = x_start, as vd_p_mean_variance launches it;
+ *   mse_out  [B] float64 (device): sum over the frames with latent_mask != 0 of (eps' - noise)^2 * latent_mask, divided by ALL
+ *            T*3*H*W elements (mean_flat(tensor, mask)); pred_xstart as in vd_vb_terms (EPSILON / START_X, the non-finite check
+ *            before the clamp, bit 1 of the device flags), eps' = (sqrt_recip x_t - pred_xstart) / sqrt_recipm1
+ *            (_predict_eps_from_xstart, gaussian_diffusion.py:392-396).  fp64 partial sums per block folded in a fixed order: the
+ *            same call gives the same bits.  A t[b] outside the schedule gives NaN for item b and sets bit 0 of the device flags;
+ *            frames in neither mask contribute nothing; an item without a latent frame scores 0.
+ * suffix_skip = 1: under the conditions of the window suffix skip (cond_emb_type 'channel', an attention layer) everything behind
+ * the last attention layer runs on the frames with latent_mask = 1 only -- the only frames the score reads; their eps, and so
+ * mse_out, are those of suffix_skip = 0 bit for bit.  The number of such frames shapes the launches, so this form reads
+ * latent_mask back first (B*T floats, one wait for `stream` before anything is enqueued); suffix_skip = 0 never waits.
+ * vd_op_eps_mse: the reduction alone on a given network output `eps` [B][per] (test entry, like the vd_op_* below). */
+int vd_score_windows(vd_engine* e, int B, int T, const float* x_start, const float* obs_mask, const float* latent_mask,
+                     const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int clip_denoised,
+                     unsigned long long seed, const unsigned long long* item_offset, const float* noise, int suffix_skip,
+                     double* mse_out, void* stream);
+int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float* eps, const long long* t, int clip_denoised,
+                  const float* latent_mask, unsigned long long seed, const unsigned long long* item_offset, const float* noise,
+                  double* mse_out, void* stream);
 
 /* Window executor -- the loop of scripts/video_sample.py:149-168 (`for timestep in reversed(range(num_timesteps)):
  * local = diffusion.p_sample(model, local, t, ...)['sample']`) with the loop state on the device: the respaced index

@@ -168,6 +168,8 @@ SIGNATURES = {
     "vd_p_mean_variance": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "vd_vb_terms": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vd_prior_bpd": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "vd_score_windows": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _U, _P, _P, _I, _P, _P]),
+    "vd_op_eps_mse": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _U, _P, _P, _P, _P]),
     "vd_window_generation": (_U, [_P]),
     "vd_set_window_prefix_cache": (_I, [_P, _I]),
     "vd_window_prefix_frames": (_I, [_P]),

@@ -297,6 +297,10 @@ struct vd_engine {
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
     double* d_part = nullptr; size_t part_cap = 0;   // NLL partial sums
+    // vd_score_windows: x_t of the scored batch, the device list of its latent frames (suffix plan) and the host copies around it
+    float* d_score_xt = nullptr; size_t score_xt_cap = 0;
+    int* d_score_list = nullptr; size_t score_list_cap = 0;
+    std::vector<float> score_mask_h; std::vector<int> score_list_h;
     // ---- window executor (vd_window_*): device-resident step state + one captured graph per window signature
     struct WinKey {                  // the arguments of vd_window_begin a captured step depends on (zero-filled: compared bytewise)
         int B, T, obs_mode, sampler, clip, flags; float eta;      // flags: 1 prefix cache, 2 suffix skip
@@ -338,6 +342,8 @@ struct vd_engine {
         if (ws) (void)hipFree(ws);
         if (d_err) (void)hipFree(d_err);
         if (d_part) (void)hipFree(d_part);
+        if (d_score_xt) (void)hipFree(d_score_xt);
+        if (d_score_list) (void)hipFree(d_score_list);
         if (d_win_t) (void)hipFree(d_win_t);
         if (d_win_rng) (void)hipFree(d_win_rng);
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
@@ -416,7 +422,7 @@ struct vd_engine {
 
     int build();
     int forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr);
-    int ensure_ws(int B, int T);
+    int ensure_ws(int B, int T, bool suffix_plan = false);
     int res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, hipStream_t st, Arena& ar, Tens* out);
     int attn_block(const AttnP& a, Tens x, int B, int T, const int64_t* fidx, const float* amask,
                    hipStream_t st, Arena& ar, Tens* out);
@@ -1244,16 +1250,17 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
     return 0;
 }
 
-int vd_engine::ensure_ws(int B, int T) {
-    if (B == ws_B && T == ws_T && ws && ws_suf == suffix_skip_on) return 0;      // the common case: every step of a window
-    // with the window suffix skip enabled the arena also holds the gathered skip tensors: sized for the worst list (every frame)
-    const long long key = ((long long)B << 32) | (unsigned)T | (suffix_skip_on ? 1ll << 61 : 0);
+int vd_engine::ensure_ws(int B, int T, bool suffix_plan) {
+    const bool suf = suffix_skip_on || suffix_plan;     // the window flag, or a call that hands forward() a SuffixPlan of its own (vd_score_windows)
+    if (B == ws_B && T == ws_T && ws && ws_suf == suf) return 0;      // the common case: every step of a window
+    // with a suffix plan the arena also holds the gathered skip tensors: sized for the worst list (every frame)
+    const long long key = ((long long)B << 32) | (unsigned)T | (suf ? 1ll << 61 : 0);
     size_t tail = 0;
     int rc = grow_ws(key, step_tail_bytes(B, T), [&](size_t* peak) {
         Arena dry; dry.dry = true;
         FwdIn fi{}; fi.B = B; fi.T = T;
         int frc = forward(fi, nullptr, dry);
-        if (!frc && suffix_skip_on) {
+        if (!frc && suf) {
             Arena dry2; dry2.dry = true;
             SuffixPlan wp; wp.n = B * T;
             frc = forward(fi, nullptr, dry2, nullptr, &wp);
@@ -1263,7 +1270,7 @@ int vd_engine::ensure_ws(int B, int T) {
         return frc;
     }, &tail);
     if (rc) return rc;
-    ws_B = B; ws_T = T; ws_tail = tail; ws_suf = suffix_skip_on;
+    ws_B = B; ws_T = T; ws_tail = tail; ws_suf = suf;
     return 0;
 }
 
@@ -1856,6 +1863,71 @@ int vd_prior_bpd(vd_engine* e, int B, int T, const float* x_start, const float* 
     if (rc) return rc;
     return launch_prior_bpd(x_start, latent_mask, e->d_tab, e->num_timesteps, B, T, per, e->d_part, nblk, out,
                             static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------ observed-frame search
+// One candidate evaluation of scripts/video_optimal_schedule.py:142-206 is run_bpd_evaluation at ONE timestep per item, of which the
+// search reads `mse` only.  vd_score_windows is that: x_t from the item's own Philox stream, one forward in 'x_0' mode, and the
+// latent frames' mean((eps' - noise)^2) in fp64 -- no KL / decoder-NLL terms, no noise or pred_xstart tensors, and (suffix_skip) no
+// network suffix for the frames the score never reads.
+static int score_args(vd_engine* e, int B, int T, const float* x_start, const float* eps, const long long* t, int clip, const float* lat,
+                      unsigned long long seed, const unsigned long long* item_offset, const float* noise, ScoreArgs* a) {
+    const long per = (long)T * 3 * e->cfg.image_size * e->cfg.image_size;
+    const int nblk = vb_terms_blocks(per);
+    int rc = e->grow(e->d_part, e->part_cap, (size_t)B * nblk, false);
+    if (rc) return rc;
+    *a = ScoreArgs{x_start, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, lat, B, T, per, clip,
+                   e->mean_type == 1 ? 1 : 0, seed, item_offset, e->d_part, nblk, e->d_err};
+    return 0;
+}
+
+int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float* eps, const long long* t, int clip, const float* lat,
+                  unsigned long long seed, const unsigned long long* item_offset, const float* noise, double* mse_out, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && x_start && eps && t && lat && mse_out && (noise || item_offset), "arguments");
+    ScoreArgs a;
+    int rc = score_args(e, B, T, x_start, eps, t, clip, lat, seed, item_offset, noise, &a);
+    if (rc) return rc;
+    return launch_eps_mse(a, mse_out, static_cast<hipStream_t>(stream));
+}
+
+int vd_score_windows(vd_engine* e, int B, int T, const float* x_start, const float* obs, const float* lat, const float* km,
+                     const long long* fidx, const long long* t, int clip, unsigned long long seed,
+                     const unsigned long long* item_offset, const float* noise, int suffix_skip, double* mse_out, void* stream) {
+    int rc = check_sampler(e, B, T, 0, 0, kObsModes);
+    if (rc) return rc;
+    VD_REQUIRE(x_start && obs && lat && km && fidx && t && mse_out && (noise || item_offset), "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int N = B * T;
+    const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
+    // the suffix plan: the frames the score reads (latent_mask = 1), under vd_window_begin's conditions for the skip.  The list's
+    // length shapes the launches, so the mask is read back first -- B*T floats, the only host wait of this entry (none without suffix_skip)
+    SuffixPlan sp;
+    if (suffix_skip && e->cfg.cond_emb_type == 0 && e->suf_blk >= -1 && !e->attn.empty()) {
+        e->score_mask_h.resize(N);
+        VD_HIP(hipMemcpyAsync(e->score_mask_h.data(), lat, N * sizeof(float), hipMemcpyDeviceToHost, st));
+        VD_HIP(hipStreamSynchronize(st));          // (also: the previous call's list upload has left score_list_h)
+        e->score_list_h.clear();
+        for (int n = 0; n < N; ++n) if (e->score_mask_h[n] == 1.f) e->score_list_h.push_back(n);
+        const int n_lat = (int)e->score_list_h.size();
+        if (n_lat > 0 && n_lat < N) {
+            if ((rc = e->grow(e->d_score_list, e->score_list_cap, (size_t)N, false))) return rc;
+            VD_HIP(hipMemcpyAsync(e->d_score_list, e->score_list_h.data(), n_lat * sizeof(int), hipMemcpyHostToDevice, st));
+            sp.n = n_lat; sp.list = e->d_score_list;
+        }
+    }
+    if ((rc = e->ensure_ws(B, T, sp.n > 0))) return rc;
+    if ((rc = e->grow(e->d_score_xt, e->score_xt_cap, (size_t)B * per, false))) return rc;
+    float* eps = e->step_eps(B);
+    ScoreArgs a;
+    if ((rc = score_args(e, B, T, x_start, eps, t, clip, lat, seed, item_offset, noise, &a))) return rc;
+    if ((rc = launch_score_q_sample(a, e->d_score_xt, st))) return rc;
+    float* tm = e->step_tm();
+    map_t(e, t, B, tm, st);
+    Arena ar = e->step_arena();
+    FwdIn fi{B, T, e->d_score_xt, x_start, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), 0, eps};
+    if ((rc = e->forward(fi, st, ar, nullptr, sp.n > 0 ? &sp : nullptr))) return rc;
+    return launch_eps_mse(a, mse_out, st);
 }
 
 // ------------------------------------------------------------------------------------------ window executor

@@ -664,6 +664,131 @@ int launch_vb_terms(const VbArgs& a, hipStream_t s) {
     return 0;
 }
 
+// ------------------------------------------------------------------ observed-frame search (scripts/video_optimal_schedule.py)
+// The search ranks candidates by calc_bpd_loop_subsampled's `mse` alone (gaussian_diffusion.py:975-990): the KL / decoder-NLL
+// terms of vb_terms_kernel are never read, and only latent frames count.  Noise is item b's own Philox stream
+// (seed, item_offset[b]) -- element j is what vd_randn(out, per, seed, item_offset[b]) writes at j -- so x_t needs no noise tensor.
+
+// the four normals of Philox block q: elements 4q .. 4q+3 of normal_at, bit for bit
+__device__ __forceinline__ f32x4 normal4_at(unsigned long long seed, unsigned long long offset, unsigned long long q) {
+    unsigned r[4];
+    philox4x32_10(offset + q, seed, r);
+    f32x4 z;
+#pragma unroll
+    for (int pair = 0; pair < 4; pair += 2) {
+        const float u1 = ((float)r[pair] + 1.0f) * 2.3283064365386963e-10f;
+        const float u2 = (float)r[pair + 1] * 2.3283064365386963e-10f;
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[pair] = rad * cs;
+        z[pair + 1] = rad * sn;
+    }
+    return z;
+}
+
+// x_t = q_sample(x_start, t[b], noise) with q_sample_kernel's rounding; a thread = one quad of one item (per % 4 == 0)
+__global__ __launch_bounds__(256) void score_q_sample_kernel(ScoreArgs a, float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const long long tl = a.t[b];
+    const int NT = a.num_timesteps;
+    const bool ok = tl >= 0 && tl < NT;
+    const float sa = ok ? a.tab[TAB_SQRT_ACP * NT + tl] : 0.f, s1 = ok ? a.tab[TAB_SQRT_1M_ACP * NT + tl] : 0.f;
+    const unsigned long long off = a.noise ? 0ull : a.item_offset[b];
+    const long nq = a.per / 4;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        const size_t i4 = ((size_t)b * a.per) / 4 + q;
+        f32x4 o;
+        if (ok) {
+            const f32x4 xs = reinterpret_cast<const f32x4*>(a.x_start)[i4];
+            const f32x4 z = a.noise ? reinterpret_cast<const f32x4*>(a.noise)[i4] : normal4_at(a.seed, off, (unsigned long long)q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = fmaf(s1, z[e], sa * xs[e]);
+        } else {
+            const float nanv = __builtin_nanf("");                  // IndexError in the reference (q_sample_kernel)
+            o = f32x4{nanv, nanv, nanv, nanv};
+        }
+        reinterpret_cast<f32x4*>(out)[i4] = o;
+    }
+}
+
+// grid (nblk, B): block (k, b) sums its slice of item b over the LATENT frames, noise and x_t regenerated in registers, pred_xstart as
+// vb_terms_kernel forms it; fp64 sums, one partial per block (no atomics in the sum), folded in block order by eps_mse_final_kernel.
+__global__ __launch_bounds__(256) void eps_mse_kernel(ScoreArgs a) {
+    const int b = blockIdx.y;
+    const long long tl = a.t[b];
+    const int NT = a.num_timesteps;
+    const bool ok = tl >= 0 && tl < NT;
+    const int t = ok ? (int)tl : 0;
+    const float* tb = a.tab + t;
+    const float sr = tb[TAB_SQRT_RECIP * NT], srm1 = tb[TAB_SQRT_RECIPM1 * NT], sa = tb[TAB_SQRT_ACP * NT], s1 = tb[TAB_SQRT_1M_ACP * NT];
+    const unsigned long long off = a.noise ? 0ull : a.item_offset[b];
+    const long fq = a.per / a.T / 4, nq = a.per / 4;               // quads per frame / per item: a quad never straddles two frames
+    double s = 0;
+    bool bad_any = false;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+        const float m = a.mask[(size_t)b * a.T + q / fq];
+        if (m == 0.f) continue;                                     // observed and padding frames: nothing is read
+        const size_t i4 = ((size_t)b * a.per) / 4 + q;
+        const f32x4 xs = reinterpret_cast<const f32x4*>(a.x_start)[i4], ev = reinterpret_cast<const f32x4*>(a.eps)[i4];
+        const f32x4 z = a.noise ? reinterpret_cast<const f32x4*>(a.noise)[i4] : normal4_at(a.seed, off, (unsigned long long)q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xt = fmaf(s1, z[e], sa * xs[e]);
+            float x0 = a.start_x ? ev[e] : sr * xt - srm1 * ev[e];
+            const bool bad = !(fabsf(x0) <= 3.4028234e38f);         // (vb_terms_kernel: never clamp a non-finite output into range)
+            bad_any |= bad;
+            if (a.clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+            const double d = (double)((sr * xt - x0) / srm1 - z[e]);    // _predict_eps_from_xstart - noise
+            s += d * d * (double)m;
+        }
+    }
+    if (a.err) {
+        if (bad_any && ok) atomicOr(a.err, VD_ERR_NONFINITE);     // (an item with a bad t is NaN already: bit 0 says why)
+        if (!ok && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.err, VD_ERR_TIMESTEP);
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.part[(size_t)b * gridDim.x + blockIdx.x] = ok ? red[0] : __builtin_nan("");
+}
+
+__global__ void eps_mse_final_kernel(const double* __restrict__ part, int nblk, int B, double per, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s = 0;
+    for (int k = 0; k < nblk; ++k) s += part[(size_t)b * nblk + k];
+    out[b] = s / per;                                               // mean_flat(tensor, mask): over ALL T*3*H*W elements
+}
+
+static int score_args_ok(const ScoreArgs& a) {
+    VD_REQUIRE(a.per % (4 * a.T) == 0, "score: frames in 16-byte units");
+    VD_REQUIRE(((uintptr_t)a.x_start | (uintptr_t)a.eps | (uintptr_t)a.noise) % 16 == 0, "score: tensors aligned to 16 bytes");
+    return 0;
+}
+
+int launch_score_q_sample(const ScoreArgs& a, float* x_t, hipStream_t s) {
+    if (int rc = score_args_ok(a)) return rc;
+    VD_REQUIRE((uintptr_t)x_t % 16 == 0, "score: tensors aligned to 16 bytes");
+    const int gx = (int)std::max<long>(1, std::min<long>(256, (a.per / 4 + 255) / 256));
+    hipLaunchKernelGGL(score_q_sample_kernel, dim3(gx, a.B), dim3(256), 0, s, a, x_t);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_eps_mse(const ScoreArgs& a, double* mse_out, hipStream_t s) {
+    if (int rc = score_args_ok(a)) return rc;
+    hipLaunchKernelGGL(eps_mse_kernel, dim3(a.nblk, a.B), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    hipLaunchKernelGGL(eps_mse_final_kernel, dim3((a.B + 63) / 64), dim3(64), 0, s, a.part, a.nblk, a.B, (double)a.per, mse_out);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void prior_bpd_kernel(const float* x_start, const float* mask, const float* tab, int NT, int T,
                                                         long per, double* part) {
     const int b = blockIdx.y;

@@ -429,6 +429,23 @@ struct VbArgs {
 };
 int launch_vb_terms(const VbArgs& a, hipStream_t s);
 int vb_terms_blocks(long per);
+// The observed-frame search's score (scripts/video_optimal_schedule.py:142-206): mean((eps_from_xstart - noise)^2) over the latent
+// frames of each item, noise = the item's own Philox stream (seed, item_offset[b]) unless given; misc.hip
+struct ScoreArgs {
+    const float* x_start;        // [B][per]
+    const float* eps;            // the network output at x_t (launch_score_q_sample does not read it)
+    const float* noise;          // explicit draws or null
+    const int64_t* t;            // [B]
+    const float* tab; int num_timesteps;
+    const float* mask;           // [B*T] latent_mask
+    int B, T; long per;          // per = T*3*H*W
+    int clip, start_x;
+    unsigned long long seed; const unsigned long long* item_offset;   // [B] Philox block offsets (device)
+    double* part; int nblk;      // [B][nblk] partial sums
+    int* err;                    // sticky error word
+};
+int launch_score_q_sample(const ScoreArgs& a, float* x_t, hipStream_t s);
+int launch_eps_mse(const ScoreArgs& a, double* mse_out, hipStream_t s);
 // _prior_bpd (gaussian_diffusion.py:909-926): KL(q(x_T | x_0) || N(0, I)) in bits per dim, masked mean
 int launch_prior_bpd(const float* x_start, const float* mask, const float* tab, int num_timesteps, int B, int T, long per,
                      double* part, int nblk, float* out, hipStream_t s);

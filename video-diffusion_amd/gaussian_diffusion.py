@@ -336,6 +336,38 @@ class GaussianDiffusion:
         _lib.check(_lib.lib().vd_prior_bpd(model._handle, B, T, _lib.ptr(xs), _lib.ptr(m), _lib.ptr(out), _lib.current_stream()))
         return out
 
+    def score_windows(self, model, x_start, t, model_kwargs, latent_mask, seed, item_offset, clip_denoised=True,
+                      suffix_skip=True, noise=None):
+        """The `mse` of calc_bpd_loop_subsampled at ONE timestep per item (gaussian_diffusion.py:975-990 with t_seq of shape
+        (B, 1)), which is all the observed-frame search reads (scripts/video_optimal_schedule.py:183-198): float64 [B] on the
+        device, one engine call (vd_score_windows), no KL / decoder-NLL terms and no noise tensor.
+
+        Item b's noise is the engine's Philox stream at (seed, item_offset[b]) -- element j equals element j of
+        vd_randn(out, x_start[b].numel(), seed, item_offset[b]) -- unless `noise` is given.  The network runs in 'x_0' mode on
+        x_start; `latent_mask` ((B, T, 1, 1, 1); None: model_kwargs['latent_mask']) is both the network's latent mask and the
+        mask of the mean.  suffix_skip: the network behind its last attention layer runs on the latent frames only (same values,
+        bit for bit).  Like the step entry points this call does not wait for the device: a host `t` out of range raises
+        IndexError here, a device-resident one (and a non-finite network output) at model.check_device_errors()."""
+        self._refuse_learned(x_start)
+        kw_in = dict(model_kwargs, x0=x_start, x_t_minus_1=x_start, observed_frames="x_0")
+        if latent_mask is not None:
+            kw_in["latent_mask"] = latent_mask
+        model, xs, tt, kw = self._prepare(model, x_start, t, kw_in)
+        B, T = xs.shape[:2]
+        dev = model.device
+        off = th.as_tensor(item_offset, dtype=th.int64).reshape(-1).to(dev).contiguous()
+        assert off.shape == (B,) and (B == 0 or int(off.min()) >= 0), "item_offset: one non-negative Philox block offset per item"
+        nz = None
+        if noise is not None:
+            nz = _f32(noise, dev)
+            assert nz.shape == xs.shape
+        out = th.empty(B, device=dev, dtype=th.float64)
+        _lib.check(_lib.lib().vd_score_windows(
+            model._handle, B, T, _lib.ptr(xs), _lib.ptr(kw["obs_mask"]), _lib.ptr(kw["latent_mask"]), _lib.ptr(kw["kinda_marg_mask"]),
+            _lib.ptr(kw["frame_indices"]), _lib.ptr(tt), 1 if clip_denoised else 0, int(seed) & (2 ** 64 - 1), _lib.ptr(off),
+            _lib.ptr(nz), 1 if suffix_skip else 0, _lib.ptr(out), _lib.current_stream()))
+        return out
+
     def calc_bpd_loop_subsampled(self, model, x_start, clip_denoised=True, model_kwargs=None, latent_mask=None, t_seq=None):
         """gaussian_diffusion.py:928-1002 -> {'total_bpd','prior_bpd','vb','xstart_mse','mse'}; t_seq may be a list of
         timesteps or a 2-D array with one row of timesteps per batch item."""

@@ -307,7 +307,7 @@ def add_job_arguments(ap):
                     help="only the batch-sized block of dataset items #task_id (composes with the rank shard)")
     ap.add_argument("--optimality", default=None,
                     choices=["linspace-t", "random-t", "linspace-t-force-nearby", "random-t-force-nearby"],
-                    help="read <eval_dir>/optimal_schedule.pt (made by the reference's video_optimal_schedule.py)")
+                    help="read <eval_dir>/optimal_schedule.pt (made by video_optimal_schedule with the same options)")
     ap.add_argument("--observed_frames", default="x_0", choices=["x_0", "x_t", "x_t_minus_1"])
     ap.add_argument("--save_all_timesteps", action="store_true")
     ap.add_argument("--image_size", type=int, default=64, help="without a checkpoint: the closed-form model's size")
