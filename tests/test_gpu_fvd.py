@@ -61,6 +61,9 @@ CONV_CASES = [
     ((3, 3, 3), (1, 1, 1), 832, 16, (3, 6, 5), False, (0, 0)),
     ((3, 3, 3), (1, 1, 1), 3, 16, (4, 8, 11), True, (0, 0)),
     ((3, 3, 3), (1, 1, 1), 24, 64, (7, 14, 13), True, (64, 0)),
+    # the 2-D use of the same kernel (LPIPS conv2 and conv3..5): kt = 1, the frames on the T axis; SAME at stride 1 = AlexNet's pads 2 and 1
+    ((1, 5, 5), (1, 1, 1), 64, 192, (3, 7, 6), True, (0, 0)),
+    ((1, 3, 3), (1, 1, 1), 192, 384, (2, 3, 3), True, (0, 0)),
 ]
 
 

@@ -56,7 +56,7 @@ def _pair_dist(e):
     return ((e[:, None, :] - e[None, :, :]) ** 2).sum(-1)
 
 
-@pytest.mark.parametrize("H,W", [(32, 32), (64, 64), (128, 128), (48, 40)])
+@pytest.mark.parametrize("H,W", [(32, 32), (64, 64), (128, 128), (48, 40), (31, 35)])
 def test_embedding_vs_restated(H, W):
     """Every tap and the whole embedding against the fp64 restatement; pairwise distances within DIST_RTOL; run-to-run identical."""
     emb, w = embedder()

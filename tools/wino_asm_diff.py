@@ -5,7 +5,7 @@ Every named kernel file of both trees is compiled to assembly with the product's
 tree, --cuda-device-only -S).  Per kernel symbol: registers, scratch, LDS, and the opcode histogram split at the kernel's last v_mfma
 in execution order (prologue + main loop | epilogue: the instructions behind which no MFMA can follow).  Register allocation differs between any two builds, so the text is not compared; what a refactor
 of these one-wave-per-SIMD loops must keep, up to the last MFMA, is checked and printed as PASS / FAIL per kernel:
-  scratch, VGPRs, AGPRs, LDS not higher (no scratch where there was none); the same number of v_mfma*, of every buffer_load* / ds_read* / ds_write* opcode, of s_barrier;
+  scratch, VGPRs, AGPRs, LDS not higher (no scratch where there was none); the same number of v_mfma*, of every buffer_load* / global_load* / ds_read* / ds_write* opcode, of s_barrier;
   the same sequence of s_waitcnt immediates (the hand-placed vmcnt values are the schedule); not more instructions in total.
 Exit status 1 if a kernel fails."""
 import argparse
@@ -147,7 +147,7 @@ def kernel_key(sym):
 
 
 def pinned(op):
-    return op.startswith(("v_mfma", "buffer_load", "ds_read", "ds_write")) or op == "s_barrier"
+    return op.startswith(("v_mfma", "buffer_load", "global_load", "ds_read", "ds_write")) or op == "s_barrier"
 
 
 def check(a, b):

@@ -10,10 +10,10 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # every header a source may include: part of the library's identity and of each object's build stamp
-HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), HEADER]
+HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), os.path.join(_CSRC, "igemm_tile.h"), HEADER]
 # per-source flags on top of the common ones.  conv_wino_z128.hip: its main loop is ONE fully unrolled body of 288 MFMA slots; past
 # LLVM's default size limit for `#pragma unroll` (16 k IR instructions) hipcc silently keeps the loops and indexes the register
 # arrays through scratch

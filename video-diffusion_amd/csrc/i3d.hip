@@ -10,13 +10,10 @@
 //   Conv3d_1a_7x7 /2, MaxPool 1,3,3 /1,2,2, Conv3d_2b_1x1, Conv3d_2c_3x3, MaxPool 1,3,3 /1,2,2, Mixed_3b, 3c, MaxPool 3,3,3 /2,
 //   Mixed_4b..4f, MaxPool 2,2,2 /2, Mixed_5b, 5c, average pool 2,7,7 VALID, logits (1x1x1 with bias), mean over time -> 400 numbers.
 //
-// Convolutions: implicit GEMM on the fp32 MFMA (v_mfma_f32_32x32x2_f32; the tiling of lpips_conv_kernel / igemm.hip: 64 x 64 block
-// tile, padded LDS rows, one barrier per K-step), fp32 operands and accumulation whatever VD_MATH says.  Activations channels-last
-// [T][H][W][C]; reduction index k = ((dt*kh + dy)*kw + dx)*Cin + ci, weights packed [Cout][Kpad] once at load.  The output is written with
+// Convolutions and max pools: the channels-last kernels of conv_cl.hip, activations [T][H][W][C].  The output is written with
 // a row stride, so the four branches of a Mixed block land in their channel slices of one tensor.  Cin % 4 == 0: the operand is
-// gathered four channels at a time; otherwise (Conv3d_1a_7x7, Cin = 3) element by element.  No split of the reduction and no atomics:
-// every sum has a fixed order, and videos are processed one after another with the same launches, so a video's feature does
-// not depend on its batch.
+// gathered four channels at a time; otherwise (Conv3d_1a_7x7, Cin = 3) element by element.  Every sum has a fixed order, and
+// videos are processed one after another with the same launches, so a video's feature does not depend on its batch.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -28,9 +25,6 @@
 namespace vd {
 namespace {
 
-constexpr int I3_BK = 32;
-constexpr int I3_LDP = 36;     // padded LDS row (floats): conflict-free ds_read_b128 (igemm.hip)
-constexpr int I3_BM = 64, I3_BN = 64;
 constexpr int kI3dMinFrames = 9;        // the time mean runs over ceil(ceil(ceil(T/2)/2)/2) - 1 positions
 constexpr int kI3dMaxFrames = 1024;
 constexpr int kI3dSide = 224;
@@ -41,161 +35,6 @@ struct Same { int out, before; };
 inline Same same_pad(int size, int k, int s) {
     const int total = size % s == 0 ? std::max(k - s, 0) : std::max(k - size % s, 0);
     return {(size + s - 1) / s, total / 2};
-}
-
-struct C3Args {
-    const float* src;    // [T][H][W][Cin]
-    const float* w;      // [Cout][K]
-    const float* bias;   // [Cout] or null
-    float* out;          // row m = (ot*Ho + oy)*Wo + ox at out + m*out_stride, Cout floats
-    long long out_stride;
-    int T, H, W, Cin, Cout, kt, kh, kw, st, sh, sw, pt, ph, pw, To, Ho, Wo, M, K, Kreal, relu;
-};
-
-template <bool ELEM>
-__global__ __launch_bounds__(256) void i3d_conv_kernel(C3Args a) {
-    constexpr int AR = I3_BM / 32, BR = I3_BN / 32;
-    __shared__ __attribute__((aligned(16))) float As[2][I3_BM * I3_LDP];
-    __shared__ __attribute__((aligned(16))) float Bs[2][I3_BN * I3_LDP];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int m0 = blockIdx.x * I3_BM, n0 = blockIdx.y * I3_BN;
-    const int lrow = tid >> 3, lq = tid & 7;
-    const int HWo = a.Ho * a.Wo;
-
-    int pz[AR], py[AR], px[AR];
-    bool pv[AR];
-#pragma unroll
-    for (int j = 0; j < AR; ++j) {
-        const int m = m0 + lrow + 32 * j;
-        pv[j] = m < a.M;
-        const int mm = pv[j] ? m : 0;
-        const int ot = mm / HWo, r = mm - ot * HWo, oy = r / a.Wo;
-        pz[j] = ot * a.st - a.pt; py[j] = oy * a.sh - a.ph; px[j] = (r - oy * a.Wo) * a.sw - a.pw;
-    }
-    const int nsteps = a.K / I3_BK;
-    f32x4 ra[AR], rb[BR];
-
-    // k -> (dt, dy, dx, ci) and the source element of row j, or -1 for padding / a row or k beyond the problem
-    auto locate = [&](int k, int j) -> long long {
-        const int tap = k / a.Cin, c = k - tap * a.Cin;
-        const int q = tap / a.kw, dx = tap - q * a.kw;
-        const int dt = q / a.kh, dy = q - dt * a.kh;
-        const int it = pz[j] + dt, iy = py[j] + dy, ix = px[j] + dx;
-        const bool ok = pv[j] && k < a.Kreal && it >= 0 && it < a.T && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        return ok ? (long long)((((size_t)it * a.H + iy) * a.W + ix) * a.Cin + c) : -1;
-    };
-    auto prefetch = [&](int s) {
-        const int k0 = s * I3_BK + lq * 4;
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            if constexpr (ELEM) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long long off = locate(k0 + e, j);
-                    // unconditional load of element 0 for a padding tap (zeroed below): no branch around the load
-                    const float v = a.src[off < 0 ? 0 : off];
-                    ra[j][e] = off < 0 ? 0.f : v;
-                }
-            } else {
-                const long long off = locate(k0, j);                 // Cin % 4 == 0: four consecutive k share a tap
-                const f32x4 v = *reinterpret_cast<const f32x4*>(a.src + (off < 0 ? 0 : off));
-                ra[j] = off < 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : v;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BR; ++j) {
-            const int co = min(n0 + lrow + 32 * j, a.Cout - 1);
-            rb[j] = *reinterpret_cast<const f32x4*>(a.w + (size_t)co * a.K + k0);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < AR; ++j) *reinterpret_cast<f32x4*>(&As[buf][(lrow + 32 * j) * I3_LDP + lq * 4]) = ra[j];
-#pragma unroll
-        for (int j = 0; j < BR; ++j) *reinterpret_cast<f32x4*>(&Bs[buf][(lrow + 32 * j) * I3_LDP + lq * 4]) = rb[j];
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    prefetch(0);
-    stage(0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        const bool more = s + 1 < nsteps;
-        if (more) prefetch(s + 1);
-        const float* Ab = &As[buf][(wm * 32 + lr) * I3_LDP + lh * 4];
-        const float* Bb = &Bs[buf][(wn * 32 + lr) * I3_LDP + lh * 4];
-#pragma unroll
-        for (int kg = 0; kg < I3_BK / 8; ++kg) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(Ab + kg * 8);
-            const f32x4 fb = *reinterpret_cast<const f32x4*>(Bb + kg * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
-        }
-        if (more) stage(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const int co = n0 + wn * 32 + lr;
-    if (co >= a.Cout) return;
-    const float bv = a.bias ? a.bias[co] : 0.f;
-    const int mb = m0 + wm * 32 + 4 * lh;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = mb + (r & 3) + 8 * (r >> 2);
-        const float v = acc[r] + bv;
-        if (m < a.M) a.out[(size_t)m * a.out_stride + co] = a.relu ? fmaxf(v, 0.f) : v;
-    }
-}
-
-// [Cout][Cin][kt][kh][kw] -> [Cout][K], k = ((dt*kh + dy)*kw + dx)*Cin + ci, zero for k >= Kreal
-__global__ __launch_bounds__(256) void i3d_pack_kernel(const float* w, float* packed, int Cout, int Cin, int taps, int K) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)Cout * K) return;
-    const int o = (int)(i / K), k = (int)(i - (long long)o * K);
-    const int tap = k / Cin, c = k - tap * Cin;
-    packed[i] = tap < taps ? w[((size_t)o * Cin + c) * taps + tap] : 0.f;
-}
-
-// max pool with SAME padding (padding ignored): [T][H][W][C] -> [To][Ho][Wo][C]; one thread per (output position, 4 channels)
-struct P3Args {
-    const float* src;
-    float* dst;
-    int T, H, W, C, kt, kh, kw, st, sh, sw, pt, ph, pw, To, Ho, Wo;
-};
-
-__global__ __launch_bounds__(256) void i3d_maxpool_kernel(P3Args a) {
-    const int C4 = a.C / 4;
-    const long long total = (long long)a.To * a.Ho * a.Wo * C4;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    const long long p = i / C4;
-    const int ox = (int)(p % a.Wo), oy = (int)((p / a.Wo) % a.Ho), ot = (int)(p / ((long long)a.Wo * a.Ho));
-    const float ninf = -__builtin_inff();
-    f32x4 m = {ninf, ninf, ninf, ninf};
-    for (int dt = 0; dt < a.kt; ++dt) {
-        const int it = ot * a.st - a.pt + dt;
-        if (it < 0 || it >= a.T) continue;
-        for (int dy = 0; dy < a.kh; ++dy) {
-            const int iy = oy * a.sh - a.ph + dy;
-            if (iy < 0 || iy >= a.H) continue;
-            for (int dx = 0; dx < a.kw; ++dx) {
-                const int ix = ox * a.sw - a.pw + dx;
-                if (ix < 0 || ix >= a.W) continue;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(a.src + (((size_t)it * a.H + iy) * a.W + ix) * a.C + c4 * 4);
-                m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-            }
-        }
-    }
-    *reinterpret_cast<f32x4*>(a.dst + (size_t)p * a.C + c4 * 4) = m;
 }
 
 // TF1 resize_bilinear (align_corners=False, no half-pixel centres) of uint8 [T][3][H][W] to [T][S][S][3], then 2 x / 255 - 1.
@@ -280,45 +119,23 @@ const std::vector<Unit>& units() {
     return u;
 }
 
-inline int kpad(int kreal) { return (kreal + I3_BK - 1) / I3_BK * I3_BK; }
-
 int launch_conv(const float* src, const float* w, const float* bias, float* out, long long out_stride, int T, int H, int W, int Cin,
                 int Cout, int kt, int kh, int kw, int st, int sh, int sw, int relu, hipStream_t stream) {
     const Same zt = same_pad(T, kt, st), zy = same_pad(H, kh, sh), zx = same_pad(W, kw, sw);
-    C3Args a{};
+    ConvClArgs a{};
     a.src = src; a.w = w; a.bias = bias; a.out = out; a.out_stride = out_stride;
     a.T = T; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.kt = kt; a.kh = kh; a.kw = kw; a.st = st; a.sh = sh; a.sw = sw;
     a.pt = zt.before; a.ph = zy.before; a.pw = zx.before;
-    a.To = zt.out; a.Ho = zy.out; a.Wo = zx.out;
-    const long long M = (long long)a.To * a.Ho * a.Wo;
-    VD_REQUIRE(M > 0 && M < (1ll << 31) - I3_BM, "conv3d: output positions beyond the 32-bit row index");
-    a.M = (int)M;
-    a.Kreal = Cin * kt * kh * kw; a.K = kpad(a.Kreal); a.relu = relu;
-    dim3 grid((a.M + I3_BM - 1) / I3_BM, (Cout + I3_BN - 1) / I3_BN);
-    if (Cin % 4 == 0) hipLaunchKernelGGL(i3d_conv_kernel<false>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(i3d_conv_kernel<true>, grid, dim3(256), 0, stream, a);
-    VD_HIP(hipGetLastError());
-    return 0;
+    a.To = zt.out; a.Ho = zy.out; a.Wo = zx.out; a.relu = relu;
+    return launch_conv_cl(a, Cin % 4 == 0 ? CG_QUAD : CG_ELEM, stream);
 }
 
 int launch_pool(const float* src, float* dst, int T, int H, int W, int C, int kt, int kh, int kw, int st, int sh, int sw,
                 hipStream_t stream) {
     const Same zt = same_pad(T, kt, st), zy = same_pad(H, kh, sh), zx = same_pad(W, kw, sw);
-    P3Args a{src, dst, T, H, W, C, kt, kh, kw, st, sh, sw, zt.before, zy.before, zx.before, zt.out, zy.out, zx.out};
-    const long long total = (long long)a.To * a.Ho * a.Wo * (C / 4);
-    VD_REQUIRE(total > 0 && (total + 255) / 256 < (1ll << 31), "maxpool3d: grid too large");
-    hipLaunchKernelGGL(i3d_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a);
-    VD_HIP(hipGetLastError());
-    return 0;
-}
-
-int launch_pack(const float* w, float* packed, int Cout, int Cin, int taps, hipStream_t stream) {
-    const int K = kpad(Cin * taps);
-    const long long n = (long long)Cout * K;
-    hipLaunchKernelGGL(i3d_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, packed, Cout, Cin, taps, K);
-    VD_HIP(hipGetLastError());
-    return 0;
+    return launch_maxpool_cl(PoolClArgs{src, dst, T, H, W, C, kt, kh, kw, st, sh, sw, zt.before, zy.before, zx.before, zt.out, zy.out, zx.out},
+                             stream);
 }
 
 int launch_resize(const uint8_t* src, float* dst, int T, int H, int W, hipStream_t stream) {
@@ -460,17 +277,20 @@ void vd_i3d_destroy(vd_i3d* h) {
     delete h;
 }
 
+// a tensor counts as loaded once its device copy exists: `fresh` = there was none before this load
+static int note_loaded(vd_i3d* h, bool fresh, const float* dev, int rc) {
+    if (fresh && dev) --h->missing;
+    return rc;
+}
 static int i3d_upload(vd_i3d* h, float** dst, const float* host, size_t n) {
-    if (!*dst) { VD_HIP(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(float))); --h->missing; }
-    VD_HIP(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
+    const bool fresh = !*dst;
+    const int rc = upload_f32(dst, host, n);
+    return note_loaded(h, fresh, *dst, rc);
 }
 
 int vd_i3d_load_weight(vd_i3d* h, const char* name, const float* host, long long bytes) {
     VD_REQUIRE(h && name && host, "null argument");
-    int cur = -1;
-    VD_HIP(hipGetDevice(&cur));
-    VD_REQUIRE(cur == h->dev, "the I3D handle belongs to another device");
+    if (int rc = require_device(h->dev, "I3D")) return rc;
     VD_REQUIRE(bytes % (long long)sizeof(float) == 0, "byte count not a multiple of 4");
     const std::string s(name);
     const long long nf = bytes / (long long)sizeof(float);
@@ -491,21 +311,9 @@ int vd_i3d_load_weight(vd_i3d* h, const char* name, const float* host, long long
         if (s == un.name + ".weight") {
             const int taps = un.k * un.k * un.k;
             VD_REQUIRE(nf == (long long)un.cout * un.cin * taps, "unit weight: size mismatch ([Cout][Cin][kt][kh][kw] expected)");
-            float* raw = nullptr;
-            VD_HIP(hipMalloc(reinterpret_cast<void**>(&raw), nf * sizeof(float)));
-            int rc = 0;
-            if (hipMemcpy(raw, host, nf * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("hipMemcpy of a unit weight"); rc = -2; }
-            if (!rc && !h->w[u]) {
-                if (hipMalloc(reinterpret_cast<void**>(&h->w[u]), (size_t)un.cout * kpad(un.cin * taps) * sizeof(float)) != hipSuccess) {
-                    set_error("hipMalloc of a packed unit weight"); rc = -2;
-                } else {
-                    --h->missing;
-                }
-            }
-            if (!rc) rc = launch_pack(raw, h->w[u], un.cout, un.cin, taps, nullptr);
-            if (!rc && hipDeviceSynchronize() != hipSuccess) { set_error("packing a unit weight"); rc = -2; }
-            (void)hipFree(raw);
-            return rc;
+            const bool fresh = !h->w[u];
+            const int rc = conv_cl_load_weight(&h->w[u], host, un.cout, un.cin, taps);
+            return note_loaded(h, fresh, h->w[u], rc);
         }
     }
     set_error("unexpected I3D weight name: " + s);
@@ -518,18 +326,11 @@ int vd_i3d_embed(vd_i3d* h, int N, int T, int H, int W, const uint8_t* videos, f
     if (int rc = i3d_frames_ok(T)) return rc;
     VD_REQUIRE(H >= 1 && W >= 1 && H <= 8192 && W <= 8192, "frame size: 1 .. 8192 per side");
     VD_REQUIRE(h->missing == 0, "I3D weights incomplete: every unit's weight and bias and logits.weight / logits.bias are required");
-    int cur = -1;
-    VD_HIP(hipGetDevice(&cur));
-    VD_REQUIRE(cur == h->dev, "the I3D handle belongs to another device");
+    if (int rc = require_device(h->dev, "I3D")) return rc;
     if (N == 0) return 0;
     const I3dPlan p = i3d_plan(T);
     const size_t need = p.pre + p.main[0] + p.main[1] + p.tmp[0] + p.tmp[1] + p.tmp[2] + kI3dFeat;
-    if (h->ws_floats < need) {
-        VD_HIP(hipFree(h->ws));
-        h->ws = nullptr; h->ws_floats = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), need * sizeof(float)));
-        h->ws_floats = need;
-    }
+    if (int rc = grow_ws(&h->ws, &h->ws_floats, need)) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     for (int n = 0; n < N; ++n)
         if (int rc = i3d_embed_one(h, T, H, W, videos + (size_t)n * T * 3 * H * W, out + (size_t)n * kI3dClasses, st)) return rc;
@@ -547,8 +348,8 @@ int vd_op_conv3d_same(const float* x, const float* w, const float* bias, int T, 
     const hipStream_t s = static_cast<hipStream_t>(stream);
     const int taps = kt * kh * kw;
     float* packed = nullptr;
-    VD_HIP(hipMalloc(reinterpret_cast<void**>(&packed), (size_t)Cout * kpad(Cin * taps) * sizeof(float)));
-    int rc = launch_pack(w, packed, Cout, Cin, taps, s);
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(&packed), (size_t)Cout * conv_cl_kpad(Cin * taps) * sizeof(float)));
+    int rc = launch_conv_cl_pack(w, packed, Cout, Cin, taps, s);
     if (!rc) rc = launch_conv(x, packed, bias, out, out_stride, T, H, W, Cin, Cout, kt, kh, kw, st, sh, sw, relu, s);
     if (hipStreamSynchronize(s) != hipSuccess && !rc) { set_error("vd_op_conv3d_same: the kernels failed"); rc = -2; }
     (void)hipFree(packed);

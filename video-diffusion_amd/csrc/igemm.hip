@@ -7,26 +7,19 @@
 // folded into this kernel's operand load, so normalised activations are never materialised
 // (ResBlock: unet.py:185-198).
 //
-// Tiling (wave64, 4 waves = 2x2, each wave (BM/2)x(BN/2) as 32x32 MFMA tiles):
-//   K-step = (tap, 32 input channels).  A tile [BM][32] gathered per tap from NHWC, B tile [BN][32]
-//   from weights stored [tap][Cout][Cin].  Rows padded to 36 floats: ds_read_b128 of 16 lanes on
-//   16 distinct 16-byte slots -> conflict-free (guide: LDS banking, ds_read_b128 lane groups).
-//   MFMA 32x32x2 takes one f32 per lane per operand with k = lane>>5; a lane's float4 from LDS
-//   feeds 4 consecutive MFMAs (k order is free as long as A and B agree), so operand traffic is
-//   one ds_read_b128 per 4 MFMAs per fragment.
-//   Pipeline: global loads of step s+1 are issued before the MFMAs of step s (register staging:
-//   the operand transform needs VALU anyway), written to the other LDS buffer after them; one
-//   barrier per K-step.
+// The tiling and the K loop are those of igemm_tile.h: K-step = (tap, 32 input channels), A tile [BM][32] gathered per tap
+// from NHWC, B tile [BN][32] from weights stored [tap][Cout][Cin].
 #include <algorithm>
 
 #include <string>
 
+#include "igemm_tile.h"
 #include "vd_common.h"
 
 namespace vd {
 
-constexpr int BK = 32;
-constexpr int LDP = 36;   // padded LDS row (floats)
+constexpr int BK = IG_BK;
+constexpr int LDP = IG_LDP;
 
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
@@ -38,7 +31,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int lr = lane & 31, lh = lane >> 5;
+    const int lr = lane & 31;
     const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
 
     // ---- loader geometry: thread -> (row lrow + 32j, 4-float quad lq of the 32-channel chunk)
@@ -61,11 +54,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
     const int nchunk = a.Cin / BK;
     const int nsteps = ntaps * nchunk;
     const int C1 = a.Cin - a.C0;
-
-    f32x4 ra[AR], rb[BR];
     unsigned avalid = 0;
 
-    auto prefetch = [&](int s) {
+    auto load = [&](int s, f32x4 (&ra)[AR], f32x4 (&rb)[BR]) {
         const int chunk = s / ntaps, tap = s - chunk * ntaps;
         const int kh = tap / a.ksz, kw = tap - kh * a.ksz;
         const int c = chunk * BK + lq * 4;
@@ -76,9 +67,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
         for (int j = 0; j < AR; ++j) {
             int iy = py[j] + kh, ix = px[j] + kw;
             const bool ok = pn[j] >= 0 && iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
-            // unconditional load (out-of-image taps read pixel 0 and are zeroed when staged): a branch around a
-            // load makes hipcc drain the whole queue (vmcnt(0)) at the join
-            const size_t pix = ok ? ((size_t)pn[j] * a.Hs + (iy >> a.ups)) * a.Ws + (ix >> a.ups) : 0;
+            const size_t pix = ok ? ((size_t)pn[j] * a.Hs + (iy >> a.ups)) * a.Ws + (ix >> a.ups) : 0;   // out-of-image taps read pixel 0
             ra[j] = *reinterpret_cast<const f32x4*>(base + pix * ld + cc);
             avalid |= (ok ? 1u : 0u) << j;
         }
@@ -89,70 +78,23 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
             rb[j] = *reinterpret_cast<const f32x4*>(wt + (size_t)co * a.Cin);
         }
     };
-
-    auto stage = [&](int s, int buf) {
-        const int chunk = s / ntaps;
-        const int c = chunk * BK + lq * 4;
-        float* Ad = As + buf * BM * LDP;
-        float* Bd = Bs + buf * BN * LDP;
-#pragma unroll
-        for (int j = 0; j < AR; ++j) {
-            f32x4 v = ra[j];
-            if (a.affA) {
-                const size_t fr = (size_t)max(pn[j], 0) * a.Cin + c;
-                const f32x4 sa = *reinterpret_cast<const f32x4*>(a.affA + fr);
-                const f32x4 sb = *reinterpret_cast<const f32x4*>(a.affB + fr);
-                v = v * sa + sb;
-            }
-            if (a.act) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
-            if (!(avalid & (1u << j))) v = f32x4{0.f, 0.f, 0.f, 0.f};   // zero padding AFTER norm+activation (conv pads its input)
-            *reinterpret_cast<f32x4*>(Ad + (lrow + 32 * j) * LDP + lq * 4) = v;
+    auto fix = [&](int s, int j, f32x4 v) {
+        const int c = s / ntaps * BK + lq * 4;
+        if (a.affA) {
+            const size_t fr = (size_t)max(pn[j], 0) * a.Cin + c;
+            const f32x4 sa = *reinterpret_cast<const f32x4*>(a.affA + fr);
+            const f32x4 sb = *reinterpret_cast<const f32x4*>(a.affB + fr);
+            v = v * sa + sb;
         }
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            *reinterpret_cast<f32x4*>(Bd + (lrow + 32 * j) * LDP + lq * 4) = rb[j];
+        if (a.act) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+        if (!(avalid & (1u << j))) v = f32x4{0.f, 0.f, 0.f, 0.f};   // zero padding AFTER norm+activation (conv pads its input)
+        return v;
     };
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    igemm_tile_loop<BM, BN>(As, Bs, nsteps, load, fix, acc);
 
-    auto compute = [&](int buf) {
-        const float* Ab = As + buf * BM * LDP + (wm * (BM / 2) + lr) * LDP + lh * 4;
-        const float* Bb = Bs + buf * BN * LDP + (wn * (BN / 2) + lr) * LDP + lh * 4;
-#pragma unroll
-        for (int kg = 0; kg < BK / 8; ++kg) {
-            f32x4 fa[MI], fb[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) fa[i] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * LDP + kg * 8);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) fb[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * LDP + kg * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int j = 0; j < NI; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][e], fb[j][e], acc[i][j], 0, 0, 0);
-        }
-    };
-
-    prefetch(0);
-    stage(0, 0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const bool more = s + 1 < nsteps;
-        if (more) prefetch(s + 1);
-        compute(s & 1);
-        if (more) stage(s + 1, (s + 1) & 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+    // ---- epilogue
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
         const int co = n0 + wn * (BN / 2) + j * 32 + lr;
@@ -162,23 +104,23 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs a) {
         for (int i = 0; i < MI; ++i) {
             // residual loads batched ahead of the stores (unconditional, row clamped): one wait per tile
             // instead of one drained L2 round trip per element
-            const int mb = m0 + wm * (BM / 2) + i * 32 + 4 * lh;
+            const int mb = m0 + wm * (BM / 2) + i * 32 + igemm_cd_row(0, lane);
             f32x16 v = acc[i][j];
             if (a.res) {
                 f32x16 rv;
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    rv[r] = a.res[(size_t)min(mb + (r & 3) + 8 * (r >> 2), a.M - 1) * a.res_ld + co];
+                    rv[r] = a.res[(size_t)min(mb + igemm_cd_row(r, 0), a.M - 1) * a.res_ld + co];
                 v += rv;
             }
             if (a.fbias) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    v[r] += a.fbias[(size_t)(min(mb + (r & 3) + 8 * (r >> 2), a.M - 1) / HWo) * a.fbias_ld + co];
+                    v[r] += a.fbias[(size_t)(min(mb + igemm_cd_row(r, 0), a.M - 1) / HWo) * a.fbias_ld + co];
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int m = mb + (r & 3) + 8 * (r >> 2);
+                const int m = mb + igemm_cd_row(r, 0);
                 if (m < a.M) a.out[(size_t)m * a.ldo + co] = v[r] + bv;
             }
         }

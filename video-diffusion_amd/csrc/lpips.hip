@@ -7,11 +7,9 @@
 //   a4 = relu(conv4 3x3 p1 a3)    a5 = relu(conv5 3x3 p1 a4)                      (torchvision alexnet.features)
 //   e_k[c][y][x] = sqrt(lin_k[c]) * a_k / (||a_k[:, y, x]||_2 + 1e-10) / sqrt(h_k w_k)   (normalize_tensor, scale_by_proj_weights,
 //   embedding = concat_k flatten(e_k)                                                       not_spatial_average)
-// Convolutions: implicit GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32; the igemm.hip tiling, 64 x 64 block tile), operands and
-// accumulation in fp32, bias + ReLU in the epilogue, activations NHWC.  The reduction dimension is k = (ky*ksz + kx)*Cin + ci
-// (weights packed [Cout][Kpad] once at load); conv1 (Cin = 3, K = 363 -> Kpad 384) gathers its operand element by element from
-// the NCHW frames and applies the scaling layer to in-image taps only.  Every sum has a fixed order: results are run-to-run
-// deterministic.
+// Convolutions and max pools: the channels-last kernels of conv_cl.hip with kt = 1 and the frames on the T axis, bias + ReLU in
+// the epilogue, activations NHWC.  conv1 (Cin = 3, K = 363 -> Kpad 384) gathers its operand element by element from the NCHW
+// frames and applies the scaling layer to in-image taps only.  Every sum has a fixed order: results are run-to-run deterministic.
 //
 // Selection (reference inference_util.py:157-185): per batch item, picked[0] = always[0], nearest[f] = +inf; pick i = 1..n-1:
 // nearest[f] = min(nearest[f], ||e[newest] - e[f]||^2) over all candidates f, then always[i] if i < n_always else the argmax of
@@ -20,7 +18,6 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <vector>
 
 #include "../../include/vd_amd.h"
 #include "vd_common.h"
@@ -28,159 +25,12 @@
 namespace vd {
 namespace {
 
-constexpr int LP_BK = 32;
-constexpr int LP_LDP = 36;     // padded LDS row (floats): conflict-free ds_read_b128 (igemm.hip)
-constexpr int LP_BM = 64, LP_BN = 64;
-
 // torchvision alexnet.features conv layers
 constexpr int kCin[5] = {3, 64, 192, 384, 256};
 constexpr int kCout[5] = {64, 192, 384, 256, 256};
 constexpr int kKsz[5] = {11, 5, 3, 3, 3};
 constexpr int kStride[5] = {4, 1, 1, 1, 1};
 constexpr int kPad[5] = {2, 2, 1, 1, 1};
-
-inline int kreal(int l) { return kCin[l] * kKsz[l] * kKsz[l]; }
-inline int kpad(int l) { return (kreal(l) + LP_BK - 1) / LP_BK * LP_BK; }
-
-struct LpConvArgs {
-    const float* src;    // CONV1: frames [nfr][3][H][W]; else [nfr][H][W][Cin]
-    const float* w;      // [Cout][K]
-    const float* bias;   // [Cout]
-    float* out;          // [nfr][Ho][Wo][Cout]
-    int nfr, H, W, Cin, Cout, ksz, stride, pad, Ho, Wo, M, K, Kreal;
-    float shift[3], scale[3];
-};
-
-template <bool CONV1>
-__global__ __launch_bounds__(256) void lpips_conv_kernel(LpConvArgs a) {
-    constexpr int AR = LP_BM / 32, BR = LP_BN / 32;
-    __shared__ __attribute__((aligned(16))) float As[2][LP_BM * LP_LDP];
-    __shared__ __attribute__((aligned(16))) float Bs[2][LP_BN * LP_LDP];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int m0 = blockIdx.x * LP_BM, n0 = blockIdx.y * LP_BN;
-    const int lrow = tid >> 3, lq = tid & 7;
-    const int HWo = a.Ho * a.Wo;
-
-    int pn[AR], py[AR], px[AR];
-#pragma unroll
-    for (int j = 0; j < AR; ++j) {
-        const int m = m0 + lrow + 32 * j;
-        if (m < a.M) {
-            const int n = m / HWo, r = m - n * HWo, oy = r / a.Wo;
-            pn[j] = n; py[j] = oy * a.stride - a.pad; px[j] = (r - oy * a.Wo) * a.stride - a.pad;
-        } else {
-            pn[j] = -1; py[j] = 0; px[j] = 0;
-        }
-    }
-    const int nsteps = a.K / LP_BK;
-    f32x4 ra[AR], rb[BR];
-
-    auto prefetch = [&](int s) {
-        const int k0 = s * LP_BK + lq * 4;
-        if constexpr (CONV1) {
-#pragma unroll
-            for (int j = 0; j < AR; ++j) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int k = k0 + e, tap = k / 3, c = k - tap * 3;
-                    const int ky = tap / a.ksz, kx = tap - ky * a.ksz;
-                    const int iy = py[j] + ky, ix = px[j] + kx;
-                    const bool ok = pn[j] >= 0 && k < a.Kreal && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                    // unconditional load of element 0 for a padding tap (zeroed below): no branch around the load
-                    const size_t off = ok ? (((size_t)pn[j] * 3 + c) * a.H + iy) * a.W + ix : 0;
-                    const float v = a.src[off];
-                    const float sh = c == 0 ? a.shift[0] : (c == 1 ? a.shift[1] : a.shift[2]);
-                    const float sc = c == 0 ? a.scale[0] : (c == 1 ? a.scale[1] : a.scale[2]);
-                    ra[j][e] = ok ? (v - sh) / sc : 0.f;
-                }
-            }
-        } else {
-            const int kb = s * LP_BK;                     // a K-step lies inside one tap (Cin % 32 == 0)
-            const int tap = kb / a.Cin, c = kb - tap * a.Cin + lq * 4;
-            const int ky = tap / a.ksz, kx = tap - ky * a.ksz;
-#pragma unroll
-            for (int j = 0; j < AR; ++j) {
-                const int iy = py[j] + ky, ix = px[j] + kx;
-                const bool ok = pn[j] >= 0 && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                const size_t pix = ok ? ((size_t)pn[j] * a.H + iy) * a.W + ix : 0;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(a.src + pix * a.Cin + c);
-                ra[j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < BR; ++j) {
-            const int co = min(n0 + lrow + 32 * j, a.Cout - 1);
-            rb[j] = *reinterpret_cast<const f32x4*>(a.w + (size_t)co * a.K + k0);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int j = 0; j < AR; ++j) *reinterpret_cast<f32x4*>(&As[buf][(lrow + 32 * j) * LP_LDP + lq * 4]) = ra[j];
-#pragma unroll
-        for (int j = 0; j < BR; ++j) *reinterpret_cast<f32x4*>(&Bs[buf][(lrow + 32 * j) * LP_LDP + lq * 4]) = rb[j];
-    };
-
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
-    prefetch(0);
-    stage(0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const int buf = s & 1;
-        const bool more = s + 1 < nsteps;
-        if (more) prefetch(s + 1);
-        const float* Ab = &As[buf][(wm * 32 + lr) * LP_LDP + lh * 4];
-        const float* Bb = &Bs[buf][(wn * 32 + lr) * LP_LDP + lh * 4];
-#pragma unroll
-        for (int kg = 0; kg < LP_BK / 8; ++kg) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(Ab + kg * 8);
-            const f32x4 fb = *reinterpret_cast<const f32x4*>(Bb + kg * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
-        }
-        if (more) stage(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const int co = n0 + wn * 32 + lr;
-    if (co >= a.Cout) return;
-    const float bv = a.bias[co];
-    const int mb = m0 + wm * 32 + 4 * lh;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = mb + (r & 3) + 8 * (r >> 2);
-        if (m < a.M) a.out[(size_t)m * a.Cout + co] = fmaxf(acc[r] + bv, 0.f);
-    }
-}
-
-// maxpool 3x3 / 2, no padding, floor: [nfr][H][W][C] -> [nfr][Ho][Wo][C]; one thread per (output pixel, 4 channels)
-__global__ __launch_bounds__(256) void lpips_maxpool_kernel(const float* src, float* dst, int nfr, int H, int W, int C, int Ho,
-                                                            int Wo) {
-    const int C4 = C / 4;
-    const long long total = (long long)nfr * Ho * Wo * C4;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int c4 = (int)(i % C4);
-    const long long p = i / C4;
-    const int ox = (int)(p % Wo), oy = (int)((p / Wo) % Ho);
-    const long long n = p / ((long long)Wo * Ho);
-    const float* base = src + ((size_t)n * H * W) * C + c4 * 4;
-    f32x4 m = *reinterpret_cast<const f32x4*>(base + ((size_t)(2 * oy) * W + 2 * ox) * C);
-#pragma unroll
-    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(base + ((size_t)(2 * oy + dy) * W + 2 * ox + dx) * C);
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
-        }
-    *reinterpret_cast<f32x4*>(dst + (size_t)p * C + c4 * 4) = m;
-}
 
 // One tap: a [nfr][hw][C] (NHWC) -> out[n][off + c*hw + p] = sqrt(lin[c]) * a[n][p][c] / (||a[n][p][:]|| + 1e-10) / sqrt(hw).
 // Block = 64 pixels of one frame x 4 channel groups; the transposed write goes through a [64][33] LDS tile per 32 channels, so
@@ -349,17 +199,9 @@ void vd_lpips_destroy(vd_lpips* h) {
     delete h;
 }
 
-static int upload(float** dst, const float* host, size_t n) {
-    if (!*dst) VD_HIP(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(float)));
-    VD_HIP(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-}
-
 int vd_lpips_load_weight(vd_lpips* h, const char* name, const float* host, long long bytes) {
     VD_REQUIRE(h && name && host, "null argument");
-    int cur = -1;
-    VD_HIP(hipGetDevice(&cur));
-    VD_REQUIRE(cur == h->dev, "the LPIPS handle belongs to another device");
+    if (int rc = require_device(h->dev, "LPIPS")) return rc;
     const std::string s(name);
     const long long nf = bytes / (long long)sizeof(float);
     VD_REQUIRE(bytes % (long long)sizeof(float) == 0, "byte count not a multiple of 4");
@@ -373,28 +215,21 @@ int vd_lpips_load_weight(vd_lpips* h, const char* name, const float* host, long 
     for (int l = 0; l < 5; ++l) {
         const std::string L = std::to_string(l + 1);
         if (s == "conv" + L + ".weight") {
-            const int O = kCout[l], I = kCin[l], k = kKsz[l], K = kpad(l);
-            VD_REQUIRE(nf == (long long)O * I * k * k, "conv weight: size mismatch (OIHW expected)");
-            std::vector<float> p((size_t)O * K, 0.f);        // [co][(ky*k + kx)*Cin + ci]
-            for (int o = 0; o < O; ++o)
-                for (int i = 0; i < I; ++i)
-                    for (int ky = 0; ky < k; ++ky)
-                        for (int kx = 0; kx < k; ++kx)
-                            p[(size_t)o * K + (ky * k + kx) * I + i] = host[(((size_t)o * I + i) * k + ky) * k + kx];
-            if (int rc = upload(&h->w[l], p.data(), p.size())) return rc;
+            VD_REQUIRE(nf == (long long)kCout[l] * kCin[l] * kKsz[l] * kKsz[l], "conv weight: size mismatch (OIHW expected)");
+            if (int rc = conv_cl_load_weight(&h->w[l], host, kCout[l], kCin[l], kKsz[l] * kKsz[l])) return rc;
             h->loaded |= 1u << l;
             return 0;
         }
         if (s == "conv" + L + ".bias") {
             VD_REQUIRE(nf == kCout[l], "conv bias: size mismatch");
-            if (int rc = upload(&h->b[l], host, nf)) return rc;
+            if (int rc = upload_f32(&h->b[l], host, nf)) return rc;
             h->loaded |= 1u << (5 + l);
             return 0;
         }
         if (s == "lin" + L) {
             VD_REQUIRE(nf == kCout[l], "lin weight: size mismatch");
             for (long long c = 0; c < nf; ++c) VD_REQUIRE(host[c] >= 0.f, "lin weight: negative entry (sqrt of it is NaN)");
-            if (int rc = upload(&h->lin[l], host, nf)) return rc;
+            if (int rc = upload_f32(&h->lin[l], host, nf)) return rc;
             h->loaded |= 1u << (10 + l);
             return 0;
         }
@@ -413,9 +248,7 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
     VD_REQUIRE(h && frames && out, "null argument");
     VD_REQUIRE(h->loaded == (1u << 15) - 1, "LPIPS weights incomplete: conv1..5 weight/bias and lin1..5 are required");
     VD_REQUIRE(N >= 0, "negative frame count");
-    int cur = -1;
-    VD_HIP(hipGetDevice(&cur));
-    VD_REQUIRE(cur == h->dev, "the LPIPS handle belongs to another device");
+    if (int rc = require_device(h->dev, "LPIPS")) return rc;
     int hs[5], wds[5];
     VD_REQUIRE(lp_dims(H, W, hs, wds), "frames too small for the AlexNet feature stack");
     if (N == 0) return 0;
@@ -428,12 +261,7 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
     for (size_t v : sz) per += v;
     const size_t cap = (size_t)1 << 26;                   // workspace bound: 256 MiB
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)N, 65535), cap / per));   // grid.y of the tap kernel
-    if (h->ws_floats < per * chunk) {
-        VD_HIP(hipFree(h->ws));
-        h->ws = nullptr; h->ws_floats = 0;
-        VD_HIP(hipMalloc(reinterpret_cast<void**>(&h->ws), per * chunk * sizeof(float)));
-        h->ws_floats = per * chunk;
-    }
+    if (int rc = grow_ws(&h->ws, &h->ws_floats, per * chunk)) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     long long offs[5];
     offs[0] = 0;
@@ -447,16 +275,13 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
         float* o = out + (size_t)f0 * D;
 
         auto conv = [&](int l, const float* src, int Hi, int Wi, float* dst) -> int {
-            LpConvArgs a{};
-            a.src = src; a.w = h->w[l]; a.bias = h->b[l]; a.out = dst;
-            a.nfr = nf; a.H = Hi; a.W = Wi; a.Cin = kCin[l]; a.Cout = kCout[l]; a.ksz = kKsz[l]; a.stride = kStride[l]; a.pad = kPad[l];
-            a.Ho = hs[l]; a.Wo = wds[l]; a.M = nf * a.Ho * a.Wo; a.K = kpad(l); a.Kreal = kreal(l);
+            ConvClArgs a{};
+            a.src = src; a.w = h->w[l]; a.bias = h->b[l]; a.out = dst; a.out_stride = kCout[l];
+            a.T = nf; a.H = Hi; a.W = Wi; a.Cin = kCin[l]; a.Cout = kCout[l];
+            a.kt = 1; a.kh = a.kw = kKsz[l]; a.st = 1; a.sh = a.sw = kStride[l]; a.pt = 0; a.ph = a.pw = kPad[l];
+            a.To = nf; a.Ho = hs[l]; a.Wo = wds[l]; a.relu = 1;
             for (int c = 0; c < 3; ++c) { a.shift[c] = h->shift[c]; a.scale[c] = h->scale[c]; }
-            dim3 grid((a.M + LP_BM - 1) / LP_BM, (a.Cout + LP_BN - 1) / LP_BN);
-            if (l == 0) hipLaunchKernelGGL(lpips_conv_kernel<true>, grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL(lpips_conv_kernel<false>, grid, dim3(256), 0, st, a);
-            VD_HIP(hipGetLastError());
-            return 0;
+            return launch_conv_cl(a, l == 0 ? CG_NCHW_SCALED : CG_QUAD, st);
         };
         auto tap = [&](int l, const float* act) -> int {
             const int hw = hs[l] * wds[l];
@@ -465,10 +290,7 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
             return 0;
         };
         auto pool = [&](const float* src, int Hi, int Wi, int C, float* dst, int Ho, int Wo) -> int {
-            const long long total = (long long)nf * Ho * Wo * (C / 4);
-            hipLaunchKernelGGL(lpips_maxpool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, dst, nf, Hi, Wi, C, Ho, Wo);
-            VD_HIP(hipGetLastError());
-            return 0;
+            return launch_maxpool_cl(PoolClArgs{src, dst, nf, Hi, Wi, C, 1, 3, 3, 1, 2, 2, 0, 0, 0, nf, Ho, Wo}, st);    // 3x3 / 2, VALID
         };
         int rc;
         if ((rc = conv(0, frames + (size_t)f0 * 3 * H * W, H, W, buf[0])) || (rc = tap(0, buf[0])) ||

@@ -273,12 +273,7 @@ int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pr
     {
         std::lock_guard<std::mutex> lock(g_ws_mutex);
         MetricsWs& ws = g_ws[dev];
-        if (ws.doubles < (size_t)blocks * 2) {
-            VD_HIP(hipFree(ws.part));
-            ws.part = nullptr; ws.doubles = 0;
-            VD_HIP(hipMalloc(reinterpret_cast<void**>(&ws.part), (size_t)blocks * 2 * sizeof(double)));
-            ws.doubles = (size_t)blocks * 2;
-        }
+        if (int rc = grow_ws(&ws.part, &ws.doubles, (size_t)blocks * 2)) return rc;
         a.part = ws.part;
     }
     const size_t lds = (size_t)2 * plane_floats(a.rows_tile, W) * sizeof(float);

@@ -56,6 +56,31 @@ inline int raise_dynamic_lds(LdsAttr& st, const void* fn, size_t bytes) {
         if (int rc_ = vd::raise_dynamic_lds(lds_attr_, reinterpret_cast<const void*>(fn), (bytes))) return rc_; \
     } while (0)
 
+// ---- small host pieces the feature networks and the metrics share (lpips.hip, i3d.hip, metrics.hip)
+// *dst <- host[0..n), allocated on first use
+inline int upload_f32(float** dst, const float* host, size_t n) {
+    if (!*dst) VD_HIP(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(float)));
+    VD_HIP(hipMemcpy(*dst, host, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+// grow a workspace to `need` elements (hipFree waits for the device, so a launch that still reads the old one has finished)
+template <class T>
+inline int grow_ws(T** ws, size_t* have, size_t need) {
+    if (*have >= need) return 0;
+    VD_HIP(hipFree(*ws));
+    *ws = nullptr; *have = 0;
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(ws), need * sizeof(T)));
+    *have = need;
+    return 0;
+}
+// a handle is used on the device it was created on
+inline int require_device(int dev, const char* what) {
+    int cur = -1;
+    VD_HIP(hipGetDevice(&cur));
+    VD_REQUIRE(cur == dev, std::string("the ") + what + " handle belongs to another device");
+    return 0;
+}
+
 // ---------------------------------------------------------------- kernel argument blocks
 // Implicit-GEMM convolution / linear layer on NHWC activations (see igemm.hip).
 struct IgemmArgs {
@@ -128,6 +153,37 @@ struct AttnTemporalArgs {
     int allow_pad;       // allow_interactions_between_padding
     float scale;
 };
+
+// ---- channels-last convolution and max pool of the feature networks (conv_cl.hip; LPIPS' 2-D layers are kt = 1 with the frames on T)
+// out[m][co] = relu?(bias[co] + sum_k src(m, k) * w[co][k]), m = (ot*Ho + oy)*Wo + ox, k = ((dt*kh + dy)*kw + dx)*Cin + ci
+enum ConvClGather {
+    CG_QUAD,          // src [T][H][W][Cin], Cin % 4 == 0: four channels at a time
+    CG_ELEM,          // src [T][H][W][Cin], element by element
+    CG_NCHW_SCALED    // src [T][3][H][W], element by element, (v - shift[c]) / scale[c] on in-image taps only (lpips ScalingLayer)
+};
+struct ConvClArgs {
+    const float* src;
+    const float* w;      // [Cout][K], K = conv_cl_kpad(Kreal), zero behind Kreal (launch_conv_cl_pack)
+    const float* bias;   // [Cout] or null
+    float* out;          // row m at out + m*out_stride, Cout floats
+    long long out_stride;
+    int T, H, W, Cin, Cout, kt, kh, kw, st, sh, sw, pt, ph, pw, To, Ho, Wo, relu;
+    float shift[3], scale[3];   // CG_NCHW_SCALED
+    int M, K, Kreal;     // set by launch_conv_cl
+};
+inline int conv_cl_kpad(int kreal) { return (kreal + 31) / 32 * 32; }
+int launch_conv_cl(ConvClArgs a, ConvClGather g, hipStream_t s);
+// [Cout][Cin][taps] (OIHW / OIDHW) -> [Cout][K], zero for k >= Cin * taps
+int launch_conv_cl_pack(const float* w, float* packed, int Cout, int Cin, int taps, hipStream_t s);
+// the same from host memory into *packed (allocated on first use); returns when the image is complete
+int conv_cl_load_weight(float** packed, const float* host, int Cout, int Cin, int taps);
+// max pool over the in-volume taps (padding ignored): [T][H][W][C] -> [To][Ho][Wo][C], C % 4 == 0
+struct PoolClArgs {
+    const float* src;
+    float* dst;
+    int T, H, W, C, kt, kh, kw, st, sh, sw, pt, ph, pw, To, Ho, Wo;
+};
+int launch_maxpool_cl(const PoolClArgs& a, hipStream_t s);
 
 int launch_igemm(const IgemmArgs& a, hipStream_t s);
 int igemm_frames_per_launch(const IgemmArgs& a);   // frames (rows) per launch: big windows are cut along the frame dimension
