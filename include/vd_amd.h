@@ -438,6 +438,37 @@ int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W,
 /* Stem backward: dcols [nfr][H*W][64] (k = tap * stem channels + channel) -> dx [nfr][3][H][W]; cond_mode 0 channel, 1 duplicate / all, 2 t=0. */
 int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, const float* km, int nfr, int H, int W,
                       int cond_mode, float* dx, void* stream);
+/* The kernels that build what the network is conditioned on (csrc/misc.hip), each through the launcher the forward pass calls and
+ * with the arguments in the forward pass' form.  Enqueued only.
+ * out[i] = [cos(t[i] f_j) | sin(t[i] f_j)], j < dim / 2, and a zero last column when dim is odd (timestep_embedding / frame_embedding,
+ * nn.py:89-122); freqs: dim / 2 floats on the device, as vd_set_freqs receives them. */
+int vd_op_sinus_embed(const float* t, int n, int dim, const float* freqs, float* out, void* stream);
+/* tv[b][t] = frame_indices[b][t] (- their float32 mean over t when center; unet.py:914-926). */
+int vd_op_frame_t(const long long* frame_indices, int B, int T, int center, float* tv, void* stream);
+/* RPENet hidden layer of nz nets at once (unet.py:283-296): E[z][b][t][s][c] = silu(te[b*T + t][tab[3z] + c] + Wd_z[c][:] . feat(d)
+ * + bd_z[c]), d = fi[b][t] - fi[b][s], feat = (log(1 + max(d, 0)), log(1 + max(-d, 0)), d == 0); te rows of te_ld floats; Wd_z [C][3]
+ * at wbase + tab[3z + 1], bd_z [C] at wbase + tab[3z + 2]; tab: 3 nz offsets (in floats) on the device; net z writes at E + z * zs_e. */
+int vd_op_rpe_hidden(const float* te, int te_ld, const float* wbase, const long long* tab, const long long* frame_indices, int B, int T,
+                     int C, float* E, int nz, long long zs_e, void* stream);
+/* Bucket-table relative positions (RPE.get_bucket_ids, unet.py:330-347): R[b][t][s][:] = table[bucket(fi[b][t] - fi[b][s])], table
+ * [2 beta + 1][C], negative buckets wrapping as torch indexing does. */
+int vd_op_rpe_table(const float* table, const long long* frame_indices, int B, int T, int C, float alpha, float beta, float gamma,
+                    float* R, void* stream);
+/* y[n][p][c] = x[n][p][c] + P[p][c] + femb[n][c] (unet.py:914-926); P and femb may each be NULL; C % 4 == 0. */
+int vd_op_posenc_add(const float* x, const float* P, const float* femb, int nfr, int HW, int C, float* y, void* stream);
+/* The network input of CondMargVideoModel.forward (unet.py:951-983,991-1013) as the im2col matrix of the 3x3 stem, x_cols
+ * [B*T*H*W][Kpad] with k = tap * Cs + channel (Cs = 5 | 6 | 3 stem channels for cond_mode 0 | 1 | 2; zeros for taps outside the image and
+ * for k >= 9 Cs; Kpad 64, 128 or 256), plus the per-frame timesteps t_frames [B*T] (obs_t_mode: 0 'x_0', 1 'x_t', 2 'x_t_minus_1') and the
+ * attention mask amask [B*T].  With frame_list (n_list device ints) the rows of frame frame_list[i] go to row block i and the per-frame
+ * scalars are not written; with scalars_only x_cols is not written; both together are refused. */
+int vd_op_assemble(const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask, const float* kinda_marg_mask,
+                   const float* t_model, int obs_t_mode, int B, int T, int H, int W, int Kpad, int cond_mode, const int* frame_list,
+                   int n_list, int scalars_only, float* x_cols, float* t_frames, float* amask, void* stream);
+/* Frame-granular moves of the window prefix cache / suffix skip: gather dst[i] = src[list[i]], scatter dst[list[i]] = src[i], rows of
+ * row_floats floats (a multiple of 4), i < n.  vd_op_scatter_stats: GroupNorm partial sums src [n][split][C][2] doubles folded over
+ * split, in order, into dst[list[i]][C][2]. */
+int vd_op_move_rows(int scatter, const float* src, const int* list, int n, long long row_floats, float* dst, void* stream);
+int vd_op_scatter_stats(const double* src, int split, int C, const int* list, int n, double* dst, void* stream);
 
 /* ---- LPIPS frame distance of the adaptive-* frame schedulers (csrc/lpips.hip).
  * Replaces LpipsEmbedder (improved_diffusion/inference_util.py:15-31: lpips.LPIPS(net='alex', spatial=False), AlexNet features

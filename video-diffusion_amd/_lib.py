@@ -229,6 +229,14 @@ SIGNATURES = {
     "vd_op_attn_spatial_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "vd_op_out_conv_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_stem_col2im": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "vd_op_sinus_embed": (_I, [_P, _I, _I, _P, _P, _P]),
+    "vd_op_frame_t": (_I, [_P, _I, _I, _I, _P, _P]),
+    "vd_op_rpe_hidden": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _L, _P]),
+    "vd_op_rpe_table": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P]),
+    "vd_op_posenc_add": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "vd_op_assemble": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "vd_op_move_rows": (_I, [_I, _P, _P, _I, _L, _P, _P]),
+    "vd_op_scatter_stats": (_I, [_P, _I, _I, _P, _I, _P, _P]),
     "vd_lpips_create": (_I, [ctypes.POINTER(_P)]),
     "vd_lpips_destroy": (None, [_P]),
     "vd_lpips_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),

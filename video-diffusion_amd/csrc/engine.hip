@@ -2590,4 +2590,58 @@ int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, co
     return launch_stem_col2im(dcols, obs, lat, km, nfr, H, W, STEM_KPAD, cond_mode, dx, static_cast<hipStream_t>(stream));
 }
 
+// ---- the kernels that build what the network is conditioned on (misc.hip), through the launchers forward() calls
+int vd_op_sinus_embed(const float* t, int n, int dim, const float* freqs, float* out, void* stream) {
+    VD_REQUIRE(t && freqs && out && n > 0 && dim >= 2, "vd_op_sinus_embed: n rows of dim >= 2 columns, dim / 2 frequencies");
+    return launch_sinus_embed(t, n, dim, freqs, out, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_frame_t(const long long* fidx, int B, int T, int center, float* tv, void* stream) {
+    VD_REQUIRE(fidx && tv && B > 0 && T > 0, "vd_op_frame_t: shape");
+    return launch_frame_t(reinterpret_cast<const int64_t*>(fidx), B, T, center, tv, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_rpe_hidden(const float* te, int te_ld, const float* wbase, const long long* tab, const long long* fidx, int B, int T, int C,
+                     float* E, int nz, long long zs_e, void* stream) {
+    VD_REQUIRE(te && wbase && tab && fidx && E && B > 0 && T > 0 && C > 0 && nz > 0, "vd_op_rpe_hidden: shape");
+    VD_REQUIRE(te_ld >= C && zs_e >= (long long)B * T * T * C, "vd_op_rpe_hidden: te rows of at least C floats, a net's output inside its stride");
+    return launch_rpe_hidden_tab(te, te_ld, wbase, tab, reinterpret_cast<const int64_t*>(fidx), B, T, C, E, nz, (size_t)zs_e,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int vd_op_rpe_table(const float* table, const long long* fidx, int B, int T, int C, float alpha, float beta, float gamma, float* R,
+                    void* stream) {
+    VD_REQUIRE(table && fidx && R && B > 0 && T > 0 && C > 0, "vd_op_rpe_table: shape");
+    VD_REQUIRE(alpha >= 1.f && beta >= alpha && gamma >= alpha, "vd_op_rpe_table: bucket parameters 1 <= alpha <= beta, alpha <= gamma");
+    return launch_rpe_table(table, reinterpret_cast<const int64_t*>(fidx), B, T, C, alpha, beta, gamma, R, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_posenc_add(const float* x, const float* P, const float* femb, int nfr, int HW, int C, float* y, void* stream) {
+    VD_REQUIRE(x && y && nfr > 0 && HW > 0 && C > 0 && C % 4 == 0, "vd_op_posenc_add: channels in 16-byte units");
+    return launch_posenc_add(x, P, femb, nfr, HW, C, y, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_assemble(const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask, const float* kinda_marg_mask,
+                   const float* t_model, int obs_t_mode, int B, int T, int H, int W, int Kpad, int cond_mode, const int* frame_list,
+                   int n_list, int scalars_only, float* x_cols, float* t_frames, float* amask, void* stream) {
+    VD_REQUIRE(x && obs_src && obs_mask && latent_mask && kinda_marg_mask && B > 0 && T > 0 && H > 0 && W > 0, "vd_op_assemble: shape");
+    VD_REQUIRE(cond_mode >= 0 && cond_mode <= 2 && obs_t_mode >= 0 && obs_t_mode <= 2, "vd_op_assemble: cond_mode / obs_t_mode 0, 1 or 2");
+    VD_REQUIRE(frame_list ? n_list >= 0 && n_list <= B * T : (t_model && t_frames && amask), "vd_op_assemble: a list of at most B*T frames, or the per-frame scalars");
+    VD_REQUIRE(scalars_only || x_cols, "vd_op_assemble: x_cols");
+    AssembleArgs a{x, obs_src, obs_mask, latent_mask, kinda_marg_mask, t_model, obs_t_mode, B, T, H, W, Kpad, cond_mode, x_cols, t_frames, amask};
+    a.frame_list = frame_list; a.n_list = n_list; a.scalars_only = scalars_only;
+    return launch_assemble(a, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_move_rows(int scatter, const float* src, const int* list, int n, long long row_floats, float* dst, void* stream) {
+    VD_REQUIRE(n >= 0 && row_floats > 0 && (n == 0 || (src && list && dst)), "vd_op_move_rows: shape");
+    return scatter ? launch_scatter_rows(src, list, n, (size_t)row_floats, dst, static_cast<hipStream_t>(stream))
+                   : launch_gather_rows(src, list, n, (size_t)row_floats, dst, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_scatter_stats(const double* src, int split, int C, const int* list, int n, double* dst, void* stream) {
+    VD_REQUIRE(n >= 0 && split > 0 && C > 0 && (n == 0 || (src && list && dst)), "vd_op_scatter_stats: shape");
+    return launch_scatter_stats(src, split, C, list, n, dst, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -215,7 +215,7 @@ int launch_rpe_hidden_tab(const float* te, int te_ld, const float* wbase, const 
 
 // bucket-table relative positions (RPE.get_bucket_ids, unet.py:330-347; iRPE eq. 18)
 __global__ __launch_bounds__(256) void rpe_table_kernel(const float* __restrict__ table, const int64_t* __restrict__ fidx,
-                                                        int T, int C, float alpha, float beta, float gamma, float lg,
+                                                        int T, int C, float alpha, float beta, float gamma, double lg,
                                                         float* __restrict__ R) {
     const int row = blockIdx.x;
     const int s_ = row % T, bt = row / T, b = bt / T;
@@ -223,8 +223,14 @@ __global__ __launch_bounds__(256) void rpe_table_kernel(const float* __restrict_
     long long id = d;
     const float ad = fabsf((float)d);
     if (ad > alpha) {
-        const float coef = logf(ad / alpha) / lg;
-        const float v = fminf(beta, alpha + coef * (beta - alpha));
+        // The bucket is a truncation, and at some integer distances the value truncated is an exact integer (alpha, beta, gamma =
+        // 3, 7, 20: d = 20 -> 7.0), which the reference's CPU float32 evaluation returns as such.  In device float32 (logf one ulp low)
+        // d = 20 landed at 6.9999995: the neighbouring table row.  So: the value in fp64, snapped to an integer it is within 1e-6 of
+        // (the float32 reference cannot tell such a value from the integer either), then the reference's minimum and truncation.
+        double v = (double)alpha + log((double)ad / (double)alpha) / lg * ((double)beta - (double)alpha);
+        const double r = rint(v);
+        if (fabs(v - r) < 1e-6) v = r;
+        v = fmin((double)beta, v);              // (alpha == beta == gamma: v is NaN, the reference's cast undefined; here: beta)
         id = (long long)(int)v * (d > 0 ? 1 : -1);
     }
     const int nb = 2 * (int)beta + 1;
@@ -234,7 +240,7 @@ __global__ __launch_bounds__(256) void rpe_table_kernel(const float* __restrict_
 
 int launch_rpe_table(const float* table, const int64_t* fidx, int B, int T, int C, float alpha, float beta,
                      float gamma, float* R, hipStream_t s) {
-    const float lg = (float)log((double)gamma / (double)alpha);
+    const double lg = log((double)gamma / (double)alpha);
     hipLaunchKernelGGL(rpe_table_kernel, dim3(B * T * T), dim3(256), 0, s, table, fidx, T, C, alpha, beta, gamma, lg, R);
     VD_HIP(hipGetLastError());
     return 0;
