@@ -512,6 +512,28 @@ int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pr
 /* out[n] = sum over d of (a[n][d] - b[n][d])^2 for rows of D floats, differences and sum in float64, fixed order. */
 int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream);
 
+/* ---- Green-hallway pixel count of GQN-Mazes frames (csrc/hallway.hip).
+ * Replaces the per-frame host loop of scripts/video_eval_room_seq_acc.py: _count_hallway_pixels (:126-137), i.e. per frame
+ * cv2.cvtColor(image[14:45], COLOR_RGB2HSV), cv2.inRange(hsv, (50, 25, 25), (70, 255, 255)), cv2.erode(mask, ones((2, 2))) and the
+ * number of non-zero pixels left, and the quantisation (x * 255).astype(np.uint8) in front of it (:247, :278).
+ *
+ * The 8-bit HSV is OpenCV's integer arithmetic restated: v = max, m = min, d = v - m, S = (d * sdiv[v] + 2048) >> 12 with
+ * sdiv[i] = round(255 * 4096 / i), H = (h' * hdiv[d] + 2048) >> 12 (arithmetic shift, + 180 when negative) with
+ * hdiv[i] = round(180 * 4096 / (6 i)) and h' = g - b if v == r, else b - r + 2d if v == g, else r - g + 4d; sdiv[0] = hdiv[0] = 0.
+ * A pixel is green when 50 <= H <= 70, S >= 25 and V >= 25.  The erosion keeps pixel (y, x) of the STRIP when every in-strip pixel
+ * among (y-1, x-1), (y-1, x), (y, x-1), (y, x) is green (anchor (1, 1); what lies outside the strip does not count).
+ *
+ * frames [N][3][H][W] planar: uint8 when is_u8, else float32 in [0, 1] quantised as (uint8)(x * 255.0f) -- one fp32 multiply, clamped
+ * to 0..255, truncated.  counts[n] = eroded green pixels of rows row0 .. row1 - 1 of frame n; only those rows are read.  One block
+ * per frame; a frame's count does not depend on the other frames of the call.  Limits: 1 <= H, W; 0 <= row0 < row1 <= H;
+ * (row1 - row0) * W <= vd_hallway_max_strip() pixels (the strip's mask is held in LDS).  Device pointers; enqueued only. */
+int vd_hallway_counts(int N, int H, int W, int row0, int row1, const void* frames, int is_u8, int* counts, void* stream);
+/* Largest strip, in pixels, that vd_hallway_counts takes. */
+int vd_hallway_max_strip(void);
+/* The per-pixel half on its own: rgb [n][3] uint8 -> hsv [n][3] (or NULL) and mask [n], 255 where green else 0, before any erosion.
+ * The same device function as vd_hallway_counts: an entry for tests. */
+int vd_op_green_mask(long long n, const unsigned char* rgb, unsigned char* hsv, unsigned char* mask, void* stream);
+
 /* ---- I3D video embedding of the Frechet video distance (csrc/i3d.hip).
  * Replaces create_id3_embedding(preprocess(videos, (224, 224))) (improved_diffusion/frechet_video_distance.py:38-133; the TF-Hub
  * module deepmind/i3d-kinetics-400/1, output RGB/inception_i3d/Mean:0): TF1 bilinear resize to 224 x 224 and 2 x / 255 - 1, the

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip", "hallway.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # every header a source may include: part of the library's identity and of each object's build stamp
 HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), os.path.join(_CSRC, "igemm_tile.h"), HEADER]
@@ -253,6 +253,9 @@ SIGNATURES = {
     "vd_op_conv3d_same": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "vd_op_maxpool3d_same": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_resize_bilinear_tf1": (_I, [_P, _I, _I, _I, _P, _P]),
+    "vd_hallway_counts": (_I, [_I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "vd_hallway_max_strip": (_I, []),
+    "vd_op_green_mask": (_I, [_L, _P, _P, _P, _P]),
 }
 
 _lib = None
