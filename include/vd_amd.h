@@ -110,7 +110,7 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * mirror raises IndexError.  bit 0: timestep index out of range.
  * bit 1: the network output a step consumed was not finite.  The reference would carry the NaN into its sample; here the clamp
  * of clip_denoised would turn it into a plausible -1, so the posterior kernels keep such an element NaN and set this bit
- * (vd_p_sample, vd_ddim_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,
+ * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,
  * the window executor's captured step).  In the default f16x3 arithmetic (two fp16 pieces per fp32 operand) this is how an
  * operand beyond the split's range (|x| >= 2^15 = 32768: the scaled remainder (x - a0) 2^12 then leaves fp16; for a 3x3 conv the operand
  * is the Winograd-domain value, a signed sum of four inputs, so |input| < 2^13 is safe) anywhere in the network shows: VD_MATH=bf16x6
@@ -153,6 +153,24 @@ int vd_ddim_sample(vd_engine* e, int B, int T, const float* x, const float* obs_
                    const long long* t, int observed_frames, int clip_denoised, float eta, const float* noise,
                    unsigned long long seed, unsigned long long offset, float* sample, float* pred_xstart, float* eps,
                    void* stream);
+
+/* diffusion.ddim_reverse_sample(model, x, t, clip_denoised, model_kwargs) -> {'sample','pred_xstart'} (gaussian_diffusion.py:636-668):
+ * the deterministic DDIM step run towards the noise, x_t -> x_{t+1} (eta = 0 is the only path the reference has).  One UNet
+ * forward, then one fused pass of its own (ddim_reverse_kernel, beside the posterior kernel) in the reference's operation order:
+ *   pred_xstart = sqrt_recip[t] x - sqrt_recipm1[t] eps   (START_X: the network output), non-finite check, clamp when clip_denoised
+ *   eps'        = (sqrt_recip[t] x - pred_xstart) / sqrt_recipm1[t]
+ *   sample      = pred_xstart sqrt(abn) + sqrt(1 - abn) eps',   abn = alphas_cumprod[t + 1], 0 at the last index
+ * (alphas_cumprod_next is the alphas_cumprod row shifted by one: no schedule row of its own).  No noise is read and no Philox
+ * draw is consumed.  Opening checks, observed_frames and the treatment of a t[b] outside the schedule (NaN for item b, bit 0 of
+ * the device flags; bit 1 for a non-finite network output) as in vd_ddim_sample.  pred_xstart and eps may be NULL.
+ * vd_ddim_reverse_from_xstart: the same pass on a caller's x_0 prediction -- the `denoised_fn` form, as vd_posterior_from_xstart
+ * is for the other samplers; per_sample = T*3*H*W must be a multiple of 4 and every tensor 16-byte aligned. */
+int vd_ddim_reverse_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask,
+                           const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
+                           const long long* t, int observed_frames, int clip_denoised, float* sample, float* pred_xstart,
+                           float* eps, void* stream);
+int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per_sample, const float* x, const float* xstart_in,
+                                const long long* t, int clip_denoised, float* sample, float* pred_xstart, void* stream);
 
 /* diffusion.p_mean_variance(model, x, t, clip_denoised, model_kwargs) (gaussian_diffusion.py:229-372): one UNet forward,
  * then 'pred_xstart' (clipped) and 'mean' = posterior mean of it; 'variance' / 'log_variance' are the schedule rows
@@ -211,7 +229,11 @@ int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float*
  * observed_frames: 0 x_0, 1 x_t, 2 x_t_minus_1 as p_sample_loop runs it (obs_src = the CLEAN frames, re-noised to t - 1 inside
  * every step from the second half of the step's Philox range, gaussian_diffusion.py:565-568), 3 x_t_minus_1 with obs_src read as it
  * is at every step (a direct p_sample caller: scripts/video_sample.py:149-166 hands x0).  Noise is always the in-kernel Philox stream (seed, offset + step*B*per + i):
- * identical to vd_p_sample(noise = NULL, seed, offset + step*B*per). */
+ * identical to vd_p_sample(noise = NULL, seed, offset + step*B*per).
+ * sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample (gaussian_diffusion.py:636-668).  Sampler 2 walks UPWARDS: t_start is
+ * the first index, the captured step ends in ddim_reverse_kernel in place and t += 1, the Philox counter does not move (seed, offset
+ * and eta are not read), and vd_window_run refuses a run that would pass num_timesteps - 1.  It serves observed_frames 0, 1 and 3;
+ * 2 needs noise inside the graph and is refused.  The prefix cache and the suffix skip apply to it unchanged. */
 int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, const float* obs_mask,
                     const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
                     int observed_frames, int sampler, int clip_denoised, float eta, unsigned long long seed,

@@ -1,0 +1,348 @@
+"""GPU: ddim_reverse_sample (gaussian_diffusion.py:636-668 of the reference) -- the fused DDIM encoding pass, its loops and
+its window graph -- against tests/golden/ddim_reverse_tiny.npz, which the imported reference produced (tools/golden/loops_nll.py:
+ddim_reverse), against the float64 restatement of the pass, and against itself (mixed t, executor vs eager calls)."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import video_diffusion_amd as vda
+from ddim_reverse_restated import rounding_bound, sample_fp64, tables
+from helpers import ATOL, RTOL, close, load_npz, synth_sd
+from video_diffusion_amd import _lib
+from video_diffusion_amd.executor import WindowExecutor
+
+pytestmark = pytest.mark.gpu
+KEYS = vda.video_model_and_diffusion_defaults().keys()
+_cache = {}
+WINDOW_CFG = dict(T=6, image_size=32, num_channels=64, num_res_blocks=1, rp_alpha=6, rp_beta=6, rp_gamma=6, timestep_respacing="ddim10")
+
+
+def engine(cfg):
+    key = json.dumps(cfg, sort_keys=True)
+    if key not in _cache:
+        model, diff = vda.create_video_model_and_diffusion(**{k: cfg[k] for k in KEYS})
+        model.load_state_dict(synth_sd(model.param_specs()))
+        model.to("cuda")
+        model.eval()
+        _cache[key] = (model, diff)
+    return _cache[key]
+
+
+def _denoised_fn(x):
+    """tools/golden/_common.py: denoised_fn: the function the reference was run with."""
+    return 1.3 * torch.tanh(1.5 * x) + 0.05
+
+
+@pytest.fixture(scope="module")
+def rec():
+    return load_npz("ddim_reverse_tiny.npz")
+
+
+def _kw(rec, observed_frames="x_0"):
+    c = {k: torch.from_numpy(rec[k]).cuda() for k in ["x0", "obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"]}
+    return dict(c, x_t_minus_1=c["x0"], observed_frames=observed_frames)
+
+
+def _thin(rec, v):
+    n = int(rec["thin"])
+    return v[..., ::n, ::n]
+
+
+def _rand_window(B, T, S, n_obs, seed):
+    g = torch.Generator().manual_seed(seed)
+    x0 = torch.rand(B, T, 3, S, S, generator=g) * 2 - 1
+    x0[:, n_obs:] = 0
+    x = torch.randn(B, T, 3, S, S, generator=g)
+    obs = torch.zeros(B, T, 1, 1, 1)
+    obs[:, :n_obs] = 1
+    return dict(x=x, x0=x0, obs_mask=obs, latent_mask=1 - obs, kinda_marg_mask=torch.zeros(B, T, 1, 1, 1),
+                frame_indices=torch.arange(T).view(1, T).repeat(B, 1))
+
+
+def _window_kw(c, observed_frames="x_0"):
+    d = {k: c[k].cuda() for k in ["x0", "obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"]}
+    return dict(d, x_t_minus_1=d["x0"], observed_frames=observed_frames)
+
+
+def _t(B, v):
+    return torch.tensor([v] * B, device="cuda")
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1
+def test_teacher_forced_steps_match_the_reference(rec):
+    """Every t in 0..4, each fed the reference's previous output, at the project's step tolerance.  At t = 0 nothing amplifies
+    the network's error: unclipped, d sample / d eps_model = sqrt(1 - abn) - sqrt_recipm1 sqrt(abn), of magnitude <= 1; clipped,
+    x0 is +-1 on both sides.  At t = 4 abn = 0.  pred_xstart = sqrt_recip x - sqrt_recipm1 eps carries the network's error times
+    sqrt_recipm1: the bound the other steps' tests give it (2e-5 (1 + sqrt_recipm1))."""
+    model, diff = engine(json.loads(str(rec["cfg_json"])))
+    x0 = torch.from_numpy(rec["x0"]).cuda()
+    B = x0.shape[0]
+    xstart_tol = lambda d, tv: dict(atol=2e-5 * (1.0 + float(d.sqrt_recipm1_alphas_cumprod[tv])), rtol=1e-4)  # noqa: E731
+    x = x0
+    for tv in range(5):
+        before = x.clone()
+        out = diff.ddim_reverse_sample(model, x, _t(B, tv), model_kwargs=_kw(rec))
+        assert set(out) == {"sample", "pred_xstart"} and torch.equal(x, before) and out["sample"].data_ptr() != x.data_ptr()
+        close(out["sample"].cpu(), rec[f"x_0_t{tv}_sample"], atol=ATOL, rtol=RTOL)
+        close(_thin(rec, out["pred_xstart"].cpu()), rec[f"x_0_t{tv}_pred_xstart_thin"], **xstart_tol(diff, tv))
+        x = torch.from_numpy(rec[f"x_0_t{tv}_sample"]).cuda()
+    assert tables(diff, 4)[2] == 0.0
+    for obsf in ("x_t", "x_t_minus_1"):
+        out = diff.ddim_reverse_sample(model, x0, _t(B, 0), model_kwargs=_kw(rec, obsf))
+        close(_thin(rec, out["sample"].cpu()), rec[f"{obsf}_t0_sample_thin"], atol=ATOL, rtol=RTOL)
+    # clip off: the first step and the last (abn = 0) of the unclipped chain
+    for tv, x in ((0, x0), (4, torch.from_numpy(rec["noclip_t3_sample"]).cuda())):
+        out = diff.ddim_reverse_sample(model, x, _t(B, tv), clip_denoised=False, model_kwargs=_kw(rec))
+        close(_thin(rec, out["sample"].cpu()), rec[f"noclip_t{tv}_sample_thin"], atol=ATOL, rtol=RTOL)
+        close(_thin(rec, out["pred_xstart"].cpu()), rec[f"noclip_t{tv}_pred_xstart_thin"], **xstart_tol(diff, tv))
+    # denoised_fn sees the unclipped x_0 prediction, the clamp runs behind it; no noise is drawn on this path either
+    calls = []
+
+    def fn(v):
+        calls.append(tuple(v.shape))
+        return _denoised_fn(v)
+
+    state = torch.cuda.get_rng_state()
+    for tv in (0, 2):
+        x = x0 if tv == 0 else torch.from_numpy(rec[f"x_0_t{tv - 1}_sample"]).cuda()
+        out = diff.ddim_reverse_sample(model, x, _t(B, tv), denoised_fn=fn, model_kwargs=_kw(rec))
+        assert set(out) == {"sample", "pred_xstart"}
+        close(_thin(rec, out["sample"].cpu()), rec[f"denoised_t{tv}_sample_thin"], atol=ATOL, rtol=RTOL)
+        # d fn / d x <= 1.95: the x_0 bound of the plain step times that (as test_denoised_fn_matches_reference_golden)
+        close(_thin(rec, out["pred_xstart"].cpu()), rec[f"denoised_t{tv}_pred_xstart_thin"],
+              atol=4e-5 * (1.0 + float(diff.sqrt_recipm1_alphas_cumprod[tv])), rtol=1e-4)
+    assert calls == [tuple(x0.shape)] * 2 and torch.equal(torch.cuda.get_rng_state(), state)
+    # START_X: the network output is the x_0 prediction
+    model_x, diff_x = engine(json.loads(str(rec["xstart_cfg_json"])))
+    assert diff_x.model_mean_type.name == "START_X"
+    for tv in (0, 120, 249):
+        for clip in (True, False):
+            out = diff_x.ddim_reverse_sample(model_x, x0, _t(B, tv), clip_denoised=clip, model_kwargs=_kw(rec))
+            tag = f"xstart_t{tv}_clip{int(clip)}"
+            close(_thin(rec, out["sample"].cpu()), rec[tag + "_sample_thin"], atol=ATOL, rtol=RTOL)
+            close(_thin(rec, out["pred_xstart"].cpu()), rec[tag + "_pred_xstart_thin"], atol=ATOL, rtol=RTOL)
+    model.check_device_errors()
+    model_x.check_device_errors()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2
+def test_chained_loop_matches_the_reference_chain(rec):
+    """The host-driven loop (this project's extension) against the reference's chain of the same five steps, at the bounds
+    test_ddim_sample_loop_matches_reference_golden holds a chain of this length and model to: step 0 at 2e-4, mean |d| of the
+    final < 1e-4, final within 1e-2."""
+    model, diff = engine(json.loads(str(rec["cfg_json"])))
+    x0 = torch.from_numpy(rec["x0"]).cuda()
+    outs = [o["sample"] for o in diff.ddim_reverse_sample_loop_progressive(model, x0, model_kwargs=_kw(rec))]
+    assert len(outs) == 5
+    close(outs[0].cpu(), rec["x_0_t0_sample"], atol=2e-4, rtol=2e-4)
+    assert np.abs(outs[-1].cpu().numpy() - rec["x_0_t4_sample"]).mean() < 1e-4
+    close(outs[-1].cpu(), rec["x_0_t4_sample"], atol=1e-2, rtol=1e-2)
+    final = diff.ddim_reverse_sample_loop(model, x0, model_kwargs=_kw(rec))
+    assert torch.is_tensor(final) and torch.equal(final, outs[-1])
+    for obsf in ("x_t", "x_t_minus_1"):
+        kw = _kw(rec, obsf)
+        handed = kw["x_t_minus_1"].clone()
+        final = diff.ddim_reverse_sample_loop(model, x0, model_kwargs=kw)
+        assert torch.equal(kw["x_t_minus_1"], handed)                     # the caller's tensor is read as it is
+        got = _thin(rec, final.cpu())
+        assert np.abs(got.numpy() - rec[f"{obsf}_final_thin"]).mean() < 1e-4
+        close(got, rec[f"{obsf}_final_thin"], atol=1e-2, rtol=1e-2)
+    final = diff.ddim_reverse_sample_loop(model, x0, clip_denoised=False, model_kwargs=_kw(rec))
+    got = _thin(rec, final.cpu())
+    assert np.abs(got.numpy() - rec["noclip_t4_sample_thin"]).mean() < 1e-4
+    close(got, rec["noclip_t4_sample_thin"], atol=1e-2, rtol=1e-2)
+    # t_end stops where asked, t_start starts there
+    part = [o["sample"] for o in diff.ddim_reverse_sample_loop_progressive(model, x0, model_kwargs=_kw(rec), t_end=2)]
+    assert len(part) == 3 and all(torch.equal(a, b) for a, b in zip(part, outs))
+    assert torch.equal(diff.ddim_reverse_sample_loop(model, x0, model_kwargs=_kw(rec), t_end=2), outs[2])
+    assert torch.equal(diff.ddim_reverse_sample_loop(model, outs[2], model_kwargs=_kw(rec), t_start=3), outs[4])
+    assert torch.equal(diff.ddim_reverse_sample_loop(diff._wrap_model(model), outs[2], model_kwargs=_kw(rec), t_start=3, t_end=3), outs[3])
+    with pytest.raises(IndexError):
+        diff.ddim_reverse_sample_loop(model, x0, model_kwargs=_kw(rec), t_end=5)
+    model.check_device_errors()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3
+@pytest.mark.parametrize("tv", [0, 4])
+def test_the_pass_per_element_against_float64(rec, tv):
+    """From the call's own x, eps, pred_xstart and sample: `sample` recomputed in float64 from the float32 table values, every
+    element inside ddim_reverse_restated.rounding_bound -- at t = 0, where the divisor sqrt_recipm1 is smallest, and at t = 4,
+    where abn = 0.  pred_xstart itself: a x - b eps is three roundings of 2^-24 on terms of at most |a x| + |b eps|, and the
+    clamp moves nothing apart."""
+    model, diff = engine(json.loads(str(rec["cfg_json"])))
+    diff._bind(model)
+    x = torch.from_numpy(rec["x0"] if tv == 0 else rec["x_0_t3_sample"]).cuda()
+    B, T = x.shape[:2]
+    k = model._pack_kwargs(x, _kw(rec))
+    for clip in (1, 0):
+        sample, xstart, eps = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.lib().vd_ddim_reverse_sample(model._handle, B, T, *model._window_ptrs(x, k), _lib.ptr(_t(B, tv)), k["obs_mode"], clip,
+                                                     _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(eps), _lib.current_stream()))
+        xn, x0n, en, sn = (v.cpu().numpy() for v in (x, xstart, eps, sample))
+        a, b, abn = tables(diff, tv)
+        want, _ = sample_fp64(xn, x0n, a, b, abn)
+        lim = rounding_bound(xn, x0n, a, b, abn)
+        err = np.abs(sn - want)
+        print(f"t={tv} clip={clip}: max |d| / bound = {(err / lim).max():.3f}, max |d| = {err.max():.3e}")
+        assert (err <= lim).all(), (tv, clip, float((err / lim).max()))
+        x0_want = a * xn.astype(np.float64) - b * en.astype(np.float64)
+        if clip:
+            x0_want = np.clip(x0_want, -1.0, 1.0)
+            assert np.abs(x0n).max() <= 1.0
+        x0_lim = 2.0 ** -23 * (np.abs(a * xn.astype(np.float64)) + np.abs(b * en.astype(np.float64)))
+        assert (np.abs(x0n - x0_want) <= x0_lim).all(), (tv, clip)
+        only = torch.empty_like(x)                                           # pred_xstart and eps may be NULL: same sample
+        _lib.check(_lib.lib().vd_ddim_reverse_sample(model._handle, B, T, *model._window_ptrs(x, k), _lib.ptr(_t(B, tv)), k["obs_mode"], clip,
+                                                     _lib.ptr(only), None, None, _lib.current_stream()))
+        assert torch.equal(only, sample)
+    model.check_device_errors()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4
+def test_mixed_t_per_item_is_bit_equal_to_the_uniform_calls():
+    model, diff = engine({**vda.video_model_and_diffusion_defaults(), **WINDOW_CFG, "timestep_respacing": "ddim5"})
+    c = _rand_window(3, 4, 32, 2, seed=311)
+    x = c["x"].cuda()
+    ts = [0, 4, 2]
+    mixed = diff.ddim_reverse_sample(model, x, torch.tensor(ts, device="cuda"), model_kwargs=_window_kw(c))
+    for b, tv in enumerate(ts):
+        one = diff.ddim_reverse_sample(model, x, _t(3, tv), model_kwargs=_window_kw(c))
+        for key in ("sample", "pred_xstart"):
+            assert torch.equal(mixed[key][b], one[key][b]), (b, tv, key)
+    assert torch.isfinite(mixed["sample"]).all() and not torch.equal(mixed["sample"][0], mixed["sample"][1])
+    model.check_device_errors()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5
+def test_out_of_range_t_and_a_learned_variance_are_loud(rec):
+    model, diff = engine(json.loads(str(rec["cfg_json"])))
+    x0 = torch.from_numpy(rec["x0"]).cuda()
+    N = diff.num_timesteps
+    model.check_device_errors()
+    for bad in (N, -1):
+        out = diff.ddim_reverse_sample(model, x0, torch.tensor([2, bad], device="cuda"), model_kwargs=_kw(rec))
+        for key in ("sample", "pred_xstart"):
+            assert torch.isfinite(out[key][0]).all() and torch.isnan(out[key][1]).all(), (bad, key)
+        with pytest.raises(IndexError):
+            model.check_device_errors()
+        model.check_device_errors()                                          # cleared by the read
+        with pytest.raises(IndexError):
+            diff.ddim_reverse_sample(model, x0, torch.tensor([2, bad]), model_kwargs=_kw(rec))
+    good = diff.ddim_reverse_sample(model, x0, torch.tensor([2, N - 1], device="cuda"), model_kwargs=_kw(rec))
+    assert torch.isfinite(good["sample"]).all()
+    model.check_device_errors()
+    var = load_npz("variants_tiny.npz")
+    model_ls, diff_ls = engine(json.loads(str(var["ls_cfg_json"])))
+    c = {k: torch.from_numpy(var[f"ls_{k}"]).cuda() for k in ["x", "x0", "obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"]}
+    kw = dict({k: v for k, v in c.items() if k != "x"}, x_t_minus_1=c["x0"], observed_frames="x_0")
+    with pytest.raises(AssertionError, match="gaussian_diffusion.py:283"):
+        diff_ls.ddim_reverse_sample(model_ls, c["x"], _t(2, 3), model_kwargs=kw)
+    with pytest.raises(AssertionError, match="gaussian_diffusion.py:283"):
+        diff_ls.ddim_reverse_sample_loop(model_ls, c["x"], model_kwargs=kw)
+    diff_ls._bind(model_ls)
+    k = model_ls._pack_kwargs(c["x"], kw)
+    rc = _lib.lib().vd_ddim_reverse_sample(model_ls._handle, 2, c["x"].shape[1], *model_ls._window_ptrs(c["x"], k), _lib.ptr(_t(2, 3)), k["obs_mode"], 1,
+                                           _lib.ptr(torch.empty_like(c["x"])), None, None, _lib.current_stream())
+    assert rc != 0 and b"learn_sigma" in _lib.lib().vd_last_error()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 6
+def _eager_reverse(model, x_init, kw, n_steps, t_start=0, keep=()):
+    """Successive vd_ddim_reverse_sample calls from t_start; returns the last sample and those after the step counts in `keep`."""
+    L = _lib.lib()
+    cur = x_init.clone()
+    B, T = cur.shape[:2]
+    k = model._pack_kwargs(cur, kw)
+    kept = {}
+    for step in range(n_steps):
+        nxt = torch.empty_like(cur)
+        obs_src = cur if kw["observed_frames"] == "x_t" else k["obs_src"]
+        _lib.check(L.vd_ddim_reverse_sample(model._handle, B, T, _lib.ptr(cur), _lib.ptr(obs_src), _lib.ptr(k["obs_mask"]), _lib.ptr(k["latent_mask"]),
+                                            _lib.ptr(k["kinda_marg_mask"]), _lib.ptr(k["frame_indices"]), _lib.ptr(_t(B, t_start + step)),
+                                            k["obs_mode"], 1, _lib.ptr(nxt), None, None, _lib.current_stream()))
+        cur = nxt
+        if step + 1 in keep:
+            kept[step + 1] = cur
+    return cur, kept
+
+
+def test_window_executor_runs_the_reverse_step_as_a_graph():
+    """sampler='ddim_reverse': the captured step is map_t -> forward -> ddim_reverse_kernel in place -> t += 1.  Step k of the window
+    is bit-equal to successive vd_ddim_reverse_sample calls for 'x_0', 'x_t' and 'x_t_minus_1' as handed; a run past the last index
+    and the re-noising form are refused; the seed is not read; a p_sample window of the same shape begun afterwards gets a graph
+    of its own and still equals its eager replay."""
+    model, diff = engine({**vda.video_model_and_diffusion_defaults(), **WINDOW_CFG})
+    diff._bind(model)
+    N = diff.num_timesteps
+    ex = WindowExecutor(model, diff)
+    for wi, (B, T, n_obs, obsf) in enumerate([(2, 6, 2, "x_0"), (2, 6, 2, "x_t"), (2, 6, 3, "x_t_minus_1"), (1, 4, 1, "x_0")]):
+        c = _rand_window(B, T, 32, n_obs, seed=400 + wi)
+        kw = _window_kw(c, obsf)
+        if obsf == "x_t_minus_1":
+            kw["x_t_minus_1"] = (c["x0"] * 0.5).cuda()                       # the tensor the steps must read, unlike x0
+        x_init = (c["x0"] + 0.1 * c["x"]).cuda()
+        ex.begin(x_init, kw, sampler="ddim_reverse", seed=wi, renoise=False)
+        got_mid = ex.run(3).clone()
+        got = ex.run(N - 3).clone()
+        with pytest.raises(_lib.VdError, match="ddim_reverse_sample"):
+            ex.run(1)                                                          # t would pass the last index
+        want, kept = _eager_reverse(model, x_init, kw, N, keep=(3,))
+        assert torch.equal(kept[3], got_mid), (wi, obsf, float((kept[3] - got_mid).abs().max()))
+        assert torch.equal(want, got) and torch.isfinite(got).all(), (wi, obsf, float((want - got).abs().max()))
+        if wi == 0:
+            ex.begin(x_init, kw, sampler="ddim_reverse", seed=12345, t_start=4)      # another seed, a later start: same graph
+            assert ex._left == N - 4
+            part = ex.run().clone()
+            assert torch.equal(part, _eager_reverse(model, x_init, kw, N - 4, t_start=4)[0])
+    model.check_device_errors()
+    # the re-noising 'x_t_minus_1' form draws noise inside the graph: refused, by name
+    c = _rand_window(2, 6, 32, 2, seed=450)
+    x_init = c["x0"].cuda().clone()
+    with pytest.raises(_lib.VdError, match="ddim_reverse_sample"):
+        ex.begin(x_init, _window_kw(c, "x_t_minus_1"), sampler="ddim_reverse", renoise=True)
+    # a p_sample window of the first window's shape and tensors: `sampler` is part of the graph key
+    kw = _window_kw(c)
+    ex.begin(x_init, kw, sampler="ddim_reverse")
+    g = ex.graphs
+    ex.begin(x_init, kw, sampler="p_sample", seed=77)
+    assert ex.graphs == g + 1
+    got = ex.run().clone()
+    L = _lib.lib()
+    cur, per = x_init.clone(), x_init[0].numel()
+    k = model._pack_kwargs(cur, kw)
+    for step, ti in enumerate(range(N)[::-1]):
+        nxt = torch.empty_like(cur)
+        _lib.check(L.vd_p_sample(model._handle, 2, 6, _lib.ptr(cur), _lib.ptr(k["obs_src"]), _lib.ptr(k["obs_mask"]), _lib.ptr(k["latent_mask"]),
+                                 _lib.ptr(k["kinda_marg_mask"]), _lib.ptr(k["frame_indices"]), _lib.ptr(_t(2, ti)), k["obs_mode"], 1, None, 77,
+                                 step * 2 * per, _lib.ptr(nxt), None, None, _lib.current_stream()))
+        cur = nxt
+    assert torch.equal(cur, got) and torch.isfinite(got).all()
+    ex.begin(x_init, kw, sampler="ddim_reverse")                                 # and back: the reverse graph is still there
+    assert ex.graphs == g + 1
+    assert torch.equal(ex.run().clone(), _eager_reverse(model, x_init, kw, N)[0])
+    model.check_device_errors()
+
+
+def test_reverse_window_with_suffix_skip_leaves_every_read_frame_bit_identical():
+    """The reverse step shares the forward's launches with the other samplers, so the suffix skip (and the prefix cache) apply
+    unchanged: every frame that is not a pure observation equals the plain executor's to the bit."""
+    model, diff = engine({**vda.video_model_and_diffusion_defaults(), **WINDOW_CFG})
+    plain, skip, both = WindowExecutor(model, diff), WindowExecutor(model, diff, suffix_skip=True), \
+        WindowExecutor(model, diff, prefix_cache=True, suffix_skip=True)
+    for wi, (B, T, n_obs, obsf) in enumerate([(2, 6, 2, "x_0"), (3, 5, 4, "x_t_minus_1")]):
+        c = _rand_window(B, T, 32, n_obs, seed=500 + wi)
+        read = ~((c["obs_mask"].reshape(B, T) == 1) & (c["latent_mask"].reshape(B, T) == 0))
+        kw = _window_kw(c, obsf)
+        x_init = (c["x0"] + 0.1 * c["x"]).cuda()
+        want = plain.begin(x_init, kw, sampler="ddim_reverse", renoise=False).run().clone().cpu()
+        skip.begin(x_init, kw, sampler="ddim_reverse", renoise=False)
+        assert skip.suffix_frames == int(read.sum())
+        got = skip.run().clone().cpu()
+        assert torch.isfinite(got).all() and torch.equal(got[read], want[read]), (wi, float((got[read] - want[read]).abs().max()))
+        assert not torch.equal(got[~read], want[~read])                          # really skipped
+        both.begin(x_init, kw, sampler="ddim_reverse", renoise=False)
+        assert both.cached_frames == (B * n_obs if obsf == "x_0" else 0)
+        close(both.run().clone().cpu()[read], want[read], atol=2e-6, rtol=2e-6)   # the prefix cache folds GroupNorm sums in another fp64 grouping
+    model.check_device_errors()

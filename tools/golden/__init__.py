@@ -35,6 +35,7 @@ MANIFEST = {
     "attn_denoised_tiny.npz": (steps.attn_denoised, 1, False),
     "variants_tiny.npz": (steps.variants, 3, False),
     "loops_tiny.npz": (loops_nll.loops, 5, False),
+    "ddim_reverse_tiny.npz": (loops_nll.ddim_reverse, 4, False),
     "nll_tiny.npz": (loops_nll.nll, 3, False),
     "nll_xstart_tiny.npz": (loops_nll.nll_xstart, 2, False),
     "grad_tiny.npz": (guidance.grad, 5, False),

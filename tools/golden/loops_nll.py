@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _reference
-from ._common import build, kwargs_of, make_inputs, save_npz, tiny_cfg
+from ._common import build, denoised_fn, kwargs_of, make_inputs, save_npz, tiny_cfg
 
 
 def _inputs(seed, fidx_rows):
@@ -46,6 +46,68 @@ def loops(out):
             rec[f"ddim_eta{int(eta)}_step0"] = steps[0]
             rec[f"ddim_eta{int(eta)}_final"] = steps[-1]
     return [save_npz(out, "loops_tiny.npz", **rec)]
+
+
+THIN = 3        # ddim_reverse: an array no later step reads as its input keeps every THIN-th row and column
+
+
+def ddim_reverse(out):
+    """GaussianDiffusion.ddim_reverse_sample (gaussian_diffusion.py:636-668), the deterministic DDIM step from x_t to x_{t+1}, on
+    the inputs of `loops`.  The reference has no loop for it: a chain here is x = x0 at t = 0, then t = 1..4 each on the previous
+    step's 'sample'.  'x_0' (clip on): every step's 'sample' and 'pred_xstart'; 'x_t' and 'x_t_minus_1' (model_kwargs['x_t_minus_1']
+    = x0, read as it is): step 0 and the final sample; a clip_denoised=False chain; the predict_xstart=True config of `xstart`
+    at t = 0, 120, 249 on x = x0; `denoised_fn` (steps.denoised's function) at t = 0 and t = 2 of the 'x_0' chain.
+    A 'sample' that a recorded later step starts from is whole; every other array is thinned to [..., ::THIN, ::THIN]
+    (`<name>_thin`), which keeps the file under loops_tiny.npz's size."""
+    cfg = tiny_cfg("ddim5")
+    model, diff = build(cfg)
+    inp = _inputs(21, [[0, 1, 2, 3], [4, 5, 8, 11]])
+    x0 = inp["x0"]
+    B = x0.shape[0]
+    rec = dict(cfg_json=np.array(json.dumps(cfg)), thin=np.array(THIN), **{k: v.numpy() for k, v in inp.items()})
+
+    def thin(v):
+        return np.ascontiguousarray(v.numpy()[..., ::THIN, ::THIN])
+
+    def step(model, diff, x, tv, obsf="x_0", clip=True, fn=None):
+        return diff.ddim_reverse_sample(model, x, torch.tensor([tv] * B), clip_denoised=clip, denoised_fn=fn,
+                                        model_kwargs=kwargs_of(inp, obsf))
+
+    def chain(obsf, clip):
+        x, outs = x0, []
+        for tv in range(diff.num_timesteps):
+            outs.append(step(model, diff, x, tv, obsf, clip))
+            assert set(outs[-1]) == {"sample", "pred_xstart"}
+            x = outs[-1]["sample"]
+        return outs
+
+    with torch.no_grad():
+        for tv, o in enumerate(chain("x_0", True)):
+            rec[f"x_0_t{tv}_sample"] = o["sample"].numpy()
+            rec[f"x_0_t{tv}_pred_xstart_thin"] = thin(o["pred_xstart"])
+        for obsf in ("x_t", "x_t_minus_1"):
+            outs = chain(obsf, True)
+            rec[f"{obsf}_t0_sample_thin"] = thin(outs[0]["sample"])
+            rec[f"{obsf}_final_thin"] = thin(outs[-1]["sample"])
+        outs = chain("x_0", False)
+        for tv, o in enumerate(outs):
+            rec[f"noclip_t{tv}_sample_thin"] = thin(o["sample"])
+            rec[f"noclip_t{tv}_pred_xstart_thin"] = thin(o["pred_xstart"])
+        rec["noclip_t3_sample"] = outs[3]["sample"].numpy()              # what the t = 4 step (alpha_bar_next = 0) starts from
+        for tv in (0, 2):
+            x = x0 if tv == 0 else torch.from_numpy(rec[f"x_0_t{tv - 1}_sample"])
+            o = step(model, diff, x, tv, fn=denoised_fn)
+            rec[f"denoised_t{tv}_sample_thin"], rec[f"denoised_t{tv}_pred_xstart_thin"] = thin(o["sample"]), thin(o["pred_xstart"])
+        cfg_x = tiny_cfg("ddim250", predict_xstart=True)
+        model_x, diff_x = build(cfg_x)
+        assert diff_x.model_mean_type.name == "START_X"
+        rec["xstart_cfg_json"] = np.array(json.dumps(cfg_x))
+        for tv in (0, 120, 249):
+            for clip in (True, False):
+                o = step(model_x, diff_x, x0, tv, clip=clip)
+                tag = f"xstart_t{tv}_clip{int(clip)}"
+                rec[tag + "_sample_thin"], rec[tag + "_pred_xstart_thin"] = thin(o["sample"]), thin(o["pred_xstart"])
+    return [save_npz(out, "ddim_reverse_tiny.npz", **rec)]
 
 
 def nll(out):

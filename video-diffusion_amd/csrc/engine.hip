@@ -1790,7 +1790,7 @@ static void map_t(const vd_engine* e, const long long* t, int B, float* tm, hipS
                        e->rescale, B, e->num_timesteps, tm, e->d_err);
 }
 
-// One denoise step on `st`: t -> t_model, UNet forward, posterior update.  `t` and (when rng != null) the Philox
+// One step on `st`: t -> t_model, UNet forward, posterior update (mode 0 p_sample, 1 ddim_sample) or the DDIM encoding pass (mode 2).  `t` and (when rng != null) the Philox
 // {seed, offset} are read from device memory, so the same launch sequence serves every step of a window (executor).
 static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
                          const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
@@ -1805,6 +1805,12 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
     Arena ar = e->step_arena();
     FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
     if ((rc = e->forward(fi, st, ar, pp, sp))) return rc;
+    if (mode == 2) {                                 // ddim_reverse_sample (gaussian_diffusion.py:636-668): its own pass, no noise
+        const bool start_x = e->mean_type == 1;      // START_X: pred_xstart = process_xstart(model_output)
+        DdimReverseArgs ra{x, start_x ? nullptr : eps, start_x ? eps : nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab,
+                           e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
+        return launch_ddim_reverse(ra, st);
+    }
     PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
                      mode, eta, seed, offset, sample, xstart, mean, rng};
     pa.err = e->d_err;
@@ -1942,9 +1948,9 @@ __global__ void win_set_kernel(long long* t, unsigned long long* rng, int B, lon
     if (b == 0) { rng[0] = seed; rng[1] = offset; }
 }
 
-__global__ void win_advance_kernel(long long* t, unsigned long long* rng, int B, unsigned long long draws) {
+__global__ void win_advance_kernel(long long* t, unsigned long long* rng, int B, long long dt, unsigned long long draws) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) t[b] -= 1;
+    if (b < B) t[b] += dt;
     if (b == 0) rng[1] += draws;
 }
 
@@ -2047,8 +2053,9 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
                                 nullptr, 0, 0, e->d_win_rng, k.x, nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
                                 suf_on ? &splan : nullptr);
     if (!rc) {
-        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B,
-                           (unsigned long long)B * per);
+        const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards and draws nothing
+        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, up ? 1LL : -1LL,
+                           up ? 0ULL : (unsigned long long)B * per);
         if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
     }
     const hipError_t ce = hipStreamEndCapture(st, &wg.graph);
@@ -2083,7 +2090,9 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(sampler == 0 || sampler == 1, "sampler: 0 p_sample, 1 ddim_sample");
+    VD_REQUIRE(sampler >= 0 && sampler <= 2, "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample");
+    VD_REQUIRE(sampler != 2 || obs_mode != 2, "sampler 2 (ddim_reverse_sample) draws no noise: observed_frames = 2 re-noises the observed frames to t - 1 inside "
+                                              "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
@@ -2098,7 +2107,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     e->win_cur = -1;
     e->win_lost = false;
     ++e->win_gen;
-    e->win_left = t_start + 1;
+    e->win_left = sampler == 2 ? e->num_timesteps - t_start : t_start + 1;
     // window prefix cache (opt-in): the frames whose network input cannot change during the window -- observed (obs = 1,
     // lat = 0) in 'x_0' mode with the default 'channel' conditioning (assemble_kernel: v = obs_src, indicator channels,
     // timestep 0) -- run the blocks before the first attention layer ONCE, now; the captured step runs them on the others.
@@ -2152,7 +2161,9 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream) {
     VD_REQUIRE(e, "null engine");
     VD_REQUIRE(!e->win_lost, "window graphs invalidated (workspace growth or a new schedule since vd_window_begin): begin the window again");
     VD_REQUIRE(e->win_cur >= 0, "vd_window_begin first");
-    VD_REQUIRE(n_steps >= 0 && n_steps <= e->win_left, "more steps than the window has left (t would pass 0)");
+    const char* past = e->win_graphs[e->win_cur].key.sampler == 2 ? "more steps than the window has left (ddim_reverse_sample: t would pass num_timesteps - 1)"
+                                                                  : "more steps than the window has left (t would pass 0)";
+    VD_REQUIRE(n_steps >= 0 && n_steps <= e->win_left, past);
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int i = 0; i < n_steps; ++i) VD_HIP(hipGraphLaunch(e->win_graphs[e->win_cur].exec, st));
     e->win_left -= n_steps;
@@ -2174,6 +2185,21 @@ int vd_ddim_sample(vd_engine* e, int B, int T, const float* x, const float* obs_
                    float* eps, void* stream) {
     return sample_impl(e, 1, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, sample,
                        xstart, eps, stream);
+}
+
+int vd_ddim_reverse_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
+                           const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float* sample,
+                           float* xstart, float* eps, void* stream) {
+    return sample_impl(e, 2, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, sample, xstart, eps, stream);
+}
+
+int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const long long* t,
+                                int clip, float* sample, float* xstart, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
+    DdimReverseArgs ra{x, nullptr, xstart_in, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
+                       sample, xstart, e->d_err};
+    return launch_ddim_reverse(ra, static_cast<hipStream_t>(stream));
 }
 
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per, const float* x, const float* eps,

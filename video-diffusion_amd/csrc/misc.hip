@@ -543,6 +543,67 @@ int launch_posterior(const PosteriorArgs& a, hipStream_t s) {
     return 0;
 }
 
+// ------------------------------------------------------------------ DDIM encoding step (one fused pass)
+// ddim_reverse_sample (gaussian_diffusion.py:636-668): x_t -> x_{t+1} on the deterministic path, the reference's operation order.
+// alphas_cumprod_next[t] = append(alphas_cumprod[1:], 0.0)[t] is the TAB_ACP row at t + 1 (0 behind the last step): the float32 cast
+// is elementwise, so these are _extract_into_tensor's bits.  No noise, no Philox draws.  Four elements per thread and pass
+// (16-byte accesses; per % 4 == 0 keeps a group inside one batch item); sample may alias x: the update is elementwise.
+__device__ __forceinline__ float ddim_reverse_one(float x, float src, bool given, float sr, float srm1, float r, float s, int clip,
+                                                  float& x0_out, bool& nonfinite) {
+    float x0 = given ? src : sr * x - srm1 * src;
+    const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
+    nonfinite |= bad;
+    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0_out = x0;
+    const float e = (sr * x - x0) / srm1;
+    return x0 * r + s * e;
+}
+
+__global__ __launch_bounds__(256) void ddim_reverse_kernel(DdimReverseArgs a) {
+    const size_t per4 = (size_t)a.per / 4, total4 = (size_t)a.B * per4;
+    const int NT = a.num_timesteps;
+    const float4* x4 = reinterpret_cast<const float4*>(a.x);
+    const float4* src4 = reinterpret_cast<const float4*>(a.x0_given ? a.x0_given : a.eps);
+    const bool given = a.x0_given != nullptr;
+    float4* sample4 = reinterpret_cast<float4*>(a.sample);
+    float4* xstart4 = reinterpret_cast<float4*>(a.xstart);
+    bool nonfinite = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const long long tl = a.t[i / per4];
+        if (tl < 0 || tl >= NT) {                // IndexError in the reference; no table read: the item is poisoned, map_t_kernel has set the flag
+            const float q = __builtin_nanf("");
+            sample4[i] = make_float4(q, q, q, q);
+            if (xstart4) xstart4[i] = make_float4(q, q, q, q);
+            continue;
+        }
+        const int t = (int)tl;
+        const float sr = a.tab[TAB_SQRT_RECIP * NT + t], srm1 = a.tab[TAB_SQRT_RECIPM1 * NT + t];
+        const float abn = t + 1 < NT ? a.tab[TAB_ACP * NT + t + 1] : 0.0f;
+        const float r = sqrtf(abn), s = sqrtf(1.0f - abn);
+        const float4 x = x4[i], src = src4[i];
+        float4 x0, o;
+        o.x = ddim_reverse_one(x.x, src.x, given, sr, srm1, r, s, a.clip, x0.x, nonfinite);
+        o.y = ddim_reverse_one(x.y, src.y, given, sr, srm1, r, s, a.clip, x0.y, nonfinite);
+        o.z = ddim_reverse_one(x.z, src.z, given, sr, srm1, r, s, a.clip, x0.z, nonfinite);
+        o.w = ddim_reverse_one(x.w, src.w, given, sr, srm1, r, s, a.clip, x0.w, nonfinite);
+        if (xstart4) xstart4[i] = x0;
+        sample4[i] = o;
+    }
+    if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
+}
+
+int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s) {
+    VD_REQUIRE(a.B > 0 && a.per > 0 && a.per % 4 == 0, "ddim_reverse_kernel: 3*H*W elements per frame, a multiple of 4");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, "ddim_reverse_kernel: null tensor");
+    VD_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.sample) && al16(a.xstart), "ddim_reverse_kernel: 16-byte aligned tensors");
+    const size_t total4 = (size_t)a.B * (a.per / 4);
+    const int grid = (int)std::min<size_t>((total4 + 255) / 256, 4096);
+    hipLaunchKernelGGL(ddim_reverse_kernel, dim3(grid), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 // q_sample (gaussian_diffusion.py:190-206)
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const float* noise, const int64_t* t,
                                                        const float* tab, int NT, size_t per, size_t total, float* out) {

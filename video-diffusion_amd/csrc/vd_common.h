@@ -412,6 +412,21 @@ struct PosteriorArgs {
 };
 enum { VD_ERR_TIMESTEP = 1, VD_ERR_NONFINITE = 2 };
 int launch_posterior(const PosteriorArgs& a, hipStream_t s);
+// ddim_reverse_sample (gaussian_diffusion.py:636-668), its own pass beside posterior_kernel: no noise, no Philox state
+struct DdimReverseArgs {
+    const float* x;         // x_t   [B][per]
+    const float* eps;       // model output (null when x0_given is set)
+    const float* x0_given;  // START_X models and the denoised_fn path: the x_0 prediction itself, or null
+    const int64_t* t;       // [B] respaced index
+    const float* tab;
+    int num_timesteps;
+    int B; long per;        // per % 4 == 0, every tensor 16-byte aligned (launch_ddim_reverse checks)
+    int clip;
+    float* sample;          // x_{t+1}; may alias x
+    float* xstart;          // or null
+    int* err;               // as PosteriorArgs::err
+};
+int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s);
 int launch_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab, int num_timesteps, int B,
                     long per, float* out, hipStream_t s);
 int launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t s);

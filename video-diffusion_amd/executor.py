@@ -25,6 +25,13 @@ from . import _lib
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
+def _sampler_id(sampler):
+    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'p_sample' 0 and every other string ddim_sample, 1."""
+    if sampler == "ddim_reverse":
+        return 2
+    return 0 if sampler == "p_sample" else 1
+
+
 class WindowExecutor:
     def __init__(self, model, diffusion, prefix_cache=False, suffix_skip=False):
         """prefix_cache: compute the observed frames' activations before the first attention layer once per window instead
@@ -52,7 +59,10 @@ class WindowExecutor:
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
-        every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller)."""
+        every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
+        sampler: 'p_sample', 'ddim' or 'ddim_reverse' (ddim_reverse_sample, gaussian_diffusion.py:636-668: the window walks from
+        t_start, default 0, UP to the last index, draws no noise -- seed and eta are not read -- and takes 'x_t_minus_1' with
+        renoise=False only)."""
         mode = model_kwargs.get("observed_frames", "x_0")
         if mode not in _OBS_MODES:
             raise NotImplementedError(f"observed_frames={mode!r}: the window executor handles 'x_0', 'x_t' and 'x_t_minus_1'")
@@ -82,24 +92,26 @@ class WindowExecutor:
                 bufs["obs_src"].copy_(kw["obs_src"])
             if seed is None:
                 seed = int(th.randint(0, 2 ** 62, (1,)).item())        # torch.manual_seed governs the run
+            sid = _sampler_id(sampler)
             if t_start is None:
-                t_start = self.diffusion.num_timesteps - 1
+                t_start = 0 if sid == 2 else self.diffusion.num_timesteps - 1
             obs_src = bufs["x"] if mode == "x_t" else bufs["obs_src"]
             _lib.check(_lib.lib().vd_set_window_prefix_cache(self.model._handle, 1 if self.prefix_cache else 0))
             _lib.check(_lib.lib().vd_set_window_suffix_skip(self.model._handle, 1 if self.suffix_skip else 0))
             _lib.check(_lib.lib().vd_window_begin(
                 self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
                 _lib.ptr(bufs["latent_mask"]), _lib.ptr(bufs["kinda_marg_mask"]), _lib.ptr(bufs["frame_indices"]),
-                3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], 0 if sampler == "p_sample" else 1, 1 if clip_denoised else 0, float(eta), seed, 0,
+                3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
                 int(t_start), self.stream.cuda_stream))
         self.x = bufs["x"]
         self.seed = seed
-        self._left = int(t_start) + 1
+        self._left = self.diffusion.num_timesteps - int(t_start) if sid == 2 else int(t_start) + 1
         self._gen = int(_lib.lib().vd_window_generation(self.model._handle))
         return self
 
     def run(self, n_steps=None):
-        """Replay the step graph n_steps times (default: down to t = 0).  Returns the window tensor (updated in place)."""
+        """Replay the step graph n_steps times (default: down to t = 0; 'ddim_reverse': up to the last index).  Returns the
+        window tensor (updated in place)."""
         if n_steps is None:
             n_steps = self._left
         # the step counters are one set per engine: refuse to continue a window another executor has re-armed since

@@ -11,7 +11,8 @@ the engine as well: one UNet forward per timestep plus one fused likelihood kern
 restates losses.py's normal_kl / discretized_gaussian_log_likelihood).  Gradient guidance (`use_gradient_method`,
 gaussian_diffusion.py:264-271,350-364) runs on the engine too: vd_guided_step = a taped forward, the loss gradient and
 a backward-data pass of the whole UNet w.r.t. its input (csrc/backward.hip); `denoised_fn` and `return_attn_weights`
-are served as well.  Training losses are out of scope.
+are served as well.  `ddim_reverse_sample` (gaussian_diffusion.py:636-668), the DDIM step towards the noise, is one forward plus its
+own fused pass (csrc/misc.hip: ddim_reverse_kernel); its two loops are this project's extension.  Training losses are out of scope.
 """
 import enum
 import math
@@ -230,17 +231,23 @@ class GaussianDiffusion:
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
         the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
-        (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample."""
+        (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
+        in vd_ddim_reverse_from_xstart and draws no noise."""
         out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
         base = self._bind(model)
         dev = base.device
         xs = _f32(x, dev)
         x0 = _f32(denoised_fn(out["pred_xstart"]), dev)
         assert x0.shape == xs.shape
-        if mode is not None:
-            noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
         tt = t.to(device=dev, dtype=th.int64).contiguous()
         out.update({"sample" if mode is not None else "mean": th.empty_like(xs), "pred_xstart": th.empty_like(xs)})
+        if mode == 2:
+            _lib.check(_lib.lib().vd_ddim_reverse_from_xstart(
+                base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
+                _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]), _lib.current_stream()))
+            return out
+        if mode is not None:
+            noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
         _lib.check(_lib.lib().vd_posterior_from_xstart(
             base._handle, mode or 0, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
             float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(out.get("sample")), _lib.ptr(out["pred_xstart"]),
@@ -412,6 +419,23 @@ class GaussianDiffusion:
         sample, xstart = self._step(1, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, None)
         return {"sample": sample, "pred_xstart": xstart}
 
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """gaussian_diffusion.py:636-668: x_{t+1} from x_t by the DDIM reverse ODE.  Deterministic: no noise is drawn."""
+        assert eta == 0.0, 'Reverse ODE only for deterministic path'
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._refuse_learned(x)
+        if denoised_fn is not None:
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
+            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
+        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
+        sample, xstart = th.empty_like(xs), th.empty_like(xs)
+        B, T = xs.shape[:2]
+        _lib.check(_lib.lib().vd_ddim_reverse_sample(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
+                                                     1 if clip_denoised else 0, _lib.ptr(sample), _lib.ptr(xstart), None,
+                                                     _lib.current_stream()))
+        return {"sample": sample, "pred_xstart": xstart}
+
     def q_sample(self, x_start, t, noise=None, model=None):
         """gaussian_diffusion.py:190-206.  Needs an engine for its tables: pass `model` (or call after
         any p_sample on the same diffusion object)."""
@@ -522,5 +546,36 @@ class GaussianDiffusion:
             t = th.tensor([i] * shape[0], device=device)
             out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                    model_kwargs=model_kwargs, eta=eta)
+            yield out
+            img = out["sample"]
+
+    def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None, t_start=0,
+                                 t_end=None, progress=False):
+        """This project's extension (the reference has the step, :636-668, and no loop for it): encode `x_start`, taken as
+        x_{t_start}, by one ddim_reverse_sample per index t_start..t_end (default: the last index); returns the last sample,
+        x_{t_end + 1}.  Shaped like ddim_sample_loop."""
+        final = None
+        for sample in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                                                model_kwargs=model_kwargs, t_start=t_start, t_end=t_end,
+                                                                progress=progress):
+            final = sample
+        getattr(model, "check_device_errors", lambda: None)()
+        return final["sample"]
+
+    def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                             t_start=0, t_end=None, progress=False):
+        """This project's extension: the steps of ddim_reverse_sample_loop, one dict per index, driven from the host like
+        ddim_sample_loop_progressive.  model_kwargs are handed to every step as they are: in 'x_t_minus_1' mode the caller's
+        tensor is read unchanged (nothing is re-noised: the step draws no noise)."""
+        base = getattr(model, "model", model)
+        if t_end is None:
+            t_end = self.num_timesteps - 1
+        if not 0 <= t_start <= t_end < self.num_timesteps:
+            raise IndexError(f"t_start..t_end = {t_start}..{t_end} is outside the schedule of {self.num_timesteps} steps")
+        img = x_start
+        for i in range(t_start, t_end + 1):
+            t = th.tensor([i] * img.shape[0], device=base.device)
+            out = self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                           model_kwargs=model_kwargs)
             yield out
             img = out["sample"]
