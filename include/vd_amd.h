@@ -110,7 +110,7 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * mirror raises IndexError.  bit 0: timestep index out of range.
  * bit 1: the network output a step consumed was not finite.  The reference would carry the NaN into its sample; here the clamp
  * of clip_denoised would turn it into a plausible -1, so the posterior kernels keep such an element NaN and set this bit
- * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,
+ * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,
  * the window executor's captured step).  In the default f16x3 arithmetic (two fp16 pieces per fp32 operand) this is how an
  * operand beyond the split's range (|x| >= 2^15 = 32768: the scaled remainder (x - a0) 2^12 then leaves fp16; for a 3x3 conv the operand
  * is the Winograd-domain value, a signed sum of four inputs, so |input| < 2^13 is safe) anywhere in the network shows: VD_MATH=bf16x6
@@ -171,6 +171,37 @@ int vd_ddim_reverse_sample(vd_engine* e, int B, int T, const float* x, const flo
                            float* eps, void* stream);
 int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per_sample, const float* x, const float* xstart_in,
                                 const long long* t, int clip_denoised, float* sample, float* pred_xstart, void* stream);
+
+/* diffusion.dpmpp_2m_sample(model, x, t, prev_xstart, clip_denoised, model_kwargs) -> {'sample','pred_xstart'}: this project's
+ * extension (the reference has no such sampler) -- DPM-Solver++(2M), the second-order multistep solver in its data-prediction
+ * form, x_t -> x_{t-1}.  One UNet forward, then one fused pass of its own (dpmpp_2m_kernel, beside ddim_reverse_kernel):
+ *   D_t    = sqrt_recip[t] x - sqrt_recipm1[t] eps   (START_X: the network output), non-finite check, clamp when clip_denoised
+ *            -- what vd_ddim_sample calls pred_xstart; it is written to `pred_xstart` and is the NEXT step's prev_xstart
+ *   D      = D_t + w[t] (D_t - D_prev)   with history (prev_xstart = D_prev, the D_t of the step at index t + 1);  D = D_t without
+ *   eps'   = (sqrt_recip[t] x - D) / sqrt_recipm1[t]
+ *   sample = D sqrt(abp) + sqrt(1 - abp) eps',   abp = alphas_cumprod_prev[t]
+ * i.e. the eta = 0 DDIM update with D in place of the x_0 prediction (algebraically x <- (sigma'/sigma) x - alpha' (e^-h - 1) D, written
+ * so that nothing infinite appears at t = 0); without history it IS the eta = 0 DDIM step.  No noise is read, no Philox draw consumed.
+ * w: the row uploaded by vd_set_multistep_weights, w[t] = (lambda[t-1] - lambda[t]) / (2 (lambda[t] - lambda[t+1])) for
+ * 1 <= t <= num_timesteps - 2 with lambda = log(alphas_cumprod / (1 - alphas_cumprod)) / 2, and w[0] = w[num_timesteps - 1] = 0 (the
+ * step to alphas_cumprod_prev = 1 is first-order: lambda is infinite there).  The row belongs to the schedule: it must have the bound
+ * schedule's length, vd_set_schedule drops it, and the sampler fails by name without one.  It is a call of its own because the
+ * VD_NTAB-row table of vd_set_schedule is public layout.  The sampler is meant for steps uniform in lambda (timestep_respacing
+ * 'logsnrN' of the host mirror): with steps uniform in t and few of them w grows past 1 at the clean end and first-order DDIM can be
+ * the better choice.
+ * prev_xstart may be NULL (no history: a chain's first step) and may be the same tensor as pred_xstart (history kept in place: an
+ * element is read and then written by one thread).  Opening checks, observed_frames, a t[b] outside the schedule and a non-finite
+ * network output as in vd_ddim_sample.  pred_xstart and eps may be NULL.
+ * vd_dpmpp_2m_from_xstart: the same pass on a caller's x_0 prediction -- the `denoised_fn` form, as vd_ddim_reverse_from_xstart;
+ * per_sample = T*3*H*W must be a multiple of 4 and every tensor 16-byte aligned. */
+int vd_set_multistep_weights(vd_engine* e, int num_timesteps, const float* host_w);
+int vd_dpmpp_2m_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask,
+                       const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
+                       const long long* t, const float* prev_xstart, int observed_frames, int clip_denoised, float* sample,
+                       float* pred_xstart, float* eps, void* stream);
+int vd_dpmpp_2m_from_xstart(vd_engine* e, int B, long long per_sample, const float* x, const float* xstart_in,
+                            const float* prev_xstart, const long long* t, int clip_denoised, float* sample, float* pred_xstart,
+                            void* stream);
 
 /* diffusion.p_mean_variance(model, x, t, clip_denoised, model_kwargs) (gaussian_diffusion.py:229-372): one UNet forward,
  * then 'pred_xstart' (clipped) and 'mean' = posterior mean of it; 'variance' / 'log_variance' are the schedule rows
@@ -233,7 +264,13 @@ int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float*
  * sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample (gaussian_diffusion.py:636-668).  Sampler 2 walks UPWARDS: t_start is
  * the first index, the captured step ends in ddim_reverse_kernel in place and t += 1, the Philox counter does not move (seed, offset
  * and eta are not read), and vd_window_run refuses a run that would pass num_timesteps - 1.  It serves observed_frames 0, 1 and 3;
- * 2 needs noise inside the graph and is refused.  The prefix cache and the suffix skip apply to it unchanged. */
+ * 2 needs noise inside the graph and is refused.  The prefix cache and the suffix skip apply to it unchanged.
+ * Sampler 3 is dpmpp_2m_sample (above): it walks downwards like 0 and 1, the captured step ends in dpmpp_2m_kernel in place, the
+ * history D_prev lives in an engine-owned buffer of B*T*3*H*W floats that the pass updates in place, and a device word counting the
+ * window's finished steps tells the pass whether there is history -- so ONE graph serves a window's first step (first-order whatever
+ * t_start is) and its later ones, and a second window on the same graph starts without history again.  No Philox draws (seed, offset
+ * and eta are not read); observed_frames 2 is refused as for sampler 2; without a weight row (vd_set_multistep_weights) it fails
+ * with a message that says so.  The prefix cache and the suffix skip apply unchanged. */
 int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, const float* obs_mask,
                     const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
                     int observed_frames, int sampler, int clip_denoised, float eta, unsigned long long seed,

@@ -167,6 +167,9 @@ SIGNATURES = {
     "vd_ddim_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _U, _U, _P, _P, _P, _P]),
     "vd_ddim_reverse_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "vd_ddim_reverse_from_xstart": (_I, [_P, _I, _L, _P, _P, _P, _I, _P, _P, _P]),
+    "vd_set_multistep_weights": (_I, [_P, _I, _P]),
+    "vd_dpmpp_2m_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "vd_dpmpp_2m_from_xstart": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P]),
     "vd_p_mean_variance": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "vd_vb_terms": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vd_prior_bpd": (_I, [_P, _I, _I, _P, _P, _P, _P]),

@@ -277,6 +277,7 @@ struct vd_engine {
     float* d_freq_frame = nullptr; int n_freq_frame = 0;
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
+    float* d_w2m = nullptr;           // [num_timesteps] dpmpp_2m extrapolation weights of the bound schedule (vd_set_multistep_weights), or null
     // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded) and the eps scratch
     char* ws = nullptr; size_t ws_cap = 0;
     bool ws_suf = false;
@@ -331,7 +332,8 @@ struct vd_engine {
     long long win_left = 0;                              // steps the current window still has (t + 1)
     long long* d_win_t = nullptr; size_t win_t_cap = 0;  // [B] current respaced index of the window
     float* d_win_xtm1 = nullptr; size_t win_xtm1_cap = 0; // 'x_t_minus_1' windows: the observed frames re-noised to t - 1, redrawn every step
-    unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset}
+    unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset, steps the armed window has done}
+    float* d_win_hist = nullptr; size_t win_hist_cap = 0; // sampler 3 (dpmpp_2m): the previous step's x_0 prediction, updated in place by the pass
 
     ~vd_engine() {
         if (d_freq_time) (void)hipFree(d_freq_time);
@@ -347,6 +349,8 @@ struct vd_engine {
         if (d_win_t) (void)hipFree(d_win_t);
         if (d_win_rng) (void)hipFree(d_win_rng);
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
+        if (d_win_hist) (void)hipFree(d_win_hist);
+        if (d_w2m) (void)hipFree(d_w2m);
         for (auto& g : win_graphs) g.release();
     }
 
@@ -1683,6 +1687,7 @@ int vd_set_schedule(vd_engine* e, int nts, const float* tab, const int* tmap, fl
     e->drop_window_graphs();
     if (e->d_tab) VD_HIP(hipFree(e->d_tab));
     if (e->d_tmap) VD_HIP(hipFree(e->d_tmap));
+    if (e->d_w2m) { VD_HIP(hipFree(e->d_w2m)); e->d_w2m = nullptr; }      // the multistep weights belong to the schedule that goes
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_tab), (size_t)NTAB * nts * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_tab, tab, (size_t)NTAB * nts * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float> tm(nts);
@@ -1695,6 +1700,23 @@ int vd_set_schedule(vd_engine* e, int nts, const float* tab, const int* tmap, fl
         VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_err), sizeof(int)));
         VD_HIP(hipMemset(e->d_err, 0, sizeof(int)));
     }
+    return 0;
+}
+
+// The dpmpp_2m extrapolation weights of the bound schedule, one float per respaced index (include/vd_amd.h).  A call of its own: the
+// NTAB-row table of vd_set_schedule is public layout.  Captured sampler-3 graphs bake the row's address in: they are dropped when it moves.
+int vd_set_multistep_weights(vd_engine* e, int nts, const float* w) {
+    VD_REQUIRE(e && w, "multistep weights");
+    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(nts == e->num_timesteps, "multistep weights: one per index of the bound schedule (" + std::to_string(e->num_timesteps) + ")");
+    if (e->d_w2m) {
+        if (e->win_cur >= 0) e->win_lost = true;
+        e->drop_window_graphs();
+        VD_HIP(hipFree(e->d_w2m));
+        e->d_w2m = nullptr;
+    }
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_w2m), (size_t)nts * sizeof(float)));
+    VD_HIP(hipMemcpy(e->d_w2m, w, (size_t)nts * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1790,13 +1812,16 @@ static void map_t(const vd_engine* e, const long long* t, int B, float* tm, hipS
                        e->rescale, B, e->num_timesteps, tm, e->d_err);
 }
 
-// One step on `st`: t -> t_model, UNet forward, posterior update (mode 0 p_sample, 1 ddim_sample) or the DDIM encoding pass (mode 2).  `t` and (when rng != null) the Philox
+// One step on `st`: t -> t_model, UNet forward, posterior update (mode 0 p_sample, 1 ddim_sample), the DDIM encoding pass (mode 2) or the
+// DPM-Solver++(2M) pass (mode 3: `hist` = the previous step's x_0 prediction or null, `hist_on` = null or a device word that is 0 while
+// there is no history).  `t` and (when rng != null) the Philox
 // {seed, offset} are read from device memory, so the same launch sequence serves every step of a window (executor).
 static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
                          const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
                          int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
                          const unsigned long long* rng, float* sample, float* xstart, float* mean, float* eps_out,
-                         hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr) {
+                         hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr, const float* hist = nullptr,
+                         const unsigned long long* hist_on = nullptr) {
     int rc;
     const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
     float* tm = e->step_tm();
@@ -1811,6 +1836,12 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
                            e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
         return launch_ddim_reverse(ra, st);
     }
+    if (mode == 3) {                                 // dpmpp_2m_sample: its own pass, no noise
+        const bool start_x = e->mean_type == 1;
+        Dpmpp2mArgs ma{x, start_x ? nullptr : eps, start_x ? eps : nullptr, hist, hist_on, reinterpret_cast<const int64_t*>(t), e->d_tab,
+                       e->d_w2m, e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
+        return launch_dpmpp_2m(ma, st);
+    }
     PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
                      mode, eta, seed, offset, sample, xstart, mean, rng};
     pa.err = e->d_err;
@@ -1822,14 +1853,15 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
 static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
                        const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
                        int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
-                       float* sample, float* xstart, float* eps_out, void* stream) {
+                       float* sample, float* xstart, float* eps_out, void* stream, const float* hist = nullptr) {
     int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && sample, "null tensor");
     VD_REQUIRE(mode == 0 || eta >= 0.f, "eta");
+    VD_REQUIRE(mode != 3 || e->d_w2m, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     if ((rc = e->ensure_ws(B, T))) return rc;
     return step_launches(e, mode, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, nullptr,
-                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream));
+                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist);
 }
 
 int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
@@ -1945,22 +1977,23 @@ __global__ void win_set_kernel(long long* t, unsigned long long* rng, int B, lon
                                unsigned long long offset) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) t[b] = t_start;
-    if (b == 0) { rng[0] = seed; rng[1] = offset; }
+    if (b == 0) { rng[0] = seed; rng[1] = offset; rng[2] = 0; }
 }
 
 __global__ void win_advance_kernel(long long* t, unsigned long long* rng, int B, long long dt, unsigned long long draws) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) t[b] += dt;
-    if (b == 0) rng[1] += draws;
+    if (b == 0) { rng[1] += draws; rng[2] += 1; }
 }
 
 // ---- the steps of vd_window_begin
-// the executor's device state for a window of B entries: the step counters, the Philox pair and, in 'x_t_minus_1' mode, the
-// observed frames re-noised to t - 1 (per: floats of one entry)
-static int window_buffers(vd_engine* e, int B, int obs_mode, size_t per) {
+// the executor's device state for a window of B entries: the step counters, the Philox pair with the count of finished steps behind
+// it, for sampler 3 the history of B * per floats and, in 'x_t_minus_1' mode, the observed frames re-noised to t - 1 (per: floats of one entry)
+static int window_buffers(vd_engine* e, int B, int obs_mode, int sampler, size_t per) {
     int rc = e->grow(e->d_win_t, e->win_t_cap, (size_t)B, true);
     if (rc) return rc;
-    if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 2 * sizeof(unsigned long long)));
+    if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 3 * sizeof(unsigned long long)));
+    if (sampler == 3 && (rc = e->grow(e->d_win_hist, e->win_hist_cap, (size_t)B * per, true))) return rc;
     return obs_mode == 2 ? e->grow(e->d_win_xtm1, e->win_xtm1_cap, (size_t)B * per, true) : 0;
 }
 
@@ -2049,13 +2082,16 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     }
     VD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     rc = renoise_observed(e, k, st);
+    // sampler 3 (dpmpp_2m_sample): the pass reads the history and writes the step's x_0 prediction over it; the count of finished steps
+    // (0 on a window's first step, whatever t_start is) tells it whether the buffer holds one
+    const bool ms = k.sampler == 3;
     if (!rc) rc = step_launches(e, k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta,
-                                nullptr, 0, 0, e->d_win_rng, k.x, nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
-                                suf_on ? &splan : nullptr);
+                                nullptr, 0, 0, e->d_win_rng, k.x, ms ? e->d_win_hist : nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
+                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr);
     if (!rc) {
-        const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards and draws nothing
+        const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards; it and dpmpp_2m_sample draw nothing
         hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, up ? 1LL : -1LL,
-                           up ? 0ULL : (unsigned long long)B * per);
+                           up || ms ? 0ULL : (unsigned long long)B * per);
         if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
     }
     const hipError_t ce = hipStreamEndCapture(st, &wg.graph);
@@ -2090,14 +2126,17 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(sampler >= 0 && sampler <= 2, "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample");
+    VD_REQUIRE(sampler >= 0 && sampler <= 3, "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample");
     VD_REQUIRE(sampler != 2 || obs_mode != 2, "sampler 2 (ddim_reverse_sample) draws no noise: observed_frames = 2 re-noises the observed frames to t - 1 inside "
                                               "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
+    VD_REQUIRE(sampler != 3 || obs_mode != 2, "sampler 3 (dpmpp_2m_sample) draws no noise: observed_frames = 2 re-noises the observed frames to t - 1 inside "
+                                              "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
+    VD_REQUIRE(sampler != 3 || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = e->ensure_ws(B, T))) return rc;
-    if ((rc = window_buffers(e, B, obs_mode, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
+    if ((rc = window_buffers(e, B, obs_mode, sampler, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
     hipLaunchKernelGGL(win_set_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, t_start, seed, offset);
     VD_HIP(hipGetLastError());
     vd_engine::WinKey key;
@@ -2191,6 +2230,22 @@ int vd_ddim_reverse_sample(vd_engine* e, int B, int T, const float* x, const flo
                            const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float* sample,
                            float* xstart, float* eps, void* stream) {
     return sample_impl(e, 2, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, sample, xstart, eps, stream);
+}
+
+int vd_dpmpp_2m_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
+                       const float* km, const long long* fidx, const long long* t, const float* prev_xstart, int obs_mode, int clip,
+                       float* sample, float* xstart, float* eps, void* stream) {
+    return sample_impl(e, 3, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, sample, xstart, eps, stream,
+                       prev_xstart);
+}
+
+int vd_dpmpp_2m_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const float* prev_xstart,
+                            const long long* t, int clip, float* sample, float* xstart, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
+    Dpmpp2mArgs ma{x, nullptr, xstart_in, prev_xstart, nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab, e->d_w2m, e->num_timesteps,
+                   B, (long)per, clip, sample, xstart, e->d_err};
+    return launch_dpmpp_2m(ma, static_cast<hipStream_t>(stream));
 }
 
 int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const long long* t,

@@ -604,6 +604,74 @@ int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s) {
     return 0;
 }
 
+// ------------------------------------------------------------------ DPM-Solver++(2M) step (one fused pass)
+// dpmpp_2m_sample (this project's extension): D_t formed as posterior_kernel forms pred_xstart; with history D = D_t + w[t] (D_t - D_prev),
+// else D = D_t; then the eta = 0 DDIM update with D for x_0: e = (sr x - D) / srm1, sample = D sqrt(abp) + sqrt(1 - abp) e.  At t = 0
+// abp = 1 and w = 0: sample = D_t, nothing infinite.  Whether there is history is DATA (a null pointer, or a device word that is 0), so
+// one captured graph serves a window's first and later steps.  hist may alias xstart (in-place history): group i is read before it is
+// written, by the same thread.  Four elements per thread and pass as ddim_reverse_kernel; sample may alias x.
+__device__ __forceinline__ float dpmpp_2m_one(float x, float src, bool given, float prev, bool have, float w, float sr, float srm1,
+                                              float r, float s, int clip, float& x0_out, bool& nonfinite) {
+    float x0 = given ? src : sr * x - srm1 * src;
+    const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
+    nonfinite |= bad;
+    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    x0_out = x0;
+    const float d = have ? x0 + w * (x0 - prev) : x0;
+    const float e = (sr * x - d) / srm1;
+    return d * r + s * e;
+}
+
+__global__ __launch_bounds__(256) void dpmpp_2m_kernel(Dpmpp2mArgs a) {
+    const size_t per4 = (size_t)a.per / 4, total4 = (size_t)a.B * per4;
+    const int NT = a.num_timesteps;
+    const float4* x4 = reinterpret_cast<const float4*>(a.x);
+    const float4* src4 = reinterpret_cast<const float4*>(a.x0_given ? a.x0_given : a.eps);
+    const bool given = a.x0_given != nullptr;
+    const float4* hist4 = reinterpret_cast<const float4*>(a.hist);
+    const bool have = hist4 != nullptr && (a.hist_on == nullptr || *a.hist_on != 0ULL);
+    float4* sample4 = reinterpret_cast<float4*>(a.sample);
+    float4* xstart4 = reinterpret_cast<float4*>(a.xstart);
+    bool nonfinite = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const long long tl = a.t[i / per4];
+        if (tl < 0 || tl >= NT) {                // as the sibling passes: no table read, the item is poisoned, map_t_kernel has set the flag
+            const float q = __builtin_nanf("");
+            sample4[i] = make_float4(q, q, q, q);
+            if (xstart4) xstart4[i] = make_float4(q, q, q, q);
+            continue;
+        }
+        const int t = (int)tl;
+        const float sr = a.tab[TAB_SQRT_RECIP * NT + t], srm1 = a.tab[TAB_SQRT_RECIPM1 * NT + t];
+        const float abp = a.tab[TAB_ACP_PREV * NT + t], w = a.w[t];
+        const float r = sqrtf(abp), s = sqrtf(1.0f - abp);
+        const float4 x = x4[i], src = src4[i];
+        const float4 p = have ? hist4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 x0, o;
+        o.x = dpmpp_2m_one(x.x, src.x, given, p.x, have, w, sr, srm1, r, s, a.clip, x0.x, nonfinite);
+        o.y = dpmpp_2m_one(x.y, src.y, given, p.y, have, w, sr, srm1, r, s, a.clip, x0.y, nonfinite);
+        o.z = dpmpp_2m_one(x.z, src.z, given, p.z, have, w, sr, srm1, r, s, a.clip, x0.z, nonfinite);
+        o.w = dpmpp_2m_one(x.w, src.w, given, p.w, have, w, sr, srm1, r, s, a.clip, x0.w, nonfinite);
+        if (xstart4) xstart4[i] = x0;
+        sample4[i] = o;
+    }
+    if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
+}
+
+int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s) {
+    VD_REQUIRE(a.B > 0 && a.per > 0 && a.per % 4 == 0, "dpmpp_2m_kernel: 3*H*W elements per frame, a multiple of 4");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, "dpmpp_2m_kernel: null tensor");
+    VD_REQUIRE(a.w, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    VD_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.hist) && al16(a.sample) && al16(a.xstart),
+               "dpmpp_2m_kernel: 16-byte aligned tensors");
+    const size_t total4 = (size_t)a.B * (a.per / 4);
+    const int grid = (int)std::min<size_t>((total4 + 255) / 256, 4096);
+    hipLaunchKernelGGL(dpmpp_2m_kernel, dim3(grid), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 // q_sample (gaussian_diffusion.py:190-206)
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* x0, const float* noise, const int64_t* t,
                                                        const float* tab, int NT, size_t per, size_t total, float* out) {

@@ -427,6 +427,26 @@ struct DdimReverseArgs {
     int* err;               // as PosteriorArgs::err
 };
 int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s);
+// dpmpp_2m_sample (this project's extension: DPM-Solver++(2M) in its data-prediction form), its own pass in the shape of the one above:
+// D_t as ddim_sample forms pred_xstart, D = D_t + w[t] (D_t - D_prev) when there is history, then the eta = 0 DDIM update with D
+struct Dpmpp2mArgs {
+    const float* x;         // x_t   [B][per]
+    const float* eps;       // model output (null when x0_given is set)
+    const float* x0_given;  // START_X models and the denoised_fn path: the x_0 prediction itself, or null
+    const float* hist;      // D_prev: the previous step's D_t, or null (no history).  May alias xstart: element i is read and then
+                            // written by the same thread, which is how the window executor keeps its history in place
+    const unsigned long long* hist_on;  // or null; a device word: 0 = this step has no history whatever `hist` holds (a window's first step)
+    const int64_t* t;       // [B] respaced index
+    const float* tab;
+    const float* w;         // [num_timesteps] extrapolation weights (vd_set_multistep_weights); w[0] = w[num_timesteps - 1] = 0
+    int num_timesteps;
+    int B; long per;        // per % 4 == 0, every tensor 16-byte aligned (launch_dpmpp_2m checks)
+    int clip;
+    float* sample;          // x_{t-1}; may alias x
+    float* xstart;          // D_t (the next step's history), or null
+    int* err;               // as PosteriorArgs::err
+};
+int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s);
 int launch_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab, int num_timesteps, int B,
                     long per, float* out, hipStream_t s);
 int launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t s);

@@ -26,9 +26,11 @@ _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
 def _sampler_id(sampler):
-    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'p_sample' 0 and every other string ddim_sample, 1."""
+    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'p_sample' 0 and every other string ddim_sample, 1."""
     if sampler == "ddim_reverse":
         return 2
+    if sampler == "dpmpp_2m":
+        return 3
     return 0 if sampler == "p_sample" else 1
 
 
@@ -62,7 +64,9 @@ class WindowExecutor:
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
         sampler: 'p_sample', 'ddim' or 'ddim_reverse' (ddim_reverse_sample, gaussian_diffusion.py:636-668: the window walks from
         t_start, default 0, UP to the last index, draws no noise -- seed and eta are not read -- and takes 'x_t_minus_1' with
-        renoise=False only)."""
+        renoise=False only) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: walks down like 'ddim', the previous step's
+        x_0 prediction lives in an engine-owned buffer, the window's first step is first-order whatever t_start is, no noise --
+        seed and eta are not read -- and 'x_t_minus_1' with renoise=False only)."""
         mode = model_kwargs.get("observed_frames", "x_0")
         if mode not in _OBS_MODES:
             raise NotImplementedError(f"observed_frames={mode!r}: the window executor handles 'x_0', 'x_t' and 'x_t_minus_1'")

@@ -12,7 +12,9 @@ restates losses.py's normal_kl / discretized_gaussian_log_likelihood).  Gradient
 gaussian_diffusion.py:264-271,350-364) runs on the engine too: vd_guided_step = a taped forward, the loss gradient and
 a backward-data pass of the whole UNet w.r.t. its input (csrc/backward.hip); `denoised_fn` and `return_attn_weights`
 are served as well.  `ddim_reverse_sample` (gaussian_diffusion.py:636-668), the DDIM step towards the noise, is one forward plus its
-own fused pass (csrc/misc.hip: ddim_reverse_kernel); its two loops are this project's extension.  Training losses are out of scope.
+own fused pass (csrc/misc.hip: ddim_reverse_kernel); its two loops are this project's extension.  `dpmpp_2m_sample` with its two
+loops is an extension as a whole: DPM-Solver++(2M), the second-order multistep sampler the reference does not have -- one forward plus
+one fused pass (dpmpp_2m_kernel) that reuses the previous step's x_0 prediction.  Training losses are out of scope.
 """
 import enum
 import math
@@ -131,6 +133,15 @@ class GaussianDiffusion:
         scale = 1000.0 / self.num_timesteps if self.rescale_timesteps else 1.0
         return list(range(self.num_timesteps)), scale
 
+    def _multistep_weights(self):
+        """dpmpp_2m_sample's extrapolation weights, float64: w[t] = (lam[t-1] - lam[t]) / (2 (lam[t] - lam[t+1])) for
+        1 <= t <= N - 2 with lam = log(acp / (1 - acp)) / 2; w[0] = 0 (the step to alphas_cumprod_prev = 1 is first-order:
+        lam is infinite there) and w[N-1] = 0 (the first step of a full chain has no history)."""
+        lam = 0.5 * np.log(self.alphas_cumprod / (1.0 - self.alphas_cumprod))
+        w = np.zeros(self.num_timesteps, dtype=np.float64)
+        w[1:-1] = 0.5 * (lam[:-2] - lam[1:-1]) / (lam[1:-1] - lam[2:])
+        return w
+
     def _bind(self, model):
         """Upload this process' tables into the model's engine (once per (diffusion, model) pair)."""
         model = getattr(model, "model", model)            # accept a _WrappedModel
@@ -141,6 +152,8 @@ class GaussianDiffusion:
             _lib.check(_lib.lib().vd_set_schedule(model._handle, self.num_timesteps, _lib.ptr(tab), _lib.ptr(tm),
                                                   float(np.float32(scale))))
             _lib.check(_lib.lib().vd_set_model_mean_type(model._handle, 1 if self.model_mean_type == ModelMeanType.START_X else 0))
+            w = np.ascontiguousarray(self._multistep_weights().astype(np.float32))       # cast elementwise, as the table's rows
+            _lib.check(_lib.lib().vd_set_multistep_weights(model._handle, self.num_timesteps, _lib.ptr(w)))
             model._bound_schedule = self
         return model
 
@@ -227,12 +240,14 @@ class GaussianDiffusion:
             _lib.ptr(sample) if want_sample else None, _lib.current_stream()))
         return {"mean": mean, "pred_xstart": xstart, "grad": grad, "sample": sample}
 
-    def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None):
+    def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None,
+                  prev_xstart=None):
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
         the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
         (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
-        in vd_ddim_reverse_from_xstart and draws no noise."""
+        in vd_ddim_reverse_from_xstart and draws no noise; mode 3 (dpmpp_2m_sample, with its `prev_xstart` or None) ends in
+        vd_dpmpp_2m_from_xstart and draws none either."""
         out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
         base = self._bind(model)
         dev = base.device
@@ -245,6 +260,13 @@ class GaussianDiffusion:
             _lib.check(_lib.lib().vd_ddim_reverse_from_xstart(
                 base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
                 _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]), _lib.current_stream()))
+            return out
+        if mode == 3:
+            prev = None if prev_xstart is None else _f32(prev_xstart, dev)
+            assert prev is None or prev.shape == xs.shape
+            _lib.check(_lib.lib().vd_dpmpp_2m_from_xstart(
+                base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(prev), _lib.ptr(tt),
+                1 if clip_denoised else 0, _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]), _lib.current_stream()))
             return out
         if mode is not None:
             noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
@@ -436,6 +458,29 @@ class GaussianDiffusion:
                                                      _lib.current_stream()))
         return {"sample": sample, "pred_xstart": xstart}
 
+    def dpmpp_2m_sample(self, model, x, t, prev_xstart=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
+        """This project's extension (the reference has no such sampler): one step x_t -> x_{t-1} of DPM-Solver++(2M), the
+        second-order multistep solver in its data-prediction form.  `pred_xstart` is formed as ddim_sample forms it; with
+        `prev_xstart` -- the 'pred_xstart' the previous step (index t + 1) returned -- the update runs on
+        D = pred_xstart + w[t] (pred_xstart - prev_xstart), without it (a chain's first step) on pred_xstart itself, and is
+        then ddim_sample's with eta = 0 (_multistep_weights; include/vd_amd.h: vd_dpmpp_2m_sample).  No noise is drawn.  Meant for
+        timestep_respacing='logsnrN'; with 'ddimN' at small N first-order ddim_sample can be the better choice."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._refuse_learned(x)
+        if denoised_fn is not None:
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=3, prev_xstart=prev_xstart)
+            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
+        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
+        prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
+        assert prev is None or prev.shape == xs.shape
+        sample, xstart = th.empty_like(xs), th.empty_like(xs)
+        B, T = xs.shape[:2]
+        _lib.check(_lib.lib().vd_dpmpp_2m_sample(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), _lib.ptr(prev),
+                                                 kw["obs_mode"], 1 if clip_denoised else 0, _lib.ptr(sample), _lib.ptr(xstart), None,
+                                                 _lib.current_stream()))
+        return {"sample": sample, "pred_xstart": xstart}
+
     def q_sample(self, x_start, t, noise=None, model=None):
         """gaussian_diffusion.py:190-206.  Needs an engine for its tables: pass `model` (or call after
         any p_sample on the same diffusion object)."""
@@ -579,3 +624,32 @@ class GaussianDiffusion:
                                            model_kwargs=model_kwargs)
             yield out
             img = out["sample"]
+
+    def dpmpp_2m_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                             latent_mask=None, device=None, progress=False):
+        """This project's extension, shaped like ddim_sample_loop: dpmpp_2m_sample from the last index down to 0, each step handed
+        the x_0 prediction of the one before; returns the sample only."""
+        final = None
+        for sample in self.dpmpp_2m_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                            denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                            device=device, progress=progress):
+            final = sample
+        getattr(model, "check_device_errors", lambda: None)()
+        return final["sample"]
+
+    def dpmpp_2m_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                         model_kwargs=None, latent_mask=None, device=None, progress=False):
+        """This project's extension: the steps of dpmpp_2m_sample_loop, one dict per index, driven from the host like
+        ddim_sample_loop_progressive.  The first step has no history and is first-order."""
+        base = getattr(model, "model", model)
+        if device is None:
+            device = base.device
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else th.randn(*shape, device=device)
+        prev = None
+        for i in list(range(self.num_timesteps))[::-1]:
+            t = th.tensor([i] * shape[0], device=device)
+            out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                       model_kwargs=model_kwargs)
+            yield out
+            img, prev = out["sample"], out["pred_xstart"]

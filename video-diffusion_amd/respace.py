@@ -36,6 +36,27 @@ def space_timesteps(num_timesteps, section_counts):
     return taken
 
 
+def logsnr_timesteps(betas, num_steps):
+    """This project's extension (the reference has no such respacing; `timestep_respacing="logsnrN"` of create_gaussian_diffusion):
+    exactly `num_steps` distinct indices of the base schedule, 0 and n - 1 among them, as uniform as the grid allows in
+    lambda_i = log(acp_i / (1 - acp_i)) / 2 -- the spacing dpmpp_2m_sample is meant for: its extrapolation weights stay
+    near 1/2, where steps uniform in t let them grow past 1 at the clean end.  float64 throughout: the targets
+    linspace(lambda_0, lambda_{n-1}, num_steps), the nearest index of each (first minimum), then one pass upwards and one
+    downwards that make the list strictly increasing inside 0..n - 1."""
+    acp = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64), axis=0)
+    n = int(acp.shape[0])
+    if not 2 <= num_steps <= n:
+        raise ValueError(f"cannot pick {num_steps} logSNR-uniform steps from a schedule of {n}: 2 <= N <= {n}")
+    lam = 0.5 * np.log(acp / (1.0 - acp))
+    idx = [int(np.argmin(np.abs(lam - target))) for target in np.linspace(lam[0], lam[-1], num_steps)]
+    for k in range(1, num_steps):
+        idx[k] = max(idx[k], idx[k - 1] + 1)
+    idx[-1] = min(idx[-1], n - 1)
+    for k in range(num_steps - 2, -1, -1):
+        idx[k] = min(idx[k], idx[k + 1] - 1)
+    return idx
+
+
 def _walk(stride, count):
     pos = 0.0                      # accumulated, not k*stride: the reference's float drift is part of the contract
     for _ in range(count):

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import gaussian_diffusion as gd
-from .respace import SpacedDiffusion, space_timesteps
+from .respace import SpacedDiffusion, logsnr_timesteps, space_timesteps
 from .unet import CondMargVideoModel
 
 
@@ -63,7 +63,8 @@ def create_video_model(T, image_size, num_channels, num_res_blocks, learn_sigma,
 def create_gaussian_diffusion(*, steps=1000, learn_sigma=False, sigma_small=False, noise_schedule="linear",
                               use_kl=False, predict_xstart=False, rescale_timesteps=False,
                               rescale_learned_sigmas=False, timestep_respacing=""):
-    """script_util.py:405-436."""
+    """script_util.py:405-436.  timestep_respacing="logsnrN" is this project's extension: N steps uniform in logSNR
+    (respace.logsnr_timesteps), the spacing dpmpp_2m_sample is meant for; every other string goes to space_timesteps."""
     betas = gd.get_named_beta_schedule(noise_schedule, steps)
     if use_kl:
         loss_type = gd.LossType.RESCALED_KL
@@ -77,8 +78,12 @@ def create_gaussian_diffusion(*, steps=1000, learn_sigma=False, sigma_small=Fals
         var_type = gd.ModelVarType.LEARNED_RANGE
     else:
         var_type = gd.ModelVarType.FIXED_SMALL if sigma_small else gd.ModelVarType.FIXED_LARGE
+    if isinstance(timestep_respacing, str) and timestep_respacing.startswith("logsnr"):
+        use_timesteps = logsnr_timesteps(betas, int(timestep_respacing[len("logsnr"):]))
+    else:
+        use_timesteps = space_timesteps(steps, timestep_respacing)
     return SpacedDiffusion(
-        use_timesteps=space_timesteps(steps, timestep_respacing), betas=betas,
+        use_timesteps=use_timesteps, betas=betas,
         model_mean_type=gd.ModelMeanType.START_X if predict_xstart else gd.ModelMeanType.EPSILON,
         model_var_type=var_type, loss_type=loss_type, rescale_timesteps=rescale_timesteps)
 

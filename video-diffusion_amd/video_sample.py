@@ -62,7 +62,11 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     the first attention layer once per window instead of once per step (executor.py; 2.6 % at 4 observed frames of 16, 12 %
     at 10 of 20, profiles/r03x_*).  `suffix_skip` (graph executor, 'x_0' / 'x_t_minus_1'): everything behind the last attention
     layer runs without the purely observed frames, whose step output this function never reads (write_back keeps the latent
-    frames only); the latent frames are those of the full step (executor.py, include/vd_amd.h: vd_set_window_suffix_skip)."""
+    frames only); the latent frames are those of the full step (executor.py, include/vd_amd.h: vd_set_window_suffix_skip).
+
+    sampler: 'p_sample' (default), 'ddim' (ddim_sample with `eta`) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: the
+    second-order multistep solver; each window starts without history, so its first step is first-order; on both executors; meant for
+    timestep_respacing='logsnrN')."""
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -130,8 +134,13 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             continue
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
+        prev_xstart = None                                  # dpmpp_2m: the history is the window's own
         for timestep in timesteps:
-            if sampler == "p_sample":
+            if sampler == "dpmpp_2m":
+                out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
+                                                model_kwargs=model_kwargs)
+                local_samples, prev_xstart = out["sample"], out["pred_xstart"]
+            elif sampler == "p_sample":
                 local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
                                                    model_kwargs=model_kwargs, return_attn_weights=False,
                                                    use_gradient_method=use_gradient_method)["sample"]
@@ -354,8 +363,12 @@ def load_lpips_for(args, device):
     return _lpips_loaded[key]
 
 
-def main(argv=None):
+def build_parser():
     ap = add_job_arguments(argparse.ArgumentParser())
+    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m"],
+                    help="the step: p_sample (default), ddim (ddim_sample with --eta) or dpmpp_2m (the second-order multistep solver, meant for "
+                         "--timestep_respacing logsnrN); a non-default sampler is named in the run directory")
+    ap.add_argument("--eta", type=float, default=0.0, help="with --sampler ddim: ddim_sample's eta")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -366,14 +379,18 @@ def main(argv=None):
                          "on the non-observed frames only")
     ap.add_argument("--prefix_cache", type=str2bool, nargs="?", const=True, default=False,
                     help="with --executor graph and observed_frames x_0: compute the observed frames' encoder prefix once per window")
-    args = parse_with_lpips(ap, argv)
-    return run(args)
+    return ap
+
+
+def main(argv=None):
+    return run(parse_with_lpips(build_parser(), argv))
 
 
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
     return infer_video(args.inference_mode, model, diffusion, batch, args.max_frames, args.obs_length, args.step_size,
                        optimal_schedule_path, use_gradient_method=getattr(args, "use_gradient_method", False),
-                       observed_frames=args.observed_frames, executor=getattr(args, "executor", "eager"),
+                       observed_frames=args.observed_frames, sampler=getattr(args, "sampler", "p_sample"), eta=getattr(args, "eta", 0.0),
+                       executor=getattr(args, "executor", "eager"),
                        adaptive_distance=getattr(args, "adaptive_distance", "l2"),
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
                        save_all_timesteps=getattr(args, "save_all_timesteps", False))
@@ -402,7 +419,9 @@ def run(args, create=None, device=None, infer=None):
     infer = infer or _default_infer
     # the run identifier is formed from the options AS GIVEN, before --max_frames / --T take their defaults from the model and
     # the dataset (video_sample.py:530-533 precedes :568-570,612-615: an unset one reads 'None' in the directory name)
-    run_id = test_util.get_eval_run_identifier(args)
+    # (a sampler other than the default is part of the name: samples of different samplers never share a directory)
+    sampler = getattr(args, "sampler", "p_sample")
+    run_id = test_util.get_eval_run_identifier(args, postfix="" if sampler == "p_sample" else f"_{sampler}")
     model, diffusion = load_model(args, device, rank, world, create=create)
     if args.max_frames is None:                                            # video_sample.py:568-570
         args.max_frames = model.config.get("max_frames") or model.config["T"]
