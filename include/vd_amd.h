@@ -125,7 +125,9 @@ int vd_device_errors(vd_engine* e, int* flags);
 int vd_max_window_frames(void);
 
 /* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
- * grow with B*T^2 (about 60 KB per (b, t, s) pair for the default 64x64 model: ~1 GB at B = 1, T = 128). */
+ * grow with B*T^2 (about 60 KB per (b, t, s) pair for the default 64x64 model: ~1 GB at B = 1, T = 128).  The figure is the
+ * activation arena of one forward plus the step's tail: t_model and the two network-output buffers (the second one is out_u of a
+ * cfg_scale != 1 step, below). */
 int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes);
 
 /* observed_frames: 0 'x_0', 1 'x_t', 2 'x_t_minus_1' (unet.py:958-974,991-1013). */
@@ -308,6 +310,33 @@ int vd_window_prefix_frames(vd_engine* e);
  * vd_window_suffix_frames: frames the suffix of the armed window runs on (0: all of them -- skip off or nothing to skip). */
 int vd_set_window_suffix_skip(vd_engine* e, int on);
 int vd_window_suffix_frames(vd_engine* e);
+
+/* cfg_scale: classifier-free guidance on the observed frames -- this project's extension (the reference samples at w = 1 only).  The
+ * model is trained on every split of a window into observed and latent frames, the empty observed set included, so one set of weights
+ * gives both branches.  For a step on (x, t, obs_mask, latent_mask, kinda_marg_mask, frame_indices, observed_frames) and w = cfg_scale:
+ *   out_c = the network output of the step as it runs at w = 1
+ *   out_u = the network output of the same call with obs_mask := 0 and nothing else changed: the formerly observed frames become
+ *           padding frames (unet.py:953-983: fed x (1 - anything_mask), masked out of temporal attention)
+ *   d     = out_c - out_u            one fp32 subtraction
+ *   out_g = fmaf(w, d, out_u)        one fused multiply-add;  NaN where d is not finite;  out_u itself at w = 0
+ * and out_g takes the place of the network output in front of the unchanged sampler pass (eps, or x_0 for predict_xstart=True: the
+ * combination is linear).  Engine state like the two window switches; default 1; a w that is not finite is refused.
+ * w == 1 is the step as it was: one forward, no combine pass.  Every other w (0 and negative values included) costs a second forward:
+ * both run at batch B, one after the other, in the same workspace arena; out_u goes to a second engine-owned output buffer, the zero mask is
+ * an engine-owned B*T buffer, one noise draw per step as before (the Philox offsets of a window do not depend on w), and in a window with
+ * observed_frames = 2 the observation is re-noised once per step.
+ * Honoured by vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance (whose `eps` output is then
+ * out_g) and vd_window_begin / vd_window_run: the weight is part of a captured graph's signature, so a later vd_window_begin under
+ * another w captures (or finds) another graph.  NOT honoured by vd_unet_forward, vd_guided_step, vd_score_windows, vd_vb_terms /
+ * vd_prior_bpd (the NLL path scores the conditional model) and the vd_*_from_xstart / vd_posterior_update passes, which run no network.
+ * With w != 1, vd_window_begin fails while the prefix cache or the suffix skip is switched on (in the unconditional forward the
+ * observed frames are padding whose content is whatever the window tensor holds: neither invariant nor meaningless), and a step fails
+ * while an attention capture (vd_set_attn_capture) is armed.
+ * vd_op_cfg_combine: the pass alone, any n > 0, no engine; out may be out_c or out_u; tensors that are not all 16-byte aligned run element
+ * by element. */
+int vd_set_cfg_scale(vd_engine* e, float w);
+float vd_cfg_scale(vd_engine* e);
+int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream);
 
 /* The posterior arithmetic alone, given eps (same formulas; mode 0 p_sample, 1 ddim). */
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per_sample, const float* x, const float* eps,

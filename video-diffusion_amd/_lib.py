@@ -180,6 +180,9 @@ SIGNATURES = {
     "vd_window_prefix_frames": (_I, [_P]),
     "vd_set_window_suffix_skip": (_I, [_P, _I]),
     "vd_window_suffix_frames": (_I, [_P]),
+    "vd_set_cfg_scale": (_I, [_P, _F]),
+    "vd_cfg_scale": (_F, [_P]),
+    "vd_op_cfg_combine": (_I, [_P, _P, _F, _L, _P, _P]),
     "vd_window_begin": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U, _U, _L, _P]),
     "vd_window_run": (_I, [_P, _I, _P]),
     "vd_window_graphs": (_I, [_P]),

@@ -278,15 +278,18 @@ struct vd_engine {
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
     float* d_w2m = nullptr;           // [num_timesteps] dpmpp_2m extrapolation weights of the bound schedule (vd_set_multistep_weights), or null
-    // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded) and the eps scratch
+    // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded), the eps scratch and
+    // a second scratch of its size for the unconditional output of a cfg step (cfg_scale != 1)
     char* ws = nullptr; size_t ws_cap = 0;
     bool ws_suf = false;
     int ws_B = 0, ws_T = 0; size_t ws_tail = 0;      // the window shape ws_tail was computed for (dry run of the topology)
     std::unordered_map<long long, size_t> ws_peaks;  // (B << 32 | T) -> arena peak
     static size_t tm_bytes(int B) { return ((size_t)B * sizeof(float) + 255) & ~(size_t)255; }
-    size_t step_tail_bytes(int B, int T) const { return tm_bytes(B) + (size_t)B * T * (cfg.learn_sigma ? 6 : 3) * cfg.image_size * cfg.image_size * sizeof(float); }
+    size_t out_floats(int B, int T) const { return (size_t)B * T * (cfg.learn_sigma ? 6 : 3) * cfg.image_size * cfg.image_size; }
+    size_t step_tail_bytes(int B, int T) const { return tm_bytes(B) + 2 * out_floats(B, T) * sizeof(float); }
     float* step_tm() const { return reinterpret_cast<float*>(ws + ws_tail); }
     float* step_eps(int B) const { return reinterpret_cast<float*>(ws + ws_tail + tm_bytes(B)); }
+    float* step_eps_u(int B, int T) const { return step_eps(B) + out_floats(B, T); }      // out_u of a cfg step
     Arena step_arena() const { Arena a; a.base = ws; a.cap = ws_tail; return a; }     // the activations end where the tail begins
     // ---- use_gradient_method: second packed image (backward-data weights) + the tape of the guided step's forward
     float* wbuf_bwd = nullptr; bool wbuf_bwd_on_host = false; size_t packed_bwd_total = 0;
@@ -294,6 +297,10 @@ struct vd_engine {
     // return_attn_weights: device buffers for the next forward, one pair per attention block in execution order
     std::vector<float*> attn_cap_t, attn_cap_s;
     int attn_seq = 0;
+    // cfg_scale (vd_set_cfg_scale): 1 = off.  Any other value: every step runs a second forward with the all-zero observation mask below
+    // and cfg_combine_kernel in front of its sampler pass
+    float cfg_w = 1.f;
+    float* d_cfg_zero = nullptr; size_t cfg_zero_cap = 0;   // [B*T] zeros: the observation mask of the unconditional forward
     int mean_type = 0;                               // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
@@ -305,6 +312,7 @@ struct vd_engine {
     // ---- window executor (vd_window_*): device-resident step state + one captured graph per window signature
     struct WinKey {                  // the arguments of vd_window_begin a captured step depends on (zero-filled: compared bytewise)
         int B, T, obs_mode, sampler, clip, flags; float eta;      // flags: 1 prefix cache, 2 suffix skip
+        float cfg_w;                                              // cfg_scale: a graph holds one forward (1) or two and the combine pass with this weight
         float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
@@ -351,6 +359,7 @@ struct vd_engine {
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
         if (d_win_hist) (void)hipFree(d_win_hist);
         if (d_w2m) (void)hipFree(d_w2m);
+        if (d_cfg_zero) (void)hipFree(d_cfg_zero);
         for (auto& g : win_graphs) g.release();
     }
 
@@ -1748,7 +1757,7 @@ int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes) {
     FwdIn fi{}; fi.B = B; fi.T = T;
     int rc = e->forward(fi, nullptr, dry);
     if (rc) return rc;
-    *bytes = (long long)dry.peak;
+    *bytes = (long long)(((dry.peak + 255) & ~(size_t)255) + e->step_tail_bytes(B, T));      // the arena, then the step's tail (both output buffers)
     return 0;
 }
 
@@ -1812,17 +1821,37 @@ static void map_t(const vd_engine* e, const long long* t, int B, float* tm, hipS
                        e->rescale, B, e->num_timesteps, tm, e->d_err);
 }
 
+// cfg_scale != 1: the all-zero observation mask of the unconditional forward, B*T floats.  Never inside a capture: a buffer that grew is
+// zeroed on `st` and waited for, so that steps on any other stream find it zero.  Captured graphs hold its address (grow drops them).
+static int cfg_zero_mask(vd_engine* e, int B, int T, hipStream_t st) {
+    const size_t n = (size_t)B * T;
+    if (n <= e->cfg_zero_cap) return 0;
+    int rc = e->grow(e->d_cfg_zero, e->cfg_zero_cap, n, true);
+    if (rc) return rc;
+    VD_HIP(hipMemsetAsync(e->d_cfg_zero, 0, n * sizeof(float), st));
+    VD_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // One step on `st`: t -> t_model, UNet forward, posterior update (mode 0 p_sample, 1 ddim_sample), the DDIM encoding pass (mode 2) or the
 // DPM-Solver++(2M) pass (mode 3: `hist` = the previous step's x_0 prediction or null, `hist_on` = null or a device word that is 0 while
 // there is no history).  `t` and (when rng != null) the Philox
 // {seed, offset} are read from device memory, so the same launch sequence serves every step of a window (executor).
+// cfg_w != 1 (cfg_scale): behind the forward a second one at the same batch size with the engine's all-zero observation mask (cfg_zero_mask
+// has sized it) into the second output buffer, in the same arena, then cfg_combine_kernel in place over the first output -- which is what
+// every sampler pass below, and the caller's eps_out, then see.  Noise, t and the passes themselves do not change.
 static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
                          const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
                          int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
                          const unsigned long long* rng, float* sample, float* xstart, float* mean, float* eps_out,
                          hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr, const float* hist = nullptr,
-                         const unsigned long long* hist_on = nullptr) {
+                         const unsigned long long* hist_on = nullptr, float cfg_w = 1.f) {
     int rc;
+    if (cfg_w != 1.f) {
+        VD_REQUIRE(!pp && !sp, "cfg_scale != 1 together with the window prefix cache or suffix skip");
+        VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "cfg_scale != 1 together with return_attn_weights: a step makes two forwards");
+        VD_REQUIRE(e->d_cfg_zero && e->cfg_zero_cap >= (size_t)B * T, "cfg_scale: zero observation mask not sized");
+    }
     const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
     float* tm = e->step_tm();
     float* eps = eps_out ? eps_out : e->step_eps(B);
@@ -1830,6 +1859,15 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
     Arena ar = e->step_arena();
     FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
     if ((rc = e->forward(fi, st, ar, pp, sp))) return rc;
+    if (cfg_w != 1.f) {
+        Arena au = e->step_arena();                  // the first forward's activations are dead: its output lives in the tail
+        FwdIn fu = fi;
+        fu.obs = e->d_cfg_zero; fu.eps = e->step_eps_u(B, T);
+        if ((rc = e->forward(fu, st, au))) return rc;
+        const long long n = (long long)e->out_floats(B, T);
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * n, 12.0 * n, st, "cfg_combine");
+        if ((rc = launch_cfg_combine(eps, fu.eps, cfg_w, n, eps, st))) return rc;
+    }
     if (mode == 2) {                                 // ddim_reverse_sample (gaussian_diffusion.py:636-668): its own pass, no noise
         const bool start_x = e->mean_type == 1;      // START_X: pred_xstart = process_xstart(model_output)
         DdimReverseArgs ra{x, start_x ? nullptr : eps, start_x ? eps : nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab,
@@ -1860,8 +1898,9 @@ static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, con
     VD_REQUIRE(mode == 0 || eta >= 0.f, "eta");
     VD_REQUIRE(mode != 3 || e->d_w2m, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     if ((rc = e->ensure_ws(B, T))) return rc;
+    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
     return step_launches(e, mode, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, nullptr,
-                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist);
+                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist, nullptr, e->cfg_w);
 }
 
 int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
@@ -1871,8 +1910,9 @@ int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* 
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && (mean || xstart || eps), "null tensor");
     if ((rc = e->ensure_ws(B, T))) return rc;
+    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
     return step_launches(e, 0, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, nullptr, nullptr,
-                         xstart, mean, eps, static_cast<hipStream_t>(stream));
+                         xstart, mean, eps, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, e->cfg_w);
 }
 
 int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x_t, const float* eps, const float* noise,
@@ -2087,7 +2127,7 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     const bool ms = k.sampler == 3;
     if (!rc) rc = step_launches(e, k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta,
                                 nullptr, 0, 0, e->d_win_rng, k.x, ms ? e->d_win_hist : nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
-                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr);
+                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr, k.cfg_w);
     if (!rc) {
         const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards; it and dpmpp_2m_sample draw nothing
         hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, up ? 1LL : -1LL,
@@ -2133,15 +2173,20 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
                                               "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
     VD_REQUIRE(sampler != 3 || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
+    // in the unconditional forward the observed frames are padding frames whose content is whatever the window tensor holds: neither
+    // "their network input cannot change" (prefix cache) nor "their output is never read" (suffix skip) holds for them
+    VD_REQUIRE(e->cfg_w == 1.f || !e->prefix_cache_on, "cfg_scale != 1 together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+    VD_REQUIRE(e->cfg_w == 1.f || !e->suffix_skip_on, "cfg_scale != 1 together with the window suffix skip (vd_set_window_suffix_skip) is not served");
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = e->ensure_ws(B, T))) return rc;
+    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, st))) return rc;
     if ((rc = window_buffers(e, B, obs_mode, sampler, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
     hipLaunchKernelGGL(win_set_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, t_start, seed, offset);
     VD_HIP(hipGetLastError());
     vd_engine::WinKey key;
     std::memset(&key, 0, sizeof(key));
-    key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.eta = eta;
+    key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.eta = eta; key.cfg_w = e->cfg_w;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
     e->win_cur = -1;
     e->win_lost = false;
@@ -2176,6 +2221,21 @@ int vd_set_window_prefix_cache(vd_engine* e, int on) {
     VD_REQUIRE(e, "null engine");
     e->prefix_cache_on = on != 0;
     return 0;
+}
+
+// cfg_scale, engine state like the two window switches: 1 = off.  A captured window graph carries the weight in its key (WinKey::cfg_w), so
+// nothing is dropped here: the next vd_window_begin finds or captures the graph of the value then set.
+int vd_set_cfg_scale(vd_engine* e, float w) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(w == w && std::fabs(w) <= 3.4028234e38f, "cfg_scale must be finite");
+    e->cfg_w = w;
+    return 0;
+}
+
+float vd_cfg_scale(vd_engine* e) { return e ? e->cfg_w : 1.f; }
+
+int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream) {
+    return launch_cfg_combine(out_c, out_u, w, n, out, static_cast<hipStream_t>(stream));
 }
 
 int vd_window_prefix_frames(vd_engine* e) {

@@ -548,9 +548,18 @@ int launch_posterior(const PosteriorArgs& a, hipStream_t s) {
 // alphas_cumprod_next[t] = append(alphas_cumprod[1:], 0.0)[t] is the TAB_ACP row at t + 1 (0 behind the last step): the float32 cast
 // is elementwise, so these are _extract_into_tensor's bits.  No noise, no Philox draws.  Four elements per thread and pass
 // (16-byte accesses; per % 4 == 0 keeps a group inside one batch item); sample may alias x: the update is elementwise.
+// The x_0 prediction of an epsilon-model as posterior_kernel forms it: two products, each rounded, then one subtraction -- NOT a fused
+// multiply-add.  The step through `denoised_fn` takes its x_0 from posterior_kernel (vd_p_mean_variance) and hands it to the *_from_xstart
+// form of the passes below: with the same rounding here, the fused step and that form agree to the bit for denoised_fn = identity.
+__device__ __forceinline__ float xstart_from_eps(float sr, float x, float srm1, float eps) {
+#pragma clang fp contract(off)
+    const float a = sr * x, b = srm1 * eps;
+    return a - b;
+}
+
 __device__ __forceinline__ float ddim_reverse_one(float x, float src, bool given, float sr, float srm1, float r, float s, int clip,
                                                   float& x0_out, bool& nonfinite) {
-    float x0 = given ? src : sr * x - srm1 * src;
+    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
     const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
     nonfinite |= bad;
     if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
@@ -612,7 +621,7 @@ int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s) {
 // written, by the same thread.  Four elements per thread and pass as ddim_reverse_kernel; sample may alias x.
 __device__ __forceinline__ float dpmpp_2m_one(float x, float src, bool given, float prev, bool have, float w, float sr, float srm1,
                                               float r, float s, int clip, float& x0_out, bool& nonfinite) {
-    float x0 = given ? src : sr * x - srm1 * src;
+    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
     const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
     nonfinite |= bad;
     if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
@@ -668,6 +677,48 @@ int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s) {
     const size_t total4 = (size_t)a.B * (a.per / 4);
     const int grid = (int)std::min<size_t>((total4 + 255) / 256, 4096);
     hipLaunchKernelGGL(dpmpp_2m_kernel, dim3(grid), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ classifier-free guidance on the observed frames (one pass)
+// cfg_scale (this project's extension): out_c is the network output of the step, out_u the output of the same call with the observation
+// mask zeroed; d = out_c - out_u (one fp32 subtraction), out_g = fmaf(w, d, out_u) (one fused multiply-add).  A d that is not finite
+// comes out NaN whatever w is (w = 0 would otherwise hide an inf of out_c), so that the sampler pass behind it sets VD_ERR_NONFINITE.
+// w = 0 hands out_u through as it is: the fma would turn a -0 of out_u into +0 whenever w d is +0.  Pure streaming: two reads and one
+// write per element, four elements per thread and pass while the three tensors are 16-byte aligned, the n % 4 last ones (or, unaligned,
+// all of them) one by one; out may alias out_c or out_u: the pass is elementwise.
+__device__ __forceinline__ float cfg_combine_one(float c, float u, float w) {
+    const float d = c - u;
+    if (!(fabsf(d) <= 3.4028234e38f)) return __builtin_nanf("");
+    return w == 0.0f ? u : fmaf(w, d, u);
+}
+
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* out_c, const float* out_u, float w, size_t n4, size_t n, float* out) {
+    const float4* c4 = reinterpret_cast<const float4*>(out_c);
+    const float4* u4 = reinterpret_cast<const float4*>(out_u);
+    float4* o4 = reinterpret_cast<float4*>(out);
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    for (size_t i = tid; i < n4; i += stride) {
+        const float4 c = c4[i], u = u4[i];
+        float4 o;
+        o.x = cfg_combine_one(c.x, u.x, w);
+        o.y = cfg_combine_one(c.y, u.y, w);
+        o.z = cfg_combine_one(c.z, u.z, w);
+        o.w = cfg_combine_one(c.w, u.w, w);
+        o4[i] = o;
+    }
+    for (size_t j = 4 * n4 + tid; j < n; j += stride) out[j] = cfg_combine_one(out_c[j], out_u[j], w);
+}
+
+int launch_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, hipStream_t s) {
+    VD_REQUIRE(out_c && out_u && out && n > 0, "cfg_combine_kernel: null tensor or no element");
+    VD_REQUIRE(w == w && fabsf(w) <= 3.4028234e38f, "cfg_scale must be finite");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const size_t n4 = al16(out_c) && al16(out_u) && al16(out) ? (size_t)n / 4 : 0;
+    const size_t work = std::max<size_t>(n4, (size_t)n - 4 * n4);
+    const int grid = (int)std::min<size_t>((work + 255) / 256, 4096);
+    hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid), dim3(256), 0, s, out_c, out_u, w, n4, (size_t)n, out);
     VD_HIP(hipGetLastError());
     return 0;
 }

@@ -447,6 +447,10 @@ struct Dpmpp2mArgs {
     int* err;               // as PosteriorArgs::err
 };
 int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s);
+// cfg_scale (this project's extension: classifier-free guidance on the observed frames): out[i] = fmaf(w, out_c[i] - out_u[i], out_u[i]),
+// NaN where the difference is not finite, out_u[i] itself at w = 0.  Any n > 0; out may alias out_c or out_u; 16-byte aligned tensors take
+// the float4 path, others run element by element.  w must be finite.
+int launch_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, hipStream_t s);
 int launch_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab, int num_timesteps, int B,
                     long per, float* out, hipStream_t s);
 int launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t s);

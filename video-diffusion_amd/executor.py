@@ -18,6 +18,8 @@ while scripts/video_sample.py:149-166 calls `p_sample` directly with `x_t_minus_
 is at every step -- `renoise=False`, what `infer_video` passes, so that its graph and eager executors sample the same
 conditional distribution.
 """
+import math
+
 import torch as th
 
 from . import _lib
@@ -58,7 +60,8 @@ class WindowExecutor:
                                    kinda_marg_mask=f(B * T), frame_indices=th.zeros(B, T, dtype=th.int64, device=dev))
         return self._bufs[key]
 
-    def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True):
+    def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
+              cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -66,7 +69,18 @@ class WindowExecutor:
         t_start, default 0, UP to the last index, draws no noise -- seed and eta are not read -- and takes 'x_t_minus_1' with
         renoise=False only) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: walks down like 'ddim', the previous step's
         x_0 prediction lives in an engine-owned buffer, the window's first step is first-order whatever t_start is, no noise --
-        seed and eta are not read -- and 'x_t_minus_1' with renoise=False only)."""
+        seed and eta are not read -- and 'x_t_minus_1' with renoise=False only).
+        cfg_scale (this project's extension; gaussian_diffusion.py: p_sample): the captured step holds both forwards, the combine pass
+        and the sampler pass; the weight is part of the graph's signature, so windows under different weights replay different graphs.
+        The noise of a window does not depend on it.  Not served together with prefix_cache or suffix_skip: in the unconditional
+        forward the observed frames are padding frames whose content is whatever the window tensor holds."""
+        cfg_scale = float(cfg_scale)
+        if not math.isfinite(cfg_scale):
+            raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
+        if cfg_scale != 1.0 and self.prefix_cache:
+            raise NotImplementedError("prefix_cache together with cfg_scale != 1")
+        if cfg_scale != 1.0 and self.suffix_skip:
+            raise NotImplementedError("suffix_skip together with cfg_scale != 1")
         mode = model_kwargs.get("observed_frames", "x_0")
         if mode not in _OBS_MODES:
             raise NotImplementedError(f"observed_frames={mode!r}: the window executor handles 'x_0', 'x_t' and 'x_t_minus_1'")
@@ -102,11 +116,19 @@ class WindowExecutor:
             obs_src = bufs["x"] if mode == "x_t" else bufs["obs_src"]
             _lib.check(_lib.lib().vd_set_window_prefix_cache(self.model._handle, 1 if self.prefix_cache else 0))
             _lib.check(_lib.lib().vd_set_window_suffix_skip(self.model._handle, 1 if self.suffix_skip else 0))
-            _lib.check(_lib.lib().vd_window_begin(
-                self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
-                _lib.ptr(bufs["latent_mask"]), _lib.ptr(bufs["kinda_marg_mask"]), _lib.ptr(bufs["frame_indices"]),
-                3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
-                int(t_start), self.stream.cuda_stream))
+            # the scale is engine state for the length of this call only: the captured graph keeps the weight, run() needs none
+            if cfg_scale != 1.0:
+                _lib.check(_lib.lib().vd_set_cfg_scale(self.model._handle, cfg_scale))
+            try:
+                rc = _lib.lib().vd_window_begin(
+                    self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
+                    _lib.ptr(bufs["latent_mask"]), _lib.ptr(bufs["kinda_marg_mask"]), _lib.ptr(bufs["frame_indices"]),
+                    3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
+                    int(t_start), self.stream.cuda_stream)
+            finally:
+                if cfg_scale != 1.0:
+                    _lib.check(_lib.lib().vd_set_cfg_scale(self.model._handle, 1.0))
+            _lib.check(rc)
         self.x = bufs["x"]
         self.seed = seed
         self._left = self.diffusion.num_timesteps - int(t_start) if sid == 2 else int(t_start) + 1
@@ -127,9 +149,9 @@ class WindowExecutor:
         th.cuda.current_stream(self.model.device).wait_stream(self.stream)
         return self.x
 
-    def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True):
+    def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, cfg_scale=1.0):
         """All num_timesteps steps of one window; returns a fresh tensor."""
-        self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise)
+        self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale)
         return self.run(self.diffusion.num_timesteps).clone()
 
     @property

@@ -14,8 +14,12 @@ a backward-data pass of the whole UNet w.r.t. its input (csrc/backward.hip); `de
 are served as well.  `ddim_reverse_sample` (gaussian_diffusion.py:636-668), the DDIM step towards the noise, is one forward plus its
 own fused pass (csrc/misc.hip: ddim_reverse_kernel); its two loops are this project's extension.  `dpmpp_2m_sample` with its two
 loops is an extension as a whole: DPM-Solver++(2M), the second-order multistep sampler the reference does not have -- one forward plus
-one fused pass (dpmpp_2m_kernel) that reuses the previous step's x_0 prediction.  Training losses are out of scope.
+one fused pass (dpmpp_2m_kernel) that reuses the previous step's x_0 prediction.  `cfg_scale` on the step and loop entry points is
+an extension too: classifier-free guidance on the observed frames, out_u + w (out_c - out_u) with out_u the network output of the same
+call under an all-zero obs_mask -- a second forward and one fused pass (cfg_combine_kernel) in front of the unchanged sampler pass
+(include/vd_amd.h: vd_set_cfg_scale).  Training losses are out of scope.
 """
+import contextlib
 import enum
 import math
 
@@ -71,6 +75,35 @@ _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 def _f32(t, device):
     return t.to(device=device, dtype=th.float32).contiguous()
+
+
+def _check_cfg(cfg_scale, return_attn_weights=False, use_gradient_method=False):
+    """The refusals of cfg_scale != 1 that need no engine; returns the scale as a float."""
+    w = float(cfg_scale)
+    if not math.isfinite(w):
+        raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
+    if w != 1.0 and return_attn_weights:
+        raise NotImplementedError("return_attn_weights together with cfg_scale != 1 (a step makes two forwards)")
+    if w != 1.0 and use_gradient_method:
+        raise NotImplementedError("use_gradient_method together with cfg_scale != 1")
+    return w
+
+
+@contextlib.contextmanager
+def _cfg_scope(model, cfg_scale):
+    """The engine's cfg_scale for the calls inside; behind them, whatever they raise, the scale found before -- 1.0 unless the caller
+    stands inside GaussianDiffusion.cfg_scale_scope (as _attn_capture / _attn_release).  cfg_scale == 1 touches nothing: the keyword's
+    default leaves the engine as it is, which outside such a scope is the step as it always was."""
+    if cfg_scale == 1.0:
+        yield
+        return
+    L = _lib.lib()
+    before = float(L.vd_cfg_scale(model._handle))
+    _lib.check(L.vd_set_cfg_scale(model._handle, float(cfg_scale)))
+    try:
+        yield
+    finally:
+        _lib.check(L.vd_set_cfg_scale(model._handle, before))
 
 
 class GaussianDiffusion:
@@ -157,6 +190,15 @@ class GaussianDiffusion:
             model._bound_schedule = self
         return model
 
+    def cfg_scale_scope(self, model, cfg_scale):
+        """This project's extension: `with diffusion.cfg_scale_scope(model, w):` -- every step entry point called inside runs with
+        classifier-free guidance weight w on the observed frames (p_sample's docstring), the keyword-less ones included:
+        ddim_reverse_sample with its two loops and dpmpp_2m_sample keep the parameter lists they were introduced with and take
+        their scale from here.  The scale found before is back when the block ends, whatever it raised.  Not honoured by
+        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_cfg_scale)."""
+        cfg_scale = _check_cfg(cfg_scale)
+        return _cfg_scope(self._bind(model), cfg_scale)
+
     def _scale_timesteps(self, t):
         if self.rescale_timesteps:
             return t.float() * (1000.0 / self.num_timesteps)
@@ -176,10 +218,11 @@ class GaussianDiffusion:
         return model, xs, t.to(device=model.device, dtype=th.int64).contiguous(), model._pack_kwargs(xs, model_kwargs)
 
     def _step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
-              return_attn_weights=False, use_gradient_method=False):
+              return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
+        cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
@@ -189,7 +232,8 @@ class GaussianDiffusion:
             out = self._guided(model, x, t, clip_denoised, model_kwargs, noise2=noise, want_sample=True)
             return out["sample"], out["pred_xstart"]
         if denoised_fn is not None:
-            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise)
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise,
+                                 cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
             return out["sample"], out["pred_xstart"]
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
@@ -205,12 +249,13 @@ class GaussianDiffusion:
         common = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0)
         self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
-            if mode == 0:
-                rc = L.vd_p_sample(*common, _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                   _lib.current_stream())
-            else:
-                rc = L.vd_ddim_sample(*common, float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                      _lib.current_stream())
+            with _cfg_scope(model, cfg_scale):
+                if mode == 0:
+                    rc = L.vd_p_sample(*common, _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
+                                       _lib.current_stream())
+                else:
+                    rc = L.vd_ddim_sample(*common, float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
+                                          _lib.current_stream())
         finally:
             if return_attn_weights:
                 model._attn_release()
@@ -241,14 +286,16 @@ class GaussianDiffusion:
         return {"mean": mean, "pred_xstart": xstart, "grad": grad, "sample": sample}
 
     def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None,
-                  prev_xstart=None):
+                  prev_xstart=None, cfg_scale=1.0):
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
         the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
         (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
         in vd_ddim_reverse_from_xstart and draws no noise; mode 3 (dpmpp_2m_sample, with its `prev_xstart` or None) ends in
-        vd_dpmpp_2m_from_xstart and draws none either."""
-        out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights)
+        vd_dpmpp_2m_from_xstart and draws none either.  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
+        the guided one, the passes behind it run no network."""
+        out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
+                                   cfg_scale=cfg_scale)
         base = self._bind(model)
         dev = base.device
         xs = _f32(x, dev)
@@ -291,10 +338,12 @@ class GaussianDiffusion:
         return res.expand(shape)
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None,
-                        return_attn_weights=False, use_gradient_method=False):
+                        return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
         """gaussian_diffusion.py:229-372 -> {'mean', 'variance', 'log_variance', 'pred_xstart', 'attn'} (+ 'eps', the raw
-        model output, which the NLL loop reuses)."""
+        model output, which the NLL loop reuses).  cfg_scale != 1 (this project's extension): mean and pred_xstart come from the
+        guided network output out_u + w (out_c - out_u), and 'eps' is that output."""
         self._refuse_learned(x)
+        cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
@@ -305,15 +354,16 @@ class GaussianDiffusion:
             return {"mean": g["mean"], **self._variance(tt, g["mean"].shape), "pred_xstart": g["pred_xstart"], "attn": None,
                     "grad": g["grad"]}
         if denoised_fn is not None:
-            return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights)
+            return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, cfg_scale=cfg_scale)
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs or {})
         B, T = xs.shape[:2]
         mean, xstart, eps = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
         attn = model._attn_capture(B, T) if return_attn_weights else None
         try:
-            rc = _lib.lib().vd_p_mean_variance(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
-                                               1 if clip_denoised else 0, _lib.ptr(mean), _lib.ptr(xstart), _lib.ptr(eps),
-                                               _lib.current_stream())
+            with _cfg_scope(model, cfg_scale):
+                rc = _lib.lib().vd_p_mean_variance(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
+                                                   1 if clip_denoised else 0, _lib.ptr(mean), _lib.ptr(xstart), _lib.ptr(eps),
+                                                   _lib.current_stream())
         finally:
             if attn is not None:
                 model._attn_release()
@@ -430,15 +480,18 @@ class GaussianDiffusion:
                                              latent_mask=latent_mask)
 
     def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None,
-                 return_attn_weights=False, use_gradient_method=False):
-        """gaussian_diffusion.py:403-448.  `x` is not modified; returns fresh tensors."""
+                 return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
+        """gaussian_diffusion.py:403-448.  `x` is not modified; returns fresh tensors.  cfg_scale (this project's extension, on every
+        step and loop entry point): the weight w of classifier-free guidance on the observed frames -- the step runs on
+        out_u + w (out_c - out_u), out_u being the network output under an all-zero obs_mask; 1.0 is the step as it always was, any
+        other value costs a second forward."""
         sample, xstart = self._step(0, model, x, t, clip_denoised, denoised_fn, model_kwargs, 0.0, None,
-                                    return_attn_weights, use_gradient_method)
+                                    return_attn_weights, use_gradient_method, cfg_scale)
         return {"sample": sample, "pred_xstart": xstart, "attn": self._last_attn if return_attn_weights else None}
 
-    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+    def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:597-634."""
-        sample, xstart = self._step(1, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, None)
+        sample, xstart = self._step(1, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, None, cfg_scale=cfg_scale)
         return {"sample": sample, "pred_xstart": xstart}
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
@@ -510,7 +563,7 @@ class GaussianDiffusion:
     # -- loops -------------------------------------------------------------------------------------
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                       latent_mask=None, device=None, progress=False, return_attn_weights=False,
-                      use_gradient_method=False):
+                      use_gradient_method=False, cfg_scale=1.0):
         """gaussian_diffusion.py:450-526: returns (sample, attns).  With return_attn_weights, attns holds one running mean
         per (quartile of the schedule, attention type): 'attn/q<k>-temporal' / 'attn/q<k>-spatial' (:496-524) -- each
         block's head-averaged weights averaged over the non-attended axis, spatial maps resized (nearest) to the first
@@ -519,7 +572,7 @@ class GaussianDiffusion:
         steps = self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                                model_kwargs=model_kwargs, latent_mask=latent_mask, device=device,
                                                progress=progress, return_attn_weights=return_attn_weights,
-                                               use_gradient_method=use_gradient_method)
+                                               use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)
         for k, out in enumerate(steps):
             final = out
             if not return_attn_weights:
@@ -543,9 +596,10 @@ class GaussianDiffusion:
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                   model_kwargs=None, latent_mask=None, device=None, progress=False,
-                                  return_attn_weights=False, use_gradient_method=False):
+                                  return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
         """gaussian_diffusion.py:528-595, including the per-step side draws that consume the global RNG
         (x_t_minus_1, random_t, x_random) so a seeded run walks the generator like the reference."""
+        cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)     # before the first side draw touches the engine
         base = getattr(model, "model", model)
         if device is None:
             device = base.device
@@ -564,24 +618,25 @@ class GaussianDiffusion:
                 th.randn_like(_f32(model_kwargs["x0"], device))   # x_random's draw: consumed, never read in eval (unet.py:962)
             out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                 model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
-                                use_gradient_method=use_gradient_method)
+                                use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)
             yield out
             img = out["sample"]
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
-                         latent_mask=None, device=None, progress=False, eta=0.0):
+                         latent_mask=None, device=None, progress=False, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:670-700: returns the sample only."""
         final = None
         for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                         denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                                                        device=device, progress=progress, eta=eta):
+                                                        device=device, progress=progress, eta=eta, cfg_scale=cfg_scale):
             final = sample
         getattr(model, "check_device_errors", lambda: None)()
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
-                                     model_kwargs=None, latent_mask=None, device=None, progress=False, eta=0.0):
+                                     model_kwargs=None, latent_mask=None, device=None, progress=False, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:702-748."""
+        cfg_scale = _check_cfg(cfg_scale)
         base = getattr(model, "model", model)
         if device is None:
             device = base.device
@@ -590,7 +645,7 @@ class GaussianDiffusion:
         for i in list(range(self.num_timesteps))[::-1]:
             t = th.tensor([i] * shape[0], device=device)
             out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                   model_kwargs=model_kwargs, eta=eta)
+                                   model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
             yield out
             img = out["sample"]
 
@@ -626,21 +681,22 @@ class GaussianDiffusion:
             img = out["sample"]
 
     def dpmpp_2m_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
-                             latent_mask=None, device=None, progress=False):
+                             latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension, shaped like ddim_sample_loop: dpmpp_2m_sample from the last index down to 0, each step handed
         the x_0 prediction of the one before; returns the sample only."""
         final = None
         for sample in self.dpmpp_2m_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                             denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                                                            device=device, progress=progress):
+                                                            device=device, progress=progress, cfg_scale=cfg_scale):
             final = sample
         getattr(model, "check_device_errors", lambda: None)()
         return final["sample"]
 
     def dpmpp_2m_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
-                                         model_kwargs=None, latent_mask=None, device=None, progress=False):
+                                         model_kwargs=None, latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension: the steps of dpmpp_2m_sample_loop, one dict per index, driven from the host like
         ddim_sample_loop_progressive.  The first step has no history and is first-order."""
+        cfg_scale = _check_cfg(cfg_scale)
         base = getattr(model, "model", model)
         if device is None:
             device = base.device
@@ -649,7 +705,8 @@ class GaussianDiffusion:
         prev = None
         for i in list(range(self.num_timesteps))[::-1]:
             t = th.tensor([i] * shape[0], device=device)
-            out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                       model_kwargs=model_kwargs)
+            with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                           model_kwargs=model_kwargs)
             yield out
             img, prev = out["sample"], out["pred_xstart"]

@@ -16,6 +16,7 @@ samples of each (`--num_samples`, `--sample_idx`), what is already on disk and t
 step runs -- follows scripts/video_sample.py:192-239,570-640; `run()` is that body.
 """
 import argparse
+import contextlib
 import logging
 import os
 
@@ -43,7 +44,7 @@ def get_masks(x0, num_obs):
 @torch.no_grad()
 def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size=1, optimal_schedule_path=None, *,
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
-                adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False):
+                adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -66,7 +67,12 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
 
     sampler: 'p_sample' (default), 'ddim' (ddim_sample with `eta`) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: the
     second-order multistep solver; each window starts without history, so its first step is first-order; on both executors; meant for
-    timestep_respacing='logsnrN')."""
+    timestep_respacing='logsnrN').
+
+    cfg_scale (this project's extension, both executors, every sampler): the weight w of classifier-free guidance on each window's
+    observed frames -- every step runs on out_u + w (out_c - out_u), out_u being the network output with the window's obs_mask
+    zeroed (gaussian_diffusion.py: p_sample).  1.0 (default) is the sampling as it always was; any other value costs two forwards
+    per step and is refused together with use_gradient_method, prefix_cache (graph) and suffix_skip (graph)."""
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -129,7 +135,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             t_tensors = [torch.tensor([ts] * B, device=device) for ts in range(diffusion.num_timesteps)]
         if use_graph:
             # renoise=False: like the eager loop below (and scripts/video_sample.py:149-166), every step reads x_t_minus_1 = x0 as it is
-            write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False))
+            write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale))
             model.check_device_errors()
             continue
         local_samples = x0.clone()
@@ -137,16 +143,18 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         prev_xstart = None                                  # dpmpp_2m: the history is the window's own
         for timestep in timesteps:
             if sampler == "dpmpp_2m":
-                out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
-                                                model_kwargs=model_kwargs)
+                # (the step keeps the parameter list it was introduced with: its scale comes from the scope)
+                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                    out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
+                                                    model_kwargs=model_kwargs)
                 local_samples, prev_xstart = out["sample"], out["pred_xstart"]
             elif sampler == "p_sample":
                 local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
                                                    model_kwargs=model_kwargs, return_attn_weights=False,
-                                                   use_gradient_method=use_gradient_method)["sample"]
+                                                   use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)["sample"]
             else:
                 local_samples = diffusion.ddim_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
-                                                      model_kwargs=model_kwargs, eta=eta)["sample"]
+                                                      model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)["sample"]
             if trace is not None:
                 trace.append(local_samples.clone())
         write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
@@ -369,6 +377,10 @@ def build_parser():
                     help="the step: p_sample (default), ddim (ddim_sample with --eta) or dpmpp_2m (the second-order multistep solver, meant for "
                          "--timestep_respacing logsnrN); a non-default sampler is named in the run directory")
     ap.add_argument("--eta", type=float, default=0.0, help="with --sampler ddim: ddim_sample's eta")
+    ap.add_argument("--cfg_scale", type=float, default=1.0,
+                    help="classifier-free guidance weight on the observed frames: every step runs on out_u + w (out_c - out_u), out_u being the "
+                         "network output with nothing observed; 1.0 (default) is plain sampling, any other value costs two forwards per step and "
+                         "is named in the run directory")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -393,7 +405,15 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        executor=getattr(args, "executor", "eager"),
                        adaptive_distance=getattr(args, "adaptive_distance", "l2"),
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
-                       save_all_timesteps=getattr(args, "save_all_timesteps", False))
+                       save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0))
+
+
+def run_postfix(args):
+    """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
+    ('_cfg2', '_cfg1.5', '_cfg-0.5') -- samples of different samplers or guidance weights never share a directory."""
+    sampler = getattr(args, "sampler", "p_sample")
+    w = float(getattr(args, "cfg_scale", 1.0))
+    return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}")
 
 
 def run(args, create=None, device=None, infer=None):
@@ -419,9 +439,8 @@ def run(args, create=None, device=None, infer=None):
     infer = infer or _default_infer
     # the run identifier is formed from the options AS GIVEN, before --max_frames / --T take their defaults from the model and
     # the dataset (video_sample.py:530-533 precedes :568-570,612-615: an unset one reads 'None' in the directory name)
-    # (a sampler other than the default is part of the name: samples of different samplers never share a directory)
-    sampler = getattr(args, "sampler", "p_sample")
-    run_id = test_util.get_eval_run_identifier(args, postfix="" if sampler == "p_sample" else f"_{sampler}")
+    # (a sampler other than the default and a cfg_scale other than 1 are part of the name: run_postfix)
+    run_id = test_util.get_eval_run_identifier(args, postfix=run_postfix(args))
     model, diffusion = load_model(args, device, rank, world, create=create)
     if args.max_frames is None:                                            # video_sample.py:568-570
         args.max_frames = model.config.get("max_frames") or model.config["T"]
