@@ -107,7 +107,13 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * gaussian_diffusion.py:1019-1031).  The step entry points stay asynchronous: such a batch element is written as NaN
  * and a sticky device flag is set; this call waits for the whole DEVICE (steps issued on any stream, non-blocking side streams included, have finished),
  * copies the flags to the host, clears them, and the host
- * mirror raises IndexError.  bit 0: timestep index out of range.
+ * mirror raises IndexError.  bit 0: timestep index out of range.  Raised by every entry that runs the network (the timestep map
+ * in front of the forward: vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_guided_step,
+ * the window executor's captured step), by vd_score_windows / vd_op_eps_mse and by vd_vb_terms.  The network-free passes
+ * vd_posterior_update, vd_posterior_from_xstart, vd_ddim_reverse_from_xstart, vd_dpmpp_2m_from_xstart and vd_q_sample (index -1 wraps
+ * to the last row there; below -num_timesteps or above the last row is out of range) poison item b with NaN and do NOT raise
+ * the bit: the range of t is their caller's to check (the host mirror reaches the *_from_xstart forms only behind
+ * vd_p_mean_variance, which has raised it).  vd_prior_bpd reads no t.
  * bit 1: the network output a step consumed was not finite.  The reference would carry the NaN into its sample; here the clamp
  * of clip_denoised would turn it into a plausible -1, so the posterior kernels keep such an element NaN and set this bit
  * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,

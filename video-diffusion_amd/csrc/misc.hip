@@ -500,7 +500,8 @@ __global__ __launch_bounds__(256) void posterior_kernel(PosteriorArgs a) {
         const long long tl = a.t[b];
         const int NT = a.num_timesteps;
         if (tl < 0 || tl >= NT) {                // the reference raises IndexError (_extract_into_tensor); no table read here:
-            if (a.sample) a.sample[i] = __builtin_nanf("");   // the element is poisoned and map_t_kernel has set the error flag
+            if (a.sample) a.sample[i] = __builtin_nanf("");   // the element is poisoned; bit 0 is map_t_kernel's, in the entries that run the
+                                                              // network before this pass -- vd_posterior_update / vd_posterior_from_xstart poison only
             if (a.xstart) a.xstart[i] = __builtin_nanf("");
             if (a.mean) a.mean[i] = __builtin_nanf("");
             continue;
@@ -513,7 +514,8 @@ __global__ __launch_bounds__(256) void posterior_kernel(PosteriorArgs a) {
         // network -- must not leave through the clamp below as a plausible -1 (fmaxf(NaN, -1) = -1): it stays NaN and sets bit 1.
         const bool bad = !(fabsf(x0) <= 3.4028234e38f);
         nonfinite |= bad;
-        if (a.clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (bad) x0 = __builtin_nanf("");        // an infinite x0 too: eps = +inf would leave pred_xstart and p_sample's sample at -inf, not at the NaN bit 1's readers are told of
+        else if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
         if (a.xstart) a.xstart[i] = x0;
         if (a.mean) a.mean[i] = tb[TAB_COEF1 * NT] * x0 + tb[TAB_COEF2 * NT] * x;
         if (!a.sample) continue;                 // p_mean_variance only
@@ -817,6 +819,7 @@ __global__ __launch_bounds__(256) void vb_terms_kernel(VbArgs a) {
             s2 += (double)(e2 * e2 * m);
         }
     }
+    if (!ok && a.err && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.err, VD_ERR_TIMESTEP);   // (eps_mse_kernel: one thread per item; no map_t_kernel on this path)
     __shared__ double red[3][256];
     red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
     __syncthreads();
@@ -829,8 +832,7 @@ __global__ __launch_bounds__(256) void vb_terms_kernel(VbArgs a) {
 }
 
 __global__ void vb_final_kernel(const double* part, int nblk, double per, float* vb, float* xstart_mse, float* mse, float scale0) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= (int)gridDim.x * (int)blockDim.x) return;
+    const int b = blockIdx.x;                                               // launched with one thread per item
     double s[3] = {0, 0, 0};
     for (int k = 0; k < nblk; ++k)
         for (int q = 0; q < 3; ++q) s[q] += part[((size_t)b * nblk + k) * 3 + q];
