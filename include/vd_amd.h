@@ -132,8 +132,8 @@ int vd_max_window_frames(void);
 
 /* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
  * grow with B*T^2 (about 60 KB per (b, t, s) pair for the default 64x64 model: ~1 GB at B = 1, T = 128).  The figure is the
- * activation arena of one forward plus the step's tail: t_model and the two network-output buffers (the second one is out_u of a
- * cfg_scale != 1 step, below). */
+ * activation arena of one forward plus the step's tail: t_model, the two network-output buffers (the second one is out_u of a
+ * cfg_scale != 1 step and the finished x_0 of a dynamic-threshold step, below) and the scratch of the two guidance options. */
 int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes);
 
 /* observed_frames: 0 'x_0', 1 'x_t', 2 'x_t_minus_1' (unet.py:958-974,991-1013). */
@@ -343,6 +343,46 @@ int vd_window_suffix_frames(vd_engine* e);
 int vd_set_cfg_scale(vd_engine* e, float w);
 float vd_cfg_scale(vd_engine* e);
 int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream);
+
+/* Guidance rescale and dynamic thresholding -- this project's extensions; the two standard remedies for the over-saturation of
+ * cfg_scale > 1 under the static clamp of x_0 to [-1, 1].  "Item" is one batch element, and each statistic below runs over the elements of
+ * the item's LATENT frames only (latent_mask == 1); observed and padding frames keep the bits of the step without the option.
+ *
+ * guidance_rescale phi in [0, 1] (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", 3.4); 0 = off (default);
+ * acts only with cfg_scale != 1.  With out_g the bits of the combine pass above:
+ *   sigma_c, sigma_g = standard deviations about the mean of out_c and out_g over the item's latent elements (fp64 sums, block partials
+ *                      folded in a fixed order, no floating-point atomics: run-to-run deterministic)
+ *   f = 1 + phi (sigma_c / sigma_g - 1)   in fp64, rounded once to fp32;  f = 1 where sigma_g = 0 or the item has no latent frame
+ *   latent frames: out_g * f (one fp32 product);  other frames: out_g
+ * It acts on the network output, whichever of eps and x_0 the model predicts.  Two passes in place of the combine pass.
+ *
+ * dynamic_threshold p in (0, 1] (Saharia et al. 2022, Imagen, 2.3); 0 = off (default); acts only with clip_denoised, whose clamp it
+ * replaces; independent of cfg_scale.  x_0 is the prediction as the step forms it (the network output of a START_X model):
+ *   n = the item's latent elements, a = sorted |x_0|, h = (n - 1) (double)p, k = floor(h)
+ *   s = a[k] + (h - k) (a[min(k + 1, n - 1)] - a[k])   in fp64, rounded once to fp32 (torch.quantile's linear interpolation);  s <- max(s, 1)
+ *   latent frames: clamp(x_0, -s, s) / s;  other frames: clamp(x_0, -1, 1) as before
+ * a[k] and a[k + 1] are exact: a radix select over the bit patterns of |x_0| (four histogram passes, integer atomics, counters zeroed in the
+ * stream by a kernel).  A latent x_0 that is not finite turns the item's latent x_0 into NaN and sets VD_ERR_NONFINITE.  Where max |x_0| <= 1 on
+ * an item's latent frames, s = 1 and the step is the clamped step to the bit.  The finished x_0 goes to an engine-owned buffer and the
+ * sampler pass runs in the form the vd_*_from_xstart entries expose, with its clamp off.
+ *
+ * Both are engine state like cfg_scale, part of a window graph's signature, and use the step's tail of the workspace
+ * (vd_workspace_bytes counts it): no allocation, no host round trip.  Honoured by the entries that honour cfg_scale (vd_p_sample,
+ * vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_window_begin / vd_window_run) and NOT honoured by
+ * vd_unet_forward, vd_guided_step (use_gradient_method), vd_score_windows, vd_vb_terms / vd_prior_bpd (the NLL path) and the
+ * vd_*_from_xstart / vd_posterior_update passes.  vd_window_begin fails while an option that would act is set together with the prefix
+ * cache or the suffix skip.  A caller's denoised_fn together with dynamic_threshold is refused on the Python side.
+ * vd_op_cfg_rescale / vd_op_dynamic_threshold: the passes alone on [B][T][frame_elems] tensors with the [B*T] latent mask `lat`, no engine;
+ * they allocate their scratch, wait for `stream` and free it.  out may alias an input; frame_elems % 4 != 0 or tensors that are not 16-byte
+ * aligned run element by element.  factor_out[B] = f;  s_out[B] = max(s, 1), NaN for a poisoned item, 1 for an item without latent frame. */
+int vd_set_guidance_rescale(vd_engine* e, float phi);
+float vd_guidance_rescale(vd_engine* e);
+int vd_set_dynamic_threshold(vd_engine* e, float p);
+float vd_dynamic_threshold(vd_engine* e);
+int vd_op_cfg_rescale(const float* out_c, const float* out_u, float w, const float* lat, int B, int T, long long frame_elems, float phi,
+                      float* out, float* factor_out, void* stream);
+int vd_op_dynamic_threshold(const float* x0, const float* lat, int B, int T, long long frame_elems, float p, float* out, float* s_out,
+                            void* stream);
 
 /* The posterior arithmetic alone, given eps (same formulas; mode 0 p_sample, 1 ddim). */
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per_sample, const float* x, const float* eps,

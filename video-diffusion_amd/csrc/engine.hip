@@ -278,18 +278,21 @@ struct vd_engine {
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
     float* d_w2m = nullptr;           // [num_timesteps] dpmpp_2m extrapolation weights of the bound schedule (vd_set_multistep_weights), or null
-    // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded), the eps scratch and
-    // a second scratch of its size for the unconditional output of a cfg step (cfg_scale != 1)
+    // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded), the eps scratch,
+    // a second scratch of its size for the unconditional output of a cfg step (cfg_scale != 1) -- dead behind the combine pass, it then holds
+    // the finished x_0 of a dynamic-threshold step -- and the scratch of the two guidance passes (guidance.hip)
     char* ws = nullptr; size_t ws_cap = 0;
     bool ws_suf = false;
     int ws_B = 0, ws_T = 0; size_t ws_tail = 0;      // the window shape ws_tail was computed for (dry run of the topology)
     std::unordered_map<long long, size_t> ws_peaks;  // (B << 32 | T) -> arena peak
     static size_t tm_bytes(int B) { return ((size_t)B * sizeof(float) + 255) & ~(size_t)255; }
     size_t out_floats(int B, int T) const { return (size_t)B * T * (cfg.learn_sigma ? 6 : 3) * cfg.image_size * cfg.image_size; }
-    size_t step_tail_bytes(int B, int T) const { return tm_bytes(B) + 2 * out_floats(B, T) * sizeof(float); }
+    size_t guid_off(int B, int T) const { return (tm_bytes(B) + 2 * out_floats(B, T) * sizeof(float) + 255) & ~(size_t)255; }
+    size_t step_tail_bytes(int B, int T) const { return guid_off(B, T) + guidance_scratch_bytes(B); }
     float* step_tm() const { return reinterpret_cast<float*>(ws + ws_tail); }
     float* step_eps(int B) const { return reinterpret_cast<float*>(ws + ws_tail + tm_bytes(B)); }
     float* step_eps_u(int B, int T) const { return step_eps(B) + out_floats(B, T); }      // out_u of a cfg step
+    void* step_guid(int B, int T) const { return ws + ws_tail + guid_off(B, T); }      // ws_tail is 256-byte rounded, hipMalloc's base more
     Arena step_arena() const { Arena a; a.base = ws; a.cap = ws_tail; return a; }     // the activations end where the tail begins
     // ---- use_gradient_method: second packed image (backward-data weights) + the tape of the guided step's forward
     float* wbuf_bwd = nullptr; bool wbuf_bwd_on_host = false; size_t packed_bwd_total = 0;
@@ -301,6 +304,9 @@ struct vd_engine {
     // and cfg_combine_kernel in front of its sampler pass
     float cfg_w = 1.f;
     float* d_cfg_zero = nullptr; size_t cfg_zero_cap = 0;   // [B*T] zeros: the observation mask of the unconditional forward
+    // guidance rescale (vd_set_guidance_rescale; 0 = off; acts with cfg_w != 1) and dynamic thresholding (vd_set_dynamic_threshold; 0 = off;
+    // acts with clip_denoised, whose clamp it replaces): engine state like cfg_w, part of a window graph's key
+    float guid_phi = 0.f, dyn_p = 0.f;
     int mean_type = 0;                               // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
@@ -313,6 +319,7 @@ struct vd_engine {
     struct WinKey {                  // the arguments of vd_window_begin a captured step depends on (zero-filled: compared bytewise)
         int B, T, obs_mode, sampler, clip, flags; float eta;      // flags: 1 prefix cache, 2 suffix skip
         float cfg_w;                                              // cfg_scale: a graph holds one forward (1) or two and the combine pass with this weight
+        float guid_phi, dyn_p;                                    // guidance rescale / dynamic threshold: the passes a graph holds and their constants
         float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
@@ -1840,13 +1847,19 @@ static int cfg_zero_mask(vd_engine* e, int B, int T, hipStream_t st) {
 // cfg_w != 1 (cfg_scale): behind the forward a second one at the same batch size with the engine's all-zero observation mask (cfg_zero_mask
 // has sized it) into the second output buffer, in the same arena, then cfg_combine_kernel in place over the first output -- which is what
 // every sampler pass below, and the caller's eps_out, then see.  Noise, t and the passes themselves do not change.
+// guid_phi != 0 with cfg_w != 1 (guidance rescale): the two passes of launch_cfg_rescale stand in for the combine pass.  dyn_p != 0 with
+// clip (dynamic thresholding): launch_dynamic_threshold writes the finished x_0 into the second output buffer, and the sampler pass runs in
+// its x0_given form with clip off -- the form `denoised_fn` uses, bit-matched to the fused step.  With both at 0 the launches are the ones above.
 static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
                          const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
                          int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
                          const unsigned long long* rng, float* sample, float* xstart, float* mean, float* eps_out,
                          hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr, const float* hist = nullptr,
-                         const unsigned long long* hist_on = nullptr, float cfg_w = 1.f) {
+                         const unsigned long long* hist_on = nullptr, float cfg_w = 1.f, float guid_phi = 0.f, float dyn_p = 0.f) {
     int rc;
+    const bool rescale = cfg_w != 1.f && guid_phi != 0.f, thresh = dyn_p != 0.f && clip;
+    VD_REQUIRE(!rescale || (!pp && !sp), "guidance_rescale together with the window prefix cache or suffix skip");
+    VD_REQUIRE(!thresh || (!pp && !sp), "dynamic_threshold together with the window prefix cache or suffix skip");
     if (cfg_w != 1.f) {
         VD_REQUIRE(!pp && !sp, "cfg_scale != 1 together with the window prefix cache or suffix skip");
         VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "cfg_scale != 1 together with return_attn_weights: a step makes two forwards");
@@ -1865,25 +1878,39 @@ static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, c
         fu.obs = e->d_cfg_zero; fu.eps = e->step_eps_u(B, T);
         if ((rc = e->forward(fu, st, au))) return rc;
         const long long n = (long long)e->out_floats(B, T);
-        ProfScope ps(PC_ELEMENTWISE, 2.0 * n, 12.0 * n, st, "cfg_combine");
-        if ((rc = launch_cfg_combine(eps, fu.eps, cfg_w, n, eps, st))) return rc;
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * n, rescale ? 20.0 * n : 12.0 * n, st, rescale ? "cfg_rescale" : "cfg_combine");
+        if (rescale) rc = launch_cfg_rescale(eps, fu.eps, cfg_w, lat, B, T, (long)(per / T), guid_phi, eps, nullptr, e->step_guid(B, T), st);
+        else rc = launch_cfg_combine(eps, fu.eps, cfg_w, n, eps, st);
+        if (rc) return rc;
     }
+    const float* x0_thr = nullptr;                   // dynamic thresholding: the finished x_0 (out_u's buffer is free by now)
+    if (thresh) {
+        const bool start_x = e->mean_type == 1;
+        DynThreshArgs da{eps, start_x ? nullptr : x, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, lat, B, T,
+                         (long)(per / T), dyn_p, e->step_eps_u(B, T), nullptr, e->d_err, e->step_guid(B, T)};
+        ProfScope ps(PC_ELEMENTWISE, 4.0 * B * per, 4.0 * B * per * 8.0, st, "dynamic_threshold");
+        if ((rc = launch_dynamic_threshold(da, st))) return rc;
+        x0_thr = da.out;
+        clip = 0;
+    }
+    // what the sampler pass reads: the network output as eps, or an x_0 prediction -- the output of a START_X model
+    // (pred_xstart = process_xstart(model_output), gaussian_diffusion.py:326-341) or the thresholded one
+    const bool given = e->mean_type == 1 || x0_thr;
+    const float* src = x0_thr ? x0_thr : eps;
     if (mode == 2) {                                 // ddim_reverse_sample (gaussian_diffusion.py:636-668): its own pass, no noise
-        const bool start_x = e->mean_type == 1;      // START_X: pred_xstart = process_xstart(model_output)
-        DdimReverseArgs ra{x, start_x ? nullptr : eps, start_x ? eps : nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab,
+        DdimReverseArgs ra{x, given ? nullptr : src, given ? src : nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab,
                            e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
         return launch_ddim_reverse(ra, st);
     }
     if (mode == 3) {                                 // dpmpp_2m_sample: its own pass, no noise
-        const bool start_x = e->mean_type == 1;
-        Dpmpp2mArgs ma{x, start_x ? nullptr : eps, start_x ? eps : nullptr, hist, hist_on, reinterpret_cast<const int64_t*>(t), e->d_tab,
+        Dpmpp2mArgs ma{x, given ? nullptr : src, given ? src : nullptr, hist, hist_on, reinterpret_cast<const int64_t*>(t), e->d_tab,
                        e->d_w2m, e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
         return launch_dpmpp_2m(ma, st);
     }
     PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
                      mode, eta, seed, offset, sample, xstart, mean, rng};
     pa.err = e->d_err;
-    if (e->mean_type == 1) pa.x0_given = eps;        // START_X: pred_xstart = process_xstart(model_output) (gaussian_diffusion.py:326-341)
+    if (given) pa.x0_given = src;
     ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
     return launch_posterior(pa, st);
 }
@@ -1900,7 +1927,8 @@ static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, con
     if ((rc = e->ensure_ws(B, T))) return rc;
     if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
     return step_launches(e, mode, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, nullptr,
-                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist, nullptr, e->cfg_w);
+                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist, nullptr, e->cfg_w,
+                         e->guid_phi, e->dyn_p);
 }
 
 int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
@@ -1912,7 +1940,7 @@ int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* 
     if ((rc = e->ensure_ws(B, T))) return rc;
     if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
     return step_launches(e, 0, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, nullptr, nullptr,
-                         xstart, mean, eps, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, e->cfg_w);
+                         xstart, mean, eps, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, e->cfg_w, e->guid_phi, e->dyn_p);
 }
 
 int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x_t, const float* eps, const float* noise,
@@ -2127,7 +2155,8 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     const bool ms = k.sampler == 3;
     if (!rc) rc = step_launches(e, k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta,
                                 nullptr, 0, 0, e->d_win_rng, k.x, ms ? e->d_win_hist : nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
-                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr, k.cfg_w);
+                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr, k.cfg_w,
+                                k.guid_phi, k.dyn_p);
     if (!rc) {
         const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards; it and dpmpp_2m_sample draw nothing
         hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, up ? 1LL : -1LL,
@@ -2177,6 +2206,11 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     // "their network input cannot change" (prefix cache) nor "their output is never read" (suffix skip) holds for them
     VD_REQUIRE(e->cfg_w == 1.f || !e->prefix_cache_on, "cfg_scale != 1 together with the window prefix cache (vd_set_window_prefix_cache) is not served");
     VD_REQUIRE(e->cfg_w == 1.f || !e->suffix_skip_on, "cfg_scale != 1 together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    // the statistics of both guidance options run over whole latent frames of a step the two window switches would cut short
+    VD_REQUIRE(e->guid_phi == 0.f || e->cfg_w == 1.f || !e->prefix_cache_on, "guidance_rescale != 0 (vd_set_guidance_rescale) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+    VD_REQUIRE(e->guid_phi == 0.f || e->cfg_w == 1.f || !e->suffix_skip_on, "guidance_rescale != 0 (vd_set_guidance_rescale) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    VD_REQUIRE(e->dyn_p == 0.f || !clip || !e->prefix_cache_on, "dynamic_threshold (vd_set_dynamic_threshold) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+    VD_REQUIRE(e->dyn_p == 0.f || !clip || !e->suffix_skip_on, "dynamic_threshold (vd_set_dynamic_threshold) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = e->ensure_ws(B, T))) return rc;
@@ -2187,6 +2221,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     vd_engine::WinKey key;
     std::memset(&key, 0, sizeof(key));
     key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.eta = eta; key.cfg_w = e->cfg_w;
+    key.guid_phi = e->guid_phi; key.dyn_p = e->dyn_p;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
     e->win_cur = -1;
     e->win_lost = false;
@@ -2236,6 +2271,46 @@ float vd_cfg_scale(vd_engine* e) { return e ? e->cfg_w : 1.f; }
 
 int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream) {
     return launch_cfg_combine(out_c, out_u, w, n, out, static_cast<hipStream_t>(stream));
+}
+
+// guidance rescale and dynamic thresholding, engine state like cfg_scale: 0 = off; the window graph's key carries both
+int vd_set_guidance_rescale(vd_engine* e, float phi) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(phi >= 0.f && phi <= 1.f, "guidance_rescale must lie in [0, 1]");
+    e->guid_phi = phi;
+    return 0;
+}
+
+float vd_guidance_rescale(vd_engine* e) { return e ? e->guid_phi : 0.f; }
+
+int vd_set_dynamic_threshold(vd_engine* e, float p) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(p >= 0.f && p <= 1.f, "dynamic_threshold must lie in (0, 1], or be 0 (off)");
+    e->dyn_p = p;
+    return 0;
+}
+
+float vd_dynamic_threshold(vd_engine* e) { return e ? e->dyn_p : 0.f; }
+
+// The op entries own their scratch for the length of the call (OpScratch; tests -- a step uses the workspace).
+int vd_op_cfg_rescale(const float* out_c, const float* out_u, float w, const float* lat, int B, int T, long long frame_elems, float phi,
+                      float* out, float* factor_out, void* stream) {
+    VD_REQUIRE(B > 0 && frame_elems > 0, "vd_op_cfg_rescale: shape");
+    OpScratch ws(stream);
+    char* buf = nullptr;
+    int rc = ws.get(&buf, guidance_scratch_bytes(B));
+    return rc ? rc : launch_cfg_rescale(out_c, out_u, w, lat, B, T, (long)frame_elems, phi, out, factor_out, buf, ws.st);
+}
+
+int vd_op_dynamic_threshold(const float* x0, const float* lat, int B, int T, long long frame_elems, float p, float* out, float* s_out,
+                            void* stream) {
+    VD_REQUIRE(B > 0 && frame_elems > 0, "vd_op_dynamic_threshold: shape");
+    OpScratch ws(stream);
+    char* buf = nullptr;
+    int rc = ws.get(&buf, guidance_scratch_bytes(B));
+    if (rc) return rc;
+    DynThreshArgs da{x0, nullptr, nullptr, nullptr, 0, lat, B, T, (long)frame_elems, p, out, s_out, nullptr, buf};
+    return launch_dynamic_threshold(da, ws.st);
 }
 
 int vd_window_prefix_frames(vd_engine* e) {

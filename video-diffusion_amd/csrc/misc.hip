@@ -553,12 +553,7 @@ int launch_posterior(const PosteriorArgs& a, hipStream_t s) {
 // The x_0 prediction of an epsilon-model as posterior_kernel forms it: two products, each rounded, then one subtraction -- NOT a fused
 // multiply-add.  The step through `denoised_fn` takes its x_0 from posterior_kernel (vd_p_mean_variance) and hands it to the *_from_xstart
 // form of the passes below: with the same rounding here, the fused step and that form agree to the bit for denoised_fn = identity.
-__device__ __forceinline__ float xstart_from_eps(float sr, float x, float srm1, float eps) {
-#pragma clang fp contract(off)
-    const float a = sr * x, b = srm1 * eps;
-    return a - b;
-}
-
+// (xstart_from_eps lives in vd_common.h: the dynamic-threshold pass of guidance.hip forms its x_0 with the same function.)
 __device__ __forceinline__ float ddim_reverse_one(float x, float src, bool given, float sr, float srm1, float r, float s, int clip,
                                                   float& x0_out, bool& nonfinite) {
     float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
@@ -690,12 +685,7 @@ int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s) {
 // w = 0 hands out_u through as it is: the fma would turn a -0 of out_u into +0 whenever w d is +0.  Pure streaming: two reads and one
 // write per element, four elements per thread and pass while the three tensors are 16-byte aligned, the n % 4 last ones (or, unaligned,
 // all of them) one by one; out may alias out_c or out_u: the pass is elementwise.
-__device__ __forceinline__ float cfg_combine_one(float c, float u, float w) {
-    const float d = c - u;
-    if (!(fabsf(d) <= 3.4028234e38f)) return __builtin_nanf("");
-    return w == 0.0f ? u : fmaf(w, d, u);
-}
-
+// (cfg_combine_one lives in vd_common.h: the combine-and-moments pass of guidance.hip produces the same bits with it.)
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* out_c, const float* out_u, float w, size_t n4, size_t n, float* out) {
     const float4* c4 = reinterpret_cast<const float4*>(out_c);
     const float4* u4 = reinterpret_cast<const float4*>(out_u);

@@ -451,6 +451,41 @@ int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s);
 // NaN where the difference is not finite, out_u[i] itself at w = 0.  Any n > 0; out may alias out_c or out_u; 16-byte aligned tensors take
 // the float4 path, others run element by element.  w must be finite.
 int launch_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, hipStream_t s);
+// The two element formulas more than one source needs bit for bit (misc.hip's sampler passes and cfg_combine_kernel, guidance.hip):
+// one guided network output, and the x_0 prediction of an epsilon-model -- two products, each rounded, then one subtraction.
+__device__ __forceinline__ float cfg_combine_one(float c, float u, float w) {
+    const float d = c - u;
+    if (!(fabsf(d) <= 3.4028234e38f)) return __builtin_nanf("");
+    return w == 0.0f ? u : fmaf(w, d, u);
+}
+__device__ __forceinline__ float xstart_from_eps(float sr, float x, float srm1, float eps) {
+#pragma clang fp contract(off)
+    const float a = sr * x, b = srm1 * eps;
+    return a - b;
+}
+// Guidance rescale and dynamic thresholding (guidance.hip; this project's extensions).  Tensors are [B][T][frame_elems], `lat` the [B*T]
+// latent mask: an item's statistic runs over the elements of its frames with lat == 1.  `scratch`: guidance_scratch_bytes(B) bytes, 256-byte
+// aligned, the caller's; nothing here allocates or waits for the device.
+size_t guidance_scratch_bytes(int B);
+// out = cfg_combine_one(out_c, out_u, w), times f = 1 + phi (sigma_c / sigma_g - 1) on the latent frames (f = 1 where sigma_g = 0 or nothing
+// is latent); factor_out [B] or null; out may alias out_c or out_u
+int launch_cfg_rescale(const float* out_c, const float* out_u, float w, const float* lat, int B, int T, long frame_elems, float phi,
+                       float* out, float* factor_out, void* scratch, hipStream_t s);
+struct DynThreshArgs {
+    const float* src;       // the network output: eps (x != null) or the x_0 prediction itself (x == null)
+    const float* x;         // x_t, or null
+    const int64_t* t;       // [B] respaced index (read with x only)
+    const float* tab;
+    int num_timesteps;
+    const float* lat;
+    int B, T; long frame_elems;
+    float p;                // the percentile, (0, 1]
+    float* out;             // the finished x_0: latent frames clamp(x_0, -s, s) / s, other frames clamp(x_0, -1, 1); may alias src
+    float* s_out;           // [B] the thresholds max(s, 1) (NaN for an item with a non-finite latent x_0), or null
+    int* err;               // as PosteriorArgs::err, or null
+    void* scratch;
+};
+int launch_dynamic_threshold(const DynThreshArgs& a, hipStream_t s);
 int launch_q_sample(const float* x0, const float* noise, const int64_t* t, const float* tab, int num_timesteps, int B,
                     long per, float* out, hipStream_t s);
 int launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, hipStream_t s);

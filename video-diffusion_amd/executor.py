@@ -73,7 +73,10 @@ class WindowExecutor:
         cfg_scale (this project's extension; gaussian_diffusion.py: p_sample): the captured step holds both forwards, the combine pass
         and the sampler pass; the weight is part of the graph's signature, so windows under different weights replay different graphs.
         The noise of a window does not depend on it.  Not served together with prefix_cache or suffix_skip: in the unconditional
-        forward the observed frames are padding frames whose content is whatever the window tensor holds."""
+        forward the observed frames are padding frames whose content is whatever the window tensor holds.
+        Guidance rescale and dynamic thresholding are not parameters: a begin() inside `diffusion.guidance_scope(...)` captures (or finds)
+        the graph of the scope's values -- they are part of the signature like the weight -- and run() may be called outside the scope.
+        The engine refuses either of them together with prefix_cache or suffix_skip."""
         cfg_scale = float(cfg_scale)
         if not math.isfinite(cfg_scale):
             raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
@@ -81,6 +84,13 @@ class WindowExecutor:
             raise NotImplementedError("prefix_cache together with cfg_scale != 1")
         if cfg_scale != 1.0 and self.suffix_skip:
             raise NotImplementedError("suffix_skip together with cfg_scale != 1")
+        if self.prefix_cache or self.suffix_skip:                 # the guidance options of an enclosing guidance_scope (engine state)
+            L, h = _lib.lib(), self.model._handle
+            which = "prefix_cache" if self.prefix_cache else "suffix_skip"
+            if float(L.vd_guidance_rescale(h)) != 0.0 and (cfg_scale != 1.0 or float(L.vd_cfg_scale(h)) != 1.0):
+                raise NotImplementedError(f"{which} together with cfg_rescale != 0")
+            if float(L.vd_dynamic_threshold(h)) != 0.0 and clip_denoised:
+                raise NotImplementedError(f"{which} together with dynamic_threshold")
         mode = model_kwargs.get("observed_frames", "x_0")
         if mode not in _OBS_MODES:
             raise NotImplementedError(f"observed_frames={mode!r}: the window executor handles 'x_0', 'x_t' and 'x_t_minus_1'")

@@ -17,7 +17,10 @@ loops is an extension as a whole: DPM-Solver++(2M), the second-order multistep s
 one fused pass (dpmpp_2m_kernel) that reuses the previous step's x_0 prediction.  `cfg_scale` on the step and loop entry points is
 an extension too: classifier-free guidance on the observed frames, out_u + w (out_c - out_u) with out_u the network output of the same
 call under an all-zero obs_mask -- a second forward and one fused pass (cfg_combine_kernel) in front of the unchanged sampler pass
-(include/vd_amd.h: vd_set_cfg_scale).  Training losses are out of scope.
+(include/vd_amd.h: vd_set_cfg_scale).  Two more extensions make w > 1 usable under clip_denoised, both through
+`GaussianDiffusion.guidance_scope`: guidance rescale (the guided output's spread over the latent frames brought back towards the
+conditional one's) and dynamic thresholding (a per-item percentile of |x_0| over the latent frames in place of the clamp's 1); their
+per-item statistics are taken on the device inside the step (csrc/guidance.hip).  Training losses are out of scope.
 """
 import contextlib
 import enum
@@ -104,6 +107,34 @@ def _cfg_scope(model, cfg_scale):
         yield
     finally:
         _lib.check(L.vd_set_cfg_scale(model._handle, before))
+
+
+def _check_guidance(cfg_rescale, dynamic_threshold):
+    """The range checks of the two guidance options (no engine): returns (phi, p) as floats, p = 0.0 for None (off)."""
+    phi = float(cfg_rescale)
+    if not 0.0 <= phi <= 1.0:                                  # (a NaN fails both comparisons)
+        raise ValueError(f"cfg_rescale={cfg_rescale!r}: the rescale blend must be finite and lie in [0, 1]")
+    if dynamic_threshold is None:
+        return phi, 0.0
+    p = float(dynamic_threshold)
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"dynamic_threshold={dynamic_threshold!r}: the percentile must lie in (0, 1] (None switches it off)")
+    return phi, p
+
+
+@contextlib.contextmanager
+def _guidance_scope(model, phi, p):
+    """The engine's guidance_rescale and dynamic_threshold for the calls inside; behind them, whatever they raise, the values found
+    before (as _cfg_scope)."""
+    L = _lib.lib()
+    before = float(L.vd_guidance_rescale(model._handle)), float(L.vd_dynamic_threshold(model._handle))
+    try:
+        _lib.check(L.vd_set_guidance_rescale(model._handle, phi))
+        _lib.check(L.vd_set_dynamic_threshold(model._handle, p))
+        yield
+    finally:
+        _lib.check(L.vd_set_guidance_rescale(model._handle, before[0]))
+        _lib.check(L.vd_set_dynamic_threshold(model._handle, before[1]))
 
 
 class GaussianDiffusion:
@@ -199,6 +230,22 @@ class GaussianDiffusion:
         cfg_scale = _check_cfg(cfg_scale)
         return _cfg_scope(self._bind(model), cfg_scale)
 
+    def guidance_scope(self, model, cfg_rescale=0.0, dynamic_threshold=None):
+        """This project's extension: `with diffusion.guidance_scope(model, cfg_rescale=phi, dynamic_threshold=p):` -- every step entry
+        point, loop and WindowExecutor.begin called inside runs with the two options below; the values found before are back when the
+        block ends, whatever it raised, and scopes nest.  Both take one statistic per batch item over the elements of the item's latent
+        frames (latent_mask == 1); observed and padding frames keep the bits of the plain step.
+        cfg_rescale phi in [0, 1] (Lin et al. 2023, 3.4; 0 = off): the guided network output times 1 + phi (sigma_c / sigma_g - 1),
+        the sigmas being the standard deviations of the conditional and the guided output; acts only with cfg_scale != 1 (with
+        cfg_scale == 1 it is accepted and does nothing).
+        dynamic_threshold p in (0, 1] (Saharia et al. 2022, 2.3; None = off): with clip_denoised, s = max(1, the p-quantile of |x_0|)
+        -- torch.quantile's linear interpolation between two exact order statistics -- and x_0 <- clamp(x_0, -s, s) / s in place of the
+        clamp to [-1, 1]; works at any cfg_scale.  Refused together with denoised_fn.
+        Either option is refused together with the window executor's prefix_cache or suffix_skip, and neither is honoured by
+        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_guidance_rescale)."""
+        phi, p = _check_guidance(cfg_rescale, dynamic_threshold)
+        return _guidance_scope(self._bind(model), phi, p)
+
     def _scale_timesteps(self, t):
         if self.rescale_timesteps:
             return t.float() * (1000.0 / self.num_timesteps)
@@ -293,7 +340,11 @@ class GaussianDiffusion:
         (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
         in vd_ddim_reverse_from_xstart and draws no noise; mode 3 (dpmpp_2m_sample, with its `prev_xstart` or None) ends in
         vd_dpmpp_2m_from_xstart and draws none either.  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
-        the guided one, the passes behind it run no network."""
+        the guided one, the passes behind it run no network.  dynamic_threshold (guidance_scope) would have to run between the
+        callback and those passes: refused."""
+        if clip_denoised and _lib.lib().vd_dynamic_threshold(self._bind(model)._handle) != 0.0:
+            raise NotImplementedError("denoised_fn together with dynamic_threshold (guidance_scope): the threshold replaces the clamp "
+                                      "of the fused step, which a step through denoised_fn does not run")
         out = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
                                    cfg_scale=cfg_scale)
         base = self._bind(model)

@@ -44,7 +44,8 @@ def get_masks(x0, num_obs):
 @torch.no_grad()
 def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size=1, optimal_schedule_path=None, *,
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
-                adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0):
+                adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
+                cfg_rescale=0.0, dynamic_threshold=None):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -72,7 +73,24 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     cfg_scale (this project's extension, both executors, every sampler): the weight w of classifier-free guidance on each window's
     observed frames -- every step runs on out_u + w (out_c - out_u), out_u being the network output with the window's obs_mask
     zeroed (gaussian_diffusion.py: p_sample).  1.0 (default) is the sampling as it always was; any other value costs two forwards
-    per step and is refused together with use_gradient_method, prefix_cache (graph) and suffix_skip (graph)."""
+    per step and is refused together with use_gradient_method, prefix_cache (graph) and suffix_skip (graph).
+
+    cfg_rescale, dynamic_threshold (this project's extensions, both executors, every sampler): the whole of this function's work runs
+    inside `diffusion.guidance_scope(model, cfg_rescale, dynamic_threshold)` -- guidance rescale (phi in [0, 1], acts with
+    cfg_scale != 1) and dynamic thresholding (the percentile p in (0, 1], in place of the clamp of x_0), each with its statistic per
+    batch item over the window's latent frames (gaussian_diffusion.py: guidance_scope).  With both at their defaults (0.0, None) no
+    scope is entered and the engine is not touched.  Refused together with use_gradient_method, prefix_cache and suffix_skip."""
+    if float(cfg_rescale) != 0.0 or dynamic_threshold is not None:
+        from .gaussian_diffusion import _check_guidance
+        _check_guidance(cfg_rescale, dynamic_threshold)                     # before anything touches the engine
+        for name, on in (("use_gradient_method", use_gradient_method), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
+            if on:
+                raise NotImplementedError(f"{name} together with cfg_rescale / dynamic_threshold")
+        with diffusion.guidance_scope(model, cfg_rescale=cfg_rescale, dynamic_threshold=dynamic_threshold):
+            return infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size, optimal_schedule_path,
+                               use_gradient_method=use_gradient_method, observed_frames=observed_frames, sampler=sampler, eta=eta,
+                               executor=executor, adaptive_distance=adaptive_distance, prefix_cache=prefix_cache, suffix_skip=suffix_skip,
+                               save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale)
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -381,6 +399,13 @@ def build_parser():
                     help="classifier-free guidance weight on the observed frames: every step runs on out_u + w (out_c - out_u), out_u being the "
                          "network output with nothing observed; 1.0 (default) is plain sampling, any other value costs two forwards per step and "
                          "is named in the run directory")
+    ap.add_argument("--cfg_rescale", type=float, default=0.0,
+                    help="guidance rescale (with --cfg_scale other than 1): blend PHI in [0, 1] that brings the guided output's standard "
+                         "deviation over each item's latent frames back towards the conditional output's; 0 (default) is off; named in the "
+                         "run directory when set")
+    ap.add_argument("--dynamic_threshold", type=float, default=None,
+                    help="dynamic thresholding: the percentile P in (0, 1] of |x_0| over each item's latent frames that replaces the 1 of the "
+                         "clamp of x_0 (never below 1); off by default; named in the run directory when set")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -405,15 +430,20 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        executor=getattr(args, "executor", "eager"),
                        adaptive_distance=getattr(args, "adaptive_distance", "l2"),
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
-                       save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0))
+                       save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
+                       cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
-    ('_cfg2', '_cfg1.5', '_cfg-0.5') -- samples of different samplers or guidance weights never share a directory."""
+    ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7') and a dynamic_threshold ('_dt0.995') -- samples of
+    different samplers or guidance settings never share a directory, and a run without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
-    return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}")
+    phi = float(getattr(args, "cfg_rescale", 0.0) or 0.0)
+    p = getattr(args, "dynamic_threshold", None)
+    return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}")
 
 
 def run(args, create=None, device=None, infer=None):
