@@ -552,6 +552,13 @@ int vd_op_gn_temporal(const float* x, const float* gamma, const float* beta, int
 int vd_op_attn_spatial(const float* qkv, int nfr, int L, int C, int heads, float* out, void* stream);
 int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, const float* Rv, const float* mask, int B,
                         int T, int HW, int C, int heads, int allow_pad, float* out, void* stream);
+/* Which kernel instantiation vd_op_attn_temporal (and the engine) runs a per-item shape on, as its C++ name --
+ * "attn_temporal_mfma_kernel<NT,JM,RPE,EXACT>", "attn_temporal_kernel<PB,TMAX,RPE>" (T <= 32),
+ * "attn_temporal_long_mfma_kernel<NJ,RPE>", "attn_temporal_long_kernel<RPE>" (T = 33..128) -- or "refused: <reason>".
+ * Returns 1 (a kernel), 0 (refused) or a negative code (no room in name[cap]).  Host only: no launch, no device call; the
+ * launchers dispatch through the same function.  The batch size is no argument: it never changes the choice.  Tests use it
+ * to know which kernel they exercised. */
+int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* name, int cap);
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
 /* Backward-data operators of use_gradient_method (csrc/backward.hip); each one synchronises its stream before it returns. */

@@ -9,6 +9,7 @@ import torch
 import torch.nn.functional as F
 
 import video_diffusion_amd as vda
+from attn_temporal_restated import attn_ref
 from helpers import close, load_npz, synth_sd
 from oracle.sampler_ref import SamplerRef
 from oracle.schedule_ref import ScheduleRef
@@ -81,33 +82,6 @@ def test_max_window_frames_is_128():
 
 
 # ---------------------------------------------------------------------------------------------------- the operator
-def attn_ref(qkv, Rk, Rq, Rv, m, allow, B, T, HW, C, heads):
-    """fp64 restatement of unet.py:486-536 + the RPE einsums :357-378 + the mask rule :511-524."""
-    Fd = C // heads
-    scale = Fd ** -0.5
-    x = qkv.double().permute(0, 2, 1, 3).reshape(B, HW, T, 3, heads, Fd).permute(3, 0, 1, 4, 2, 5)     # t B D H T F
-    q, k, v = x[0] * scale, x[1], x[2]
-    w = q @ k.transpose(-1, -2)
-    if Rk is not None:
-        rk, rq, rv = (r.double().view(B, T, T, heads, Fd) for r in (Rk, Rq, Rv))
-        w = w + torch.einsum("bdhtf,btshf->bdhts", q, rk)
-        w = w + torch.einsum("bdhtf,btshf->bdhts", k * scale, rq).transpose(-1, -2)
-    if m is not None:
-        m = m.double()
-        ok = m.view(B, 1, T) * m.view(B, T, 1)
-        if allow:
-            ok = ok + (1 - m.view(B, 1, T)) * (1 - m.view(B, T, 1))
-        else:
-            ok = ok.clone()
-            ok[:, range(T), range(T)] = 1.0
-        w = w.masked_fill((ok == 0).view(B, 1, 1, T, T), float("-inf"))
-    a = torch.softmax(w, -1)
-    o = a @ v
-    if Rk is not None:
-        o = o + torch.einsum("bdhts,btshf->bdhtf", a, rv)
-    return o.permute(0, 3, 1, 2, 4).reshape(B, T, HW, C)
-
-
 # (B, T, HW, C, heads, rpe, mask, allow, hot): head dims 16, 32, 64, 96, 128 and 24 (a multiple of 8, not of 16); pixel
 # counts divisible by 16 (matrix-pipe kernel) and ragged (generic kernel); mask "half": every other frame of item 0 and the
 # middle frame are padding; "pad16": the last 20 frames are padding, so whole 16-key tiles are masked for the real rows;

@@ -489,36 +489,61 @@ static int launch_tt(const AttnTemporalArgs& a, size_t lds, hipStream_t s) {
     return 0;
 }
 
+// The kernel is chosen by the per-item shape alone (pixels, heads, head dim, T), never by the batch: a clip gives the same
+// bits whether it is sampled alone (a strong-scaling shard) or inside a batch.  (At B = 1 the 4-pixel blocks of the
+// VALU kernel fill the chip slightly better -- 5.87 against 5.95 ms per step -- which is not worth a batch-dependent result.)
+AttnTemporalVariant attn_temporal_variant(int T, int HW, int C, int heads, bool rpe) {
+    using V = AttnTemporalVariant;
+    V v{V::kRefused, 0, 0, false, rpe, 0, nullptr};
+    auto pick = [&](V::Family fam, int p0, int p1, bool exact, size_t lds) { v.family = fam; v.p0 = p0; v.p1 = p1; v.exact = exact; v.lds = lds; return v; };
+    if (!(T >= 1 && T <= kMaxWindowFrames)) { v.why = "temporal window of 1..128 frames"; return v; }
+    if (!(heads > 0 && C > 0 && C % heads == 0 && (C / heads) % 8 == 0)) { v.why = "head dim multiple of 8"; return v; }
+    const int F = C / heads;
+    const bool pipe = HW % 16 == 0 && F % 16 == 0 && F <= 128;   // the matrix-pipe kernels: 16-pixel blocks, 16-feature k steps, one feature tile per wave
+    if (T > 32)                                                 // key tiles + online softmax (attn_temporal_long.hip)
+        return pipe ? pick(V::kLongMfma, F / 16, 0, false, 0) : pick(V::kLongGeneric, 0, 0, false, 0);
+    if (pipe) {
+        if (T == 16 && F == 96) return pick(V::kMfma, 1, 6, true, 0);      // the default models' two shapes
+        if (T == 16 && F == 128) return pick(V::kMfma, 1, 8, true, 0);
+        return pick(V::kMfma, T <= 16 ? 1 : 2, F <= 64 ? 4 : 8, false, 0);
+    }
+    auto lds_for = [&](int pb) { return ((size_t)2 * pb * T * (F + 4) + (size_t)pb * T * (T + 1)) * sizeof(float); };
+    if (!(lds_for(2) <= 150 * 1024)) { v.why = "head dim too large for the temporal attention tile"; return v; }
+    const int pb = lds_for(4) > 96 * 1024 ? 2 : 4;
+    return pick(V::kValu, pb, T <= 16 ? 16 : 32, false, lds_for(pb));
+}
+
+std::string attn_temporal_variant_name(const AttnTemporalVariant& v) {
+    using V = AttnTemporalVariant;
+    const char* r = v.rpe ? "true" : "false";
+    const std::string p0 = std::to_string(v.p0), p1 = std::to_string(v.p1);
+    switch (v.family) {
+        case V::kMfma: return "attn_temporal_mfma_kernel<" + p0 + "," + p1 + "," + r + "," + (v.exact ? "true" : "false") + ">";
+        case V::kValu: return "attn_temporal_kernel<" + p0 + "," + p1 + "," + r + ">";
+        case V::kLongMfma: return "attn_temporal_long_mfma_kernel<" + p0 + "," + r + ">";
+        case V::kLongGeneric: return std::string("attn_temporal_long_kernel<") + r + ">";
+        default: return std::string("refused: ") + (v.why ? v.why : "");
+    }
+}
+
+template <bool RPE>
+static int launch_variant(const AttnTemporalVariant& v, const AttnTemporalArgs& a, hipStream_t s) {
+    if (v.family == AttnTemporalVariant::kMfma) {
+        if (v.exact) return v.p1 == 6 ? launch_tm<1, 6, RPE, true>(a, s) : launch_tm<1, 8, RPE, true>(a, s);
+        if (v.p0 == 1) return v.p1 == 4 ? launch_tm<1, 4, RPE, false>(a, s) : launch_tm<1, 8, RPE, false>(a, s);
+        return v.p1 == 4 ? launch_tm<2, 4, RPE, false>(a, s) : launch_tm<2, 8, RPE, false>(a, s);
+    }
+    if (v.p1 == 16) return v.p0 == 2 ? launch_tt<2, 16, RPE>(a, v.lds, s) : launch_tt<4, 16, RPE>(a, v.lds, s);
+    return v.p0 == 2 ? launch_tt<2, 32, RPE>(a, v.lds, s) : launch_tt<4, 32, RPE>(a, v.lds, s);
+}
+
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.T >= 1 && a.T <= kMaxWindowFrames, "temporal window of 1..128 frames");
-    VD_REQUIRE(a.C % a.heads == 0 && (a.C / a.heads) % 8 == 0, "head dim multiple of 8");
-    VD_REQUIRE((a.Rk == nullptr) == (a.Rq == nullptr) && (a.Rk == nullptr) == (a.Rv == nullptr), "all or no RPE terms");
-    if (a.T > 32) return launch_attn_temporal_long(a, s);     // key tiles + online softmax (attn_temporal_long.hip)
-    const int F = a.C / a.heads;
-    // The kernel is chosen by the per-item shape alone (pixels, heads, head dim, T), never by the batch: a clip gives the same
-    // bits whether it is sampled alone (a strong-scaling shard) or inside a batch.  (At B = 1 the 4-pixel blocks of the
-    // VALU kernel fill the chip slightly better -- 5.87 against 5.95 ms per step -- which is not worth a batch-dependent result.)
-    if (a.HW % 16 == 0 && F % 16 == 0 && F <= 128) {           // the matrix-pipe kernel: 16-pixel blocks, 16-feature k steps, one feature tile per wave
-        const bool rpe = a.Rk != nullptr;
-        if (a.T == 16 && F == 96) return rpe ? launch_tm<1, 6, true, true>(a, s) : launch_tm<1, 6, false, true>(a, s);     // the default models' two shapes
-        if (a.T == 16 && F == 128) return rpe ? launch_tm<1, 8, true, true>(a, s) : launch_tm<1, 8, false, true>(a, s);
-        if (a.T <= 16) {
-            if (F <= 64) return rpe ? launch_tm<1, 4, true, false>(a, s) : launch_tm<1, 4, false, false>(a, s);
-            return rpe ? launch_tm<1, 8, true, false>(a, s) : launch_tm<1, 8, false, false>(a, s);
-        }
-        if (F <= 64) return rpe ? launch_tm<2, 4, true, false>(a, s) : launch_tm<2, 4, false, false>(a, s);
-        return rpe ? launch_tm<2, 8, true, false>(a, s) : launch_tm<2, 8, false, false>(a, s);
-    }
-    auto lds_for = [&](int pb) { return ((size_t)2 * pb * a.T * (F + 4) + (size_t)pb * a.T * (a.T + 1)) * sizeof(float); };
     const bool rpe = a.Rk != nullptr;
-    const bool big = lds_for(4) > 96 * 1024;
-    VD_REQUIRE(lds_for(2) <= 150 * 1024, "head dim too large for the temporal attention tile");
-    if (a.T <= 16) {
-        if (big) return rpe ? launch_tt<2, 16, true>(a, lds_for(2), s) : launch_tt<2, 16, false>(a, lds_for(2), s);
-        return rpe ? launch_tt<4, 16, true>(a, lds_for(4), s) : launch_tt<4, 16, false>(a, lds_for(4), s);
-    }
-    if (big) return rpe ? launch_tt<2, 32, true>(a, lds_for(2), s) : launch_tt<2, 32, false>(a, lds_for(2), s);
-    return rpe ? launch_tt<4, 32, true>(a, lds_for(4), s) : launch_tt<4, 32, false>(a, lds_for(4), s);
+    const AttnTemporalVariant v = attn_temporal_variant(a.T, a.HW, a.C, a.heads, rpe);
+    VD_REQUIRE(v.family != AttnTemporalVariant::kRefused, v.why);
+    VD_REQUIRE((a.Rk == nullptr) == (a.Rq == nullptr) && (a.Rk == nullptr) == (a.Rv == nullptr), "all or no RPE terms");
+    if (v.family == AttnTemporalVariant::kLongMfma || v.family == AttnTemporalVariant::kLongGeneric) return launch_attn_temporal_long(a, s);
+    return rpe ? launch_variant<true>(v, a, s) : launch_variant<false>(v, a, s);
 }
 
 }  // namespace vd

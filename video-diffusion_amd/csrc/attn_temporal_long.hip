@@ -315,13 +315,13 @@ static int launch_long_nj(const AttnTemporalArgs& a, int nj, hipStream_t s) {
     }
 }
 
-// T in 33..kMaxWindowFrames; the caller (launch_attn_temporal) has checked the head dim and the RPE pointers.  The kernel is
-// chosen by the per-item shape alone (pixels, head dim), never by the batch: a clip alone and inside a batch get the same bits.
+// T in 33..kMaxWindowFrames; the caller (launch_attn_temporal) has checked the RPE pointers.  The kernel is the one
+// attn_temporal_variant() names: chosen by the per-item shape alone (pixels, head dim), never by the batch.
 int launch_attn_temporal_long(const AttnTemporalArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.T > 32 && a.T <= kMaxWindowFrames, "long temporal window: 33..128 frames");
-    const int F = a.C / a.heads;
     const bool rpe = a.Rk != nullptr;
-    if (a.HW % 16 == 0 && F % 16 == 0 && F <= 128) return rpe ? launch_long_nj<true>(a, F / 16, s) : launch_long_nj<false>(a, F / 16, s);
+    const AttnTemporalVariant v = attn_temporal_variant(a.T, a.HW, a.C, a.heads, rpe);
+    VD_REQUIRE(v.family == AttnTemporalVariant::kLongMfma || v.family == AttnTemporalVariant::kLongGeneric, "long temporal window: 33..128 frames");
+    if (v.family == AttnTemporalVariant::kLongMfma) return rpe ? launch_long_nj<true>(a, v.p0, s) : launch_long_nj<false>(a, v.p0, s);
     return rpe ? launch_long_generic<true>(a, s) : launch_long_generic<false>(a, s);
 }
 

@@ -2757,6 +2757,15 @@ int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, cons
     return launch_attn_temporal(a, static_cast<hipStream_t>(stream));
 }
 
+int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* name, int cap) {
+    VD_REQUIRE(name && cap > 0, "vd_attn_temporal_variant: a name buffer");
+    const AttnTemporalVariant v = attn_temporal_variant(T, HW, C, heads, rpe != 0);
+    const std::string n = attn_temporal_variant_name(v);
+    VD_REQUIRE((int)n.size() < cap, "vd_attn_temporal_variant: name buffer too small");
+    memcpy(name, n.c_str(), n.size() + 1);
+    return v.family != AttnTemporalVariant::kRefused ? 1 : 0;
+}
+
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w, const float* bias, int nfr,
                    int H, int W, int C, int Cout, float* out, void* stream) {
     return launch_out_conv(x, affA, affB, w, bias, nfr, H, W, C, Cout, out, static_cast<hipStream_t>(stream));

@@ -316,6 +316,19 @@ int launch_conv_wino(const IgemmArgs& a, hipStream_t s);
 void pack_conv3_wino(const float* oihw, float* out, int O, int I);      // out: 16*O*I floats
 int launch_attn_spatial(const AttnSpatialArgs& a, hipStream_t s);
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s);
+// Which instantiation a temporal-attention shape runs on: the ONE place the choice is made (attn_temporal.hip).  Both launchers
+// dispatch through it and vd_attn_temporal_variant() prints it, so what the tests ask for is what is launched.  A function of the
+// per-item shape alone (never of B).  p0 / p1: NT, JM (kMfma) | PB, TMAX (kValu) | NJ, - (kLongMfma) | -, - (kLongGeneric).
+struct AttnTemporalVariant {
+    enum Family { kRefused = 0, kMfma, kValu, kLongMfma, kLongGeneric };
+    Family family;
+    int p0, p1;
+    bool exact, rpe;     // exact: kMfma's EXACT
+    size_t lds;          // kValu: dynamic LDS bytes of the block
+    const char* why;     // kRefused: the requirement that failed
+};
+AttnTemporalVariant attn_temporal_variant(int T, int HW, int C, int heads, bool rpe);
+std::string attn_temporal_variant_name(const AttnTemporalVariant& v);   // e.g. "attn_temporal_mfma_kernel<1,6,true,true>"
 int launch_attn_temporal_long(const AttnTemporalArgs& a, hipStream_t s);   // 33 <= T <= kMaxWindowFrames (attn_temporal_long.hip)
 
 // GroupNorm statistics over (pixels x channels-of-group) of one frame, 32 groups, virtual concat.
