@@ -164,7 +164,7 @@ int vd_ddim_sample(vd_engine* e, int B, int T, const float* x, const float* obs_
 
 /* diffusion.ddim_reverse_sample(model, x, t, clip_denoised, model_kwargs) -> {'sample','pred_xstart'} (gaussian_diffusion.py:636-668):
  * the deterministic DDIM step run towards the noise, x_t -> x_{t+1} (eta = 0 is the only path the reference has).  One UNet
- * forward, then one fused pass of its own (ddim_reverse_kernel, beside the posterior kernel) in the reference's operation order:
+ * forward, then one fused pass (launch_sampler_pass: deterministic_kernel, beside the posterior kernel) in the reference's operation order:
  *   pred_xstart = sqrt_recip[t] x - sqrt_recipm1[t] eps   (START_X: the network output), non-finite check, clamp when clip_denoised
  *   eps'        = (sqrt_recip[t] x - pred_xstart) / sqrt_recipm1[t]
  *   sample      = pred_xstart sqrt(abn) + sqrt(1 - abn) eps',   abn = alphas_cumprod[t + 1], 0 at the last index
@@ -182,7 +182,7 @@ int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per_sample, const
 
 /* diffusion.dpmpp_2m_sample(model, x, t, prev_xstart, clip_denoised, model_kwargs) -> {'sample','pred_xstart'}: this project's
  * extension (the reference has no such sampler) -- DPM-Solver++(2M), the second-order multistep solver in its data-prediction
- * form, x_t -> x_{t-1}.  One UNet forward, then one fused pass of its own (dpmpp_2m_kernel, beside ddim_reverse_kernel):
+ * form, x_t -> x_{t-1}.  One UNet forward, then one fused pass (the same kernel template as ddim_reverse_sample):
  *   D_t    = sqrt_recip[t] x - sqrt_recipm1[t] eps   (START_X: the network output), non-finite check, clamp when clip_denoised
  *            -- what vd_ddim_sample calls pred_xstart; it is written to `pred_xstart` and is the NEXT step's prev_xstart
  *   D      = D_t + w[t] (D_t - D_prev)   with history (prev_xstart = D_prev, the D_t of the step at index t + 1);  D = D_t without
@@ -270,10 +270,10 @@ int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float*
  * is at every step (a direct p_sample caller: scripts/video_sample.py:149-166 hands x0).  Noise is always the in-kernel Philox stream (seed, offset + step*B*per + i):
  * identical to vd_p_sample(noise = NULL, seed, offset + step*B*per).
  * sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample (gaussian_diffusion.py:636-668).  Sampler 2 walks UPWARDS: t_start is
- * the first index, the captured step ends in ddim_reverse_kernel in place and t += 1, the Philox counter does not move (seed, offset
+ * the first index, the captured step ends in its sampler pass in place and t += 1, the Philox counter does not move (seed, offset
  * and eta are not read), and vd_window_run refuses a run that would pass num_timesteps - 1.  It serves observed_frames 0, 1 and 3;
  * 2 needs noise inside the graph and is refused.  The prefix cache and the suffix skip apply to it unchanged.
- * Sampler 3 is dpmpp_2m_sample (above): it walks downwards like 0 and 1, the captured step ends in dpmpp_2m_kernel in place, the
+ * Sampler 3 is dpmpp_2m_sample (above): it walks downwards like 0 and 1, the captured step ends in its sampler pass in place, the
  * history D_prev lives in an engine-owned buffer of B*T*3*H*W floats that the pass updates in place, and a device word counting the
  * window's finished steps tells the pass whether there is history -- so ONE graph serves a window's first step (first-order whatever
  * t_start is) and its later ones, and a second window on the same graph starts without history again.  No Philox draws (seed, offset

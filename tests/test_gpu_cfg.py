@@ -276,7 +276,7 @@ def test_fused_dpmpp_2m_and_ddim_reverse_steps_equal_their_denoised_fn_form_to_t
     The figures are printed before they are asserted, for the scale under test and for w = 1 (no second forward, no combine pass).
 
     Both forms must take the x_0 prediction of an epsilon-model with one rounding sequence: posterior_kernel (the denoised_fn form) forms
-    sr x - srm1 eps as two rounded products and a subtraction, and so do ddim_reverse_kernel and dpmpp_2m_kernel (xstart_from_eps)."""
+    sr x - srm1 eps as two rounded products and a subtraction, and so does deterministic_kernel, through the same head (pass_x0: xstart_from_eps)."""
     start_x = case == "predict_xstart"
     model, diff = tiny(predict_xstart=True) if start_x else tiny()
     obsf = case if case.startswith("x_") else "x_0"

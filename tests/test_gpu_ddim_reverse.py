@@ -269,7 +269,7 @@ def _eager_reverse(model, x_init, kw, n_steps, t_start=0, keep=()):
 
 
 def test_window_executor_runs_the_reverse_step_as_a_graph():
-    """sampler='ddim_reverse': the captured step is map_t -> forward -> ddim_reverse_kernel in place -> t += 1.  Step k of the window
+    """sampler='ddim_reverse': the captured step is map_t -> forward -> deterministic_kernel<SAMPLER_DDIM_REVERSE> in place -> t += 1.  Step k of the window
     is bit-equal to successive vd_ddim_reverse_sample calls for 'x_0', 'x_t' and 'x_t_minus_1' as handed; a run past the last index
     and the re-noising form are refused; the seed is not read; a p_sample window of the same shape begun afterwards gets a graph
     of its own and still equals its eager replay."""

@@ -286,7 +286,7 @@ def _eager(model, diff, x_init, kw, n_steps, t_start, keep=()):
 
 
 def test_window_executor_runs_the_step_as_a_graph():
-    """sampler='dpmpp_2m': the captured step is map_t -> forward -> dpmpp_2m_kernel in place (history in place too) -> t -= 1, steps += 1.
+    """sampler='dpmpp_2m': the captured step is map_t -> forward -> deterministic_kernel<SAMPLER_DPMPP_2M> in place (history in place too) -> t -= 1, steps += 1.
     The window is bit-equal to the eager chain: two windows of one shape on ONE graph (the second one's first step first-order again),
     a later t_start, run(k) then run(), 'x_0' / 'x_t' / 'x_t_minus_1' as handed."""
     model, diff = tiny()

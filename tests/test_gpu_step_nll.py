@@ -377,3 +377,41 @@ def test_randn_is_philox4x32_10_with_box_muller_element_by_element(seed, offset)
     nxt = randn(n, seed, offset + 1)
     assert np.array_equal(nxt[:n - 4], got[4:])
     assert np.abs(nxt[n - 4:] - R.normal_fp64(seed, offset, np.arange(n, n + 4))[0]).max() < 1e-4
+
+
+# ------------------------------------------------------------------------------------------------------------ one x_0 head
+@pytest.mark.parametrize("clip", [True, False], ids=["clip", "noclip"])
+@pytest.mark.parametrize("start_x", [False, True], ids=["eps", "predict_xstart"])
+def test_pred_xstart_is_one_bit_pattern_in_all_five_step_entries(start_x, clip):
+    """What the shared x_0 head of the sampler passes is for: on the same window, the same x and per-item t = {0, last index},
+    vd_p_mean_variance, vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample and vd_dpmpp_2m_sample (no history) return the same
+    pred_xstart, compared as int32 bit patterns -- for an epsilon model (x_0 = two rounded products and one subtraction in every pass)
+    and a predict_xstart model (the network output itself), with and without the clamp.  The forward is deterministic, so the five
+    passes read the same network output.  (The separate kernels this head replaced passed the same four cases: the test pins
+    behaviour the library had, it does not depend on the compiler's contraction default any more.)"""
+    key = ("x0_head", start_x)
+    if key not in _state:
+        cfg = dict(vda.video_model_and_diffusion_defaults(), T=6, image_size=32, num_channels=64, num_res_blocks=1, rp_alpha=6, rp_beta=6,
+                   rp_gamma=6, timestep_respacing="logsnr10", predict_xstart=start_x)
+        model, diff = vda.create_video_model_and_diffusion(**cfg)
+        model.load_state_dict(synth_sd(model.param_specs()))
+        model.to("cuda")
+        model.eval()
+        _state[key] = (model, diff)
+    model, diff = _state[key]
+    assert diff.model_mean_type.name == ("START_X" if start_x else "EPSILON") and diff.num_timesteps == 10
+    B, T = 2, 6
+    x, kw = _window(B, T, 2, seed=71)
+    kw = dict(kw, observed_frames="x_0")
+    t = torch.tensor([0, diff.num_timesteps - 1], device="cuda")
+    steps = {"p_mean_variance": diff.p_mean_variance, "p_sample": diff.p_sample, "ddim_sample": diff.ddim_sample,
+             "ddim_reverse_sample": diff.ddim_reverse_sample, "dpmpp_2m_sample": diff.dpmpp_2m_sample}
+    got = {name: f(model, x, t, clip_denoised=clip, model_kwargs=kw)["pred_xstart"] for name, f in steps.items()}
+    model.check_device_errors()
+    want = got["p_mean_variance"]
+    assert torch.isfinite(want).all() and (not clip or float(want.abs().max()) <= 1.0)
+    assert not torch.equal(want[0], want[1])
+    for name, v in got.items():
+        diffs = int((v.view(torch.int32) != want.view(torch.int32)).sum())
+        print(f"pred_xstart {name} vs p_mean_variance ({'START_X' if start_x else 'EPSILON'}, clip={clip}): {diffs} differing bit patterns")
+        assert diffs == 0, (name, diffs)

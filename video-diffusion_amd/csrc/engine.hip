@@ -344,11 +344,11 @@ struct vd_engine {
     int win_cur = -1;
     bool win_lost = false;                               // the armed window's graph was dropped (workspace growth / new schedule)
     unsigned long long win_gen = 0;                      // bumped by every vd_window_begin: a run must name the window it continues
-    long long win_left = 0;                              // steps the current window still has (t + 1)
+    long long win_left = 0;                              // steps the current window still has (t + 1; walking up: num_timesteps - t)
     long long* d_win_t = nullptr; size_t win_t_cap = 0;  // [B] current respaced index of the window
     float* d_win_xtm1 = nullptr; size_t win_xtm1_cap = 0; // 'x_t_minus_1' windows: the observed frames re-noised to t - 1, redrawn every step
     unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset, steps the armed window has done}
-    float* d_win_hist = nullptr; size_t win_hist_cap = 0; // sampler 3 (dpmpp_2m): the previous step's x_0 prediction, updated in place by the pass
+    float* d_win_hist = nullptr; size_t win_hist_cap = 0; // samplers with history (dpmpp_2m): the previous step's x_0 prediction, updated in place by the pass
 
     ~vd_engine() {
         if (d_freq_time) (void)hipFree(d_freq_time);
@@ -1840,107 +1840,136 @@ static int cfg_zero_mask(vd_engine* e, int B, int T, hipStream_t st) {
     return 0;
 }
 
-// One step on `st`: t -> t_model, UNet forward, posterior update (mode 0 p_sample, 1 ddim_sample), the DDIM encoding pass (mode 2) or the
-// DPM-Solver++(2M) pass (mode 3: `hist` = the previous step's x_0 prediction or null, `hist_on` = null or a device word that is 0 while
-// there is no history).  `t` and (when rng != null) the Philox
-// {seed, offset} are read from device memory, so the same launch sequence serves every step of a window (executor).
+// One step, as the C entries and capture_window state it.
+struct StepReq {
+    int sampler;                                     // Sampler
+    // the window tensors of one (B, T) batch, and the respaced index per item (device; the executor's moves between launches)
+    int B, T;
+    const float *x, *obs_src, *obs, *lat, *km;
+    const long long* fidx;
+    const long long* t;
+    int obs_mode, clip;
+    float eta = 0.f;
+    // the noise of p_sample / ddim_sample: explicit, or Philox at (seed, offset), or at the {seed, offset} pair in device memory (`rng`)
+    const float* noise = nullptr;
+    unsigned long long seed = 0, offset = 0;
+    const unsigned long long* rng = nullptr;
+    // dpmpp_2m_sample: the previous step's x_0 prediction or null; `hist_on` null, or a device word that is 0 while there is no history
+    const float* hist = nullptr;
+    const unsigned long long* hist_on = nullptr;
+    // outputs, each optional except where the entry says otherwise; eps_out = the (guided) network output
+    float *sample = nullptr, *xstart = nullptr, *mean = nullptr, *eps_out = nullptr;
+    const PrefixPlan* pp = nullptr;
+    const SuffixPlan* sp = nullptr;
+    // the guidance constants of this step: the engine's switches (eager entries) or a window graph's key
+    float cfg_w = 1.f, guid_phi = 0.f, dyn_p = 0.f;
+};
+
+// The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
+// unconditional forward the observed frames are padding frames whose content is whatever the window tensor holds -- neither "their
+// network input cannot change" (prefix cache) nor "their output is never read" (suffix skip) holds for them.  Dynamic thresholding
+// (`thresh`: on and clipping): its statistic runs over whole latent frames of the step.  (Guidance rescale acts only beside
+// cfg_scale != 1: the first rule refuses it.)  vd_window_begin asks this of the engine's switches, step_launches of the plans it is handed.
+static int refuse_cut_step(float cfg_w, bool thresh, bool prefix, bool suffix) {
+    for (int i = 0; i < 2; ++i) {
+        if (!(i ? suffix : prefix)) continue;
+        const std::string sw = i ? "the window suffix skip (vd_set_window_suffix_skip)" : "the window prefix cache (vd_set_window_prefix_cache)";
+        VD_REQUIRE(cfg_w == 1.f, "cfg_scale != 1 together with " + sw + " is not served");
+        VD_REQUIRE(!thresh, "dynamic_threshold (vd_set_dynamic_threshold) together with " + sw + " is not served");
+    }
+    return 0;
+}
+
+// a sampler pass on the engine's tables: what the step and the network-free entries share; the caller adds its sampler's own fields
+static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long long per, const float* x, const long long* t, int clip,
+                                 float* sample, float* xstart) {
+    SamplerPassArgs a{sampler, x, nullptr, nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
+                      sample, xstart, e->d_err};
+    a.w = e->d_w2m;
+    return a;
+}
+
+// The launches of one step on `st`: t -> t_model, UNet forward, the sampler pass.  Nothing here allocates or waits, and `t`, `rng` and
+// `hist_on` are read on the device, so the same launch sequence serves every step of a window (executor).
 // cfg_w != 1 (cfg_scale): behind the forward a second one at the same batch size with the engine's all-zero observation mask (cfg_zero_mask
 // has sized it) into the second output buffer, in the same arena, then cfg_combine_kernel in place over the first output -- which is what
-// every sampler pass below, and the caller's eps_out, then see.  Noise, t and the passes themselves do not change.
+// the sampler pass, and the caller's eps_out, then see.  Noise, t and the pass itself do not change.
 // guid_phi != 0 with cfg_w != 1 (guidance rescale): the two passes of launch_cfg_rescale stand in for the combine pass.  dyn_p != 0 with
 // clip (dynamic thresholding): launch_dynamic_threshold writes the finished x_0 into the second output buffer, and the sampler pass runs in
 // its x0_given form with clip off -- the form `denoised_fn` uses, bit-matched to the fused step.  With both at 0 the launches are the ones above.
-static int step_launches(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
-                         const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
-                         int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
-                         const unsigned long long* rng, float* sample, float* xstart, float* mean, float* eps_out,
-                         hipStream_t st, const PrefixPlan* pp = nullptr, const SuffixPlan* sp = nullptr, const float* hist = nullptr,
-                         const unsigned long long* hist_on = nullptr, float cfg_w = 1.f, float guid_phi = 0.f, float dyn_p = 0.f) {
+static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     int rc;
-    const bool rescale = cfg_w != 1.f && guid_phi != 0.f, thresh = dyn_p != 0.f && clip;
-    VD_REQUIRE(!rescale || (!pp && !sp), "guidance_rescale together with the window prefix cache or suffix skip");
-    VD_REQUIRE(!thresh || (!pp && !sp), "dynamic_threshold together with the window prefix cache or suffix skip");
-    if (cfg_w != 1.f) {
-        VD_REQUIRE(!pp && !sp, "cfg_scale != 1 together with the window prefix cache or suffix skip");
+    const int B = r.B, T = r.T;
+    const bool rescale = r.cfg_w != 1.f && r.guid_phi != 0.f, thresh = r.dyn_p != 0.f && r.clip;
+    if ((rc = refuse_cut_step(r.cfg_w, thresh, r.pp != nullptr, r.sp != nullptr))) return rc;
+    if (r.cfg_w != 1.f) {
         VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "cfg_scale != 1 together with return_attn_weights: a step makes two forwards");
         VD_REQUIRE(e->d_cfg_zero && e->cfg_zero_cap >= (size_t)B * T, "cfg_scale: zero observation mask not sized");
     }
     const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
     float* tm = e->step_tm();
-    float* eps = eps_out ? eps_out : e->step_eps(B);
-    map_t(e, t, B, tm, st);
+    float* eps = r.eps_out ? r.eps_out : e->step_eps(B);
+    map_t(e, r.t, B, tm, st);
     Arena ar = e->step_arena();
-    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
-    if ((rc = e->forward(fi, st, ar, pp, sp))) return rc;
-    if (cfg_w != 1.f) {
+    FwdIn fi{B, T, r.x, r.obs_src, r.obs, r.lat, r.km, tm, reinterpret_cast<const int64_t*>(r.fidx), r.obs_mode, eps};
+    if ((rc = e->forward(fi, st, ar, r.pp, r.sp))) return rc;
+    if (r.cfg_w != 1.f) {
         Arena au = e->step_arena();                  // the first forward's activations are dead: its output lives in the tail
         FwdIn fu = fi;
         fu.obs = e->d_cfg_zero; fu.eps = e->step_eps_u(B, T);
         if ((rc = e->forward(fu, st, au))) return rc;
         const long long n = (long long)e->out_floats(B, T);
         ProfScope ps(PC_ELEMENTWISE, 2.0 * n, rescale ? 20.0 * n : 12.0 * n, st, rescale ? "cfg_rescale" : "cfg_combine");
-        if (rescale) rc = launch_cfg_rescale(eps, fu.eps, cfg_w, lat, B, T, (long)(per / T), guid_phi, eps, nullptr, e->step_guid(B, T), st);
-        else rc = launch_cfg_combine(eps, fu.eps, cfg_w, n, eps, st);
+        if (rescale) rc = launch_cfg_rescale(eps, fu.eps, r.cfg_w, r.lat, B, T, (long)(per / T), r.guid_phi, eps, nullptr, e->step_guid(B, T), st);
+        else rc = launch_cfg_combine(eps, fu.eps, r.cfg_w, n, eps, st);
         if (rc) return rc;
     }
-    const float* x0_thr = nullptr;                   // dynamic thresholding: the finished x_0 (out_u's buffer is free by now)
-    if (thresh) {
-        const bool start_x = e->mean_type == 1;
-        DynThreshArgs da{eps, start_x ? nullptr : x, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, lat, B, T,
-                         (long)(per / T), dyn_p, e->step_eps_u(B, T), nullptr, e->d_err, e->step_guid(B, T)};
+    SamplerPassArgs pa = pass_args(e, r.sampler, B, (long long)per, r.x, r.t, r.clip, r.sample, r.xstart);
+    // what the pass reads: the network output as eps, or an x_0 prediction -- the output of a START_X model
+    // (pred_xstart = process_xstart(model_output), gaussian_diffusion.py:326-341) or the thresholded one
+    (e->mean_type == 1 ? pa.x0_given : pa.eps) = eps;
+    if (thresh) {                                    // the finished x_0 (out_u's buffer is free by now)
+        DynThreshArgs da{eps, e->mean_type == 1 ? nullptr : r.x, pa.t, e->d_tab, e->num_timesteps, r.lat, B, T,
+                         (long)(per / T), r.dyn_p, e->step_eps_u(B, T), nullptr, e->d_err, e->step_guid(B, T)};
         ProfScope ps(PC_ELEMENTWISE, 4.0 * B * per, 4.0 * B * per * 8.0, st, "dynamic_threshold");
         if ((rc = launch_dynamic_threshold(da, st))) return rc;
-        x0_thr = da.out;
-        clip = 0;
+        pa.eps = nullptr; pa.x0_given = da.out;
+        pa.clip = 0;
     }
-    // what the sampler pass reads: the network output as eps, or an x_0 prediction -- the output of a START_X model
-    // (pred_xstart = process_xstart(model_output), gaussian_diffusion.py:326-341) or the thresholded one
-    const bool given = e->mean_type == 1 || x0_thr;
-    const float* src = x0_thr ? x0_thr : eps;
-    if (mode == 2) {                                 // ddim_reverse_sample (gaussian_diffusion.py:636-668): its own pass, no noise
-        DdimReverseArgs ra{x, given ? nullptr : src, given ? src : nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab,
-                           e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
-        return launch_ddim_reverse(ra, st);
-    }
-    if (mode == 3) {                                 // dpmpp_2m_sample: its own pass, no noise
-        Dpmpp2mArgs ma{x, given ? nullptr : src, given ? src : nullptr, hist, hist_on, reinterpret_cast<const int64_t*>(t), e->d_tab,
-                       e->d_w2m, e->num_timesteps, B, (long)per, clip, sample, xstart, e->d_err};
-        return launch_dpmpp_2m(ma, st);
-    }
-    PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
-                     mode, eta, seed, offset, sample, xstart, mean, rng};
-    pa.err = e->d_err;
-    if (given) pa.x0_given = src;
+    pa.mean = r.mean; pa.eta = r.eta; pa.noise = r.noise; pa.seed = r.seed; pa.offset = r.offset; pa.dstate = r.rng;
+    pa.hist = r.hist; pa.hist_on = r.hist_on;
+    if (!sampler_draws_noise(r.sampler)) return launch_sampler_pass(pa, st);
     ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
-    return launch_posterior(pa, st);
+    return launch_sampler_pass(pa, st);
 }
 
-static int sample_impl(vd_engine* e, int mode, int B, int T, const float* x, const float* obs_src, const float* obs,
-                       const float* lat, const float* km, const long long* fidx, const long long* t, int obs_mode,
-                       int clip, float eta, const float* noise, unsigned long long seed, unsigned long long offset,
-                       float* sample, float* xstart, float* eps_out, void* stream, const float* hist = nullptr) {
-    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
+// what a step needs sized before its launches (never inside a capture): the workspace, and the zero mask of a cfg_scale step
+static int step_workspace(vd_engine* e, int B, int T, hipStream_t st) {
+    int rc = e->ensure_ws(B, T);
+    if (!rc && e->cfg_w != 1.f) rc = cfg_zero_mask(e, B, T, st);
+    return rc;
+}
+
+// An eager step under the engine's guidance switches: vd_p_sample and its siblings (the sample is wanted) and vd_p_mean_variance
+static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
+    int rc = check_sampler(e, r.B, r.T, r.obs_mode, 2, kObsModes);
     if (rc) return rc;
-    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && sample, "null tensor");
-    VD_REQUIRE(mode == 0 || eta >= 0.f, "eta");
-    VD_REQUIRE(mode != 3 || e->d_w2m, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
-    if ((rc = e->ensure_ws(B, T))) return rc;
-    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
-    return step_launches(e, mode, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, nullptr,
-                         sample, xstart, nullptr, eps_out, static_cast<hipStream_t>(stream), nullptr, nullptr, hist, nullptr, e->cfg_w,
-                         e->guid_phi, e->dyn_p);
+    VD_REQUIRE(r.x && r.obs_src && r.obs && r.lat && r.km && r.fidx && r.t && (want_sample ? r.sample != nullptr : r.mean || r.xstart || r.eps_out),
+               "null tensor");
+    VD_REQUIRE(r.sampler == SAMPLER_P || r.eta >= 0.f, "eta");
+    VD_REQUIRE(!sampler_has_history(r.sampler) || e->d_w2m, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
+    r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
+    return step_launches(e, r, st);
 }
 
 int vd_p_mean_variance(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                        const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float* mean,
                        float* xstart, float* eps, void* stream) {
-    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
-    if (rc) return rc;
-    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && (mean || xstart || eps), "null tensor");
-    if ((rc = e->ensure_ws(B, T))) return rc;
-    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, static_cast<hipStream_t>(stream)))) return rc;
-    return step_launches(e, 0, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, nullptr, nullptr,
-                         xstart, mean, eps, static_cast<hipStream_t>(stream), nullptr, nullptr, nullptr, nullptr, e->cfg_w, e->guid_phi, e->dyn_p);
+    StepReq r{SAMPLER_P, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.xstart = xstart; r.mean = mean; r.eps_out = eps;
+    return run_step(e, r, false, stream);
 }
 
 int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x_t, const float* eps, const float* noise,
@@ -2056,12 +2085,12 @@ __global__ void win_advance_kernel(long long* t, unsigned long long* rng, int B,
 
 // ---- the steps of vd_window_begin
 // the executor's device state for a window of B entries: the step counters, the Philox pair with the count of finished steps behind
-// it, for sampler 3 the history of B * per floats and, in 'x_t_minus_1' mode, the observed frames re-noised to t - 1 (per: floats of one entry)
+// it, for a sampler with history B * per floats of it and, in 'x_t_minus_1' mode, the observed frames re-noised to t - 1 (per: floats of one entry)
 static int window_buffers(vd_engine* e, int B, int obs_mode, int sampler, size_t per) {
     int rc = e->grow(e->d_win_t, e->win_t_cap, (size_t)B, true);
     if (rc) return rc;
     if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 3 * sizeof(unsigned long long)));
-    if (sampler == 3 && (rc = e->grow(e->d_win_hist, e->win_hist_cap, (size_t)B * per, true))) return rc;
+    if (sampler_has_history(sampler) && (rc = e->grow(e->d_win_hist, e->win_hist_cap, (size_t)B * per, true))) return rc;
     return obs_mode == 2 ? e->grow(e->d_win_xtm1, e->win_xtm1_cap, (size_t)B * per, true) : 0;
 }
 
@@ -2150,17 +2179,22 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     }
     VD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     rc = renoise_observed(e, k, st);
-    // sampler 3 (dpmpp_2m_sample): the pass reads the history and writes the step's x_0 prediction over it; the count of finished steps
-    // (0 on a window's first step, whatever t_start is) tells it whether the buffer holds one
-    const bool ms = k.sampler == 3;
-    if (!rc) rc = step_launches(e, k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta,
-                                nullptr, 0, 0, e->d_win_rng, k.x, ms ? e->d_win_hist : nullptr, nullptr, nullptr, st, pre_on ? &plan : nullptr,
-                                suf_on ? &splan : nullptr, ms ? e->d_win_hist : nullptr, ms ? e->d_win_rng + 2 : nullptr, k.cfg_w,
-                                k.guid_phi, k.dyn_p);
+    StepReq r{k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta};
+    r.rng = e->d_win_rng;
+    r.sample = k.x;
+    if (sampler_has_history(k.sampler)) {
+        // the pass reads the history and writes the step's x_0 prediction over it; the count of finished steps (0 on a window's first
+        // step, whatever t_start is) tells it whether the buffer holds one
+        r.hist = r.xstart = e->d_win_hist;
+        r.hist_on = e->d_win_rng + 2;
+    }
+    if (pre_on) r.pp = &plan;
+    if (suf_on) r.sp = &splan;
+    r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
+    if (!rc) rc = step_launches(e, r, st);
     if (!rc) {
-        const bool up = k.sampler == 2;                         // ddim_reverse_sample walks t upwards; it and dpmpp_2m_sample draw nothing
-        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, up ? 1LL : -1LL,
-                           up || ms ? 0ULL : (unsigned long long)B * per);
+        hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B,
+                           sampler_walks_up(k.sampler) ? 1LL : -1LL, sampler_draws_noise(k.sampler) ? (unsigned long long)B * per : 0ULL);
         if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
     }
     const hipError_t ce = hipStreamEndCapture(st, &wg.graph);
@@ -2195,26 +2229,15 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(sampler >= 0 && sampler <= 3, "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample");
-    VD_REQUIRE(sampler != 2 || obs_mode != 2, "sampler 2 (ddim_reverse_sample) draws no noise: observed_frames = 2 re-noises the observed frames to t - 1 inside "
-                                              "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
-    VD_REQUIRE(sampler != 3 || obs_mode != 2, "sampler 3 (dpmpp_2m_sample) draws no noise: observed_frames = 2 re-noises the observed frames to t - 1 inside "
-                                              "the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
-    VD_REQUIRE(sampler != 3 || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    VD_REQUIRE(sampler_valid(sampler), "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample");
+    VD_REQUIRE(sampler_draws_noise(sampler) || obs_mode != 2, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ") draws no noise: observed_frames = 2 "
+               "re-noises the observed frames to t - 1 inside the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
+    VD_REQUIRE(!sampler_has_history(sampler) || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
-    // in the unconditional forward the observed frames are padding frames whose content is whatever the window tensor holds: neither
-    // "their network input cannot change" (prefix cache) nor "their output is never read" (suffix skip) holds for them
-    VD_REQUIRE(e->cfg_w == 1.f || !e->prefix_cache_on, "cfg_scale != 1 together with the window prefix cache (vd_set_window_prefix_cache) is not served");
-    VD_REQUIRE(e->cfg_w == 1.f || !e->suffix_skip_on, "cfg_scale != 1 together with the window suffix skip (vd_set_window_suffix_skip) is not served");
-    // the statistics of both guidance options run over whole latent frames of a step the two window switches would cut short
-    VD_REQUIRE(e->guid_phi == 0.f || e->cfg_w == 1.f || !e->prefix_cache_on, "guidance_rescale != 0 (vd_set_guidance_rescale) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
-    VD_REQUIRE(e->guid_phi == 0.f || e->cfg_w == 1.f || !e->suffix_skip_on, "guidance_rescale != 0 (vd_set_guidance_rescale) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
-    VD_REQUIRE(e->dyn_p == 0.f || !clip || !e->prefix_cache_on, "dynamic_threshold (vd_set_dynamic_threshold) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
-    VD_REQUIRE(e->dyn_p == 0.f || !clip || !e->suffix_skip_on, "dynamic_threshold (vd_set_dynamic_threshold) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
-    if ((rc = e->ensure_ws(B, T))) return rc;
-    if (e->cfg_w != 1.f && (rc = cfg_zero_mask(e, B, T, st))) return rc;
+    if ((rc = step_workspace(e, B, T, st))) return rc;
     if ((rc = window_buffers(e, B, obs_mode, sampler, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
     hipLaunchKernelGGL(win_set_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, t_start, seed, offset);
     VD_HIP(hipGetLastError());
@@ -2226,7 +2249,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     e->win_cur = -1;
     e->win_lost = false;
     ++e->win_gen;
-    e->win_left = sampler == 2 ? e->num_timesteps - t_start : t_start + 1;
+    e->win_left = sampler_walks_up(sampler) ? e->num_timesteps - t_start : t_start + 1;
     // window prefix cache (opt-in): the frames whose network input cannot change during the window -- observed (obs = 1,
     // lat = 0) in 'x_0' mode with the default 'channel' conditioning (assemble_kernel: v = obs_src, indicator channels,
     // timestep 0) -- run the blocks before the first attention layer ONCE, now; the captured step runs them on the others.
@@ -2335,7 +2358,7 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream) {
     VD_REQUIRE(e, "null engine");
     VD_REQUIRE(!e->win_lost, "window graphs invalidated (workspace growth or a new schedule since vd_window_begin): begin the window again");
     VD_REQUIRE(e->win_cur >= 0, "vd_window_begin first");
-    const char* past = e->win_graphs[e->win_cur].key.sampler == 2 ? "more steps than the window has left (ddim_reverse_sample: t would pass num_timesteps - 1)"
+    const char* past = sampler_walks_up(e->win_graphs[e->win_cur].key.sampler) ? "more steps than the window has left (ddim_reverse_sample: t would pass num_timesteps - 1)"
                                                                   : "more steps than the window has left (t would pass 0)";
     VD_REQUIRE(n_steps >= 0 && n_steps <= e->win_left, past);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2349,70 +2372,76 @@ int vd_window_graphs(vd_engine* e) { return e ? (int)e->win_graphs.size() : -1; 
 int vd_p_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                 const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, const float* noise,
                 unsigned long long seed, unsigned long long offset, float* sample, float* xstart, float* eps, void* stream) {
-    return sample_impl(e, 0, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, noise, seed, offset, sample,
-                       xstart, eps, stream);
+    StepReq r{SAMPLER_P, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.noise = noise; r.seed = seed; r.offset = offset;
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
 }
 
 int vd_ddim_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                    const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float eta,
                    const float* noise, unsigned long long seed, unsigned long long offset, float* sample, float* xstart,
                    float* eps, void* stream) {
-    return sample_impl(e, 1, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta, noise, seed, offset, sample,
-                       xstart, eps, stream);
+    StepReq r{SAMPLER_DDIM, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, eta};
+    r.noise = noise; r.seed = seed; r.offset = offset;
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
 }
 
 int vd_ddim_reverse_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                            const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, float* sample,
                            float* xstart, float* eps, void* stream) {
-    return sample_impl(e, 2, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, sample, xstart, eps, stream);
+    StepReq r{SAMPLER_DDIM_REVERSE, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
 }
 
 int vd_dpmpp_2m_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                        const float* km, const long long* fidx, const long long* t, const float* prev_xstart, int obs_mode, int clip,
                        float* sample, float* xstart, float* eps, void* stream) {
-    return sample_impl(e, 3, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip, 0.f, nullptr, 0, 0, sample, xstart, eps, stream,
-                       prev_xstart);
+    StepReq r{SAMPLER_DPMPP_2M, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.hist = prev_xstart;
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
 }
 
+// ---- the sampler passes alone, on an x_0 prediction (the step through denoised_fn) or on eps: no network
 int vd_dpmpp_2m_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const float* prev_xstart,
                             const long long* t, int clip, float* sample, float* xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
-    Dpmpp2mArgs ma{x, nullptr, xstart_in, prev_xstart, nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab, e->d_w2m, e->num_timesteps,
-                   B, (long)per, clip, sample, xstart, e->d_err};
-    return launch_dpmpp_2m(ma, static_cast<hipStream_t>(stream));
+    SamplerPassArgs a = pass_args(e, SAMPLER_DPMPP_2M, B, per, x, t, clip, sample, xstart);
+    a.x0_given = xstart_in; a.hist = prev_xstart;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 
 int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const long long* t,
                                 int clip, float* sample, float* xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
-    DdimReverseArgs ra{x, nullptr, xstart_in, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
-                       sample, xstart, e->d_err};
-    return launch_ddim_reverse(ra, static_cast<hipStream_t>(stream));
+    SamplerPassArgs a = pass_args(e, SAMPLER_DDIM_REVERSE, B, per, x, t, clip, sample, xstart);
+    a.x0_given = xstart_in;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per, const float* x, const float* eps,
                         const long long* t, int clip, float eta, const float* noise, unsigned long long seed,
                         unsigned long long offset, float* sample, float* xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(x && eps && t && sample && (mode == 0 || mode == 1), "arguments");
-    PosteriorArgs pa{x, eps, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
-                     mode, eta, seed, offset, sample, xstart, nullptr, nullptr};
-    pa.err = e->d_err;
-    return launch_posterior(pa, static_cast<hipStream_t>(stream));
+    VD_REQUIRE(x && eps && t && sample && sampler_draws_noise(mode), "arguments");
+    SamplerPassArgs a = pass_args(e, mode, B, per, x, t, clip, sample, xstart);
+    a.eps = eps; a.eta = eta; a.noise = noise; a.seed = seed; a.offset = offset;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 
 int vd_posterior_from_xstart(vd_engine* e, int mode, int B, long long per, const float* x, const float* xstart_in,
                              const long long* t, int clip, float eta, const float* noise, unsigned long long seed,
                              unsigned long long offset, float* sample, float* xstart, float* mean, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(x && xstart_in && t && (sample || xstart || mean) && (mode == 0 || mode == 1), "arguments");
-    PosteriorArgs pa{x, nullptr, noise, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
-                     mode, eta, seed, offset, sample, xstart, mean, nullptr};
-    pa.x0_given = xstart_in;
-    pa.err = e->d_err;
-    return launch_posterior(pa, static_cast<hipStream_t>(stream));
+    VD_REQUIRE(x && xstart_in && t && (sample || xstart || mean) && sampler_draws_noise(mode), "arguments");
+    SamplerPassArgs a = pass_args(e, mode, B, per, x, t, clip, sample, xstart);
+    a.x0_given = xstart_in; a.mean = mean; a.eta = eta; a.noise = noise; a.seed = seed; a.offset = offset;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 
 

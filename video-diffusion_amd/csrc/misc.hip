@@ -488,41 +488,60 @@ int launch_randn(float* out, long n, unsigned long long seed, unsigned long long
     return 0;
 }
 
-// ------------------------------------------------------------------ posterior update (one fused pass)
-// p_sample (gaussian_diffusion.py:319-343,374-382,208-227,438-443) and ddim_sample (:597-634).
+// ------------------------------------------------------------------ sampler passes (the closing pass of a step, one launch)
+// The head every pass shares.  An index t outside the schedule (the reference raises IndexError in _extract_into_tensor) reads no table:
+// every non-null output of group i is poisoned.  Bit 0 of the error word is map_t_kernel's, in the entries that run the network before
+// this pass; the network-free entries poison only.
+__device__ __forceinline__ void splat(float& v, float q) { v = q; }
+__device__ __forceinline__ void splat(float4& v, float q) { v = make_float4(q, q, q, q); }
+template <class V>      // float | float4: the width group i is counted in
+__device__ __forceinline__ bool pass_t(const SamplerPassArgs& a, size_t item, size_t i, int& t) {
+    const long long tl = a.t[item];
+    if (tl >= 0 && tl < a.num_timesteps) { t = (int)tl; return true; }
+    V q;
+    splat(q, __builtin_nanf(""));
+    if (a.sample) reinterpret_cast<V*>(a.sample)[i] = q;
+    if (a.xstart) reinterpret_cast<V*>(a.xstart)[i] = q;
+    if (a.mean) reinterpret_cast<V*>(a.mean)[i] = q;
+    return false;
+}
+// The x_0 prediction: an epsilon-model's through xstart_from_eps (two products, each rounded, then one subtraction -- never a fused
+// multiply-add), or the one handed in.  The step through `denoised_fn` takes its x_0 from the p_sample pass (vd_p_mean_variance) and hands
+// it to the *_from_xstart form of another: with one head, the fused step and that form agree to the bit for denoised_fn = identity.
+// A network output that is not finite -- in the f16x3 arithmetic: an operand beyond fp16's range (|x| > 65504) anywhere in the network --
+// must not leave through the clamp as a plausible -1 (fmaxf(NaN, -1) = -1): it is left as it is and raises `nonfinite`.
+__device__ __forceinline__ float pass_x0(float x, float src, bool given, float sr, float srm1, int clip, bool& nonfinite) {
+    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
+    const bool bad = !(fabsf(x0) <= 3.4028234e38f);
+    nonfinite |= bad;
+    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
+
+// p_sample (gaussian_diffusion.py:319-343,374-382,208-227,438-443) and ddim_sample (:597-634), element by element (any per).
 // Coefficients are float32 casts of the float64 tables, exactly what _extract_into_tensor yields.
-__global__ __launch_bounds__(256) void posterior_kernel(PosteriorArgs a) {
+__global__ __launch_bounds__(256) void posterior_kernel(SamplerPassArgs a) {
     const size_t total = (size_t)a.B * a.per;
     if (a.dstate) { a.seed = a.dstate[0]; a.offset = a.dstate[1]; }
+    const int NT = a.num_timesteps;
+    const float* src = a.x0_given ? a.x0_given : a.eps;
     bool nonfinite = false;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int b = (int)(i / a.per);
-        const long long tl = a.t[b];
-        const int NT = a.num_timesteps;
-        if (tl < 0 || tl >= NT) {                // the reference raises IndexError (_extract_into_tensor); no table read here:
-            if (a.sample) a.sample[i] = __builtin_nanf("");   // the element is poisoned; bit 0 is map_t_kernel's, in the entries that run the
-                                                              // network before this pass -- vd_posterior_update / vd_posterior_from_xstart poison only
-            if (a.xstart) a.xstart[i] = __builtin_nanf("");
-            if (a.mean) a.mean[i] = __builtin_nanf("");
-            continue;
-        }
-        const int t = (int)tl;
+        int t;
+        if (!pass_t<float>(a, i / a.per, i, t)) continue;
         const float* tb = a.tab + t;
         const float x = a.x[i];
-        float x0 = a.x0_given ? a.x0_given[i] : tb[TAB_SQRT_RECIP * NT] * x - tb[TAB_SQRT_RECIPM1 * NT] * a.eps[i];
-        // A network output that is not finite -- in the f16x3 arithmetic: an operand beyond fp16's range (|x| > 65504) anywhere in the
-        // network -- must not leave through the clamp below as a plausible -1 (fmaxf(NaN, -1) = -1): it stays NaN and sets bit 1.
-        const bool bad = !(fabsf(x0) <= 3.4028234e38f);
-        nonfinite |= bad;
-        if (bad) x0 = __builtin_nanf("");        // an infinite x0 too: eps = +inf would leave pred_xstart and p_sample's sample at -inf, not at the NaN bit 1's readers are told of
-        else if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        float x0 = pass_x0(x, src[i], a.x0_given != nullptr, tb[TAB_SQRT_RECIP * NT], tb[TAB_SQRT_RECIPM1 * NT], a.clip, nonfinite);
+        // this pass alone turns an INFINITE x0 into NaN too (eps = +inf would leave pred_xstart and p_sample's sample at -inf, not at the
+        // NaN bit 1's readers are told of); the deterministic passes below hand it through as it is
+        if (!(fabsf(x0) <= 3.4028234e38f)) x0 = __builtin_nanf("");
         if (a.xstart) a.xstart[i] = x0;
         if (a.mean) a.mean[i] = tb[TAB_COEF1 * NT] * x0 + tb[TAB_COEF2 * NT] * x;
         if (!a.sample) continue;                 // p_mean_variance only
         const float z = a.noise ? a.noise[i] : normal_at(a.seed, a.offset, i);
         const float nz = t != 0 ? 1.0f : 0.0f;
         float smp;
-        if (a.mode == 0) {
+        if (a.sampler == SAMPLER_P) {
             const float mean = tb[TAB_COEF1 * NT] * x0 + tb[TAB_COEF2 * NT] * x;
             smp = mean + nz * expf(0.5f * tb[TAB_LOGVAR * NT]) * z;
         } else {
@@ -537,143 +556,81 @@ __global__ __launch_bounds__(256) void posterior_kernel(PosteriorArgs a) {
     if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);     // (never taken on a healthy step: no cost beside the compare above)
 }
 
-int launch_posterior(const PosteriorArgs& a, hipStream_t s) {
-    const size_t total = (size_t)a.B * a.per;
-    const int grid = (int)std::min<size_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(posterior_kernel, dim3(grid), dim3(256), 0, s, a);
-    VD_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------ DDIM encoding step (one fused pass)
-// ddim_reverse_sample (gaussian_diffusion.py:636-668): x_t -> x_{t+1} on the deterministic path, the reference's operation order.
-// alphas_cumprod_next[t] = append(alphas_cumprod[1:], 0.0)[t] is the TAB_ACP row at t + 1 (0 behind the last step): the float32 cast
-// is elementwise, so these are _extract_into_tensor's bits.  No noise, no Philox draws.  Four elements per thread and pass
-// (16-byte accesses; per % 4 == 0 keeps a group inside one batch item); sample may alias x: the update is elementwise.
-// The x_0 prediction of an epsilon-model as posterior_kernel forms it: two products, each rounded, then one subtraction -- NOT a fused
-// multiply-add.  The step through `denoised_fn` takes its x_0 from posterior_kernel (vd_p_mean_variance) and hands it to the *_from_xstart
-// form of the passes below: with the same rounding here, the fused step and that form agree to the bit for denoised_fn = identity.
-// (xstart_from_eps lives in vd_common.h: the dynamic-threshold pass of guidance.hip forms its x_0 with the same function.)
-__device__ __forceinline__ float ddim_reverse_one(float x, float src, bool given, float sr, float srm1, float r, float s, int clip,
-                                                  float& x0_out, bool& nonfinite) {
-    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
-    const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
-    nonfinite |= bad;
-    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+// The two samplers that draw no noise: the eta = 0 DDIM update from x_0 (or D) towards the cumulative alpha `ab`,
+// e = (sr x - D) / srm1, sample = D sqrt(ab) + sqrt(1 - ab) e.  Four elements per thread and pass (16-byte accesses; per % 4 == 0 keeps a
+// group inside one batch item); sample may alias x: the update is elementwise.
+//   ddim_reverse_sample (gaussian_diffusion.py:636-668), x_t -> x_{t+1} in the reference's operation order: ab = alphas_cumprod_next[t] =
+//     append(alphas_cumprod[1:], 0.0)[t], the TAB_ACP row at t + 1 (0 behind the last step); the float32 cast is elementwise, so these are
+//     _extract_into_tensor's bits.  D = x_0.
+//   dpmpp_2m_sample (this project's extension), x_t -> x_{t-1}: ab = TAB_ACP_PREV at t; with history D = D_t + w[t] (D_t - D_prev), else
+//     D = D_t.  At t = 0 ab = 1 and w = 0: sample = D_t, nothing infinite.  Whether there is history is DATA (a null pointer, or a device
+//     word that is 0), so one captured graph serves a window's first and later steps.  hist may alias xstart (in-place history): group i
+//     is read before it is written, by the same thread.
+template <int S>
+__device__ __forceinline__ float deterministic_one(float x, float src, bool given, float prev, bool have, float w, float sr, float srm1,
+                                                   float r, float s, int clip, float& x0_out, bool& nonfinite) {
+    const float x0 = pass_x0(x, src, given, sr, srm1, clip, nonfinite);
     x0_out = x0;
-    const float e = (sr * x - x0) / srm1;
-    return x0 * r + s * e;
-}
-
-__global__ __launch_bounds__(256) void ddim_reverse_kernel(DdimReverseArgs a) {
-    const size_t per4 = (size_t)a.per / 4, total4 = (size_t)a.B * per4;
-    const int NT = a.num_timesteps;
-    const float4* x4 = reinterpret_cast<const float4*>(a.x);
-    const float4* src4 = reinterpret_cast<const float4*>(a.x0_given ? a.x0_given : a.eps);
-    const bool given = a.x0_given != nullptr;
-    float4* sample4 = reinterpret_cast<float4*>(a.sample);
-    float4* xstart4 = reinterpret_cast<float4*>(a.xstart);
-    bool nonfinite = false;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
-        const long long tl = a.t[i / per4];
-        if (tl < 0 || tl >= NT) {                // IndexError in the reference; no table read: the item is poisoned, map_t_kernel has set the flag
-            const float q = __builtin_nanf("");
-            sample4[i] = make_float4(q, q, q, q);
-            if (xstart4) xstart4[i] = make_float4(q, q, q, q);
-            continue;
-        }
-        const int t = (int)tl;
-        const float sr = a.tab[TAB_SQRT_RECIP * NT + t], srm1 = a.tab[TAB_SQRT_RECIPM1 * NT + t];
-        const float abn = t + 1 < NT ? a.tab[TAB_ACP * NT + t + 1] : 0.0f;
-        const float r = sqrtf(abn), s = sqrtf(1.0f - abn);
-        const float4 x = x4[i], src = src4[i];
-        float4 x0, o;
-        o.x = ddim_reverse_one(x.x, src.x, given, sr, srm1, r, s, a.clip, x0.x, nonfinite);
-        o.y = ddim_reverse_one(x.y, src.y, given, sr, srm1, r, s, a.clip, x0.y, nonfinite);
-        o.z = ddim_reverse_one(x.z, src.z, given, sr, srm1, r, s, a.clip, x0.z, nonfinite);
-        o.w = ddim_reverse_one(x.w, src.w, given, sr, srm1, r, s, a.clip, x0.w, nonfinite);
-        if (xstart4) xstart4[i] = x0;
-        sample4[i] = o;
+    if constexpr (S == SAMPLER_DPMPP_2M) {
+        const float d = have ? x0 + w * (x0 - prev) : x0;
+        const float e = (sr * x - d) / srm1;
+        return d * r + s * e;
+    } else {
+        const float e = (sr * x - x0) / srm1;
+        return x0 * r + s * e;
     }
-    if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
 }
 
-int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.B > 0 && a.per > 0 && a.per % 4 == 0, "ddim_reverse_kernel: 3*H*W elements per frame, a multiple of 4");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, "ddim_reverse_kernel: null tensor");
-    VD_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.sample) && al16(a.xstart), "ddim_reverse_kernel: 16-byte aligned tensors");
-    const size_t total4 = (size_t)a.B * (a.per / 4);
-    const int grid = (int)std::min<size_t>((total4 + 255) / 256, 4096);
-    hipLaunchKernelGGL(ddim_reverse_kernel, dim3(grid), dim3(256), 0, s, a);
-    VD_HIP(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------ DPM-Solver++(2M) step (one fused pass)
-// dpmpp_2m_sample (this project's extension): D_t formed as posterior_kernel forms pred_xstart; with history D = D_t + w[t] (D_t - D_prev),
-// else D = D_t; then the eta = 0 DDIM update with D for x_0: e = (sr x - D) / srm1, sample = D sqrt(abp) + sqrt(1 - abp) e.  At t = 0
-// abp = 1 and w = 0: sample = D_t, nothing infinite.  Whether there is history is DATA (a null pointer, or a device word that is 0), so
-// one captured graph serves a window's first and later steps.  hist may alias xstart (in-place history): group i is read before it is
-// written, by the same thread.  Four elements per thread and pass as ddim_reverse_kernel; sample may alias x.
-__device__ __forceinline__ float dpmpp_2m_one(float x, float src, bool given, float prev, bool have, float w, float sr, float srm1,
-                                              float r, float s, int clip, float& x0_out, bool& nonfinite) {
-    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
-    const bool bad = !(fabsf(x0) <= 3.4028234e38f);                 // (posterior_kernel: a non-finite eps must not be clamped into range)
-    nonfinite |= bad;
-    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    x0_out = x0;
-    const float d = have ? x0 + w * (x0 - prev) : x0;
-    const float e = (sr * x - d) / srm1;
-    return d * r + s * e;
-}
-
-__global__ __launch_bounds__(256) void dpmpp_2m_kernel(Dpmpp2mArgs a) {
+template <int S>        // SAMPLER_DDIM_REVERSE | SAMPLER_DPMPP_2M
+__global__ __launch_bounds__(256) void deterministic_kernel(SamplerPassArgs a) {
     const size_t per4 = (size_t)a.per / 4, total4 = (size_t)a.B * per4;
     const int NT = a.num_timesteps;
     const float4* x4 = reinterpret_cast<const float4*>(a.x);
     const float4* src4 = reinterpret_cast<const float4*>(a.x0_given ? a.x0_given : a.eps);
     const bool given = a.x0_given != nullptr;
     const float4* hist4 = reinterpret_cast<const float4*>(a.hist);
-    const bool have = hist4 != nullptr && (a.hist_on == nullptr || *a.hist_on != 0ULL);
+    bool have = false;
+    if constexpr (S == SAMPLER_DPMPP_2M) have = hist4 != nullptr && (a.hist_on == nullptr || *a.hist_on != 0ULL);
     float4* sample4 = reinterpret_cast<float4*>(a.sample);
     float4* xstart4 = reinterpret_cast<float4*>(a.xstart);
     bool nonfinite = false;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
-        const long long tl = a.t[i / per4];
-        if (tl < 0 || tl >= NT) {                // as the sibling passes: no table read, the item is poisoned, map_t_kernel has set the flag
-            const float q = __builtin_nanf("");
-            sample4[i] = make_float4(q, q, q, q);
-            if (xstart4) xstart4[i] = make_float4(q, q, q, q);
-            continue;
-        }
-        const int t = (int)tl;
+        int t;
+        if (!pass_t<float4>(a, i / per4, i, t)) continue;
         const float sr = a.tab[TAB_SQRT_RECIP * NT + t], srm1 = a.tab[TAB_SQRT_RECIPM1 * NT + t];
-        const float abp = a.tab[TAB_ACP_PREV * NT + t], w = a.w[t];
-        const float r = sqrtf(abp), s = sqrtf(1.0f - abp);
+        float ab, w = 0.0f;
+        if constexpr (S == SAMPLER_DPMPP_2M) { ab = a.tab[TAB_ACP_PREV * NT + t]; w = a.w[t]; }
+        else ab = t + 1 < NT ? a.tab[TAB_ACP * NT + t + 1] : 0.0f;
+        const float r = sqrtf(ab), s = sqrtf(1.0f - ab);
         const float4 x = x4[i], src = src4[i];
         const float4 p = have ? hist4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
         float4 x0, o;
-        o.x = dpmpp_2m_one(x.x, src.x, given, p.x, have, w, sr, srm1, r, s, a.clip, x0.x, nonfinite);
-        o.y = dpmpp_2m_one(x.y, src.y, given, p.y, have, w, sr, srm1, r, s, a.clip, x0.y, nonfinite);
-        o.z = dpmpp_2m_one(x.z, src.z, given, p.z, have, w, sr, srm1, r, s, a.clip, x0.z, nonfinite);
-        o.w = dpmpp_2m_one(x.w, src.w, given, p.w, have, w, sr, srm1, r, s, a.clip, x0.w, nonfinite);
+        o.x = deterministic_one<S>(x.x, src.x, given, p.x, have, w, sr, srm1, r, s, a.clip, x0.x, nonfinite);
+        o.y = deterministic_one<S>(x.y, src.y, given, p.y, have, w, sr, srm1, r, s, a.clip, x0.y, nonfinite);
+        o.z = deterministic_one<S>(x.z, src.z, given, p.z, have, w, sr, srm1, r, s, a.clip, x0.z, nonfinite);
+        o.w = deterministic_one<S>(x.w, src.w, given, p.w, have, w, sr, srm1, r, s, a.clip, x0.w, nonfinite);
         if (xstart4) xstart4[i] = x0;
         sample4[i] = o;
     }
     if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
 }
 
-int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.B > 0 && a.per > 0 && a.per % 4 == 0, "dpmpp_2m_kernel: 3*H*W elements per frame, a multiple of 4");
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, "dpmpp_2m_kernel: null tensor");
-    VD_REQUIRE(a.w, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
-    VD_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.hist) && al16(a.sample) && al16(a.xstart),
-               "dpmpp_2m_kernel: 16-byte aligned tensors");
-    const size_t total4 = (size_t)a.B * (a.per / 4);
-    const int grid = (int)std::min<size_t>((total4 + 255) / 256, 4096);
-    hipLaunchKernelGGL(dpmpp_2m_kernel, dim3(grid), dim3(256), 0, s, a);
+int launch_sampler_pass(const SamplerPassArgs& a, hipStream_t s) {
+    VD_REQUIRE(sampler_valid(a.sampler), "sampler pass: sampler");
+    const bool f4 = !sampler_draws_noise(a.sampler);        // the float4 passes; posterior_kernel takes any per and any alignment
+    if (f4) {
+        const std::string k = std::string(a.sampler == SAMPLER_DPMPP_2M ? "dpmpp_2m" : "ddim_reverse") + "_kernel: ";
+        VD_REQUIRE(a.B > 0 && a.per > 0 && a.per % 4 == 0, k + "3*H*W elements per frame, a multiple of 4");
+        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+        VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, k + "null tensor");
+        VD_REQUIRE(!sampler_has_history(a.sampler) || a.w, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+        VD_REQUIRE(al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.hist) && al16(a.sample) && al16(a.xstart), k + "16-byte aligned tensors");
+    }
+    const size_t groups = (size_t)a.B * (f4 ? a.per / 4 : a.per);
+    const int grid = (int)std::min<size_t>((groups + 255) / 256, 4096);
+    if (a.sampler == SAMPLER_DDIM_REVERSE) hipLaunchKernelGGL(deterministic_kernel<SAMPLER_DDIM_REVERSE>, dim3(grid), dim3(256), 0, s, a);
+    else if (a.sampler == SAMPLER_DPMPP_2M) hipLaunchKernelGGL(deterministic_kernel<SAMPLER_DPMPP_2M>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(posterior_kernel, dim3(grid), dim3(256), 0, s, a);
     VD_HIP(hipGetLastError());
     return 0;
 }

@@ -404,62 +404,44 @@ int launch_head_gemm(const float* h, const float* affA, const float* affB, const
 // the head's second half: out_nchw[n][co][y][x] = bias[co] + sum_tap T[n][y + dy][x + dx][co * 9 + tap] (zero outside the image); T [nfr][H][W][ldt]
 int launch_out_gather(const float* T, const float* bias, int nfr, int H, int W, int ldt, int Cout, float* out_nchw, hipStream_t s);
 
-struct PosteriorArgs {
-    const float* x;      // x_t   [B][per]
-    const float* eps;    // model output
-    const float* noise;  // explicit noise or null (then Philox(seed, offset))
-    const int64_t* t;    // [B] respaced index
-    const float* tab;    // [NTAB][num_timesteps] float32 tables (gathered in f64 on host, cast like the reference)
+// The samplers of the step path.  The values are ABI (vd_window_begin's `sampler`, vd_posterior_update's `mode`).
+enum Sampler { SAMPLER_P = 0, SAMPLER_DDIM = 1, SAMPLER_DDIM_REVERSE = 2, SAMPLER_DPMPP_2M = 3 };
+inline bool sampler_valid(int s) { return s >= SAMPLER_P && s <= SAMPLER_DPMPP_2M; }
+inline bool sampler_walks_up(int s) { return s == SAMPLER_DDIM_REVERSE; }                   // t += 1 per step; the others walk down to 0
+inline bool sampler_draws_noise(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM; }      // the others read no noise and no Philox state
+inline bool sampler_has_history(int s) { return s == SAMPLER_DPMPP_2M; }                    // reads the previous step's x_0 prediction
+inline const char* sampler_name(int s) {
+    return s == SAMPLER_P ? "p_sample" : s == SAMPLER_DDIM ? "ddim_sample" : s == SAMPLER_DDIM_REVERSE ? "ddim_reverse_sample" : "dpmpp_2m_sample";
+}
+// The closing pass of a step (misc.hip: launch_sampler_pass), one argument block for every sampler.
+struct SamplerPassArgs {
+    int sampler;            // Sampler
+    const float* x;         // x_t   [B][per]
+    const float* eps;       // model output (not read when x0_given is set)
+    const float* x0_given;  // START_X models, the thresholded x_0 and the denoised_fn path: the x_0 prediction itself, or null
+    const int64_t* t;       // [B] respaced index
+    const float* tab;       // [NTAB][num_timesteps] float32 tables (gathered in f64 on host, cast like the reference)
     int num_timesteps;
-    int B; long per;
+    int B; long per;        // samplers that draw no noise: per % 4 == 0, every tensor 16-byte aligned (launch_sampler_pass checks)
     int clip;
-    int mode;            // 0: p_sample, 1: ddim
-    float eta;
-    unsigned long long seed, offset;
-    float* sample; float* xstart;   // outputs (either may be null; sample may alias x: the update is elementwise)
-    float* mean;                    // p_mean_variance's 'mean' (posterior mean of the clipped x0 prediction), or null
-    const unsigned long long* dstate;   // window executor: {seed, offset} read from device memory instead of the arguments
-    const float* x0_given = nullptr;    // denoised_fn path: the caller's x_0 prediction replaces the one derived from eps
-    int* err = nullptr;                 // the engine's sticky error word: bit 1 is set when the network output (eps, or the x_0 handed in)
-                                        // is not finite -- the clamp of clip_denoised would otherwise turn a NaN into a plausible -1 silently
+    float* sample;          // x_{t-1} (x_{t+1}: ddim_reverse); may alias x: the update is elementwise.  Null: SAMPLER_P only (p_mean_variance)
+    float* xstart;          // the x_0 prediction (dpmpp_2m: D_t, the next step's history), or null
+    int* err;               // the engine's sticky error word: bit 1 is set when the network output (eps, or the x_0 handed in) is not
+                            // finite -- the clamp of clip_denoised would otherwise turn a NaN into a plausible -1 silently
+    // ---- p_sample, ddim_sample
+    float* mean = nullptr;              // p_mean_variance's 'mean' (posterior mean of the clipped x0 prediction), or null
+    float eta = 0.f;
+    const float* noise = nullptr;       // explicit noise or null (then Philox(seed, offset))
+    unsigned long long seed = 0, offset = 0;
+    const unsigned long long* dstate = nullptr;     // window executor: {seed, offset} read from device memory instead of the arguments
+    // ---- dpmpp_2m_sample
+    const float* hist = nullptr;        // D_prev: the previous step's D_t, or null (no history).  May alias xstart: element i is read and then
+                                        // written by the same thread, which is how the window executor keeps its history in place
+    const unsigned long long* hist_on = nullptr;    // or null; a device word: 0 = this step has no history whatever `hist` holds (a window's first step)
+    const float* w = nullptr;           // [num_timesteps] extrapolation weights (vd_set_multistep_weights); w[0] = w[num_timesteps - 1] = 0
 };
 enum { VD_ERR_TIMESTEP = 1, VD_ERR_NONFINITE = 2 };
-int launch_posterior(const PosteriorArgs& a, hipStream_t s);
-// ddim_reverse_sample (gaussian_diffusion.py:636-668), its own pass beside posterior_kernel: no noise, no Philox state
-struct DdimReverseArgs {
-    const float* x;         // x_t   [B][per]
-    const float* eps;       // model output (null when x0_given is set)
-    const float* x0_given;  // START_X models and the denoised_fn path: the x_0 prediction itself, or null
-    const int64_t* t;       // [B] respaced index
-    const float* tab;
-    int num_timesteps;
-    int B; long per;        // per % 4 == 0, every tensor 16-byte aligned (launch_ddim_reverse checks)
-    int clip;
-    float* sample;          // x_{t+1}; may alias x
-    float* xstart;          // or null
-    int* err;               // as PosteriorArgs::err
-};
-int launch_ddim_reverse(const DdimReverseArgs& a, hipStream_t s);
-// dpmpp_2m_sample (this project's extension: DPM-Solver++(2M) in its data-prediction form), its own pass in the shape of the one above:
-// D_t as ddim_sample forms pred_xstart, D = D_t + w[t] (D_t - D_prev) when there is history, then the eta = 0 DDIM update with D
-struct Dpmpp2mArgs {
-    const float* x;         // x_t   [B][per]
-    const float* eps;       // model output (null when x0_given is set)
-    const float* x0_given;  // START_X models and the denoised_fn path: the x_0 prediction itself, or null
-    const float* hist;      // D_prev: the previous step's D_t, or null (no history).  May alias xstart: element i is read and then
-                            // written by the same thread, which is how the window executor keeps its history in place
-    const unsigned long long* hist_on;  // or null; a device word: 0 = this step has no history whatever `hist` holds (a window's first step)
-    const int64_t* t;       // [B] respaced index
-    const float* tab;
-    const float* w;         // [num_timesteps] extrapolation weights (vd_set_multistep_weights); w[0] = w[num_timesteps - 1] = 0
-    int num_timesteps;
-    int B; long per;        // per % 4 == 0, every tensor 16-byte aligned (launch_dpmpp_2m checks)
-    int clip;
-    float* sample;          // x_{t-1}; may alias x
-    float* xstart;          // D_t (the next step's history), or null
-    int* err;               // as PosteriorArgs::err
-};
-int launch_dpmpp_2m(const Dpmpp2mArgs& a, hipStream_t s);
+int launch_sampler_pass(const SamplerPassArgs& a, hipStream_t s);
 // cfg_scale (this project's extension: classifier-free guidance on the observed frames): out[i] = fmaf(w, out_c[i] - out_u[i], out_u[i]),
 // NaN where the difference is not finite, out_u[i] itself at w = 0.  Any n > 0; out may alias out_c or out_u; 16-byte aligned tensors take
 // the float4 path, others run element by element.  w must be finite.
@@ -495,7 +477,7 @@ struct DynThreshArgs {
     float p;                // the percentile, (0, 1]
     float* out;             // the finished x_0: latent frames clamp(x_0, -s, s) / s, other frames clamp(x_0, -1, 1); may alias src
     float* s_out;           // [B] the thresholds max(s, 1) (NaN for an item with a non-finite latent x_0), or null
-    int* err;               // as PosteriorArgs::err, or null
+    int* err;               // as SamplerPassArgs::err, or null
     void* scratch;
 };
 int launch_dynamic_threshold(const DynThreshArgs& a, hipStream_t s);

@@ -12,9 +12,9 @@ restates losses.py's normal_kl / discretized_gaussian_log_likelihood).  Gradient
 gaussian_diffusion.py:264-271,350-364) runs on the engine too: vd_guided_step = a taped forward, the loss gradient and
 a backward-data pass of the whole UNet w.r.t. its input (csrc/backward.hip); `denoised_fn` and `return_attn_weights`
 are served as well.  `ddim_reverse_sample` (gaussian_diffusion.py:636-668), the DDIM step towards the noise, is one forward plus its
-own fused pass (csrc/misc.hip: ddim_reverse_kernel); its two loops are this project's extension.  `dpmpp_2m_sample` with its two
+own fused pass (csrc/misc.hip: deterministic_kernel); its two loops are this project's extension.  `dpmpp_2m_sample` with its two
 loops is an extension as a whole: DPM-Solver++(2M), the second-order multistep sampler the reference does not have -- one forward plus
-one fused pass (dpmpp_2m_kernel) that reuses the previous step's x_0 prediction.  `cfg_scale` on the step and loop entry points is
+one fused pass (the same kernel template) that reuses the previous step's x_0 prediction.  `cfg_scale` on the step and loop entry points is
 an extension too: classifier-free guidance on the observed frames, out_u + w (out_c - out_u) with out_u the network output of the same
 call under an all-zero obs_mask -- a second forward and one fused pass (cfg_combine_kernel) in front of the unchanged sampler pass
 (include/vd_amd.h: vd_set_cfg_scale).  Two more extensions make w > 1 usable under clip_denoised, both through
@@ -283,26 +283,36 @@ class GaussianDiffusion:
                                  cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
             return out["sample"], out["pred_xstart"]
+        return self._fused_step(mode, model, x, t, clip_denoised, model_kwargs, eta=eta, noise=noise,
+                                return_attn_weights=return_attn_weights, cfg_scale=cfg_scale)
+
+    # per sampler (the engine's numbering: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample): the fused step's
+    # entry, and the network-free one that finishes a step through denoised_fn
+    _ENTRIES = {0: ("vd_p_sample", "vd_posterior_from_xstart"), 1: ("vd_ddim_sample", "vd_posterior_from_xstart"),
+                2: ("vd_ddim_reverse_sample", "vd_ddim_reverse_from_xstart"), 3: ("vd_dpmpp_2m_sample", "vd_dpmpp_2m_from_xstart")}
+
+    def _fused_step(self, mode, model, x, t, clip_denoised, model_kwargs, eta=0.0, noise=None, prev_xstart=None,
+                    return_attn_weights=None, cfg_scale=1.0):
+        """One step of sampler `mode` as one engine call -> (sample, pred_xstart), fresh tensors.  Samplers 0 and 1 read `noise`
+        (drawn from the global generator when None, even for eta = 0: gaussian_diffusion.py:438 / :628), sampler 3 its `prev_xstart`
+        or None; the others draw and read nothing.  return_attn_weights True / False sets self._last_attn (None leaves it alone)."""
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        if noise is None:
-            noise = th.randn_like(xs)                            # gaussian_diffusion.py:438 / :628 (drawn even for eta=0)
-        else:
-            noise = _f32(noise, model.device)
-        assert noise.shape == xs.shape
-        sample = th.empty_like(xs)
-        xstart = th.empty_like(xs)
+        if mode in (0, 1):
+            noise = th.randn_like(xs) if noise is None else _f32(noise, model.device)
+            assert noise.shape == xs.shape
+        prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
+        assert prev is None or prev.shape == xs.shape
+        sample, xstart = th.empty_like(xs), th.empty_like(xs)
         B, T = xs.shape[:2]
-        L = _lib.lib()
-        common = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0)
-        self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
+        window = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt))
+        flags = (kw["obs_mode"], 1 if clip_denoised else 0)
+        own = {0: (*flags, _lib.ptr(noise), 0, 0), 1: (*flags, float(eta), _lib.ptr(noise), 0, 0), 2: flags, 3: (_lib.ptr(prev), *flags)}[mode]
+        if return_attn_weights is not None:
+            self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
             with _cfg_scope(model, cfg_scale):
-                if mode == 0:
-                    rc = L.vd_p_sample(*common, _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                       _lib.current_stream())
-                else:
-                    rc = L.vd_ddim_sample(*common, float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                          _lib.current_stream())
+                rc = getattr(_lib.lib(), self._ENTRIES[mode][0])(*window, *own, _lib.ptr(sample), _lib.ptr(xstart), None,
+                                                                 _lib.current_stream())
         finally:
             if return_attn_weights:
                 model._attn_release()
@@ -354,24 +364,19 @@ class GaussianDiffusion:
         assert x0.shape == xs.shape
         tt = t.to(device=dev, dtype=th.int64).contiguous()
         out.update({"sample" if mode is not None else "mean": th.empty_like(xs), "pred_xstart": th.empty_like(xs)})
-        if mode == 2:
-            _lib.check(_lib.lib().vd_ddim_reverse_from_xstart(
-                base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
-                _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]), _lib.current_stream()))
-            return out
-        if mode == 3:
+        head = (base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0))
+        clip = 1 if clip_denoised else 0
+        if mode in (2, 3):
             prev = None if prev_xstart is None else _f32(prev_xstart, dev)
             assert prev is None or prev.shape == xs.shape
-            _lib.check(_lib.lib().vd_dpmpp_2m_from_xstart(
-                base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(prev), _lib.ptr(tt),
-                1 if clip_denoised else 0, _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]), _lib.current_stream()))
-            return out
-        if mode is not None:
-            noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
-        _lib.check(_lib.lib().vd_posterior_from_xstart(
-            base._handle, mode or 0, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0), _lib.ptr(tt), 1 if clip_denoised else 0,
-            float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(out.get("sample")), _lib.ptr(out["pred_xstart"]),
-            _lib.ptr(out["mean"] if mode is None else None), _lib.current_stream()))
+            own = (_lib.ptr(tt), clip) if mode == 2 else (_lib.ptr(prev), _lib.ptr(tt), clip)
+            args = (*head, *own, _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]))
+        else:
+            if mode is not None:
+                noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
+            args = (base._handle, mode or 0, *head[1:], _lib.ptr(tt), clip, float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(out.get("sample")),
+                    _lib.ptr(out["pred_xstart"]), _lib.ptr(out["mean"] if mode is None else None))
+        _lib.check(getattr(_lib.lib(), self._ENTRIES[mode or 0][1])(*args, _lib.current_stream()))
         return out
 
     def _variance(self, t, shape):
@@ -554,12 +559,7 @@ class GaussianDiffusion:
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        sample, xstart = th.empty_like(xs), th.empty_like(xs)
-        B, T = xs.shape[:2]
-        _lib.check(_lib.lib().vd_ddim_reverse_sample(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
-                                                     1 if clip_denoised else 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                                     _lib.current_stream()))
+        sample, xstart = self._fused_step(2, model, x, t, clip_denoised, model_kwargs)
         return {"sample": sample, "pred_xstart": xstart}
 
     def dpmpp_2m_sample(self, model, x, t, prev_xstart=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
@@ -575,14 +575,7 @@ class GaussianDiffusion:
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=3, prev_xstart=prev_xstart)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-        model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
-        assert prev is None or prev.shape == xs.shape
-        sample, xstart = th.empty_like(xs), th.empty_like(xs)
-        B, T = xs.shape[:2]
-        _lib.check(_lib.lib().vd_dpmpp_2m_sample(model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt), _lib.ptr(prev),
-                                                 kw["obs_mode"], 1 if clip_denoised else 0, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                                 _lib.current_stream()))
+        sample, xstart = self._fused_step(3, model, x, t, clip_denoised, model_kwargs, prev_xstart=prev_xstart)
         return {"sample": sample, "pred_xstart": xstart}
 
     def q_sample(self, x_start, t, noise=None, model=None):
