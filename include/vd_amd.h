@@ -384,6 +384,56 @@ int vd_op_cfg_rescale(const float* out_c, const float* out_u, float w, const flo
 int vd_op_dynamic_threshold(const float* x0, const float* lat, int B, int T, long long frame_elems, float p, float* out, float* s_out,
                             void* stream);
 
+/* Known region: pixel-mask inpainting -- this project's extension (RePaint, Lugmayr et al. 2022; the reference conditions on whole frames
+ * only).  It needs no weights of its own: after every reverse step the known pixels of the LATENT frames are overwritten with the known
+ * content noised to the level the step just reached, and a caller may walk the chain a few steps back up and down again ("resampling")
+ * so that the generated part harmonises with the known part.  No claim about sample quality is made here: that depends on the checkpoint.
+ *   known_src  [B][T][3][H][W] float32, the known content (clean, in the model's [-1, 1] space)
+ *   known_mask [B][T][H][W] float32, broadcast over the three channels; a pixel is known where the mask is != 0
+ * The merge pass (csrc/known.hip: known_merge_kernel), for a step at respaced index t[b] that produced `sample`, in place:
+ *   an element is merged iff its frame has latent_mask == 1 and its pixel is known; every other element keeps the bits of the step
+ *   (observed and padding frames are never touched);
+ *   t >= 1: sample = fmaf(sqrt_one_minus_alphas_cumprod[t-1], z, sqrt_alphas_cumprod[t-1] * known_src) = q_sample(known_src, t - 1, z)
+ *           in vd_q_sample's rounding order;   t == 0: sample = known_src, bit for bit;
+ *   z = known_noise[i] (explicit, [B][T][3][H][W]), or element i of the Philox stream (seed, offset + B*per/4), per = T*3*H*W, integer
+ *       division.  Philox layout of a step's range of B*per blocks: the sampler noise uses blocks [0, B*per/4), the merge
+ *       [B*per/4, B*per/2), the 'x_t_minus_1' re-noise of a window [B*per/2, 3*B*per/4);
+ *   a t[b] outside the schedule turns every element of item b into NaN, as the sampler pass did; the merge sets no error bit of its own.
+ * vd_set_known_region: engine state like cfg_scale; the caller's device tensors, which must stay alive and of the shape of the steps that
+ * follow; NULL known_src and known_mask clear it (both or neither); known_noise may be NULL.  vd_known_region: 1 while set, else 0.
+ * Honoured by vd_p_sample, vd_ddim_sample, vd_dpmpp_2m_sample and vd_window_begin / vd_window_run: the merge runs on `sample` right behind
+ * the sampler pass; pred_xstart and eps stay the model's own.  vd_ddim_reverse_sample (and sampler 2 in a window) fails by name while it is
+ * set: the merge noises to t - 1.  NOT honoured by vd_unet_forward, vd_p_mean_variance (it has no sample), vd_guided_step, vd_score_windows,
+ * vd_vb_terms / vd_prior_bpd and the vd_*_from_xstart / vd_posterior_update passes.  It composes with cfg_scale, guidance rescale and
+ * dynamic thresholding: they act before or inside the sampler pass, the merge behind it.
+ * In a window the two addresses are part of the graph's signature; known_noise must be NULL: the draws come from the window's own Philox
+ * pair at offset + B*per/4, and EVERY sampler's captured step then advances the counter by B*per -- sampler 3 (dpmpp_2m_sample) included,
+ * which otherwise draws nothing.  vd_window_begin fails by name while the prefix cache or the suffix skip is on together with a known
+ * region (the merge touches latent frames only, so they are compatible in principle; not built).
+ * vd_known_merge: the pass alone on frames of frame_pixels = H*W pixels (any value; the engine's image size is not read), no network, like
+ * vd_posterior_update.  Four elements per thread while frame_pixels % 4 == 0 and the tensors are 16-byte aligned, else element by element.
+ *
+ * vd_q_jump: one forward diffusion step x_{t-1} -> x_t at index t[b] (csrc/known.hip: q_jump_kernel), out = x allowed: on the frames with
+ * latent_mask == 1 (all pixels) out = fmaf(sqrt_beta[t], z, sqrt_alpha[t] * x); other frames keep their bits; z = noise[i] or element i of
+ * the Philox stream (seed, offset) -- blocks [0, B*per/4) of a range of its own; a t[b] outside the schedule gives NaN for item b.
+ * vd_set_jump_rows uploads sqrt_alpha = sqrt(1 - betas) and sqrt_beta = sqrt(betas) of the bound (respaced) schedule, float32 casts of the
+ * float64 values (1 - alpha in fp32 would lose three digits at beta = 1e-4; the VD_NTAB-row table is public layout).  The rows belong to the
+ * schedule: vd_set_schedule drops them, and a jump without them fails with a message that says so.
+ * vd_window_jump: n times on the armed window, as plain launches on `stream` (not captured): t += 1; a jump of the window tensor at the new
+ * t from the device's {seed, offset}; offset += B*per; the count of finished steps returns to 0, so a dpmpp_2m window's next step is
+ * first-order again.  It extends the window's remaining-step count by n and refuses a jump past num_timesteps - 1, sampler 2, and a window
+ * without a known region. */
+int vd_set_known_region(vd_engine* e, const float* known_src, const float* known_mask, const float* known_noise,
+                        unsigned long long seed, unsigned long long offset);
+int vd_known_region(vd_engine* e);
+int vd_known_merge(vd_engine* e, int B, int T, long long frame_pixels, float* sample, const float* known_src, const float* known_mask,
+                   const float* latent_mask, const long long* t, const float* known_noise, unsigned long long seed,
+                   unsigned long long offset, void* stream);
+int vd_set_jump_rows(vd_engine* e, int num_timesteps, const float* sqrt_alpha, const float* sqrt_beta);
+int vd_q_jump(vd_engine* e, int B, int T, long long frame_pixels, const float* x, const float* latent_mask, const long long* t,
+              const float* noise, unsigned long long seed, unsigned long long offset, float* out, void* stream);
+int vd_window_jump(vd_engine* e, int n, void* stream);
+
 /* The posterior arithmetic alone, given eps (same formulas; mode 0 p_sample, 1 ddim). */
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per_sample, const float* x, const float* eps,
                         const long long* t, int clip_denoised, float eta, const float* noise,

@@ -278,6 +278,7 @@ struct vd_engine {
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
     float* d_w2m = nullptr;           // [num_timesteps] dpmpp_2m extrapolation weights of the bound schedule (vd_set_multistep_weights), or null
+    float* d_jump = nullptr;          // [2][num_timesteps] sqrt(1 - beta) | sqrt(beta) of the bound schedule (vd_set_jump_rows), or null
     // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded), the eps scratch,
     // a second scratch of its size for the unconditional output of a cfg step (cfg_scale != 1) -- dead behind the combine pass, it then holds
     // the finished x_0 of a dynamic-threshold step -- and the scratch of the two guidance passes (guidance.hip)
@@ -307,6 +308,10 @@ struct vd_engine {
     // guidance rescale (vd_set_guidance_rescale; 0 = off; acts with cfg_w != 1) and dynamic thresholding (vd_set_dynamic_threshold; 0 = off;
     // acts with clip_denoised, whose clamp it replaces): engine state like cfg_w, part of a window graph's key
     float guid_phi = 0.f, dyn_p = 0.f;
+    // known region (vd_set_known_region; null = off): every sampling step ends in the merge pass of known.hip on its sample.  The caller's
+    // tensors; a window graph's key carries the two addresses.  known_noise / seed / offset: the draws of the eager entries.
+    const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
+    unsigned long long known_seed = 0, known_offset = 0;
     int mean_type = 0;                               // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
@@ -321,6 +326,7 @@ struct vd_engine {
         float cfg_w;                                              // cfg_scale: a graph holds one forward (1) or two and the combine pass with this weight
         float guid_phi, dyn_p;                                    // guidance rescale / dynamic threshold: the passes a graph holds and their constants
         float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
+        const float *known_src, *known_mask;                      // known region: the merge pass a graph ends in reads them (null: none)
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -366,6 +372,7 @@ struct vd_engine {
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
         if (d_win_hist) (void)hipFree(d_win_hist);
         if (d_w2m) (void)hipFree(d_w2m);
+        if (d_jump) (void)hipFree(d_jump);
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
         for (auto& g : win_graphs) g.release();
     }
@@ -1704,6 +1711,7 @@ int vd_set_schedule(vd_engine* e, int nts, const float* tab, const int* tmap, fl
     if (e->d_tab) VD_HIP(hipFree(e->d_tab));
     if (e->d_tmap) VD_HIP(hipFree(e->d_tmap));
     if (e->d_w2m) { VD_HIP(hipFree(e->d_w2m)); e->d_w2m = nullptr; }      // the multistep weights belong to the schedule that goes
+    if (e->d_jump) { VD_HIP(hipFree(e->d_jump)); e->d_jump = nullptr; }   // and so do the jump rows
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_tab), (size_t)NTAB * nts * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_tab, tab, (size_t)NTAB * nts * sizeof(float), hipMemcpyHostToDevice));
     std::vector<float> tm(nts);
@@ -1733,6 +1741,20 @@ int vd_set_multistep_weights(vd_engine* e, int nts, const float* w) {
     }
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_w2m), (size_t)nts * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_w2m, w, (size_t)nts * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The coefficients of one forward diffusion step of the bound schedule, sqrt(1 - beta) | sqrt(beta) per respaced index (include/vd_amd.h:
+// vd_q_jump).  Rows of their own for the reason the multistep weights are, and because 1 - TAB_ALPHA in fp32 loses three digits at beta = 1e-4.
+// No captured graph reads them (vd_window_jump launches plainly): nothing is dropped.
+int vd_set_jump_rows(vd_engine* e, int nts, const float* sqrt_alpha, const float* sqrt_beta) {
+    VD_REQUIRE(e && sqrt_alpha && sqrt_beta, "jump rows");
+    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(nts == e->num_timesteps, "jump rows: one entry per index of the bound schedule (" + std::to_string(e->num_timesteps) + ")");
+    if (!e->d_jump) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_jump), 2 * (size_t)nts * sizeof(float)));
+    VD_HIP(hipDeviceSynchronize());                  // a jump still in flight reads the old rows
+    VD_HIP(hipMemcpy(e->d_jump, sqrt_alpha, (size_t)nts * sizeof(float), hipMemcpyHostToDevice));
+    VD_HIP(hipMemcpy(e->d_jump + nts, sqrt_beta, (size_t)nts * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1863,6 +1885,10 @@ struct StepReq {
     const SuffixPlan* sp = nullptr;
     // the guidance constants of this step: the engine's switches (eager entries) or a window graph's key
     float cfg_w = 1.f, guid_phi = 0.f, dyn_p = 0.f;
+    // known region (null: none): the merge pass behind the sampler pass, in place on `sample`; its draws are known_noise, or Philox at
+    // (known_seed, known_offset + B*per/4), or at the pair `rng` points to
+    const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
+    unsigned long long known_seed = 0, known_offset = 0;
 };
 
 // The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
@@ -1897,6 +1923,8 @@ static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long lo
 // guid_phi != 0 with cfg_w != 1 (guidance rescale): the two passes of launch_cfg_rescale stand in for the combine pass.  dyn_p != 0 with
 // clip (dynamic thresholding): launch_dynamic_threshold writes the finished x_0 into the second output buffer, and the sampler pass runs in
 // its x0_given form with clip off -- the form `denoised_fn` uses, bit-matched to the fused step.  With both at 0 the launches are the ones above.
+// known_src (a known region; run_step and vd_window_begin refuse it for a sampler that walks up): one more pass behind the sampler pass,
+// launch_known_merge in place on the sample, drawing from the free quarter of the step's Philox range.  Null: no launch is added.
 static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     int rc;
     const int B = r.B, T = r.T;
@@ -1938,9 +1966,17 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     }
     pa.mean = r.mean; pa.eta = r.eta; pa.noise = r.noise; pa.seed = r.seed; pa.offset = r.offset; pa.dstate = r.rng;
     pa.hist = r.hist; pa.hist_on = r.hist_on;
-    if (!sampler_draws_noise(r.sampler)) return launch_sampler_pass(pa, st);
-    ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
-    return launch_sampler_pass(pa, st);
+    if (!sampler_draws_noise(r.sampler)) rc = launch_sampler_pass(pa, st);
+    else {
+        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
+        rc = launch_sampler_pass(pa, st);
+    }
+    if (rc || !r.known_src || !r.sample) return rc;
+    // known region: the known pixels of the latent frames of the sample, noised to the level the step just reached (known.hip)
+    KnownMergeArgs ka{r.sample, r.known_src, r.known_mask, r.lat, pa.t, e->d_tab, e->num_timesteps, B, T, (long)(per / T / 3)};
+    ka.noise = r.known_noise; ka.seed = r.known_seed; ka.offset = r.known_offset; ka.dstate = r.rng;
+    ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 3.0, st, "known_merge");
+    return launch_known_merge(ka, st);
 }
 
 // what a step needs sized before its launches (never inside a capture): the workspace, and the zero mask of a cfg_scale step
@@ -1961,6 +1997,11 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
     r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
+    if (want_sample && e->known_src) {
+        VD_REQUIRE(!sampler_walks_up(r.sampler), std::string(sampler_name(r.sampler)) + " together with a known region (vd_set_known_region) is not served: the merge noises to t - 1");
+        r.known_src = e->known_src; r.known_mask = e->known_mask; r.known_noise = e->known_noise;
+        r.known_seed = e->known_seed; r.known_offset = e->known_offset;
+    }
     return step_launches(e, r, st);
 }
 
@@ -2191,10 +2232,12 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     if (pre_on) r.pp = &plan;
     if (suf_on) r.sp = &splan;
     r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
+    r.known_src = k.known_src; r.known_mask = k.known_mask;      // the merge draws from the window's own Philox pair (r.rng)
     if (!rc) rc = step_launches(e, r, st);
     if (!rc) {
+        // a step with a merge pass consumes its range whatever the sampler: the merge's quarter of it is drawn from
         hipLaunchKernelGGL(win_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B,
-                           sampler_walks_up(k.sampler) ? 1LL : -1LL, sampler_draws_noise(k.sampler) ? (unsigned long long)B * per : 0ULL);
+                           sampler_walks_up(k.sampler) ? 1LL : -1LL, sampler_draws_noise(k.sampler) || k.known_src ? (unsigned long long)B * per : 0ULL);
         if (hipGetLastError() != hipSuccess) { set_error("win_advance_kernel launch"); rc = -2; }
     }
     const hipError_t ce = hipStreamEndCapture(st, &wg.graph);
@@ -2235,6 +2278,12 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     VD_REQUIRE(!sampler_has_history(sampler) || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
+    if (e->known_src) {
+        VD_REQUIRE(!sampler_walks_up(sampler), "sampler 2 (ddim_reverse_sample) together with a known region (vd_set_known_region) is not served: the merge noises to t - 1");
+        VD_REQUIRE(!e->known_noise, "a window draws the known region's noise from its own Philox stream: known_noise must be NULL (vd_set_known_region)");
+        VD_REQUIRE(!e->prefix_cache_on, "a known region (vd_set_known_region) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+        VD_REQUIRE(!e->suffix_skip_on, "a known region (vd_set_known_region) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = step_workspace(e, B, T, st))) return rc;
@@ -2246,6 +2295,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.eta = eta; key.cfg_w = e->cfg_w;
     key.guid_phi = e->guid_phi; key.dyn_p = e->dyn_p;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
+    key.known_src = e->known_src; key.known_mask = e->known_mask;
     e->win_cur = -1;
     e->win_lost = false;
     ++e->win_gen;
@@ -2368,6 +2418,74 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream) {
 }
 
 int vd_window_graphs(vd_engine* e) { return e ? (int)e->win_graphs.size() : -1; }
+
+// ---- known region (pixel-mask inpainting): engine state like cfg_scale; a window graph's key carries the two addresses
+int vd_set_known_region(vd_engine* e, const float* known_src, const float* known_mask, const float* known_noise, unsigned long long seed,
+                        unsigned long long offset) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE((known_src == nullptr) == (known_mask == nullptr), "known region: known_src and known_mask are set together, or both NULL (clear)");
+    VD_REQUIRE(known_src || !known_noise, "known region: known_noise without a region");
+    e->known_src = known_src; e->known_mask = known_mask; e->known_noise = known_noise;
+    e->known_seed = seed; e->known_offset = offset;
+    return 0;
+}
+
+int vd_known_region(vd_engine* e) { return e && e->known_src ? 1 : 0; }
+
+int vd_known_merge(vd_engine* e, int B, int T, long long frame_pixels, float* sample, const float* known_src, const float* known_mask,
+                   const float* lat, const long long* t, const float* known_noise, unsigned long long seed, unsigned long long offset,
+                   void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    KnownMergeArgs a{sample, known_src, known_mask, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)frame_pixels};
+    a.noise = known_noise; a.seed = seed; a.offset = offset;
+    return launch_known_merge(a, static_cast<hipStream_t>(stream));
+}
+
+static const char* const kNoJumpRows = "q_jump: no jump rows for the bound schedule (vd_set_jump_rows, after vd_set_schedule)";
+
+int vd_q_jump(vd_engine* e, int B, int T, long long frame_pixels, const float* x, const float* lat, const long long* t, const float* noise,
+              unsigned long long seed, unsigned long long offset, float* out, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(e->d_jump, kNoJumpRows);
+    QJumpArgs a{x, out, lat, reinterpret_cast<const int64_t*>(t), e->d_jump, e->num_timesteps, B, T, (long)frame_pixels};
+    a.noise = noise; a.seed = seed; a.offset = offset;
+    return launch_q_jump(a, static_cast<hipStream_t>(stream));
+}
+
+// t += dt; the Philox counter moves on by `draws`; the count of finished steps returns to 0 (a dpmpp_2m window has no history behind a jump)
+__global__ void win_jump_kernel(long long* t, unsigned long long* rng, int B, long long dt, unsigned long long draws) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) t[b] += dt;
+    if (b == 0) { rng[1] += draws; rng[2] = 0; }
+}
+
+// n forward jumps of the armed window as plain launches (the resampling walk of RePaint revisits a level a few times per window: not worth a
+// graph): t += 1, the jump at the new t from the device's Philox pair, offset += B*per
+int vd_window_jump(vd_engine* e, int n, void* stream) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(!e->win_lost, "window graphs invalidated (workspace growth or a new schedule since vd_window_begin): begin the window again");
+    VD_REQUIRE(e->win_cur >= 0, "vd_window_begin first");
+    const vd_engine::WinKey& k = e->win_graphs[e->win_cur].key;
+    VD_REQUIRE(!sampler_walks_up(k.sampler), "vd_window_jump: sampler 2 (ddim_reverse_sample) walks upwards by itself");
+    VD_REQUIRE(k.known_src, "vd_window_jump: the armed window has no known region (vd_set_known_region before vd_window_begin)");
+    VD_REQUIRE(e->d_jump, kNoJumpRows);
+    VD_REQUIRE(n >= 0 && e->win_left + n <= e->num_timesteps, "vd_window_jump: t would pass num_timesteps - 1");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t per = (size_t)k.T * 3 * e->cfg.image_size * e->cfg.image_size;
+    for (int i = 0; i < n; ++i) {
+        hipLaunchKernelGGL(win_jump_kernel, dim3((k.B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, k.B, 1LL, 0ULL);
+        VD_HIP(hipGetLastError());
+        QJumpArgs a{k.x, k.x, k.lat, reinterpret_cast<const int64_t*>(e->d_win_t), e->d_jump, e->num_timesteps, k.B, k.T,
+                    (long)e->cfg.image_size * e->cfg.image_size};
+        a.dstate = e->d_win_rng;
+        int rc = launch_q_jump(a, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(win_jump_kernel, dim3((k.B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, k.B, 0LL, (unsigned long long)k.B * per);
+        VD_HIP(hipGetLastError());
+        ++e->win_left;
+    }
+    return 0;
+}
 
 int vd_p_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
                 const float* km, const long long* fidx, const long long* t, int obs_mode, int clip, const float* noise,

@@ -446,35 +446,7 @@ int launch_out_gather(const float* T, const float* bias, int nfr, int H, int W, 
     return 0;
 }
 
-// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller
-__device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long key, unsigned (&o)[4]) {
-    unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0x5eed5eedu, c3 = 0;
-    unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
-// element i -> standard normal; elements 4j..4j+3 share one Philox block
-__device__ __forceinline__ float normal_at(unsigned long long seed, unsigned long long offset, unsigned long long i) {
-    unsigned r[4];
-    philox4x32_10(offset + (i >> 2), seed, r);
-    const int pair = (int)(i & 2);
-    const float u1 = ((float)r[pair] + 1.0f) * 2.3283064365386963e-10f;       // (0,1]
-    const float u2 = (float)r[pair + 1] * 2.3283064365386963e-10f;
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    return (i & 1) ? rad * sn : rad * cs;
-}
-
+// ------------------------------------------------------------------ Philox4x32-10 + Box-Muller (vd_common.h: philox4x32_10, normal_at, normal4_at)
 __global__ __launch_bounds__(256) void randn_kernel(float* out, size_t n, unsigned long long seed,
                                                     unsigned long long offset) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
@@ -803,24 +775,6 @@ int launch_vb_terms(const VbArgs& a, hipStream_t s) {
 // The search ranks candidates by calc_bpd_loop_subsampled's `mse` alone (gaussian_diffusion.py:975-990): the KL / decoder-NLL
 // terms of vb_terms_kernel are never read, and only latent frames count.  Noise is item b's own Philox stream
 // (seed, item_offset[b]) -- element j is what vd_randn(out, per, seed, item_offset[b]) writes at j -- so x_t needs no noise tensor.
-
-// the four normals of Philox block q: elements 4q .. 4q+3 of normal_at, bit for bit
-__device__ __forceinline__ f32x4 normal4_at(unsigned long long seed, unsigned long long offset, unsigned long long q) {
-    unsigned r[4];
-    philox4x32_10(offset + q, seed, r);
-    f32x4 z;
-#pragma unroll
-    for (int pair = 0; pair < 4; pair += 2) {
-        const float u1 = ((float)r[pair] + 1.0f) * 2.3283064365386963e-10f;
-        const float u2 = (float)r[pair + 1] * 2.3283064365386963e-10f;
-        const float rad = sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        z[pair] = rad * cs;
-        z[pair + 1] = rad * sn;
-    }
-    return z;
-}
 
 // x_t = q_sample(x_start, t[b], noise) with q_sample_kernel's rounding; a thread = one quad of one item (per % 4 == 0)
 __global__ __launch_bounds__(256) void score_q_sample_kernel(ScoreArgs a, float* __restrict__ out) {

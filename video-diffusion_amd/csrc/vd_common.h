@@ -487,8 +487,88 @@ int launch_randn(float* out, long n, unsigned long long seed, unsigned long long
 int launch_q_sample_prev(const float* x0, const int64_t* t, const float* tab, int num_timesteps, int B, long per, const unsigned long long* dstate,
                          unsigned long long draw_offset, float* out, hipStream_t s);
 
+// Pixel-mask inpainting (known.hip; this project's extension, RePaint: Lugmayr et al. 2022).  Tensors are [B][T][3][hw] (the mask
+// [B][T][hw], broadcast over the channels), `lat` the [B*T] latent mask.
+// The merge, the closing pass of a step in place on `sample`: an element whose frame has lat == 1 and whose pixel has mask != 0 becomes
+// q_sample(known_src, t - 1, z) in q_sample_kernel's rounding order (known_src itself at t == 0); every other element keeps its bits.
+// z: noise[i], or normal_at(seed, offset + B*per/4, i) with per = T*3*hw -- the free quarter of a step's Philox range -- the pair read
+// from `dstate` when given.  A t[b] outside the schedule: NaN for every element of item b; no error bit (the sampler pass set it).
+// Four elements per thread while hw % 4 == 0 and the tensors are 16-byte aligned, else element by element: same bits.
+struct KnownMergeArgs {
+    float* sample;
+    const float* known_src; const float* known_mask; const float* lat;
+    const int64_t* t;       // [B] respaced index of the step that produced `sample`
+    const float* tab; int num_timesteps;
+    int B, T; long hw;
+    const float* noise = nullptr;
+    unsigned long long seed = 0, offset = 0;
+    const unsigned long long* dstate = nullptr;
+};
+int launch_known_merge(const KnownMergeArgs& a, hipStream_t s);
+// One forward diffusion step x_{t-1} -> x_t at index t[b] on the frames with lat == 1: out = fmaf(sqrt_beta[t], z, sqrt_alpha[t] * x);
+// other frames out = x (in place: untouched).  rows: [2][num_timesteps] = sqrt(1 - beta) | sqrt(beta), float32 casts of the float64 values
+// (1 - alpha is never formed in fp32).  z: noise[i] or normal_at(seed, offset, i), the pair from `dstate` when given.  Bad t[b]: NaN for item b.
+struct QJumpArgs {
+    const float* x; float* out;        // out may be x
+    const float* lat;
+    const int64_t* t;
+    const float* rows; int num_timesteps;
+    int B, T; long hw;
+    const float* noise = nullptr;
+    unsigned long long seed = 0, offset = 0;
+    const unsigned long long* dstate = nullptr;
+};
+int launch_q_jump(const QJumpArgs& a, hipStream_t s);
+
 enum { TAB_SQRT_RECIP = 0, TAB_SQRT_RECIPM1, TAB_COEF1, TAB_COEF2, TAB_LOGVAR, TAB_ACP, TAB_ACP_PREV,
        TAB_SQRT_ACP, TAB_SQRT_1M_ACP, TAB_POST_LOGVAR, TAB_LOG_1M_ACP, TAB_ALPHA, NTAB };
+
+// ---- Philox4x32-10 + Box-Muller: the counter-based generator every source that draws noise shares bit for bit (misc.hip, known.hip)
+__device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long key, unsigned (&o)[4]) {
+    unsigned c0 = (unsigned)ctr, c1 = (unsigned)(ctr >> 32), c2 = 0x5eed5eedu, c3 = 0;
+    unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// element i -> standard normal; elements 4j..4j+3 share one Philox block
+__device__ __forceinline__ float normal_at(unsigned long long seed, unsigned long long offset, unsigned long long i) {
+    unsigned r[4];
+    philox4x32_10(offset + (i >> 2), seed, r);
+    const int pair = (int)(i & 2);
+    const float u1 = ((float)r[pair] + 1.0f) * 2.3283064365386963e-10f;       // (0,1]
+    const float u2 = (float)r[pair + 1] * 2.3283064365386963e-10f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    return (i & 1) ? rad * sn : rad * cs;
+}
+
+// the four normals of Philox block q: elements 4q .. 4q+3 of normal_at, bit for bit
+__device__ __forceinline__ f32x4 normal4_at(unsigned long long seed, unsigned long long offset, unsigned long long q) {
+    unsigned r[4];
+    philox4x32_10(offset + q, seed, r);
+    f32x4 z;
+#pragma unroll
+    for (int pair = 0; pair < 4; pair += 2) {
+        const float u1 = ((float)r[pair] + 1.0f) * 2.3283064365386963e-10f;
+        const float u2 = (float)r[pair + 1] * 2.3283064365386963e-10f;
+        const float rad = sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.283185307179586f * u2, &sn, &cs);
+        z[pair] = rad * cs;
+        z[pair + 1] = rad * sn;
+    }
+    return z;
+}
 
 // ---- backward-data pieces of `use_gradient_method` (backward.hip)
 struct GnBwdArgs {

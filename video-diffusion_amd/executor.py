@@ -17,6 +17,10 @@ callers in the reference and they differ: `p_sample_loop` re-noises the clean ob
 while scripts/video_sample.py:149-166 calls `p_sample` directly with `x_t_minus_1 = x0`, a clean placeholder that is read as it
 is at every step -- `renoise=False`, what `infer_video` passes, so that its graph and eager executors sample the same
 conditional distribution.
+
+Pixel-mask inpainting (this project's extension, RePaint): `begin(..., known_src=, known_mask=)` captures a step that ends in the merge pass
+on the window tensor, `jump(n)` walks the armed window n forward diffusion steps back up (plain launches), and `run_repaint(j, r)` is the
+walk of `respace.repaint_schedule` over both; all noise stays on the window's Philox stream (include/vd_amd.h: vd_set_known_region).
 """
 import math
 
@@ -60,8 +64,17 @@ class WindowExecutor:
                                    kinda_marg_mask=f(B * T), frame_indices=th.zeros(B, T, dtype=th.int64, device=dev))
         return self._bufs[key]
 
+    def _known_buffers(self, B, T):
+        """The window's known region, one pair per (B, T) like the window tensors: stable addresses, so one graph per shape."""
+        bufs = self._buffers(B, T)
+        if "known_src" not in bufs:
+            S = self.model.image_size
+            bufs["known_src"] = th.zeros(B, T, 3, S, S, dtype=th.float32, device=self.model.device)
+            bufs["known_mask"] = th.zeros(B, T, S, S, dtype=th.float32, device=self.model.device)
+        return bufs["known_src"], bufs["known_mask"]
+
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
-              cfg_scale=1.0):
+              known_src=None, known_mask=None, cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -76,7 +89,11 @@ class WindowExecutor:
         forward the observed frames are padding frames whose content is whatever the window tensor holds.
         Guidance rescale and dynamic thresholding are not parameters: a begin() inside `diffusion.guidance_scope(...)` captures (or finds)
         the graph of the scope's values -- they are part of the signature like the weight -- and run() may be called outside the scope.
-        The engine refuses either of them together with prefix_cache or suffix_skip."""
+        The engine refuses either of them together with prefix_cache or suffix_skip.
+        known_src, known_mask (this project's extension; gaussian_diffusion.py: known_region_scope): pixel-mask inpainting -- both are
+        copied into buffers of this object, the captured step ends in the merge pass, and the merge's noise comes from the window's own
+        Philox stream (the step's range at + B*per/4; every sampler's step then advances the counter by B*per).  Without them, a begin()
+        inside `diffusion.known_region_scope(...)` takes the scope's region.  Not served with 'ddim_reverse', prefix_cache or suffix_skip."""
         cfg_scale = float(cfg_scale)
         if not math.isfinite(cfg_scale):
             raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
@@ -84,6 +101,20 @@ class WindowExecutor:
             raise NotImplementedError("prefix_cache together with cfg_scale != 1")
         if cfg_scale != 1.0 and self.suffix_skip:
             raise NotImplementedError("suffix_skip together with cfg_scale != 1")
+        from .gaussian_diffusion import _engine_region, _known, check_known_region
+        if (known_src is None) != (known_mask is None):
+            raise ValueError("known_src and known_mask are given together")
+        scope = _known(self.model)
+        if known_src is not None:
+            known_src, known_mask = check_known_region(known_src, known_mask)
+        elif scope is not None:
+            known_src, known_mask = scope["src"], scope["mask"]
+        if known_src is not None:
+            if tuple(known_src.shape) != tuple(x_init.shape):
+                raise ValueError(f"known_src {tuple(known_src.shape)} against a window of {tuple(x_init.shape)}")
+            for name, on in (("prefix_cache", self.prefix_cache), ("suffix_skip", self.suffix_skip), ("sampler='ddim_reverse'", sampler == "ddim_reverse")):
+                if on:
+                    raise NotImplementedError(f"{name} together with a known region")
         if self.prefix_cache or self.suffix_skip:                 # the guidance options of an enclosing guidance_scope (engine state)
             L, h = _lib.lib(), self.model._handle
             which = "prefix_cache" if self.prefix_cache else "suffix_skip"
@@ -110,6 +141,15 @@ class WindowExecutor:
                 if v.is_cuda:
                     v.record_stream(self.stream)
             bufs["x"].copy_(x_init)
+            region = None
+            if known_src is not None:
+                ks, km = self._known_buffers(B, T)
+                for v in (known_src, known_mask):
+                    if v.is_cuda:
+                        v.record_stream(self.stream)
+                ks.copy_(known_src)
+                km.copy_(known_mask)
+                region = dict(src=ks, mask=km)
             for k in ("obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"):
                 bufs[k].copy_(kw[k].view(bufs[k].shape))
             if mode == "x_0":
@@ -129,6 +169,9 @@ class WindowExecutor:
             # the scale is engine state for the length of this call only: the captured graph keeps the weight, run() needs none
             if cfg_scale != 1.0:
                 _lib.check(_lib.lib().vd_set_cfg_scale(self.model._handle, cfg_scale))
+            # ... and so is the region: the graph's signature keeps the two buffer addresses
+            if region is not None or scope is not None:
+                _engine_region(self.model, region)
             try:
                 rc = _lib.lib().vd_window_begin(
                     self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
@@ -136,6 +179,8 @@ class WindowExecutor:
                     3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
                     int(t_start), self.stream.cuda_stream)
             finally:
+                if region is not None or scope is not None:
+                    _engine_region(self.model, scope)
                 if cfg_scale != 1.0:
                     _lib.check(_lib.lib().vd_set_cfg_scale(self.model._handle, 1.0))
             _lib.check(rc)
@@ -150,18 +195,51 @@ class WindowExecutor:
         window tensor (updated in place)."""
         if n_steps is None:
             n_steps = self._left
-        # the step counters are one set per engine: refuse to continue a window another executor has re-armed since
-        if getattr(self, "_gen", None) != int(_lib.lib().vd_window_generation(self.model._handle)):
-            raise RuntimeError("WindowExecutor.run: another window was begun on this model since this executor's begin(); "
-                               "begin() again")
+        self._check_gen("run")
         _lib.check(_lib.lib().vd_window_run(self.model._handle, int(n_steps), self.stream.cuda_stream))
         self._left -= int(n_steps)
         th.cuda.current_stream(self.model.device).wait_stream(self.stream)
         return self.x
 
-    def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, cfg_scale=1.0):
-        """All num_timesteps steps of one window; returns a fresh tensor."""
-        self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale)
+    def _check_gen(self, what):
+        # the step counters are one set per engine: refuse to continue a window another executor has re-armed since
+        if getattr(self, "_gen", None) != int(_lib.lib().vd_window_generation(self.model._handle)):
+            raise RuntimeError(f"WindowExecutor.{what}: another window was begun on this model since this executor's begin(); "
+                               "begin() again")
+
+    def jump(self, n=1):
+        """n forward diffusion steps of the armed window (a window with a known region only): t += 1 and q_jump at the new t, n times,
+        noise from the window's Philox stream (a range of B*per each); a 'dpmpp_2m' window's next step is first-order again.  Returns
+        the window tensor (updated in place)."""
+        self._check_gen("jump")
+        _lib.check(_lib.lib().vd_window_jump(self.model._handle, int(n), self.stream.cuda_stream))
+        self._left += int(n)
+        th.cuda.current_stream(self.model.device).wait_stream(self.stream)
+        return self.x
+
+    def run_repaint(self, jump_length=1, n_resample=1):
+        """The walk of respace.repaint_schedule from the armed window's current index down to 0: runs of steps as graph replays, runs of
+        jumps through jump().  Returns the window tensor."""
+        from .respace import repaint_schedule
+        if self._left < 1:
+            raise RuntimeError("WindowExecutor.run_repaint: the window has no step left")
+        ops = repaint_schedule(self._left - 1, jump_length, n_resample)
+        k = 0
+        while k < len(ops):
+            n = 1
+            while k + n < len(ops) and ops[k + n][0] == ops[k][0]:
+                n += 1
+            (self.run if ops[k][0] == "step" else self.jump)(n)
+            k += n
+        return self.x
+
+    def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, known_src=None, known_mask=None,
+                      jump_length=1, n_resample=1, cfg_scale=1.0):
+        """All num_timesteps steps of one window (with a known region and n_resample > 1: the walk of run_repaint); returns a fresh tensor."""
+        self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale, known_src=known_src,
+                   known_mask=known_mask)
+        if int(n_resample) != 1:
+            return self.run_repaint(jump_length, n_resample).clone()
         return self.run(self.diffusion.num_timesteps).clone()
 
     @property

@@ -20,7 +20,10 @@ call under an all-zero obs_mask -- a second forward and one fused pass (cfg_comb
 (include/vd_amd.h: vd_set_cfg_scale).  Two more extensions make w > 1 usable under clip_denoised, both through
 `GaussianDiffusion.guidance_scope`: guidance rescale (the guided output's spread over the latent frames brought back towards the
 conditional one's) and dynamic thresholding (a per-item percentile of |x_0| over the latent frames in place of the clamp's 1); their
-per-item statistics are taken on the device inside the step (csrc/guidance.hip).  Training losses are out of scope.
+per-item statistics are taken on the device inside the step (csrc/guidance.hip).  Pixel-mask inpainting is an extension as well
+(RePaint): inside `GaussianDiffusion.known_region_scope` every p_sample / ddim_sample / dpmpp_2m_sample step ends in one more fused pass
+that overwrites the known pixels of the latent frames with the known content noised to the level just reached (csrc/known.hip), `q_jump`
+is the forward step of its resampling walk and `repaint_sample_loop` the loop around both.  Training losses are out of scope.
 """
 import contextlib
 import enum
@@ -137,6 +140,42 @@ def _guidance_scope(model, phi, p):
         _lib.check(L.vd_set_dynamic_threshold(model._handle, before[1]))
 
 
+def check_known_region(known_src, known_mask):
+    """The shape and value checks of a known region (no engine): known_src (B, T, 3, H, W); known_mask (B, T, 1, H, W) or (B, T, H, W),
+    bool, uint8 or float with every value in {0, 1} (soft masks are out of scope).  Returns (src float32 (B, T, 3, H, W), mask float32
+    (B, T, H, W)), both contiguous, on the devices they came on."""
+    if not (th.is_tensor(known_src) and known_src.dim() == 5 and known_src.shape[2] == 3):
+        raise ValueError(f"known_src must be a (B, T, 3, H, W) tensor, got {tuple(getattr(known_src, 'shape', ()))}")
+    B, T, _, H, W = known_src.shape
+    if not th.is_tensor(known_mask) or tuple(known_mask.shape) not in ((B, T, 1, H, W), (B, T, H, W)):
+        raise ValueError(f"known_mask must be {(B, T, 1, H, W)} or {(B, T, H, W)} for a known_src of {tuple(known_src.shape)}, got "
+                         f"{tuple(getattr(known_mask, 'shape', ()))}")
+    if not (known_mask.dtype in (th.bool, th.uint8) or known_mask.dtype.is_floating_point):
+        raise ValueError(f"known_mask must be bool, uint8 or float, got {known_mask.dtype}")
+    m = known_mask.reshape(B, T, H, W).to(th.float32)
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise ValueError("known_mask must hold the values 0 and 1 only (1 = known): soft masks are not served")
+    return known_src.to(th.float32).contiguous(), m.contiguous()
+
+
+def _known(model):
+    """The known region the innermost known_region_scope set on this model, or None."""
+    return getattr(getattr(model, "model", model), "_known_region", None)
+
+
+def _engine_region(model, region, noise=None):
+    """Engine state <- a region dict (src, mask; device tensors the caller keeps alive) or None (clear)."""
+    if region is None:
+        _lib.check(_lib.lib().vd_set_known_region(model._handle, None, None, None, 0, 0))
+    else:
+        _lib.check(_lib.lib().vd_set_known_region(model._handle, _lib.ptr(region["src"]), _lib.ptr(region["mask"]), _lib.ptr(noise), 0, 0))
+
+
+def _refuse_known(model, what):
+    if _known(model) is not None:
+        raise NotImplementedError(f"{what} inside known_region_scope is not served")
+
+
 class GaussianDiffusion:
     """gaussian_diffusion.py:107-172 (tables) + the sampling methods."""
 
@@ -206,6 +245,11 @@ class GaussianDiffusion:
         w[1:-1] = 0.5 * (lam[:-2] - lam[1:-1]) / (lam[1:-1] - lam[2:])
         return w
 
+    def _jump_rows(self):
+        """q_jump's coefficients, float64: sqrt(1 - betas) and sqrt(betas) of this (respaced) schedule.  Rows of their own: the float32
+        1 - alpha would lose three digits of beta = 1e-4."""
+        return np.sqrt(1.0 - self.betas), np.sqrt(self.betas)
+
     def _bind(self, model):
         """Upload this process' tables into the model's engine (once per (diffusion, model) pair)."""
         model = getattr(model, "model", model)            # accept a _WrappedModel
@@ -218,6 +262,8 @@ class GaussianDiffusion:
             _lib.check(_lib.lib().vd_set_model_mean_type(model._handle, 1 if self.model_mean_type == ModelMeanType.START_X else 0))
             w = np.ascontiguousarray(self._multistep_weights().astype(np.float32))       # cast elementwise, as the table's rows
             _lib.check(_lib.lib().vd_set_multistep_weights(model._handle, self.num_timesteps, _lib.ptr(w)))
+            sa, sb = (np.ascontiguousarray(r.astype(np.float32)) for r in self._jump_rows())
+            _lib.check(_lib.lib().vd_set_jump_rows(model._handle, self.num_timesteps, _lib.ptr(sa), _lib.ptr(sb)))
             model._bound_schedule = self
         return model
 
@@ -246,6 +292,57 @@ class GaussianDiffusion:
         phi, p = _check_guidance(cfg_rescale, dynamic_threshold)
         return _guidance_scope(self._bind(model), phi, p)
 
+    @contextlib.contextmanager
+    def known_region_scope(self, model, known_src, known_mask, known_noise=None):
+        """This project's extension (RePaint, Lugmayr et al. 2022): `with diffusion.known_region_scope(model, known_src, known_mask):`
+        -- pixel-mask inpainting.  Every p_sample, ddim_sample and dpmpp_2m_sample call inside, and so every loop built on them, ends in
+        the merge pass: on the frames with latent_mask == 1 the pixels where known_mask is 1 are overwritten with
+        q_sample(known_src, t - 1, z), known_src itself at t == 0; every other element keeps the bits of the plain step, and
+        'pred_xstart' stays the model's own (include/vd_amd.h: vd_set_known_region).  known_src (B, T, 3, H, W); known_mask
+        (B, T, 1, H, W) or (B, T, H, W), bool, uint8 or float in {0, 1} -- anything else raises ValueError.
+        Draw order of a step: the sampler's own noise first (p_sample, ddim_sample), then z = th.randn_like(x), at every t (t == 0 reads
+        none of it); the noise is handed to the engine for the length of the call.  `known_noise` fixes z for every step inside (tests).
+        Scopes nest; the region found before is back when the block ends, whatever it raised.  A WindowExecutor.begin inside the scope
+        takes the region into its own buffers.  Refused inside: denoised_fn, use_gradient_method, ddim_reverse_sample.  Not honoured by
+        model(...) itself, p_mean_variance, score_windows and the NLL path.  No claim about sample quality is made."""
+        base = self._bind(model)
+        src, mask = check_known_region(known_src, known_mask)
+        region = dict(src=_f32(src, base.device), mask=_f32(mask, base.device),
+                      noise=None if known_noise is None else _f32(known_noise, base.device))
+        assert region["noise"] is None or region["noise"].shape == region["src"].shape
+        before = _known(base)
+        base._known_region = region
+        try:
+            _engine_region(base, region)
+            yield
+        finally:
+            base._known_region = before
+            _engine_region(base, before)
+
+    def q_jump(self, x, t, latent_mask=None, noise=None, model=None):
+        """This project's extension: one forward diffusion step x_{t-1} -> x_t at index t, the move RePaint's resampling walks back up
+        with: on the frames with latent_mask == 1 (None: every frame) sqrt(1 - beta_t) x + sqrt(beta_t) noise, the other frames unchanged;
+        noise drawn with th.randn_like when None.  Needs the engine for its rows, as q_sample."""
+        model = self._bind(model if model is not None else self._last_model())
+        dev = model.device
+        xs = _f32(x, dev)
+        assert xs.dim() == 5 and xs.shape[2] == 3
+        B, T = xs.shape[:2]
+        noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
+        assert noise.shape == xs.shape
+        lat = th.ones(B * T, device=dev) if latent_mask is None else _f32(latent_mask, dev).reshape(-1)
+        assert lat.shape == (B * T,)
+        tt = t.to(device=dev, dtype=th.int64).reshape(-1)
+        if tt.numel() == 1 and B != 1:
+            tt = tt.expand(B)
+        tt = tt.contiguous()
+        if t.device.type == "cpu" and B and (int(tt.min()) < 0 or int(tt.max()) >= self.num_timesteps):
+            raise IndexError(f"index {int(tt.max())} is out of bounds for dimension 0 with size {self.num_timesteps}")
+        out = th.empty_like(xs)
+        _lib.check(_lib.lib().vd_q_jump(model._handle, B, T, xs.shape[3] * xs.shape[4], _lib.ptr(xs), _lib.ptr(lat), _lib.ptr(tt),
+                                        _lib.ptr(noise), 0, 0, _lib.ptr(out), _lib.current_stream()))
+        return out
+
     def _scale_timesteps(self, t):
         if self.rescale_timesteps:
             return t.float() * (1000.0 / self.num_timesteps)
@@ -273,12 +370,14 @@ class GaussianDiffusion:
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
+            _refuse_known(model, "use_gradient_method")
             if mode != 0 or denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method: p_sample without denoised_fn (the reference's ddim_sample "
                                           "has no such option, gaussian_diffusion.py:597-634)")
             out = self._guided(model, x, t, clip_denoised, model_kwargs, noise2=noise, want_sample=True)
             return out["sample"], out["pred_xstart"]
         if denoised_fn is not None:
+            _refuse_known(model, "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise,
                                  cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
@@ -302,6 +401,13 @@ class GaussianDiffusion:
             assert noise.shape == xs.shape
         prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
         assert prev is None or prev.shape == xs.shape
+        region = _known(model)
+        if region is not None:
+            if mode == 2:
+                raise NotImplementedError("ddim_reverse_sample inside known_region_scope is not served")
+            if region["src"].shape != xs.shape:
+                raise ValueError(f"known_region_scope: known_src {tuple(region['src'].shape)} against a step on {tuple(xs.shape)}")
+            known_noise = region["noise"] if region["noise"] is not None else th.randn_like(xs)    # behind the sampler's own draw
         sample, xstart = th.empty_like(xs), th.empty_like(xs)
         B, T = xs.shape[:2]
         window = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt))
@@ -310,10 +416,14 @@ class GaussianDiffusion:
         if return_attn_weights is not None:
             self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
+            if region is not None:
+                _engine_region(model, region, known_noise)
             with _cfg_scope(model, cfg_scale):
                 rc = getattr(_lib.lib(), self._ENTRIES[mode][0])(*window, *own, _lib.ptr(sample), _lib.ptr(xstart), None,
                                                                  _lib.current_stream())
         finally:
+            if region is not None:
+                _engine_region(model, region)
             if return_attn_weights:
                 model._attn_release()
         _lib.check(rc)
@@ -403,6 +513,7 @@ class GaussianDiffusion:
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
+            _refuse_known(model, "use_gradient_method")
             if denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method with denoised_fn")
             g = self._guided(model, x, t, clip_denoised, model_kwargs or {}, _noise=getattr(self, "_guidance_noise", None))
@@ -556,6 +667,7 @@ class GaussianDiffusion:
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
+        _refuse_known(model, "ddim_reverse_sample")
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
@@ -573,6 +685,7 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         if denoised_fn is not None:
+            _refuse_known(model, "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=3, prev_xstart=prev_xstart)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
         sample, xstart = self._fused_step(3, model, x, t, clip_denoised, model_kwargs, prev_xstart=prev_xstart)
@@ -652,19 +765,23 @@ class GaussianDiffusion:
         self._model_hint = base
         for i in list(range(self.num_timesteps))[::-1]:
             t = th.tensor([i] * shape[0], device=device)
-            if "hybrid" in model_kwargs["observed_frames"]:
-                raise NotImplementedError("observed_frames='hybrid_<k>' is a training-time option")
-            model_kwargs["x_t_minus_1"] = self.q_sample(
-                model_kwargs["x0"], t - 1, noise=th.randn_like(_f32(model_kwargs["x0"], device)) if noise is None else noise,
-                model=base)
-            model_kwargs["random_t"] = th.floor(t * th.rand(t.shape).to(device)).long()   # CPU generator, as :569-570
-            if noise is None:
-                th.randn_like(_f32(model_kwargs["x0"], device))   # x_random's draw: consumed, never read in eval (unet.py:962)
+            self._loop_side_draws(base, model_kwargs, t, noise, device)
             out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
                                 model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
                                 use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)
             yield out
             img = out["sample"]
+
+    def _loop_side_draws(self, base, model_kwargs, t, noise, device):
+        """What p_sample_loop_progressive does before each step (gaussian_diffusion.py:560-573): x_t_minus_1, random_t and x_random's draw."""
+        if "hybrid" in model_kwargs["observed_frames"]:
+            raise NotImplementedError("observed_frames='hybrid_<k>' is a training-time option")
+        model_kwargs["x_t_minus_1"] = self.q_sample(
+            model_kwargs["x0"], t - 1, noise=th.randn_like(_f32(model_kwargs["x0"], device)) if noise is None else noise,
+            model=base)
+        model_kwargs["random_t"] = th.floor(t * th.rand(t.shape).to(device)).long()   # CPU generator, as :569-570
+        if noise is None:
+            th.randn_like(_f32(model_kwargs["x0"], device))   # x_random's draw: consumed, never read in eval (unet.py:962)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                          latent_mask=None, device=None, progress=False, eta=0.0, cfg_scale=1.0):
@@ -754,3 +871,50 @@ class GaussianDiffusion:
                                            model_kwargs=model_kwargs)
             yield out
             img, prev = out["sample"], out["pred_xstart"]
+
+    def repaint_sample_loop(self, model, shape, known_src, known_mask, sampler="p_sample", jump_length=1, n_resample=1, noise=None,
+                            clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
+        """This project's extension: RePaint inpainting from the last index down to 0 -- every step inside
+        known_region_scope(model, known_src, known_mask), and with n_resample > 1 the walk of respace.repaint_schedule: every
+        jump_length steps the chain goes jump_length steps back up (q_jump) and down again, n_resample times in all.  Returns the sample,
+        whose known pixels on the latent frames are known_src to the bit.  sampler: 'p_sample' (with p_sample_loop's per-step side
+        draws: n_resample = 1 is p_sample_loop inside the scope), 'ddim' (with `eta`) or 'dpmpp_2m' (first-order after a jump)."""
+        final = None
+        for out in self.repaint_sample_loop_progressive(model, shape, known_src, known_mask, sampler=sampler, jump_length=jump_length,
+                                                        n_resample=n_resample, noise=noise, clip_denoised=clip_denoised,
+                                                        model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale, progress=progress):
+            final = out
+        getattr(model, "check_device_errors", lambda: None)()
+        return final["sample"]
+
+    def repaint_sample_loop_progressive(self, model, shape, known_src, known_mask, sampler="p_sample", jump_length=1, n_resample=1,
+                                        noise=None, clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
+        """The ops of repaint_sample_loop, one dict per op: {'op': 'step', 't', 'sample', 'pred_xstart'} or {'op': 'jump', 't', 'sample'}."""
+        from .respace import repaint_schedule
+        if sampler not in ("p_sample", "ddim", "dpmpp_2m"):
+            raise ValueError(f"sampler={sampler!r}: 'p_sample', 'ddim' or 'dpmpp_2m'")
+        ops = repaint_schedule(self.num_timesteps - 1, jump_length, n_resample)
+        cfg_scale = _check_cfg(cfg_scale)
+        base = getattr(model, "model", model)
+        device = base.device
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else th.randn(*shape, device=device)
+        self._model_hint = base
+        prev = None
+        with self.known_region_scope(model, known_src, known_mask):
+            for op, i in ops:
+                t = th.tensor([i] * shape[0], device=device)
+                if op == "jump":
+                    img, prev = self.q_jump(img, t, latent_mask=model_kwargs["latent_mask"], model=base), None
+                    yield {"op": op, "t": i, "sample": img}
+                    continue
+                if sampler == "p_sample":
+                    self._loop_side_draws(base, model_kwargs, t, noise, device)
+                    out = self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, cfg_scale=cfg_scale)
+                elif sampler == "ddim":
+                    out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
+                else:
+                    with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                        out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+                img, prev = out["sample"], out["pred_xstart"]
+                yield {"op": op, "t": i, "sample": img, "pred_xstart": prev}

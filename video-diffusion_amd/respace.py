@@ -57,6 +57,30 @@ def logsnr_timesteps(betas, num_steps):
     return idx
 
 
+def repaint_schedule(t_start, jump_length, n_resample):
+    """This project's extension: the walk of RePaint (Lugmayr et al. 2022, algorithm 1 with jumps) over respaced indices, as a list of
+    ("step", t) -- one reverse step at index t, x_t -> x_{t-1} -- and ("jump", t) -- one forward step x_{t-1} -> x_t.  From t_start down
+    to 0; every jump_length steps below t_start the chain goes jump_length steps back up and comes down again, until each such level
+    has been left n_resample times.  n_resample == 1 is the plain descent; no jump passes t_start.  Steps in all:
+    t_start + 1 + (n_resample - 1) * jump_length * (t_start // jump_length)."""
+    if int(jump_length) != jump_length or jump_length < 1:
+        raise ValueError(f"jump_length={jump_length!r}: an integer >= 1")
+    if int(n_resample) != n_resample or n_resample < 1:
+        raise ValueError(f"n_resample={n_resample!r}: an integer >= 1")
+    if int(t_start) != t_start or t_start < 0:
+        raise ValueError(f"t_start={t_start!r}: a respaced index >= 0")
+    ops, done, level = [], {}, int(t_start)
+    while level >= 0:
+        ops.append(("step", level))
+        level -= 1
+        if level >= 0 and (t_start - level) % jump_length == 0 and done.get(level, 0) < n_resample - 1:
+            done[level] = done.get(level, 0) + 1
+            for _ in range(int(jump_length)):
+                level += 1
+                ops.append(("jump", level))
+    return ops
+
+
 def _walk(stride, count):
     pos = 0.0                      # accumulated, not k*stride: the reference's float drift is part of the contract
     for _ in range(count):

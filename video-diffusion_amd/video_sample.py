@@ -45,7 +45,7 @@ def get_masks(x0, num_obs):
 def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size=1, optimal_schedule_path=None, *,
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
                 adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
-                cfg_rescale=0.0, dynamic_threshold=None):
+                cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -79,7 +79,27 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     inside `diffusion.guidance_scope(model, cfg_rescale, dynamic_threshold)` -- guidance rescale (phi in [0, 1], acts with
     cfg_scale != 1) and dynamic thresholding (the percentile p in (0, 1], in place of the clamp of x_0), each with its statistic per
     batch item over the window's latent frames (gaussian_diffusion.py: guidance_scope).  With both at their defaults (0.0, None) no
-    scope is entered and the engine is not touched.  Refused together with use_gradient_method, prefix_cache and suffix_skip."""
+    scope is entered and the engine is not touched.  Refused together with use_gradient_method, prefix_cache and suffix_skip.
+
+    known_mask, known_video, jump_length, n_resample (this project's extension: pixel-mask inpainting, RePaint; both executors, every
+    sampler; composes with cfg_scale, cfg_rescale and dynamic_threshold): known_mask (T, H, W) or (B, T, H, W) over the WHOLE video, nonzero
+    = known; known_video (B, T, C, H, W), default `batch`.  Per window both are gathered by the window's frame indices exactly as x0 is
+    (per item in the adaptive-* modes) and every step ends in the merge pass on the window's latent frames (gaussian_diffusion.py:
+    known_region_scope): the known pixels of every generated frame come out equal to known_video.  n_resample > 1 walks
+    respace.repaint_schedule(num_timesteps - 1, jump_length, n_resample) in every window.  The noise of the merge and of the jumps is the
+    engine's Philox stream on both executors, from a seed drawn per window from torch's global generator (the sampler's own noise stays
+    th.randn_like on the eager executor): with a sampler that draws none, the two executors agree to the bit.  Refused with
+    use_gradient_method, prefix_cache and suffix_skip, and n_resample > 1 with save_all_timesteps (the record has one slot per
+    timestep).  With known_mask=None no scope is entered and the engine is not touched."""
+    if known_mask is not None:
+        for name, on in (("use_gradient_method", use_gradient_method), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
+            if on:
+                raise NotImplementedError(f"{name} together with known_mask")
+        if int(n_resample) != 1 and save_all_timesteps:
+            raise NotImplementedError("n_resample > 1 together with save_all_timesteps: the record has one slot per timestep")
+        from .respace import repaint_schedule
+        repaint_schedule(diffusion.num_timesteps - 1, jump_length, n_resample)     # the range checks, before anything touches the engine
+        known_mask_v, known_video_v = video_known_region(batch, known_mask, known_video)
     if float(cfg_rescale) != 0.0 or dynamic_threshold is not None:
         from .gaussian_diffusion import _check_guidance
         _check_guidance(cfg_rescale, dynamic_threshold)                     # before anything touches the engine
@@ -90,7 +110,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             return infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size, optimal_schedule_path,
                                use_gradient_method=use_gradient_method, observed_frames=observed_frames, sampler=sampler, eta=eta,
                                executor=executor, adaptive_distance=adaptive_distance, prefix_cache=prefix_cache, suffix_skip=suffix_skip,
-                               save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale)
+                               save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
+                               jump_length=jump_length, n_resample=n_resample)
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -151,9 +172,19 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                             kinda_marg_mask=kinda_marg_mask, x_t_minus_1=x0, observed_frames=observed_frames)
         if t_tensors is None:          # the reference re-creates this tensor every step (video_sample.py:154-155)
             t_tensors = [torch.tensor([ts] * B, device=device) for ts in range(diffusion.num_timesteps)]
+        k_src = k_mask = None
+        if known_mask is not None:     # the window's share of the region, gathered like x0
+            k_src, k_mask = (gather_window(v, frame_indices).to(device) for v in (known_video_v, known_mask_v))
         if use_graph:
             # renoise=False: like the eager loop below (and scripts/video_sample.py:149-166), every step reads x_t_minus_1 = x0 as it is
-            write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale))
+            write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, known_src=k_src,
+                                         known_mask=k_mask, jump_length=jump_length, n_resample=n_resample))
+            model.check_device_errors()
+            continue
+        if known_mask is not None:
+            local_samples, trace = _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampler, eta, cfg_scale, jump_length,
+                                                       n_resample, save_all_timesteps)
+            write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
             model.check_device_errors()
             continue
         local_samples = x0.clone()
@@ -178,6 +209,58 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
         model.check_device_errors()    # once per window (write_back has synchronised): a non-finite network output of any of its steps raises here
     return samples.numpy(), all_timestep_samples.numpy()
+
+
+def video_known_region(batch, known_mask, known_video=None):
+    """infer_video's known region over the whole video, on the host: known_mask (T, H, W) or (B, T, H, W), nonzero = known, ->
+    (B, T, H, W) float32 of 0 / 1; known_video (B, T, C, H, W), default `batch`, -> float32.  ValueError on any other shape."""
+    B, T, C, H, W = batch.shape
+    m = torch.as_tensor(known_mask)
+    if tuple(m.shape) == (T, H, W):
+        m = m.unsqueeze(0).expand(B, T, H, W)
+    if tuple(m.shape) != (B, T, H, W):
+        raise ValueError(f"known_mask must be {(T, H, W)} or {(B, T, H, W)} for a batch of {tuple(batch.shape)}, got {tuple(m.shape)}")
+    src = batch if known_video is None else torch.as_tensor(known_video)
+    if tuple(src.shape) != tuple(batch.shape):
+        raise ValueError(f"known_video must be {tuple(batch.shape)}, got {tuple(src.shape)}")
+    return (m != 0).to(torch.float32).cpu().contiguous(), src.to(torch.float32).cpu().contiguous()
+
+
+def gather_window(video, frame_indices):
+    """video (B, T, ...) -> (B, Tw, ...): item i's frames frame_indices[i] ((B, Tw) int64), the way infer_video forms x0."""
+    fi = torch.as_tensor(frame_indices).cpu()
+    return torch.stack([video[i, fi[i]] for i in range(video.shape[0])], dim=0).clone()
+
+
+def _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampler, eta, cfg_scale, jump_length, n_resample, want_trace):
+    """One window of infer_video's eager executor with a known region: the walk of repaint_schedule through the step entry points inside
+    known_region_scope.  The merge's and the jumps' noise is what the window executor would draw: vd_randn at (seed, k B per + B per / 4)
+    for op k's merge and (seed, k B per) for a jump, the seed drawn as WindowExecutor.begin draws it."""
+    from . import _lib
+    from .respace import repaint_schedule
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    B = x0.shape[0]
+    n = x0.numel()
+    local, prev, trace = x0.clone(), None, ([] if want_trace else None)
+    z = torch.empty_like(local)
+    for k, (op, ts) in enumerate(repaint_schedule(diffusion.num_timesteps - 1, jump_length, n_resample)):
+        t = torch.tensor([ts] * B, device=x0.device)
+        _lib.check(_lib.lib().vd_randn(_lib.ptr(z), n, seed, k * n + (n // 4 if op == "step" else 0), _lib.current_stream()))
+        if op == "jump":
+            local, prev = diffusion.q_jump(local, t, latent_mask=model_kwargs["latent_mask"], noise=z, model=model), None
+            continue
+        with diffusion.known_region_scope(model, k_src, k_mask, known_noise=z):
+            if sampler == "dpmpp_2m":
+                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                    out = diffusion.dpmpp_2m_sample(model, local, t=t, prev_xstart=prev, clip_denoised=True, model_kwargs=model_kwargs)
+            elif sampler == "p_sample":
+                out = diffusion.p_sample(model, local, t=t, clip_denoised=True, model_kwargs=model_kwargs, cfg_scale=cfg_scale)
+            else:
+                out = diffusion.ddim_sample(model, local, t=t, clip_denoised=True, model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
+        local, prev = out["sample"], out["pred_xstart"]
+        if trace is not None:
+            trace.append(local.clone())
+    return local, trace
 
 
 def to_uint8(recon):
@@ -406,6 +489,13 @@ def build_parser():
     ap.add_argument("--dynamic_threshold", type=float, default=None,
                     help="dynamic thresholding: the percentile P in (0, 1] of |x_0| over each item's latent frames that replaces the 1 of the "
                          "clamp of x_0 (never below 1); off by default; named in the run directory when set")
+    ap.add_argument("--known_mask", default=None, metavar="MASK.npy",
+                    help="pixel-mask inpainting: a (T, H, W) or (H, W) array, nonzero = known, one mask for all videos; the known pixels of every "
+                         "generated frame are kept from the source (--known_videos, default: the test videos themselves)")
+    ap.add_argument("--known_videos", default=None, metavar="K.npy",
+                    help="with --known_mask: the source of the known pixels, (N, T, 3, H, W) indexed like --videos; float in [-1, 1] or uint8")
+    ap.add_argument("--jump_length", type=int, default=1, help="with --known_mask and --n_resample > 1: steps per resampling jump")
+    ap.add_argument("--n_resample", type=int, default=1, help="with --known_mask: times each level is walked (RePaint resampling); 1 = off")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -423,6 +513,26 @@ def main(argv=None):
     return run(parse_with_lpips(build_parser(), argv))
 
 
+def _known_options(args, batch):
+    """--known_mask / --known_videos of the job -> infer_video's keywords for this batch ({} without a mask).  The batch's dataset
+    items are args._batch_ids (run() sets it)."""
+    path = getattr(args, "known_mask", None)
+    if not path:
+        return {}
+    m = np.load(path)
+    T = batch.shape[1]
+    if m.ndim == 2:
+        m = np.broadcast_to(m[None], (T, *m.shape))
+    if m.ndim != 3:
+        raise ValueError(f"{path}: --known_mask is (T, H, W) or (H, W), got {m.shape}")
+    kw = dict(known_mask=torch.from_numpy(np.ascontiguousarray(m[:T] != 0)), jump_length=getattr(args, "jump_length", 1),
+              n_resample=getattr(args, "n_resample", 1))
+    if getattr(args, "known_videos", None):
+        src = ArrayVideos(args.known_videos)
+        kw["known_video"] = torch.stack([src[i][0] for i in args._batch_ids])[:, :T]
+    return kw
+
+
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
     return infer_video(args.inference_mode, model, diffusion, batch, args.max_frames, args.obs_length, args.step_size,
                        optimal_schedule_path, use_gradient_method=getattr(args, "use_gradient_method", False),
@@ -431,19 +541,24 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        adaptive_distance=getattr(args, "adaptive_distance", "l2"),
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
                        save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
-                       cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None))
+                       cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None),
+                       **_known_options(args, batch))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
-    ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7') and a dynamic_threshold ('_dt0.995') -- samples of
+    ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995') and a --known_mask -- samples of
     different samplers or guidance settings never share a directory, and a run without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
     phi = float(getattr(args, "cfg_rescale", 0.0) or 0.0)
     p = getattr(args, "dynamic_threshold", None)
+    known = ""
+    if getattr(args, "known_mask", None):         # '_known', '_known_j2r3' with resampling
+        r = int(getattr(args, "n_resample", 1))
+        known = "_known" + ("" if r == 1 else f"_j{int(getattr(args, 'jump_length', 1))}r{r}")
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
-        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}")
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known
 
 
 def run(args, create=None, device=None, infer=None):
@@ -513,6 +628,7 @@ def run(args, create=None, device=None, infer=None):
             if batch is None:
                 batch = torch.stack([dataset[i][0] for i in ids])[:, :args.T].to(device)
             q_all = q_sample_every_timestep(diffusion, model, batch) if every else None
+            args._batch_ids = ids
             recon, recon_all = infer(args, model, diffusion, batch, optimal_schedule_path)
             outputs = [(names, to_uint8(recon))]
             if every:
