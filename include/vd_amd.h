@@ -434,6 +434,36 @@ int vd_q_jump(vd_engine* e, int B, int T, long long frame_pixels, const float* x
               const float* noise, unsigned long long seed, unsigned long long offset, float* out, void* stream);
 int vd_window_jump(vd_engine* e, int n, void* stream);
 
+/* Measurement: zero-shot restoration -- this project's extension (DDNM, Wang, Yu, Zhang 2022: the range/null-space projection
+ * x_0 <- x_0 + A^+(y - A x_0) applied to the x_0 prediction of every step; the reference has nothing like it).  It needs no weights of its
+ * own and conditions on a DEGRADED copy of the video, where the known region conditions on known pixels.  No claim about restoration
+ * quality is made here: what is pinned is the arithmetic.
+ * One operator family, "cell mean".  A cell is scale x scale pixels of one channel plane (gray = 0) or of the three planes of its frame
+ * (gray = 1, channel weights 1/3 each).  A = the mean over every cell: y [B][T][Cy][H/scale][W/scale] float32, Cy = 3, or 1 with gray.
+ * A^+ replicates a cell's value over its cell, so A A^+ = I.  Served: scale 2, 4, 8 with either gray value and scale 1 with gray = 1
+ * (super-resolution, colourisation, both); H and W must be divisible by scale.
+ * The pass (csrc/measure.hip: measurement_project_kernel), one launch, on the frames with latent_mask == 1 only: every element of a cell
+ * becomes x_0 + (y_cell - mean_cell(x_0)), mean_cell = sum / n with the sum in a fixed order (no atomics: item b of a batch has the bits of
+ * the call on item b alone) -- |out - exact| <= gamma_n mean_cell|x_0| + u |y - m| + u |out|, n the cell's size, u = 2^-24; other frames
+ * keep the unprojected x_0.  A cell that holds a value that is not finite comes out not finite in every element.
+ * vd_set_measurement: engine state like cfg_scale; y is the caller's device tensor, which must stay alive and of the shape of the steps
+ * that follow; NULL clears it.  vd_measurement: 1 while set, else 0; the scale and gray flag through the two pointers (either may be NULL).
+ * Honoured by vd_p_sample, vd_ddim_sample, vd_dpmpp_2m_sample, vd_p_mean_variance and vd_window_begin / vd_window_run.  Order inside a
+ * step: network (both forwards and the combine or rescale pass of cfg_scale), x_0 with the clamp of clip_denoised or the dynamic
+ * threshold in its place, the projection, then the sampler pass on the projected x_0 with its clamp off -- pred_xstart, the mean and
+ * dpmpp_2m's history are the projected x_0, and at t == 0, where every sampler returns x_0, A(sample) = y up to rounding on the latent
+ * frames.  With no measurement set a step launches exactly what it launched before.
+ * Fails by name: vd_ddim_reverse_sample (sampler 2 in a window), vd_guided_step (use_gradient_method), a window with the prefix cache or
+ * the suffix skip on, and a measurement together with a known region (vd_set_known_region; not built).  NOT honoured by vd_unet_forward,
+ * vd_score_windows, vd_vb_terms / vd_prior_bpd and the vd_*_from_xstart / vd_posterior_update passes.
+ * In a window y's address, scale and gray are part of the graph's signature: one graph per (signature, scale, gray).
+ * vd_measurement_project: the projection alone, in place on an x_0 handed in, on frames of H x W (any size; the engine's image size is
+ * not read), no network and no clamp.  16-byte accesses while W % 4 == 0 and x0_inout is 16-byte aligned, else element by element: same bits. */
+int vd_set_measurement(vd_engine* e, const float* y, int scale, int gray);
+int vd_measurement(vd_engine* e, int* scale, int* gray);
+int vd_measurement_project(vd_engine* e, int B, int T, int H, int W, float* x0_inout, const float* y, const float* latent_mask, int scale,
+                           int gray, void* stream);
+
 /* The posterior arithmetic alone, given eps (same formulas; mode 0 p_sample, 1 ddim). */
 int vd_posterior_update(vd_engine* e, int mode, int B, long long per_sample, const float* x, const float* eps,
                         const long long* t, int clip_denoised, float eta, const float* noise,

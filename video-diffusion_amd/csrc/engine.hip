@@ -312,6 +312,10 @@ struct vd_engine {
     // tensors; a window graph's key carries the two addresses.  known_noise / seed / offset: the draws of the eager entries.
     const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
     unsigned long long known_seed = 0, known_offset = 0;
+    // measurement (vd_set_measurement; null = off): the x_0 prediction of every step is projected onto it (measure.hip) before the sampler
+    // pass reads it.  The caller's tensor; a window graph's key carries the address, the scale and the gray flag.
+    const float* meas_y = nullptr;
+    int meas_scale = 1, meas_gray = 0;
     int mean_type = 0;                               // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
@@ -327,6 +331,7 @@ struct vd_engine {
         float guid_phi, dyn_p;                                    // guidance rescale / dynamic threshold: the passes a graph holds and their constants
         float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
         const float *known_src, *known_mask;                      // known region: the merge pass a graph ends in reads them (null: none)
+        const float* meas_y; int meas_scale, meas_gray;           // measurement: the projection pass a graph holds reads y (null: none)
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -1889,6 +1894,9 @@ struct StepReq {
     // (known_seed, known_offset + B*per/4), or at the pair `rng` points to
     const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
     unsigned long long known_seed = 0, known_offset = 0;
+    // measurement (null: none): the projection of the step's x_0 prediction onto y, in front of the sampler pass
+    const float* meas_y = nullptr;
+    int meas_scale = 1, meas_gray = 0;
 };
 
 // The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
@@ -1925,6 +1933,11 @@ static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long lo
 // its x0_given form with clip off -- the form `denoised_fn` uses, bit-matched to the fused step.  With both at 0 the launches are the ones above.
 // known_src (a known region; run_step and vd_window_begin refuse it for a sampler that walks up): one more pass behind the sampler pass,
 // launch_known_merge in place on the sample, drawing from the free quarter of the step's Philox range.  Null: no launch is added.
+// meas_y (a measurement; refused together with a known region, a sampler that walks up and a cut step): one more pass in front of the
+// sampler pass, launch_measurement_project.  Behind launch_dynamic_threshold it projects the finished x_0 in place; otherwise it forms
+// x_0 itself (pass_x0: the sampler pass's head, clamp included) and writes the projected one into the second output buffer.  Either way
+// the sampler pass then runs in its x0_given form with clip off, so pred_xstart, the mean and the 2M history are the projected x_0.
+// Null: no launch is added.
 static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     int rc;
     const int B = r.B, T = r.T;
@@ -1964,6 +1977,18 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
         pa.eps = nullptr; pa.x0_given = da.out;
         pa.clip = 0;
     }
+    if (r.meas_y) {
+        VD_REQUIRE(!r.pp && !r.sp, "a measurement (vd_set_measurement) together with the window prefix cache or suffix skip is not served");
+        const int S = e->cfg.image_size;
+        float* out = e->step_eps_u(B, T);
+        // behind the threshold: its output, in place, as it is; else the network output through pass_x0 with the step's clamp
+        MeasureArgs ma{thresh || e->mean_type == 1 ? nullptr : r.x, thresh ? out : eps, out, r.meas_y, r.lat, pa.t, e->d_tab, e->num_timesteps,
+                       B, T, S, S, r.meas_scale, r.meas_gray, thresh ? 0 : r.clip};
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * (ma.x ? 3.0 : 2.0), st, "measurement_project");
+        if ((rc = launch_measurement_project(ma, st))) return rc;
+        pa.eps = nullptr; pa.x0_given = out;
+        pa.clip = 0;
+    }
     pa.mean = r.mean; pa.eta = r.eta; pa.noise = r.noise; pa.seed = r.seed; pa.offset = r.offset; pa.dstate = r.rng;
     pa.hist = r.hist; pa.hist_on = r.hist_on;
     if (!sampler_draws_noise(r.sampler)) rc = launch_sampler_pass(pa, st);
@@ -1977,6 +2002,14 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     ka.noise = r.known_noise; ka.seed = r.known_seed; ka.offset = r.known_offset; ka.dstate = r.rng;
     ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 3.0, st, "known_merge");
     return launch_known_merge(ka, st);
+}
+
+// what a measurement is refused together with, by name: the eager entries and vd_window_begin ask this of the engine's state
+static int refuse_with_measurement(const vd_engine* e, int sampler) {
+    VD_REQUIRE(!sampler_walks_up(sampler), std::string(sampler_name(sampler)) + " together with a measurement (vd_set_measurement) is not served: the projection constrains x_0 of a reverse step");
+    VD_REQUIRE(!e->known_src, "a measurement (vd_set_measurement) together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(e->cfg.image_size % e->meas_scale == 0, "measurement: H and W must be divisible by scale");
+    return 0;
 }
 
 // what a step needs sized before its launches (never inside a capture): the workspace, and the zero mask of a cfg_scale step
@@ -2001,6 +2034,10 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
         VD_REQUIRE(!sampler_walks_up(r.sampler), std::string(sampler_name(r.sampler)) + " together with a known region (vd_set_known_region) is not served: the merge noises to t - 1");
         r.known_src = e->known_src; r.known_mask = e->known_mask; r.known_noise = e->known_noise;
         r.known_seed = e->known_seed; r.known_offset = e->known_offset;
+    }
+    if (e->meas_y) {
+        if ((rc = refuse_with_measurement(e, r.sampler))) return rc;
+        r.meas_y = e->meas_y; r.meas_scale = e->meas_scale; r.meas_gray = e->meas_gray;
     }
     return step_launches(e, r, st);
 }
@@ -2233,6 +2270,7 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     if (suf_on) r.sp = &splan;
     r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
     r.known_src = k.known_src; r.known_mask = k.known_mask;      // the merge draws from the window's own Philox pair (r.rng)
+    r.meas_y = k.meas_y; r.meas_scale = k.meas_scale; r.meas_gray = k.meas_gray;
     if (!rc) rc = step_launches(e, r, st);
     if (!rc) {
         // a step with a merge pass consumes its range whatever the sampler: the merge's quarter of it is drawn from
@@ -2284,6 +2322,11 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
         VD_REQUIRE(!e->prefix_cache_on, "a known region (vd_set_known_region) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
         VD_REQUIRE(!e->suffix_skip_on, "a known region (vd_set_known_region) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
     }
+    if (e->meas_y) {
+        if ((rc = refuse_with_measurement(e, sampler))) return rc;
+        VD_REQUIRE(!e->prefix_cache_on, "a measurement (vd_set_measurement) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+        VD_REQUIRE(!e->suffix_skip_on, "a measurement (vd_set_measurement) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = step_workspace(e, B, T, st))) return rc;
@@ -2296,6 +2339,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     key.guid_phi = e->guid_phi; key.dyn_p = e->dyn_p;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
     key.known_src = e->known_src; key.known_mask = e->known_mask;
+    if (e->meas_y) { key.meas_y = e->meas_y; key.meas_scale = e->meas_scale; key.meas_gray = e->meas_gray; }
     e->win_cur = -1;
     e->win_lost = false;
     ++e->win_gen;
@@ -2439,6 +2483,29 @@ int vd_known_merge(vd_engine* e, int B, int T, long long frame_pixels, float* sa
     KnownMergeArgs a{sample, known_src, known_mask, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)frame_pixels};
     a.noise = known_noise; a.seed = seed; a.offset = offset;
     return launch_known_merge(a, static_cast<hipStream_t>(stream));
+}
+
+// ---- measurement (zero-shot restoration, DDNM): engine state like the known region; a window graph's key carries y, scale and gray
+int vd_set_measurement(vd_engine* e, const float* y, int scale, int gray) {
+    VD_REQUIRE(e, "null engine");
+    if (!y) { e->meas_y = nullptr; e->meas_scale = 1; e->meas_gray = 0; return 0; }
+    VD_REQUIRE(measurement_served(scale, gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
+    e->meas_y = y; e->meas_scale = scale; e->meas_gray = gray ? 1 : 0;
+    return 0;
+}
+
+int vd_measurement(vd_engine* e, int* scale, int* gray) {
+    if (scale) *scale = e ? e->meas_scale : 1;
+    if (gray) *gray = e ? e->meas_gray : 0;
+    return e && e->meas_y ? 1 : 0;
+}
+
+// the projection alone on an x_0 handed in, in place, on frames of H x W (any size; the engine's image size is not read), no network
+int vd_measurement_project(vd_engine* e, int B, int T, int H, int W, float* x0_inout, const float* y, const float* lat, int scale, int gray,
+                           void* stream) {
+    VD_REQUIRE(e, "null engine");
+    MeasureArgs a{nullptr, x0_inout, x0_inout, y, lat, nullptr, nullptr, 0, B, T, H, W, scale, gray ? 1 : 0, 0};
+    return launch_measurement_project(a, static_cast<hipStream_t>(stream));
 }
 
 static const char* const kNoJumpRows = "q_jump: no jump rows for the bound schedule (vd_set_jump_rows, after vd_set_schedule)";
@@ -2659,6 +2726,7 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs,
     VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283)");
     VD_REQUIRE(e->mean_type == 0, "use_gradient_method: epsilon-prediction models only");
+    VD_REQUIRE(!e->meas_y, "use_gradient_method together with a measurement (vd_set_measurement) is not served");
     VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, "use_gradient_method: the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
     VD_REQUIRE(x && obs && lat && km && fidx && t && x_t_minus_1 && noise && (sample == nullptr || noise2 != nullptr), "null tensor");
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -477,18 +477,7 @@ __device__ __forceinline__ bool pass_t(const SamplerPassArgs& a, size_t item, si
     if (a.mean) reinterpret_cast<V*>(a.mean)[i] = q;
     return false;
 }
-// The x_0 prediction: an epsilon-model's through xstart_from_eps (two products, each rounded, then one subtraction -- never a fused
-// multiply-add), or the one handed in.  The step through `denoised_fn` takes its x_0 from the p_sample pass (vd_p_mean_variance) and hands
-// it to the *_from_xstart form of another: with one head, the fused step and that form agree to the bit for denoised_fn = identity.
-// A network output that is not finite -- in the f16x3 arithmetic: an operand beyond fp16's range (|x| > 65504) anywhere in the network --
-// must not leave through the clamp as a plausible -1 (fmaxf(NaN, -1) = -1): it is left as it is and raises `nonfinite`.
-__device__ __forceinline__ float pass_x0(float x, float src, bool given, float sr, float srm1, int clip, bool& nonfinite) {
-    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
-    const bool bad = !(fabsf(x0) <= 3.4028234e38f);
-    nonfinite |= bad;
-    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    return x0;
-}
+// (pass_x0, the x_0 head of every pass, lives in vd_common.h: measure.hip forms the same bits with it)
 
 // p_sample (gaussian_diffusion.py:319-343,374-382,208-227,438-443) and ddim_sample (:597-634), element by element (any per).
 // Coefficients are float32 casts of the float64 tables, exactly what _extract_into_tensor yields.

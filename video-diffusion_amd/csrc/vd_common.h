@@ -458,6 +458,18 @@ __device__ __forceinline__ float xstart_from_eps(float sr, float x, float srm1, 
     const float a = sr * x, b = srm1 * eps;
     return a - b;
 }
+// The x_0 prediction: an epsilon-model's through xstart_from_eps (two products, each rounded, then one subtraction -- never a fused
+// multiply-add), or the one handed in.  The step through `denoised_fn` takes its x_0 from the p_sample pass (vd_p_mean_variance) and hands
+// it to the *_from_xstart form of another: with one head, the fused step and that form agree to the bit for denoised_fn = identity.
+// A network output that is not finite -- in the f16x3 arithmetic: an operand beyond fp16's range (|x| > 65504) anywhere in the network --
+// must not leave through the clamp as a plausible -1 (fmaxf(NaN, -1) = -1): it is left as it is and raises `nonfinite`.
+__device__ __forceinline__ float pass_x0(float x, float src, bool given, float sr, float srm1, int clip, bool& nonfinite) {
+    float x0 = given ? src : xstart_from_eps(sr, x, srm1, src);
+    const bool bad = !(fabsf(x0) <= 3.4028234e38f);
+    nonfinite |= bad;
+    if (clip && !bad) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    return x0;
+}
 // Guidance rescale and dynamic thresholding (guidance.hip; this project's extensions).  Tensors are [B][T][frame_elems], `lat` the [B*T]
 // latent mask: an item's statistic runs over the elements of its frames with lat == 1.  `scratch`: guidance_scratch_bytes(B) bytes, 256-byte
 // aligned, the caller's; nothing here allocates or waits for the device.
@@ -519,6 +531,29 @@ struct QJumpArgs {
     const unsigned long long* dstate = nullptr;
 };
 int launch_q_jump(const QJumpArgs& a, hipStream_t s);
+
+// Zero-shot restoration (measure.hip; this project's extension, DDNM: Wang, Yu, Zhang 2022): the projection of a step's x_0 prediction onto
+// a measurement, x_0 <- x_0 + A^+(y - A x_0), for the "cell mean" operators.  Tensors are [B][T][3][H][W], `lat` the [B*T] latent mask.
+// A cell is scale x scale pixels of one channel plane (gray: of the three planes of its frame); A is the mean over every cell,
+// y [B][T][Cy][H/scale][W/scale] with Cy = 3 (gray: 1); A^+ replicates.  In one launch: x_0 = pass_x0(...) -- from (x, src = eps) with the
+// tables at t[b], or src itself when x is null, clamped when `clip` -- then, on the frames with lat == 1, every element of a cell becomes
+// x_0 + (y_cell - mean_cell(x_0)); other frames get x_0 unprojected.  out may alias src.  Fixed summation order, no atomics: an item's
+// bits do not depend on B.  A cell with a value that is not finite comes out not finite; no error bit (the sampler pass behind it sets
+// it).  A t[b] outside the schedule (x != null): item b of `out` is not written, the sampler pass poisons the item without reading it.
+// 16-byte accesses while W % 4 == 0 and x, src, out are 16-byte aligned, else element by element: same bits.
+struct MeasureArgs {
+    const float* x;         // x_t, or null: src is the x_0 prediction itself
+    const float* src;       // the network output (eps), or the x_0 prediction
+    float* out;
+    const float* y;
+    const float* lat;
+    const int64_t* t;       // [B] respaced index (read with x only)
+    const float* tab; int num_timesteps;
+    int B, T, H, W;
+    int scale, gray, clip;
+};
+inline bool measurement_served(int scale, int gray) { return scale == 2 || scale == 4 || scale == 8 || (scale == 1 && gray); }
+int launch_measurement_project(const MeasureArgs& a, hipStream_t s);
 
 enum { TAB_SQRT_RECIP = 0, TAB_SQRT_RECIPM1, TAB_COEF1, TAB_COEF2, TAB_LOGVAR, TAB_ACP, TAB_ACP_PREV,
        TAB_SQRT_ACP, TAB_SQRT_1M_ACP, TAB_POST_LOGVAR, TAB_LOG_1M_ACP, TAB_ALPHA, NTAB };

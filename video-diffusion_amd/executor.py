@@ -21,6 +21,8 @@ conditional distribution.
 Pixel-mask inpainting (this project's extension, RePaint): `begin(..., known_src=, known_mask=)` captures a step that ends in the merge pass
 on the window tensor, `jump(n)` walks the armed window n forward diffusion steps back up (plain launches), and `run_repaint(j, r)` is the
 walk of `respace.repaint_schedule` over both; all noise stays on the window's Philox stream (include/vd_amd.h: vd_set_known_region).
+Zero-shot restoration (DDNM, this project's extension too): `begin(..., measurement=, sr_scale=, gray=)` captures a step whose x_0
+prediction is projected onto the measurement in front of the sampler pass (include/vd_amd.h: vd_set_measurement).
 """
 import math
 
@@ -73,8 +75,17 @@ class WindowExecutor:
             bufs["known_mask"] = th.zeros(B, T, S, S, dtype=th.float32, device=self.model.device)
         return bufs["known_src"], bufs["known_mask"]
 
+    def _measurement_buffer(self, B, T, scale, gray):
+        """The window's measurement, one buffer per (B, T, scale, gray): a stable address, so one graph per shape and operator."""
+        from .gaussian_diffusion import measurement_shape
+        bufs, key = self._buffers(B, T), f"measurement_s{scale}_g{int(gray)}"
+        if key not in bufs:
+            S = self.model.image_size
+            bufs[key] = th.zeros(*measurement_shape((B, T, 3, S, S), scale, gray), dtype=th.float32, device=self.model.device)
+        return bufs[key]
+
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
-              known_src=None, known_mask=None, cfg_scale=1.0):
+              known_src=None, known_mask=None, measurement=None, sr_scale=1, gray=False, cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -93,7 +104,12 @@ class WindowExecutor:
         known_src, known_mask (this project's extension; gaussian_diffusion.py: known_region_scope): pixel-mask inpainting -- both are
         copied into buffers of this object, the captured step ends in the merge pass, and the merge's noise comes from the window's own
         Philox stream (the step's range at + B*per/4; every sampler's step then advances the counter by B*per).  Without them, a begin()
-        inside `diffusion.known_region_scope(...)` takes the scope's region.  Not served with 'ddim_reverse', prefix_cache or suffix_skip."""
+        inside `diffusion.known_region_scope(...)` takes the scope's region.  Not served with 'ddim_reverse', prefix_cache or suffix_skip.
+        measurement, sr_scale, gray (this project's extension; gaussian_diffusion.py: measurement_scope): zero-shot restoration -- y =
+        measure(window, sr_scale, gray) is checked (check_measurement) and copied into a buffer of this object, one per (B, T, sr_scale,
+        gray); the captured step projects its x_0 prediction onto it, and y's address, the scale and the flag are part of the graph's
+        signature.  Without it, a begin() inside `diffusion.measurement_scope(...)` takes the scope's measurement.  The engine refuses it
+        by name with 'ddim_reverse', prefix_cache, suffix_skip and a known region."""
         cfg_scale = float(cfg_scale)
         if not math.isfinite(cfg_scale):
             raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
@@ -115,6 +131,14 @@ class WindowExecutor:
             for name, on in (("prefix_cache", self.prefix_cache), ("suffix_skip", self.suffix_skip), ("sampler='ddim_reverse'", sampler == "ddim_reverse")):
                 if on:
                     raise NotImplementedError(f"{name} together with a known region")
+        from .gaussian_diffusion import _engine_measurement, _measurement, check_measurement
+        m_scope = _measurement(self.model)
+        if measurement is not None:
+            meas = dict(y=check_measurement(measurement, x_init.shape, sr_scale, gray), scale=int(sr_scale), gray=bool(gray))
+        elif m_scope is not None:
+            meas = dict(m_scope, y=check_measurement(m_scope["y"], x_init.shape, m_scope["scale"], m_scope["gray"]))
+        else:
+            meas = None
         if self.prefix_cache or self.suffix_skip:                 # the guidance options of an enclosing guidance_scope (engine state)
             L, h = _lib.lib(), self.model._handle
             which = "prefix_cache" if self.prefix_cache else "suffix_skip"
@@ -150,6 +174,12 @@ class WindowExecutor:
                 ks.copy_(known_src)
                 km.copy_(known_mask)
                 region = dict(src=ks, mask=km)
+            if meas is not None:
+                yb = self._measurement_buffer(B, T, meas["scale"], meas["gray"])
+                if meas["y"].is_cuda:
+                    meas["y"].record_stream(self.stream)
+                yb.copy_(meas["y"])
+                meas = dict(meas, y=yb)
             for k in ("obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"):
                 bufs[k].copy_(kw[k].view(bufs[k].shape))
             if mode == "x_0":
@@ -172,6 +202,9 @@ class WindowExecutor:
             # ... and so is the region: the graph's signature keeps the two buffer addresses
             if region is not None or scope is not None:
                 _engine_region(self.model, region)
+            # ... and the measurement: the signature keeps the buffer's address, the scale and the gray flag
+            if meas is not None:
+                _engine_measurement(self.model, meas)
             try:
                 rc = _lib.lib().vd_window_begin(
                     self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
@@ -179,6 +212,8 @@ class WindowExecutor:
                     3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
                     int(t_start), self.stream.cuda_stream)
             finally:
+                if meas is not None:
+                    _engine_measurement(self.model, m_scope)
                 if region is not None or scope is not None:
                     _engine_region(self.model, scope)
                 if cfg_scale != 1.0:
@@ -196,10 +231,16 @@ class WindowExecutor:
         if n_steps is None:
             n_steps = self._left
         self._check_gen("run")
+        self._after_caller()
         _lib.check(_lib.lib().vd_window_run(self.model._handle, int(n_steps), self.stream.cuda_stream))
         self._left -= int(n_steps)
         th.cuda.current_stream(self.model.device).wait_stream(self.stream)
         return self.x
+
+    def _after_caller(self):
+        """The executor's stream waits for what the caller's stream holds: a read of the window tensor enqueued there (`run(3).clone()`)
+        must finish before the next replay or jump writes the tensor."""
+        self.stream.wait_stream(th.cuda.current_stream(self.model.device))
 
     def _check_gen(self, what):
         # the step counters are one set per engine: refuse to continue a window another executor has re-armed since
@@ -212,6 +253,7 @@ class WindowExecutor:
         noise from the window's Philox stream (a range of B*per each); a 'dpmpp_2m' window's next step is first-order again.  Returns
         the window tensor (updated in place)."""
         self._check_gen("jump")
+        self._after_caller()
         _lib.check(_lib.lib().vd_window_jump(self.model._handle, int(n), self.stream.cuda_stream))
         self._left += int(n)
         th.cuda.current_stream(self.model.device).wait_stream(self.stream)
@@ -234,10 +276,10 @@ class WindowExecutor:
         return self.x
 
     def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, known_src=None, known_mask=None,
-                      jump_length=1, n_resample=1, cfg_scale=1.0):
+                      jump_length=1, n_resample=1, measurement=None, sr_scale=1, gray=False, cfg_scale=1.0):
         """All num_timesteps steps of one window (with a known region and n_resample > 1: the walk of run_repaint); returns a fresh tensor."""
         self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale, known_src=known_src,
-                   known_mask=known_mask)
+                   known_mask=known_mask, measurement=measurement, sr_scale=sr_scale, gray=gray)
         if int(n_resample) != 1:
             return self.run_repaint(jump_length, n_resample).clone()
         return self.run(self.diffusion.num_timesteps).clone()

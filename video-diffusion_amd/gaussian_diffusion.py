@@ -23,7 +23,10 @@ conditional one's) and dynamic thresholding (a per-item percentile of |x_0| over
 per-item statistics are taken on the device inside the step (csrc/guidance.hip).  Pixel-mask inpainting is an extension as well
 (RePaint): inside `GaussianDiffusion.known_region_scope` every p_sample / ddim_sample / dpmpp_2m_sample step ends in one more fused pass
 that overwrites the known pixels of the latent frames with the known content noised to the level just reached (csrc/known.hip), `q_jump`
-is the forward step of its resampling walk and `repaint_sample_loop` the loop around both.  Training losses are out of scope.
+is the forward step of its resampling walk and `repaint_sample_loop` the loop around both.  Zero-shot restoration is the last one
+(DDNM): inside `GaussianDiffusion.measurement_scope` the x_0 prediction of every step is projected onto a degraded copy y of the video,
+x_0 + A^+(y - A x_0), for the cell-mean operators A of `measure` -- super-resolution, colourisation, or both (csrc/measure.hip).
+Training losses are out of scope.
 """
 import contextlib
 import enum
@@ -176,8 +179,84 @@ def _refuse_known(model, what):
         raise NotImplementedError(f"{what} inside known_region_scope is not served")
 
 
+MEASUREMENT_SCALES = (1, 2, 4, 8)
+
+
+def _check_operator(scale, gray):
+    """The cell-mean operators served: scale 2, 4, 8 with either gray value, scale 1 with gray.  Returns (scale, gray) as (int, bool)."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in MEASUREMENT_SCALES:
+        raise ValueError(f"scale={scale!r}: the cell size must be one of 2, 4, 8, or 1 together with gray=True")
+    if int(scale) == 1 and not gray:
+        raise ValueError("scale=1 with gray=False is the identity: nothing to restore")
+    return int(scale), bool(gray)
+
+
+def measurement_shape(shape, scale, gray):
+    """The shape of y = A x for a video of `shape` (B, T, 3, H, W): (B, T, Cy, H / scale, W / scale), Cy = 1 with gray else 3.
+    ValueError for an operator that is not served, a shape that is no video, or H, W not divisible by scale."""
+    scale, gray = _check_operator(scale, gray)
+    if len(shape) != 5 or shape[2] != 3:
+        raise ValueError(f"a video is (B, T, 3, H, W), got {tuple(shape)}")
+    B, T, _, H, W = (int(v) for v in shape)
+    if H % scale or W % scale:
+        raise ValueError(f"H={H} and W={W} must be divisible by scale={scale}")
+    return (B, T, 1 if gray else 3, H // scale, W // scale)
+
+
+def measure(video, scale=1, gray=False):
+    """A on the host, in torch: video (B, T, 3, H, W) -> y (B, T, Cy, H / scale, W / scale), the mean over every scale x scale cell of
+    each channel plane, or with gray=True over the cell in all three planes (channel weights 1/3 each, as in DDNM).  How a caller
+    makes the y of `measurement_scope` from a video; float64 in, float64 out, anything else float32."""
+    if not th.is_tensor(video):
+        raise ValueError("measure: a (B, T, 3, H, W) tensor")
+    B, T, Cy, Hs, Ws = measurement_shape(video.shape, scale, gray)
+    v = video if video.dtype == th.float64 else video.to(th.float32)
+    v = v.reshape(B, T, 3, Hs, int(scale), Ws, int(scale))
+    return (v.mean(dim=(2, 4, 6)).unsqueeze(2) if gray else v.mean(dim=(4, 6))).contiguous()
+
+
+def check_measurement(y, shape, scale=1, gray=False):
+    """The checks of a measurement against the video `shape` (B, T, 3, H, W) it constrains (no engine): the operator is served, H and W
+    are divisible by scale, y is a tensor of measurement_shape(shape, scale, gray) and every value of it is finite -- ValueError naming
+    the rule otherwise.  Returns y as contiguous float32, on the device it came on."""
+    want = measurement_shape(shape, scale, gray)
+    if not th.is_tensor(y) or tuple(y.shape) != want:
+        raise ValueError(f"y must be {want} for a video of {tuple(shape)} at scale={int(scale)}, gray={bool(gray)}, got "
+                         f"{tuple(getattr(y, 'shape', ()))}")
+    y = y.to(th.float32).contiguous()
+    if not bool(th.isfinite(y).all()):
+        raise ValueError("y must be finite: a measurement holds no NaN and no Inf")
+    return y
+
+
+def _measurement(model):
+    """The measurement the innermost measurement_scope set on this model (dict y, scale, gray), or None."""
+    return getattr(getattr(model, "model", model), "_measurement", None)
+
+
+def _engine_measurement(model, m):
+    """Engine state <- a measurement dict (y: a device tensor the caller keeps alive; scale; gray) or None (clear)."""
+    if m is None:
+        _lib.check(_lib.lib().vd_set_measurement(model._handle, None, 1, 0))
+    else:
+        _lib.check(_lib.lib().vd_set_measurement(model._handle, _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0))
+
+
+def _refuse_measurement(model, what):
+    if _measurement(model) is not None:
+        raise _lib.VdError(f"{what} inside measurement_scope is not served")
+
+
+def _check_step_measurement(model, shape):
+    m = _measurement(model)
+    if m is not None and tuple(m["y"].shape) != measurement_shape(shape, m["scale"], m["gray"]):
+        raise ValueError(f"measurement_scope: y {tuple(m['y'].shape)} against a step on {tuple(shape)} at scale={m['scale']}, gray={m['gray']}")
+
+
 class GaussianDiffusion:
     """gaussian_diffusion.py:107-172 (tables) + the sampling methods."""
+
+    measure = staticmethod(measure)          # diffusion.measure(video, scale, gray): the y of measurement_scope from a video
 
     def __init__(self, *, betas, model_mean_type, model_var_type, loss_type, rescale_timesteps=False):
         self.model_mean_type = model_mean_type
@@ -319,6 +398,37 @@ class GaussianDiffusion:
             base._known_region = before
             _engine_region(base, before)
 
+    @contextlib.contextmanager
+    def measurement_scope(self, model, y, scale=1, gray=False):
+        """This project's extension (DDNM, Wang, Yu, Zhang 2022): `with diffusion.measurement_scope(model, y, scale=4):` -- zero-shot
+        restoration from a degraded copy of the video.  y = measure(video, scale, gray), (B, T, Cy, H / scale, W / scale): the mean over
+        every scale x scale cell per channel, or over all three channels with gray=True (Cy = 1).  Every p_sample, ddim_sample and
+        dpmpp_2m_sample call inside, every loop built on them and p_mean_variance project the x_0 prediction of the step on the frames
+        with latent_mask == 1: x_0 + A^+(y - A x_0), every element of a cell moved by (y_cell - mean_cell(x_0)), behind the clamp of
+        clip_denoised (or the dynamic threshold in its place) and in front of the sampler's own arithmetic, whose clamp is then off
+        (include/vd_amd.h: vd_set_measurement).  'pred_xstart', 'mean' and dpmpp_2m's history are the projected x_0; at t == 0 every
+        sampler returns it, so measure(sample) == y up to rounding on the latent frames.  Served: scale 2, 4, 8 with either gray value
+        and scale 1 with gray=True; anything else, H or W not divisible by scale, a y of another shape or with a value that is not
+        finite raises ValueError (check_measurement).
+        Scopes nest; the measurement found before is back when the block ends, whatever it raised.  A WindowExecutor.begin inside the
+        scope takes y into its own buffers.  Composes with cfg_scale and guidance_scope.  Refused inside, by name: denoised_fn,
+        use_gradient_method, ddim_reverse_sample, and a known_region_scope on the same model (the engine refuses the step).  Not honoured
+        by model(...) itself, score_windows and the NLL path.  No claim about restoration quality is made."""
+        base = self._bind(model)
+        scale, gray = _check_operator(scale, gray)
+        if not th.is_tensor(y) or y.dim() != 5:
+            raise ValueError(f"y must be a (B, T, Cy, H / scale, W / scale) tensor, got {tuple(getattr(y, 'shape', ()))}")
+        B, T, Cy, Hs, Ws = y.shape
+        m = dict(y=_f32(check_measurement(y, (B, T, 3, Hs * scale, Ws * scale), scale, gray), base.device), scale=scale, gray=gray)
+        before = _measurement(base)
+        base._measurement = m
+        try:
+            _engine_measurement(base, m)
+            yield
+        finally:
+            base._measurement = before
+            _engine_measurement(base, before)
+
     def q_jump(self, x, t, latent_mask=None, noise=None, model=None):
         """This project's extension: one forward diffusion step x_{t-1} -> x_t at index t, the move RePaint's resampling walks back up
         with: on the frames with latent_mask == 1 (None: every frame) sqrt(1 - beta_t) x + sqrt(beta_t) noise, the other frames unchanged;
@@ -371,6 +481,7 @@ class GaussianDiffusion:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
             _refuse_known(model, "use_gradient_method")
+            _refuse_measurement(model, "use_gradient_method")
             if mode != 0 or denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method: p_sample without denoised_fn (the reference's ddim_sample "
                                           "has no such option, gaussian_diffusion.py:597-634)")
@@ -378,6 +489,7 @@ class GaussianDiffusion:
             return out["sample"], out["pred_xstart"]
         if denoised_fn is not None:
             _refuse_known(model, "denoised_fn")
+            _refuse_measurement(model, "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise,
                                  cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
@@ -408,6 +520,9 @@ class GaussianDiffusion:
             if region["src"].shape != xs.shape:
                 raise ValueError(f"known_region_scope: known_src {tuple(region['src'].shape)} against a step on {tuple(xs.shape)}")
             known_noise = region["noise"] if region["noise"] is not None else th.randn_like(xs)    # behind the sampler's own draw
+        if mode == 2:
+            _refuse_measurement(model, "ddim_reverse_sample")
+        _check_step_measurement(model, xs.shape)
         sample, xstart = th.empty_like(xs), th.empty_like(xs)
         B, T = xs.shape[:2]
         window = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt))
@@ -514,6 +629,7 @@ class GaussianDiffusion:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
             _refuse_known(model, "use_gradient_method")
+            _refuse_measurement(model, "use_gradient_method")
             if denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method with denoised_fn")
             g = self._guided(model, x, t, clip_denoised, model_kwargs or {}, _noise=getattr(self, "_guidance_noise", None))
@@ -521,8 +637,10 @@ class GaussianDiffusion:
             return {"mean": g["mean"], **self._variance(tt, g["mean"].shape), "pred_xstart": g["pred_xstart"], "attn": None,
                     "grad": g["grad"]}
         if denoised_fn is not None:
+            _refuse_measurement(model, "denoised_fn")
             return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, cfg_scale=cfg_scale)
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs or {})
+        _check_step_measurement(model, xs.shape)
         B, T = xs.shape[:2]
         mean, xstart, eps = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
         attn = model._attn_capture(B, T) if return_attn_weights else None
@@ -668,6 +786,7 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         _refuse_known(model, "ddim_reverse_sample")
+        _refuse_measurement(model, "ddim_reverse_sample")
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
@@ -686,6 +805,7 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         if denoised_fn is not None:
             _refuse_known(model, "denoised_fn")
+            _refuse_measurement(model, "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=3, prev_xstart=prev_xstart)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
         sample, xstart = self._fused_step(3, model, x, t, clip_denoised, model_kwargs, prev_xstart=prev_xstart)

@@ -45,7 +45,8 @@ def get_masks(x0, num_obs):
 def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size=1, optimal_schedule_path=None, *,
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
                 adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
-                cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1):
+                cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
+                measurement=None, sr_scale=1, gray=False):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -90,7 +91,23 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     engine's Philox stream on both executors, from a seed drawn per window from torch's global generator (the sampler's own noise stays
     th.randn_like on the eager executor): with a sampler that draws none, the two executors agree to the bit.  Refused with
     use_gradient_method, prefix_cache and suffix_skip, and n_resample > 1 with save_all_timesteps (the record has one slot per
-    timestep).  With known_mask=None no scope is entered and the engine is not touched."""
+    timestep).  With known_mask=None no scope is entered and the engine is not touched.
+
+    measurement, sr_scale, gray (this project's extension: zero-shot restoration, DDNM; both executors, every sampler; composes with
+    cfg_scale, cfg_rescale and dynamic_threshold): measurement = y over the WHOLE video, (B, T, Cy, H / sr_scale, W / sr_scale) with
+    Cy = 1 when gray else 3 -- what diffusion.measure(video, sr_scale, gray) returns.  Per window it is gathered by the window's frame
+    indices exactly as x0 is (per item in the adaptive-* modes) and the x_0 prediction of every step is projected onto it on the
+    window's latent frames (gaussian_diffusion.py: measurement_scope): measure(generated frames) == y up to rounding.  The observed
+    frames still come from `batch`, untouched.  Refused by name with use_gradient_method, prefix_cache, suffix_skip and known_mask.  With
+    measurement=None no scope is entered and the engine is not touched."""
+    if measurement is not None:
+        from . import _lib
+        from .gaussian_diffusion import check_measurement
+        measurement_v = check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray).cpu()   # before anything touches the engine
+        if known_mask is not None:
+            raise _lib.VdError("a measurement together with a known region (known_mask) is not served")
+        if use_gradient_method:
+            raise _lib.VdError("use_gradient_method together with a measurement is not served")
     if known_mask is not None:
         for name, on in (("use_gradient_method", use_gradient_method), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
             if on:
@@ -111,7 +128,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                                use_gradient_method=use_gradient_method, observed_frames=observed_frames, sampler=sampler, eta=eta,
                                executor=executor, adaptive_distance=adaptive_distance, prefix_cache=prefix_cache, suffix_skip=suffix_skip,
                                save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
-                               jump_length=jump_length, n_resample=n_resample)
+                               jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray)
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -175,10 +192,14 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         k_src = k_mask = None
         if known_mask is not None:     # the window's share of the region, gathered like x0
             k_src, k_mask = (gather_window(v, frame_indices).to(device) for v in (known_video_v, known_mask_v))
+        y_w = None
+        if measurement is not None:    # ... and so is the window's share of the measurement
+            y_w = gather_window(measurement_v, frame_indices).to(device)
         if use_graph:
             # renoise=False: like the eager loop below (and scripts/video_sample.py:149-166), every step reads x_t_minus_1 = x0 as it is
             write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, known_src=k_src,
-                                         known_mask=k_mask, jump_length=jump_length, n_resample=n_resample))
+                                         known_mask=k_mask, jump_length=jump_length, n_resample=n_resample, measurement=y_w,
+                                         sr_scale=sr_scale, gray=gray))
             model.check_device_errors()
             continue
         if known_mask is not None:
@@ -190,22 +211,23 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
         prev_xstart = None                                  # dpmpp_2m: the history is the window's own
-        for timestep in timesteps:
-            if sampler == "dpmpp_2m":
-                # (the step keeps the parameter list it was introduced with: its scale comes from the scope)
-                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                    out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
-                                                    model_kwargs=model_kwargs)
-                local_samples, prev_xstart = out["sample"], out["pred_xstart"]
-            elif sampler == "p_sample":
-                local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
-                                                   model_kwargs=model_kwargs, return_attn_weights=False,
-                                                   use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)["sample"]
-            else:
-                local_samples = diffusion.ddim_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
-                                                      model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)["sample"]
-            if trace is not None:
-                trace.append(local_samples.clone())
+        with (diffusion.measurement_scope(model, y_w, sr_scale, gray) if y_w is not None else contextlib.nullcontext()):
+            for timestep in timesteps:
+                if sampler == "dpmpp_2m":
+                    # (the step keeps the parameter list it was introduced with: its scale comes from the scope)
+                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                        out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
+                                                        model_kwargs=model_kwargs)
+                    local_samples, prev_xstart = out["sample"], out["pred_xstart"]
+                elif sampler == "p_sample":
+                    local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
+                                                       model_kwargs=model_kwargs, return_attn_weights=False,
+                                                       use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)["sample"]
+                else:
+                    local_samples = diffusion.ddim_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
+                                                          model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)["sample"]
+                if trace is not None:
+                    trace.append(local_samples.clone())
         write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
         model.check_device_errors()    # once per window (write_back has synchronised): a non-finite network output of any of its steps raises here
     return samples.numpy(), all_timestep_samples.numpy()
@@ -496,6 +518,14 @@ def build_parser():
                     help="with --known_mask: the source of the known pixels, (N, T, 3, H, W) indexed like --videos; float in [-1, 1] or uint8")
     ap.add_argument("--jump_length", type=int, default=1, help="with --known_mask and --n_resample > 1: steps per resampling jump")
     ap.add_argument("--n_resample", type=int, default=1, help="with --known_mask: times each level is walked (RePaint resampling); 1 = off")
+    ap.add_argument("--measurement", default=None, metavar="Y.npy",
+                    help="zero-shot restoration (DDNM): a degraded copy of the test videos, (N, T, Cy, H / S, W / S) float32 indexed like "
+                         "--videos, Cy = 1 with --gray else 3 -- the mean over every S x S cell per channel (--gray: over the three "
+                         "channels too); every generated frame reproduces it (needs --sr_scale and / or --gray)")
+    ap.add_argument("--sr_scale", type=int, default=1, choices=[1, 2, 4, 8],
+                    help="with --measurement: the cell size S of the measurement (super-resolution factor); 1 needs --gray")
+    ap.add_argument("--gray", type=str2bool, nargs="?", const=True, default=False,
+                    help="with --measurement: the measurement is greyscale, channel weights 1/3 each (colourisation)")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -533,6 +563,20 @@ def _known_options(args, batch):
     return kw
 
 
+def _measurement_options(args, batch):
+    """--measurement / --sr_scale / --gray of the job -> infer_video's keywords for this batch ({} without a measurement).  The
+    batch's dataset items are args._batch_ids (run() sets it)."""
+    path = getattr(args, "measurement", None)
+    if not path:
+        return {}
+    y = np.load(path, mmap_mode="r")
+    if y.ndim != 5:
+        raise ValueError(f"{path}: --measurement is (N, T, Cy, H / S, W / S), got {y.shape}")
+    T = batch.shape[1]
+    rows = np.stack([np.asarray(y[i][:T], dtype=np.float32) for i in args._batch_ids])
+    return dict(measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)))
+
+
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
     return infer_video(args.inference_mode, model, diffusion, batch, args.max_frames, args.obs_length, args.step_size,
                        optimal_schedule_path, use_gradient_method=getattr(args, "use_gradient_method", False),
@@ -542,13 +586,14 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
                        save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
                        cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None),
-                       **_known_options(args, batch))
+                       **_known_options(args, batch), **_measurement_options(args, batch))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
-    ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995') and a --known_mask -- samples of
-    different samplers or guidance settings never share a directory, and a run without the options keeps its name."""
+    ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
+    --measurement ('_sr4', '_gray', '_sr4gray') -- samples of different samplers or guidance settings never share a directory, and a run
+    without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
     phi = float(getattr(args, "cfg_rescale", 0.0) or 0.0)
@@ -557,8 +602,12 @@ def run_postfix(args):
     if getattr(args, "known_mask", None):         # '_known', '_known_j2r3' with resampling
         r = int(getattr(args, "n_resample", 1))
         known = "_known" + ("" if r == 1 else f"_j{int(getattr(args, 'jump_length', 1))}r{r}")
+    meas = ""
+    if getattr(args, "measurement", None):        # '_sr4', '_gray', '_sr4gray'
+        S = int(getattr(args, "sr_scale", 1))
+        meas = "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
-        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas
 
 
 def run(args, create=None, device=None, infer=None):
