@@ -639,6 +639,12 @@ int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, cons
  * launchers dispatch through the same function.  The batch size is no argument: it never changes the choice.  Tests use it
  * to know which kernel they exercised. */
 int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* name, int cap);
+/* The same for vd_op_attn_spatial (and the engine), in the process' own VD_MATH: "attn_spatial_split_kernel<F,F16,NW>" (f16x3: F16 =
+ * true, bf16x6: false; NW = 2 for L <= 64, 4 for L <= 128, 8 above), "attn_spatial_kernel<F>" (fp32), or "refused: <reason>" -- C not
+ * divisible by heads, a head dim F = C / heads outside {8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128}, a non-positive L, C or
+ * heads.  Same return values; host only; the launcher dispatches through the same table and vd_op_attn_spatial returns -1 for a
+ * refused shape before any launch.  The frame count is no argument: it never changes the choice. */
+int vd_attn_spatial_variant(int L, int C, int heads, char* name, int cap);
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
 /* Backward-data operators of use_gradient_method (csrc/backward.hip); each one synchronises its stream before it returns. */

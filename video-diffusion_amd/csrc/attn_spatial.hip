@@ -418,31 +418,57 @@ static int launch_attn_spatial_split(const AttnSpatialArgs& a, hipStream_t s) {
     VD_HIP(hipGetLastError());
     return 0;
 }
-template <int F, bool F16>
-static int launch_attn_spatial_nw(const AttnSpatialArgs& a, hipStream_t s) {
-    // tokens per block: the whole (frame, head) when it has <= 256 of them
-    if (a.L > 128) return launch_attn_spatial_split<F, F16, 8>(a, s);
-    if (a.L > 64) return launch_attn_spatial_split<F, F16, 4>(a, s);
-    return launch_attn_spatial_split<F, F16, 2>(a, s);
+template <int F>
+static int launch_attn_spatial_fp32(const AttnSpatialArgs& a, hipStream_t s) {
+    dim3 grid((a.L + 127) / 128, a.heads, a.nfr);
+    hipLaunchKernelGGL((attn_spatial_kernel<F>), grid, dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
+// Every instantiation behind launch_attn_spatial, 7 per head dim: the fp32 kernel (NW = 0), then f16x3 and bf16x6 at NW = 2, 4, 8.
+struct AttnSpatialRow {
+    int F, NW;
+    bool f16;
+    int (*launch)(const AttnSpatialArgs&, hipStream_t);
+};
+#define VD_ROWS(FV) {FV, 0, false, launch_attn_spatial_fp32<FV>},                                                                                                     \
+                    {FV, 2, true, launch_attn_spatial_split<FV, true, 2>}, {FV, 4, true, launch_attn_spatial_split<FV, true, 4>}, {FV, 8, true, launch_attn_spatial_split<FV, true, 8>},    \
+                    {FV, 2, false, launch_attn_spatial_split<FV, false, 2>}, {FV, 4, false, launch_attn_spatial_split<FV, false, 4>}, {FV, 8, false, launch_attn_spatial_split<FV, false, 8>}
+static const AttnSpatialRow kAttnSpatialRows[] = {VD_ROWS(8), VD_ROWS(16), VD_ROWS(24), VD_ROWS(32), VD_ROWS(40), VD_ROWS(48),
+                                                  VD_ROWS(56), VD_ROWS(64), VD_ROWS(80), VD_ROWS(96), VD_ROWS(112), VD_ROWS(128)};
+#undef VD_ROWS
+
+AttnSpatialVariant attn_spatial_variant(int L, int C, int heads) {
+    AttnSpatialVariant v{-1, 0, 0, false, nullptr};
+    if (!(L > 0 && heads > 0 && C > 0)) { v.why = "a positive token, head and channel count"; return v; }
+    if (C % heads != 0) { v.why = "channels divisible by heads"; return v; }
+    const int F = C / heads, mode = math_mode();
+    // tokens per block of the split kernels: the whole (frame, head) when it has <= 256 of them
+    const int NW = mode == MATH_FP32 ? 0 : L > 128 ? 8 : L > 64 ? 4 : 2;
+    const bool f16 = mode == MATH_F16X3;
+    for (int i = 0; i < (int)(sizeof(kAttnSpatialRows) / sizeof(kAttnSpatialRows[0])); ++i) {
+        const AttnSpatialRow& r = kAttnSpatialRows[i];
+        if (r.F == F && r.NW == NW && r.f16 == f16) return AttnSpatialVariant{i, F, NW, f16, nullptr};
+    }
+    v.why = "head dim one of 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128";
+    return v;
+}
+
+std::string attn_spatial_variant_name(const AttnSpatialVariant& v) {
+    if (v.row < 0) return std::string("refused: ") + (v.why ? v.why : "");
+    if (v.NW == 0) return "attn_spatial_kernel<" + std::to_string(v.F) + ">";
+    return "attn_spatial_split_kernel<" + std::to_string(v.F) + "," + (v.f16 ? "true" : "false") + "," + std::to_string(v.NW) + ">";
 }
 
 int launch_attn_spatial(const AttnSpatialArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.C % a.heads == 0, "channels divisible by heads");
-    const int F = a.C / a.heads;
-    dim3 grid((a.L + 127) / 128, a.heads, a.nfr);
-    const int mode = math_mode();
-    switch (F) {
-#define VD_CASE(FV) case FV: if (mode == MATH_FP32) hipLaunchKernelGGL((attn_spatial_kernel<FV>), grid, dim3(256), 0, s, a); \
-                             else if (mode == MATH_F16X3) { if (launch_attn_spatial_nw<FV, true>(a, s)) return -1; } \
-                             else { if (launch_attn_spatial_nw<FV, false>(a, s)) return -1; } break;
-        VD_CASE(8) VD_CASE(16) VD_CASE(24) VD_CASE(32) VD_CASE(40) VD_CASE(48) VD_CASE(56) VD_CASE(64) VD_CASE(80) VD_CASE(96) VD_CASE(112) VD_CASE(128)
-#undef VD_CASE
-        default:
-            set_error("spatial attention: unsupported head dim " + std::to_string(F));
-            return -1;
+    const AttnSpatialVariant v = attn_spatial_variant(a.L, a.C, a.heads);
+    if (v.row < 0) {
+        set_error(std::string("spatial attention: ") + v.why + " (L " + std::to_string(a.L) + ", C " + std::to_string(a.C) + ", heads " + std::to_string(a.heads) + ")");
+        return -1;
     }
-    VD_HIP(hipGetLastError());
-    return 0;
+    VD_REQUIRE(a.nfr > 0, "spatial attention: a positive frame count");
+    return kAttnSpatialRows[v.row].launch(a, s);
 }
 
 }  // namespace vd

@@ -2962,7 +2962,7 @@ int vd_op_gn_temporal(const float* x, const float* gamma, const float* beta, int
 }
 
 int vd_op_attn_spatial(const float* qkv, int nfr, int L, int C, int heads, float* out, void* stream) {
-    AttnSpatialArgs a{qkv, out, nfr, L, C, heads, 1.0f / sqrtf((float)(C / heads))};
+    AttnSpatialArgs a{qkv, out, nfr, L, C, heads, heads > 0 && C >= heads ? 1.0f / sqrtf((float)(C / heads)) : 0.f};     // (a refused shape: never read)
     return launch_attn_spatial(a, static_cast<hipStream_t>(stream));
 }
 
@@ -2979,6 +2979,15 @@ int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* nam
     VD_REQUIRE((int)n.size() < cap, "vd_attn_temporal_variant: name buffer too small");
     memcpy(name, n.c_str(), n.size() + 1);
     return v.family != AttnTemporalVariant::kRefused ? 1 : 0;
+}
+
+int vd_attn_spatial_variant(int L, int C, int heads, char* name, int cap) {
+    VD_REQUIRE(name && cap > 0, "vd_attn_spatial_variant: a name buffer");
+    const AttnSpatialVariant v = attn_spatial_variant(L, C, heads);
+    const std::string n = attn_spatial_variant_name(v);
+    VD_REQUIRE((int)n.size() < cap, "vd_attn_spatial_variant: name buffer too small");
+    memcpy(name, n.c_str(), n.size() + 1);
+    return v.row >= 0 ? 1 : 0;
 }
 
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w, const float* bias, int nfr,

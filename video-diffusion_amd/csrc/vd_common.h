@@ -315,6 +315,17 @@ void pack_linear_split(const float* w, unsigned short* out_base, int rows, int K
 int launch_conv_wino(const IgemmArgs& a, hipStream_t s);
 void pack_conv3_wino(const float* oihw, float* out, int O, int I);      // out: 16*O*I floats
 int launch_attn_spatial(const AttnSpatialArgs& a, hipStream_t s);
+// Which instantiation a spatial-attention shape runs on in this process' VD_MATH: the ONE place the choice is made (the table of
+// attn_spatial.hip).  launch_attn_spatial dispatches through it and vd_attn_spatial_variant() prints it.  A function of L, the head
+// dim and the mode alone (never of the frame count).  row: index into that table, -1 = refused.
+struct AttnSpatialVariant {
+    int row;
+    int F, NW;           // head dim; waves per block of attn_spatial_split_kernel, 0 = attn_spatial_kernel<F> (VD_MATH=fp32)
+    bool f16;            // the split kernel's F16
+    const char* why;     // refused: the requirement that failed
+};
+AttnSpatialVariant attn_spatial_variant(int L, int C, int heads);
+std::string attn_spatial_variant_name(const AttnSpatialVariant& v);     // e.g. "attn_spatial_split_kernel<64,true,8>"
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s);
 // Which instantiation a temporal-attention shape runs on: the ONE place the choice is made (attn_temporal.hip).  Both launchers
 // dispatch through it and vd_attn_temporal_variant() prints it, so what the tests ask for is what is launched.  A function of the
