@@ -109,14 +109,14 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * copies the flags to the host, clears them, and the host
  * mirror raises IndexError.  bit 0: timestep index out of range.  Raised by every entry that runs the network (the timestep map
  * in front of the forward: vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_guided_step,
- * the window executor's captured step), by vd_score_windows / vd_op_eps_mse and by vd_vb_terms.  The network-free passes
+ * vd_dps_step, the window executor's captured step), by vd_score_windows / vd_op_eps_mse, vd_op_dps_seed and by vd_vb_terms.  The network-free passes
  * vd_posterior_update, vd_posterior_from_xstart, vd_ddim_reverse_from_xstart, vd_dpmpp_2m_from_xstart and vd_q_sample (index -1 wraps
  * to the last row there; below -num_timesteps or above the last row is out of range) poison item b with NaN and do NOT raise
  * the bit: the range of t is their caller's to check (the host mirror reaches the *_from_xstart forms only behind
  * vd_p_mean_variance, which has raised it).  vd_prior_bpd reads no t.
  * bit 1: the network output a step consumed was not finite.  The reference would carry the NaN into its sample; here the clamp
  * of clip_denoised would turn it into a plausible -1, so the posterior kernels keep such an element NaN and set this bit
- * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step,
+ * (vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_posterior_update, vd_posterior_from_xstart, vd_vb_terms, vd_guided_step, vd_dps_step,
  * the window executor's captured step).  In the default f16x3 arithmetic (two fp16 pieces per fp32 operand) this is how an
  * operand beyond the split's range (|x| >= 2^15 = 32768: the scaled remainder (x - a0) 2^12 then leaves fp16; for a 3x3 conv the operand
  * is the Winograd-domain value, a signed sum of four inputs, so |input| < 2^13 is safe) anywhere in the network shows: VD_MATH=bf16x6
@@ -127,7 +127,7 @@ int vd_device_errors(vd_engine* e, int* flags);
 /* Longest window, in frames per batch item, that every forward / step / window entry point accepts: 128.  A window is any
  * T in 1..vd_max_window_frames() (the reference's UNet takes any T; --max_frames picks it at sampling time).  T <= 32 runs
  * on the original temporal attention / GroupNorm kernels, 33..128 on their long-window forms (key tiles with an online
- * softmax).  vd_guided_step (use_gradient_method) is limited to T <= 32.  Larger T fails with a message naming the limit. */
+ * softmax).  vd_guided_step (use_gradient_method) and vd_dps_step are limited to T <= 32.  Larger T fails with a message naming the limit. */
 int vd_max_window_frames(void);
 
 /* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
@@ -334,7 +334,8 @@ int vd_window_suffix_frames(vd_engine* e);
  * Honoured by vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance (whose `eps` output is then
  * out_g) and vd_window_begin / vd_window_run: the weight is part of a captured graph's signature, so a later vd_window_begin under
  * another w captures (or finds) another graph.  NOT honoured by vd_unet_forward, vd_guided_step, vd_score_windows, vd_vb_terms /
- * vd_prior_bpd (the NLL path scores the conditional model) and the vd_*_from_xstart / vd_posterior_update passes, which run no network.
+ * vd_prior_bpd (the NLL path scores the conditional model) and the vd_*_from_xstart / vd_posterior_update passes, which run no network;
+ * vd_dps_step fails by name while w != 1.
  * With w != 1, vd_window_begin fails while the prefix cache or the suffix skip is switched on (in the unconditional forward the
  * observed frames are padding whose content is whatever the window tensor holds: neither invariant nor meaningless), and a step fails
  * while an attention capture (vd_set_attn_capture) is armed.
@@ -370,7 +371,7 @@ int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long
  * (vd_workspace_bytes counts it): no allocation, no host round trip.  Honoured by the entries that honour cfg_scale (vd_p_sample,
  * vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_window_begin / vd_window_run) and NOT honoured by
  * vd_unet_forward, vd_guided_step (use_gradient_method), vd_score_windows, vd_vb_terms / vd_prior_bpd (the NLL path) and the
- * vd_*_from_xstart / vd_posterior_update passes.  vd_window_begin fails while an option that would act is set together with the prefix
+ * vd_*_from_xstart / vd_posterior_update passes; vd_dps_step fails by name while either is set.  vd_window_begin fails while an option that would act is set together with the prefix
  * cache or the suffix skip.  A caller's denoised_fn together with dynamic_threshold is refused on the Python side.
  * vd_op_cfg_rescale / vd_op_dynamic_threshold: the passes alone on [B][T][frame_elems] tensors with the [B*T] latent mask `lat`, no engine;
  * they allocate their scratch, wait for `stream` and free it.  out may alias an input; frame_elems % 4 != 0 or tensors that are not 16-byte
@@ -404,7 +405,7 @@ int vd_op_dynamic_threshold(const float* x0, const float* lat, int B, int T, lon
  * Honoured by vd_p_sample, vd_ddim_sample, vd_dpmpp_2m_sample and vd_window_begin / vd_window_run: the merge runs on `sample` right behind
  * the sampler pass; pred_xstart and eps stay the model's own.  vd_ddim_reverse_sample (and sampler 2 in a window) fails by name while it is
  * set: the merge noises to t - 1.  NOT honoured by vd_unet_forward, vd_p_mean_variance (it has no sample), vd_guided_step, vd_score_windows,
- * vd_vb_terms / vd_prior_bpd and the vd_*_from_xstart / vd_posterior_update passes.  It composes with cfg_scale, guidance rescale and
+ * vd_vb_terms / vd_prior_bpd and the vd_*_from_xstart / vd_posterior_update passes; vd_dps_step fails by name while it is set.  It composes with cfg_scale, guidance rescale and
  * dynamic thresholding: they act before or inside the sampler pass, the merge behind it.
  * In a window the two addresses are part of the graph's signature; known_noise must be NULL: the draws come from the window's own Philox
  * pair at offset + B*per/4, and EVERY sampler's captured step then advances the counter by B*per -- sampler 3 (dpmpp_2m_sample) included,
@@ -453,7 +454,7 @@ int vd_window_jump(vd_engine* e, int n, void* stream);
  * threshold in its place, the projection, then the sampler pass on the projected x_0 with its clamp off -- pred_xstart, the mean and
  * dpmpp_2m's history are the projected x_0, and at t == 0, where every sampler returns x_0, A(sample) = y up to rounding on the latent
  * frames.  With no measurement set a step launches exactly what it launched before.
- * Fails by name: vd_ddim_reverse_sample (sampler 2 in a window), vd_guided_step (use_gradient_method), a window with the prefix cache or
+ * Fails by name: vd_ddim_reverse_sample (sampler 2 in a window), vd_guided_step (use_gradient_method), vd_dps_step, a window with the prefix cache or
  * the suffix skip on, and a measurement together with a known region (vd_set_known_region; not built).  NOT honoured by vd_unet_forward,
  * vd_score_windows, vd_vb_terms / vd_prior_bpd and the vd_*_from_xstart / vd_posterior_update passes.
  * In a window y's address, scale and gray are part of the graph's signature: one graph per (signature, scale, gray).
@@ -506,6 +507,44 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs_
                    const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int clip_denoised,
                    const float* x_t_minus_1, const float* noise, const float* noise2, float* mean, float* pred_xstart,
                    float* grad, float* sample, void* stream);
+
+/* Diffusion posterior sampling for noisy measurements -- this project's extension (DPS: Chung, Kim, McCann, Klasky, Ye, ICLR 2023; the
+ * reference has nothing like it).  Where a measurement (vd_set_measurement, DDNM) takes y = A x as exact and copies its noise into every
+ * frame, DPS moves the sample of every reverse step down the gradient of rho_b = ||y - A x_0(x_t)||_2 with respect to x_t -- a derivative
+ * through the whole UNet, on the backward-data pass of use_gradient_method (second packed image: vd_set_bwd_weight_storage).  No claim about
+ * restoration quality is made here: what is pinned is the arithmetic.
+ * The operators and y's layout are the measurement's ("cell mean": scale 2, 4, 8, or any of 1, 2, 4, 8 with gray); n_c = scale^2, with
+ * gray 3 scale^2, is the number of elements of a cell.  Per item b, with L_b its frames with latent_mask == 1, for an epsilon model at t:
+ *   1. eps: the taped forward of the window as the plain step runs it (the caller's masks and obs_mode; obs_src is a constant);
+ *   2. x_0r = a x_t - b eps (a = sqrt_recip_alphas_cumprod[t], b = sqrt_recipm1_alphas_cumprod[t]; two rounded products, one
+ *      subtraction), x_0 = clamp(x_0r, -1, 1) with clip_denoised -- the x_0 head of every sampler pass;
+ *   3. r = y - A x_0 on the cells of the frames in L_b, 0 elsewhere; rho_b = sqrt(sum r^2): the sum in fp64 in a fixed order that does
+ *      not depend on B (an item handed alone gives the same bits), rounded once to fp32; no floating-point atomics;
+ *   4. q = -r_cell / (rho_b n_c) on every element of a cell (0 where rho_b == 0 or L_b is empty), q_r = q [-1 <= x_0r <= 1] with
+ *      clip_denoised, d eps = -b q_r, d_x = a q_r: one fp32 rounding each (rho_b n_c is exact without gray);
+ *   5. g = d_x + (d eps / d x_t)^T d eps: the backward-data pass on a power-of-two multiple of d eps, as vd_guided_step runs it;
+ *   6. sample' and pred_xstart: the plain sampler pass (sampler 0 p_sample, 1 ddim_sample with eta) on (x_t, eps) with `noise` -- the
+ *      bits of vd_p_sample / vd_ddim_sample with the same noise;
+ *   7. sample = fmaf(-zeta, g, sample') on the frames of L_b; every other frame keeps the bits of sample'.
+ * This is x_{t-1} = x'_{t-1} - zeta grad ||y - A x_0||_2 of the official implementation, per batch item.  zeta = 0 is the plain step.
+ * Outputs: sample, pred_xstart; grad (g on every frame: 0 on observed frames, the network's own gradient on padding frames) and
+ * residual_norm ([B], rho_b) may be NULL.  `noise` is explicit.  Plain launches on `stream`, no host wait; the workspace is the guided
+ * step's (r and the partial sums lie in spare slots of its tail), and a plain step behind it has its usual bits.  A t[b] outside the
+ * schedule poisons item b with NaN as the sampler pass does; a network output that is not finite sets VD_ERR_NONFINITE through it.
+ * Fails by name: T above 32, a model that is not epsilon-prediction, a missing backward image, a sampler other than 0 or 1, zeta
+ * negative or not finite, an operator that is not served or an image size not divisible by scale, and engine state that would act on
+ * a plain step: cfg_scale != 1, guidance rescale, dynamic threshold, a known region, a measurement, an armed attention capture.
+ * Not part of vd_window_begin / vd_window_run: eager steps only.
+ * vd_op_dps_seed: steps 2-4 alone on a caller's (x_t, eps) on frames of H x W (any size; the engine's image size is not read), no network:
+ * d_eps, d_x, rho ([B], may be NULL) and pred_xstart (x_0 of every frame, may be NULL).  It allocates its scratch, waits for `stream` and
+ * frees it.  16-byte accesses while W % 4 == 0 and the tensors are 16-byte aligned, else element by element: same bits. */
+int vd_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, int clip_denoised,
+                int sampler, float eta, const float* noise, const float* y, int scale, int gray, float zeta, float* sample,
+                float* pred_xstart, float* grad, float* residual_norm, void* stream);
+int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, const float* eps, const long long* t, int clip_denoised,
+                   const float* y, const float* latent_mask, int scale, int gray, float* d_eps, float* d_x, float* rho,
+                   float* pred_xstart, void* stream);
 
 /* diffusion.q_sample(x_start, t, noise) (gaussian_diffusion.py:190-206). */
 int vd_q_sample(vd_engine* e, int B, long long per_sample, const float* x_start, const long long* t,

@@ -2760,6 +2760,91 @@ int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs,
     return rc;
 }
 
+// One step of diffusion posterior sampling (dps.hip) on a measurement y of the "cell mean" operators.  The network sees the window as the
+// plain step hands it over -- the caller's masks and obs_mode -- under the tape; the sampler pass writes the plain step's sample' and
+// pred_xstart; the residual and seed passes give rho_b and its cotangents, the backward-data pass carries d eps to x_t (on a power-of-two
+// multiple, launch_grad_rescale), and the final pass moves the latent frames: sample = fmaf(-zeta, g, sample').  Plain launches on
+// `stream`, no host wait.  The workspace is the guided step's: r and the partials lie in the two spare slots of its tail.
+int vd_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                const long long* fidx, const long long* t, int obs_mode, int clip, int sampler, float eta, const float* noise,
+                const float* y, int scale, int gray, float zeta, float* sample, float* xstart, float* grad, float* residual_norm,
+                void* stream) {
+    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
+    if (rc) return rc;
+    VD_REQUIRE(T <= kMaxGuidedWindowFrames, "dps: windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
+                                            " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
+    VD_REQUIRE(e->mean_type == 0, "dps: epsilon-prediction models only");
+    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, "dps: the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
+    VD_REQUIRE(sampler == SAMPLER_P || sampler == SAMPLER_DDIM, "dps: p_sample (0) or ddim_sample (1), got sampler " + std::to_string(sampler));
+    VD_REQUIRE(sampler == SAMPLER_P || eta >= 0.f, "eta");
+    VD_REQUIRE(zeta >= 0.f && zeta <= 3.4028234e38f, "dps: zeta must be finite and not negative");
+    VD_REQUIRE(measurement_served(scale, gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
+    VD_REQUIRE(e->cfg.image_size % scale == 0, "measurement: H and W must be divisible by scale");
+    VD_REQUIRE(e->cfg_w == 1.f, "dps together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
+    VD_REQUIRE(e->guid_phi == 0.f, "dps together with guidance_rescale (vd_set_guidance_rescale) is not served");
+    VD_REQUIRE(e->dyn_p == 0.f, "dps together with dynamic_threshold (vd_set_dynamic_threshold) is not served");
+    VD_REQUIRE(!e->known_src, "dps together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(!e->meas_y, "dps together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "dps together with return_attn_weights is not served");
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && noise && y && sample && xstart, "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = e->ensure_ws_guided(B, T))) return rc;
+    const int S = e->cfg.image_size;
+    const size_t per = (size_t)T * 3 * S * S, tot = (size_t)B * per;
+    VD_REQUIRE(B <= 256, "dps: at most 256 items");
+    // tail of the workspace, as the guided step lays it out: t_model and the rescale words, then eps, deps, dxd, (free), dx_net, (free), r, partials
+    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
+    float* tm = reinterpret_cast<float*>(tail);
+    float* gs = tm + 768;
+    float* buf = reinterpret_cast<float*>(tail + 4096);
+    float *eps = buf, *deps = buf + tot, *dxd = buf + 2 * tot, *dxn = buf + 4 * tot, *rbuf = buf + 6 * tot;
+    double* part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(buf + 7 * tot) + 7) & ~(uintptr_t)7);
+    VD_REQUIRE((size_t)B * dps_partials_per_item() * sizeof(double) + 8 <= tot * sizeof(float), "dps: window too small for its partial sums");
+    map_t(e, t, B, tm, st);
+    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);       // forward + backward live below the step's own buffers
+    Tape tp; e->tape = &tp;
+    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
+    rc = e->forward(fi, st, ar);
+    if (!rc) {
+        SamplerPassArgs pa = pass_args(e, sampler, B, (long long)per, x, t, clip, sample, xstart);
+        pa.eps = eps; pa.eta = eta; pa.noise = noise;
+        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
+        rc = launch_sampler_pass(pa, st);
+    }
+    if (!rc) {
+        DpsArgs da{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, S, S, scale, gray ? 1 : 0, clip,
+                   rbuf, part, deps, dxd, nullptr, residual_norm, e->d_err};
+        ProfScope ps(PC_ELEMENTWISE, 4.0 * B * per, 4.0 * B * per * 6.0, st, "dps_seed");
+        rc = launch_dps_seed(da, st);
+    }
+    if (!rc) rc = launch_grad_rescale(deps, tot, gs, st);
+    if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
+    if (!rc) {
+        ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "dps_final");
+        rc = launch_dps_final(dxd, dxn, gs, lat, B, T, (long)(per / T), zeta, sample, grad, st);
+    }
+    e->tape = nullptr;
+    return rc;
+}
+
+// The residual and seed passes of vd_dps_step alone, on a caller's (x_t, eps): no network, no workspace of the engine (tests).
+int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, const float* eps, const long long* t, int clip,
+                   const float* y, const float* lat, int scale, int gray, float* deps, float* dxd, float* rho, float* xstart,
+                   void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && x && eps && t && y && lat && deps && dxd, "arguments");
+    VD_REQUIRE(measurement_served(scale, gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
+    VD_REQUIRE(H % scale == 0 && W % scale == 0, "measurement: H and W must be divisible by scale");
+    OpScratch sc(stream);
+    float* rbuf; double* part;
+    int rc = sc.get(&rbuf, (size_t)B * T * (gray ? 1 : 3) * (H / scale) * (W / scale));
+    if (!rc) rc = sc.get(&part, (size_t)B * dps_partials_per_item());
+    if (rc) return rc;
+    DpsArgs da{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, scale, gray ? 1 : 0, clip,
+               rbuf, part, deps, dxd, xstart, rho, e->d_err};
+    return launch_dps_seed(da, static_cast<hipStream_t>(stream));
+}
+
 int vd_q_sample(vd_engine* e, int B, long long per, const float* x0, const long long* t, const float* noise, float* out,
                 void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");

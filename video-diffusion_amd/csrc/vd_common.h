@@ -566,6 +566,37 @@ struct MeasureArgs {
 inline bool measurement_served(int scale, int gray) { return scale == 2 || scale == 4 || scale == 8 || (scale == 1 && gray); }
 int launch_measurement_project(const MeasureArgs& a, hipStream_t s);
 
+// Diffusion posterior sampling (dps.hip; this project's extension, DPS: Chung et al. 2023) on the operators above.  Tensors are
+// [B][T][3][H][W], y [B][T][Cy][H/scale][W/scale], `lat` the [B*T] latent mask.  launch_dps_seed, two launches: per item b, over the cells
+// of its frames with lat == 1, r = y - A x_0 with x_0 = pass_x0(x, eps, ...) at t[b] (clamped when `clip`), rho_b = sqrt(sum r^2) -- the
+// sum folded in fp64 in a fixed order that does not depend on B, rounded once to fp32 -- and the cotangents of rho_b: q = -r_cell / (rho_b n_c)
+// on every element of a cell (n_c = scale^2, gray: 3 scale^2), q_r = q where !clip or -1 <= x_0r <= 1 else 0, deps = -sqrt_recipm1[t] q_r,
+// dxd = sqrt_recip[t] q_r; 0 on every other frame, and everywhere for an item with rho_b == 0 or no latent frame.  A t[b] outside the
+// schedule: NaN in deps, dxd, rho and xstart of item b, and bit 0 of `err`.  16-byte accesses while W % 4 == 0 and the tensors are
+// 16-byte aligned, else element by element: same bits.  No floating-point atomics.
+struct DpsArgs {
+    const float* x;         // x_t
+    const float* eps;       // the network output
+    const float* y;
+    const float* lat;
+    const int64_t* t;       // [B] respaced index
+    const float* tab; int num_timesteps;
+    int B, T, H, W;
+    int scale, gray, clip;
+    float* r;               // scratch: y's shape
+    double* part;           // scratch: [B][dps_partials_per_item()]
+    float* deps; float* dxd;
+    float* xstart;          // the x_0 prediction of every frame (the sampler pass's bits), or null
+    float* rho;             // [B], or null
+    int* err;               // the engine's sticky error word, or null
+    int nblk = 0;           // set by launch_dps_seed: partials per item of this launch
+};
+size_t dps_partials_per_item();
+int launch_dps_seed(DpsArgs a, hipStream_t s);
+// g = dxd + dx_net * gs[1] (launch_grad_rescale's 1 / s) -> grad (or null); sample = fmaf(-zeta, g, sample) on the frames with lat == 1
+int launch_dps_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, float zeta,
+                     float* sample, float* grad, hipStream_t s);
+
 enum { TAB_SQRT_RECIP = 0, TAB_SQRT_RECIPM1, TAB_COEF1, TAB_COEF2, TAB_LOGVAR, TAB_ACP, TAB_ACP_PREV,
        TAB_SQRT_ACP, TAB_SQRT_1M_ACP, TAB_POST_LOGVAR, TAB_LOG_1M_ACP, TAB_ALPHA, NTAB };
 

@@ -253,6 +253,26 @@ def _check_step_measurement(model, shape):
         raise ValueError(f"measurement_scope: y {tuple(m['y'].shape)} against a step on {tuple(shape)} at scale={m['scale']}, gray={m['gray']}")
 
 
+def _dps(model):
+    """The DPS setting the innermost dps_scope set on this model (dict y, scale, gray, zeta), or None."""
+    return getattr(getattr(model, "model", model), "_dps", None)
+
+
+def check_zeta(zeta):
+    """The DPS step size as a float: finite and not negative, ValueError otherwise (no engine)."""
+    if isinstance(zeta, bool) or not isinstance(zeta, (int, float, np.integer, np.floating)):
+        raise ValueError(f"zeta={zeta!r}: the DPS step size must be a number")
+    z = float(zeta)
+    if not (math.isfinite(z) and z >= 0.0):
+        raise ValueError(f"zeta={zeta!r}: the DPS step size must be finite and not negative")
+    return z
+
+
+def _refuse_dps(model, what):
+    if _dps(model) is not None:
+        raise _lib.VdError(f"{what} inside dps_scope is not served")
+
+
 class GaussianDiffusion:
     """gaussian_diffusion.py:107-172 (tables) + the sampling methods."""
 
@@ -351,7 +371,8 @@ class GaussianDiffusion:
         classifier-free guidance weight w on the observed frames (p_sample's docstring), the keyword-less ones included:
         ddim_reverse_sample with its two loops and dpmpp_2m_sample keep the parameter lists they were introduced with and take
         their scale from here.  The scale found before is back when the block ends, whatever it raised.  Not honoured by
-        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_cfg_scale)."""
+        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_cfg_scale); a step inside
+        dps_scope refuses a scale other than 1 by name."""
         cfg_scale = _check_cfg(cfg_scale)
         return _cfg_scope(self._bind(model), cfg_scale)
 
@@ -367,7 +388,8 @@ class GaussianDiffusion:
         -- torch.quantile's linear interpolation between two exact order statistics -- and x_0 <- clamp(x_0, -s, s) / s in place of the
         clamp to [-1, 1]; works at any cfg_scale.  Refused together with denoised_fn.
         Either option is refused together with the window executor's prefix_cache or suffix_skip, and neither is honoured by
-        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_guidance_rescale)."""
+        model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_guidance_rescale); a step
+        inside dps_scope refuses either option by name."""
         phi, p = _check_guidance(cfg_rescale, dynamic_threshold)
         return _guidance_scope(self._bind(model), phi, p)
 
@@ -382,7 +404,8 @@ class GaussianDiffusion:
         Draw order of a step: the sampler's own noise first (p_sample, ddim_sample), then z = th.randn_like(x), at every t (t == 0 reads
         none of it); the noise is handed to the engine for the length of the call.  `known_noise` fixes z for every step inside (tests).
         Scopes nest; the region found before is back when the block ends, whatever it raised.  A WindowExecutor.begin inside the scope
-        takes the region into its own buffers.  Refused inside: denoised_fn, use_gradient_method, ddim_reverse_sample.  Not honoured by
+        takes the region into its own buffers.  Refused inside: denoised_fn, use_gradient_method, ddim_reverse_sample, and by a step inside
+        dps_scope.  Not honoured by
         model(...) itself, p_mean_variance, score_windows and the NLL path.  No claim about sample quality is made."""
         base = self._bind(model)
         src, mask = check_known_region(known_src, known_mask)
@@ -412,8 +435,9 @@ class GaussianDiffusion:
         finite raises ValueError (check_measurement).
         Scopes nest; the measurement found before is back when the block ends, whatever it raised.  A WindowExecutor.begin inside the
         scope takes y into its own buffers.  Composes with cfg_scale and guidance_scope.  Refused inside, by name: denoised_fn,
-        use_gradient_method, ddim_reverse_sample, and a known_region_scope on the same model (the engine refuses the step).  Not honoured
-        by model(...) itself, score_windows and the NLL path.  No claim about restoration quality is made."""
+        use_gradient_method, ddim_reverse_sample, and a known_region_scope on the same model (the engine refuses the step); a step inside
+        a dps_scope on the same model refuses this scope by name.  Not honoured by model(...) itself, score_windows and the NLL path.  For a
+        y that carries noise see dps_scope.  No claim about restoration quality is made."""
         base = self._bind(model)
         scale, gray = _check_operator(scale, gray)
         if not th.is_tensor(y) or y.dim() != 5:
@@ -428,6 +452,71 @@ class GaussianDiffusion:
         finally:
             base._measurement = before
             _engine_measurement(base, before)
+
+    @contextlib.contextmanager
+    def dps_scope(self, model, y, scale=1, gray=False, *, zeta):
+        """This project's extension (DPS: Chung, Kim, McCann, Klasky, Ye, ICLR 2023): `with diffusion.dps_scope(model, y, scale=4,
+        zeta=0.5):` -- restoration from a NOISY degraded copy of the video.  y, scale and gray are measurement_scope's (y =
+        measure(video, scale, gray) plus whatever noise the footage carries); where measurement_scope takes y as exact and projects x_0
+        onto it, every p_sample and ddim_sample call inside, and every loop built on them, runs the plain step and then moves the
+        frames with latent_mask == 1 down the gradient of rho = ||y - A x_0(x_t)||_2 with respect to x_t, per batch item:
+        sample = fmaf(-zeta, grad, sample_plain) (include/vd_amd.h: vd_dps_step).  The gradient runs through the whole UNet on the
+        backward pass of use_gradient_method, so a step costs what that step costs; windows of at most 32 frames, epsilon-prediction
+        models.  The returned dict gains 'residual_norm' (B,), rho per item, and 'grad', the gradient on every frame (0 on observed
+        frames); 'pred_xstart' is the plain step's, and zeta = 0 is the plain step to the bit.  The sampler noise is drawn once per step,
+        where the plain step draws it.  zeta is required: finite and not negative, ValueError otherwise; y is checked as
+        measurement_scope checks it.
+        Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name:
+        dpmpp_2m_sample, ddim_reverse_sample, denoised_fn, use_gradient_method, cfg_scale != 1, guidance_scope with either option set,
+        known_region_scope and measurement_scope on the same model, return_attn_weights, and WindowExecutor.begin.  Not honoured by
+        model(...) itself, p_mean_variance, score_windows and the NLL path.  No claim about restoration quality is made."""
+        base = self._bind(model)
+        scale, gray = _check_operator(scale, gray)
+        zeta = check_zeta(zeta)
+        if not th.is_tensor(y) or y.dim() != 5:
+            raise ValueError(f"y must be a (B, T, Cy, H / scale, W / scale) tensor, got {tuple(getattr(y, 'shape', ()))}")
+        B, T, Cy, Hs, Ws = y.shape
+        d = dict(y=_f32(check_measurement(y, (B, T, 3, Hs * scale, Ws * scale), scale, gray), base.device), scale=scale, gray=gray,
+                 zeta=zeta)
+        before = _dps(base)
+        base._dps = d
+        try:
+            yield
+        finally:
+            base._dps = before
+
+    def _dps_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                  use_gradient_method, cfg_scale):
+        """One p_sample (mode 0) / ddim_sample (mode 1) step inside dps_scope -> dict sample, pred_xstart, grad, residual_norm."""
+        d = _dps(model)
+        if self.model_mean_type != ModelMeanType.EPSILON:
+            raise NotImplementedError("dps_scope with predict_xstart=True: epsilon-prediction models only")
+        for flag, what in ((denoised_fn is not None, "denoised_fn"), (use_gradient_method, "use_gradient_method"),
+                           (return_attn_weights, "return_attn_weights"), (cfg_scale != 1.0, "cfg_scale != 1")):
+            if flag:
+                _refuse_dps(model, what)
+        base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
+        L = _lib.lib()
+        if L.vd_cfg_scale(base._handle) != 1.0:
+            _refuse_dps(base, "cfg_scale != 1 (cfg_scale_scope)")
+        if L.vd_guidance_rescale(base._handle) != 0.0 or L.vd_dynamic_threshold(base._handle) != 0.0:
+            _refuse_dps(base, "guidance_scope with cfg_rescale or dynamic_threshold set")
+        if _known(base) is not None:
+            _refuse_dps(base, "known_region_scope")
+        if _measurement(base) is not None:
+            _refuse_dps(base, "measurement_scope")
+        if tuple(d["y"].shape) != measurement_shape(xs.shape, d["scale"], d["gray"]):
+            raise ValueError(f"dps_scope: y {tuple(d['y'].shape)} against a step on {tuple(xs.shape)} at scale={d['scale']}, gray={d['gray']}")
+        base._require_guidance()
+        noise = th.randn_like(xs) if noise is None else _f32(noise, base.device)
+        assert noise.shape == xs.shape
+        B, T = xs.shape[:2]
+        sample, xstart, grad = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
+        rho = th.empty(B, dtype=th.float32, device=base.device)
+        _lib.check(L.vd_dps_step(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0,
+                                 mode, float(eta), _lib.ptr(noise), _lib.ptr(d["y"]), d["scale"], 1 if d["gray"] else 0, d["zeta"],
+                                 _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
+        return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
 
     def q_jump(self, x, t, latent_mask=None, noise=None, model=None):
         """This project's extension: one forward diffusion step x_{t-1} -> x_t at index t, the move RePaint's resampling walks back up
@@ -477,6 +566,11 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
+        self._last_dps = None
+        if _dps(model) is not None:                                # p_sample / ddim_sample inside dps_scope: the plain step, then the DPS move
+            self._last_dps = self._dps_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                                            use_gradient_method, cfg_scale)
+            return self._last_dps["sample"], self._last_dps["pred_xstart"]
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
@@ -772,12 +866,17 @@ class GaussianDiffusion:
         other value costs a second forward."""
         sample, xstart = self._step(0, model, x, t, clip_denoised, denoised_fn, model_kwargs, 0.0, None,
                                     return_attn_weights, use_gradient_method, cfg_scale)
-        return {"sample": sample, "pred_xstart": xstart, "attn": self._last_attn if return_attn_weights else None}
+        return {"sample": sample, "pred_xstart": xstart, "attn": self._last_attn if return_attn_weights else None, **self._dps_extras()}
+
+    def _dps_extras(self):
+        """'grad' and 'residual_norm' of the step just made inside dps_scope; nothing outside it."""
+        d = getattr(self, "_last_dps", None)
+        return {} if d is None else {"grad": d["grad"], "residual_norm": d["residual_norm"]}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:597-634."""
         sample, xstart = self._step(1, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, None, cfg_scale=cfg_scale)
-        return {"sample": sample, "pred_xstart": xstart}
+        return {"sample": sample, "pred_xstart": xstart, **self._dps_extras()}
 
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
         """gaussian_diffusion.py:636-668: x_{t+1} from x_t by the DDIM reverse ODE.  Deterministic: no noise is drawn."""
@@ -787,6 +886,7 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         _refuse_known(model, "ddim_reverse_sample")
         _refuse_measurement(model, "ddim_reverse_sample")
+        _refuse_dps(model, "ddim_reverse_sample")
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
@@ -803,6 +903,7 @@ class GaussianDiffusion:
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
+        _refuse_dps(model, "dpmpp_2m_sample")
         if denoised_fn is not None:
             _refuse_known(model, "denoised_fn")
             _refuse_measurement(model, "denoised_fn")

@@ -46,7 +46,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
                 adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
-                measurement=None, sr_scale=1, gray=False):
+                measurement=None, sr_scale=1, gray=False, dps_zeta=None):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -99,7 +99,25 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     indices exactly as x0 is (per item in the adaptive-* modes) and the x_0 prediction of every step is projected onto it on the
     window's latent frames (gaussian_diffusion.py: measurement_scope): measure(generated frames) == y up to rounding.  The observed
     frames still come from `batch`, untouched.  Refused by name with use_gradient_method, prefix_cache, suffix_skip and known_mask.  With
-    measurement=None no scope is entered and the engine is not touched."""
+    measurement=None no scope is entered and the engine is not touched.
+
+    dps_zeta (this project's extension: diffusion posterior sampling, DPS, for a measurement that carries NOISE; eager executor,
+    samplers 'p_sample' and 'ddim'): with a step size zeta given, the measurement -- gathered per window exactly as above -- drives
+    gaussian_diffusion.py: dps_scope in place of the projection: every step is the plain step followed by a move of the window's latent
+    frames down the gradient of ||y - A x_0(x_t)||_2, through the whole UNet (windows of at most 32 frames).  Refused by name before the
+    engine is touched: no measurement, executor='graph', prefix_cache, suffix_skip, sampler='dpmpp_2m', use_gradient_method, known_mask,
+    cfg_scale != 1, cfg_rescale and dynamic_threshold.  None (default): the projection, as before."""
+    if dps_zeta is not None:
+        from . import _lib
+        from .gaussian_diffusion import check_zeta
+        dps_zeta = check_zeta(dps_zeta)
+        if measurement is None:
+            raise ValueError("dps_zeta needs a measurement (measurement=, sr_scale=, gray=)")
+        for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
+                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("cfg_scale != 1", float(cfg_scale) != 1.0),
+                         ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
+            if on:
+                raise _lib.VdError(f"{name} together with dps_zeta is not served")
     if measurement is not None:
         from . import _lib
         from .gaussian_diffusion import check_measurement
@@ -211,7 +229,13 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
         prev_xstart = None                                  # dpmpp_2m: the history is the window's own
-        with (diffusion.measurement_scope(model, y_w, sr_scale, gray) if y_w is not None else contextlib.nullcontext()):
+        if y_w is None:
+            scope = contextlib.nullcontext()
+        elif dps_zeta is not None:
+            scope = diffusion.dps_scope(model, y_w, sr_scale, gray, zeta=dps_zeta)
+        else:
+            scope = diffusion.measurement_scope(model, y_w, sr_scale, gray)
+        with scope:
             for timestep in timesteps:
                 if sampler == "dpmpp_2m":
                     # (the step keeps the parameter list it was introduced with: its scale comes from the scope)
@@ -406,6 +430,8 @@ def load_model(args, device, rank=0, world=1, create=None):
             holder["sd"] = {k: torch.from_numpy(synth_param(k, s)) for k, s in model.param_specs()}
         return holder["sd"]
 
+    if rank == 0 and getattr(args, "dps_zeta", None) is not None:
+        model.enable_guidance()      # --dps_zeta runs the backward-data pass: rank 0 packs the second image, share_weights broadcasts it
     vdist.share_weights(model, state_dict_fn, rank)
     return model, diffusion
 
@@ -526,6 +552,10 @@ def build_parser():
                     help="with --measurement: the cell size S of the measurement (super-resolution factor); 1 needs --gray")
     ap.add_argument("--gray", type=str2bool, nargs="?", const=True, default=False,
                     help="with --measurement: the measurement is greyscale, channel weights 1/3 each (colourisation)")
+    ap.add_argument("--dps_zeta", type=float, default=None, metavar="Z",
+                    help="with --measurement: diffusion posterior sampling (DPS) for a measurement that carries noise -- every step moves the "
+                         "generated frames down the gradient of ||y - A x_0||_2 through the network with step size Z, in place of the exact "
+                         "projection; eager executor, samplers p_sample and ddim; named in the run directory when set")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -567,14 +597,18 @@ def _measurement_options(args, batch):
     """--measurement / --sr_scale / --gray of the job -> infer_video's keywords for this batch ({} without a measurement).  The
     batch's dataset items are args._batch_ids (run() sets it)."""
     path = getattr(args, "measurement", None)
+    zeta = getattr(args, "dps_zeta", None)
     if not path:
+        if zeta is not None:
+            raise ValueError("--dps_zeta needs --measurement")
         return {}
     y = np.load(path, mmap_mode="r")
     if y.ndim != 5:
         raise ValueError(f"{path}: --measurement is (N, T, Cy, H / S, W / S), got {y.shape}")
     T = batch.shape[1]
     rows = np.stack([np.asarray(y[i][:T], dtype=np.float32) for i in args._batch_ids])
-    return dict(measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)))
+    return dict(measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)),
+                **({} if zeta is None else dict(dps_zeta=float(zeta))))
 
 
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
@@ -592,7 +626,7 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
-    --measurement ('_sr4', '_gray', '_sr4gray') -- samples of different samplers or guidance settings never share a directory, and a run
+    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5') -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
@@ -606,6 +640,8 @@ def run_postfix(args):
     if getattr(args, "measurement", None):        # '_sr4', '_gray', '_sr4gray'
         S = int(getattr(args, "sr_scale", 1))
         meas = "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
+        if getattr(args, "dps_zeta", None) is not None:
+            meas += f"_dps{float(args.dps_zeta):g}"
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
         ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas
 
