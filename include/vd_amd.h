@@ -684,6 +684,37 @@ int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* nam
  * heads.  Same return values; host only; the launcher dispatches through the same table and vd_op_attn_spatial returns -1 for a
  * refused shape before any launch.  The frame count is no argument: it never changes the choice. */
 int vd_attn_spatial_variant(int L, int C, int heads, char* name, int cap);
+/* The same for every convolution and linear layer (vd_op_conv, vd_op_conv_wino_*, vd_op_conv_split, vd_op_linear_split*, the entries below
+ * and the engine), in the process' own VD_MATH: the full instantiation name out of the table its kernel file dispatches through --
+ * "gemm_split_kernel<BM,BN,ACT,CONV,F16,SIDE>", "conv3x3_wino_r64_kernel<TF4,F16>" ("+ksplitS" appended when the channel loop is cut
+ * into S slices), "conv3x3_wino_r64_ups_kernel<TF4,F16>", "conv3x3_wino_z128_kernel<ACT>", "gemm_frag_kernel<BM,BN,ACT>",
+ * "conv3x3_wino_kernel<TF4>", "igemm_kernel<BM,BN>" -- or "refused: <reason>".  Arguments, as they decide the dispatch: kernel size (1 |
+ * 3), stride, ups (source read through a nearest x2 upsample), channels (C0 < Cin: a virtual concat), frames of this launch and of the
+ * whole layer call (nfr_sel, 0 = nfr), the square source map H (a linear layer of M rows: nfr = M, H = 1), the weight image given --
+ * 0 [tap][Cout][Cin], 1 vd_pack_linear_frag, 2 vd_pack_conv3_wino, 3 vd_pack_linear_split | vd_pack_conv3_split, 4
+ * vd_pack_conv3_wino_split, 5 vd_pack_conv3_wino_ups (the sub-pixel form) --, SiLU on the operand, presence of the operand's affine
+ * pair, per-frame bias, residual and side output, the number of batched problems, and whether split-K scratch is offered (the engine
+ * and vd_op_conv_wino_split_k do, the other entries do not).  Returns 1 / 0 (refused) / < 0 (no room for the name); host only. */
+int vd_igemm_variant(int ksz, int stride, int ups, int Cin, int C0, int Cout, int nfr, int nfr_sel, int H, int weights, int act, int affine,
+                     int fbias, int res, int side, int zcount, int ksplit_scratch, char* name, int cap);
+/* Every instantiation name those tables hold for the process' VD_MATH, one per line; returns their number. */
+int vd_igemm_variant_list(char* names, int cap);
+/* Engine-only paths as single operators.  vd_conv_wino_ksplit: slices of the channel loop conv_wino_r64.hip cuts a small grid into (1: none).
+ * vd_op_conv_wino_split_k: vd_op_conv_wino_split with the split-K scratch the engine provides, kernel and slices chosen for nfr_sel frames
+ * (0: nfr) -- a frame's bits do not depend on which other frames share its launch.  vd_op_linear_split_side: the ResBlock's fused skip
+ * conv, a 1x1 over the virtual concat (a0 [M][C0], a1 [M][K - C0] or NULL) on the 128x128 tile, which also writes side [M][K] =
+ * SiLU(a * sideA[frame][k] + sideB[frame][k]) (frames of HW rows); -1 where the shape is not one the engine would fuse.
+ * vd_op_linear_batched: zcount problems of one shape in one launch (the relative-position nets): problem z reads a + z M K, writes out +
+ * z M N, weight image at zbase + ztab[2z] and bias at zbase + ztab[2z + 1] (float offsets, a device table); the image is the mode's
+ * (vd_pack_linear_split, or vd_pack_linear_frag under VD_MATH=fp32). */
+int vd_conv_wino_ksplit(int nfr, int H, int Cin, int Cout);
+int vd_op_conv_wino_split_k(const float* src0, int Cin, int nfr, int Hs, int Ws, int ups, const void* w_split, const float* bias,
+                            const float* res, const float* fbias, int fbias_ld, float* out, int Cout, double* gn_part, int nfr_sel,
+                            void* stream);
+int vd_op_linear_split_side(const float* a0, const float* a1, int C0, int K, int M, int HW, const void* w_split, const float* bias,
+                            const float* sideA, const float* sideB, float* out, float* side, int N, void* stream);
+int vd_op_linear_batched(const float* a, int zcount, int M, int K, int N, const float* zbase, const long long* ztab_dev, float* out,
+                         void* stream);
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
 /* Backward-data operators of use_gradient_method (csrc/backward.hip); each one synchronises its stream before it returns. */

@@ -249,6 +249,12 @@ SIGNATURES = {
     "vd_op_attn_temporal": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vd_attn_temporal_variant": (_I, [_I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
     "vd_attn_spatial_variant": (_I, [_I, _I, _I, ctypes.c_char_p, _I]),
+    "vd_igemm_variant": (_I, [_I] * 17 + [ctypes.c_char_p, _I]),
+    "vd_igemm_variant_list": (_I, [ctypes.c_char_p, _I]),
+    "vd_conv_wino_ksplit": (_I, [_I, _I, _I, _I]),
+    "vd_op_conv_wino_split_k": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P]),
+    "vd_op_linear_split_side": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "vd_op_linear_batched": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vd_op_out_conv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_gn_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vd_op_gn_temporal_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),

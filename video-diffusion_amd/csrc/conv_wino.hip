@@ -432,22 +432,53 @@ bool conv_wino_supported(const IgemmArgs& a) {
 
 int conv_wino_stats_split(int Hout) { return Hout >= 16 ? (Hout / 16) * (Hout / 16) : 1; }
 
-int launch_conv_wino(const IgemmArgs& a, hipStream_t s) {
-    const int Hl = a.Hs << a.ups;
-    VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl), "GroupNorm partial table: split");
-    WinoGeom g;
-    const int TT = Hl >= 16 ? 8 : 4;                   // tiles per dim per frame in a block
-    g.TF = 64 / (TT * TT);                             // 1 or 4 frames
-    g.tiles_x = Hl / (2 * TT); g.tiles_y = Hl / (2 * TT);
-    const size_t lds = std::max((size_t)2 * (g.TF == 4 ? 7 : 6) * 64 * WLD * sizeof(float), (size_t)4 * 2 * 2 * 2 * 4 * 64 * 4 * sizeof(float));
-    VD_RAISE_LDS((&conv3x3_wino_kernel<true>), (size_t)160 * 1024);
-    VD_RAISE_LDS((&conv3x3_wino_kernel<false>), (size_t)160 * 1024);
-    const int fgroups = (a.nfr + g.TF - 1) / g.TF;
-    dim3 grid(g.tiles_x * g.tiles_y * fgroups, a.Cout / 64);
-    if (g.TF == 4) hipLaunchKernelGGL((conv3x3_wino_kernel<true>), grid, dim3(256), lds, s, a, g);
-    else hipLaunchKernelGGL((conv3x3_wino_kernel<false>), grid, dim3(256), lds, s, a, g);
+// ---- the two instantiations behind launch_conv_wino: ONE table, read by the launcher and by conv_wino_variant() (vd_igemm_variant)
+template <bool TF4>
+static int conv_wino_go(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& a, const WinoGeom& g) {
+    VD_RAISE_LDS((&conv3x3_wino_kernel<TF4>), (size_t)160 * 1024);
+    hipLaunchKernelGGL((conv3x3_wino_kernel<TF4>), grid, dim3(256), lds, s, a, g);
     VD_HIP(hipGetLastError());
     return 0;
+}
+struct ConvWinoRow {
+    int TF;                          // frames per block: 4 on an 8 x 8 map, else 1
+    const char* name;
+    int (*go)(dim3, size_t, hipStream_t, const IgemmArgs&, const WinoGeom&);
+};
+static const ConvWinoRow kConvWinoRows[] = {{4, "conv3x3_wino_kernel<true>", conv_wino_go<true>}, {1, "conv3x3_wino_kernel<false>", conv_wino_go<false>}};
+
+static const ConvWinoRow* conv_wino_row(const IgemmArgs& a, WinoGeom* g, const char** why) {
+    const int Hl = a.Hs << a.ups;
+    if (!(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl))) { *why = "GroupNorm partial table: split"; return nullptr; }
+    const int TT = Hl >= 16 ? 8 : 4;                   // tiles per dim per frame in a block
+    g->TF = 64 / (TT * TT);                            // 1 or 4 frames
+    g->tiles_x = Hl / (2 * TT); g->tiles_y = Hl / (2 * TT);
+    for (const ConvWinoRow& r : kConvWinoRows)
+        if (r.TF == g->TF) return &r;
+    *why = "conv_wino.hip: no instantiation";
+    return nullptr;
+}
+
+IgemmVariant conv_wino_variant(const IgemmArgs& a) {
+    IgemmVariant v{nullptr, 1, nullptr};
+    WinoGeom g;
+    if (const ConvWinoRow* r = conv_wino_row(a, &g, &v.why)) v.name = r->name;
+    return v;
+}
+
+void conv_wino_variant_names(std::vector<std::string>& out) {
+    for (const ConvWinoRow& r : kConvWinoRows) out.push_back(r.name);
+}
+
+int launch_conv_wino(const IgemmArgs& a, hipStream_t s) {
+    WinoGeom g;
+    const char* why = nullptr;
+    const ConvWinoRow* r = conv_wino_row(a, &g, &why);
+    VD_REQUIRE(r != nullptr, why);
+    const size_t lds = std::max((size_t)2 * (g.TF == 4 ? 7 : 6) * 64 * WLD * sizeof(float), (size_t)4 * 2 * 2 * 2 * 4 * 64 * 4 * sizeof(float));
+    const int fgroups = (a.nfr + g.TF - 1) / g.TF;
+    dim3 grid(g.tiles_x * g.tiles_y * fgroups, a.Cout / 64);
+    return r->go(grid, lds, s, a, g);
 }
 
 // host: U = G g G^T (fp64, rounded once), packed [Cin/16][xi 16][Cout/32][kg 2][lane 64][4]:

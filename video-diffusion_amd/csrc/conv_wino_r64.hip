@@ -475,6 +475,22 @@ static int r64_launch(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& k, 
     return 0;
 }
 
+// ---- every instantiation behind launch_conv_wino_r64: ONE table, read by the launchers and by conv_wino_r64_variant() (vd_igemm_variant)
+struct ConvWinoR64Row {
+    bool ups, tf4, f16;              // sub-pixel form; four frames of an 8 x 8 map per item; VD_MATH=f16x3
+    const char* name;
+    size_t lds;
+    int (*go)(dim3, size_t, hipStream_t, const IgemmArgs&, const WinoItemGeom&);
+};
+#define VD_R64_ROW(UPS, KERN, TF4, F16) {UPS, TF4, F16, #KERN "<" #TF4 "," #F16 ">", r64::lds_bytes<TF4>(), r64_launch<&KERN<TF4, F16>>}
+static const ConvWinoR64Row kConvWinoR64Rows[] = {
+    VD_R64_ROW(false, conv3x3_wino_r64_kernel, true, true), VD_R64_ROW(false, conv3x3_wino_r64_kernel, true, false),
+    VD_R64_ROW(false, conv3x3_wino_r64_kernel, false, true), VD_R64_ROW(false, conv3x3_wino_r64_kernel, false, false),
+    VD_R64_ROW(true, conv3x3_wino_r64_ups_kernel, true, true), VD_R64_ROW(true, conv3x3_wino_r64_ups_kernel, true, false),
+    VD_R64_ROW(true, conv3x3_wino_r64_ups_kernel, false, true), VD_R64_ROW(true, conv3x3_wino_r64_ups_kernel, false, false),
+};
+#undef VD_R64_ROW
+
 bool conv_wino_r64_supported(const IgemmArgs& a) {
     const int Hl = a.Hs << a.ups, Wl = a.Ws << a.ups;
     return a.wsplit == 2 && a.wwino != nullptr && a.ksz == 3 && a.stride == 1 && a.pad == 1 && Hl == Wl && wino_pow2(Hl) && Hl >= 8 &&
@@ -539,52 +555,67 @@ size_t conv_wino_r64_ksplit_floats(int nfr, int Hl, int Cin, int Cout, int nfr_s
 
 int conv_wino_ups_stats_split(int Hs) { return 4 * conv_wino_stats_split(Hs); }
 
-// Upsample + conv3x3 in its sub-pixel form: a.wwino is the image of pack_conv3_wino_ups (4 x Cout phase kernels), the kernel
-// convolves the LOW-resolution map and writes the interleaved output.
-static int launch_conv_wino_r64_ups(const IgemmArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.ups == 1 && a.res == nullptr && a.fbias == nullptr && a.Cout % 64 == 0, "sub-pixel Upsample conv: no residual, no per-frame bias");
-    VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_ups_stats_split(a.Hs), "GroupNorm partial table: split (sub-pixel form)");
-    VD_REQUIRE((size_t)a.Cin * a.Cout * 4 * 96 < ((size_t)1 << 31), "sub-pixel weight image beyond 2 GiB");
-    const int Hl = a.Hs;
-    const bool tf4 = Hl == 8;
-    WinoItemGeom g = wino_item_geom(Hl, a.nfr, 4 * a.Cout, 64, tf4);
-    g.phase_cb = a.Cout / 32;
-    g.cgroup = g.ncb % 4 == 0 ? 4 : 2;                                // groups of 1 / 2 / 4 / 8 measured: 1 loses the patch reuse (1347 us at 256 couts), 2 .. 8 within noise
-    IgemmArgs k = a;
-    k.ups = 0; k.Cout = 4 * a.Cout;                                  // the kernel's view: a stride-1 conv of the source map with 4 x Cout outputs
-    const dim3 grid(g.nitems, 1);
+// The row and the work items of a launch, or null and the requirement that failed.  Sub-pixel form (a.ups_phase): a.wwino is the image of
+// pack_conv3_wino_ups (4 x Cout phase kernels), the kernel convolves the LOW-resolution map and writes the interleaved output.
+static const ConvWinoR64Row* conv_wino_r64_row(const IgemmArgs& a, WinoItemGeom* g, const char** why) {
+    const bool ups = a.ups_phase != 0;
+    const int Hl = ups ? a.Hs : a.Hs << a.ups;
+    if (ups) {
+        if (!(a.ups == 1 && a.res == nullptr && a.fbias == nullptr && a.Cout % 64 == 0)) { *why = "sub-pixel Upsample conv: no residual, no per-frame bias"; return nullptr; }
+        if (!(a.stats == nullptr || a.stats_split == conv_wino_ups_stats_split(a.Hs))) { *why = "GroupNorm partial table: split (sub-pixel form)"; return nullptr; }
+        if (!((size_t)a.Cin * a.Cout * 4 * 96 < ((size_t)1 << 31))) { *why = "sub-pixel weight image beyond 2 GiB"; return nullptr; }
+    } else if (!(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl))) {
+        *why = "GroupNorm partial table: split";
+        return nullptr;
+    }
+    const bool tf4 = Hl == 8;                       // four frames of 4 x 4 tiles per item
+    *g = wino_item_geom(Hl, a.nfr, ups ? 4 * a.Cout : a.Cout, 64, tf4);
+    if (ups) {
+        g->phase_cb = a.Cout / 32;
+        g->cgroup = g->ncb % 4 == 0 ? 4 : 2;                              // groups of 1 / 2 / 4 / 8 measured: 1 loses the patch reuse (1347 us at 256 couts), 2 .. 8 within noise
+    } else {
+        // (no grouped cout walk here, unlike the sub-pixel form: 2 .. 8 cout blocks per patch, headline 27.55 ms with groups of 0 / 2 / 4;
+        // re-measured in round 6 on the f16x3 kernel, LAB_NOTES R6)
+        // split-K only with scratch from the caller (the engine's arena; vd_op_conv_wino_split_k): the other single-operator entry points run one slice
+        g->ksplit = a.ksplit_ws && a.ksplit_ws_floats >= conv_wino_r64_ksplit_floats(a.nfr, Hl, a.Cin, a.Cout, a.nfr_sel)
+                        ? conv_wino_r64_ksplit(a.nfr_sel ? a.nfr_sel : a.nfr, Hl, a.Cin, a.Cout) : 1;
+    }
     const bool f16 = f16_math();
-    if (tf4) return f16 ? r64_launch<&conv3x3_wino_r64_ups_kernel<true, true>>(grid, r64::lds_bytes<true>(), s, k, g)
-                        : r64_launch<&conv3x3_wino_r64_ups_kernel<true, false>>(grid, r64::lds_bytes<true>(), s, k, g);
-    return f16 ? r64_launch<&conv3x3_wino_r64_ups_kernel<false, true>>(grid, r64::lds_bytes<false>(), s, k, g)
-               : r64_launch<&conv3x3_wino_r64_ups_kernel<false, false>>(grid, r64::lds_bytes<false>(), s, k, g);
+    for (const ConvWinoR64Row& r : kConvWinoR64Rows)
+        if (r.ups == ups && r.tf4 == tf4 && r.f16 == f16) return &r;
+    *why = "conv_wino_r64.hip: no instantiation";
+    return nullptr;
+}
+
+IgemmVariant conv_wino_r64_variant(const IgemmArgs& a) {
+    IgemmVariant v{nullptr, 1, nullptr};
+    WinoItemGeom g;
+    if (const ConvWinoR64Row* r = conv_wino_r64_row(a, &g, &v.why)) { v.name = r->name; v.ksplit = g.ksplit; }
+    return v;
+}
+
+void conv_wino_r64_variant_names(std::vector<std::string>& out) {
+    if (math_mode() == MATH_FP32) return;            // (the split Winograd image is not built in fp32 arithmetic)
+    for (const ConvWinoR64Row& r : kConvWinoR64Rows)
+        if (r.f16 == f16_math()) out.push_back(r.name);
 }
 
 int launch_conv_wino_r64(const IgemmArgs& a, hipStream_t s) {
-    if (a.ups_phase) return launch_conv_wino_r64_ups(a, s);
-    const int Hl = a.Hs << a.ups;
-    VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl), "GroupNorm partial table: split");
-    const bool tf4 = Hl == 8;                       // four frames of 4 x 4 tiles per item
-    WinoItemGeom g = wino_item_geom(Hl, a.nfr, a.Cout, 64, tf4);
-    // (no grouped cout walk here, unlike the sub-pixel form: 2 .. 8 cout blocks per patch, headline 27.55 ms with groups of 0 / 2 / 4;
-    // re-measured in round 6 on the f16x3 kernel, LAB_NOTES R6)
-    // split-K only with scratch from the caller (the engine's arena; the single-operator entry points run one slice)
-    g.ksplit = a.ksplit_ws && a.ksplit_ws_floats >= conv_wino_r64_ksplit_floats(a.nfr, Hl, a.Cin, a.Cout, a.nfr_sel)
-                   ? conv_wino_r64_ksplit(a.nfr_sel ? a.nfr_sel : a.nfr, Hl, a.Cin, a.Cout) : 1;
+    WinoItemGeom g;
+    const char* why = nullptr;
+    const ConvWinoR64Row* r = conv_wino_r64_row(a, &g, &why);
+    VD_REQUIRE(r != nullptr, why);
     IgemmArgs k = a;
+    if (r->ups) {
+        k.ups = 0; k.Cout = 4 * a.Cout;                                  // the kernel's view: a stride-1 conv of the source map with 4 x Cout outputs
+        return r->go(dim3(g.nitems, 1), r->lds, s, k, g);
+    }
     if (g.ksplit > 1) {
         k.out = a.ksplit_ws; k.ldo = a.Cout; k.bias = nullptr; k.fbias = nullptr; k.res = nullptr; k.stats = nullptr;
     }
-    const dim3 grid(g.nitems, g.ksplit);
-    const bool f16 = f16_math();
-    int rc;
-    if (tf4) rc = f16 ? r64_launch<&conv3x3_wino_r64_kernel<true, true>>(grid, r64::lds_bytes<true>(), s, k, g)
-                      : r64_launch<&conv3x3_wino_r64_kernel<true, false>>(grid, r64::lds_bytes<true>(), s, k, g);
-    else rc = f16 ? r64_launch<&conv3x3_wino_r64_kernel<false, true>>(grid, r64::lds_bytes<false>(), s, k, g)
-                  : r64_launch<&conv3x3_wino_r64_kernel<false, false>>(grid, r64::lds_bytes<false>(), s, k, g);
-    if (rc) return rc;
+    if (int rc = r->go(dim3(g.nitems, g.ksplit), r->lds, s, k, g)) return rc;
     if (g.ksplit > 1) {
-        const int HW = Hl * Hl;
+        const int Hl = a.Hs << a.ups, HW = Hl * Hl;
         hipLaunchKernelGGL(wino_r64_reduce_kernel, dim3(a.nfr, a.Cout / 16), dim3(256), 0, s, a.ksplit_ws, g.ksplit,
                            (size_t)a.nfr * HW * a.Cout, a.bias, a.fbias, a.fbias_ld, a.res, a.res_ld, a.out, a.ldo, HW, a.Cout, a.stats);
         VD_HIP(hipGetLastError());

@@ -476,20 +476,47 @@ bool conv_wino_z128_act_supported(const IgemmArgs& a) {
     return conv_wino_r64_supported(b) && a.ups == 0 && !a.ups_phase && conv_wino_z128_act_shape(a.nfr_sel ? a.nfr_sel : a.nfr, a.Hs, a.Cin, a.Cout);
 }
 
-int launch_conv_wino_z128(const IgemmArgs& a, hipStream_t s) {
-    const int Hl = a.Hs;
-    VD_REQUIRE(a.stats == nullptr || a.stats_split == conv_wino_stats_split(Hl), "GroupNorm partial table: split");
-    const WinoItemGeom g = wino_item_geom(Hl, a.nfr, a.Cout, 128, false);
-    VD_RAISE_LDS((&conv3x3_wino_z128_kernel<false>), (size_t)160 * 1024);
-    VD_RAISE_LDS((&conv3x3_wino_z128_kernel<true>), (size_t)160 * 1024);
-    if (a.affA) {
-        VD_REQUIRE(conv_wino_z128_act_supported(a), "conv_wino_z128 with the activation in its patch staging: shape not covered");
-        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<true>, dim3(g.nitems), dim3(256), R64G<false>::LDS_BYTES + 2 * a.Cin * sizeof(float), s, a, g);
-    } else {
-        hipLaunchKernelGGL(conv3x3_wino_z128_kernel<false>, dim3(g.nitems), dim3(256), R64G<false>::LDS_BYTES, s, a, g);
-    }
+// ---- the two instantiations behind launch_conv_wino_z128 (f16x3 only): ONE table, read by the launcher and by conv_wino_z128_variant()
+template <bool ACT>
+static int z128_go(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& a, const WinoItemGeom& g) {
+    VD_RAISE_LDS((&conv3x3_wino_z128_kernel<ACT>), (size_t)160 * 1024);
+    hipLaunchKernelGGL(conv3x3_wino_z128_kernel<ACT>, grid, dim3(256), lds, s, a, g);
     VD_HIP(hipGetLastError());
     return 0;
+}
+struct ConvWinoZ128Row {
+    bool act;                        // the GroupNorm(+FiLM) affine + SiLU of the input in the patch staging (a.affA)
+    const char* name;
+    int (*go)(dim3, size_t, hipStream_t, const IgemmArgs&, const WinoItemGeom&);
+};
+static const ConvWinoZ128Row kConvWinoZ128Rows[] = {{false, "conv3x3_wino_z128_kernel<false>", z128_go<false>}, {true, "conv3x3_wino_z128_kernel<true>", z128_go<true>}};
+
+static const ConvWinoZ128Row* conv_wino_z128_row(const IgemmArgs& a, const char** why) {
+    if (!(a.stats == nullptr || a.stats_split == conv_wino_stats_split(a.Hs))) { *why = "GroupNorm partial table: split"; return nullptr; }
+    if (a.affA && !conv_wino_z128_act_supported(a)) { *why = "conv_wino_z128 with the activation in its patch staging: shape not covered"; return nullptr; }
+    for (const ConvWinoZ128Row& r : kConvWinoZ128Rows)
+        if (r.act == (a.affA != nullptr)) return &r;
+    *why = "conv_wino_z128.hip: no instantiation";
+    return nullptr;
+}
+
+IgemmVariant conv_wino_z128_variant(const IgemmArgs& a) {
+    IgemmVariant v{nullptr, 1, nullptr};
+    if (const ConvWinoZ128Row* r = conv_wino_z128_row(a, &v.why)) v.name = r->name;
+    return v;
+}
+
+void conv_wino_z128_variant_names(std::vector<std::string>& out) {
+    if (!f16_math()) return;                         // conv_wino_z128_shape: f16x3 only
+    for (const ConvWinoZ128Row& r : kConvWinoZ128Rows) out.push_back(r.name);
+}
+
+int launch_conv_wino_z128(const IgemmArgs& a, hipStream_t s) {
+    const char* why = nullptr;
+    const ConvWinoZ128Row* r = conv_wino_z128_row(a, &why);
+    VD_REQUIRE(r != nullptr, why);
+    const WinoItemGeom g = wino_item_geom(a.Hs, a.nfr, a.Cout, 128, false);
+    return r->go(dim3(g.nitems), R64G<false>::LDS_BYTES + (r->act ? 2 * a.Cin * sizeof(float) : 0), s, a, g);
 }
 
 }  // namespace vd

@@ -3003,6 +3003,98 @@ int vd_op_conv(const float* src0, const float* src1, int C0, int Cin, int nfr, i
 int vd_conv_stats_split(int Hout) { return conv_wino_stats_split(Hout); }
 int vd_conv_wino_block_couts(int nfr, int H, int Cin, int Cout) { return conv_wino_z128_shape(nfr, H, Cin, Cout) ? 128 : 64; }
 
+// ---- which instantiation a conv / linear call runs on (the tables of igemm.hip, gemm_split.hip, gemm_frag.hip, conv_wino*.hip): no launch
+static int copy_name(const std::string& n, char* name, int cap, const char* who) {
+    VD_REQUIRE((int)n.size() < cap, std::string(who) + ": name buffer too small");
+    memcpy(name, n.c_str(), n.size() + 1);
+    return 0;
+}
+
+int vd_igemm_variant(int ksz, int stride, int ups, int Cin, int C0, int Cout, int nfr, int nfr_sel, int H, int weights, int act, int affine,
+                     int fbias, int res, int side, int zcount, int ksplit_scratch, char* name, int cap) {
+    VD_REQUIRE(name && cap > 0, "vd_igemm_variant: a name buffer");
+    VD_REQUIRE(weights >= 0 && weights <= 5 && H > 0 && nfr > 0 && stride > 0, "vd_igemm_variant: weights 0..5, positive H, nfr and stride");
+    const float* any = reinterpret_cast<const float*>(0x1000);      // presence only: nothing is read
+    IgemmArgs g = conv_args(any, C0 < Cin ? any : nullptr, C0, Cin, nfr, H, H, ups, stride, ksz == 3 ? 1 : 0, ksz);
+    g.nfr_sel = nfr_sel;
+    g.w = weights == 0 ? any : nullptr;
+    g.wfrag = weights == 1 || weights == 3 ? any : nullptr;
+    g.wwino = weights == 2 || weights >= 4 ? any : nullptr;
+    g.wsplit = weights == 3 ? 1 : weights >= 4 ? 2 : 0;
+    g.ups_phase = weights == 5;
+    g.act = act;
+    if (affine) { g.affA = any; g.affB = any; }
+    if (fbias) { g.fbias = any; g.fbias_ld = Cout; }
+    if (res) g.res = any;
+    g.res_ld = Cout; g.out = const_cast<float*>(any); g.ldo = Cout; g.Cout = Cout;
+    if (side) { g.side = const_cast<float*>(any); g.sideA = any; g.sideB = any; g.side_hw = g.Ho * g.Wo; }
+    g.zcount = zcount; g.zs_a = g.M * Cin; g.zs_out = g.M * Cout;
+    if (ksplit_scratch) { g.ksplit_ws = const_cast<float*>(any); g.ksplit_ws_floats = conv_wino_r64_ksplit_floats(nfr, g.Ho, Cin, Cout, nfr_sel); }
+    const IgemmVariant v = igemm_variant(g);
+    if (int rc = copy_name(igemm_variant_name(v), name, cap, "vd_igemm_variant")) return rc;
+    return v.name ? 1 : 0;
+}
+
+int vd_igemm_variant_list(char* names, int cap) {
+    VD_REQUIRE(names && cap > 0, "vd_igemm_variant_list: a name buffer");
+    std::vector<std::string> rows;
+    igemm_variant_names(rows);
+    std::string all;
+    for (const std::string& r : rows) all += r + "\n";
+    if (int rc = copy_name(all, names, cap, "vd_igemm_variant_list")) return rc;
+    return (int)rows.size();
+}
+
+int vd_conv_wino_ksplit(int nfr, int H, int Cin, int Cout) { return conv_wino_r64_ksplit(nfr, H, Cin, Cout); }
+
+// vd_op_conv_wino_split as the engine's res_block launches it: split-K scratch of conv_wino_r64_ksplit_floats() offered, slices and kernel
+// chosen for nfr_sel frames (0: nfr)
+int vd_op_conv_wino_split_k(const float* src0, int Cin, int nfr, int Hs, int Ws, int ups, const void* w_split, const float* bias,
+                            const float* res, const float* fbias, int fbias_ld, float* out, int Cout, double* gn_part, int nfr_sel,
+                            void* stream) {
+    IgemmArgs g = conv_args(src0, nullptr, Cin, Cin, nfr, Hs, Ws, ups, 1, 1, 3);
+    g.nfr_sel = nfr_sel;
+    g.wwino = static_cast<const float*>(w_split); g.wsplit = 2; g.bias = bias; g.res = res; g.res_ld = Cout;
+    g.fbias = fbias; g.fbias_ld = fbias_ld; g.out = out; g.ldo = Cout; g.Cout = Cout;
+    g.stats = gn_part; g.stats_split = conv_wino_stats_split(g.Ho);
+    VD_REQUIRE(conv_wino_r64_supported(g) && nfr_sel >= 0, "vd_op_conv_wino_split_k: shape not covered by conv_wino_r64.hip");
+    OpScratch ws(stream);
+    g.ksplit_ws_floats = conv_wino_r64_ksplit_floats(nfr, g.Ho, Cin, Cout, nfr_sel);
+    if (g.ksplit_ws_floats)
+        if (int rc = ws.get(&g.ksplit_ws, g.ksplit_ws_floats)) return rc;
+    return launch_igemm(g, ws.st);
+}
+
+// The fused skip conv of res_block: a 1x1 over the virtual concat (a0: C0 channels, a1: K - C0 or null) on the 128x128 tile whose column
+// blocks 0 also write side = SiLU(a * sideA[frame] + sideB[frame])
+int vd_op_linear_split_side(const float* a0, const float* a1, int C0, int K, int M, int HW, const void* w_split, const float* bias,
+                            const float* sideA, const float* sideB, float* out, float* side, int N, void* stream) {
+    int H = 1;
+    while (H * H < HW) ++H;
+    VD_REQUIRE(a0 && (a1 ? C0 > 0 && C0 < K : C0 == K) && HW > 0 && H * H == HW && M > 0 && M % HW == 0 && out && side && sideA && sideB,
+               "vd_op_linear_split_side: one source of K channels or two of C0 and K - C0, M whole frames of HW = H x H rows");
+    IgemmArgs g = conv_args(a0, a1, C0, K, M / HW, H, H, 0, 1, 0, 1);
+    g.wfrag = static_cast<const float*>(w_split); g.wsplit = 1; g.bias = bias; g.out = out; g.ldo = N; g.Cout = N; g.res_ld = N;
+    g.side = side; g.sideA = sideA; g.sideB = sideB; g.side_hw = HW;
+    VD_REQUIRE(gemm_split_side_supported(g), "vd_op_linear_split_side: not a plain 1x1 on the 128x128 tile of gemm_split.hip over whole frames of a multiple of 128 rows");
+    return launch_igemm(g, static_cast<hipStream_t>(stream));
+}
+
+// The zcount launch of rpe_all in the process' arithmetic: problem z reads a + z M K, writes out + z M N, its weight image (the mode's:
+// vd_pack_linear_split, or vd_pack_linear_frag under VD_MATH=fp32) at zbase + ztab[2z] and its bias at zbase + ztab[2z + 1]
+int vd_op_linear_batched(const float* a, int zcount, int M, int K, int N, const float* zbase, const long long* ztab_dev, float* out,
+                         void* stream) {
+    VD_REQUIRE(a && zcount > 1 && M > 0 && zbase && ztab_dev && out, "vd_op_linear_batched: zcount >= 2 problems and a device table of 2 zcount offsets");
+    long long z0[2];
+    VD_HIP(hipMemcpy(z0, ztab_dev, sizeof(z0), hipMemcpyDeviceToHost));
+    IgemmArgs q = linear_args(M, K, N);
+    q.src0 = a; q.out = out;
+    q.wfrag = zbase + z0[0]; q.bias = zbase + z0[1];                    // (problem 0's: the shape checks read them)
+    q.zcount = zcount; q.zs_a = M * K; q.zs_out = M * N; q.ztab = ztab_dev; q.zbase = zbase;
+    VD_REQUIRE(igemm_kernel(q) == (split_math() ? IK_SPLIT : IK_FRAG), "vd_op_linear_batched: shape not covered by gemm_split.hip / gemm_frag.hip");
+    return launch_igemm(q, static_cast<hipStream_t>(stream));
+}
+
 int vd_op_conv_stats(const float* src0, int Cin, int nfr, int Hs, int Ws, int ups, const float* w_wino, const float* bias,
                      const float* res, const float* fbias, int fbias_ld, float* out, int Cout, double* gn_part,
                      void* stream) {

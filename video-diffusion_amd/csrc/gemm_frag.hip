@@ -194,23 +194,46 @@ bool gemm_frag_supported(const IgemmArgs& a) {
            (size_t)a.M * std::max(std::max(a.C0, a.Cin - a.C0), a.ldo) < (1u << 28);
 }
 
-template <int BM, int BN>
+// ---- every instantiation behind launch_gemm_frag: ONE table, read by the launcher and by gemm_frag_variant() (vd_igemm_variant)
+template <int BM, int BN, bool ACT>
 static int launch_gf(const IgemmArgs& a, hipStream_t s) {
     const size_t lds = (size_t)2 * BM * GLD * sizeof(float);
     dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN, a.zcount > 1 ? a.zcount : 1);
-    if (a.act) hipLaunchKernelGGL((gemm_frag_kernel<BM, BN, true>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((gemm_frag_kernel<BM, BN, false>), grid, dim3(256), lds, s, a);
+    hipLaunchKernelGGL((gemm_frag_kernel<BM, BN, ACT>), grid, dim3(256), lds, s, a);
     VD_HIP(hipGetLastError());
     return 0;
 }
+struct GemmFragRow {
+    int cls;                         // igemm_tile_class
+    bool act;
+    const char* name;
+    int (*launch)(const IgemmArgs&, hipStream_t);
+};
+#define VD_GF_TILE(CLS, BM, BN) {CLS, false, "gemm_frag_kernel<" #BM "," #BN ",false>", launch_gf<BM, BN, false>}, \
+                                {CLS, true, "gemm_frag_kernel<" #BM "," #BN ",true>", launch_gf<BM, BN, true>}
+static const GemmFragRow kGemmFragRows[] = {VD_GF_TILE(0, 128, 128), VD_GF_TILE(1, 128, 64), VD_GF_TILE(2, 64, 128), VD_GF_TILE(3, 64, 64)};
+#undef VD_GF_TILE
+
+static const GemmFragRow* gemm_frag_row(const IgemmArgs& a, int tile_class) {
+    const int cls = tile_class >= 0 && tile_class <= 2 ? tile_class : 3;
+    for (const GemmFragRow& r : kGemmFragRows)
+        if (r.cls == cls && r.act == (a.act != 0)) return &r;
+    return nullptr;                  // (not reached: every (class, act) pair has its row)
+}
+
+IgemmVariant gemm_frag_variant(const IgemmArgs& a, int tile_class) {
+    const GemmFragRow* r = gemm_frag_row(a, tile_class);
+    return IgemmVariant{r ? r->name : nullptr, 1, r ? nullptr : "gemm_frag.hip: no instantiation"};
+}
+
+void gemm_frag_variant_names(std::vector<std::string>& out) {
+    for (const GemmFragRow& r : kGemmFragRows) out.push_back(r.name);
+}
 
 int launch_gemm_frag(const IgemmArgs& a, int tile_class, hipStream_t s) {
-    switch (tile_class) {
-        case 0: return launch_gf<128, 128>(a, s);
-        case 1: return launch_gf<128, 64>(a, s);
-        case 2: return launch_gf<64, 128>(a, s);
-        default: return launch_gf<64, 64>(a, s);
-    }
+    const GemmFragRow* r = gemm_frag_row(a, tile_class);
+    VD_REQUIRE(r != nullptr, "gemm_frag.hip: no instantiation");
+    return r->launch(a, s);
 }
 
 // host-side repack of `rows` rows of a [N_total][K] row-major matrix (rows row0 .. row0+rows-1, all multiples of 32)

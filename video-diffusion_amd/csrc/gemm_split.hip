@@ -468,31 +468,66 @@ bool gemm_split_side_supported(const IgemmArgs& a) {
            a.side_hw > 0 && a.side_hw % 128 == 0 && a.M % a.side_hw == 0;
 }
 
-template <int BM, int BN, bool F16>
-static int launch_gs_m(const IgemmArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)2 * (F16 ? 2 : 3) * BM * SROW;
-    dim3 grid((a.M + BM - 1) / BM, (a.Cout + BN - 1) / BN, a.zcount > 1 ? a.zcount : 1);
-    if (a.side) {
-        if constexpr (BM == 128 && BN == 128) {
-            VD_REQUIRE(gemm_split_side_supported(a) && a.sideA && a.sideB, "side output: plain 1x1 on the 128x128 tile, whole frames of a multiple of 128 rows");
-            hipLaunchKernelGGL((gemm_split_kernel<128, 128, false, false, F16, true>), grid, dim3(256), lds, s, a);
-            VD_HIP(hipGetLastError());
-            return 0;
-        } else {
-            VD_REQUIRE(false, "side output: 128x128 tile only");
-        }
-    }
-    if (a.ksz == 3) {
-        if (a.act) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, true, true, F16>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, false, true, F16>), grid, dim3(256), lds, s, a);
-    } else if (a.act) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, true, false, F16>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, false, false, F16>), grid, dim3(256), lds, s, a);
+// ---- every instantiation behind launch_gemm_split: ONE table, read by the launcher and by gemm_split_variant() (vd_igemm_variant).
+// Per tile class and arithmetic: plain, ACT (SiLU on the operand: the embedding MLPs) and CONV (implicit im2col of a 3x3); SIDE on the
+// 128x128 tile only.  (No ACT + CONV row: no caller activates the operand of a 3x3 split conv -- the Winograd kernels take those.)
+template <auto KERN>
+static int gs_go(dim3 grid, size_t lds, hipStream_t s, const IgemmArgs& a) {
+    hipLaunchKernelGGL(KERN, grid, dim3(256), lds, s, a);
     VD_HIP(hipGetLastError());
     return 0;
 }
-template <int BM, int BN>
-static int launch_gs(const IgemmArgs& a, hipStream_t s) {
-    return f16_math() ? launch_gs_m<BM, BN, true>(a, s) : launch_gs_m<BM, BN, false>(a, s);
+struct GemmSplitRow {
+    int cls, BM, BN;                 // gemm_split_tile_class and its tile
+    bool act, conv, f16, side;
+    const char* name;
+    int (*go)(dim3, size_t, hipStream_t, const IgemmArgs&);
+};
+#define VD_GS_ROW(CLS, BM, BN, ACT, CONV, F16, SIDE)                                                          \
+    {CLS, BM, BN, ACT, CONV, F16, SIDE, "gemm_split_kernel<" #BM "," #BN "," #ACT "," #CONV "," #F16 "," #SIDE ">", \
+     gs_go<&gemm_split_kernel<BM, BN, ACT, CONV, F16, SIDE>>}
+#define VD_GS_TILE(CLS, BM, BN, F16) \
+    VD_GS_ROW(CLS, BM, BN, false, false, F16, false), VD_GS_ROW(CLS, BM, BN, true, false, F16, false), VD_GS_ROW(CLS, BM, BN, false, true, F16, false)
+static const GemmSplitRow kGemmSplitRows[] = {
+    VD_GS_TILE(4, 128, 192, true), VD_GS_TILE(0, 128, 128, true), VD_GS_TILE(1, 128, 64, true), VD_GS_TILE(2, 64, 128, true), VD_GS_TILE(3, 64, 64, true),
+    VD_GS_ROW(0, 128, 128, false, false, true, true),
+    VD_GS_TILE(4, 128, 192, false), VD_GS_TILE(0, 128, 128, false), VD_GS_TILE(1, 128, 64, false), VD_GS_TILE(2, 64, 128, false), VD_GS_TILE(3, 64, 64, false),
+    VD_GS_ROW(0, 128, 128, false, false, false, true),
+};
+#undef VD_GS_TILE
+#undef VD_GS_ROW
+
+// the row of a launch (tile_class 0: decided here, from the rows of the whole layer call), or null and the requirement that failed
+static const GemmSplitRow* gemm_split_row(const IgemmArgs& a, int tile_class, const char** why) {
+    if (tile_class == 0) tile_class = gemm_split_tile_class(igemm_sel_M(a), a.Cout);
+    if (a.stats) {
+        const int rows = tile_class == 2 || tile_class == 3 ? 32 : 64;
+        if (!(a.zcount <= 1 && a.stats_hw > 0 && a.stats_hw % rows == 0 && a.M % a.stats_hw == 0 && a.stats_split == a.stats_hw / rows)) {
+            *why = "GroupNorm partial sums from the GEMM epilogue: whole frames of a multiple of the wave tile's rows";
+            return nullptr;
+        }
+    }
+    if (a.side && !(tile_class == 0 && gemm_split_side_supported(a) && a.sideA && a.sideB)) {
+        *why = "side output: plain 1x1 on the 128x128 tile, whole frames of a multiple of 128 rows";
+        return nullptr;
+    }
+    const bool f16 = f16_math();
+    for (const GemmSplitRow& r : kGemmSplitRows)
+        if (r.cls == tile_class && r.f16 == f16 && r.side == (a.side != nullptr) && r.conv == (a.ksz == 3) && r.act == (a.act != 0)) return &r;
+    *why = "gemm_split.hip: no 3x3 form with an activated operand";
+    return nullptr;
+}
+
+IgemmVariant gemm_split_variant(const IgemmArgs& a, int tile_class) {
+    IgemmVariant v{nullptr, 1, nullptr};
+    if (const GemmSplitRow* r = gemm_split_row(a, tile_class, &v.why)) v.name = r->name;
+    return v;
+}
+
+void gemm_split_variant_names(std::vector<std::string>& out) {
+    if (math_mode() == MATH_FP32) return;            // (no caller hands a split image to a process in fp32 arithmetic)
+    for (const GemmSplitRow& r : kGemmSplitRows)
+        if (r.f16 == f16_math()) out.push_back(r.name);
 }
 
 // 128x192 tile for the wide projections (qkv: N = 1152, 1536; proj: N = 384): the A tile is staged and split once per 192
@@ -510,19 +545,12 @@ int gemm_split_stats_rows(int M, int Cout) {
 }
 
 int launch_gemm_split(const IgemmArgs& a, int tile_class, hipStream_t s) {
-    if (tile_class == 0) tile_class = gemm_split_tile_class(igemm_sel_M(a), a.Cout);
-    if (a.stats) {
-        const int rows = tile_class == 2 || tile_class == 3 ? 32 : 64;
-        VD_REQUIRE(a.zcount <= 1 && a.stats_hw > 0 && a.stats_hw % rows == 0 && a.M % a.stats_hw == 0 &&
-                   a.stats_split == a.stats_hw / rows, "GroupNorm partial sums from the GEMM epilogue: whole frames of a multiple of the wave tile's rows");
-    }
-    switch (tile_class) {
-        case 4: return launch_gs<128, 192>(a, s);
-        case 0: return launch_gs<128, 128>(a, s);
-        case 1: return launch_gs<128, 64>(a, s);
-        case 2: return launch_gs<64, 128>(a, s);
-        default: return launch_gs<64, 64>(a, s);
-    }
+    const char* why = nullptr;
+    const GemmSplitRow* r = gemm_split_row(a, tile_class, &why);
+    VD_REQUIRE(r != nullptr, why);
+    const size_t lds = (size_t)2 * (r->f16 ? 2 : 3) * r->BM * SROW;
+    const dim3 grid((a.M + r->BM - 1) / r->BM, (a.Cout + r->BN - 1) / r->BN, a.zcount > 1 ? a.zcount : 1);
+    return r->go(grid, lds, s, a);
 }
 
 }  // namespace vd

@@ -148,29 +148,78 @@ IgemmKernel igemm_kernel(const IgemmArgs& a) {
     return IK_GENERIC;
 }
 
-// One launch: every operand of `a` is small enough for the 32-bit byte offsets the kernels address with.
-static int launch_igemm_one(const IgemmArgs& a, hipStream_t s) {
-    const IgemmKernel k = igemm_kernel(a);
+// ---- the generic kernel's instantiations: ONE table, read by the launcher and by igemm_variant() (vd_igemm_variant)
+struct IgemmRow {
+    int cls;                         // igemm_tile_class
+    const char* name;
+    int (*launch)(const IgemmArgs&, hipStream_t);
+};
+static const IgemmRow kIgemmRows[] = {{0, "igemm_kernel<128,128>", launch_t<128, 128>}, {1, "igemm_kernel<128,64>", launch_t<128, 64>},
+                                      {2, "igemm_kernel<64,128>", launch_t<64, 128>}, {3, "igemm_kernel<64,64>", launch_t<64, 64>}};
+
+static const IgemmRow* igemm_row(const IgemmArgs& a, int tile, const char** why) {
+    if (a.wsplit) { *why = "split weight image given for a shape the split kernels do not cover"; return nullptr; }
+    if (a.w == nullptr) { *why = "this shape runs on the generic kernel and needs [tap][Cout][Cin] weights"; return nullptr; }
+    const int cls = tile >= 0 && tile <= 2 ? tile : 3;
+    for (const IgemmRow& r : kIgemmRows)
+        if (r.cls == cls) return &r;
+    *why = "igemm.hip: no instantiation";
+    return nullptr;
+}
+
+// what launch_igemm asks of a call before it looks at the kernels: null, or the requirement that failed
+static const char* igemm_refusal(const IgemmArgs& a) {
+    if (a.Cin % BK != 0) return "Cin must be a multiple of 32 (pad the operand)";
+    if (!(a.C0 % BK == 0 && a.C0 <= a.Cin)) return "concat split must be a multiple of 32";
+    if (!(a.src1 != nullptr || a.C0 == a.Cin)) return "second source missing";
+    if (!(a.ksz == 1 || a.ksz == 3)) return "kernel size 1 or 3";
+    if (!(a.M > 0 && a.Cout > 0)) return "empty problem";
+    if (a.M != a.nfr * a.Ho * a.Wo) return "M != nfr*Ho*Wo";
+    if (igemm_frames_per_launch(a) <= 0) return "one frame of this layer exceeds 2^28 elements";
+    return nullptr;
+}
+
+// ONE launch's args (every operand small enough for the 32-bit byte offsets the kernels address with) -> igemm_kernel()'s choice, then the
+// row of that file's table: named into *v (vd_igemm_variant: no launch), or launched when v is null.  One switch serves both.
+static int igemm_one(const IgemmArgs& a, hipStream_t s, IgemmVariant* v) {
     const int tile = igemm_tile_class(igemm_sel_M(a), a.Cout);
-    switch (k) {
+    const char* why = nullptr;
+    switch (igemm_kernel(a)) {
         case IK_R64_UPS:
-            VD_REQUIRE(conv_wino_r64_supported(a), "sub-pixel Upsample conv: shape not covered by conv_wino_r64.hip");
-            return launch_conv_wino_r64(a, s);
-        case IK_SPLIT: return launch_gemm_split(a, tile, s);
-        case IK_Z128: return launch_conv_wino_z128(a, s);
-        case IK_R64: return launch_conv_wino_r64(a, s);
-        case IK_FRAG: return launch_gemm_frag(a, tile, s);
-        case IK_WINO: return launch_conv_wino(a, s);
-        case IK_GENERIC: break;
+            if (!conv_wino_r64_supported(a)) { why = "sub-pixel Upsample conv: shape not covered by conv_wino_r64.hip"; break; }
+            return v ? (*v = conv_wino_r64_variant(a), 0) : launch_conv_wino_r64(a, s);
+        case IK_SPLIT: return v ? (*v = gemm_split_variant(a, tile), 0) : launch_gemm_split(a, tile, s);
+        case IK_Z128: return v ? (*v = conv_wino_z128_variant(a), 0) : launch_conv_wino_z128(a, s);
+        case IK_R64: return v ? (*v = conv_wino_r64_variant(a), 0) : launch_conv_wino_r64(a, s);
+        case IK_FRAG: return v ? (*v = gemm_frag_variant(a, tile), 0) : launch_gemm_frag(a, tile, s);
+        case IK_WINO: return v ? (*v = conv_wino_variant(a), 0) : launch_conv_wino(a, s);
+        case IK_GENERIC:
+            if (const IgemmRow* r = igemm_row(a, tile, &why)) return v ? (*v = IgemmVariant{r->name, 1, nullptr}, 0) : r->launch(a, s);
+            break;
     }
-    VD_REQUIRE(!a.wsplit, "split weight image given for a shape the split kernels do not cover");
-    VD_REQUIRE(a.w != nullptr, "this shape runs on the generic kernel and needs [tap][Cout][Cin] weights");
-    switch (tile) {
-        case 0: return launch_t<128, 128>(a, s);
-        case 1: return launch_t<128, 64>(a, s);
-        case 2: return launch_t<64, 128>(a, s);
-        default: return launch_t<64, 64>(a, s);
-    }
+    if (v) { *v = IgemmVariant{nullptr, 1, why}; return 0; }
+    VD_REQUIRE(false, why);
+}
+
+IgemmVariant igemm_variant(const IgemmArgs& a) {
+    if (const char* why = igemm_refusal(a)) return IgemmVariant{nullptr, 1, why};
+    IgemmVariant v{nullptr, 1, nullptr};
+    (void)igemm_one(igemm_first_launch(a), nullptr, &v);
+    return v;
+}
+
+std::string igemm_variant_name(const IgemmVariant& v) {
+    if (!v.name) return std::string("refused: ") + (v.why ? v.why : "");
+    return v.ksplit > 1 ? std::string(v.name) + "+ksplit" + std::to_string(v.ksplit) : std::string(v.name);
+}
+
+void igemm_variant_names(std::vector<std::string>& out) {
+    gemm_split_variant_names(out);
+    conv_wino_r64_variant_names(out);
+    conv_wino_z128_variant_names(out);
+    gemm_frag_variant_names(out);
+    conv_wino_variant_names(out);
+    for (const IgemmRow& r : kIgemmRows) out.push_back(r.name);
 }
 
 // Frames (rows, for a linear layer) per launch.  The fast kernels reach their operands through buffer descriptors with
@@ -218,18 +267,12 @@ IgemmArgs igemm_first_launch(const IgemmArgs& a) {
 }
 
 int launch_igemm(const IgemmArgs& a, hipStream_t s) {
-    VD_REQUIRE(a.Cin % BK == 0, "Cin must be a multiple of 32 (pad the operand)");
-    VD_REQUIRE(a.C0 % BK == 0 && a.C0 <= a.Cin, "concat split must be a multiple of 32");
-    VD_REQUIRE(a.src1 != nullptr || a.C0 == a.Cin, "second source missing");
-    VD_REQUIRE(a.ksz == 1 || a.ksz == 3, "kernel size 1 or 3");
-    VD_REQUIRE(a.M > 0 && a.Cout > 0, "empty problem");
-    VD_REQUIRE(a.M == a.nfr * a.Ho * a.Wo, "M != nfr*Ho*Wo");
+    if (const char* why = igemm_refusal(a)) { set_error(std::string("requirement failed: ") + why); return -1; }
     const int per = igemm_frames_per_launch(a);
-    VD_REQUIRE(per > 0, "one frame of this layer exceeds 2^28 elements");
-    if (per >= a.nfr) return launch_igemm_one(a, s);
+    if (per >= a.nfr) return igemm_one(a, s, nullptr);
     VD_REQUIRE(!(a.stats && a.stats_hw > 0), "GroupNorm partial sums from the split GEMM: one launch only (the tile choice, and with it the table, depends on M)");
     for (int f0 = 0; f0 < a.nfr; f0 += per) {
-        const int rc = launch_igemm_one(frame_range(a, f0, std::min(per, a.nfr - f0)), s);
+        const int rc = igemm_one(frame_range(a, f0, std::min(per, a.nfr - f0)), s, nullptr);
         if (rc) return rc;
     }
     return 0;

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -313,6 +314,23 @@ int gemm_split_tile_class(int M, int Cout);               // igemm_tile_class, o
 int gemm_split_stats_rows(int M, int Cout);               // rows of a wave tile = rows behind one GroupNorm partial sum (64 | 32)
 void pack_linear_split(const float* w, unsigned short* out_base, int rows, int K, int n_total, int row0);          // blocks per frame = partial sums per (frame, channel)
 int launch_conv_wino(const IgemmArgs& a, hipStream_t s);
+// Which instantiation serves ONE launch's IgemmArgs in this process' VD_MATH.  Every kernel file keeps ONE table of its instantiations;
+// its launcher dispatches through the table and its *_variant() reads the same row, so what vd_igemm_variant() prints is what is launched.
+// name: null = refused (why: the requirement that failed).  ksplit: slices of the channel loop (conv_wino_r64.hip with scratch), else 1.
+struct IgemmVariant { const char* name; int ksplit; const char* why; };
+IgemmVariant igemm_variant(const IgemmArgs& a);                          // igemm.hip: igemm_kernel()'s choice, then the file's own
+std::string igemm_variant_name(const IgemmVariant& v);                   // e.g. "conv3x3_wino_r64_kernel<true,false>+ksplit4" | "refused: ..."
+void igemm_variant_names(std::vector<std::string>& out);                 // every row of every table that this process' mode can launch
+IgemmVariant gemm_split_variant(const IgemmArgs& a, int tile_class);
+IgemmVariant gemm_frag_variant(const IgemmArgs& a, int tile_class);
+IgemmVariant conv_wino_variant(const IgemmArgs& a);
+IgemmVariant conv_wino_r64_variant(const IgemmArgs& a);
+IgemmVariant conv_wino_z128_variant(const IgemmArgs& a);
+void gemm_split_variant_names(std::vector<std::string>& out);
+void gemm_frag_variant_names(std::vector<std::string>& out);
+void conv_wino_variant_names(std::vector<std::string>& out);
+void conv_wino_r64_variant_names(std::vector<std::string>& out);
+void conv_wino_z128_variant_names(std::vector<std::string>& out);
 void pack_conv3_wino(const float* oihw, float* out, int O, int I);      // out: 16*O*I floats
 int launch_attn_spatial(const AttnSpatialArgs& a, hipStream_t s);
 // Which instantiation a spatial-attention shape runs on in this process' VD_MATH: the ONE place the choice is made (the table of
