@@ -211,6 +211,37 @@ int vd_dpmpp_2m_from_xstart(vd_engine* e, int B, long long per_sample, const flo
                             const float* prev_xstart, const long long* t, int clip_denoised, float* sample, float* pred_xstart,
                             void* stream);
 
+/* diffusion.dpmpp_2m_sde_sample(model, x, t, prev_xstart, clip_denoised, model_kwargs) -> {'sample','pred_xstart'}: this project's
+ * extension (the reference has no such sampler) -- SDE-DPM-Solver++(2M) of Lu et al. 2022, the STOCHASTIC second-order multistep
+ * solver, x_t -> x_{t-1}.  One UNet forward, then one fused pass (dpmpp_2m_sde_kernel, a third kernel beside the two above):
+ *   D_t    = as vd_dpmpp_2m_sample forms it; written to `pred_xstart`, the NEXT step's prev_xstart
+ *   D      = D_t + w[t] (D_t - D_prev)   with history;  D = D_t without          (w: the row of vd_set_multistep_weights)
+ *   sigma  = sqrt((1 - abp) / (1 - ab)) sqrt(1 - ab / abp),   ab = alphas_cumprod[t], abp = alphas_cumprod_prev[t]   (vd_ddim_sample's at eta = 1)
+ *   eps'   = (sqrt_recip[t] x - D) / sqrt_recipm1[t]
+ *   sample = D sqrt(abp) + sqrt(1 - abp - sigma^2) eps' + [t != 0] sigma z
+ * i.e. the eta = 1 DDIM update with D in place of the x_0 prediction, as vd_dpmpp_2m_sample is the eta = 0 update on the same D.  With
+ * lambda = log(ab / (1 - ab)) / 2, h = lambda[t-1] - lambda[t], r = h_prev / h and w[t] = 1 / (2 r) it is term by term
+ *   x_{t-1} = (sigma'/sigma) e^-h x + alpha' (1 - e^-2h) D_t + alpha' (1 - e^-2h) (D_t - D_prev) / (2 r) + sigma' sqrt(1 - e^-2h) z.
+ * At t = 0 abp = 1, w = 0 and sigma = 0: sample = D_0, nothing infinite, no noise.  Without history it IS vd_ddim_sample at eta = 1.
+ * There is no eta: the stochasticity is the solver's own.  Meant for steps uniform in lambda ('logsnrN'), as vd_dpmpp_2m_sample.
+ * z: `noise` [B][per], or with noise = NULL element i of the Philox stream at (seed, offset) -- vd_randn's element i, the draw
+ * vd_ddim_sample makes for the same state; a step consumes the range of B*per blocks the other drawing samplers consume.
+ * prev_xstart may be NULL and may be the same tensor as pred_xstart, sample may be x (an element is read and then written by one
+ * thread).  A t[b] outside the schedule poisons every output of item b and reads no table; a network output that is not finite
+ * leaves as NaN and sets bit 1 of the device flags, both as in vd_ddim_sample.  Without a weight row the call fails by name.
+ * pred_xstart and eps may be NULL.
+ * vd_dpmpp_2m_sde_from_xstart: the same pass on a caller's x_0 prediction, no network -- the `denoised_fn` form.  ANY per_sample and
+ * alignment are served: 16-byte accesses where per_sample % 4 == 0 and every tensor is 16-byte aligned, element by element otherwise
+ * (same values: the Philox draw of an element does not depend on the path). */
+int vd_dpmpp_2m_sde_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask,
+                           const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
+                           const long long* t, const float* prev_xstart, int observed_frames, int clip_denoised, const float* noise,
+                           unsigned long long seed, unsigned long long offset, float* sample, float* pred_xstart, float* eps,
+                           void* stream);
+int vd_dpmpp_2m_sde_from_xstart(vd_engine* e, int B, long long per_sample, const float* x, const float* xstart_in,
+                                const float* prev_xstart, const long long* t, int clip_denoised, const float* noise,
+                                unsigned long long seed, unsigned long long offset, float* sample, float* pred_xstart, void* stream);
+
 /* diffusion.p_mean_variance(model, x, t, clip_denoised, model_kwargs) (gaussian_diffusion.py:229-372): one UNet forward,
  * then 'pred_xstart' (clipped) and 'mean' = posterior mean of it; 'variance' / 'log_variance' are the schedule rows
  * VD_TAB_LOGVAR at t (the host mirror broadcasts them).  Any of mean / pred_xstart / eps may be NULL. */
@@ -278,7 +309,11 @@ int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float*
  * window's finished steps tells the pass whether there is history -- so ONE graph serves a window's first step (first-order whatever
  * t_start is) and its later ones, and a second window on the same graph starts without history again.  No Philox draws (seed, offset
  * and eta are not read); observed_frames 2 is refused as for sampler 2; without a weight row (vd_set_multistep_weights) it fails
- * with a message that says so.  The prefix cache and the suffix skip apply unchanged. */
+ * with a message that says so.  The prefix cache and the suffix skip apply unchanged.
+ * Sampler 4 is dpmpp_2m_sde_sample (above): history AND noise state live in the graph -- the history buffer and step count of sampler 3,
+ * the Philox pair of samplers 0 and 1 (offset += B*T*3*H*W per step; element i of step k is vd_randn's at (seed, offset + k*B*per)).
+ * It serves observed_frames 0 to 3 as sampler 1 does; eta is not read (and is no part of its signature); vd_window_jump drops its
+ * history; the prefix cache and the suffix skip apply as for sampler 3; without a weight row it fails by name. */
 int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, const float* obs_mask,
                     const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
                     int observed_frames, int sampler, int clip_denoised, float eta, unsigned long long seed,

@@ -359,7 +359,7 @@ struct vd_engine {
     long long* d_win_t = nullptr; size_t win_t_cap = 0;  // [B] current respaced index of the window
     float* d_win_xtm1 = nullptr; size_t win_xtm1_cap = 0; // 'x_t_minus_1' windows: the observed frames re-noised to t - 1, redrawn every step
     unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset, steps the armed window has done}
-    float* d_win_hist = nullptr; size_t win_hist_cap = 0; // samplers with history (dpmpp_2m): the previous step's x_0 prediction, updated in place by the pass
+    float* d_win_hist = nullptr; size_t win_hist_cap = 0; // samplers with history (dpmpp_2m, dpmpp_2m_sde): the previous step's x_0 prediction, updated in place by the pass
 
     ~vd_engine() {
         if (d_freq_time) (void)hipFree(d_freq_time);
@@ -1881,7 +1881,7 @@ struct StepReq {
     const float* noise = nullptr;
     unsigned long long seed = 0, offset = 0;
     const unsigned long long* rng = nullptr;
-    // dpmpp_2m_sample: the previous step's x_0 prediction or null; `hist_on` null, or a device word that is 0 while there is no history
+    // dpmpp_2m_sample, dpmpp_2m_sde_sample: the previous step's x_0 prediction or null; `hist_on` null, or a device word that is 0 while there is no history
     const float* hist = nullptr;
     const unsigned long long* hist_on = nullptr;
     // outputs, each optional except where the entry says otherwise; eps_out = the (guided) network output
@@ -2025,8 +2025,8 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
     if (rc) return rc;
     VD_REQUIRE(r.x && r.obs_src && r.obs && r.lat && r.km && r.fidx && r.t && (want_sample ? r.sample != nullptr : r.mean || r.xstart || r.eps_out),
                "null tensor");
-    VD_REQUIRE(r.sampler == SAMPLER_P || r.eta >= 0.f, "eta");
-    VD_REQUIRE(!sampler_has_history(r.sampler) || e->d_w2m, "dpmpp_2m_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    VD_REQUIRE(r.sampler != SAMPLER_DDIM || r.eta >= 0.f, "eta");
+    VD_REQUIRE(!sampler_has_history(r.sampler) || e->d_w2m, std::string(sampler_name(r.sampler)) + ": no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
     r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
@@ -2310,10 +2310,10 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(sampler_valid(sampler), "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample");
+    VD_REQUIRE(sampler_valid(sampler), "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample, 4 dpmpp_2m_sde_sample");
     VD_REQUIRE(sampler_draws_noise(sampler) || obs_mode != 2, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ") draws no noise: observed_frames = 2 "
                "re-noises the observed frames to t - 1 inside the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
-    VD_REQUIRE(!sampler_has_history(sampler) || e->d_w2m, "sampler 3 (dpmpp_2m_sample): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    VD_REQUIRE(!sampler_has_history(sampler) || e->d_w2m, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + "): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
     if (e->known_src) {
@@ -2335,7 +2335,8 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     VD_HIP(hipGetLastError());
     vd_engine::WinKey key;
     std::memset(&key, 0, sizeof(key));
-    key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.eta = eta; key.cfg_w = e->cfg_w;
+    key.B = B; key.T = T; key.obs_mode = obs_mode; key.sampler = sampler; key.clip = clip; key.cfg_w = e->cfg_w;
+    key.eta = sampler == SAMPLER_DPMPP_2M_SDE ? 0.f : eta;        // (sampler 4 reads no eta: one graph whatever the caller hands)
     key.guid_phi = e->guid_phi; key.dyn_p = e->dyn_p;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
     key.known_src = e->known_src; key.known_mask = e->known_mask;
@@ -2519,7 +2520,7 @@ int vd_q_jump(vd_engine* e, int B, int T, long long frame_pixels, const float* x
     return launch_q_jump(a, static_cast<hipStream_t>(stream));
 }
 
-// t += dt; the Philox counter moves on by `draws`; the count of finished steps returns to 0 (a dpmpp_2m window has no history behind a jump)
+// t += dt; the Philox counter moves on by `draws`; the count of finished steps returns to 0 (a dpmpp_2m or dpmpp_2m_sde window has no history behind a jump)
 __global__ void win_jump_kernel(long long* t, unsigned long long* rng, int B, long long dt, unsigned long long draws) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) t[b] += dt;
@@ -2600,6 +2601,28 @@ int vd_dpmpp_2m_from_xstart(vd_engine* e, int B, long long per, const float* x, 
     return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 
+int vd_dpmpp_2m_sde_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat,
+                           const float* km, const long long* fidx, const long long* t, const float* prev_xstart, int obs_mode, int clip,
+                           const float* noise, unsigned long long seed, unsigned long long offset, float* sample, float* xstart,
+                           float* eps, void* stream) {
+    StepReq r{SAMPLER_DPMPP_2M_SDE, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.hist = prev_xstart;
+    r.noise = noise; r.seed = seed; r.offset = offset;
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
+}
+
+int vd_dpmpp_2m_sde_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const float* prev_xstart,
+                                const long long* t, int clip, const float* noise, unsigned long long seed, unsigned long long offset,
+                                float* sample, float* xstart, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
+    SamplerPassArgs a = pass_args(e, SAMPLER_DPMPP_2M_SDE, B, per, x, t, clip, sample, xstart);
+    a.x0_given = xstart_in; a.hist = prev_xstart;
+    a.noise = noise; a.seed = seed; a.offset = offset;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
+}
+
 int vd_ddim_reverse_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const long long* t,
                                 int clip, float* sample, float* xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
@@ -2613,7 +2636,7 @@ int vd_posterior_update(vd_engine* e, int mode, int B, long long per, const floa
                         const long long* t, int clip, float eta, const float* noise, unsigned long long seed,
                         unsigned long long offset, float* sample, float* xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(x && eps && t && sample && sampler_draws_noise(mode), "arguments");
+    VD_REQUIRE(x && eps && t && sample && sampler_is_posterior(mode), "arguments");
     SamplerPassArgs a = pass_args(e, mode, B, per, x, t, clip, sample, xstart);
     a.eps = eps; a.eta = eta; a.noise = noise; a.seed = seed; a.offset = offset;
     return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
@@ -2623,7 +2646,7 @@ int vd_posterior_from_xstart(vd_engine* e, int mode, int B, long long per, const
                              const long long* t, int clip, float eta, const float* noise, unsigned long long seed,
                              unsigned long long offset, float* sample, float* xstart, float* mean, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(x && xstart_in && t && (sample || xstart || mean) && sampler_draws_noise(mode), "arguments");
+    VD_REQUIRE(x && xstart_in && t && (sample || xstart || mean) && sampler_is_posterior(mode), "arguments");
     SamplerPassArgs a = pass_args(e, mode, B, per, x, t, clip, sample, xstart);
     a.x0_given = xstart_in; a.mean = mean; a.eta = eta; a.noise = noise; a.seed = seed; a.offset = offset;
     return launch_sampler_pass(a, static_cast<hipStream_t>(stream));

@@ -576,8 +576,88 @@ __global__ __launch_bounds__(256) void deterministic_kernel(SamplerPassArgs a) {
     if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
 }
 
+// dpmpp_2m_sde_sample (this project's extension: SDE-DPM-Solver++(2M)), x_t -> x_{t-1}: the one pass that reads history AND noise.  It is
+// ddim_sample's update at eta = 1 on the extrapolated prediction, as dpmpp_2m_sample is the eta = 0 update on it:
+//   D = D_t + w[t] (D_t - D_prev) with history, else D_t;   sigma = sqrt((1 - abp) / (1 - ab)) sqrt(1 - ab / abp);   e = (sr x - D) / srm1
+//   sample = D sqrt(abp) + sqrt(1 - abp - sigma^2) e + [t != 0] sigma z;   pred_xstart = D_t (the next step's history, not D)
+// At t = 0 abp = 1, w = 0, sigma = 0: sample = D_0, nothing infinite, no noise.  z of element i is noise[i] or normal_at(seed, offset, i) --
+// ddim_sample's draw for the same state; {seed, offset} from `dstate` when set.  The head, the NaN of a non-finite x_0 and the error word
+// are posterior_kernel's; history as data (null, or a device word that is 0) and hist aliasing xstart are deterministic_kernel's.
+// V = float4: four elements per thread and pass, 16-byte accesses, one Philox block (normal4_at: normal_at's bits) -- per % 4 == 0 keeps a
+// group inside one batch item.  V = float: any per and any alignment, element by element (launch_sampler_pass chooses).
+__device__ __forceinline__ void pass_ld(const float* p, size_t i, float (&o)[1]) { o[0] = p[i]; }
+__device__ __forceinline__ void pass_ld(const float* p, size_t i, float (&o)[4]) {
+    const float4 v = reinterpret_cast<const float4*>(p)[i];
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+}
+__device__ __forceinline__ void pass_st(float* p, size_t i, const float (&o)[1]) { p[i] = o[0]; }
+__device__ __forceinline__ void pass_st(float* p, size_t i, const float (&o)[4]) { reinterpret_cast<float4*>(p)[i] = make_float4(o[0], o[1], o[2], o[3]); }
+__device__ __forceinline__ void pass_normal(unsigned long long seed, unsigned long long offset, size_t i, float (&o)[1]) { o[0] = normal_at(seed, offset, i); }
+__device__ __forceinline__ void pass_normal(unsigned long long seed, unsigned long long offset, size_t i, float (&o)[4]) {
+    const f32x4 z = normal4_at(seed, offset, i);
+    o[0] = z[0]; o[1] = z[1]; o[2] = z[2]; o[3] = z[3];
+}
+
+template <class V>      // float | float4
+__global__ __launch_bounds__(256) void dpmpp_2m_sde_kernel(SamplerPassArgs a) {
+    constexpr int W = sizeof(V) / sizeof(float);
+    const size_t perv = (size_t)a.per / W, total = (size_t)a.B * perv;
+    if (a.dstate) { a.seed = a.dstate[0]; a.offset = a.dstate[1]; }
+    const int NT = a.num_timesteps;
+    const float* src = a.x0_given ? a.x0_given : a.eps;
+    const bool given = a.x0_given != nullptr;
+    const bool have = a.hist != nullptr && (a.hist_on == nullptr || *a.hist_on != 0ULL);
+    bool nonfinite = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        int t;
+        if (!pass_t<V>(a, i / perv, i, t)) continue;
+        const float* tb = a.tab + t;
+        const float sr = tb[TAB_SQRT_RECIP * NT], srm1 = tb[TAB_SQRT_RECIPM1 * NT];
+        const float ab = tb[TAB_ACP * NT], abp = tb[TAB_ACP_PREV * NT], w = a.w[t];
+        const float sigma = sqrtf((1.f - abp) / (1.f - ab)) * sqrtf(1.f - ab / abp);
+        const float r = sqrtf(abp), c = sqrtf(fmaxf(1.f - abp - sigma * sigma, 0.f));
+        const float sz = t != 0 ? sigma : 0.0f;
+        float x[W], sv[W], p[W] = {}, z[W], x0[W], o[W];
+        pass_ld(a.x, i, x);
+        pass_ld(src, i, sv);
+        if (have) pass_ld(a.hist, i, p);
+        if (a.noise) pass_ld(a.noise, i, z);
+        else pass_normal(a.seed, a.offset, i, z);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            float d0 = pass_x0(x[k], sv[k], given, sr, srm1, a.clip, nonfinite);
+            if (!(fabsf(d0) <= 3.4028234e38f)) d0 = __builtin_nanf("");         // as posterior_kernel: an infinite x_0 leaves as NaN too
+            x0[k] = d0;
+            const float d = have ? d0 + w * (d0 - p[k]) : d0;
+            const float e = (sr * x[k] - d) / srm1;
+            const float mean = d * r + c * e;
+            o[k] = mean + sz * z[k];
+        }
+        if (a.xstart) pass_st(a.xstart, i, x0);
+        pass_st(a.sample, i, o);
+    }
+    if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
+}
+
+static int launch_dpmpp_2m_sde(const SamplerPassArgs& a, hipStream_t s) {
+    const std::string k = "dpmpp_2m_sde_kernel: ";
+    VD_REQUIRE(a.B > 0 && a.per > 0, k + "B and the elements per item must be positive");
+    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, k + "null tensor");
+    VD_REQUIRE(!a.mean, k + "the pass writes no posterior mean");
+    VD_REQUIRE(a.w, "dpmpp_2m_sde_sample: no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool v4 = a.per % 4 == 0 && al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.hist) && al16(a.noise) && al16(a.sample) && al16(a.xstart);
+    const size_t groups = (size_t)a.B * (v4 ? a.per / 4 : a.per);
+    const int grid = (int)std::min<size_t>((groups + 255) / 256, 4096);
+    if (v4) hipLaunchKernelGGL(dpmpp_2m_sde_kernel<float4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(dpmpp_2m_sde_kernel<float>, dim3(grid), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_sampler_pass(const SamplerPassArgs& a, hipStream_t s) {
     VD_REQUIRE(sampler_valid(a.sampler), "sampler pass: sampler");
+    if (a.sampler == SAMPLER_DPMPP_2M_SDE) return launch_dpmpp_2m_sde(a, s);
     const bool f4 = !sampler_draws_noise(a.sampler);        // the float4 passes; posterior_kernel takes any per and any alignment
     if (f4) {
         const std::string k = std::string(a.sampler == SAMPLER_DPMPP_2M ? "dpmpp_2m" : "ddim_reverse") + "_kernel: ";

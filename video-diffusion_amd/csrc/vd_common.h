@@ -434,13 +434,17 @@ int launch_head_gemm(const float* h, const float* affA, const float* affB, const
 int launch_out_gather(const float* T, const float* bias, int nfr, int H, int W, int ldt, int Cout, float* out_nchw, hipStream_t s);
 
 // The samplers of the step path.  The values are ABI (vd_window_begin's `sampler`, vd_posterior_update's `mode`).
-enum Sampler { SAMPLER_P = 0, SAMPLER_DDIM = 1, SAMPLER_DDIM_REVERSE = 2, SAMPLER_DPMPP_2M = 3 };
-inline bool sampler_valid(int s) { return s >= SAMPLER_P && s <= SAMPLER_DPMPP_2M; }
+enum Sampler { SAMPLER_P = 0, SAMPLER_DDIM = 1, SAMPLER_DDIM_REVERSE = 2, SAMPLER_DPMPP_2M = 3, SAMPLER_DPMPP_2M_SDE = 4 };
+inline bool sampler_valid(int s) { return s >= SAMPLER_P && s <= SAMPLER_DPMPP_2M_SDE; }
 inline bool sampler_walks_up(int s) { return s == SAMPLER_DDIM_REVERSE; }                   // t += 1 per step; the others walk down to 0
-inline bool sampler_draws_noise(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM; }      // the others read no noise and no Philox state
-inline bool sampler_has_history(int s) { return s == SAMPLER_DPMPP_2M; }                    // reads the previous step's x_0 prediction
+inline bool sampler_draws_noise(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM || s == SAMPLER_DPMPP_2M_SDE; }   // the others read no noise and no Philox state
+inline bool sampler_has_history(int s) { return s == SAMPLER_DPMPP_2M || s == SAMPLER_DPMPP_2M_SDE; }   // reads the previous step's x_0 prediction
+// the entries that take a `mode` (vd_posterior_update, vd_posterior_from_xstart, vd_dps_step) serve these two alone: sampler 4 draws
+// noise too but has entries of its own
+inline bool sampler_is_posterior(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM; }
 inline const char* sampler_name(int s) {
-    return s == SAMPLER_P ? "p_sample" : s == SAMPLER_DDIM ? "ddim_sample" : s == SAMPLER_DDIM_REVERSE ? "ddim_reverse_sample" : "dpmpp_2m_sample";
+    return s == SAMPLER_P ? "p_sample" : s == SAMPLER_DDIM ? "ddim_sample" : s == SAMPLER_DDIM_REVERSE ? "ddim_reverse_sample"
+         : s == SAMPLER_DPMPP_2M ? "dpmpp_2m_sample" : "dpmpp_2m_sde_sample";
 }
 // The closing pass of a step (misc.hip: launch_sampler_pass), one argument block for every sampler.
 struct SamplerPassArgs {
@@ -451,19 +455,20 @@ struct SamplerPassArgs {
     const int64_t* t;       // [B] respaced index
     const float* tab;       // [NTAB][num_timesteps] float32 tables (gathered in f64 on host, cast like the reference)
     int num_timesteps;
-    int B; long per;        // samplers that draw no noise: per % 4 == 0, every tensor 16-byte aligned (launch_sampler_pass checks)
+    int B; long per;        // samplers that draw no noise: per % 4 == 0, every tensor 16-byte aligned (launch_sampler_pass checks);
+                            // dpmpp_2m_sde: any per and alignment (16-byte accesses where per % 4 == 0 and every tensor is aligned)
     int clip;
     float* sample;          // x_{t-1} (x_{t+1}: ddim_reverse); may alias x: the update is elementwise.  Null: SAMPLER_P only (p_mean_variance)
     float* xstart;          // the x_0 prediction (dpmpp_2m: D_t, the next step's history), or null
     int* err;               // the engine's sticky error word: bit 1 is set when the network output (eps, or the x_0 handed in) is not
                             // finite -- the clamp of clip_denoised would otherwise turn a NaN into a plausible -1 silently
-    // ---- p_sample, ddim_sample
+    // ---- p_sample, ddim_sample (dpmpp_2m_sde: noise, seed, offset and dstate; it reads no eta and writes no mean)
     float* mean = nullptr;              // p_mean_variance's 'mean' (posterior mean of the clipped x0 prediction), or null
     float eta = 0.f;
     const float* noise = nullptr;       // explicit noise or null (then Philox(seed, offset))
     unsigned long long seed = 0, offset = 0;
     const unsigned long long* dstate = nullptr;     // window executor: {seed, offset} read from device memory instead of the arguments
-    // ---- dpmpp_2m_sample
+    // ---- dpmpp_2m_sample, dpmpp_2m_sde_sample
     const float* hist = nullptr;        // D_prev: the previous step's D_t, or null (no history).  May alias xstart: element i is read and then
                                         // written by the same thread, which is how the window executor keeps its history in place
     const unsigned long long* hist_on = nullptr;    // or null; a device word: 0 = this step has no history whatever `hist` holds (a window's first step)

@@ -34,11 +34,13 @@ _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
 def _sampler_id(sampler):
-    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'p_sample' 0 and every other string ddim_sample, 1."""
+    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'dpmpp_2m_sde' 4, 'p_sample' 0 and every other string ddim_sample, 1."""
     if sampler == "ddim_reverse":
         return 2
     if sampler == "dpmpp_2m":
         return 3
+    if sampler == "dpmpp_2m_sde":
+        return 4
     return 0 if sampler == "p_sample" else 1
 
 
@@ -93,7 +95,9 @@ class WindowExecutor:
         t_start, default 0, UP to the last index, draws no noise -- seed and eta are not read -- and takes 'x_t_minus_1' with
         renoise=False only) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: walks down like 'ddim', the previous step's
         x_0 prediction lives in an engine-owned buffer, the window's first step is first-order whatever t_start is, no noise --
-        seed and eta are not read -- and 'x_t_minus_1' with renoise=False only).
+        seed and eta are not read -- and 'x_t_minus_1' with renoise=False only) or 'dpmpp_2m_sde' (dpmpp_2m_sde_sample, this project's
+        extension: the history of 'dpmpp_2m' and the Philox noise of 'ddim' both live in the graph; eta is not read; every
+        observed_frames mode 'ddim' takes, renoise=True included).
         cfg_scale (this project's extension; gaussian_diffusion.py: p_sample): the captured step holds both forwards, the combine pass
         and the sampler pass; the weight is part of the graph's signature, so windows under different weights replay different graphs.
         The noise of a window does not depend on it.  Not served together with prefix_cache or suffix_skip: in the unconditional
@@ -253,7 +257,7 @@ class WindowExecutor:
 
     def jump(self, n=1):
         """n forward diffusion steps of the armed window (a window with a known region only): t += 1 and q_jump at the new t, n times,
-        noise from the window's Philox stream (a range of B*per each); a 'dpmpp_2m' window's next step is first-order again.  Returns
+        noise from the window's Philox stream (a range of B*per each); a 'dpmpp_2m' or 'dpmpp_2m_sde' window's next step is first-order again.  Returns
         the window tensor (updated in place)."""
         self._check_gen("jump")
         self._after_caller()

@@ -14,14 +14,16 @@ a backward-data pass of the whole UNet w.r.t. its input (csrc/backward.hip); `de
 are served as well.  `ddim_reverse_sample` (gaussian_diffusion.py:636-668), the DDIM step towards the noise, is one forward plus its
 own fused pass (csrc/misc.hip: deterministic_kernel); its two loops are this project's extension.  `dpmpp_2m_sample` with its two
 loops is an extension as a whole: DPM-Solver++(2M), the second-order multistep sampler the reference does not have -- one forward plus
-one fused pass (the same kernel template) that reuses the previous step's x_0 prediction.  `cfg_scale` on the step and loop entry points is
+one fused pass (the same kernel template) that reuses the previous step's x_0 prediction; `dpmpp_2m_sde_sample` with its two loops is its
+stochastic form, SDE-DPM-Solver++(2M): ddim_sample's update at eta = 1 on the same extrapolated prediction, one fused pass of its own
+(dpmpp_2m_sde_kernel) that reads history and noise.  `cfg_scale` on the step and loop entry points is
 an extension too: classifier-free guidance on the observed frames, out_u + w (out_c - out_u) with out_u the network output of the same
 call under an all-zero obs_mask -- a second forward and one fused pass (cfg_combine_kernel) in front of the unchanged sampler pass
 (include/vd_amd.h: vd_set_cfg_scale).  Two more extensions make w > 1 usable under clip_denoised, both through
 `GaussianDiffusion.guidance_scope`: guidance rescale (the guided output's spread over the latent frames brought back towards the
 conditional one's) and dynamic thresholding (a per-item percentile of |x_0| over the latent frames in place of the clamp's 1); their
 per-item statistics are taken on the device inside the step (csrc/guidance.hip).  Pixel-mask inpainting is an extension as well
-(RePaint): inside `GaussianDiffusion.known_region_scope` every p_sample / ddim_sample / dpmpp_2m_sample step ends in one more fused pass
+(RePaint): inside `GaussianDiffusion.known_region_scope` every p_sample / ddim_sample / dpmpp_2m_sample / dpmpp_2m_sde_sample step ends in one more fused pass
 that overwrites the known pixels of the latent frames with the known content noised to the level just reached (csrc/known.hip), `q_jump`
 is the forward step of its resampling walk and `repaint_sample_loop` the loop around both.  Zero-shot restoration is the last one
 (DDNM): inside `GaussianDiffusion.measurement_scope` the x_0 prediction of every step is projected onto a degraded copy y of the video,
@@ -369,7 +371,7 @@ class GaussianDiffusion:
     def cfg_scale_scope(self, model, cfg_scale):
         """This project's extension: `with diffusion.cfg_scale_scope(model, w):` -- every step entry point called inside runs with
         classifier-free guidance weight w on the observed frames (p_sample's docstring), the keyword-less ones included:
-        ddim_reverse_sample with its two loops and dpmpp_2m_sample keep the parameter lists they were introduced with and take
+        ddim_reverse_sample with its two loops, dpmpp_2m_sample and dpmpp_2m_sde_sample keep the parameter lists they were introduced with and take
         their scale from here.  The scale found before is back when the block ends, whatever it raised.  Not honoured by
         model(...) itself, use_gradient_method, score_windows and the NLL path (include/vd_amd.h: vd_set_cfg_scale); a step inside
         dps_scope refuses a scale other than 1 by name."""
@@ -396,7 +398,7 @@ class GaussianDiffusion:
     @contextlib.contextmanager
     def known_region_scope(self, model, known_src, known_mask, known_noise=None):
         """This project's extension (RePaint, Lugmayr et al. 2022): `with diffusion.known_region_scope(model, known_src, known_mask):`
-        -- pixel-mask inpainting.  Every p_sample, ddim_sample and dpmpp_2m_sample call inside, and so every loop built on them, ends in
+        -- pixel-mask inpainting.  Every p_sample, ddim_sample, dpmpp_2m_sample and dpmpp_2m_sde_sample call inside, and so every loop built on them, ends in
         the merge pass: on the frames with latent_mask == 1 the pixels where known_mask is 1 are overwritten with
         q_sample(known_src, t - 1, z), known_src itself at t == 0; every other element keeps the bits of the plain step, and
         'pred_xstart' stays the model's own (include/vd_amd.h: vd_set_known_region).  known_src (B, T, 3, H, W); known_mask
@@ -425,8 +427,8 @@ class GaussianDiffusion:
     def measurement_scope(self, model, y, scale=1, gray=False):
         """This project's extension (DDNM, Wang, Yu, Zhang 2022): `with diffusion.measurement_scope(model, y, scale=4):` -- zero-shot
         restoration from a degraded copy of the video.  y = measure(video, scale, gray), (B, T, Cy, H / scale, W / scale): the mean over
-        every scale x scale cell per channel, or over all three channels with gray=True (Cy = 1).  Every p_sample, ddim_sample and
-        dpmpp_2m_sample call inside, every loop built on them and p_mean_variance project the x_0 prediction of the step on the frames
+        every scale x scale cell per channel, or over all three channels with gray=True (Cy = 1).  Every p_sample, ddim_sample,
+        dpmpp_2m_sample and dpmpp_2m_sde_sample call inside, every loop built on them and p_mean_variance project the x_0 prediction of the step on the frames
         with latent_mask == 1: x_0 + A^+(y - A x_0), every element of a cell moved by (y_cell - mean_cell(x_0)), behind the clamp of
         clip_denoised (or the dynamic threshold in its place) and in front of the sampler's own arithmetic, whose clamp is then off
         (include/vd_amd.h: vd_set_measurement).  'pred_xstart', 'mean' and dpmpp_2m's history are the projected x_0; at t == 0 every
@@ -467,7 +469,7 @@ class GaussianDiffusion:
         where the plain step draws it.  zeta is required: finite and not negative, ValueError otherwise; y is checked as
         measurement_scope checks it.
         Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name:
-        dpmpp_2m_sample, ddim_reverse_sample, denoised_fn, use_gradient_method, cfg_scale != 1, guidance_scope with either option set,
+        dpmpp_2m_sample, dpmpp_2m_sde_sample, ddim_reverse_sample, denoised_fn, use_gradient_method, cfg_scale != 1, guidance_scope with either option set,
         known_region_scope and measurement_scope on the same model, return_attn_weights, and WindowExecutor.begin.  Not honoured by
         model(...) itself, p_mean_variance, score_windows and the NLL path.  No claim about restoration quality is made."""
         base = self._bind(model)
@@ -591,20 +593,24 @@ class GaussianDiffusion:
         return self._fused_step(mode, model, x, t, clip_denoised, model_kwargs, eta=eta, noise=noise,
                                 return_attn_weights=return_attn_weights, cfg_scale=cfg_scale)
 
-    # per sampler (the engine's numbering: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample): the fused step's
+    # per sampler (the engine's numbering: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample, 4 dpmpp_2m_sde_sample): the fused step's
     # entry, and the network-free one that finishes a step through denoised_fn
     _ENTRIES = {0: ("vd_p_sample", "vd_posterior_from_xstart"), 1: ("vd_ddim_sample", "vd_posterior_from_xstart"),
-                2: ("vd_ddim_reverse_sample", "vd_ddim_reverse_from_xstart"), 3: ("vd_dpmpp_2m_sample", "vd_dpmpp_2m_from_xstart")}
+                2: ("vd_ddim_reverse_sample", "vd_ddim_reverse_from_xstart"), 3: ("vd_dpmpp_2m_sample", "vd_dpmpp_2m_from_xstart"),
+                4: ("vd_dpmpp_2m_sde_sample", "vd_dpmpp_2m_sde_from_xstart")}
 
     def _fused_step(self, mode, model, x, t, clip_denoised, model_kwargs, eta=0.0, noise=None, prev_xstart=None,
-                    return_attn_weights=None, cfg_scale=1.0):
-        """One step of sampler `mode` as one engine call -> (sample, pred_xstart), fresh tensors.  Samplers 0 and 1 read `noise`
-        (drawn from the global generator when None, even for eta = 0: gaussian_diffusion.py:438 / :628), sampler 3 its `prev_xstart`
-        or None; the others draw and read nothing.  return_attn_weights True / False sets self._last_attn (None leaves it alone)."""
+                    return_attn_weights=None, cfg_scale=1.0, philox=None):
+        """One step of sampler `mode` as one engine call -> (sample, pred_xstart), fresh tensors.  Samplers 0, 1 and 4 read `noise`
+        (drawn from the global generator when None, even for eta = 0: gaussian_diffusion.py:438 / :628), samplers 3 and 4 their
+        `prev_xstart` or None; sampler 2 draws and reads nothing.  philox = (seed, offset), sampler 4 only: no noise tensor -- the pass
+        draws element i from the engine's Philox stream at that state, as a window graph does.  return_attn_weights True / False sets self._last_attn (None leaves it alone)."""
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        if mode in (0, 1):
+        if mode in (0, 1, 4) and philox is None:
             noise = th.randn_like(xs) if noise is None else _f32(noise, model.device)
             assert noise.shape == xs.shape
+        assert philox is None or (mode == 4 and noise is None)
+        seed, offset = (0, 0) if philox is None else (int(philox[0]), int(philox[1]))
         prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
         assert prev is None or prev.shape == xs.shape
         region = _known(model)
@@ -621,7 +627,8 @@ class GaussianDiffusion:
         B, T = xs.shape[:2]
         window = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt))
         flags = (kw["obs_mode"], 1 if clip_denoised else 0)
-        own = {0: (*flags, _lib.ptr(noise), 0, 0), 1: (*flags, float(eta), _lib.ptr(noise), 0, 0), 2: flags, 3: (_lib.ptr(prev), *flags)}[mode]
+        own = {0: (*flags, _lib.ptr(noise), 0, 0), 1: (*flags, float(eta), _lib.ptr(noise), 0, 0), 2: flags, 3: (_lib.ptr(prev), *flags),
+               4: (_lib.ptr(prev), *flags, _lib.ptr(noise), seed, offset)}[mode]
         if return_attn_weights is not None:
             self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
@@ -662,13 +669,14 @@ class GaussianDiffusion:
         return {"mean": mean, "pred_xstart": xstart, "grad": grad, "sample": sample}
 
     def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None,
-                  prev_xstart=None, cfg_scale=1.0):
+                  prev_xstart=None, cfg_scale=1.0, philox=None):
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
         the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
         (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
         in vd_ddim_reverse_from_xstart and draws no noise; mode 3 (dpmpp_2m_sample, with its `prev_xstart` or None) ends in
-        vd_dpmpp_2m_from_xstart and draws none either.  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
+        vd_dpmpp_2m_from_xstart and draws none either; mode 4 (dpmpp_2m_sde_sample) ends in vd_dpmpp_2m_sde_from_xstart with its
+        `prev_xstart` and `noise` (drawn here when None, behind the callback, as for modes 0 and 1).  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
         the guided one, the passes behind it run no network.  dynamic_threshold (guidance_scope) would have to run between the
         callback and those passes: refused."""
         if clip_denoised and _lib.lib().vd_dynamic_threshold(self._bind(model)._handle) != 0.0:
@@ -685,10 +693,16 @@ class GaussianDiffusion:
         out.update({"sample" if mode is not None else "mean": th.empty_like(xs), "pred_xstart": th.empty_like(xs)})
         head = (base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0))
         clip = 1 if clip_denoised else 0
-        if mode in (2, 3):
+        if mode in (2, 3, 4):
             prev = None if prev_xstart is None else _f32(prev_xstart, dev)
             assert prev is None or prev.shape == xs.shape
             own = (_lib.ptr(tt), clip) if mode == 2 else (_lib.ptr(prev), _lib.ptr(tt), clip)
+            if mode == 4 and philox is not None:                   # (seed, offset): the pass draws from the engine's Philox stream
+                own = (*own, None, int(philox[0]), int(philox[1]))
+            elif mode == 4:
+                noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
+                assert noise.shape == xs.shape
+                own = (*own, _lib.ptr(noise), 0, 0)
             args = (*head, *own, _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]))
         else:
             if mode is not None:
@@ -912,6 +926,34 @@ class GaussianDiffusion:
         sample, xstart = self._fused_step(3, model, x, t, clip_denoised, model_kwargs, prev_xstart=prev_xstart)
         return {"sample": sample, "pred_xstart": xstart}
 
+    def dpmpp_2m_sde_sample(self, model, x, t, prev_xstart=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
+        """This project's extension (the reference has no such sampler): one step x_t -> x_{t-1} of SDE-DPM-Solver++(2M) (Lu et al.
+        2022), the STOCHASTIC second-order multistep solver.  `pred_xstart` is formed as ddim_sample forms it; with `prev_xstart` --
+        the 'pred_xstart' the previous step (index t + 1) returned -- the update runs on
+        D = pred_xstart + w[t] (pred_xstart - prev_xstart), without it (a chain's first step, the step behind a jump) on pred_xstart
+        itself, and is then ddim_sample's with eta = 1 (_multistep_weights; include/vd_amd.h: vd_dpmpp_2m_sde_sample).  There is no
+        eta: the stochasticity is the solver's own.  The noise is drawn from the global generator as ddim_sample draws it; the scale
+        of classifier-free guidance comes from cfg_scale_scope.  Meant for timestep_respacing='logsnrN': on steps uniform in t the
+        extrapolation weights grow at the clean end and the second order is lost."""
+        return self._dpmpp_2m_sde(model, x, t, prev_xstart, clip_denoised, denoised_fn, model_kwargs)
+
+    def _dpmpp_2m_sde(self, model, x, t, prev_xstart, clip_denoised, denoised_fn, model_kwargs, noise=None, philox=None):
+        """dpmpp_2m_sde_sample with the step's noise handed in: `noise` (None: drawn from the global generator), or philox =
+        (seed, offset) -- the pass then draws from the engine's Philox stream at that state, which is how infer_video's eager loop
+        repeats a window graph's draws."""
+        if model_kwargs is None:
+            model_kwargs = {}
+        self._refuse_learned(x)
+        _refuse_dps(model, "dpmpp_2m_sde_sample")
+        if denoised_fn is not None:
+            _refuse_known(model, "denoised_fn")
+            _refuse_measurement(model, "denoised_fn")
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=4, noise=noise, prev_xstart=prev_xstart,
+                                 philox=philox)
+            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
+        sample, xstart = self._fused_step(4, model, x, t, clip_denoised, model_kwargs, noise=noise, prev_xstart=prev_xstart, philox=philox)
+        return {"sample": sample, "pred_xstart": xstart}
+
     def q_sample(self, x_start, t, noise=None, model=None):
         """gaussian_diffusion.py:190-206.  Needs an engine for its tables: pass `model` (or call after
         any p_sample on the same diffusion object)."""
@@ -1093,13 +1135,45 @@ class GaussianDiffusion:
             yield out
             img, prev = out["sample"], out["pred_xstart"]
 
+    def dpmpp_2m_sde_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                 latent_mask=None, device=None, progress=False, cfg_scale=1.0):
+        """This project's extension, shaped like dpmpp_2m_sample_loop: dpmpp_2m_sde_sample from the last index down to 0, each step
+        handed the x_0 prediction of the one before and drawing its noise from the global generator; returns the sample only."""
+        final = None
+        for sample in self.dpmpp_2m_sde_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                                device=device, progress=progress, cfg_scale=cfg_scale):
+            final = sample
+        getattr(model, "check_device_errors", lambda: None)()
+        return final["sample"]
+
+    def dpmpp_2m_sde_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
+                                             model_kwargs=None, latent_mask=None, device=None, progress=False, cfg_scale=1.0):
+        """This project's extension: the steps of dpmpp_2m_sde_sample_loop, one dict per index, driven from the host like
+        dpmpp_2m_sample_loop_progressive.  The first step has no history: it is ddim_sample at eta = 1."""
+        cfg_scale = _check_cfg(cfg_scale)
+        base = getattr(model, "model", model)
+        if device is None:
+            device = base.device
+        assert isinstance(shape, (tuple, list))
+        img = noise if noise is not None else th.randn(*shape, device=device)
+        prev = None
+        for i in list(range(self.num_timesteps))[::-1]:
+            t = th.tensor([i] * shape[0], device=device)
+            with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                out = self.dpmpp_2m_sde_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                               model_kwargs=model_kwargs)
+            yield out
+            img, prev = out["sample"], out["pred_xstart"]
+
     def repaint_sample_loop(self, model, shape, known_src, known_mask, sampler="p_sample", jump_length=1, n_resample=1, noise=None,
                             clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
         """This project's extension: RePaint inpainting from the last index down to 0 -- every step inside
         known_region_scope(model, known_src, known_mask), and with n_resample > 1 the walk of respace.repaint_schedule: every
         jump_length steps the chain goes jump_length steps back up (q_jump) and down again, n_resample times in all.  Returns the sample,
         whose known pixels on the latent frames are known_src to the bit.  sampler: 'p_sample' (with p_sample_loop's per-step side
-        draws: n_resample = 1 is p_sample_loop inside the scope), 'ddim' (with `eta`) or 'dpmpp_2m' (first-order after a jump)."""
+        draws: n_resample = 1 is p_sample_loop inside the scope), 'ddim' (with `eta`), 'dpmpp_2m' or 'dpmpp_2m_sde' (both first-order
+        after a jump)."""
         final = None
         for out in self.repaint_sample_loop_progressive(model, shape, known_src, known_mask, sampler=sampler, jump_length=jump_length,
                                                         n_resample=n_resample, noise=noise, clip_denoised=clip_denoised,
@@ -1112,8 +1186,8 @@ class GaussianDiffusion:
                                         noise=None, clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
         """The ops of repaint_sample_loop, one dict per op: {'op': 'step', 't', 'sample', 'pred_xstart'} or {'op': 'jump', 't', 'sample'}."""
         from .respace import repaint_schedule
-        if sampler not in ("p_sample", "ddim", "dpmpp_2m"):
-            raise ValueError(f"sampler={sampler!r}: 'p_sample', 'ddim' or 'dpmpp_2m'")
+        if sampler not in ("p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+            raise ValueError(f"sampler={sampler!r}: 'p_sample', 'ddim', 'dpmpp_2m' or 'dpmpp_2m_sde'")
         ops = repaint_schedule(self.num_timesteps - 1, jump_length, n_resample)
         cfg_scale = _check_cfg(cfg_scale)
         base = getattr(model, "model", model)
@@ -1135,7 +1209,8 @@ class GaussianDiffusion:
                 elif sampler == "ddim":
                     out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
                 else:
+                    step = self.dpmpp_2m_sample if sampler == "dpmpp_2m" else self.dpmpp_2m_sde_sample
                     with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                        out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
+                        out = step(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
                 img, prev = out["sample"], out["pred_xstart"]
                 yield {"op": op, "t": i, "sample": img, "pred_xstart": prev}

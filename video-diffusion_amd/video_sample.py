@@ -69,7 +69,10 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
 
     sampler: 'p_sample' (default), 'ddim' (ddim_sample with `eta`) or 'dpmpp_2m' (dpmpp_2m_sample, this project's extension: the
     second-order multistep solver; each window starts without history, so its first step is first-order; on both executors; meant for
-    timestep_respacing='logsnrN').
+    timestep_respacing='logsnrN') or 'dpmpp_2m_sde' (dpmpp_2m_sde_sample, this project's extension: the stochastic second-order
+    multistep solver; history per window like 'dpmpp_2m'; `eta` is not read; its noise is the engine's Philox stream on BOTH executors,
+    from a seed drawn per window from torch's global generator, so the two executors agree to the bit; refused by name with
+    use_gradient_method and dps_zeta; meant for timestep_respacing='logsnrN').
 
     cfg_scale (this project's extension, both executors, every sampler): the weight w of classifier-free guidance on each window's
     observed frames -- every step runs on out_u + w (out_c - out_u), out_u being the network output with the window's obs_mask
@@ -114,10 +117,13 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         if measurement is None:
             raise ValueError("dps_zeta needs a measurement (measurement=, sr_scale=, gray=)")
         for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
-                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("cfg_scale != 1", float(cfg_scale) != 1.0),
+                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("sampler='dpmpp_2m_sde'", sampler == "dpmpp_2m_sde"),
+                         ("cfg_scale != 1", float(cfg_scale) != 1.0),
                          ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
             if on:
                 raise _lib.VdError(f"{name} together with dps_zeta is not served")
+    if sampler == "dpmpp_2m_sde" and use_gradient_method:
+        raise NotImplementedError("sampler='dpmpp_2m_sde' together with use_gradient_method")
     if measurement is not None:
         from . import _lib
         from .gaussian_diffusion import check_measurement
@@ -228,7 +234,9 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             continue
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
-        prev_xstart = None                                  # dpmpp_2m: the history is the window's own
+        prev_xstart = None                                  # dpmpp_2m, dpmpp_2m_sde: the history is the window's own
+        if sampler == "dpmpp_2m_sde":                       # ... and the noise what the window executor would draw (its seed, its ranges)
+            sde_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if y_w is None:
             scope = contextlib.nullcontext()
         elif dps_zeta is not None:
@@ -242,6 +250,12 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                     with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
                         out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
                                                         model_kwargs=model_kwargs)
+                    local_samples, prev_xstart = out["sample"], out["pred_xstart"]
+                elif sampler == "dpmpp_2m_sde":
+                    k = diffusion.num_timesteps - 1 - timestep
+                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                        out = diffusion._dpmpp_2m_sde(model, local_samples, t_tensors[timestep], prev_xstart, True, None, model_kwargs,
+                                                      philox=(sde_seed, k * local_samples.numel()))
                     local_samples, prev_xstart = out["sample"], out["pred_xstart"]
                 elif sampler == "p_sample":
                     local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
@@ -299,6 +313,9 @@ def _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampl
             if sampler == "dpmpp_2m":
                 with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
                     out = diffusion.dpmpp_2m_sample(model, local, t=t, prev_xstart=prev, clip_denoised=True, model_kwargs=model_kwargs)
+            elif sampler == "dpmpp_2m_sde":
+                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):    # the head of op k's range
+                    out = diffusion._dpmpp_2m_sde(model, local, t, prev, True, None, model_kwargs, philox=(seed, k * n))
             elif sampler == "p_sample":
                 out = diffusion.p_sample(model, local, t=t, clip_denoised=True, model_kwargs=model_kwargs, cfg_scale=cfg_scale)
             else:
@@ -522,9 +539,9 @@ def load_lpips_for(args, device):
 
 def build_parser():
     ap = add_job_arguments(argparse.ArgumentParser())
-    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m"],
-                    help="the step: p_sample (default), ddim (ddim_sample with --eta) or dpmpp_2m (the second-order multistep solver, meant for "
-                         "--timestep_respacing logsnrN); a non-default sampler is named in the run directory")
+    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde"],
+                    help="the step: p_sample (default), ddim (ddim_sample with --eta), dpmpp_2m (the second-order multistep solver) or dpmpp_2m_sde "
+                         "(its stochastic form; both meant for --timestep_respacing logsnrN); a non-default sampler is named in the run directory")
     ap.add_argument("--eta", type=float, default=0.0, help="with --sampler ddim: ddim_sample's eta")
     ap.add_argument("--cfg_scale", type=float, default=1.0,
                     help="classifier-free guidance weight on the observed frames: every step runs on out_u + w (out_c - out_u), out_u being the "
