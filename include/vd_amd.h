@@ -109,7 +109,7 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * copies the flags to the host, clears them, and the host
  * mirror raises IndexError.  bit 0: timestep index out of range.  Raised by every entry that runs the network (the timestep map
  * in front of the forward: vd_p_sample, vd_ddim_sample, vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_p_mean_variance, vd_guided_step,
- * vd_dps_step, the window executor's captured step), by vd_score_windows / vd_op_eps_mse, vd_op_dps_seed and by vd_vb_terms.  The network-free passes
+ * vd_dps_step, vd_eps_vjp, vd_ode_nll_eval, the window executor's captured step), by vd_score_windows / vd_op_eps_mse, vd_op_dps_seed, vd_op_ode_heun and by vd_vb_terms.  The network-free passes
  * vd_posterior_update, vd_posterior_from_xstart, vd_ddim_reverse_from_xstart, vd_dpmpp_2m_from_xstart and vd_q_sample (index -1 wraps
  * to the last row there; below -num_timesteps or above the last row is out of range) poison item b with NaN and do NOT raise
  * the bit: the range of t is their caller's to check (the host mirror reaches the *_from_xstart forms only behind
@@ -127,7 +127,7 @@ int vd_device_errors(vd_engine* e, int* flags);
 /* Longest window, in frames per batch item, that every forward / step / window entry point accepts: 128.  A window is any
  * T in 1..vd_max_window_frames() (the reference's UNet takes any T; --max_frames picks it at sampling time).  T <= 32 runs
  * on the original temporal attention / GroupNorm kernels, 33..128 on their long-window forms (key tiles with an online
- * softmax).  vd_guided_step (use_gradient_method) and vd_dps_step are limited to T <= 32.  Larger T fails with a message naming the limit. */
+ * softmax).  vd_guided_step (use_gradient_method), vd_dps_step, vd_eps_vjp and vd_ode_nll_eval are limited to T <= 32.  Larger T fails with a message naming the limit. */
 int vd_max_window_frames(void);
 
 /* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
@@ -580,6 +580,52 @@ int vd_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src
 int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, const float* eps, const long long* t, int clip_denoised,
                    const float* y, const float* latent_mask, int scale, int gray, float* d_eps, float* d_x, float* rho,
                    float* pred_xstart, void* stream);
+
+/* The vector-Jacobian product of the network, and on it the exact log-likelihood of the probability-flow ODE -- this project's extension
+ * (Song, Sohl-Dickstein, Kingma, Kumar, Ermon, Poole, ICLR 2021; trace estimate: Skilling-Hutchinson; the reference has the variational
+ * bound only, vd_vb_terms).  Both run the taped forward and the backward-data pass of use_gradient_method (second packed image:
+ * vd_set_bwd_weight_storage) and are modelled on vd_dps_step: its workspace, plain launches on `stream`, no host wait.
+ * vd_eps_vjp: eps = eps_theta(x, t) (eps_out, may be NULL) and vjp_out = (d eps / d x)^T cot for a caller's cotangent `cot` of x's shape,
+ *   read on every frame.  The pass runs on s * cot with s the power of two that puts max |cot| into [1, 2) (the split arithmetic keeps its
+ *   22 bits there) and 1 / s is applied on the way out.  The observed frames reach the network through obs_src and are constants: vjp_out
+ *   is exactly 0 on them; on padding frames it is the network's own derivative.
+ * vd_ode_nll_eval: eps (eps_out, may be NULL) and trace_out[b] = (1 / K) sum_k v_k^T (d eps / d x)^T v_k, K = n_probes in 1..64, the dot
+ *   over the frames of item b with latent_mask == 1, accumulated in fp64 in a fixed order (no floating-point atomics: the same bits on
+ *   every run and for every B).  One taped forward serves the K backward passes.  probe == NULL: v_k is the Rademacher probe number
+ *   probe0 + k of vd_rademacher at (seed, item_offset): +-1 needs no rescaling.  Else probe is [K][B][T][3][H][W], read in place as it is
+ *   (no rescaling: keep max |v| near 1; it should be 0 off the latent frames, where the dot does not look).  x_next (may be NULL): the
+ *   Euler step of d(x / r) / d sigma = eps to index t + 1, r = sqrt_alphas_cumprod, sigma = sqrt_recipm1_alphas_cumprod -- the pass of
+ *   vd_ddim_reverse_sample on (x, eps) with its clamp off, on the frames with latent_mask == 1; every other frame keeps the bits of x.
+ * Both fail by name: T above 32, a model that is not epsilon-prediction, learn_sigma, an obs_mode other than 0 (x_0), cfg_scale != 1,
+ *   guidance rescale, dynamic threshold, a known region, a measurement, an armed attention capture, a missing backward image; vd_ode_nll_eval
+ *   also n_probes outside 1..64.  A t[b] outside the schedule raises bit 0 of the error word as every entry that runs the network does.
+ * vd_rademacher: out [B][T][frame_elems] = probe number `probe`: +-1.0f on the frames with lat == 1, 0 elsewhere.  Element j of item b
+ *   (j in 0..per-1, per = T * frame_elems < 2^31) is bit j & 31 of word (j >> 5) & 3 of the Philox4x32-10 block
+ *   (seed, item_offset[b] + probe * ceil(per / 128) + (j >> 7)) of vd_randn's generator; a set bit is -1.  item_offset: [B] device words;
+ *   item b of a batched call has the bits of the call on b alone.
+ * vd_op_masked_dot: out[b] (double, device) = sum over the frames of item b with lat == 1 of (double)a * (double)b: every product exact, the
+ *   sum in an order fixed by (T, frame_elems).  It allocates its scratch, waits for `stream` and frees it.
+ * vd_op_ode_heun: the corrector of Heun's method on the frames with lat == 1, out = r' (x / r + 0.5 (sigma' - sigma) (eps + eps2)) with
+ *   the float32 tables at t[b] and t[b] + 1, one fp32 rounding per operation, nothing fused; other frames keep the bits of x.  out may
+ *   alias x.  A t[b] with no next level poisons item b with NaN and raises bit 0 of the error word.
+ * vd_dequantize: uniform dequantisation of 8-bit data scaled to [-1, 1]: on the frames with lat == 1 out = x + (2 / 256) u, u in [0, 1) with 24
+ *   bits: u = (w >> 8) 2^-24, w word j & 3 of the Philox block (seed, item_offset[b] + (j >> 2)) for element j of item b (the block element j
+ *   of vd_randn(., seed, item_offset[b]) reads); other frames keep the bits of x; out may alias x.
+ * vd_rademacher, vd_op_masked_dot and vd_op_ode_heun take 16-byte accesses while frame_elems % 4 == 0 and the tensors are 16-byte aligned, else element by element: same bits. */
+int vd_eps_vjp(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+               const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, const float* cot,
+               float* eps_out, float* vjp_out, void* stream);
+int vd_ode_nll_eval(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                    const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, int n_probes,
+                    unsigned long long seed, const unsigned long long* item_offset, unsigned long long probe0, const float* probe,
+                    float* eps_out, double* trace_out, float* x_next, void* stream);
+int vd_rademacher(float* out, const float* latent_mask, int B, int T, long long frame_elems, unsigned long long seed,
+                  const unsigned long long* item_offset, unsigned long long probe, void* stream);
+int vd_dequantize(const float* x, const float* latent_mask, int B, int T, long long frame_elems, unsigned long long seed,
+                  const unsigned long long* item_offset, float* out, void* stream);
+int vd_op_masked_dot(const float* a, const float* b, const float* latent_mask, int B, int T, long long frame_elems, double* out, void* stream);
+int vd_op_ode_heun(vd_engine* e, int B, int T, long long frame_elems, const float* x, const float* eps, const float* eps2, const long long* t,
+                   const float* latent_mask, float* out, void* stream);
 
 /* diffusion.q_sample(x_start, t, noise) (gaussian_diffusion.py:190-206). */
 int vd_q_sample(vd_engine* e, int B, long long per_sample, const float* x_start, const long long* t,

@@ -2868,6 +2868,146 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, con
     return launch_dps_seed(da, static_cast<hipStream_t>(stream));
 }
 
+// The opening checks of the two entries that hand out the vector-Jacobian product of the network (vd_eps_vjp, vd_ode_nll_eval): what
+// vd_dps_step checks, under messages of their own that name the entry (`what`: "eps_vjp" | "ode_nll").
+static int check_vjp(vd_engine* e, int B, int T, int obs_mode, const std::string& what) {
+    int rc = check_ready(e, B, T);
+    if (rc) return rc;
+    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(T <= kMaxGuidedWindowFrames, what + ": windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
+                                            " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
+    VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only (predict_xstart is not served)");
+    VD_REQUIRE(!e->cfg.learn_sigma, what + ": learn_sigma is not served (the backward pass carries the 3-channel head only)");
+    VD_REQUIRE(obs_mode == 0, what + ": observed_frames must be x_0 (the observed frames are conditioning: a constant of the derivative)");
+    VD_REQUIRE(e->cfg_w == 1.f, what + " together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
+    VD_REQUIRE(e->guid_phi == 0.f, what + " together with guidance_rescale (vd_set_guidance_rescale) is not served");
+    VD_REQUIRE(e->dyn_p == 0.f, what + " together with dynamic_threshold (vd_set_dynamic_threshold) is not served");
+    VD_REQUIRE(!e->known_src, what + " together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(!e->meas_y, what + " together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), what + " together with return_attn_weights is not served");
+    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, what + ": the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
+    VD_REQUIRE(B <= 256, what + ": at most 256 items");
+    return 0;
+}
+
+// The vector-Jacobian product of the network as a primitive: one taped forward, one backward-data pass with d eps = cot (a copy of it
+// times a power of two, launch_grad_rescale, and 1 / s on the way out).  Modelled on vd_dps_step: its workspace (ensure_ws_guided) and
+// tail layout (eps, deps, ., ., dx_net), plain launches on `stream`, no host wait.  The observed frames come from obs_src (x_0 mode) and
+// are constants: vjp is exactly 0 there.
+int vd_eps_vjp(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+               const long long* fidx, const long long* t, int obs_mode, const float* cot, float* eps_out, float* vjp_out, void* stream) {
+    int rc = check_vjp(e, B, T, obs_mode, "eps_vjp");
+    if (rc) return rc;
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && cot && vjp_out, "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = e->ensure_ws_guided(B, T))) return rc;
+    const int S = e->cfg.image_size;
+    const size_t per = (size_t)T * 3 * S * S, tot = (size_t)B * per;
+    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
+    float* tm = reinterpret_cast<float*>(tail);
+    float* gs = tm + 768;
+    float* buf = reinterpret_cast<float*>(tail + 4096);
+    float *eps = buf, *deps = buf + tot, *dxn = buf + 4 * tot;
+    map_t(e, t, B, tm, st);
+    VD_HIP(hipMemcpyAsync(deps, cot, tot * sizeof(float), hipMemcpyDeviceToDevice, st));     // the forward does not touch the tail
+    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);
+    Tape tp; e->tape = &tp;
+    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps_out ? eps_out : eps};
+    rc = e->forward(fi, st, ar);
+    if (!rc) rc = launch_grad_rescale(deps, tot, gs, st);
+    if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
+    if (!rc) {
+        ProfScope ps(PC_ELEMENTWISE, 1.0 * B * per, 4.0 * B * per * 2.0, st, "eps_vjp_scale");
+        rc = launch_scale_by(dxn, gs, tot, vjp_out, st);
+    }
+    e->tape = nullptr;
+    return rc;
+}
+
+// One point of the probability-flow ODE likelihood (ode_nll.hip): eps = eps_theta(x, t) under the tape, then per probe k the seed --
+// rademacher_kernel at (seed, item_offset[b], probe0 + k), or the caller's probe[k] read in place -- the backward-data pass and
+// masked_dot: trace[b] = (1 / K) sum_k v_k^T (d eps / d x)^T v_k over the item's latent frames, in fp64.  The tape is kept across the K
+// probes: a backward pass reads the taped tensors and writes only what it takes from the arena above the mark, which is released behind
+// it.  x_next (or null): the Euler move to t + 1, deterministic_kernel<SAMPLER_DDIM_REVERSE> on (x, eps) with its clamp off; the frames
+// that are not latent then get the bits of x back (keep_frames_kernel).  Modelled on vd_dps_step (workspace, tail: eps, probe, ., ., dx_net, ., ., partials); plain launches, no host wait.
+int vd_ode_nll_eval(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                    const long long* fidx, const long long* t, int obs_mode, int n_probes, unsigned long long seed,
+                    const unsigned long long* item_offset, unsigned long long probe0, const float* probe, float* eps_out, double* trace_out,
+                    float* x_next, void* stream) {
+    int rc = check_vjp(e, B, T, obs_mode, "ode_nll");
+    if (rc) return rc;
+    VD_REQUIRE(n_probes >= 1 && n_probes <= 64, "ode_nll: n_probes must be 1..64, got " + std::to_string(n_probes));
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && trace_out && (probe || item_offset), "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if ((rc = e->ensure_ws_guided(B, T))) return rc;
+    const int S = e->cfg.image_size;
+    const long fe = 3L * S * S;
+    const size_t per = (size_t)T * fe, tot = (size_t)B * per;
+    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
+    float* tm = reinterpret_cast<float*>(tail);
+    float* buf = reinterpret_cast<float*>(tail + 4096);
+    float *eps = eps_out ? eps_out : buf, *vbuf = buf + tot, *dxn = buf + 4 * tot;
+    double* part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(buf + 7 * tot) + 7) & ~(uintptr_t)7);
+    VD_REQUIRE((size_t)B * masked_dot_blocks((long)per) * sizeof(double) + 8 <= tot * sizeof(float), "ode_nll: window too small for its partial sums");
+    map_t(e, t, B, tm, st);
+    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);
+    Tape tp; e->tape = &tp;
+    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
+    rc = e->forward(fi, st, ar);
+    if (!rc && x_next) {
+        SamplerPassArgs pa = pass_args(e, SAMPLER_DDIM_REVERSE, B, (long long)per, x, t, 0, x_next, nullptr);
+        pa.eps = eps;
+        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 3.0, st);
+        rc = launch_sampler_pass(pa, st);
+        if (!rc) rc = launch_keep_frames(x, lat, B, T, fe, x_next, st);
+    }
+    for (int k = 0; k < n_probes && !rc; ++k) {
+        const float* v = probe ? probe + (size_t)k * tot : vbuf;
+        if (!probe) {
+            ProfScope ps(PC_ELEMENTWISE, 0.0, 4.0 * B * per, st, "rademacher");
+            rc = launch_rademacher(vbuf, lat, B, T, fe, seed, item_offset, probe0 + (unsigned long long)k, st);
+        }
+        const size_t mk = ar.mark();
+        if (!rc) rc = e->backward(fi, v, dxn, st, ar);
+        ar.release(mk);
+        if (!rc) {
+            ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 2.0, st, "masked_dot");
+            rc = launch_masked_dot(v, dxn, lat, B, T, fe, part, k > 0, k == n_probes - 1 ? (double)n_probes : 1.0, trace_out, st);
+        }
+    }
+    e->tape = nullptr;
+    return rc;
+}
+
+// The passes of ode_nll.hip alone on caller's tensors of any frame size: no network, scratch from OpScratch (tests, and the loop's
+// corrector and prior term).
+int vd_rademacher(float* out, const float* lat, int B, int T, long long frame_elems, unsigned long long seed,
+                  const unsigned long long* item_offset, unsigned long long probe, void* stream) {
+    return launch_rademacher(out, lat, B, T, (long)frame_elems, seed, item_offset, probe, static_cast<hipStream_t>(stream));
+}
+
+int vd_dequantize(const float* x, const float* lat, int B, int T, long long frame_elems, unsigned long long seed,
+                  const unsigned long long* item_offset, float* out, void* stream) {
+    return launch_dequantize(x, lat, B, T, (long)frame_elems, seed, item_offset, out, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_masked_dot(const float* a, const float* b, const float* lat, int B, int T, long long frame_elems, double* out, void* stream) {
+    VD_REQUIRE(a && b && lat && out && B > 0 && T > 0 && frame_elems > 0, "masked_dot: arguments");
+    VD_REQUIRE((double)T * (double)frame_elems < 2147483648.0, "masked_dot: an item of fewer than 2^31 elements");
+    OpScratch sc(stream);
+    double* part;
+    int rc = sc.get(&part, (size_t)B * masked_dot_blocks((long)T * (long)frame_elems));
+    if (rc) return rc;
+    return launch_masked_dot(a, b, lat, B, T, (long)frame_elems, part, 0, 1.0, out, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_ode_heun(vd_engine* e, int B, int T, long long frame_elems, const float* x, const float* eps, const float* eps2, const long long* t,
+                   const float* lat, float* out, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    return launch_ode_heun(x, eps, eps2, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, lat, B, T, (long)frame_elems, out,
+                           e->d_err, static_cast<hipStream_t>(stream));
+}
+
 int vd_q_sample(vd_engine* e, int B, long long per, const float* x0, const long long* t, const float* noise, float* out,
                 void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");

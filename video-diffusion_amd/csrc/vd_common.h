@@ -620,6 +620,32 @@ int launch_dps_seed(DpsArgs a, hipStream_t s);
 int launch_dps_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, float zeta,
                      float* sample, float* grad, hipStream_t s);
 
+// Probability-flow ODE likelihood (ode_nll.hip; this project's extension, Song et al. 2021).  Tensors are [B][T][frame_elems], `lat` the
+// [B*T] latent mask, an item has fewer than 2^31 elements.  16-byte accesses while frame_elems % 4 == 0 and the tensors are 16-byte
+// aligned, else element by element: same bits.  No floating-point atomics.
+// launch_rademacher: probe number `probe` of every item: +-1.0f on the frames with lat == 1, 0 elsewhere.  Element j of item b is bit
+// j & 31 of word (j >> 5) & 3 of Philox block (seed, item_offset[b] + probe * ceil(per / 128) + (j >> 7)), per = T * frame_elems; set: -1.
+int launch_rademacher(float* out, const float* lat, int B, int T, long frame_elems, unsigned long long seed,
+                      const unsigned long long* item_offset, unsigned long long probe, hipStream_t s);
+// launch_masked_dot, two launches: per item the fp64 sum of (double)a * (double)b over the elements of its frames with lat == 1, in an
+// order that depends on (T, frame_elems) alone; out[b] = ((accumulate ? out[b] : 0) + sum) / divisor.  part: [B][masked_dot_blocks(per)].
+int masked_dot_blocks(long per);
+int launch_masked_dot(const float* a, const float* b, const float* lat, int B, int T, long frame_elems, double* part, int accumulate,
+                      double divisor, double* out, hipStream_t s);
+// launch_ode_heun: on the frames with lat == 1 out = r' * (x / r + 0.5f * (sigma' - sigma) * (eps + eps2)), r = TAB_SQRT_ACP and
+// sigma = TAB_SQRT_RECIPM1 at t[b] and t[b] + 1, one fp32 rounding per operation; other frames: the bits of x.  out may alias x.  A t[b]
+// with no next level (t < 0 or t + 1 >= num_timesteps): NaN for item b and bit 0 of `err` (or null).
+int launch_ode_heun(const float* x, const float* eps, const float* eps2, const int64_t* t, const float* tab, int num_timesteps,
+                    const float* lat, int B, int T, long frame_elems, float* out, int* err, hipStream_t s);
+// out = x on the frames with lat != 1; the other frames of out are not touched
+int launch_keep_frames(const float* x, const float* lat, int B, int T, long frame_elems, float* out, hipStream_t s);
+// out = x + (2 / 256) u on the frames with lat == 1, u = (w >> 8) 2^-24 with w word j & 3 of Philox block (seed, item_offset[b] + (j >> 2));
+// other frames: the bits of x.  out may alias x.
+int launch_dequantize(const float* x, const float* lat, int B, int T, long frame_elems, unsigned long long seed,
+                      const unsigned long long* item_offset, float* out, hipStream_t s);
+// out = in * gs[1] (launch_grad_rescale's 1 / s)
+int launch_scale_by(const float* in, const float* gs, size_t n, float* out, hipStream_t s);
+
 enum { TAB_SQRT_RECIP = 0, TAB_SQRT_RECIPM1, TAB_COEF1, TAB_COEF2, TAB_LOGVAR, TAB_ACP, TAB_ACP_PREV,
        TAB_SQRT_ACP, TAB_SQRT_1M_ACP, TAB_POST_LOGVAR, TAB_LOG_1M_ACP, TAB_ALPHA, NTAB };
 

@@ -24,8 +24,8 @@ def _window_table(obs_indices, lat_indices, n_items):
     return table, slot < n_obs, (slot >= n_obs) & (slot < n_all)
 
 
-@torch.no_grad()
-def run_bpd_evaluation(model, diffusion, batch, clip_denoised, obs_indices, lat_indices, t_seq=None, observed_frames="x_0"):
+def _build_window(model, batch, obs_indices, lat_indices, observed_frames="x_0"):
+    """(x0, model_kwargs, latent mask, window length) of one window type for every item of the batch: what both evaluations score."""
     dev = model.device
     table, observed, latent = _window_table(obs_indices, lat_indices, batch.shape[0])
     n_slots = table.shape[1]
@@ -38,13 +38,53 @@ def run_bpd_evaluation(model, diffusion, batch, clip_denoised, obs_indices, lat_
     lat_mask = as_mask(latent)
     model_kwargs = dict(frame_indices=table.to(dev), x0=x0, obs_mask=as_mask(observed), latent_mask=lat_mask,
                         kinda_marg_mask=torch.zeros_like(lat_mask), observed_frames=observed_frames, x_t_minus_1=x0)
-    per_t = diffusion.calc_bpd_loop_subsampled(model, x0, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
-                                               latent_mask=lat_mask, t_seq=t_seq)
+    return x0, model_kwargs, lat_mask, n_slots
+
+
+def _scaled(per_t, n_slots):
+    """Every metric summed over its second axis and multiplied by the window length, as numpy arrays."""
     out = {}
     for name, v in per_t.items():
         total = v.sum(dim=1) if v.ndim > 1 else v
         out[name] = (total * n_slots).detach().cpu().numpy()
     return out
+
+
+@torch.no_grad()
+def run_bpd_evaluation(model, diffusion, batch, clip_denoised, obs_indices, lat_indices, t_seq=None, observed_frames="x_0"):
+    x0, model_kwargs, lat_mask, n_slots = _build_window(model, batch, obs_indices, lat_indices, observed_frames)
+    per_t = diffusion.calc_bpd_loop_subsampled(model, x0, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                                               latent_mask=lat_mask, t_seq=t_seq)
+    return _scaled(per_t, n_slots)
+
+
+ODE_DEQUANT_OFFSET = 1 << 39           # Philox blocks: the dequantisation noise of an item sits in the upper half of its 2^40 range, the probes below
+
+
+@torch.no_grad()
+def run_ode_evaluation(model, diffusion, batch, obs_indices, lat_indices, order=2, n_probes=1, seed=0, item_offset=None, dequantize=True):
+    """This project's extension: the probability-flow ODE likelihood (diffusion.ode_nll_loop) of the windows run_bpd_evaluation scores, on the
+    same window tensors.  dequantize: uniform noise U[0, 2 / 256) -- one 8-bit bin of data scaled to [-1, 1] -- is added to the LATENT frames
+    first, element j of item b from the engine's Philox stream at (seed, item_offset[b] + 2^39) (include/vd_amd.h: vd_dequantize), so that
+    the density of continuous x bounds the probability of the discrete video from below; the observed frames the network is conditioned
+    on stay as they are.  item_offset: one Philox block offset per item (default b << 40); the probes read the range below offset + 2^39.
+    Returned like run_bpd_evaluation's: every key of the loop but x_T, summed over the step axis and multiplied by the window length."""
+    from . import _lib
+    x0, model_kwargs, lat_mask, n_slots = _build_window(model, batch, obs_indices, lat_indices, "x_0")
+    B, T = x0.shape[:2]
+    if item_offset is None:
+        item_offset = [b << 40 for b in range(B)]
+    x = x0
+    if dequantize:
+        off = (torch.as_tensor(item_offset, dtype=torch.int64) + ODE_DEQUANT_OFFSET).to(model.device).contiguous()
+        lat = lat_mask.reshape(B * T).float().contiguous()
+        x = torch.empty_like(x0)
+        _lib.check(_lib.lib().vd_dequantize(_lib.ptr(x0), _lib.ptr(lat), B, T, x0[0, 0].numel(), int(seed) & (2 ** 64 - 1), _lib.ptr(off),
+                                            _lib.ptr(x), _lib.current_stream()))
+    res = diffusion.ode_nll_loop(model, x, model_kwargs=model_kwargs, latent_mask=lat_mask, order=order, n_probes=n_probes, seed=seed,
+                                 item_offset=item_offset, clip_denoised=False)
+    res.pop("x_T")
+    return _scaled(res, n_slots)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -89,7 +129,8 @@ def run(args, create=None, device=None):
     """Body of scripts/video_nll.py:87-140,262-352 on the engine: load + share the weights, name the run directory
     (test_util.py:65-132), deal the batches of the selected dataset items to the ranks, and per batch: skip it if every
     `elbos/elbo_<dataset index><postfix>.pkl` exists, else score every window type (`run_bpd_evaluation`) and pickle
-    {metric: array over windows} per video.  Videos come from --videos / --synthetic as in video_sample."""
+    {metric: array over windows} per video.  args.method == 'ode' (this project's extension): the same windows, index files and skipping,
+    scored by `run_ode_evaluation` into `ode_nll/ode_<dataset index>_order<o>_k<K>_seed<S><postfix>.pkl`.  Videos come from --videos / --synthetic as in video_sample."""
     import json
     import os
     import pickle
@@ -115,11 +156,17 @@ def run(args, create=None, device=None):
         args.T = int(dataset[0][0].shape[0])
     args.test_set_size = len(dataset)
     out_dir = None
+    method = getattr(args, "method", "elbo")
+    if method not in ("elbo", "ode"):
+        raise ValueError(f"--method {method!r}: elbo or ode")
+    if method == "ode" and world > 1:
+        raise NotImplementedError("video_nll --method ode on several ranks is not built: run one rank per --task_id")
+    sub, stem = ("elbos", "elbo") if method == "elbo" else ("ode_nll", "ode")
     if rank == 0:
         if args.eval_dir is None and not args.checkpoint_path:
             args.eval_dir = "results/synthetic"
         out_dir = test_util.get_model_results_path(args) / run_id
-        os.makedirs(out_dir / "elbos", exist_ok=True)
+        os.makedirs(out_dir / sub, exist_ok=True)
         json_path = out_dir / "model_config.json"
         if not json_path.exists():
             with test_util.Protect(json_path):
@@ -137,12 +184,16 @@ def run(args, create=None, device=None):
     if getattr(args, "indices_path", None) is None:
         args.indices_path = out_dir / "frame_indices.pt"
     postfix = ("_ddim" if args.use_ddim else "") + (f"_respace{args.timestep_respacing}" if args.timestep_respacing != "" else "")
+    if method == "ode":
+        order, probes, ode_seed = getattr(args, "ode_order", 2), getattr(args, "ode_probes", 1), getattr(args, "ode_seed", 0)
+        dequantize = not getattr(args, "no_dequantize", False)
+        postfix = f"_order{order}_k{probes}_seed{ode_seed}" + ("" if dequantize else "_nodeq") + postfix
     optimal_schedule_path = None if getattr(args, "optimality", None) is None else out_dir / "optimal_schedule.pt"
     batches = [args.indices[k:k + args.batch_size] for k in range(0, len(args.indices), args.batch_size)]
     shared = None
     for task in vdist.task_ids(len(batches), rank, world):
         ids = batches[task]
-        names = [out_dir / "elbos" / f"elbo_{i}{postfix}.pkl" for i in ids]
+        names = [out_dir / sub / f"{stem}_{i}{postfix}.pkl" for i in ids]
         if all(p.exists() for p in names):
             print("Already exist. Skipping", names)
             continue
@@ -153,8 +204,14 @@ def run(args, create=None, device=None):
             if shared is None:
                 shared = get_eval_frame_indices(args, optimal_schedule_path=optimal_schedule_path)
             obs_b, lat_b = [shared[0][i] for i in ids], [shared[1][i] for i in ids]
-        per_window = [run_bpd_evaluation(model, diffusion, batch, args.clip_denoised, [o[w] for o in obs_b], [l[w] for l in lat_b])
-                      for w in range(len(obs_b[0]))]
+        n_win = len(obs_b[0])
+        if method == "ode":                     # item (video i, window w) owns the Philox range [(i n_win + w) << 40, + 2^40): its value does not depend on the batch
+            per_window = [run_ode_evaluation(model, diffusion, batch, [o[w] for o in obs_b], [l[w] for l in lat_b], order=order,
+                                             n_probes=probes, seed=ode_seed, item_offset=[(i * n_win + w) << 40 for i in ids],
+                                             dequantize=dequantize) for w in range(n_win)]
+        else:
+            per_window = [run_bpd_evaluation(model, diffusion, batch, args.clip_denoised, [o[w] for o in obs_b], [l[w] for l in lat_b])
+                          for w in range(n_win)]
         stacked = {k: np.stack([r[k] for r in per_window], axis=1) for k in per_window[0]}
         for j, path in enumerate(names):
             with open(path, "wb") as f:
@@ -172,6 +229,13 @@ def main(argv=None):
     ap.add_argument("--indices_path", default=None, help="saved (obs_indices, lat_indices); default <eval_dir>/frame_indices.pt")
     ap.add_argument("--clip_denoised", type=str2bool, default=True)
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"])
+    ap.add_argument("--method", default="elbo", choices=["elbo", "ode"],
+                    help="elbo: the variational bound (calc_bpd_loop_subsampled, pickles under elbos/); ode: the exact log-likelihood of the "
+                         "probability-flow ODE (ode_nll_loop, pickles under ode_nll/; one rank, windows of at most 32 frames)")
+    ap.add_argument("--ode_order", type=int, default=2, choices=[1, 2], help="1 Euler, 2 Heun")
+    ap.add_argument("--ode_probes", type=int, default=1, help="Rademacher probes per trace, 1..64")
+    ap.add_argument("--ode_seed", type=int, default=0, help="Philox seed of the probes and of the dequantisation noise")
+    ap.add_argument("--no_dequantize", action="store_true", help="score the videos as they are: no U[0, 2/256) noise on the latent frames")
     add_lpips_arguments(ap)
     return run(parse_with_lpips(ap, argv))
 
