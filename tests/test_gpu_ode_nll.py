@@ -15,7 +15,9 @@ import ode_nll_restated as R
 import video_diffusion_amd as vda
 from helpers import ATOL, RTOL, close, synth_sd
 from step_nll_restated import ratio, tables
+from test_gpu_backward import cfg_of, window
 from test_gpu_dpmpp_2m import _rand_window, tiny
+from test_gpu_dps import _dps_call
 from test_gpu_engine import KEYS, _oracle, engine
 from test_gpu_known_region import _np, _same_bits
 from video_diffusion_amd import _lib
@@ -402,7 +404,55 @@ def test_every_refusal_by_its_message():
     model.check_device_errors()
 
 
-# ---------------------------------------------------------------------------------------------------------------- 6 job
+# ---------------------------------------------------------------------------------------------------------------- 6 workspace
+def test_results_do_not_depend_on_where_the_workspace_tail_lies():
+    """The four differentiated entries (use_gradient_method, dps, eps_vjp, ode_nll) keep their own buffers at the END of the engine's
+    workspace.  On one engine of its own (cfg_of(12): 32 x 32, 64 channels): each entry on a window of B = 2, T = 4 (one observed frame,
+    frame 3 of item 1 padding), then eps_vjp at B = 2, T = 12, which grows the workspace and so moves that end, then the four small calls
+    again: every output has the bits it had.  The kernels use no floating-point atomics, so nothing but an address may differ.  A plain
+    p_sample behind all of it has the bits it had on the engine while it was fresh."""
+    cfg = cfg_of(12)
+    model, diff = vda.create_video_model_and_diffusion(**{k: cfg[k] for k in KEYS})
+    model.load_state_dict(synth_sd(model.param_specs()))
+    model.to("cuda").eval()
+
+    def case(T, pad, seed):
+        c = window(2, T, 32, 1, seed=seed, pad=pad)
+        kw = {k: v.cuda() for k, v in c.items() if k != "x"}
+        return c["x"].cuda(), dict(kw, x_t_minus_1=kw["x0"], observed_frames="x_0")
+    x, kw = case(4, [[], [3]], 404)
+    big_x, big_kw = case(12, [[], [11]], 412)
+    g = torch.Generator().manual_seed(405)
+    n1, n2, cot = (torch.randn(x.shape, generator=g).cuda() for _ in range(3))
+    y = vda.gaussian_diffusion.measure(torch.rand(tuple(x.shape), generator=g) * 2 - 1, 4, False)
+    t = torch.tensor([30, 30]).cuda()
+
+    def small_calls():
+        out = {}
+        guided = diff._guided(model, x, t, True, kw, noise2=n2, want_sample=True, _noise=n1)
+        out.update({f"guided.{k}": guided[k] for k in ("mean", "pred_xstart", "grad", "sample")})
+        dps = _dps_call(diff, model, 0, x, t, kw, 0.0, n1, y, 4, False, 0.5)
+        out.update({f"dps.{k}": dps[k] for k in ("sample", "pred_xstart", "grad", "residual_norm")})
+        vjp = diff.eps_vjp(model, x, t, cot, kw)
+        out.update({f"eps_vjp.{k}": vjp[k] for k in ("eps", "vjp")})
+        out.update(zip(("ode_nll.eps", "ode_nll.trace", "ode_nll.x_next"),
+                       _eval(diff, model, x, 30, kw, K=2, seed=9, offsets=[3, (1 << 40) + 17], want_next=True)))
+        return {k: _np(v) for k, v in out.items()}
+    torch.manual_seed(3)
+    plain = _np(diff.p_sample(model, x, t, model_kwargs=kw)["sample"])          # the engine is fresh: no differentiated pass has run on it
+    before = small_calls()
+    assert len(before) == 13 and all(np.isfinite(v).all() for v in before.values())
+    assert np.abs(before["guided.grad"]).max() > 0 and np.abs(before["dps.grad"]).max() > 0 and np.abs(before["eps_vjp.vjp"]).max() > 0
+    assert torch.isfinite(diff.eps_vjp(model, big_x, t, torch.ones_like(big_x), big_kw)["vjp"]).all()
+    after = small_calls()
+    for k, v in before.items():
+        assert _same_bits(after[k], v), k
+    torch.manual_seed(3)
+    assert _same_bits(_np(diff.p_sample(model, x, t, model_kwargs=kw)["sample"]), plain)
+    model.check_device_errors()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7 job
 def test_job_writes_what_the_loop_returns(tmp_path, monkeypatch):
     """video_nll --method ode on two synthetic videos from a checkpoint file: the pickles hold what run_ode_evaluation returns for the item's
     own Philox range, a second run skips finished videos, and --method elbo writes what it wrote before the flag existed."""

@@ -1478,24 +1478,51 @@ int vd_engine::backward(const FwdIn& in, const float* deps, float* dx, hipStream
     return 0;
 }
 
-// workspace of a guided step: forward (taped, nothing released that the backward reads) + backward + the step's own buffers
+// A Tape on the engine while this object lives: forward() records into it, backward() reads it, no return path leaves a dead one behind
+struct TapeScope {
+    vd_engine* e; Tape tp;
+    explicit TapeScope(vd_engine* e_) : e(e_) { e->tape = &tp; }
+    ~TapeScope() { e->tape = nullptr; }
+    TapeScope(const TapeScope&) = delete;
+};
+
+// The workspace of a differentiated pass (vd_guided_step, vd_dps_step, vd_eps_vjp, vd_ode_nll_eval) on a (B, T) window: the arena of the
+// taped forward and the backward, and the pass's own buffers, which END where the buffer ends (ws_cap, also where a larger window grew it):
+//   a header of kHeader bytes in rows of kRow floats: t_model [B] | obs_net [B*T] | lat_net [B*T] (the guided step's network masks) | gscale
+//   kSlots slots of tot floats: eps | deps (ode_nll: the probe) | dxd | mean0 | dx_net | xstart0 | r | the fp64 partial sums (8-byte rounded)
+// mean0 and xstart0 are the guided step's alone, r and the partials dps's and ode_nll's.  Addresses: valid behind ensure_ws_guided(B, T).
+struct DiffWs {
+    static constexpr int kRow = 256, kHeader = 4096, kSlots = 8;      // B <= kRow, and B * T <= kRow where the masks are written
+    const vd_engine* e; size_t tot;
+    DiffWs(const vd_engine* e_, int B, int T) : e(e_), tot((size_t)B * T * 3 * e_->cfg.image_size * e_->cfg.image_size) {}
+    size_t bytes() const { return kHeader + kSlots * tot * sizeof(float); }
+    bool partials_fit(size_t doubles) const { return doubles * sizeof(double) + 8 <= tot * sizeof(float); }
+    char* tail() const { return e->ws + e->ws_cap - bytes(); }
+    float* row(int i) const { return reinterpret_cast<float*>(tail()) + i * kRow; }
+    float* slot(size_t i) const { return reinterpret_cast<float*>(tail() + kHeader) + i * tot; }
+    float* t_model() const { return row(0); }   float* obs_net() const { return row(1); }   float* lat_net() const { return row(2); }
+    float* eps() const { return slot(0); }      float* deps() const { return slot(1); }     float* probe() const { return slot(1); }
+    float* dxd() const { return slot(2); }      float* mean0() const { return slot(3); }    float* dx_net() const { return slot(4); }
+    float* xstart0() const { return slot(5); }  float* r() const { return slot(6); }        float* gscale() const { return row(3); }      // launch_grad_rescale's words
+    double* partials() const { return reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(slot(7)) + 7) & ~(uintptr_t)7); }
+    Arena arena() const { Arena a; a.base = e->ws; a.cap = (size_t)(tail() - e->ws); return a; }      // forward + backward live below the tail
+};
+
+// workspace of a differentiated pass: forward (taped, nothing released that the backward reads) + backward + DiffWs's tail
 int vd_engine::ensure_ws_guided(int B, int T) {
     const long long key = ((long long)B << 32) | (unsigned)T | (1ll << 62);
-    const size_t per = (size_t)B * T * 3 * cfg.image_size * cfg.image_size * sizeof(float);
     size_t tail = 0;
-    int rc = grow_ws(key, 4096 + 8 * per, [&](size_t* peak) {
+    int rc = grow_ws(key, DiffWs(this, B, T).bytes(), [&](size_t* peak) {
         Arena dry; dry.dry = true;
-        Tape tp; tape = &tp;
+        TapeScope ts(this);
         FwdIn fi{}; fi.B = B; fi.T = T;
         int frc = forward(fi, nullptr, dry);
         if (!frc) frc = backward(fi, nullptr, nullptr, nullptr, dry);
-        tape = nullptr;
         *peak = dry.peak;
         return frc;
     }, &tail);
-    if (rc) return rc;
-    ws_B = ws_T = 0;                       // the plain step recomputes its tail offsets on its next call
-    return 0;
+    if (!rc) ws_B = ws_T = 0;              // the plain step recomputes its tail offsets on its next call
+    return rc;
 }
 
 // device workspace of one operator call: released once the call's launches have run
@@ -2730,6 +2757,44 @@ int vd_load_weight_bwd(vd_engine* e, const char* name, const float* host, long l
     return 0;
 }
 
+// ---- the differentiated passes: taped forward -> seed -> backward-data pass (vd_guided_step, vd_dps_step, vd_eps_vjp, vd_ode_nll_eval)
+// Their shared refusals under the entry's name.  plain_state: also the engine state that would act on a plain step, and the item limit
+// (the guided step leaves those switches to its Python caller and has its own limit); eps_note: what the vjp entries add on a START_X model.
+static int check_diff(vd_engine* e, int B, int T, const std::string& what, bool plain_state = true, const char* eps_note = "") {
+    VD_REQUIRE(T <= kMaxGuidedWindowFrames, what + ": windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
+                                            " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
+    VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only" + eps_note);
+    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, what + ": the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
+    VD_REQUIRE(!e->meas_y, what + " together with a measurement (vd_set_measurement) is not served");
+    if (!plain_state) return 0;
+    VD_REQUIRE(e->cfg_w == 1.f, what + " together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
+    VD_REQUIRE(e->guid_phi == 0.f, what + " together with guidance_rescale (vd_set_guidance_rescale) is not served");
+    VD_REQUIRE(e->dyn_p == 0.f, what + " together with dynamic_threshold (vd_set_dynamic_threshold) is not served");
+    VD_REQUIRE(!e->known_src, what + " together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), what + " together with return_attn_weights is not served");
+    VD_REQUIRE(B <= DiffWs::kRow, what + ": at most 256 items");
+    return 0;
+}
+
+extern "C++" {
+// The opening of every differentiated pass: the workspace, t_model, `pre` (the entry's own launches ahead of the network; it may point the
+// forward at DiffWs's masks), the taped forward, then `body` under the tape, with the arena the backward goes on in.  The forward reads
+// t_model from DiffWs and, where in.eps is null, writes its eps slot.
+template <class Pre, class Body>
+static int taped_pass(vd_engine* e, const DiffWs& w, FwdIn fi, const long long* t, hipStream_t st, Pre pre, Body body) {
+    if (int rc = e->ensure_ws_guided(fi.B, fi.T)) return rc;
+    fi.t_model = w.t_model();
+    if (!fi.eps) fi.eps = w.eps();
+    map_t(e, t, fi.B, w.t_model(), st);
+    if (int rc = pre(fi)) return rc;
+    Arena ar = w.arena();
+    TapeScope ts(e);
+    const int rc = e->forward(fi, st, ar);
+    return rc ? rc : body(fi, ar);
+}
+}
+static int no_pre(FwdIn&) { return 0; }
+
 __global__ void guided_masks_kernel(const float* obs, const float* lat, int n, float* obs_net, float* lat_net) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { obs_net[i] = 0.f; lat_net[i] = obs[i] + lat[i]; }      // gaussian_diffusion.py:268-271
@@ -2742,112 +2807,75 @@ __global__ void guided_masks_kernel(const float* obs, const float* lat, int n, f
 int vd_guided_step(vd_engine* e, int B, int T, const float* x, const float* obs, const float* lat, const float* km,
                    const long long* fidx, const long long* t, int clip, const float* x_t_minus_1, const float* noise,
                    const float* noise2, float* mean, float* xstart, float* grad, float* sample, void* stream) {
-    int rc = check_ready(e, B, T);
-    if (rc) return rc;
-    VD_REQUIRE(T <= kMaxGuidedWindowFrames, "use_gradient_method: windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
-                                            " frames (its temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
+    if (int rc = check_ready(e, B, T)) return rc;
     VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
     VD_REQUIRE(!e->cfg.learn_sigma, "learn_sigma: the reference's sampler asserts on video tensors (gaussian_diffusion.py:283)");
-    VD_REQUIRE(e->mean_type == 0, "use_gradient_method: epsilon-prediction models only");
-    VD_REQUIRE(!e->meas_y, "use_gradient_method together with a measurement (vd_set_measurement) is not served");
-    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, "use_gradient_method: the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
+    if (int rc = check_diff(e, B, T, "use_gradient_method", false)) return rc;
     VD_REQUIRE(x && obs && lat && km && fidx && t && x_t_minus_1 && noise && (sample == nullptr || noise2 != nullptr), "null tensor");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = e->ensure_ws_guided(B, T))) return rc;
     const int N = B * T;
-    const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size, tot = (size_t)B * per;
-    // tail of the workspace: t_model, the two masks, then eps, deps, dxd, mean0, dx_net, xstart0
-    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
-    float* tm = reinterpret_cast<float*>(tail);
-    float* obs_net = tm + 256; float* lat_net = obs_net + 256;
-    VD_REQUIRE(N <= 256 && B <= 256, "window of at most 256 frames");
-    float* buf = reinterpret_cast<float*>(tail + 4096);
-    float *eps = buf, *deps = buf + tot, *dxd = buf + 2 * tot, *mean0 = buf + 3 * tot, *dxn = buf + 4 * tot, *xs0 = buf + 5 * tot;
-    map_t(e, t, B, tm, st);
-    hipLaunchKernelGGL(guided_masks_kernel, dim3((N + 63) / 64), dim3(64), 0, st, obs, lat, N, obs_net, lat_net);
-    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);       // forward + backward live below the step's own buffers
-    Tape tp; e->tape = &tp;
-    FwdIn fi{B, T, x, x, obs_net, lat_net, km, tm, reinterpret_cast<const int64_t*>(fidx), 0, eps};
-    rc = e->forward(fi, st, ar);
-    if (!rc) {
-        GuidedArgs ga{x, eps, noise, x_t_minus_1, obs, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)per, clip,
-                      deps, dxd, mean0, xstart ? xstart : xs0};
-        ga.err = e->d_err;
-        rc = launch_guided_grad(ga, st);
-        float* gs = lat_net + 256;                                            // 4 floats of the tail's spare kilobyte
-        if (!rc) { rc = launch_grad_rescale(deps, tot, gs, st); ga.gscale = gs; }
-        if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
-        if (!rc) rc = launch_guided_final(ga, dxn, noise2, grad, mean, sample, st);
-    }
-    e->tape = nullptr;
-    return rc;
+    VD_REQUIRE(N <= DiffWs::kRow && B <= DiffWs::kRow, "window of at most 256 frames");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
+    const DiffWs w(e, B, T);
+    FwdIn in{B, T, x, x, nullptr, nullptr, km, nullptr, reinterpret_cast<const int64_t*>(fidx), 0, nullptr};
+    return taped_pass(e, w, in, t, st, [&](FwdIn& fi) {
+        fi.obs = w.obs_net(); fi.lat = w.lat_net();
+        hipLaunchKernelGGL(guided_masks_kernel, dim3((N + 63) / 64), dim3(64), 0, st, obs, lat, N, w.obs_net(), w.lat_net());
+        return 0;
+    }, [&](const FwdIn& fi, Arena& ar) {
+        GuidedArgs ga{x, fi.eps, noise, x_t_minus_1, obs, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)per, clip,
+                      w.deps(), w.dxd(), w.mean0(), xstart ? xstart : w.xstart0()};
+        ga.err = e->d_err; ga.gscale = w.gscale();
+        int rc = launch_guided_grad(ga, st);
+        if (!rc) rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+        if (!rc) rc = e->backward(fi, w.deps(), w.dx_net(), st, ar);
+        if (!rc) rc = launch_guided_final(ga, w.dx_net(), noise2, grad, mean, sample, st);
+        return rc;
+    });
 }
 
 // One step of diffusion posterior sampling (dps.hip) on a measurement y of the "cell mean" operators.  The network sees the window as the
 // plain step hands it over -- the caller's masks and obs_mode -- under the tape; the sampler pass writes the plain step's sample' and
 // pred_xstart; the residual and seed passes give rho_b and its cotangents, the backward-data pass carries d eps to x_t (on a power-of-two
 // multiple, launch_grad_rescale), and the final pass moves the latent frames: sample = fmaf(-zeta, g, sample').  Plain launches on
-// `stream`, no host wait.  The workspace is the guided step's: r and the partials lie in the two spare slots of its tail.
+// `stream`, no host wait.  Workspace: DiffWs.
 int vd_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
                 const long long* fidx, const long long* t, int obs_mode, int clip, int sampler, float eta, const float* noise,
                 const float* y, int scale, int gray, float zeta, float* sample, float* xstart, float* grad, float* residual_norm,
                 void* stream) {
-    int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes);
-    if (rc) return rc;
-    VD_REQUIRE(T <= kMaxGuidedWindowFrames, "dps: windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
-                                            " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
-    VD_REQUIRE(e->mean_type == 0, "dps: epsilon-prediction models only");
-    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, "dps: the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
+    if (int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes)) return rc;
+    if (int rc = check_diff(e, B, T, "dps")) return rc;
     VD_REQUIRE(sampler == SAMPLER_P || sampler == SAMPLER_DDIM, "dps: p_sample (0) or ddim_sample (1), got sampler " + std::to_string(sampler));
     VD_REQUIRE(sampler == SAMPLER_P || eta >= 0.f, "eta");
     VD_REQUIRE(zeta >= 0.f && zeta <= 3.4028234e38f, "dps: zeta must be finite and not negative");
     VD_REQUIRE(measurement_served(scale, gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
     VD_REQUIRE(e->cfg.image_size % scale == 0, "measurement: H and W must be divisible by scale");
-    VD_REQUIRE(e->cfg_w == 1.f, "dps together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
-    VD_REQUIRE(e->guid_phi == 0.f, "dps together with guidance_rescale (vd_set_guidance_rescale) is not served");
-    VD_REQUIRE(e->dyn_p == 0.f, "dps together with dynamic_threshold (vd_set_dynamic_threshold) is not served");
-    VD_REQUIRE(!e->known_src, "dps together with a known region (vd_set_known_region) is not served");
-    VD_REQUIRE(!e->meas_y, "dps together with a measurement (vd_set_measurement) is not served");
-    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "dps together with return_attn_weights is not served");
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && noise && y && sample && xstart, "null tensor");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = e->ensure_ws_guided(B, T))) return rc;
     const int S = e->cfg.image_size;
-    const size_t per = (size_t)T * 3 * S * S, tot = (size_t)B * per;
-    VD_REQUIRE(B <= 256, "dps: at most 256 items");
-    // tail of the workspace, as the guided step lays it out: t_model and the rescale words, then eps, deps, dxd, (free), dx_net, (free), r, partials
-    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
-    float* tm = reinterpret_cast<float*>(tail);
-    float* gs = tm + 768;
-    float* buf = reinterpret_cast<float*>(tail + 4096);
-    float *eps = buf, *deps = buf + tot, *dxd = buf + 2 * tot, *dxn = buf + 4 * tot, *rbuf = buf + 6 * tot;
-    double* part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(buf + 7 * tot) + 7) & ~(uintptr_t)7);
-    VD_REQUIRE((size_t)B * dps_partials_per_item() * sizeof(double) + 8 <= tot * sizeof(float), "dps: window too small for its partial sums");
-    map_t(e, t, B, tm, st);
-    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);       // forward + backward live below the step's own buffers
-    Tape tp; e->tape = &tp;
-    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
-    rc = e->forward(fi, st, ar);
-    if (!rc) {
+    const size_t per = (size_t)T * 3 * S * S;
+    const DiffWs w(e, B, T);
+    VD_REQUIRE(w.partials_fit((size_t)B * dps_partials_per_item()), "dps: window too small for its partial sums");
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, nullptr};
+    return taped_pass(e, w, in, t, st, no_pre, [&](const FwdIn& fi, Arena& ar) {
         SamplerPassArgs pa = pass_args(e, sampler, B, (long long)per, x, t, clip, sample, xstart);
-        pa.eps = eps; pa.eta = eta; pa.noise = noise;
-        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
-        rc = launch_sampler_pass(pa, st);
-    }
-    if (!rc) {
-        DpsArgs da{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, S, S, scale, gray ? 1 : 0, clip,
-                   rbuf, part, deps, dxd, nullptr, residual_norm, e->d_err};
-        ProfScope ps(PC_ELEMENTWISE, 4.0 * B * per, 4.0 * B * per * 6.0, st, "dps_seed");
-        rc = launch_dps_seed(da, st);
-    }
-    if (!rc) rc = launch_grad_rescale(deps, tot, gs, st);
-    if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
-    if (!rc) {
-        ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "dps_final");
-        rc = launch_dps_final(dxd, dxn, gs, lat, B, T, (long)(per / T), zeta, sample, grad, st);
-    }
-    e->tape = nullptr;
-    return rc;
+        pa.eps = fi.eps; pa.eta = eta; pa.noise = noise;
+        int rc;
+        { ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st); rc = launch_sampler_pass(pa, st); }
+        if (!rc) {
+            DpsArgs da{x, fi.eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, S, S, scale, gray ? 1 : 0, clip,
+                       w.r(), w.partials(), w.deps(), w.dxd(), nullptr, residual_norm, e->d_err};
+            ProfScope ps(PC_ELEMENTWISE, 4.0 * B * per, 4.0 * B * per * 6.0, st, "dps_seed");
+            rc = launch_dps_seed(da, st);
+        }
+        if (!rc) rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+        if (!rc) rc = e->backward(fi, w.deps(), w.dx_net(), st, ar);
+        if (!rc) {
+            ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "dps_final");
+            rc = launch_dps_final(w.dxd(), w.dx_net(), w.gscale(), lat, B, T, (long)(per / T), zeta, sample, grad, st);
+        }
+        return rc;
+    });
 }
 
 // The residual and seed passes of vd_dps_step alone, on a caller's (x_t, eps): no network, no workspace of the engine (tests).
@@ -2869,59 +2897,37 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, con
 }
 
 // The opening checks of the two entries that hand out the vector-Jacobian product of the network (vd_eps_vjp, vd_ode_nll_eval): what
-// vd_dps_step checks, under messages of their own that name the entry (`what`: "eps_vjp" | "ode_nll").
+// vd_dps_step checks (check_diff) under the entry's name (`what`: "eps_vjp" | "ode_nll"), and two of their own.
 static int check_vjp(vd_engine* e, int B, int T, int obs_mode, const std::string& what) {
-    int rc = check_ready(e, B, T);
-    if (rc) return rc;
+    if (int rc = check_ready(e, B, T)) return rc;
     VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
-    VD_REQUIRE(T <= kMaxGuidedWindowFrames, what + ": windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
-                                            " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
-    VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only (predict_xstart is not served)");
     VD_REQUIRE(!e->cfg.learn_sigma, what + ": learn_sigma is not served (the backward pass carries the 3-channel head only)");
     VD_REQUIRE(obs_mode == 0, what + ": observed_frames must be x_0 (the observed frames are conditioning: a constant of the derivative)");
-    VD_REQUIRE(e->cfg_w == 1.f, what + " together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
-    VD_REQUIRE(e->guid_phi == 0.f, what + " together with guidance_rescale (vd_set_guidance_rescale) is not served");
-    VD_REQUIRE(e->dyn_p == 0.f, what + " together with dynamic_threshold (vd_set_dynamic_threshold) is not served");
-    VD_REQUIRE(!e->known_src, what + " together with a known region (vd_set_known_region) is not served");
-    VD_REQUIRE(!e->meas_y, what + " together with a measurement (vd_set_measurement) is not served");
-    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), what + " together with return_attn_weights is not served");
-    VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, what + ": the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
-    VD_REQUIRE(B <= 256, what + ": at most 256 items");
-    return 0;
+    return check_diff(e, B, T, what, true, " (predict_xstart is not served)");
 }
 
 // The vector-Jacobian product of the network as a primitive: one taped forward, one backward-data pass with d eps = cot (a copy of it
-// times a power of two, launch_grad_rescale, and 1 / s on the way out).  Modelled on vd_dps_step: its workspace (ensure_ws_guided) and
-// tail layout (eps, deps, ., ., dx_net), plain launches on `stream`, no host wait.  The observed frames come from obs_src (x_0 mode) and
-// are constants: vjp is exactly 0 there.
+// times a power of two, launch_grad_rescale, and 1 / s on the way out).  Workspace: DiffWs; plain launches on `stream`, no host wait.
+// The observed frames come from obs_src (x_0 mode) and are constants: vjp is exactly 0 there.
 int vd_eps_vjp(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
                const long long* fidx, const long long* t, int obs_mode, const float* cot, float* eps_out, float* vjp_out, void* stream) {
-    int rc = check_vjp(e, B, T, obs_mode, "eps_vjp");
-    if (rc) return rc;
+    if (int rc = check_vjp(e, B, T, obs_mode, "eps_vjp")) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && cot && vjp_out, "null tensor");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = e->ensure_ws_guided(B, T))) return rc;
-    const int S = e->cfg.image_size;
-    const size_t per = (size_t)T * 3 * S * S, tot = (size_t)B * per;
-    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
-    float* tm = reinterpret_cast<float*>(tail);
-    float* gs = tm + 768;
-    float* buf = reinterpret_cast<float*>(tail + 4096);
-    float *eps = buf, *deps = buf + tot, *dxn = buf + 4 * tot;
-    map_t(e, t, B, tm, st);
-    VD_HIP(hipMemcpyAsync(deps, cot, tot * sizeof(float), hipMemcpyDeviceToDevice, st));     // the forward does not touch the tail
-    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);
-    Tape tp; e->tape = &tp;
-    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps_out ? eps_out : eps};
-    rc = e->forward(fi, st, ar);
-    if (!rc) rc = launch_grad_rescale(deps, tot, gs, st);
-    if (!rc) rc = e->backward(fi, deps, dxn, st, ar);
-    if (!rc) {
-        ProfScope ps(PC_ELEMENTWISE, 1.0 * B * per, 4.0 * B * per * 2.0, st, "eps_vjp_scale");
-        rc = launch_scale_by(dxn, gs, tot, vjp_out, st);
-    }
-    e->tape = nullptr;
-    return rc;
+    const DiffWs w(e, B, T);
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps_out};
+    return taped_pass(e, w, in, t, st, [&](FwdIn&) -> int {
+        VD_HIP(hipMemcpyAsync(w.deps(), cot, w.tot * sizeof(float), hipMemcpyDeviceToDevice, st));     // the forward does not touch the tail
+        return 0;
+    }, [&](const FwdIn& fi, Arena& ar) {
+        int rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+        if (!rc) rc = e->backward(fi, w.deps(), w.dx_net(), st, ar);
+        if (!rc) {
+            ProfScope ps(PC_ELEMENTWISE, 1.0 * w.tot, 4.0 * w.tot * 2.0, st, "eps_vjp_scale");
+            rc = launch_scale_by(w.dx_net(), w.gscale(), w.tot, vjp_out, st);
+        }
+        return rc;
+    });
 }
 
 // One point of the probability-flow ODE likelihood (ode_nll.hip): eps = eps_theta(x, t) under the tape, then per probe k the seed --
@@ -2929,54 +2935,45 @@ int vd_eps_vjp(vd_engine* e, int B, int T, const float* x, const float* obs_src,
 // masked_dot: trace[b] = (1 / K) sum_k v_k^T (d eps / d x)^T v_k over the item's latent frames, in fp64.  The tape is kept across the K
 // probes: a backward pass reads the taped tensors and writes only what it takes from the arena above the mark, which is released behind
 // it.  x_next (or null): the Euler move to t + 1, deterministic_kernel<SAMPLER_DDIM_REVERSE> on (x, eps) with its clamp off; the frames
-// that are not latent then get the bits of x back (keep_frames_kernel).  Modelled on vd_dps_step (workspace, tail: eps, probe, ., ., dx_net, ., ., partials); plain launches, no host wait.
+// that are not latent then get the bits of x back (keep_frames_kernel).  Workspace: DiffWs; plain launches, no host wait.
 int vd_ode_nll_eval(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
                     const long long* fidx, const long long* t, int obs_mode, int n_probes, unsigned long long seed,
                     const unsigned long long* item_offset, unsigned long long probe0, const float* probe, float* eps_out, double* trace_out,
                     float* x_next, void* stream) {
-    int rc = check_vjp(e, B, T, obs_mode, "ode_nll");
-    if (rc) return rc;
+    if (int rc = check_vjp(e, B, T, obs_mode, "ode_nll")) return rc;
     VD_REQUIRE(n_probes >= 1 && n_probes <= 64, "ode_nll: n_probes must be 1..64, got " + std::to_string(n_probes));
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && trace_out && (probe || item_offset), "null tensor");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((rc = e->ensure_ws_guided(B, T))) return rc;
-    const int S = e->cfg.image_size;
-    const long fe = 3L * S * S;
-    const size_t per = (size_t)T * fe, tot = (size_t)B * per;
-    char* tail = e->ws + e->ws_cap - (4096 + 8 * tot * sizeof(float));
-    float* tm = reinterpret_cast<float*>(tail);
-    float* buf = reinterpret_cast<float*>(tail + 4096);
-    float *eps = eps_out ? eps_out : buf, *vbuf = buf + tot, *dxn = buf + 4 * tot;
-    double* part = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(buf + 7 * tot) + 7) & ~(uintptr_t)7);
-    VD_REQUIRE((size_t)B * masked_dot_blocks((long)per) * sizeof(double) + 8 <= tot * sizeof(float), "ode_nll: window too small for its partial sums");
-    map_t(e, t, B, tm, st);
-    Arena ar; ar.base = e->ws; ar.cap = (size_t)(tail - e->ws);
-    Tape tp; e->tape = &tp;
-    FwdIn fi{B, T, x, obs_src, obs, lat, km, tm, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
-    rc = e->forward(fi, st, ar);
-    if (!rc && x_next) {
-        SamplerPassArgs pa = pass_args(e, SAMPLER_DDIM_REVERSE, B, (long long)per, x, t, 0, x_next, nullptr);
-        pa.eps = eps;
-        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 3.0, st);
-        rc = launch_sampler_pass(pa, st);
-        if (!rc) rc = launch_keep_frames(x, lat, B, T, fe, x_next, st);
-    }
-    for (int k = 0; k < n_probes && !rc; ++k) {
-        const float* v = probe ? probe + (size_t)k * tot : vbuf;
-        if (!probe) {
-            ProfScope ps(PC_ELEMENTWISE, 0.0, 4.0 * B * per, st, "rademacher");
-            rc = launch_rademacher(vbuf, lat, B, T, fe, seed, item_offset, probe0 + (unsigned long long)k, st);
+    const long fe = 3L * e->cfg.image_size * e->cfg.image_size;
+    const size_t per = (size_t)T * fe;
+    const DiffWs w(e, B, T);
+    VD_REQUIRE(w.partials_fit((size_t)B * masked_dot_blocks((long)per)), "ode_nll: window too small for its partial sums");
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps_out};
+    return taped_pass(e, w, in, t, st, no_pre, [&](const FwdIn& fi, Arena& ar) {
+        int rc = 0;
+        if (x_next) {
+            SamplerPassArgs pa = pass_args(e, SAMPLER_DDIM_REVERSE, B, (long long)per, x, t, 0, x_next, nullptr);
+            pa.eps = fi.eps;
+            ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 3.0, st);
+            rc = launch_sampler_pass(pa, st);
+            if (!rc) rc = launch_keep_frames(x, lat, B, T, fe, x_next, st);
         }
-        const size_t mk = ar.mark();
-        if (!rc) rc = e->backward(fi, v, dxn, st, ar);
-        ar.release(mk);
-        if (!rc) {
-            ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 2.0, st, "masked_dot");
-            rc = launch_masked_dot(v, dxn, lat, B, T, fe, part, k > 0, k == n_probes - 1 ? (double)n_probes : 1.0, trace_out, st);
+        for (int k = 0; k < n_probes && !rc; ++k) {
+            const float* v = probe ? probe + (size_t)k * w.tot : w.probe();
+            if (!probe) {
+                ProfScope ps(PC_ELEMENTWISE, 0.0, 4.0 * B * per, st, "rademacher");
+                rc = launch_rademacher(w.probe(), lat, B, T, fe, seed, item_offset, probe0 + (unsigned long long)k, st);
+            }
+            const size_t mk = ar.mark();
+            if (!rc) rc = e->backward(fi, v, w.dx_net(), st, ar);
+            ar.release(mk);
+            if (!rc) {
+                ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 2.0, st, "masked_dot");
+                rc = launch_masked_dot(v, w.dx_net(), lat, B, T, fe, w.partials(), k > 0, k == n_probes - 1 ? (double)n_probes : 1.0, trace_out, st);
+            }
         }
-    }
-    e->tape = nullptr;
-    return rc;
+        return rc;
+    });
 }
 
 // The passes of ode_nll.hip alone on caller's tensors of any frame size: no network, scratch from OpScratch (tests, and the loop's
