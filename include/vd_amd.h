@@ -685,6 +685,23 @@ int vd_op_conv_stats(const float* src0, int Cin, int nfr, int Hs, int Ws, int up
 int vd_op_gn_affine(const double* part0, int split0, int C0, const double* part1, int split1, int C, int nfr, int HW,
                     const float* gamma, const float* beta, const float* film, int film_ld, float* affA, float* affB,
                     void* stream);
+/* The same fold, also writing mr_out[nfr][32][2] = the groups' (mean, rstd) as floats: what the backward pass reads. */
+int vd_op_gn_affine_mr(const double* part0, int split0, int C0, const double* part1, int split1, int C, int nfr, int HW,
+                       const float* gamma, const float* beta, const float* film, int film_ld, float* affA, float* affB,
+                       float* mr_out, void* stream);
+/* The statistics pass alone: part[nfr][split][C][2] doubles = per (frame, pixel range, channel) [sum, sum of squares] of the
+ * virtual concat (src0: channels [0, C0), src1: [C0, C), null when C0 == C); range r covers pixels [r * per, min(HW, (r + 1) * per)),
+ * per = ceil(HW / split), an empty range writes zeros.  split <= 0: vd_gn_stats_split(nfr, HW, C), the engine's choice. */
+int vd_gn_stats_split(int nfr, int HW, int C);
+int vd_op_gn_stats(const float* src0, const float* src1, int C0, int C, int nfr, int HW, int split, double* part, void* stream);
+/* GroupNorm(+FiLM)(+SiLU) in one launch: every block folds its frame's statistics from the one or two tables itself, then
+ * y[n][p][c] = SiLU?(concat(src0, src1)[n][p][c] * A[n][c] + B[n][c]) with the (A, B) of vd_op_gn_affine. */
+int vd_op_gn_act_fold(const float* src0, const float* src1, int C0, int C, const double* part0, int split0, const double* part1,
+                      int split1, int nfr, int HW, const float* gamma, const float* beta, const float* film, int film_ld, int act,
+                      float* y, void* stream);
+/* The form the engine's GroupNorm + activation takes for a layer call of layer_frames frames of HW pixels and C channels:
+ * 0 = vd_op_gn_act_fold's kernel, 1 = vd_op_gn_affine then vd_op_affine_act (from 64 MB of fp32 tensor on). */
+int vd_gn_act_form(int layer_frames, int HW, int C);
 /* Winograd F(2x2,3x3) image of a 3x3 weight for the fp32-MFMA kernel: U = G g G^T per (cout, cin) with row 2 negated (the
  * kernel negates row 2 of B^T as well), 16*O*I floats in [I/16][16][O/32][2][64][4]; pass as w_wino. */
 int vd_pack_conv3_wino(const float* host_oihw, float* host_out, int O, int I);

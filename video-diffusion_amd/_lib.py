@@ -231,6 +231,11 @@ SIGNATURES = {
     "vd_conv_wino_block_couts": (_I, [_I, _I, _I, _I]),
     "vd_op_conv_stats": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P]),
     "vd_op_gn_affine": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "vd_op_gn_affine_mr": (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "vd_gn_stats_split": (_I, [_I, _I, _I]),
+    "vd_op_gn_stats": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_gn_act_fold": (_I, [_P, _P, _I, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "vd_gn_act_form": (_I, [_I, _I, _I]),
     "vd_pack_conv3_wino": (_I, [_P, _P, _I, _I]),
     "vd_pack_linear_frag": (_I, [_P, _P, _I, _I]),
     "vd_pack_linear_split": (_I, [_P, _P, _I, _I]),

@@ -747,6 +747,13 @@ int vd_engine::gn_fold(const Tens& x0, const Tens* x1, int N, int gw, int gb,
                             C, *A, *Bp, st, mrp);
 }
 
+// The form gn_act takes for a layer call of `layer_frames` frames: 0 = the folding pass, 1 = gn_final_affine + the activation pass,
+// from 64 MB of fp32 tensor on (see gn_act).  Exported as vd_gn_act_form.
+static int gn_act_form(int layer_frames, int HW, int C) {
+    constexpr size_t big = (size_t)64 << 20;
+    return (size_t)layer_frames * HW * C * 4 >= big ? 1 : 0;
+}
+
 // GroupNorm(+FiLM) + SiLU of a (virtually concatenated) tensor into y in ONE launch: the activation pass folds the statistics
 // itself (norm.hip: affine_act_fold_kernel).  For consumers that need nothing but y; not with a tape (the backward pass reads
 // A, B and mean / rstd).
@@ -761,8 +768,7 @@ int vd_engine::gn_act(const Tens& x0, const Tens* x1, int N, int gw, int gb, con
     // sums differs (gn_final_affine deals a group's pairs to eight lanes, the folding pass walks them in sequence), so (A, B) agree to fp64
     // rounding -- after the cast to fp32 in practice to the bit, by construction to 1 ulp.  The 64 MB switch is by the
     // size of the whole layer call (g_sel_nfr): a full window and the compact suffix batch of the same layer take the same form.
-    constexpr size_t big = (size_t)64 << 20;
-    const bool two = (size_t)(g_sel_nfr > N ? g_sel_nfr : N) * HW * C * 4 >= big;      // by the size of the whole layer call: the compact suffix batch takes the full window's form
+    const bool two = gn_act_form(g_sel_nfr > N ? g_sel_nfr : N, HW, C) == 1;      // by the size of the whole layer call: the compact suffix batch takes the full window's form
     float* Aab = two ? ar.get<float>((size_t)N * C) : nullptr;
     float* Bab = two ? ar.get<float>((size_t)N * C) : nullptr;
     if (ar.dry) return 0;
@@ -3272,6 +3278,35 @@ int vd_op_gn_affine(const double* part0, int split0, int C0, const double* part1
     return launch_gn_affine(part0, split0, C0, part1, split1, (double)HW * (C / 32), gamma, beta, film, film_ld, nfr, C, affA,
                             affB, static_cast<hipStream_t>(stream));
 }
+
+int vd_op_gn_affine_mr(const double* part0, int split0, int C0, const double* part1, int split1, int C, int nfr, int HW,
+                       const float* gamma, const float* beta, const float* film, int film_ld, float* affA, float* affB,
+                       float* mr_out, void* stream) {
+    return launch_gn_affine(part0, split0, C0, part1, split1, (double)HW * (C / 32), gamma, beta, film, film_ld, nfr, C, affA,
+                            affB, static_cast<hipStream_t>(stream), mr_out);
+}
+
+int vd_gn_stats_split(int nfr, int HW, int C) {
+    if (nfr <= 0 || HW <= 0 || C < 32 || C % 32 != 0 || C > 1024) return -1;
+    return gn_stats_split(nfr, HW, C);
+}
+
+int vd_op_gn_stats(const float* src0, const float* src1, int C0, int C, int nfr, int HW, int split, double* part, void* stream) {
+    VD_REQUIRE(nfr > 0 && HW > 0 && part, "vd_op_gn_stats: frames, pixels and the table");
+    VD_REQUIRE(C >= 32 && C % 32 == 0 && C <= 1024, "GroupNorm32 channel constraints");
+    return launch_gn_stats(src0, src1, C0, C, nfr, HW, part, split > 0 ? split : gn_stats_split(nfr, HW, C),
+                           static_cast<hipStream_t>(stream));
+}
+
+int vd_op_gn_act_fold(const float* src0, const float* src1, int C0, int C, const double* part0, int split0, const double* part1,
+                      int split1, int nfr, int HW, const float* gamma, const float* beta, const float* film, int film_ld, int act,
+                      float* y, void* stream) {
+    VD_REQUIRE(nfr > 0 && HW > 0 && y && gamma && beta, "vd_op_gn_act_fold: frames, pixels and buffers");
+    GnFold f{part0, split0, part1, split1, (double)HW * (C / 32), gamma, beta, film, film_ld};
+    return launch_affine_act_fold(src0, src1, C0, C, f, nfr, HW, act, y, static_cast<hipStream_t>(stream));
+}
+
+int vd_gn_act_form(int layer_frames, int HW, int C) { return gn_act_form(layer_frames, HW, C); }
 
 int vd_op_gn_fold(const float* src0, const float* src1, int C0, int C, int nfr, int HW, const float* gamma,
                   const float* beta, const float* film, int film_ld, float* affA, float* affB, void* stream) {

@@ -73,7 +73,9 @@ int gn_stats_split(int nfr, int HW, int C) {
 
 int launch_gn_stats(const float* src0, const float* src1, int C0, int C, int nfr, int HW, double* part, int split,
                     hipStream_t s) {
-    VD_REQUIRE(C % 32 == 0 && C <= 1024 && C0 % 4 == 0, "GroupNorm32 channel constraints");
+    VD_REQUIRE(C >= 32 && C % 32 == 0 && C <= 1024 && C0 % 4 == 0 && C0 > 0 && C0 <= C, "GroupNorm32 channel constraints");
+    VD_REQUIRE(src0 != nullptr && (src1 != nullptr || C0 == C), "gn_stats: a second source for the channels from C0 on");
+    VD_REQUIRE(split >= 1 && part != nullptr, "gn_stats: pixel ranges and their table");
     hipLaunchKernelGGL(gn_stats_partial, dim3(split, nfr), dim3(256), 0, s, src0, src1, C0, C, HW, split, part);
     VD_HIP(hipGetLastError());
     return 0;
@@ -144,7 +146,8 @@ __global__ __launch_bounds__(256) void gn_final_affine_kernel(const double* __re
 int launch_gn_affine(const double* part0, int split0, int C0, const double* part1, int split1, double count,
                      const float* gamma, const float* beta, const float* film, int film_ld, int nfr, int C, float* affA,
                      float* affB, hipStream_t s, float* mr_out) {
-    VD_REQUIRE(part0 && (C0 == C || part1), "GroupNorm partial tables");
+    VD_REQUIRE(C >= 32 && C % 32 == 0 && C <= 1024 && C0 % 4 == 0 && C0 > 0 && C0 <= C, "GroupNorm32 channel constraints");
+    VD_REQUIRE(part0 && split0 >= 1 && (C0 == C || (part1 && split1 >= 1)), "GroupNorm partial tables");
     hipLaunchKernelGGL(gn_final_affine_kernel, dim3(nfr), dim3(256), 0, s, part0, split0, C0, part1, split1, count, gamma,
                        beta, film, film_ld, C, affA, affB, mr_out);
     VD_HIP(hipGetLastError());
@@ -199,7 +202,8 @@ constexpr int kAaTargetBlocks = 8192, kAaMinIters = 1;
 
 int launch_affine_act(const float* src0, const float* src1, int C0, int C, const float* affA, const float* affB, int nfr,
                       int HW, int act, float* y, hipStream_t s) {
-    VD_REQUIRE(C % 4 == 0 && C0 % 4 == 0 && C <= 1024 && (src1 != nullptr || C0 == C), "affine_act: channel counts");
+    VD_REQUIRE(C >= 4 && C % 4 == 0 && C0 % 4 == 0 && C0 > 0 && C0 <= C && C <= 1024, "affine_act: channel counts");
+    VD_REQUIRE(src0 != nullptr && (src1 != nullptr || C0 == C), "affine_act: a second source for the channels from C0 on");
     const int tpp = C / 4, ppi = 256 / tpp, threads = ppi * tpp;
     // pixel ranges: enough blocks to fill the chip (>= 2048), at least 4 iterations of 4 loads per block where the frame allows
     int split = 1;
@@ -326,8 +330,9 @@ __global__ __launch_bounds__(256) void affine_act_fold_kernel(const float* __res
 
 int launch_affine_act_fold(const float* src0, const float* src1, int C0, int C, const GnFold& f, int nfr, int HW, int act, float* y,
                            hipStream_t s) {
-    VD_REQUIRE(C % 32 == 0 && C0 % 4 == 0 && C <= 1024 && (src1 != nullptr || C0 == C), "affine_act_fold: channel counts");
-    VD_REQUIRE(f.part0 && (C0 == C || f.part1), "affine_act_fold: GroupNorm partial tables");
+    VD_REQUIRE(C >= 32 && C % 32 == 0 && C0 % 4 == 0 && C0 > 0 && C0 <= C && C <= 1024, "affine_act_fold: channel counts");
+    VD_REQUIRE(src0 != nullptr && (src1 != nullptr || C0 == C), "affine_act_fold: a second source for the channels from C0 on");
+    VD_REQUIRE(f.part0 && f.split0 >= 1 && (C0 == C || (f.part1 && f.split1 >= 1)), "affine_act_fold: GroupNorm partial tables");
     const int tpp = C / 4, ppi = 256 / tpp, threads = ppi * tpp;
     int split = 1;                                  // (coarse blocks: every block folds its frame's table first -- 8192 blocks: 1.74 -> 2.58 ms per step, r05h)
     while (nfr * split < kFoldTargetBlocks && HW / (split * 2) >= ppi * kFoldMinRows) split *= 2;
