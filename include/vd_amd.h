@@ -242,6 +242,48 @@ int vd_dpmpp_2m_sde_from_xstart(vd_engine* e, int B, long long per_sample, const
                                 const float* prev_xstart, const long long* t, int clip_denoised, const float* noise,
                                 unsigned long long seed, unsigned long long offset, float* sample, float* pred_xstart, void* stream);
 
+/* diffusion.unipc_sample(model, x, t, state, clip_denoised, model_kwargs) -> {'sample','pred_xstart','state'}: this project's extension
+ * (the reference has no such sampler) -- UniPC of Zhao et al. 2023 in its data-prediction form, multistep order 2, B(h) = e^-h - 1
+ * ("bh2"), x~_t -> x~_{t-1}.  The forward a step runs anyway at the PREDICTED point x~_t also corrects that point before the next
+ * prediction: one order more than vd_dpmpp_2m_sample with no further network call.  One UNet forward, then one fused pass (unipc_kernel):
+ *   D_t    = as vd_dpmpp_2m_sample forms it (non-finite check, clamp or threshold, measurement projection); written to `pred_xstart`
+ *   n      = min(count, num_timesteps - 1 - t): the steps behind this one, never more than the schedule has above t
+ *   x^c_t  = c0 base + c1 D1 + c2 D2 + c3 D_t     the corrector for the move t+1 -> t, of order min(2, n);  n = 0: x^c_t = x~_t
+ *   sample = p0 x^c_t + p1 D_t + p2 D1            the predictor t -> t-1, of order min(2, n + 1)
+ *   state  <- (x^c_t, D_t, D1)
+ * with the state read (base, D1, D2) = (x^c_{t+1}, D_{t+1}, D_{t+2}).  With lambda = log(ab / (1 - ab)) / 2, alpha = sqrt(ab),
+ * sigma = sqrt(1 - ab), ab = alphas_cumprod, and for a move s -> u = s - 1: h = lambda_u - lambda_s, phi = e^-h - 1 = B,
+ * r = (lambda_{s+1} - lambda_s) / h (negative):
+ *   corrector, order 1:  x^c_u = (sigma_u/sigma_s) base - alpha_u phi D1 - alpha_u B (D_u - D1) / 2
+ *   corrector, order 2:  x^c_u = (sigma_u/sigma_s) base - alpha_u phi D1 - alpha_u B [rho1 (D2 - D1) / r + rho2 (D_u - D1)],
+ *                        rho1 + rho2 = g1 / B, r rho1 + rho2 = 2 g2 / B, g1 = phi / (-h) - 1, g2 = g1 / (-h) - 1/2
+ *   predictor:           x~_u  = (sigma_u/sigma_s) x^c_s - alpha_u phi D_s - [order 2] alpha_u B (D_{s+1} - D_s) / (2 r)
+ * (the published multistep_uni_pc_bh_update; the order-2 predictor is vd_dpmpp_2m_sample's update).  At t = 0 the predictor row is
+ * (0, 1, 0): sample = D_0, nothing infinite.
+ * vd_set_unipc_rows uploads the coefficients, host_rows [14][num_timesteps] float32 (computed in float64, cast elementwise): rows
+ * 0-3 c0..c3 at order 1 (c2 = 0), 4-7 c0..c3 at order 2, 8-10 p0..p2 at order 1 (p2 = 0), 11-13 p0..p2 at order 2, each at the index t
+ * the step runs at.  Rows that do not exist are zero and never selected: any corrector at t = num_timesteps - 1, the order-2 corrector at
+ * t > num_timesteps - 3, the order-2 predictor at t = num_timesteps - 1.  The table belongs to the schedule as the multistep weight row
+ * does: the bound schedule's length, dropped by vd_set_schedule, and the sampler fails by name without it.
+ * State: base / d1 / d2 are read (all three, or all NULL = no state: count must be 0), base_out / d1_out / d2_out written (all three, or
+ * all NULL = not kept); the tensors written may be the tensors read (in place) and sample may be x: an element is read and then
+ * written by one thread.  count = the steps the chain has finished (0: a chain's first step, first-order, no corrector).  No noise is
+ * read, no Philox draw consumed.  A t[b] outside the schedule poisons every output of item b, the state written included, and reads no
+ * table; a network output that is not finite leaves as NaN and sets bit 1 of the device flags.  Refused together with a known region
+ * (vd_set_known_region), by name: the corrector rebuilds the state from `base`, a merge behind the pass would be discarded.
+ * pred_xstart and eps may be NULL.  Meant for steps uniform in lambda ('logsnrN') and not too few: at h near 1 (logsnr10) the
+ * corrector makes the result worse than vd_dpmpp_2m_sample's.
+ * vd_unipc_from_xstart: the same pass on a caller's x_0 prediction, no network -- the `denoised_fn` form.  ANY per_sample and alignment
+ * are served: 16-byte accesses where per_sample % 4 == 0 and every tensor is 16-byte aligned, element by element otherwise (same values). */
+int vd_set_unipc_rows(vd_engine* e, int num_timesteps, const float* host_rows);
+int vd_unipc_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                    const float* kinda_marg_mask, const long long* frame_indices, const long long* t, const float* base,
+                    const float* d1, const float* d2, int count, int observed_frames, int clip_denoised, float* sample,
+                    float* pred_xstart, float* base_out, float* d1_out, float* d2_out, float* eps, void* stream);
+int vd_unipc_from_xstart(vd_engine* e, int B, long long per_sample, const float* x, const float* xstart_in, const float* base,
+                         const float* d1, const float* d2, int count, const long long* t, int clip_denoised, float* sample,
+                         float* pred_xstart, float* base_out, float* d1_out, float* d2_out, void* stream);
+
 /* diffusion.p_mean_variance(model, x, t, clip_denoised, model_kwargs) (gaussian_diffusion.py:229-372): one UNet forward,
  * then 'pred_xstart' (clipped) and 'mean' = posterior mean of it; 'variance' / 'log_variance' are the schedule rows
  * VD_TAB_LOGVAR at t (the host mirror broadcasts them).  Any of mean / pred_xstart / eps may be NULL. */
@@ -313,7 +355,13 @@ int vd_op_eps_mse(vd_engine* e, int B, int T, const float* x_start, const float*
  * Sampler 4 is dpmpp_2m_sde_sample (above): history AND noise state live in the graph -- the history buffer and step count of sampler 3,
  * the Philox pair of samplers 0 and 1 (offset += B*T*3*H*W per step; element i of step k is vd_randn's at (seed, offset + k*B*per)).
  * It serves observed_frames 0 to 3 as sampler 1 does; eta is not read (and is no part of its signature); vd_window_jump drops its
- * history; the prefix cache and the suffix skip apply as for sampler 3; without a weight row it fails by name. */
+ * history; the prefix cache and the suffix skip apply as for sampler 3; without a weight row it fails by name.
+ * Sampler 5 is unipc_sample (above): its three state tensors live in engine-owned buffers of B*T*3*H*W floats each (sampler 3's history
+ * buffer and two more) that the pass updates in place, and the device word counting the window's finished steps picks the order of both
+ * moves -- so ONE graph serves a window's first step (no corrector, first-order predictor, whatever t_start is), its second and its later
+ * ones, and a second window on the same graph starts without state again.  The window tensor at index t holds the predicted x~_t.  No
+ * Philox draws (seed, offset and eta are not read); observed_frames 2 is refused as for sampler 3; a known region and vd_window_jump are
+ * refused by name; without its rows (vd_set_unipc_rows) it fails by name.  The prefix cache and the suffix skip apply unchanged. */
 int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, const float* obs_mask,
                     const float* latent_mask, const float* kinda_marg_mask, const long long* frame_indices,
                     int observed_frames, int sampler, int clip_denoised, float eta, unsigned long long seed,

@@ -172,6 +172,9 @@ SIGNATURES = {
     "vd_dpmpp_2m_from_xstart": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _P, _P]),
     "vd_dpmpp_2m_sde_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _U, _U, _P, _P, _P, _P]),
     "vd_dpmpp_2m_sde_from_xstart": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P, _U, _U, _P, _P, _P]),
+    "vd_set_unipc_rows": (_I, [_P, _I, _P]),
+    "vd_unipc_sample": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "vd_unipc_from_xstart": (_I, [_P, _I, _L, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vd_p_mean_variance": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "vd_vb_terms": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "vd_prior_bpd": (_I, [_P, _I, _I, _P, _P, _P, _P]),

@@ -278,6 +278,7 @@ struct vd_engine {
     float* d_tab = nullptr; int num_timesteps = 0;
     float* d_tmap = nullptr; float rescale = 1.f;
     float* d_w2m = nullptr;           // [num_timesteps] dpmpp_2m extrapolation weights of the bound schedule (vd_set_multistep_weights), or null
+    float* d_unipc = nullptr;         // [UNIPC_ROWS][num_timesteps] unipc_sample's coefficient rows of the bound schedule (vd_set_unipc_rows), or null
     float* d_jump = nullptr;          // [2][num_timesteps] sqrt(1 - beta) | sqrt(beta) of the bound schedule (vd_set_jump_rows), or null
     // workspace: activations of one (B, T) window [0, ws_tail), then the step's tail: t_model [B] (256-byte rounded), the eps scratch,
     // a second scratch of its size for the unconditional output of a cfg step (cfg_scale != 1) -- dead behind the combine pass, it then holds
@@ -360,6 +361,9 @@ struct vd_engine {
     float* d_win_xtm1 = nullptr; size_t win_xtm1_cap = 0; // 'x_t_minus_1' windows: the observed frames re-noised to t - 1, redrawn every step
     unsigned long long* d_win_rng = nullptr;             // {seed, Philox offset, steps the armed window has done}
     float* d_win_hist = nullptr; size_t win_hist_cap = 0; // samplers with history (dpmpp_2m, dpmpp_2m_sde): the previous step's x_0 prediction, updated in place by the pass
+                                                          // (unipc: D_{t+1}, beside the two below)
+    float* d_win_ubase = nullptr; size_t win_ubase_cap = 0; // unipc windows: the corrected state x^c_{t+1} ...
+    float* d_win_ud2 = nullptr; size_t win_ud2_cap = 0;     // ... and D_{t+2}; all three updated in place by the pass
 
     ~vd_engine() {
         if (d_freq_time) (void)hipFree(d_freq_time);
@@ -376,7 +380,10 @@ struct vd_engine {
         if (d_win_rng) (void)hipFree(d_win_rng);
         if (d_win_xtm1) (void)hipFree(d_win_xtm1);
         if (d_win_hist) (void)hipFree(d_win_hist);
+        if (d_win_ubase) (void)hipFree(d_win_ubase);
+        if (d_win_ud2) (void)hipFree(d_win_ud2);
         if (d_w2m) (void)hipFree(d_w2m);
+        if (d_unipc) (void)hipFree(d_unipc);
         if (d_jump) (void)hipFree(d_jump);
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
         for (auto& g : win_graphs) g.release();
@@ -1749,6 +1756,7 @@ int vd_set_schedule(vd_engine* e, int nts, const float* tab, const int* tmap, fl
     if (e->d_tab) VD_HIP(hipFree(e->d_tab));
     if (e->d_tmap) VD_HIP(hipFree(e->d_tmap));
     if (e->d_w2m) { VD_HIP(hipFree(e->d_w2m)); e->d_w2m = nullptr; }      // the multistep weights belong to the schedule that goes
+    if (e->d_unipc) { VD_HIP(hipFree(e->d_unipc)); e->d_unipc = nullptr; } // and so do unipc_sample's rows
     if (e->d_jump) { VD_HIP(hipFree(e->d_jump)); e->d_jump = nullptr; }   // and so do the jump rows
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_tab), (size_t)NTAB * nts * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_tab, tab, (size_t)NTAB * nts * sizeof(float), hipMemcpyHostToDevice));
@@ -1779,6 +1787,23 @@ int vd_set_multistep_weights(vd_engine* e, int nts, const float* w) {
     }
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_w2m), (size_t)nts * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_w2m, w, (size_t)nts * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// unipc_sample's coefficient rows of the bound schedule, [UNIPC_ROWS][num_timesteps] (include/vd_amd.h).  A call of its own for the reason
+// the multistep weights have one.  Captured sampler-5 graphs bake the table's address in: they are dropped when it moves.
+int vd_set_unipc_rows(vd_engine* e, int nts, const float* rows) {
+    VD_REQUIRE(e && rows, "unipc rows");
+    VD_REQUIRE(e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(nts == e->num_timesteps, "unipc rows: " + std::to_string((int)UNIPC_ROWS) + " rows of one entry per index of the bound schedule (" + std::to_string(e->num_timesteps) + ")");
+    if (e->d_unipc) {
+        if (e->win_cur >= 0) e->win_lost = true;
+        e->drop_window_graphs();
+        VD_HIP(hipFree(e->d_unipc));
+        e->d_unipc = nullptr;
+    }
+    VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_unipc), (size_t)UNIPC_ROWS * nts * sizeof(float)));
+    VD_HIP(hipMemcpy(e->d_unipc, rows, (size_t)UNIPC_ROWS * nts * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -1917,6 +1942,11 @@ struct StepReq {
     // dpmpp_2m_sample, dpmpp_2m_sde_sample: the previous step's x_0 prediction or null; `hist_on` null, or a device word that is 0 while there is no history
     const float* hist = nullptr;
     const unsigned long long* hist_on = nullptr;
+    // unipc_sample: the state read (x^c_{t+1}, D_{t+1}, D_{t+2}; all null: none) and written (all null: not kept; may be the tensors read), and
+    // the chain's finished steps -- `count`, or the device word `hist_on` when that is set
+    const float *ubase = nullptr, *ud1 = nullptr, *ud2 = nullptr;
+    float *ubase_out = nullptr, *ud1_out = nullptr, *ud2_out = nullptr;
+    int count = 0;
     // outputs, each optional except where the entry says otherwise; eps_out = the (guided) network output
     float *sample = nullptr, *xstart = nullptr, *mean = nullptr, *eps_out = nullptr;
     const PrefixPlan* pp = nullptr;
@@ -1953,6 +1983,7 @@ static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long lo
     SamplerPassArgs a{sampler, x, nullptr, nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, (long)per, clip,
                       sample, xstart, e->d_err};
     a.w = e->d_w2m;
+    a.urows = e->d_unipc;
     return a;
 }
 
@@ -2024,6 +2055,10 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     }
     pa.mean = r.mean; pa.eta = r.eta; pa.noise = r.noise; pa.seed = r.seed; pa.offset = r.offset; pa.dstate = r.rng;
     pa.hist = r.hist; pa.hist_on = r.hist_on;
+    if (sampler_is_unipc(r.sampler)) {
+        pa.ubase = r.ubase; pa.ud1 = r.ud1; pa.ud2 = r.ud2; pa.count = r.count;
+        pa.ubase_out = r.ubase_out; pa.ud1_out = r.ud1_out; pa.ud2_out = r.ud2_out;
+    }
     if (!sampler_draws_noise(r.sampler)) rc = launch_sampler_pass(pa, st);
     else {
         ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
@@ -2035,6 +2070,19 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     ka.noise = r.known_noise; ka.seed = r.known_seed; ka.offset = r.known_offset; ka.dstate = r.rng;
     ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 3.0, st, "known_merge");
     return launch_known_merge(ka, st);
+}
+
+// what a sampler with history needs beside the schedule (run_step and vd_window_begin; `who` names the caller's sampler), and what sampler 5
+// is refused together with: the corrector rebuilds the state from `base`, so a merge behind the pass would be discarded at the next step
+static int require_history_rows(const vd_engine* e, int sampler, const std::string& who) {
+    if (!sampler_has_history(sampler)) return 0;
+    if (sampler_is_unipc(sampler)) {
+        VD_REQUIRE(e->d_unipc, who + ": no coefficient rows for the bound schedule (vd_set_unipc_rows, after vd_set_schedule)");
+        VD_REQUIRE(!e->known_src, who + " together with a known region (vd_set_known_region) is not served: the corrector rebuilds the state from its own, a merge behind the pass would be discarded");
+        return 0;
+    }
+    VD_REQUIRE(e->d_w2m, who + ": no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    return 0;
 }
 
 // what a measurement is refused together with, by name: the eager entries and vd_window_begin ask this of the engine's state
@@ -2059,7 +2107,7 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
     VD_REQUIRE(r.x && r.obs_src && r.obs && r.lat && r.km && r.fidx && r.t && (want_sample ? r.sample != nullptr : r.mean || r.xstart || r.eps_out),
                "null tensor");
     VD_REQUIRE(r.sampler != SAMPLER_DDIM || r.eta >= 0.f, "eta");
-    VD_REQUIRE(!sampler_has_history(r.sampler) || e->d_w2m, std::string(sampler_name(r.sampler)) + ": no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    if ((rc = require_history_rows(e, r.sampler, sampler_name(r.sampler)))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
     r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
@@ -2202,6 +2250,8 @@ static int window_buffers(vd_engine* e, int B, int obs_mode, int sampler, size_t
     if (rc) return rc;
     if (!e->d_win_rng) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_win_rng), 3 * sizeof(unsigned long long)));
     if (sampler_has_history(sampler) && (rc = e->grow(e->d_win_hist, e->win_hist_cap, (size_t)B * per, true))) return rc;
+    if (sampler_is_unipc(sampler) && ((rc = e->grow(e->d_win_ubase, e->win_ubase_cap, (size_t)B * per, true)) ||
+                                      (rc = e->grow(e->d_win_ud2, e->win_ud2_cap, (size_t)B * per, true)))) return rc;
     return obs_mode == 2 ? e->grow(e->d_win_xtm1, e->win_xtm1_cap, (size_t)B * per, true) : 0;
 }
 
@@ -2293,7 +2343,13 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     StepReq r{k.sampler, B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, k.fidx, e->d_win_t, net_mode, k.clip, k.eta};
     r.rng = e->d_win_rng;
     r.sample = k.x;
-    if (sampler_has_history(k.sampler)) {
+    if (sampler_is_unipc(k.sampler)) {
+        // the three state tensors in place; the count of finished steps picks the order of both moves (0: no corrector, first-order predictor)
+        r.ubase = r.ubase_out = e->d_win_ubase;
+        r.ud1 = r.ud1_out = e->d_win_hist;
+        r.ud2 = r.ud2_out = e->d_win_ud2;
+        r.hist_on = e->d_win_rng + 2;
+    } else if (sampler_has_history(k.sampler)) {
         // the pass reads the history and writes the step's x_0 prediction over it; the count of finished steps (0 on a window's first
         // step, whatever t_start is) tells it whether the buffer holds one
         r.hist = r.xstart = e->d_win_hist;
@@ -2343,10 +2399,10 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     int rc = check_sampler(e, B, T, obs_mode, 3, "observed_frames must be x_0 / x_t / x_t_minus_1 (2: re-noised per step, 3: the caller's tensor as it is)");
     if (rc) return rc;
     VD_REQUIRE(x && obs_src && obs && lat && km && fidx, "null tensor");
-    VD_REQUIRE(sampler_valid(sampler), "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample, 4 dpmpp_2m_sde_sample");
+    VD_REQUIRE(sampler_valid(sampler), "sampler: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample, 4 dpmpp_2m_sde_sample, 5 unipc_sample");
     VD_REQUIRE(sampler_draws_noise(sampler) || obs_mode != 2, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ") draws no noise: observed_frames = 2 "
                "re-noises the observed frames to t - 1 inside the graph and is not served; hand x_t_minus_1 as it is (observed_frames = 3)");
-    VD_REQUIRE(!sampler_has_history(sampler) || e->d_w2m, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + "): no multistep weight row for the bound schedule (vd_set_multistep_weights, after vd_set_schedule)");
+    if ((rc = require_history_rows(e, sampler, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ")"))) return rc;
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
     if (e->known_src) {
@@ -2568,6 +2624,7 @@ int vd_window_jump(vd_engine* e, int n, void* stream) {
     VD_REQUIRE(e->win_cur >= 0, "vd_window_begin first");
     const vd_engine::WinKey& k = e->win_graphs[e->win_cur].key;
     VD_REQUIRE(!sampler_walks_up(k.sampler), "vd_window_jump: sampler 2 (ddim_reverse_sample) walks upwards by itself");
+    VD_REQUIRE(!sampler_is_unipc(k.sampler), "vd_window_jump: sampler 5 (unipc_sample) is not served: its corrector rebuilds the state from the one before the jump");
     VD_REQUIRE(k.known_src, "vd_window_jump: the armed window has no known region (vd_set_known_region before vd_window_begin)");
     VD_REQUIRE(e->d_jump, kNoJumpRows);
     VD_REQUIRE(n >= 0 && e->win_left + n <= e->num_timesteps, "vd_window_jump: t would pass num_timesteps - 1");
@@ -2653,6 +2710,28 @@ int vd_dpmpp_2m_sde_from_xstart(vd_engine* e, int B, long long per, const float*
     SamplerPassArgs a = pass_args(e, SAMPLER_DPMPP_2M_SDE, B, per, x, t, clip, sample, xstart);
     a.x0_given = xstart_in; a.hist = prev_xstart;
     a.noise = noise; a.seed = seed; a.offset = offset;
+    return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
+}
+
+int vd_unipc_sample(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                    const long long* fidx, const long long* t, const float* base, const float* d1, const float* d2, int count, int obs_mode,
+                    int clip, float* sample, float* xstart, float* base_out, float* d1_out, float* d2_out, float* eps, void* stream) {
+    StepReq r{SAMPLER_UNIPC, B, T, x, obs_src, obs, lat, km, fidx, t, obs_mode, clip};
+    r.ubase = base; r.ud1 = d1; r.ud2 = d2; r.count = count;
+    r.ubase_out = base_out; r.ud1_out = d1_out; r.ud2_out = d2_out;
+    r.sample = sample; r.xstart = xstart; r.eps_out = eps;
+    return run_step(e, r, true, stream);
+}
+
+int vd_unipc_from_xstart(vd_engine* e, int B, long long per, const float* x, const float* xstart_in, const float* base, const float* d1,
+                         const float* d2, int count, const long long* t, int clip, float* sample, float* xstart, float* base_out,
+                         float* d1_out, float* d2_out, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && x && xstart_in && t && sample, "arguments");
+    SamplerPassArgs a = pass_args(e, SAMPLER_UNIPC, B, per, x, t, clip, sample, xstart);
+    a.x0_given = xstart_in;
+    a.ubase = base; a.ud1 = d1; a.ud2 = d2; a.count = count;
+    a.ubase_out = base_out; a.ud1_out = d1_out; a.ud2_out = d2_out;
     return launch_sampler_pass(a, static_cast<hipStream_t>(stream));
 }
 

@@ -655,9 +655,94 @@ static int launch_dpmpp_2m_sde(const SamplerPassArgs& a, hipStream_t s) {
     return 0;
 }
 
+// unipc_sample (this project's extension: UniPC of Zhao et al. 2023, data prediction, multistep order 2, B(h) = e^-h - 1), x_t -> x_{t-1}:
+// the forward the step runs at the PREDICTED point x~_t first corrects that point, then predicts the next one -- one pass, both linear:
+//   D_t    = the head every pass shares (pass_x0; a non-finite one leaves as NaN and raises bit 1, as in dpmpp_2m_sde_kernel)
+//   x^c_t  = c0 base + c1 D1 + c2 D2 + c3 D_t      base = x^c_{t+1}, D1 = D_{t+1}, D2 = D_{t+2};  order min(2, n);  n = 0: x^c_t = x~_t
+//   sample = p0 x^c_t + p1 D_t + p2 D1             order min(2, n + 1)
+//   state  <- (x^c_t, D_t, D1)
+// n = min(count, num_timesteps - 1 - t): the steps behind this one, never more than the schedule has above t -- so a row that does not exist
+// (vd_set_unipc_rows leaves it zero) is never selected, whatever count a caller hands.  count is DATA (the host's, or a device word), so one
+// captured graph serves a window's first, second and later steps.  Each sum is one rounded product and a chain of fused multiply-adds, in
+// the order written: 4 roundings into x^c_t, 3 more into the sample (tests/unipc_restated.py counts on it).  At t = 0 the predictor row is
+// (0, 1, 0): sample = D_0.  The state may be updated in place and the sample may alias x: element i is read and then written by one thread.
+// V = float4 | float as in dpmpp_2m_sde_kernel (launch_unipc chooses).
+template <class V>
+__global__ __launch_bounds__(256) void unipc_kernel(SamplerPassArgs a) {
+    constexpr int W = sizeof(V) / sizeof(float);
+    const size_t perv = (size_t)a.per / W, total = (size_t)a.B * perv;
+    const int NT = a.num_timesteps;
+    const float* src = a.x0_given ? a.x0_given : a.eps;
+    const bool given = a.x0_given != nullptr;
+    const bool state = a.ubase != nullptr;
+    const unsigned long long cnt = !state ? 0ULL : a.hist_on ? *a.hist_on : (unsigned long long)a.count;
+    bool nonfinite = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        int t;
+        if (!pass_t<V>(a, i / perv, i, t)) {         // (sample and pred_xstart are poisoned by now) the state of the item as well
+            V q;
+            splat(q, __builtin_nanf(""));
+            if (a.ubase_out) reinterpret_cast<V*>(a.ubase_out)[i] = q;
+            if (a.ud1_out) reinterpret_cast<V*>(a.ud1_out)[i] = q;
+            if (a.ud2_out) reinterpret_cast<V*>(a.ud2_out)[i] = q;
+            continue;
+        }
+        const int above = NT - 1 - t;
+        const int n = cnt < (unsigned long long)above ? (int)cnt : above;
+        const float sr = a.tab[TAB_SQRT_RECIP * NT + t], srm1 = a.tab[TAB_SQRT_RECIPM1 * NT + t];
+        const float* cr = a.urows + (size_t)(n >= 2 ? UNIPC_C2 : UNIPC_C1) * NT + t;
+        const float* pr = a.urows + (size_t)(n >= 1 ? UNIPC_P2 : UNIPC_P1) * NT + t;
+        const float p0 = pr[0], p1 = pr[NT], p2 = pr[2 * NT];
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f;
+        if (n >= 1) { c0 = cr[0]; c1 = cr[NT]; c2 = cr[2 * NT]; c3 = cr[3 * NT]; }
+        float x[W], sv[W], bs[W] = {}, d1[W] = {}, d2[W] = {}, x0[W], xc[W], o[W];
+        pass_ld(a.x, i, x);
+        pass_ld(src, i, sv);
+        if (state) { pass_ld(a.ubase, i, bs); pass_ld(a.ud1, i, d1); pass_ld(a.ud2, i, d2); }
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            float dt = pass_x0(x[k], sv[k], given, sr, srm1, a.clip, nonfinite);
+            if (!(fabsf(dt) <= 3.4028234e38f)) dt = __builtin_nanf("");
+            x0[k] = dt;
+            // a tensor the order does not reach is not used, whatever it holds (a window's buffers before its first step: any bits)
+            const float e1 = n >= 1 ? d1[k] : 0.f, e2 = n >= 2 ? d2[k] : 0.f;
+            xc[k] = n >= 1 ? fmaf(c3, dt, fmaf(c2, e2, fmaf(c1, e1, c0 * bs[k]))) : x[k];
+            o[k] = fmaf(p2, e1, fmaf(p1, dt, p0 * xc[k]));
+            d1[k] = e1;
+        }
+        if (a.xstart) pass_st(a.xstart, i, x0);
+        if (a.ubase_out) pass_st(a.ubase_out, i, xc);
+        if (a.ud2_out) pass_st(a.ud2_out, i, d1);
+        if (a.ud1_out) pass_st(a.ud1_out, i, x0);
+        pass_st(a.sample, i, o);
+    }
+    if (nonfinite && a.err) atomicOr(a.err, VD_ERR_NONFINITE);
+}
+
+static int launch_unipc(const SamplerPassArgs& a, hipStream_t s) {
+    const std::string k = "unipc_kernel: ";
+    VD_REQUIRE(a.B > 0 && a.per > 0, k + "B and the elements per item must be positive");
+    VD_REQUIRE(a.x && (a.eps || a.x0_given) && a.t && a.tab && a.sample, k + "null tensor");
+    VD_REQUIRE(!a.mean, k + "the pass writes no posterior mean");
+    VD_REQUIRE(a.urows, "unipc_sample: no coefficient rows for the bound schedule (vd_set_unipc_rows, after vd_set_schedule)");
+    VD_REQUIRE((a.ubase != nullptr) == (a.ud1 != nullptr) && (a.ud1 != nullptr) == (a.ud2 != nullptr), k + "the state read is three tensors, or none");
+    VD_REQUIRE((a.ubase_out != nullptr) == (a.ud1_out != nullptr) && (a.ud1_out != nullptr) == (a.ud2_out != nullptr), k + "the state written is three tensors, or none");
+    VD_REQUIRE(a.count >= 0 && (a.ubase || a.count == 0), k + "a step count without a state");
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool v4 = a.per % 4 == 0 && al16(a.x) && al16(a.eps) && al16(a.x0_given) && al16(a.sample) && al16(a.xstart) && al16(a.ubase) && al16(a.ud1) &&
+                    al16(a.ud2) && al16(a.ubase_out) && al16(a.ud1_out) && al16(a.ud2_out);
+    const size_t groups = (size_t)a.B * (v4 ? a.per / 4 : a.per);
+    const int grid = (int)std::min<size_t>((groups + 255) / 256, 4096);
+    if (v4) hipLaunchKernelGGL(unipc_kernel<float4>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(unipc_kernel<float>, dim3(grid), dim3(256), 0, s, a);
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_sampler_pass(const SamplerPassArgs& a, hipStream_t s) {
     VD_REQUIRE(sampler_valid(a.sampler), "sampler pass: sampler");
     if (a.sampler == SAMPLER_DPMPP_2M_SDE) return launch_dpmpp_2m_sde(a, s);
+    if (a.sampler == SAMPLER_UNIPC) return launch_unipc(a, s);
     const bool f4 = !sampler_draws_noise(a.sampler);        // the float4 passes; posterior_kernel takes any per and any alignment
     if (f4) {
         const std::string k = std::string(a.sampler == SAMPLER_DPMPP_2M ? "dpmpp_2m" : "ddim_reverse") + "_kernel: ";

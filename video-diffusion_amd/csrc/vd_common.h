@@ -434,17 +434,18 @@ int launch_head_gemm(const float* h, const float* affA, const float* affB, const
 int launch_out_gather(const float* T, const float* bias, int nfr, int H, int W, int ldt, int Cout, float* out_nchw, hipStream_t s);
 
 // The samplers of the step path.  The values are ABI (vd_window_begin's `sampler`, vd_posterior_update's `mode`).
-enum Sampler { SAMPLER_P = 0, SAMPLER_DDIM = 1, SAMPLER_DDIM_REVERSE = 2, SAMPLER_DPMPP_2M = 3, SAMPLER_DPMPP_2M_SDE = 4 };
-inline bool sampler_valid(int s) { return s >= SAMPLER_P && s <= SAMPLER_DPMPP_2M_SDE; }
+enum Sampler { SAMPLER_P = 0, SAMPLER_DDIM = 1, SAMPLER_DDIM_REVERSE = 2, SAMPLER_DPMPP_2M = 3, SAMPLER_DPMPP_2M_SDE = 4, SAMPLER_UNIPC = 5 };
+inline bool sampler_valid(int s) { return s >= SAMPLER_P && s <= SAMPLER_UNIPC; }
 inline bool sampler_walks_up(int s) { return s == SAMPLER_DDIM_REVERSE; }                   // t += 1 per step; the others walk down to 0
 inline bool sampler_draws_noise(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM || s == SAMPLER_DPMPP_2M_SDE; }   // the others read no noise and no Philox state
-inline bool sampler_has_history(int s) { return s == SAMPLER_DPMPP_2M || s == SAMPLER_DPMPP_2M_SDE; }   // reads the previous step's x_0 prediction
+inline bool sampler_has_history(int s) { return s == SAMPLER_DPMPP_2M || s == SAMPLER_DPMPP_2M_SDE || s == SAMPLER_UNIPC; }   // reads the previous step's x_0 prediction
+inline bool sampler_is_unipc(int s) { return s == SAMPLER_UNIPC; }     // its history is three tensors, its rows vd_set_unipc_rows' (not the multistep weight row)
 // the entries that take a `mode` (vd_posterior_update, vd_posterior_from_xstart, vd_dps_step) serve these two alone: sampler 4 draws
 // noise too but has entries of its own
 inline bool sampler_is_posterior(int s) { return s == SAMPLER_P || s == SAMPLER_DDIM; }
 inline const char* sampler_name(int s) {
     return s == SAMPLER_P ? "p_sample" : s == SAMPLER_DDIM ? "ddim_sample" : s == SAMPLER_DDIM_REVERSE ? "ddim_reverse_sample"
-         : s == SAMPLER_DPMPP_2M ? "dpmpp_2m_sample" : "dpmpp_2m_sde_sample";
+         : s == SAMPLER_DPMPP_2M ? "dpmpp_2m_sample" : s == SAMPLER_DPMPP_2M_SDE ? "dpmpp_2m_sde_sample" : "unipc_sample";
 }
 // The closing pass of a step (misc.hip: launch_sampler_pass), one argument block for every sampler.
 struct SamplerPassArgs {
@@ -456,7 +457,7 @@ struct SamplerPassArgs {
     const float* tab;       // [NTAB][num_timesteps] float32 tables (gathered in f64 on host, cast like the reference)
     int num_timesteps;
     int B; long per;        // samplers that draw no noise: per % 4 == 0, every tensor 16-byte aligned (launch_sampler_pass checks);
-                            // dpmpp_2m_sde: any per and alignment (16-byte accesses where per % 4 == 0 and every tensor is aligned)
+                            // dpmpp_2m_sde, unipc: any per and alignment (16-byte accesses where per % 4 == 0 and every tensor is aligned)
     int clip;
     float* sample;          // x_{t-1} (x_{t+1}: ddim_reverse); may alias x: the update is elementwise.  Null: SAMPLER_P only (p_mean_variance)
     float* xstart;          // the x_0 prediction (dpmpp_2m: D_t, the next step's history), or null
@@ -473,7 +474,16 @@ struct SamplerPassArgs {
                                         // written by the same thread, which is how the window executor keeps its history in place
     const unsigned long long* hist_on = nullptr;    // or null; a device word: 0 = this step has no history whatever `hist` holds (a window's first step)
     const float* w = nullptr;           // [num_timesteps] extrapolation weights (vd_set_multistep_weights); w[0] = w[num_timesteps - 1] = 0
+    // ---- unipc_sample (it also reads hist_on: there the COUNT of finished steps, in place of `count`, when set)
+    const float* urows = nullptr;       // [UNIPC_ROWS][num_timesteps] coefficient rows (vd_set_unipc_rows)
+    const float *ubase = nullptr, *ud1 = nullptr, *ud2 = nullptr;      // the state read: x^c_{t+1}, D_{t+1}, D_{t+2}; all null = no state (count 0)
+    float *ubase_out = nullptr, *ud1_out = nullptr, *ud2_out = nullptr; // the state written: x^c_t, D_t, D_{t+1}; all null = not kept.  Each may
+                                        // alias any tensor read: element i is read and then written by the same thread
+    int count = 0;                      // steps the chain has finished (host); the pass uses min(count, num_timesteps - 1 - t[b])
 };
+// unipc_sample's rows, per respaced index t: the corrector into t (move t+1 -> t) x^c = c0 base + c1 D1 + c2 D2 + c3 D_t at order 1 and
+// order 2, then the predictor t -> t-1, sample = p0 x^c + p1 D_t + p2 D1, at order 1 and order 2
+enum { UNIPC_C1 = 0, UNIPC_C2 = 4, UNIPC_P1 = 8, UNIPC_P2 = 11, UNIPC_ROWS = 14 };
 enum { VD_ERR_TIMESTEP = 1, VD_ERR_NONFINITE = 2 };
 int launch_sampler_pass(const SamplerPassArgs& a, hipStream_t s);
 // cfg_scale (this project's extension: classifier-free guidance on the observed frames): out[i] = fmaf(w, out_c[i] - out_u[i], out_u[i]),

@@ -34,13 +34,15 @@ _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
 def _sampler_id(sampler):
-    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'dpmpp_2m_sde' 4, 'p_sample' 0 and every other string ddim_sample, 1."""
+    """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'dpmpp_2m_sde' 4, 'unipc' 5, 'p_sample' 0 and every other string ddim_sample, 1."""
     if sampler == "ddim_reverse":
         return 2
     if sampler == "dpmpp_2m":
         return 3
     if sampler == "dpmpp_2m_sde":
         return 4
+    if sampler == "unipc":
+        return 5
     return 0 if sampler == "p_sample" else 1
 
 
@@ -97,7 +99,10 @@ class WindowExecutor:
         x_0 prediction lives in an engine-owned buffer, the window's first step is first-order whatever t_start is, no noise --
         seed and eta are not read -- and 'x_t_minus_1' with renoise=False only) or 'dpmpp_2m_sde' (dpmpp_2m_sde_sample, this project's
         extension: the history of 'dpmpp_2m' and the Philox noise of 'ddim' both live in the graph; eta is not read; every
-        observed_frames mode 'ddim' takes, renoise=True included).
+        observed_frames mode 'ddim' takes, renoise=True included) or 'unipc' (unipc_sample, this project's extension: walks down like
+        'dpmpp_2m', its three state tensors live in engine-owned buffers, the window's first step runs no corrector and a first-order
+        predictor whatever t_start is, no noise -- seed and eta are not read -- 'x_t_minus_1' with renoise=False only, and a known
+        region is refused by name).
         cfg_scale (this project's extension; gaussian_diffusion.py: p_sample): the captured step holds both forwards, the combine pass
         and the sampler pass; the weight is part of the graph's signature, so windows under different weights replay different graphs.
         The noise of a window does not depend on it.  Not served together with prefix_cache or suffix_skip: in the unconditional
@@ -135,7 +140,8 @@ class WindowExecutor:
         if known_src is not None:
             if tuple(known_src.shape) != tuple(x_init.shape):
                 raise ValueError(f"known_src {tuple(known_src.shape)} against a window of {tuple(x_init.shape)}")
-            for name, on in (("prefix_cache", self.prefix_cache), ("suffix_skip", self.suffix_skip), ("sampler='ddim_reverse'", sampler == "ddim_reverse")):
+            for name, on in (("prefix_cache", self.prefix_cache), ("suffix_skip", self.suffix_skip), ("sampler='ddim_reverse'", sampler == "ddim_reverse"),
+                             ("sampler='unipc'", sampler == "unipc")):
                 if on:
                     raise NotImplementedError(f"{name} together with a known region")
         from .gaussian_diffusion import _engine_measurement, _measurement, check_measurement

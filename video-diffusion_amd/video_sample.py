@@ -72,7 +72,10 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     timestep_respacing='logsnrN') or 'dpmpp_2m_sde' (dpmpp_2m_sde_sample, this project's extension: the stochastic second-order
     multistep solver; history per window like 'dpmpp_2m'; `eta` is not read; its noise is the engine's Philox stream on BOTH executors,
     from a seed drawn per window from torch's global generator, so the two executors agree to the bit; refused by name with
-    use_gradient_method and dps_zeta; meant for timestep_respacing='logsnrN').
+    use_gradient_method and dps_zeta; meant for timestep_respacing='logsnrN') or 'unipc' (unipc_sample, this project's extension: UniPC,
+    dpmpp_2m's predictor plus a corrector that reuses the step's own forward -- third order at no further network call; state per window,
+    the first step of each first-order; no noise, both executors agree to the bit; refused by name with use_gradient_method, dps_zeta and
+    known_mask; meant for timestep_respacing='logsnrN' with N of 20 or more).
 
     cfg_scale (this project's extension, both executors, every sampler): the weight w of classifier-free guidance on each window's
     observed frames -- every step runs on out_u + w (out_c - out_u), out_u being the network output with the window's obs_mask
@@ -118,12 +121,18 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             raise ValueError("dps_zeta needs a measurement (measurement=, sr_scale=, gray=)")
         for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
                          ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("sampler='dpmpp_2m_sde'", sampler == "dpmpp_2m_sde"),
+                         ("sampler='unipc'", sampler == "unipc"),
                          ("cfg_scale != 1", float(cfg_scale) != 1.0),
                          ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
             if on:
                 raise _lib.VdError(f"{name} together with dps_zeta is not served")
     if sampler == "dpmpp_2m_sde" and use_gradient_method:
         raise NotImplementedError("sampler='dpmpp_2m_sde' together with use_gradient_method")
+    if sampler == "unipc" and use_gradient_method:
+        raise NotImplementedError("sampler='unipc' together with use_gradient_method")
+    if sampler == "unipc" and known_mask is not None:
+        raise NotImplementedError("sampler='unipc' together with known_mask: the corrector rebuilds the state from its own, the merge of a "
+                                  "known region behind the pass would be discarded")
     if measurement is not None:
         from . import _lib
         from .gaussian_diffusion import check_measurement
@@ -235,6 +244,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
         prev_xstart = None                                  # dpmpp_2m, dpmpp_2m_sde: the history is the window's own
+        unipc_state = None                                  # ... and so is unipc's state
         if sampler == "dpmpp_2m_sde":                       # ... and the noise what the window executor would draw (its seed, its ranges)
             sde_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if y_w is None:
@@ -257,6 +267,11 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                         out = diffusion._dpmpp_2m_sde(model, local_samples, t_tensors[timestep], prev_xstart, True, None, model_kwargs,
                                                       philox=(sde_seed, k * local_samples.numel()))
                     local_samples, prev_xstart = out["sample"], out["pred_xstart"]
+                elif sampler == "unipc":
+                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
+                        out = diffusion.unipc_sample(model, local_samples, t_tensors[timestep], state=unipc_state, clip_denoised=True,
+                                                     model_kwargs=model_kwargs)
+                    local_samples, unipc_state = out["sample"], out["state"]
                 elif sampler == "p_sample":
                     local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
                                                        model_kwargs=model_kwargs, return_attn_weights=False,
@@ -539,9 +554,10 @@ def load_lpips_for(args, device):
 
 def build_parser():
     ap = add_job_arguments(argparse.ArgumentParser())
-    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde"],
-                    help="the step: p_sample (default), ddim (ddim_sample with --eta), dpmpp_2m (the second-order multistep solver) or dpmpp_2m_sde "
-                         "(its stochastic form; both meant for --timestep_respacing logsnrN); a non-default sampler is named in the run directory")
+    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde", "unipc"],
+                    help="the step: p_sample (default), ddim (ddim_sample with --eta), dpmpp_2m (the second-order multistep solver), dpmpp_2m_sde "
+                         "(its stochastic form) or unipc (dpmpp_2m's predictor plus a corrector on the same forward: third order; all three "
+                         "meant for --timestep_respacing logsnrN, unipc for N of 20 or more); a non-default sampler is named in the run directory")
     ap.add_argument("--eta", type=float, default=0.0, help="with --sampler ddim: ddim_sample's eta")
     ap.add_argument("--cfg_scale", type=float, default=1.0,
                     help="classifier-free guidance weight on the observed frames: every step runs on out_u + w (out_c - out_u), out_u being the "
