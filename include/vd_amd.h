@@ -817,6 +817,16 @@ int vd_op_gn_temporal(const float* x, const float* gamma, const float* beta, int
 int vd_op_attn_spatial(const float* qkv, int nfr, int L, int C, int heads, float* out, void* stream);
 int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, const float* Rv, const float* mask, int B,
                         int T, int HW, int C, int heads, int allow_pad, float* out, void* stream);
+/* The return_attn_weights maps (unet.py:457-466: attn.view(B*D, -1, T, T).mean(dim=1).abs()) alone, through the launchers the forward
+ * calls under vd_set_attn_capture, with the operands, layouts and scale of the two entries above.
+ * Temporal: out [B*HW][T][T] = | mean over heads of softmax_s(q'_t . (k_s + Rk[t,s]) + scale k_s . Rq[s,t]) |, masked by the rule of
+ * unet.py:511-524 (a masked entry is exactly 0); Rk and Rq both or neither; mask may be NULL; T <= 128, one kernel for T <= 32 and one
+ * that cuts the query rows into chunks of 32 above; refused ("head dim too large") where a block's rows exceed 150 KiB of LDS.
+ * Spatial: out [nfr][L][L], no relative positions, no mask; head dim a multiple of 4 ("shape"), refused ("sequence too long") where 16
+ * score rows and their mean exceed 150 KiB of LDS (L above about 1100). */
+int vd_op_attn_temporal_weights(const float* qkv, const float* Rk, const float* Rq, const float* mask, int B, int T, int HW, int C,
+                                int heads, int allow_pad, float* out, void* stream);
+int vd_op_attn_spatial_weights(const float* qkv, int nfr, int L, int C, int heads, float* out, void* stream);
 /* Which kernel instantiation vd_op_attn_temporal (and the engine) runs a per-item shape on, as its C++ name --
  * "attn_temporal_mfma_kernel<NT,JM,RPE,EXACT>", "attn_temporal_kernel<PB,TMAX,RPE>" (T <= 32),
  * "attn_temporal_long_mfma_kernel<NJ,RPE>", "attn_temporal_long_kernel<RPE>" (T = 33..128) -- or "refused: <reason>".
@@ -861,8 +871,25 @@ int vd_op_linear_split_side(const float* a0, const float* a1, int C0, int K, int
                             const float* sideA, const float* sideB, float* out, float* side, int N, void* stream);
 int vd_op_linear_batched(const float* a, int zcount, int M, int K, int N, const float* zbase, const long long* ztab_dev, float* out,
                          void* stream);
+/* The output head out = conv3x3(SiLU(h * A[frame] + B[frame])) + bias (unet.py:744-749,838) in its direct form (out_conv_kernel):
+ * h [nfr][H][W][C], w_packed [tap][Cout][C], out NCHW; Cout <= 8, C % 32 == 0.  This kernel is the op-only form and is NOT on the
+ * forward, which runs the head as vd_op_out_head does. */
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w_packed, const float* bias,
                    int nfr, int H, int W, int C, int Cout, float* out_nchw, void* stream);
+/* The same head (unet.py:744-749,838) through the code the forward runs: T[pixel][co * 9 + tap] = SiLU(h * A + B) . w[co][:][tap] as a
+ * 1x1 GEMM over 32 (Cout 3) or 64 (Cout 6) columns -- head_gemm_kernel where H * W % 1024 == 0, C % 8 == 0 and C <= 128 at 32
+ * columns, in its 2- or 8-tiles-per-wave form by the pixel count; the generic fp32 kernel with the affine and SiLU in its operand
+ * load otherwise (C % 32 == 0) -- then out[n][co][y][x] = bias[co] + sum over the 9 taps of T at the neighbour the tap points to,
+ * zero outside the image (out_gather_kernel).  h [nfr][H][W][C], affA / affB [nfr][C], bias [Cout] and out_nchw [nfr][Cout][H][W] on
+ * the device; w_oihw is the checkpoint's out.2.weight [Cout][C][3][3] in host or device memory, packed here by the function
+ * vd_load_weight packs it with.  Cout is 3 or 6.  The scratch T is allocated for the call, which synchronises the stream before it
+ * returns.  A refused shape returns -1 with the reason in vd_last_error() before any launch. */
+int vd_op_out_head(const float* h, const float* affA, const float* affB, const float* w_oihw, const float* bias, int nfr, int H, int W,
+                   int C, int Cout, float* out_nchw, void* stream);
+/* Which GEMM vd_op_out_head (and the forward) runs a head shape on: "head_gemm/tpw2", "head_gemm/tpw8", "igemm/32", "igemm/64" (the
+ * generic kernel at 32 | 64 columns), or "refused: <reason>".  Returns 1, 0 (refused) or a negative code (no room in name[cap]).
+ * Host only: no launch, no device call; read off the function that launches. */
+int vd_out_head_variant(int nfr, int H, int W, int C, int Cout, char* name, int cap);
 /* Backward-data operators of use_gradient_method (csrc/backward.hip); each one synchronises its stream before it returns. */
 /* GroupNorm32(+FiLM)(+SiLU) backward over a virtual concat; mr [nfr][32][2] (mean, rstd); dx0 / dx1 assigned or accumulated (acc0 / acc1), plus extra if given. */
 int vd_op_gn_bwd(const float* x0, const float* x1, int C0, int C, const float* affA, const float* affB, const float* mr,

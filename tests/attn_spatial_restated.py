@@ -12,12 +12,17 @@ head's v_j, so no feature of it exceeds S = max over the keys and the head's fea
 import torch
 
 
-def attn_ref(qkv, N, L, C, heads, dtype=torch.float64):
-    """softmax(q F^-0.5 k^T) v per (frame, head), evaluated in `dtype`: out [N][L][C]."""
+def attn_weights(qkv, N, L, C, heads, dtype=torch.float64):
+    """(a, v): softmax(q F^-0.5 k^T) [N][heads][L][L] and the values [N][heads][L][F], evaluated in `dtype`."""
     Fd = C // heads
     x = qkv.to(dtype).reshape(N, L, 3, heads, Fd).permute(2, 0, 3, 1, 4)              # t N H L F
     q, k, v = x[0] * Fd ** -0.5, x[1], x[2]
-    a = torch.softmax(q @ k.transpose(-1, -2), -1)
+    return torch.softmax(q @ k.transpose(-1, -2), -1), v
+
+
+def attn_ref(qkv, N, L, C, heads, dtype=torch.float64):
+    """softmax(q F^-0.5 k^T) v per (frame, head), evaluated in `dtype`: out [N][L][C]."""
+    a, v = attn_weights(qkv, N, L, C, heads, dtype)
     return (a @ v).permute(0, 2, 1, 3).reshape(N, L, C)
 
 

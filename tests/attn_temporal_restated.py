@@ -32,23 +32,29 @@ def allowed_pairs(m, allow, B, T):
     return ok != 0
 
 
-def attn_ref(qkv, Rk, Rq, Rv, m, allow, B, T, HW, C, heads, dtype=torch.float64):
-    """unet.py:486-536 + the RPE einsums :357-378 + the mask rule :511-524, evaluated in `dtype`."""
+def attn_weights(qkv, Rk, Rq, m, allow, B, T, HW, C, heads, dtype=torch.float64, pairs=allowed_pairs):
+    """(a, v): the softmax weights a [B][HW][heads][T][T] of unet.py:486-525 (RPE terms :357-366, :502-509; mask rule :511-524 as
+    `pairs` states it) and the values v [B][HW][heads][T][F], evaluated in `dtype`."""
     Fd = C // heads
     scale = Fd ** -0.5
     x = qkv.to(dtype).permute(0, 2, 1, 3).reshape(B, HW, T, 3, heads, Fd).permute(3, 0, 1, 4, 2, 5)     # t B D H T F
     q, k, v = x[0] * scale, x[1], x[2]
     w = q @ k.transpose(-1, -2)
     if Rk is not None:
-        rk, rq, rv = (r.to(dtype).view(B, T, T, heads, Fd) for r in (Rk, Rq, Rv))
+        rk, rq = (r.to(dtype).view(B, T, T, heads, Fd) for r in (Rk, Rq))
         w = w + torch.einsum("bdhtf,btshf->bdhts", q, rk)
         w = w + torch.einsum("bdhtf,btshf->bdhts", k * scale, rq).transpose(-1, -2)
     if m is not None:
-        w = w.masked_fill(~allowed_pairs(m, allow, B, T).view(B, 1, 1, T, T), float("-inf"))
-    a = torch.softmax(w, -1)
+        w = w.masked_fill(~pairs(m, allow, B, T).view(B, 1, 1, T, T), float("-inf"))
+    return torch.softmax(w, -1), v
+
+
+def attn_ref(qkv, Rk, Rq, Rv, m, allow, B, T, HW, C, heads, dtype=torch.float64):
+    """unet.py:486-536 + the RPE einsums :357-378 + the mask rule :511-524, evaluated in `dtype`."""
+    a, v = attn_weights(qkv, Rk, Rq, m, allow, B, T, HW, C, heads, dtype)
     o = a @ v
     if Rk is not None:
-        o = o + torch.einsum("bdhts,btshf->bdhtf", a, rv)
+        o = o + torch.einsum("bdhts,btshf->bdhtf", a, Rv.to(dtype).view(B, T, T, heads, C // heads))
     return o.permute(0, 3, 1, 2, 4).reshape(B, T, HW, C)
 
 

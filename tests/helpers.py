@@ -38,6 +38,32 @@ def synth_sd(specs):
     return {n: torch.from_numpy(vda.weights_init.synth_param(n, s)) for n, s in specs}
 
 
+class Guarded:
+    """An output tensor on the GPU prefilled with NaN between two pads of a sentinel: read() returns it on the CPU after checking that
+    the pads are intact and that every element was overwritten with a finite value."""
+    PAD, SENTINEL = 4096, -7.25e30
+
+    def __init__(self, *shape):
+        n = int(np.prod(shape))
+        self.buf = torch.full((n + 2 * self.PAD,), self.SENTINEL, dtype=torch.float32, device="cuda")
+        self.t = self.buf[self.PAD:self.PAD + n].view(*shape)
+        self.t.fill_(float("nan"))
+        self.n = n
+
+    def pads_intact(self):
+        torch.cuda.synchronize()
+        return bool((self.buf[:self.PAD] == self.SENTINEL).all()) and bool((self.buf[self.PAD + self.n:] == self.SENTINEL).all())
+
+    def untouched(self):
+        return self.pads_intact() and bool(torch.isnan(self.t).all())
+
+    def read(self):
+        assert self.pads_intact(), "a pad was written"
+        out = self.t.cpu()
+        assert bool(torch.isfinite(out).all()), "an element was not written (or is not finite)"
+        return out
+
+
 def close(a, b, atol=ATOL, rtol=RTOL):
     a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     b = b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b)

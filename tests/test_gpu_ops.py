@@ -437,7 +437,8 @@ def test_attention_temporal(B, T, HW, C, heads, rpe, mask, allow):
 
 @pytest.mark.parametrize("N,H,C", [(2, 32, 32), (3, 16, 128), (1, 20, 64), (2, 4, 32)])
 def test_output_head(N, H, C):
-    """out = conv3x3(silu(GN(h))) to 3 channels, written NCHW (unet.py:744-749,838)."""
+    """out = conv3x3(silu(GN(h))) to 3 channels, written NCHW (unet.py:744-749,838).
+    out_conv_kernel, the op-only direct form: not on the forward, whose head tests/test_gpu_out_head.py covers."""
     x = rnd(N, C, H, H)
     A, B = rnd(N, C, seed=1) + 1.2, rnd(N, C, seed=2)
     w, b = rnd(3, C, 3, 3, scale=0.1), rnd(3, scale=0.1)

@@ -272,6 +272,10 @@ SIGNATURES = {
     "vd_op_linear_split_side": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "vd_op_linear_batched": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "vd_op_out_conv": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_out_head": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_out_head_variant": (_I, [_I, _I, _I, _I, _I, ctypes.c_char_p, _I]),
+    "vd_op_attn_temporal_weights": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_attn_spatial_weights": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "vd_op_gn_bwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "vd_op_gn_temporal_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_attn_temporal_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -827,6 +827,44 @@ static IgemmArgs conv_args(Tens x0, const Tens* x1, int N, int ksz, int stride, 
     return g;
 }
 
+// The GEMM half of the PK_OUTCONV image: OIHW -> [out_t_cols(O)][I], rows co * 9 + tap, the rows past 9 O zero (vd_load_weight, vd_op_out_head)
+static void pack_out_head(const float* oihw, int O, int I, float* wt) {
+    std::fill(wt, wt + (size_t)out_t_cols(O) * I, 0.f);
+    for (int o = 0; o < O; ++o)
+        for (int i = 0; i < I; ++i)
+            for (int t = 0; t < 9; ++t) wt[((size_t)o * 9 + t) * I + i] = oihw[((size_t)o * I + i) * 9 + t];
+}
+
+// out = conv3x3(silu(gn(h))) with 3 | 6 outputs (unet.py:744-749,838): T[pixel][cout * 9 + tap] = silu(A h + B) . w[cout][:][tap] as ONE
+// 1x1 GEMM over the 27 | 54 (cout, tap) columns (head_gemm_kernel, or the generic kernel for shapes it does not take: GroupNorm
+// affine + SiLU in the operand load), then
+// eps[cout][y][x] = bias + sum over the 9 taps of T at the neighbour the tap points to (out_gather_kernel).
+// h [nfr][H][W][C], (A, B) [nfr][C], Wt by pack_out_head, T [nfr][H][W][out_t_cols(Cout)] scratch, out [nfr][Cout][H][W].  The forward
+// and vd_op_out_head launch through here; with `path` set nothing is launched and the path is named instead (vd_out_head_variant:
+// the pointers are then only looked at for presence).  One switch serves both.
+static int out_head(const float* h, const float* A, const float* Bf, const float* Wt, const float* bias, int nfr, int H, int W, int C, int Cout,
+                    float* T, float* out, hipStream_t st, std::string* path = nullptr) {
+    const int ldt = out_t_cols(Cout);
+    int rc = 0;
+    if (head_gemm_supported(H * W, C, ldt)) {
+        if (path) { *path = "head_gemm/tpw" + std::to_string(head_gemm_tiles_per_wave(nfr, H * W)); return 0; }
+        rc = launch_head_gemm(h, A, Bf, Wt, nfr, H * W, C, ldt, T, st);
+    } else {
+        IgemmArgs g = conv_args(h, nullptr, C, C, nfr, H, W, 0, 1, 0, 1);
+        g.nfr_sel = g_sel_nfr;
+        g.w = Wt; g.wsplit = 0; g.affA = A; g.affB = Bf; g.act = 1;
+        g.out = T; g.ldo = ldt; g.Cout = ldt;
+        if (path) {
+            const IgemmVariant v = igemm_variant(g);
+            *path = v.name ? "igemm/" + std::to_string(ldt) : igemm_variant_name(v);
+            return 0;
+        }
+        rc = launch_igemm(g, st);
+    }
+    if (!rc) rc = launch_out_gather(T, bias, nfr, H, W, ldt, Cout, out, st);
+    return rc;
+}
+
 int vd_engine::res_block(const ResP& r, Tens x0, const Tens* x1, int N, const float* film_all, hipStream_t st, Arena& ar, Tens* out) {
     const int H = x0.H, HW = H * H;
     const int cin = x0.C + (x1 ? x1->C : 0);
@@ -1271,20 +1309,9 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
     float* head_t = ar.get<float>((size_t)Nrun * S * S * out_t_cols(oc));
     if (!ar.dry) {
         VD_REQUIRE(h.H == S && h.C == final_ch, "output head shape");
-        { // out = conv3x3(silu(gn(h))) with 3 | 6 outputs (unet.py:744-749,838): T[pixel][cout * 9 + tap] = silu(A h + B) . w[cout][:][tap] as ONE
-          // 1x1 GEMM over the 27 | 54 (cout, tap) columns (head_gemm_kernel, or the generic kernel for shapes it does not take: GroupNorm
-          // affine + SiLU in the operand load), then
-          // eps[cout][y][x] = bias + sum over the 9 taps of T at the neighbour the tap points to (out_gather_kernel)
+        { // out = conv3x3(silu(gn(h))) with 3 | 6 outputs (unet.py:744-749,838): out_head()
           ProfScope ps(PC_OUT_CONV, 2.0 * Nrun * S * S * h.C * 27.0, 4.0 * Nrun * S * S * (h.C + 3.0), st);
-          if (head_gemm_supported(S * S, h.C, out_t_cols(oc))) {
-              rc = launch_head_gemm(h.p, A, Bf, W(p_outw) + (size_t)9 * oc * h.C, Nrun, S * S, h.C, out_t_cols(oc), head_t, st);
-          } else {
-              IgemmArgs g = conv_args(h, nullptr, Nrun, 1, 1, 0);
-              g.w = W(p_outw) + (size_t)9 * oc * h.C; g.wsplit = 0; g.affA = A; g.affB = Bf; g.act = 1;
-              g.out = head_t; g.ldo = out_t_cols(oc); g.Cout = out_t_cols(oc);
-              rc = launch_igemm(g, st);
-          }
-          if (!rc) rc = launch_out_gather(head_t, W(p_outb), Nrun, S, S, out_t_cols(oc), oc, compact ? eps_c : in.eps, st); }
+          rc = out_head(h.p, A, Bf, W(p_outw) + (size_t)9 * oc * h.C, W(p_outb), Nrun, S, S, h.C, oc, head_t, compact ? eps_c : in.eps, st); }
         if (rc) return rc;
         if (compact) {                                               // the other frames' eps: zeros (their samples stay finite; nobody reads them)
             VD_HIP(hipMemsetAsync(in.eps, 0, (size_t)N * oc * S * S * sizeof(float), st));
@@ -1700,10 +1727,7 @@ int vd_load_weight(vd_engine* e, const char* name, const float* host, long long 
         for (int o = 0; o < O; ++o)
             for (int i = 0; i < I; ++i)
                 for (int t = 0; t < 9; ++t) tmp[((size_t)t * O + o) * I + i] = host[((size_t)o * I + i) * 9 + t];
-        if (p.kind == PK_OUTCONV)
-            for (int o = 0; o < O; ++o)
-                for (int i = 0; i < I; ++i)
-                    for (int t = 0; t < 9; ++t) tmp[(size_t)9 * O * I + ((size_t)o * 9 + t) * I + i] = host[((size_t)o * I + i) * 9 + t];
+        if (p.kind == PK_OUTCONV) pack_out_head(host, O, I, tmp.data() + (size_t)9 * O * I);
         src = tmp.data();
     } else if (p.kind == PK_POSENC) {
         const int C = (int)p.shape[1], HW = (int)(p.shape[2] * p.shape[3]);
@@ -3423,6 +3447,22 @@ int vd_op_attn_temporal(const float* qkv, const float* Rk, const float* Rq, cons
     return launch_attn_temporal(a, static_cast<hipStream_t>(stream));
 }
 
+// ---- the return_attn_weights maps (backward.hip) on caller's tensors: the launchers the forward calls under vd_set_attn_capture,
+// args filled as by the two entries above
+int vd_op_attn_temporal_weights(const float* qkv, const float* Rk, const float* Rq, const float* mask, int B, int T, int HW, int C,
+                                int heads, int allow_pad, float* out, void* stream) {
+    VD_REQUIRE(qkv && out && B > 0 && HW > 0 && C > 0 && heads > 0 && (Rk != nullptr) == (Rq != nullptr),
+               "vd_op_attn_temporal_weights: tensors, a positive shape, Rk and Rq both or neither");
+    AttnTemporalArgs a{qkv, Rk, Rq, nullptr, mask, nullptr, B, T, HW, C, heads, allow_pad, 1.0f / sqrtf((float)(C / heads))};
+    return launch_attn_temporal_weights(a, out, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_attn_spatial_weights(const float* qkv, int nfr, int L, int C, int heads, float* out, void* stream) {
+    VD_REQUIRE(qkv && out && nfr > 0 && L > 0 && C > 0 && heads > 0, "vd_op_attn_spatial_weights: tensors and a positive shape");
+    AttnSpatialArgs a{qkv, nullptr, nfr, L, C, heads, 1.0f / sqrtf((float)(C / heads))};
+    return launch_attn_spatial_weights(a, out, static_cast<hipStream_t>(stream));
+}
+
 int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* name, int cap) {
     VD_REQUIRE(name && cap > 0, "vd_attn_temporal_variant: a name buffer");
     const AttnTemporalVariant v = attn_temporal_variant(T, HW, C, heads, rpe != 0);
@@ -3444,6 +3484,42 @@ int vd_attn_spatial_variant(int L, int C, int heads, char* name, int cap) {
 int vd_op_out_conv(const float* x, const float* affA, const float* affB, const float* w, const float* bias, int nfr,
                    int H, int W, int C, int Cout, float* out, void* stream) {
     return launch_out_conv(x, affA, affB, w, bias, nfr, H, W, C, Cout, out, static_cast<hipStream_t>(stream));
+}
+
+// ---- the output head as the forward runs it (out_head(): GEMM over (cout, tap) columns + 9-tap gather), on caller's tensors
+static const char* out_head_refusal(int nfr, int H, int W, int C, int Cout) {
+    if (!(nfr > 0 && H > 0 && W > 0 && C > 0)) return "output head: positive nfr, H, W and C";
+    if (!(Cout == 3 || Cout == 6)) return "output head: 3 or 6 output channels";
+    if ((size_t)nfr * H * W >= ((size_t)1 << 31)) return "output head: 2^31 pixels or more";
+    return nullptr;
+}
+
+int vd_out_head_variant(int nfr, int H, int W, int C, int Cout, char* name, int cap) {
+    VD_REQUIRE(name && cap > 0, "vd_out_head_variant: a name buffer");
+    std::string path;
+    if (const char* why = out_head_refusal(nfr, H, W, C, Cout)) path = std::string("refused: ") + why;
+    else {
+        float* any = reinterpret_cast<float*>(0x1000);              // presence only: nothing is read
+        if (int rc = out_head(any, any, any, any, any, nfr, H, W, C, Cout, any, any, nullptr, &path)) return rc;
+    }
+    if (int rc = copy_name(path, name, cap, "vd_out_head_variant")) return rc;
+    return path.compare(0, 8, "refused:") != 0 ? 1 : 0;
+}
+
+int vd_op_out_head(const float* h, const float* affA, const float* affB, const float* w_oihw, const float* bias, int nfr, int H, int W,
+                   int C, int Cout, float* out_nchw, void* stream) {
+    VD_REQUIRE(h && affA && affB && w_oihw && bias && out_nchw, "vd_op_out_head: null argument");
+    if (const char* why = out_head_refusal(nfr, H, W, C, Cout)) { set_error(std::string("requirement failed: ") + why); return -1; }
+    std::vector<float> oihw((size_t)Cout * C * 9), wt((size_t)out_t_cols(Cout) * C);
+    VD_HIP(hipMemcpy(oihw.data(), w_oihw, oihw.size() * sizeof(float), hipMemcpyDefault));      // (host or device memory)
+    pack_out_head(oihw.data(), Cout, C, wt.data());
+    OpScratch ws(stream);
+    float *Wt = nullptr, *T = nullptr;
+    int rc = ws.get(&Wt, wt.size());
+    if (!rc) rc = ws.get(&T, (size_t)nfr * H * W * out_t_cols(Cout));
+    if (rc) return rc;
+    VD_HIP(hipMemcpy(Wt, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
+    return out_head(h, affA, affB, Wt, bias, nfr, H, W, C, Cout, T, out_nchw, ws.st);
 }
 
 // ---- backward-data operators of use_gradient_method (backward.hip)

@@ -398,10 +398,13 @@ __global__ __launch_bounds__(256, 2) void head_gemm_kernel(const float* __restri
 // (32 columns: the 3-channel head; the 6-channel head of a learn_sigma network needs twice the weight registers and stays on the generic kernel)
 bool head_gemm_supported(int HW, int C, int ldt) { return HW % 1024 == 0 && C % 8 == 0 && C <= 128 && ldt == 32; }
 
+// tiles of 32 pixels per wave: a small window (one rank's share of a strong-scaling split: 16 frames = 64 blocks of 1024 pixels) takes
+// 256-pixel blocks: head 58 -> 29 us there
+int head_gemm_tiles_per_wave(int nfr, int HW) { return (size_t)nfr * HW / 1024 < 512 ? 2 : 8; }
+
 int launch_head_gemm(const float* h, const float* affA, const float* affB, const float* Wt, int nfr, int HW, int C, int ldt, float* T, hipStream_t s) {
     VD_REQUIRE(head_gemm_supported(HW, C, ldt), "output head GEMM: whole 1024-pixel blocks of a frame, C <= 128, 32 columns");
-    // a small window (one rank's share of a strong-scaling split: 16 frames = 64 blocks of 1024 pixels) takes 256-pixel blocks: head 58 -> 29 us there
-    const int tpw = (size_t)nfr * HW / 1024 < 512 ? 2 : 8;
+    const int tpw = head_gemm_tiles_per_wave(nfr, HW);
     const dim3 grid((unsigned)((size_t)nfr * HW / (128 * tpw)));
     hipLaunchKernelGGL((head_gemm_kernel<1, 128>), grid, dim3(256), 0, s, h, affA, affB, Wt, HW, C, tpw, T);
     VD_HIP(hipGetLastError());

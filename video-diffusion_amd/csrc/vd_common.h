@@ -423,12 +423,14 @@ int launch_posenc_add(const float* x, const float* P, const float* femb, int nfr
                       hipStream_t s);
 // tv[b*T+t] = fidx - (center ? mean_t fidx : 0)   (unet.py:914-926)
 int launch_frame_t(const int64_t* fidx, int B, int T, int center, float* tv, hipStream_t s);
-// out conv: GN-affine + SiLU + conv3x3 (C -> Cout<=8), NHWC in, NCHW out  (unet.py:744-749,838)
+// out conv: GN-affine + SiLU + conv3x3 (C -> Cout<=8), NHWC in, NCHW out  (unet.py:744-749,838).  The direct form, launched by
+// vd_op_out_conv alone: the forward runs the head as the GEMM + gather below
 int launch_out_conv(const float* x, const float* affA, const float* affB, const float* w, const float* bias, int nfr,
                     int H, int W, int C, int Cout, float* out_nchw, hipStream_t s);
 
 // the head's first half as its own kernel: T[pixel][ldt] = silu(h * A + B) . Wt^T, Wt [ldt][C] fp32 (misc.hip)
 bool head_gemm_supported(int HW, int C, int ldt);
+int head_gemm_tiles_per_wave(int nfr, int HW);                           // the launch form of head_gemm_kernel: 2 | 8
 int launch_head_gemm(const float* h, const float* affA, const float* affB, const float* Wt, int nfr, int HW, int C, int ldt, float* T, hipStream_t s);
 // the head's second half: out_nchw[n][co][y][x] = bias[co] + sum_tap T[n][y + dy][x + dx][co * 9 + tap] (zero outside the image); T [nfr][H][W][ldt]
 int launch_out_gather(const float* T, const float* bias, int nfr, int H, int W, int ldt, int Cout, float* out_nchw, hipStream_t s);
