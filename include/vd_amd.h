@@ -629,6 +629,50 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, c
                    const float* y, const float* latent_mask, int scale, int gray, float* d_eps, float* d_x, float* rho,
                    float* pred_xstart, void* stream);
 
+/* Loss-guided sampling -- this project's extension: a reverse step moved down the gradient, with respect to x_t, of ANY differentiable
+ * function of the step's x_0 prediction.  The function is the caller's own code: vd_dps_step is split in two around the point where the
+ * cotangent of x_0 is formed, and the taped forward survives between the two calls.  Per item b, with L_b its frames with
+ * latent_mask == 1, for an epsilon model at t (a, b as above):
+ *   vd_guide_begin   steps 1, 2 and 6 of vd_dps_step: the taped forward, and the plain sampler pass (sampler 0 p_sample, 1 ddim_sample with
+ *                    eta) -> sample' and pred_xstart, the bits of vd_p_sample / vd_ddim_sample with the same noise.  The tape is kept: the
+ *                    engine holds the pass and *ticket (never 0) names it.
+ *   (the caller)     cot = d loss / d pred_xstart, [B][T][3][H][W], by any means, on the device; what it holds off L_b is not read.
+ *   vd_guide_finish  c_r = cot [-1 <= x_0r <= 1] with clip_denoised, else cot (x_0r = a x_t - b eps: the sampler pass's bits);
+ *                    d eps = (-b) c_r, d_x = a c_r on L_b, 0 elsewhere: one fp32 rounding each;
+ *                    g = d_x + (d eps / d x_t)^T d eps: the backward-data pass on a power-of-two multiple of d eps;
+ *                    normalize: n_b = fp32(sqrt(sum over L_b of g^2)), the sum in fp64 in a fixed order that does not depend on B, no
+ *                    floating-point atomics; m_b = n_b == 0 ? 0 : fp32(scale[b] / n_b); else m_b = scale[b];
+ *                    sample = fmaf(-m_b, g, sample) on the frames of L_b, in place; every other frame keeps its bits.
+ * `sample` of vd_guide_finish is the tensor vd_guide_begin wrote (or a copy of it); grad (g on every frame: 0 on observed frames) may be
+ * NULL; grad_norm ([B], n_b) is written only with normalize and may be NULL; scale is [B] floats on the device, each finite and not
+ * negative (the caller checks: the host does not read them).  A cot element that is not finite propagates into grad and sample and raises
+ * no error bit: it is the caller's value.  A scale of 0 leaves sample' as it is.  A step costs one taped forward and one backward pass.
+ * LIFETIME: x, obs_src, the masks, frame_indices and t of vd_guide_begin are read again by vd_guide_finish and must stay alive and
+ * unchanged until it returns.  Both calls issue plain launches on `stream`, no host wait; the caller's code between them must be ordered
+ * on that stream.
+ * THE HELD PASS is never read stale.  One pass is held at most; it points into the workspace, so every entry that runs the network
+ * (forward or backward), sizes the workspace or replays a window graph (vd_window_run) drops it before doing anything else, as do
+ * vd_set_schedule and vd_set_bwd_weight_storage; a second vd_guide_begin drops the first pass and hands out a new ticket.
+ * vd_guide_finish with a ticket that is not the live one fails with "loss_guidance: no taped pass is held for this ticket" and the cause
+ * (never begun, already finished, or dropped by an engine call in between), launches nothing and leaves `sample` untouched.  Otherwise
+ * the held pass is released when vd_guide_finish returns, whatever it returns.  vd_guide_abort drops a held pass (none: no effect);
+ * vd_destroy calls it.  With no pass held no other entry changes what it launches.
+ * vd_guide_begin fails by name ("loss_guidance") where vd_dps_step fails ("dps"): T above 32, a model that is not epsilon-prediction, a
+ * missing backward image, a sampler other than 0 or 1, cfg_scale != 1, guidance rescale, dynamic threshold, a known region, a
+ * measurement, an armed attention capture.  Not part of vd_window_begin / vd_window_run: a caller's code cannot be captured.
+ * vd_op_guide_seed: the seed pass alone on a caller's (x_t, eps, cot) on frames of H x W (any size), no network, no workspace: d_eps, d_x.
+ * A t[b] outside the schedule writes NaN on item b and raises bit 0 of the error word.  16-byte accesses while W % 4 == 0 and the tensors
+ * are 16-byte aligned, else element by element: same bits. */
+int vd_guide_begin(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                   const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, int clip_denoised,
+                   int sampler, float eta, const float* noise, float* sample, float* pred_xstart, unsigned long long* ticket,
+                   void* stream);
+int vd_guide_finish(vd_engine* e, unsigned long long ticket, const float* cot, const float* scale, int normalize, float* sample,
+                    float* grad, float* grad_norm, void* stream);
+int vd_guide_abort(vd_engine* e);
+int vd_op_guide_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, const float* eps, const long long* t, int clip_denoised,
+                     const float* cot, const float* latent_mask, float* d_eps, float* d_x, void* stream);
+
 /* The vector-Jacobian product of the network, and on it the exact log-likelihood of the probability-flow ODE -- this project's extension
  * (Song, Sohl-Dickstein, Kingma, Kumar, Ermon, Poole, ICLR 2021; trace estimate: Skilling-Hutchinson; the reference has the variational
  * bound only, vd_vb_terms).  Both run the taped forward and the backward-data pass of use_gradient_method (second packed image:

@@ -10,6 +10,7 @@
 //   UNetVideoModel.forward :898-912 -> UNetModel.forward :768-839 ; p_sample gaussian_diffusion.py:403-448.
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <unordered_map>
 #include <vector>
 
@@ -299,6 +300,23 @@ struct vd_engine {
     // ---- use_gradient_method: second packed image (backward-data weights) + the tape of the guided step's forward
     float* wbuf_bwd = nullptr; bool wbuf_bwd_on_host = false; size_t packed_bwd_total = 0;
     Tape* tape = nullptr;
+    // ---- loss guidance (vd_guide_begin / vd_guide_finish): the one taped pass that outlives a C call.  Its tape points into the arena and
+    // its eps lies in DiffWs's tail, so it is good only while nothing else has touched the workspace or set a tape: forward(), backward(),
+    // grow_ws() and vd_window_run() -- every path to the workspace -- open with drop_held(), as do the setters of what the finish reads.
+    struct HeldPass {
+        Tape tape; FwdIn fi; Arena ar;       // ar: where the forward left the arena, the mark the backward goes on from
+        int B, T, clip; const long long* t;
+        unsigned long long ticket;
+    };
+    std::unique_ptr<HeldPass> held;
+    unsigned long long guide_seq = 0;        // tickets handed out so far (a ticket is never 0)
+    unsigned long long guide_end_ticket = 0; const char* guide_end_why = "";      // how the last held pass ended
+    void end_held(const char* why) {
+        if (!held) return;
+        guide_end_ticket = held->ticket; guide_end_why = why;
+        held.reset();
+    }
+    void drop_held() { end_held("dropped by an engine call in between: one that runs the network, sizes the workspace or replays a window graph"); }
     // return_attn_weights: device buffers for the next forward, one pair per attention block in execution order
     std::vector<float*> attn_cap_t, attn_cap_s;
     int attn_seq = 0;
@@ -413,6 +431,7 @@ struct vd_engine {
     // The workspace of a window shape: the arena peak of its dry run (cached under `key`: the run walks the whole topology),
     // 256-byte rounded into *tail, plus `extra` bytes of the caller's own buffers behind it
     template <class DryRun> int grow_ws(long long key, size_t extra, DryRun dry_run, size_t* tail) {
+        drop_held();
         if (int rc = rpe_tables()) return rc;
         auto it = ws_peaks.find(key);
         if (it == ws_peaks.end()) {
@@ -1120,6 +1139,7 @@ int vd_engine::rpe_all(const float* te, const int64_t* fidx, int B, int T, hipSt
 int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixPlan* pp, const SuffixPlan* sp) {
     const int B = in.B, T = in.T, N = B * T, S = cfg.image_size, mc = cfg.num_channels;
     int rc;
+    drop_held();
     VD_REQUIRE(!pp || (!tape && !ar.dry && pp->store && n_before_attn > 0), "prefix plan: executor steps only");
     VD_REQUIRE(!sp || (!tape && sp->n > 0 && sp->n <= N && (ar.dry || sp->list)), "suffix plan: executor steps only, at least one frame");
     struct SelGuard { ~SelGuard() { g_sel_nfr = 0; } } sel_guard;      // (every return path leaves the selection hint cleared)
@@ -1394,6 +1414,7 @@ int vd_engine::backward(const FwdIn& in, const float* deps, float* dx, hipStream
     const int B = in.B, T = in.T, N = B * T, S = cfg.image_size;
     const bool dry = ar.dry;
     int rc;
+    drop_held();
     GradMap gm; gm.ar = &ar;
     bool fresh;
     // GroupNorm(+act) backward with its workspaces
@@ -1518,10 +1539,11 @@ int vd_engine::backward(const FwdIn& in, const float* deps, float* dx, hipStream
     return 0;
 }
 
-// A Tape on the engine while this object lives: forward() records into it, backward() reads it, no return path leaves a dead one behind
+// A Tape on the engine while this object lives: forward() records into it, backward() reads it, no return path leaves a dead one behind.
+// Its own tape, or `kept`: one that outlives the scope (the held pass of vd_guide_begin / vd_guide_finish).
 struct TapeScope {
     vd_engine* e; Tape tp;
-    explicit TapeScope(vd_engine* e_) : e(e_) { e->tape = &tp; }
+    explicit TapeScope(vd_engine* e_, Tape* kept = nullptr) : e(e_) { e->tape = kept ? kept : &tp; }
     ~TapeScope() { e->tape = nullptr; }
     TapeScope(const TapeScope&) = delete;
 };
@@ -1594,7 +1616,7 @@ int vd_create(const vd_config* cfg, vd_engine** out) {
     return 0;
 }
 
-void vd_destroy(vd_engine* e) { delete e; }
+void vd_destroy(vd_engine* e) { if (e) (void)vd_guide_abort(e); delete e; }
 
 int vd_param_count(vd_engine* e) { return e ? (int)e->params.size() : -1; }
 
@@ -1777,6 +1799,7 @@ int vd_set_schedule(vd_engine* e, int nts, const float* tab, const int* tmap, fl
     // the tables' addresses, num_timesteps and rescale are kernel arguments of every captured window graph
     if (e->win_cur >= 0) e->win_lost = true;
     e->drop_window_graphs();
+    e->drop_held();                      // vd_guide_finish's seed pass reads the rows of the schedule the pass began on
     if (e->d_tab) VD_HIP(hipFree(e->d_tab));
     if (e->d_tmap) VD_HIP(hipFree(e->d_tmap));
     if (e->d_w2m) { VD_HIP(hipFree(e->d_w2m)); e->d_w2m = nullptr; }      // the multistep weights belong to the schedule that goes
@@ -2570,6 +2593,7 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream) {
                                                                   : "more steps than the window has left (t would pass 0)";
     VD_REQUIRE(n_steps >= 0 && n_steps <= e->win_left, past);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    e->drop_held();                                   // a captured step writes the workspace without passing forward()
     for (int i = 0; i < n_steps; ++i) VD_HIP(hipGraphLaunch(e->win_graphs[e->win_cur].exec, st));
     e->win_left -= n_steps;
     return 0;
@@ -2820,6 +2844,7 @@ int vd_set_bwd_weight_storage(vd_engine* e, void* buf, long long bytes, int on_h
     VD_REQUIRE(e && buf, "null argument");
     VD_REQUIRE(split_math(), "use_gradient_method runs on the split arithmetic only (VD_MATH=f16x3 | bf16x6)");
     VD_REQUIRE(bytes >= (long long)(e->packed_bwd_total * sizeof(float)), "backward weight buffer too small");
+    e->drop_held();
     e->wbuf_bwd = static_cast<float*>(buf);
     e->wbuf_bwd_on_host = on_host != 0;
     return 0;
@@ -2888,16 +2913,16 @@ static int check_diff(vd_engine* e, int B, int T, const std::string& what, bool 
 extern "C++" {
 // The opening of every differentiated pass: the workspace, t_model, `pre` (the entry's own launches ahead of the network; it may point the
 // forward at DiffWs's masks), the taped forward, then `body` under the tape, with the arena the backward goes on in.  The forward reads
-// t_model from DiffWs and, where in.eps is null, writes its eps slot.
+// t_model from DiffWs and, where in.eps is null, writes its eps slot.  `kept`: record into this tape in place of the scope's own.
 template <class Pre, class Body>
-static int taped_pass(vd_engine* e, const DiffWs& w, FwdIn fi, const long long* t, hipStream_t st, Pre pre, Body body) {
+static int taped_pass(vd_engine* e, const DiffWs& w, FwdIn fi, const long long* t, hipStream_t st, Pre pre, Body body, Tape* kept = nullptr) {
     if (int rc = e->ensure_ws_guided(fi.B, fi.T)) return rc;
     fi.t_model = w.t_model();
     if (!fi.eps) fi.eps = w.eps();
     map_t(e, t, fi.B, w.t_model(), st);
     if (int rc = pre(fi)) return rc;
     Arena ar = w.arena();
-    TapeScope ts(e);
+    TapeScope ts(e, kept);
     const int rc = e->forward(fi, st, ar);
     return rc ? rc : body(fi, ar);
 }
@@ -3003,6 +3028,99 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, con
     DpsArgs da{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, scale, gray ? 1 : 0, clip,
                rbuf, part, deps, dxd, xstart, rho, e->d_err};
     return launch_dps_seed(da, static_cast<hipStream_t>(stream));
+}
+
+// ---- loss guidance: vd_dps_step split where the cotangent is formed, the caller's own code running between the two halves
+// The first half: vd_dps_step's checks under the name "loss_guidance", the opening of taped_pass and the sampler pass -- the plain step's
+// sample and pred_xstart.  The tape is then kept: it is recorded into the engine's held pass, beside what the second half reads, and
+// *ticket names it.  A pass held before is dropped (ensure_ws_guided -> grow_ws).
+int vd_guide_begin(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                   const long long* fidx, const long long* t, int obs_mode, int clip, int sampler, float eta, const float* noise,
+                   float* sample, float* xstart, unsigned long long* ticket, void* stream) {
+    if (int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes)) return rc;
+    if (int rc = check_diff(e, B, T, "loss_guidance")) return rc;
+    VD_REQUIRE(sampler == SAMPLER_P || sampler == SAMPLER_DDIM, "loss_guidance: p_sample (0) or ddim_sample (1), got sampler " + std::to_string(sampler));
+    VD_REQUIRE(sampler == SAMPLER_P || eta >= 0.f, "eta");
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && noise && sample && xstart && ticket, "null tensor");
+    *ticket = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
+    const DiffWs w(e, B, T);
+    VD_REQUIRE(w.partials_fit((size_t)B * guide_norm_blocks((long)per)), "loss_guidance: window too small for its partial sums");
+    auto hp = std::make_unique<vd_engine::HeldPass>();
+    hp->B = B; hp->T = T; hp->clip = clip; hp->t = t;
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, nullptr};
+    const int rc = taped_pass(e, w, in, t, st, no_pre, [&](const FwdIn& fi, Arena& ar) {
+        SamplerPassArgs pa = pass_args(e, sampler, B, (long long)per, x, t, clip, sample, xstart);
+        pa.eps = fi.eps; pa.eta = eta; pa.noise = noise;
+        hp->fi = fi; hp->ar = ar;
+        ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
+        return launch_sampler_pass(pa, st);
+    }, &hp->tape);
+    if (rc) return rc;
+    hp->ticket = *ticket = ++e->guide_seq;
+    e->held = std::move(hp);
+    return 0;
+}
+
+// The second half on the held pass `ticket` names: the seed pass on the caller's cotangent of x_0, launch_grad_rescale, the backward-data
+// pass under the kept tape, the norm pass (normalize) and the final pass on `sample` in place.  A ticket that is not the live one fails
+// before anything is launched; the held pass is released whatever happens behind that.
+int vd_guide_finish(vd_engine* e, unsigned long long ticket, const float* cot, const float* scale, int normalize, float* sample, float* grad,
+                    float* grad_norm, void* stream) {
+    VD_REQUIRE(e, "null engine");
+    if (!e->held || e->held->ticket != ticket) {
+        const std::string why = ticket == 0 || ticket > e->guide_seq ? "it was never begun"
+                                : ticket == e->guide_end_ticket      ? std::string(e->guide_end_why)
+                                                                     : "already finished, or dropped by an engine call in between";
+        set_error("loss_guidance: no taped pass is held for this ticket (" + why + ")");
+        return -1;
+    }
+    std::unique_ptr<vd_engine::HeldPass> hp = std::move(e->held);
+    e->guide_end_ticket = ticket; e->guide_end_why = "already finished";
+    VD_REQUIRE(cot && scale && sample, "loss_guidance: null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int B = hp->B, T = hp->T, S = e->cfg.image_size;
+    const long fe = 3L * S * S;
+    const size_t per = (size_t)T * fe;
+    const DiffWs w(e, B, T);
+    int rc;
+    {
+        GuideSeedArgs ga{hp->fi.x, hp->fi.eps, cot, hp->fi.lat, reinterpret_cast<const int64_t*>(hp->t), e->d_tab, e->num_timesteps, B, T, S, S,
+                         hp->clip, w.deps(), w.dxd(), e->d_err};
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 5.0, st, "guide_seed");
+        rc = launch_guide_seed(ga, st);
+    }
+    if (!rc) rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+    if (!rc) {
+        TapeScope ts(e, &hp->tape);
+        rc = e->backward(hp->fi, w.deps(), w.dx_net(), st, hp->ar);
+    }
+    if (!rc && normalize) {
+        ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 2.0, st, "guide_norm");
+        rc = launch_guide_norm(w.dxd(), w.dx_net(), w.gscale(), hp->fi.lat, B, T, fe, w.partials(), st);
+    }
+    if (!rc) {
+        ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "guide_final");
+        rc = launch_guide_final(w.dxd(), w.dx_net(), w.gscale(), hp->fi.lat, B, T, fe, scale, normalize ? w.partials() : nullptr, sample, grad,
+                                normalize ? grad_norm : nullptr, st);
+    }
+    return rc;
+}
+
+int vd_guide_abort(vd_engine* e) {
+    VD_REQUIRE(e, "null engine");
+    e->end_held("aborted (vd_guide_abort)");
+    return 0;
+}
+
+// The seed pass of vd_guide_finish alone, on a caller's (x_t, eps, cot): no network, no workspace of the engine (tests).
+int vd_op_guide_seed(vd_engine* e, int B, int T, int H, int W, const float* x, const float* eps, const long long* t, int clip,
+                     const float* cot, const float* lat, float* deps, float* dxd, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && x && eps && t && cot && lat && deps && dxd, "arguments");
+    GuideSeedArgs ga{x, eps, cot, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, clip, deps, dxd, e->d_err};
+    return launch_guide_seed(ga, static_cast<hipStream_t>(stream));
 }
 
 // The opening checks of the two entries that hand out the vector-Jacobian product of the network (vd_eps_vjp, vd_ode_nll_eval): what

@@ -632,6 +632,31 @@ int launch_dps_seed(DpsArgs a, hipStream_t s);
 int launch_dps_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, float zeta,
                      float* sample, float* grad, hipStream_t s);
 
+// Loss-guided sampling (guide.hip; this project's extension): a reverse step moved down the gradient of a caller's function of its x_0
+// prediction.  Tensors are [B][T][3][H][W], `lat` the [B*T] latent mask.  launch_guide_seed: on the frames with lat == 1, with cot the
+// caller's d loss / d x_0, c_r = cot where !clip or -1 <= x_0r <= 1 else 0 (x_0r = xstart_from_eps(...) at t[b]: the sampler pass's bits),
+// deps = (-sqrt_recipm1[t]) c_r, dxd = sqrt_recip[t] c_r; 0 on every other frame.  A t[b] outside the schedule: NaN on the item and bit 0
+// of `err`; a cot that is not finite propagates and raises nothing.  16-byte accesses while W % 4 == 0 and the tensors are 16-byte
+// aligned, else element by element: same bits.
+struct GuideSeedArgs {
+    const float* x; const float* eps; const float* cot; const float* lat;
+    const int64_t* t; const float* tab; int num_timesteps;
+    int B, T, H, W, clip;
+    float* deps; float* dxd;
+    int* err;               // the engine's sticky error word, or null
+};
+int launch_guide_seed(const GuideSeedArgs& a, hipStream_t s);
+// launch_guide_norm: part[b][k], k < guide_norm_blocks(per), the fp64 partial sums of g^2 over the item's frames with lat == 1,
+// g = dxd + dx_net * gs[1] in fp32 (launch_guide_final's g), in an order that depends on (T, frame_elems) alone.
+int guide_norm_blocks(long per);
+int launch_guide_norm(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, double* part,
+                      hipStream_t s);
+// launch_guide_final: g = dxd + dx_net * gs[1] -> grad (or null); per item m_b = scale[b], or with `part` (launch_guide_norm's)
+// n_b = fp32(sqrt(sum_k part[b][k])) -> grad_norm[b] (or null) and m_b = n_b == 0 ? 0 : scale[b] / n_b; sample = fmaf(-m_b, g, sample) on
+// the frames with lat == 1, every other frame keeps its bits.
+int launch_guide_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems,
+                       const float* scale, const double* part, float* sample, float* grad, float* grad_norm, hipStream_t s);
+
 // Probability-flow ODE likelihood (ode_nll.hip; this project's extension, Song et al. 2021).  Tensors are [B][T][frame_elems], `lat` the
 // [B*T] latent mask, an item has fewer than 2^31 elements.  16-byte accesses while frame_elems % 4 == 0 and the tensors are 16-byte
 // aligned, else element by element: same bits.  No floating-point atomics.

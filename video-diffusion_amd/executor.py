@@ -119,7 +119,8 @@ class WindowExecutor:
         gray); the captured step projects its x_0 prediction onto it, and y's address, the scale and the flag are part of the graph's
         signature.  Without it, a begin() inside `diffusion.measurement_scope(...)` takes the scope's measurement.  The engine refuses it
         by name with 'ddim_reverse', prefix_cache, suffix_skip and a known region.
-        A begin() inside `diffusion.dps_scope(...)` is refused by name: a DPS step runs a backward pass and is eager only."""
+        A begin() inside `diffusion.dps_scope(...)` is refused by name: a DPS step runs a backward pass and is eager only; so is one
+        inside `diffusion.loss_guidance_scope(...)`, whose step runs the caller's Python between two launches."""
         cfg_scale = float(cfg_scale)
         if not math.isfinite(cfg_scale):
             raise ValueError(f"cfg_scale={cfg_scale!r}: the guidance weight must be finite")
@@ -130,8 +131,9 @@ class WindowExecutor:
         from .gaussian_diffusion import _engine_region, _known, check_known_region
         if (known_src is None) != (known_mask is None):
             raise ValueError("known_src and known_mask are given together")
-        from .gaussian_diffusion import _refuse_dps
+        from .gaussian_diffusion import _refuse_dps, _refuse_loss_guidance
         _refuse_dps(self.model, "WindowExecutor.begin")                  # before anything touches the engine
+        _refuse_loss_guidance(self.model, "WindowExecutor.begin")        # (a Python callback between two launches cannot be captured)
         scope = _known(self.model)
         if known_src is not None:
             known_src, known_mask = check_known_region(known_src, known_mask)

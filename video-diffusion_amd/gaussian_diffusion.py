@@ -33,6 +33,7 @@ x_0 + A^+(y - A x_0), for the cell-mean operators A of `measure` -- super-resolu
 Training losses are out of scope.
 """
 import contextlib
+import ctypes
 import enum
 import math
 
@@ -275,6 +276,51 @@ def check_zeta(zeta):
 def _refuse_dps(model, what):
     if _dps(model) is not None:
         raise _lib.VdError(f"{what} inside dps_scope is not served")
+
+
+def _loss_guidance(model):
+    """The setting the innermost loss_guidance_scope set on this model (dict loss_fn, cotangent_fn, scale, normalize), or None."""
+    return getattr(getattr(model, "model", model), "_loss_guidance", None)
+
+
+def _refuse_loss_guidance(model, what):
+    if _loss_guidance(model) is not None:
+        raise _lib.VdError(f"{what} inside loss_guidance_scope is not served")
+
+
+def _scale_number(v, what="scale"):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"loss_guidance_scope: {what}={v!r}: the step size must be a number, or a callable scale(t) returning one or a (B,) tensor")
+    z = float(v)
+    if not (0.0 <= z <= 3.4028234663852886e38):              # (a NaN fails both comparisons; the engine takes it as a float32)
+        raise ValueError(f"loss_guidance_scope: {what}={v!r}: the step size must be finite and not negative")
+    return z
+
+
+def check_loss_guidance(loss_fn, cotangent_fn, scale):
+    """The host checks of loss_guidance_scope's arguments (no engine): exactly one of the two functions, both callable; `scale` a finite
+    number that is not negative (returned as a float) or a callable (returned as it is, checked at every step).  ValueError otherwise."""
+    if (loss_fn is None) == (cotangent_fn is None):
+        raise ValueError("loss_guidance_scope: exactly one of loss_fn and cotangent_fn is given")
+    if not callable(loss_fn if loss_fn is not None else cotangent_fn):
+        raise ValueError("loss_guidance_scope: loss_fn / cotangent_fn must be callable: fn(x0, t)")
+    return scale if callable(scale) else _scale_number(scale)
+
+
+def loss_guidance_step_scale(scale, t, B):
+    """The (B,) float32 host tensor of a step's per-item step sizes: `scale` as check_loss_guidance returned it, or scale(t) -- a number,
+    or a tensor of B values (one value: every item's) -- each checked here, on the host, finite and not negative; ValueError otherwise."""
+    v = scale(t) if callable(scale) else scale
+    if th.is_tensor(v):
+        v = v.detach().to(device="cpu", dtype=th.float32).reshape(-1)
+        if v.numel() == 1:
+            v = v.expand(B)
+        if v.numel() != B:
+            raise ValueError(f"loss_guidance_scope: scale(t) returned {v.numel()} values for a batch of {B}")
+        if not bool((th.isfinite(v) & (v >= 0)).all()):
+            raise ValueError(f"loss_guidance_scope: scale(t)={v.tolist()!r}: every step size must be finite and not negative")
+        return v.contiguous()
+    return th.full((B,), _scale_number(v, "scale(t)" if callable(scale) else "scale"), dtype=th.float32)
 
 
 class GaussianDiffusion:
@@ -567,6 +613,101 @@ class GaussianDiffusion:
                                  _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
         return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
 
+    @contextlib.contextmanager
+    def loss_guidance_scope(self, model, loss_fn=None, *, cotangent_fn=None, scale, normalize=False):
+        """This project's extension: `with diffusion.loss_guidance_scope(model, loss_fn, scale=s):` -- every p_sample and ddim_sample call
+        inside, and every loop built on them, runs the plain step and then moves the frames with latent_mask == 1 down the gradient, with
+        respect to x_t, of the caller's own function of the step's x_0 prediction; the gradient runs through the clamp of clip_denoised and
+        the whole UNet.  Classifier or regressor guidance, a perceptual loss against a reference frame, a colour constraint, PiGDM's
+        cotangent and DPS itself are instances.  Exactly one of:
+          loss_fn(x0, t)       x0 is 'pred_xstart' (B, T, 3, H, W) as a leaf that requires grad, t the step's (B,) int64 indices, both on
+                               the device; called under torch.enable_grad(); returns a tensor of any shape, whose SUM is differentiated
+                               with torch.autograd.grad (a loss that does not depend on x0 gives a zero gradient);
+          cotangent_fn(x0, t)  returns d loss / d x0 itself: x0's shape, float32, on the device; no autograd is involved.
+        What either says about frames that are not latent is ignored.  A step is vd_guide_begin, the function on torch's current stream,
+        vd_guide_finish (include/vd_amd.h): ONE taped forward and one backward-data pass -- what a dps_scope step costs, and one forward
+        less than the plain step followed by eps_vjp.  sample = fmaf(-m_b, grad, sample_plain) per item b, m_b = scale, or with
+        normalize=True scale / ||grad_b||_2 over the item's latent frames (0 where that norm is 0).  The returned dict gains 'grad' (the
+        unscaled gradient on every frame, 0 on observed frames) and, with normalize, 'grad_norm' (B,); 'pred_xstart' is the plain
+        step's, scale 0 is the plain step to the bit, and the sampler noise is drawn once per step, where the plain step draws it.
+        scale: a finite number that is not negative, or a callable scale(t) -> number | (B,) tensor, checked on the host at every step
+        (a tensor costs a device wait); ValueError otherwise.  Windows of at most 32 frames, epsilon-prediction models.
+        Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name: dpmpp_2m_sample,
+        dpmpp_2m_sde_sample, unipc_sample, ddim_reverse_sample, denoised_fn, use_gradient_method, return_attn_weights, cfg_scale != 1,
+        guidance_scope with either option set, known_region_scope, measurement_scope and dps_scope on the same model, predict_xstart
+        models, and WindowExecutor.begin (a Python callback cannot be captured in a graph).  Not honoured by model(...) itself,
+        p_mean_variance, score_windows and the NLL path.
+        The engine holds the taped pass between the two calls and drops it as soon as anything else runs the network on the same model:
+        a function that itself calls the engine on this model (model(...), a step, eps_vjp, ...) makes the step fail with
+        'loss_guidance: no taped pass is held for this ticket'; use another model instance for that.  If the function raises, the held
+        pass is dropped and the exception passes through.  PiGDM (Song et al. 2023) for a measurement y of `measure` is five lines:
+            def pigdm(x0, t):                                   # cotangent_fn: A^+ (A x0 - y) for the cell-mean operators, r_t^2 = 1
+                r = measure(x0, 4) - y                          # (B, T, 3, H / 4, W / 4)
+                up = r.repeat_interleave(4, -1).repeat_interleave(4, -2)
+                return up                                       # A^+ r: every element of a cell takes r_cell
+        and DPS is loss_fn = lambda x0, t: (y - measure(x0, 4)).flatten(1).norm(dim=1).  No claim about sample quality is made."""
+        base = self._bind(model)
+        scale = check_loss_guidance(loss_fn, cotangent_fn, scale)
+        d = dict(loss_fn=loss_fn, cotangent_fn=cotangent_fn, scale=scale, normalize=bool(normalize))
+        before = _loss_guidance(base)
+        base._loss_guidance = d
+        try:
+            yield
+        finally:
+            base._loss_guidance = before
+
+    def _loss_guidance_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                            use_gradient_method, cfg_scale):
+        """One p_sample (mode 0) / ddim_sample (mode 1) step inside loss_guidance_scope -> dict sample, pred_xstart, grad[, grad_norm]."""
+        d = _loss_guidance(model)
+        if self.model_mean_type != ModelMeanType.EPSILON:
+            raise NotImplementedError("loss_guidance_scope with predict_xstart=True: epsilon-prediction models only")
+        for flag, what in ((denoised_fn is not None, "denoised_fn"), (use_gradient_method, "use_gradient_method"),
+                           (return_attn_weights, "return_attn_weights"), (cfg_scale != 1.0, "cfg_scale != 1")):
+            if flag:
+                _refuse_loss_guidance(model, what)
+        base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
+        L = _lib.lib()
+        if L.vd_cfg_scale(base._handle) != 1.0:
+            _refuse_loss_guidance(base, "cfg_scale != 1 (cfg_scale_scope)")
+        if L.vd_guidance_rescale(base._handle) != 0.0 or L.vd_dynamic_threshold(base._handle) != 0.0:
+            _refuse_loss_guidance(base, "guidance_scope with cfg_rescale or dynamic_threshold set")
+        for on, what in ((_known(base), "known_region_scope"), (_measurement(base), "measurement_scope"), (_dps(base), "dps_scope")):
+            if on is not None:
+                _refuse_loss_guidance(base, what)
+        B, T = xs.shape[:2]
+        scale = loss_guidance_step_scale(d["scale"], tt, B).to(base.device)
+        base._require_guidance()
+        noise = th.randn_like(xs) if noise is None else _f32(noise, base.device)
+        assert noise.shape == xs.shape
+        sample, xstart, grad = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
+        norm = th.empty(B, dtype=th.float32, device=base.device) if d["normalize"] else None
+        stream = _lib.current_stream()
+        ticket = ctypes.c_ulonglong(0)
+        _lib.check(L.vd_guide_begin(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0,
+                                    mode, float(eta), _lib.ptr(noise), _lib.ptr(sample), _lib.ptr(xstart), ctypes.byref(ticket), stream))
+        try:
+            if d["cotangent_fn"] is not None:
+                cot = d["cotangent_fn"](xstart, tt)
+            else:
+                with th.enable_grad():
+                    leaf = xstart.detach().requires_grad_(True)
+                    (cot,) = th.autograd.grad(d["loss_fn"](leaf, tt).sum(), leaf, allow_unused=True)
+                cot = th.zeros_like(xs) if cot is None else cot.detach()
+            if not (th.is_tensor(cot) and cot.shape == xs.shape and cot.dtype == th.float32 and cot.device == xs.device):
+                raise ValueError(f"loss_guidance_scope: the cotangent must be a float32 tensor of {tuple(xs.shape)} on {xs.device}, got "
+                                 f"{getattr(cot, 'dtype', type(cot))} {tuple(getattr(cot, 'shape', ()))} on {getattr(cot, 'device', None)}")
+            cot = cot.contiguous()
+        except BaseException:
+            L.vd_guide_abort(base._handle)
+            raise
+        _lib.check(L.vd_guide_finish(base._handle, ticket.value, _lib.ptr(cot), _lib.ptr(scale), 1 if d["normalize"] else 0, _lib.ptr(sample),
+                                     _lib.ptr(grad), _lib.ptr(norm), stream))
+        out = {"sample": sample, "pred_xstart": xstart, "grad": grad}
+        if d["normalize"]:
+            out["grad_norm"] = norm
+        return out
+
     def q_jump(self, x, t, latent_mask=None, noise=None, model=None):
         """This project's extension: one forward diffusion step x_{t-1} -> x_t at index t, the move RePaint's resampling walks back up
         with: on the frames with latent_mask == 1 (None: every frame) sqrt(1 - beta_t) x + sqrt(beta_t) noise, the other frames unchanged;
@@ -616,6 +757,10 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         self._last_dps = None
+        if _loss_guidance(model) is not None:                      # ... inside loss_guidance_scope: the plain step, the caller's function, the move
+            self._last_dps = self._loss_guidance_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
+                                                      return_attn_weights, use_gradient_method, cfg_scale)
+            return self._last_dps["sample"], self._last_dps["pred_xstart"]
         if _dps(model) is not None:                                # p_sample / ddim_sample inside dps_scope: the plain step, then the DPS move
             self._last_dps = self._dps_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
                                             use_gradient_method, cfg_scale)
@@ -1103,9 +1248,10 @@ class GaussianDiffusion:
         return {"sample": sample, "pred_xstart": xstart, "attn": self._last_attn if return_attn_weights else None, **self._dps_extras()}
 
     def _dps_extras(self):
-        """'grad' and 'residual_norm' of the step just made inside dps_scope; nothing outside it."""
+        """'grad' and 'residual_norm' of the step just made inside dps_scope, 'grad' and (normalize) 'grad_norm' of one inside
+        loss_guidance_scope; nothing outside them."""
         d = getattr(self, "_last_dps", None)
-        return {} if d is None else {"grad": d["grad"], "residual_norm": d["residual_norm"]}
+        return {} if d is None else {k: d[k] for k in ("grad", "residual_norm", "grad_norm") if k in d}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:597-634."""
@@ -1121,6 +1267,7 @@ class GaussianDiffusion:
         _refuse_known(model, "ddim_reverse_sample")
         _refuse_measurement(model, "ddim_reverse_sample")
         _refuse_dps(model, "ddim_reverse_sample")
+        _refuse_loss_guidance(model, "ddim_reverse_sample")
         if denoised_fn is not None:
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
             return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
@@ -1138,6 +1285,7 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         _refuse_dps(model, "dpmpp_2m_sample")
+        _refuse_loss_guidance(model, "dpmpp_2m_sample")
         if denoised_fn is not None:
             _refuse_known(model, "denoised_fn")
             _refuse_measurement(model, "denoised_fn")
@@ -1165,6 +1313,7 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         _refuse_dps(model, "dpmpp_2m_sde_sample")
+        _refuse_loss_guidance(model, "dpmpp_2m_sde_sample")
         if denoised_fn is not None:
             _refuse_known(model, "denoised_fn")
             _refuse_measurement(model, "denoised_fn")
@@ -1191,6 +1340,7 @@ class GaussianDiffusion:
             model_kwargs = {}
         self._refuse_learned(x)
         _refuse_dps(model, "unipc_sample")
+        _refuse_loss_guidance(model, "unipc_sample")
         _refuse_known(model, "unipc_sample")
         base = self._bind(model)
         dev = base.device

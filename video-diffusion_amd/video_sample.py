@@ -46,7 +46,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 use_gradient_method=False, observed_frames="x_0", sampler="p_sample", eta=0.0, executor="eager",
                 adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
-                measurement=None, sr_scale=1, gray=False, dps_zeta=None):
+                measurement=None, sr_scale=1, gray=False, dps_zeta=None, loss_fn=None, cotangent_fn=None, loss_scale=None,
+                loss_normalize=False):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -112,7 +113,31 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     gaussian_diffusion.py: dps_scope in place of the projection: every step is the plain step followed by a move of the window's latent
     frames down the gradient of ||y - A x_0(x_t)||_2, through the whole UNet (windows of at most 32 frames).  Refused by name before the
     engine is touched: no measurement, executor='graph', prefix_cache, suffix_skip, sampler='dpmpp_2m', use_gradient_method, known_mask,
-    cfg_scale != 1, cfg_rescale and dynamic_threshold.  None (default): the projection, as before."""
+    cfg_scale != 1, cfg_rescale and dynamic_threshold.  None (default): the projection, as before.
+
+    loss_fn, cotangent_fn, loss_scale, loss_normalize (this project's extension: loss-guided sampling; eager executor, samplers
+    'p_sample' and 'ddim'): with one of the two functions given, every window's step loop runs inside gaussian_diffusion.py:
+    loss_guidance_scope(model, loss_fn, cotangent_fn=cotangent_fn, scale=loss_scale, normalize=loss_normalize) -- every step is the
+    plain step followed by a move of the window's latent frames down the gradient of the caller's function of the step's x_0
+    prediction, through the whole UNet (windows of at most 32 frames).  The function sees a WINDOW (B, Tw, 3, H, W), observed frames
+    first, not the whole video.  Refused by name before the engine is touched: both or a missing loss_scale (ValueError),
+    executor='graph', prefix_cache, suffix_skip, the samplers 'dpmpp_2m', 'dpmpp_2m_sde' and 'unipc', use_gradient_method, known_mask,
+    a measurement, cfg_scale != 1, cfg_rescale and dynamic_threshold.  Both None (default): no scope is entered."""
+    loss_guided = loss_fn is not None or cotangent_fn is not None
+    if loss_guided or loss_scale is not None:
+        from . import _lib
+        from .gaussian_diffusion import check_loss_guidance
+        if loss_scale is None:
+            raise ValueError("loss_fn / cotangent_fn need a step size (loss_scale=)")
+        loss_scale = check_loss_guidance(loss_fn, cotangent_fn, loss_scale)
+        for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
+                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("sampler='dpmpp_2m_sde'", sampler == "dpmpp_2m_sde"),
+                         ("sampler='unipc'", sampler == "unipc"), ("use_gradient_method", use_gradient_method),
+                         ("known_mask", known_mask is not None), ("a measurement", measurement is not None),
+                         ("cfg_scale != 1", float(cfg_scale) != 1.0),
+                         ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
+            if on:
+                raise _lib.VdError(f"{name} together with loss_fn / cotangent_fn (loss_guidance_scope) is not served")
     if dps_zeta is not None:
         from . import _lib
         from .gaussian_diffusion import check_zeta
@@ -247,7 +272,9 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         unipc_state = None                                  # ... and so is unipc's state
         if sampler == "dpmpp_2m_sde":                       # ... and the noise what the window executor would draw (its seed, its ranges)
             sde_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        if y_w is None:
+        if loss_guided:
+            scope = diffusion.loss_guidance_scope(model, loss_fn, cotangent_fn=cotangent_fn, scale=loss_scale, normalize=loss_normalize)
+        elif y_w is None:
             scope = contextlib.nullcontext()
         elif dps_zeta is not None:
             scope = diffusion.dps_scope(model, y_w, sr_scale, gray, zeta=dps_zeta)
@@ -462,8 +489,8 @@ def load_model(args, device, rank=0, world=1, create=None):
             holder["sd"] = {k: torch.from_numpy(synth_param(k, s)) for k, s in model.param_specs()}
         return holder["sd"]
 
-    if rank == 0 and getattr(args, "dps_zeta", None) is not None:
-        model.enable_guidance()      # --dps_zeta runs the backward-data pass: rank 0 packs the second image, share_weights broadcasts it
+    if rank == 0 and (getattr(args, "dps_zeta", None) is not None or getattr(args, "loss_guidance", None)):
+        model.enable_guidance()      # --dps_zeta / --loss_guidance run the backward-data pass: rank 0 packs the second image, share_weights broadcasts it
     vdist.share_weights(model, state_dict_fn, rank)
     return model, diffusion
 
@@ -589,6 +616,16 @@ def build_parser():
                     help="with --measurement: diffusion posterior sampling (DPS) for a measurement that carries noise -- every step moves the "
                          "generated frames down the gradient of ||y - A x_0||_2 through the network with step size Z, in place of the exact "
                          "projection; eager executor, samplers p_sample and ddim; named in the run directory when set")
+    ap.add_argument("--loss_guidance", default=None, metavar="MODULE:FUNCTION",
+                    help="loss-guided sampling: FUNCTION(x0, t) of the importable MODULE (the current directory is searched too) is a loss on "
+                         "each window's x_0 prediction (B, Tw, 3, H, W), differentiated by torch; every step moves the generated frames down "
+                         "its gradient through the network; needs --loss_guidance_scale; eager executor, samplers p_sample and ddim; "
+                         "named in the run directory when set")
+    ap.add_argument("--loss_guidance_scale", type=float, default=None, metavar="S", help="with --loss_guidance: the step size, finite and not negative")
+    ap.add_argument("--loss_guidance_normalize", action="store_true",
+                    help="with --loss_guidance: the step is S / ||grad||_2 per video, the norm over the window's generated frames")
+    ap.add_argument("--loss_guidance_cotangent", action="store_true",
+                    help="with --loss_guidance: FUNCTION returns d loss / d x_0 itself (float32, x_0's shape, on the device), no autograd")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -644,6 +681,44 @@ def _measurement_options(args, batch):
                 **({} if zeta is None else dict(dps_zeta=float(zeta))))
 
 
+def import_function(spec):
+    """'MODULE:FUNCTION' -> the callable FUNCTION of the module importlib finds under the name MODULE; the current directory is searched
+    like the rest of sys.path (a script run as `python -m` does not have it there).  ValueError for a spec of another form, a module that
+    cannot be imported, or a name that is missing or not callable."""
+    import importlib
+    import sys
+    mod, sep, fn = str(spec).partition(":")
+    if not (sep and mod and fn):
+        raise ValueError(f"--loss_guidance {spec!r}: expected MODULE:FUNCTION")
+    if os.getcwd() not in sys.path and "" not in sys.path:
+        sys.path.append(os.getcwd())
+    try:
+        module = importlib.import_module(mod)
+    except ImportError as e:
+        raise ValueError(f"--loss_guidance {spec!r}: cannot import module {mod!r}: {e}") from e
+    f = getattr(module, fn, None)
+    if not callable(f):
+        raise ValueError(f"--loss_guidance {spec!r}: module {mod!r} has no callable {fn!r}")
+    return f
+
+
+def _loss_guidance_options(args):
+    """--loss_guidance MODULE:FUNCTION and its companions -> infer_video's keywords ({} without the option)."""
+    spec = getattr(args, "loss_guidance", None)
+    scale = getattr(args, "loss_guidance_scale", None)
+    if not spec:
+        for name in ("loss_guidance_scale", "loss_guidance_normalize", "loss_guidance_cotangent"):
+            if getattr(args, name, None):
+                raise ValueError(f"--{name} needs --loss_guidance MODULE:FUNCTION")
+        return {}
+    if scale is None:
+        raise ValueError("--loss_guidance needs --loss_guidance_scale S")
+    f = import_function(spec)
+    cot = bool(getattr(args, "loss_guidance_cotangent", False))
+    return dict(loss_fn=None if cot else f, cotangent_fn=f if cot else None, loss_scale=float(scale),
+                loss_normalize=bool(getattr(args, "loss_guidance_normalize", False)))
+
+
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
     return infer_video(args.inference_mode, model, diffusion, batch, args.max_frames, args.obs_length, args.step_size,
                        optimal_schedule_path, use_gradient_method=getattr(args, "use_gradient_method", False),
@@ -653,13 +728,13 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
                        save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
                        cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None),
-                       **_known_options(args, batch), **_measurement_options(args, batch))
+                       **_known_options(args, batch), **_measurement_options(args, batch), **_loss_guidance_options(args))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
-    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5') -- samples of different samplers or guidance settings never share a directory, and a run
+    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'), and a --loss_guidance ('_lg0.5': its scale) -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
@@ -675,8 +750,11 @@ def run_postfix(args):
         meas = "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
         if getattr(args, "dps_zeta", None) is not None:
             meas += f"_dps{float(args.dps_zeta):g}"
+    lg = ""
+    if getattr(args, "loss_guidance", None):      # '_lg0.5' (the function is not named: a run directory is one function's)
+        lg = "_lg" + ("None" if getattr(args, "loss_guidance_scale", None) is None else f"{float(args.loss_guidance_scale):g}")
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
-        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas + lg
 
 
 def run(args, create=None, device=None, infer=None):
