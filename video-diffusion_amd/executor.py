@@ -29,21 +29,15 @@ import math
 import torch as th
 
 from . import _lib
+from .gaussian_diffusion import (SAMPLERS, _engine_measurement, _engine_region, _refuse, _scope, check_known_region, check_measurement,
+                                 measurement_shape)
 
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
 def _sampler_id(sampler):
     """vd_window_begin's sampler: 'ddim_reverse' is 2, 'dpmpp_2m' 3, 'dpmpp_2m_sde' 4, 'unipc' 5, 'p_sample' 0 and every other string ddim_sample, 1."""
-    if sampler == "ddim_reverse":
-        return 2
-    if sampler == "dpmpp_2m":
-        return 3
-    if sampler == "dpmpp_2m_sde":
-        return 4
-    if sampler == "unipc":
-        return 5
-    return 0 if sampler == "p_sample" else 1
+    return SAMPLERS.get(sampler, SAMPLERS["ddim"]).id
 
 
 class WindowExecutor:
@@ -81,7 +75,6 @@ class WindowExecutor:
 
     def _measurement_buffer(self, B, T, scale, gray):
         """The window's measurement, one buffer per (B, T, scale, gray): a stable address, so one graph per shape and operator."""
-        from .gaussian_diffusion import measurement_shape
         bufs, key = self._buffers(B, T), f"measurement_s{scale}_g{int(gray)}"
         if key not in bufs:
             S = self.model.image_size
@@ -128,13 +121,11 @@ class WindowExecutor:
             raise NotImplementedError("prefix_cache together with cfg_scale != 1")
         if cfg_scale != 1.0 and self.suffix_skip:
             raise NotImplementedError("suffix_skip together with cfg_scale != 1")
-        from .gaussian_diffusion import _engine_region, _known, check_known_region
         if (known_src is None) != (known_mask is None):
             raise ValueError("known_src and known_mask are given together")
-        from .gaussian_diffusion import _refuse_dps, _refuse_loss_guidance
-        _refuse_dps(self.model, "WindowExecutor.begin")                  # before anything touches the engine
-        _refuse_loss_guidance(self.model, "WindowExecutor.begin")        # (a Python callback between two launches cannot be captured)
-        scope = _known(self.model)
+        _refuse(self.model, "dps", "WindowExecutor.begin")               # before anything touches the engine
+        _refuse(self.model, "loss_guidance", "WindowExecutor.begin")     # (a Python callback between two launches cannot be captured)
+        scope = _scope(self.model, "known_region")
         if known_src is not None:
             known_src, known_mask = check_known_region(known_src, known_mask)
         elif scope is not None:
@@ -146,8 +137,7 @@ class WindowExecutor:
                              ("sampler='unipc'", sampler == "unipc")):
                 if on:
                     raise NotImplementedError(f"{name} together with a known region")
-        from .gaussian_diffusion import _engine_measurement, _measurement, check_measurement
-        m_scope = _measurement(self.model)
+        m_scope = _scope(self.model, "measurement")
         if measurement is not None:
             meas = dict(y=check_measurement(measurement, x_init.shape, sr_scale, gray), scale=int(sr_scale), gray=bool(gray))
         elif m_scope is not None:
@@ -205,9 +195,9 @@ class WindowExecutor:
                 bufs["obs_src"].copy_(kw["obs_src"])
             if seed is None:
                 seed = int(th.randint(0, 2 ** 62, (1,)).item())        # torch.manual_seed governs the run
-            sid = _sampler_id(sampler)
+            sid, up = _sampler_id(sampler), SAMPLERS.get(sampler, SAMPLERS["ddim"]).up
             if t_start is None:
-                t_start = 0 if sid == 2 else self.diffusion.num_timesteps - 1
+                t_start = 0 if up else self.diffusion.num_timesteps - 1
             obs_src = bufs["x"] if mode == "x_t" else bufs["obs_src"]
             _lib.check(_lib.lib().vd_set_window_prefix_cache(self.model._handle, 1 if self.prefix_cache else 0))
             _lib.check(_lib.lib().vd_set_window_suffix_skip(self.model._handle, 1 if self.suffix_skip else 0))
@@ -236,7 +226,7 @@ class WindowExecutor:
             _lib.check(rc)
         self.x = bufs["x"]
         self.seed = seed
-        self._left = self.diffusion.num_timesteps - int(t_start) if sid == 2 else int(t_start) + 1
+        self._left = self.diffusion.num_timesteps - int(t_start) if up else int(t_start) + 1
         self._gen = int(_lib.lib().vd_window_generation(self.model._handle))
         return self
 

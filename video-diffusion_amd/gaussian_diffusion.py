@@ -36,6 +36,7 @@ import contextlib
 import ctypes
 import enum
 import math
+import typing
 
 import numpy as np
 import torch as th
@@ -87,8 +88,71 @@ class LossType(enum.Enum):
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
 
+class Sampler(typing.NamedTuple):
+    """What the step path knows about one sampler; every dispatch on a sampler reads a row of SAMPLERS."""
+    id: int                  # the engine's numbering (include/vd_amd.h: vd_window_begin)
+    step: str                # the public step method
+    fused: str               # the C entry of the fused step
+    from_xstart: str         # ... and the network-free one that finishes a step through denoised_fn
+    noise: str               # None: draws nothing; "tensor": reads a noise tensor; "philox": a tensor, or a (seed, offset) pair in its place
+    eta: bool                # the step reads eta
+    carry: str               # what a chain hands from step to step: None, "prev_xstart", or "state" (UniPC's three tensors and count)
+    up: bool                 # t walks up (towards the noise)
+    cfg_keyword: bool        # cfg_scale is a keyword of the step; False: the step takes it from cfg_scale_scope
+    known_region: bool       # a step inside known_region_scope is served (the merge pass behind it)
+
+
+SAMPLERS = {
+    "p_sample": Sampler(0, "p_sample", "vd_p_sample", "vd_posterior_from_xstart", "tensor", False, None, False, True, True),
+    "ddim": Sampler(1, "ddim_sample", "vd_ddim_sample", "vd_posterior_from_xstart", "tensor", True, None, False, True, True),
+    "ddim_reverse": Sampler(2, "ddim_reverse_sample", "vd_ddim_reverse_sample", "vd_ddim_reverse_from_xstart", None, False, None, True, False,
+                            False),
+    "dpmpp_2m": Sampler(3, "dpmpp_2m_sample", "vd_dpmpp_2m_sample", "vd_dpmpp_2m_from_xstart", None, False, "prev_xstart", False, False, True),
+    "dpmpp_2m_sde": Sampler(4, "dpmpp_2m_sde_sample", "vd_dpmpp_2m_sde_sample", "vd_dpmpp_2m_sde_from_xstart", "philox", False, "prev_xstart",
+                            False, False, True),
+    "unipc": Sampler(5, "unipc_sample", "vd_unipc_sample", "vd_unipc_from_xstart", None, False, "state", False, False, False),
+}
+_BY_ID = {row.id: row for row in SAMPLERS.values()}
+
+
 def _f32(t, device):
     return t.to(device=device, dtype=th.float32).contiguous()
+
+
+def _entry_args(row, lead, xs, flags, eta, noise, outs, prev_xstart=None, state=None):
+    """The one statement of the order sampler `row`'s two C entries take their arguments in -> (the arguments up to the stream, the state
+    the step returns or None).  `lead`: the fused step's window up to t, or handle[, sampler], B, per-item count, x and x_0 behind
+    denoised_fn; then what the sampler carries (prev_xstart; UniPC's three tensors and count); `flags` ((obs_mode, clip), or (t, clip)
+    behind denoised_fn); `eta` as a tuple, empty where the entry has none; `noise` = (tensor, seed, offset) for a sampler that reads
+    noise; `outs` (sample, pred_xstart[, what the entry takes behind them]) around UniPC's three new tensors.  Tensors stay tensors, so
+    that the caller holds them for the length of the call: _ptrs() at the call itself."""
+    carry, new = (), ()
+    if row.carry == "prev_xstart":
+        carry = (None if prev_xstart is None else _f32(prev_xstart, xs.device),)
+        assert carry[0] is None or carry[0].shape == xs.shape
+    elif row.carry == "state":
+        carry = (None, None, None, 0) if state is None else (*(_f32(v, xs.device) for v in state[:3]), int(state[3]))
+        assert state is None or (all(v.shape == xs.shape for v in carry[:3]) and carry[3] >= 0)
+        new = tuple(th.empty_like(xs) for _ in range(3))
+    return (*lead, *carry, *flags, *eta, *(noise or ()), *outs[:2], *new, *outs[2:]), (*new, carry[3] + 1) if new else None
+
+
+def _ptrs(args):
+    return [_lib.ptr(a) if isinstance(a, th.Tensor) else a for a in args]
+
+
+def _step_noise(row, xs, noise, philox):
+    """(noise tensor, seed, offset) of a step of sampler `row`: `noise`, drawn from the global generator when None (even for eta = 0:
+    gaussian_diffusion.py:438 / :628); with philox = (seed, offset) no tensor -- the pass draws element i from the engine's Philox stream
+    at that state, as a window graph does.  None for a sampler that reads no noise."""
+    assert philox is None or (row.noise == "philox" and noise is None)
+    if row.noise is None:
+        return None
+    if philox is not None:
+        return None, int(philox[0]), int(philox[1])
+    noise = th.randn_like(xs) if noise is None else _f32(noise, xs.device)
+    assert noise.shape == xs.shape
+    return noise, 0, 0
 
 
 def _check_cfg(cfg_scale, return_attn_weights=False, use_gradient_method=False):
@@ -166,9 +230,36 @@ def check_known_region(known_src, known_mask):
     return known_src.to(th.float32).contiguous(), m.contiguous()
 
 
-def _known(model):
-    """The known region the innermost known_region_scope set on this model, or None."""
-    return getattr(getattr(model, "model", model), "_known_region", None)
+# the scopes that keep their setting on the model, as attribute _<name> -- in the order a step inside a later one refuses the earlier
+# ones -- and what a refusal raises
+_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "loss_guidance": _lib.VdError}
+
+
+def _scope(model, name):
+    """What the innermost <name>_scope set on this model, or None: known_region (dict src, mask, noise), measurement (dict y, scale, gray),
+    dps (dict y, scale, gray, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize)."""
+    return getattr(getattr(model, "model", model), "_" + name, None)
+
+
+def _refuse(model, scope, what):
+    if _scope(model, scope) is not None:
+        raise _SCOPES[scope](f"{what} inside {scope}_scope is not served")
+
+
+@contextlib.contextmanager
+def _scoped(base, name, value, engine=None):
+    """The body of a <name>_scope: the setting on the model, and through `engine` (setting or None -> engine state) in the engine; behind
+    the block, whatever it raised, what was found before."""
+    before = _scope(base, name)
+    setattr(base, "_" + name, value)
+    try:
+        if engine is not None:
+            engine(base, value)
+        yield
+    finally:
+        setattr(base, "_" + name, before)
+        if engine is not None:
+            engine(base, before)
 
 
 def _engine_region(model, region, noise=None):
@@ -177,11 +268,6 @@ def _engine_region(model, region, noise=None):
         _lib.check(_lib.lib().vd_set_known_region(model._handle, None, None, None, 0, 0))
     else:
         _lib.check(_lib.lib().vd_set_known_region(model._handle, _lib.ptr(region["src"]), _lib.ptr(region["mask"]), _lib.ptr(noise), 0, 0))
-
-
-def _refuse_known(model, what):
-    if _known(model) is not None:
-        raise NotImplementedError(f"{what} inside known_region_scope is not served")
 
 
 MEASUREMENT_SCALES = (1, 2, 4, 8)
@@ -234,11 +320,6 @@ def check_measurement(y, shape, scale=1, gray=False):
     return y
 
 
-def _measurement(model):
-    """The measurement the innermost measurement_scope set on this model (dict y, scale, gray), or None."""
-    return getattr(getattr(model, "model", model), "_measurement", None)
-
-
 def _engine_measurement(model, m):
     """Engine state <- a measurement dict (y: a device tensor the caller keeps alive; scale; gray) or None (clear)."""
     if m is None:
@@ -247,20 +328,10 @@ def _engine_measurement(model, m):
         _lib.check(_lib.lib().vd_set_measurement(model._handle, _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0))
 
 
-def _refuse_measurement(model, what):
-    if _measurement(model) is not None:
-        raise _lib.VdError(f"{what} inside measurement_scope is not served")
-
-
 def _check_step_measurement(model, shape):
-    m = _measurement(model)
+    m = _scope(model, "measurement")
     if m is not None and tuple(m["y"].shape) != measurement_shape(shape, m["scale"], m["gray"]):
         raise ValueError(f"measurement_scope: y {tuple(m['y'].shape)} against a step on {tuple(shape)} at scale={m['scale']}, gray={m['gray']}")
-
-
-def _dps(model):
-    """The DPS setting the innermost dps_scope set on this model (dict y, scale, gray, zeta), or None."""
-    return getattr(getattr(model, "model", model), "_dps", None)
 
 
 def check_zeta(zeta):
@@ -271,21 +342,6 @@ def check_zeta(zeta):
     if not (math.isfinite(z) and z >= 0.0):
         raise ValueError(f"zeta={zeta!r}: the DPS step size must be finite and not negative")
     return z
-
-
-def _refuse_dps(model, what):
-    if _dps(model) is not None:
-        raise _lib.VdError(f"{what} inside dps_scope is not served")
-
-
-def _loss_guidance(model):
-    """The setting the innermost loss_guidance_scope set on this model (dict loss_fn, cotangent_fn, scale, normalize), or None."""
-    return getattr(getattr(model, "model", model), "_loss_guidance", None)
-
-
-def _refuse_loss_guidance(model, what):
-    if _loss_guidance(model) is not None:
-        raise _lib.VdError(f"{what} inside loss_guidance_scope is not served")
 
 
 def _scale_number(v, what="scale"):
@@ -321,6 +377,31 @@ def loss_guidance_step_scale(scale, t, B):
             raise ValueError(f"loss_guidance_scope: scale(t)={v.tolist()!r}: every step size must be finite and not negative")
         return v.contiguous()
     return th.full((B,), _scale_number(v, "scale(t)" if callable(scale) else "scale"), dtype=th.float32)
+
+
+def _cfg_scope_or_null(diffusion, model, cfg_scale):
+    return diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()
+
+
+def _sampler_step(diffusion, sampler, model, x, t, carry=None, cfg_scale=1.0, eta=0.0, philox=None, **step_kw):
+    """One step of SAMPLERS[sampler] through `diffusion`'s public step method, as every loop makes it -> (the step's dict, what the next
+    step of the chain is handed as `carry`; None in front of a chain's first step and behind a jump).  The row says where eta, cfg_scale and
+    the carried value go: a step without the cfg_scale keyword keeps the parameter list it was introduced with and takes its scale from
+    cfg_scale_scope.  philox = (seed, offset): the step's noise from the engine's Philox stream (_dpmpp_2m_sde).  step_kw: clip_denoised,
+    model_kwargs and whatever else the step takes."""
+    row = SAMPLERS[sampler]
+    if row.eta:
+        step_kw["eta"] = eta
+    if row.cfg_keyword:
+        out = getattr(diffusion, row.step)(model, x, t, cfg_scale=cfg_scale, **step_kw)
+    else:
+        with _cfg_scope_or_null(diffusion, model, cfg_scale):
+            if philox is not None:
+                out = diffusion._dpmpp_2m_sde(model, x, t, carry, step_kw["clip_denoised"], step_kw.get("denoised_fn"), step_kw["model_kwargs"],
+                                              philox=philox)
+            else:
+                out = getattr(diffusion, row.step)(model, x, t, **({row.carry: carry} if row.carry else {}), **step_kw)
+    return out, (out["pred_xstart"] if row.carry == "prev_xstart" else out["state"] if row.carry == "state" else None)
 
 
 class GaussianDiffusion:
@@ -487,7 +568,6 @@ class GaussianDiffusion:
         phi, p = _check_guidance(cfg_rescale, dynamic_threshold)
         return _guidance_scope(self._bind(model), phi, p)
 
-    @contextlib.contextmanager
     def known_region_scope(self, model, known_src, known_mask, known_noise=None):
         """This project's extension (RePaint, Lugmayr et al. 2022): `with diffusion.known_region_scope(model, known_src, known_mask):`
         -- pixel-mask inpainting.  Every p_sample, ddim_sample, dpmpp_2m_sample and dpmpp_2m_sde_sample call inside, and so every loop built on them, ends in
@@ -507,16 +587,8 @@ class GaussianDiffusion:
         region = dict(src=_f32(src, base.device), mask=_f32(mask, base.device),
                       noise=None if known_noise is None else _f32(known_noise, base.device))
         assert region["noise"] is None or region["noise"].shape == region["src"].shape
-        before = _known(base)
-        base._known_region = region
-        try:
-            _engine_region(base, region)
-            yield
-        finally:
-            base._known_region = before
-            _engine_region(base, before)
+        return _scoped(base, "known_region", region, _engine_region)
 
-    @contextlib.contextmanager
     def measurement_scope(self, model, y, scale=1, gray=False):
         """This project's extension (DDNM, Wang, Yu, Zhang 2022): `with diffusion.measurement_scope(model, y, scale=4):` -- zero-shot
         restoration from a degraded copy of the video.  y = measure(video, scale, gray), (B, T, Cy, H / scale, W / scale): the mean over
@@ -539,16 +611,8 @@ class GaussianDiffusion:
             raise ValueError(f"y must be a (B, T, Cy, H / scale, W / scale) tensor, got {tuple(getattr(y, 'shape', ()))}")
         B, T, Cy, Hs, Ws = y.shape
         m = dict(y=_f32(check_measurement(y, (B, T, 3, Hs * scale, Ws * scale), scale, gray), base.device), scale=scale, gray=gray)
-        before = _measurement(base)
-        base._measurement = m
-        try:
-            _engine_measurement(base, m)
-            yield
-        finally:
-            base._measurement = before
-            _engine_measurement(base, before)
+        return _scoped(base, "measurement", m, _engine_measurement)
 
-    @contextlib.contextmanager
     def dps_scope(self, model, y, scale=1, gray=False, *, zeta):
         """This project's extension (DPS: Chung, Kim, McCann, Klasky, Ye, ICLR 2023): `with diffusion.dps_scope(model, y, scale=4,
         zeta=0.5):` -- restoration from a NOISY degraded copy of the video.  y, scale and gray are measurement_scope's (y =
@@ -573,47 +637,53 @@ class GaussianDiffusion:
         B, T, Cy, Hs, Ws = y.shape
         d = dict(y=_f32(check_measurement(y, (B, T, 3, Hs * scale, Ws * scale), scale, gray), base.device), scale=scale, gray=gray,
                  zeta=zeta)
-        before = _dps(base)
-        base._dps = d
-        try:
-            yield
-        finally:
-            base._dps = before
+        return _scoped(base, "dps", d)
+
+    def _moved_step_window(self, scope, model, x, t, denoised_fn, model_kwargs, return_attn_weights, use_gradient_method, cfg_scale):
+        """The opening of a step inside dps_scope / loss_guidance_scope (`scope`: 'dps' / 'loss_guidance'), which runs the plain step and then
+        moves the latent frames: every refusal by name, around _prepare -> (the scope's setting, base, xs, tt, kw)."""
+        if self.model_mean_type != ModelMeanType.EPSILON:
+            raise NotImplementedError(f"{scope}_scope with predict_xstart=True: epsilon-prediction models only")
+        for flag, what in ((denoised_fn is not None, "denoised_fn"), (use_gradient_method, "use_gradient_method"),
+                           (return_attn_weights, "return_attn_weights"), (cfg_scale != 1.0, "cfg_scale != 1")):
+            if flag:
+                _refuse(model, scope, what)
+        base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
+        L = _lib.lib()
+        if L.vd_cfg_scale(base._handle) != 1.0:
+            _refuse(base, scope, "cfg_scale != 1 (cfg_scale_scope)")
+        if L.vd_guidance_rescale(base._handle) != 0.0 or L.vd_dynamic_threshold(base._handle) != 0.0:
+            _refuse(base, scope, "guidance_scope with cfg_rescale or dynamic_threshold set")
+        for other in list(_SCOPES)[:list(_SCOPES).index(scope)]:
+            if _scope(base, other) is not None:
+                _refuse(base, scope, f"{other}_scope")
+        return _scope(model, scope), base, xs, tt, kw
+
+    @staticmethod
+    def _moved_step_tensors(base, xs, noise):
+        """... and behind the scope's own check of the step: the backward image, the sampler noise -- drawn once, where the plain step
+        draws it -- and the outputs -> (noise, sample, xstart, grad)."""
+        base._require_guidance()
+        noise = th.randn_like(xs) if noise is None else _f32(noise, base.device)
+        assert noise.shape == xs.shape
+        return noise, th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
 
     def _dps_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
                   use_gradient_method, cfg_scale):
         """One p_sample (mode 0) / ddim_sample (mode 1) step inside dps_scope -> dict sample, pred_xstart, grad, residual_norm."""
-        d = _dps(model)
-        if self.model_mean_type != ModelMeanType.EPSILON:
-            raise NotImplementedError("dps_scope with predict_xstart=True: epsilon-prediction models only")
-        for flag, what in ((denoised_fn is not None, "denoised_fn"), (use_gradient_method, "use_gradient_method"),
-                           (return_attn_weights, "return_attn_weights"), (cfg_scale != 1.0, "cfg_scale != 1")):
-            if flag:
-                _refuse_dps(model, what)
-        base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        L = _lib.lib()
-        if L.vd_cfg_scale(base._handle) != 1.0:
-            _refuse_dps(base, "cfg_scale != 1 (cfg_scale_scope)")
-        if L.vd_guidance_rescale(base._handle) != 0.0 or L.vd_dynamic_threshold(base._handle) != 0.0:
-            _refuse_dps(base, "guidance_scope with cfg_rescale or dynamic_threshold set")
-        if _known(base) is not None:
-            _refuse_dps(base, "known_region_scope")
-        if _measurement(base) is not None:
-            _refuse_dps(base, "measurement_scope")
+        d, base, xs, tt, kw = self._moved_step_window("dps", model, x, t, denoised_fn, model_kwargs, return_attn_weights, use_gradient_method,
+                                                      cfg_scale)
         if tuple(d["y"].shape) != measurement_shape(xs.shape, d["scale"], d["gray"]):
             raise ValueError(f"dps_scope: y {tuple(d['y'].shape)} against a step on {tuple(xs.shape)} at scale={d['scale']}, gray={d['gray']}")
-        base._require_guidance()
-        noise = th.randn_like(xs) if noise is None else _f32(noise, base.device)
-        assert noise.shape == xs.shape
+        noise, sample, xstart, grad = self._moved_step_tensors(base, xs, noise)
         B, T = xs.shape[:2]
-        sample, xstart, grad = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
+        L = _lib.lib()
         rho = th.empty(B, dtype=th.float32, device=base.device)
         _lib.check(L.vd_dps_step(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0,
                                  mode, float(eta), _lib.ptr(noise), _lib.ptr(d["y"]), d["scale"], 1 if d["gray"] else 0, d["zeta"],
                                  _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
         return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
 
-    @contextlib.contextmanager
     def loss_guidance_scope(self, model, loss_fn=None, *, cotangent_fn=None, scale, normalize=False):
         """This project's extension: `with diffusion.loss_guidance_scope(model, loss_fn, scale=s):` -- every p_sample and ddim_sample call
         inside, and every loop built on them, runs the plain step and then moves the frames with latent_mask == 1 down the gradient, with
@@ -649,38 +719,17 @@ class GaussianDiffusion:
         base = self._bind(model)
         scale = check_loss_guidance(loss_fn, cotangent_fn, scale)
         d = dict(loss_fn=loss_fn, cotangent_fn=cotangent_fn, scale=scale, normalize=bool(normalize))
-        before = _loss_guidance(base)
-        base._loss_guidance = d
-        try:
-            yield
-        finally:
-            base._loss_guidance = before
+        return _scoped(base, "loss_guidance", d)
 
     def _loss_guidance_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
                             use_gradient_method, cfg_scale):
         """One p_sample (mode 0) / ddim_sample (mode 1) step inside loss_guidance_scope -> dict sample, pred_xstart, grad[, grad_norm]."""
-        d = _loss_guidance(model)
-        if self.model_mean_type != ModelMeanType.EPSILON:
-            raise NotImplementedError("loss_guidance_scope with predict_xstart=True: epsilon-prediction models only")
-        for flag, what in ((denoised_fn is not None, "denoised_fn"), (use_gradient_method, "use_gradient_method"),
-                           (return_attn_weights, "return_attn_weights"), (cfg_scale != 1.0, "cfg_scale != 1")):
-            if flag:
-                _refuse_loss_guidance(model, what)
-        base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        L = _lib.lib()
-        if L.vd_cfg_scale(base._handle) != 1.0:
-            _refuse_loss_guidance(base, "cfg_scale != 1 (cfg_scale_scope)")
-        if L.vd_guidance_rescale(base._handle) != 0.0 or L.vd_dynamic_threshold(base._handle) != 0.0:
-            _refuse_loss_guidance(base, "guidance_scope with cfg_rescale or dynamic_threshold set")
-        for on, what in ((_known(base), "known_region_scope"), (_measurement(base), "measurement_scope"), (_dps(base), "dps_scope")):
-            if on is not None:
-                _refuse_loss_guidance(base, what)
+        d, base, xs, tt, kw = self._moved_step_window("loss_guidance", model, x, t, denoised_fn, model_kwargs, return_attn_weights,
+                                                      use_gradient_method, cfg_scale)
         B, T = xs.shape[:2]
         scale = loss_guidance_step_scale(d["scale"], tt, B).to(base.device)
-        base._require_guidance()
-        noise = th.randn_like(xs) if noise is None else _f32(noise, base.device)
-        assert noise.shape == xs.shape
-        sample, xstart, grad = th.empty_like(xs), th.empty_like(xs), th.empty_like(xs)
+        noise, sample, xstart, grad = self._moved_step_tensors(base, xs, noise)
+        L = _lib.lib()
         norm = th.empty(B, dtype=th.float32, device=base.device) if d["normalize"] else None
         stream = _lib.current_stream()
         ticket = ctypes.c_ulonglong(0)
@@ -757,27 +806,24 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         self._last_dps = None
-        if _loss_guidance(model) is not None:                      # ... inside loss_guidance_scope: the plain step, the caller's function, the move
-            self._last_dps = self._loss_guidance_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
-                                                      return_attn_weights, use_gradient_method, cfg_scale)
-            return self._last_dps["sample"], self._last_dps["pred_xstart"]
-        if _dps(model) is not None:                                # p_sample / ddim_sample inside dps_scope: the plain step, then the DPS move
-            self._last_dps = self._dps_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
-                                            use_gradient_method, cfg_scale)
-            return self._last_dps["sample"], self._last_dps["pred_xstart"]
+        for scope, step in (("loss_guidance", self._loss_guidance_step), ("dps", self._dps_step)):
+            if _scope(model, scope) is not None:                   # p_sample / ddim_sample inside the scope: the plain step, then the scope's move
+                self._last_dps = step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                                      use_gradient_method, cfg_scale)
+                return self._last_dps["sample"], self._last_dps["pred_xstart"]
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
-            _refuse_known(model, "use_gradient_method")
-            _refuse_measurement(model, "use_gradient_method")
+            _refuse(model, "known_region", "use_gradient_method")
+            _refuse(model, "measurement", "use_gradient_method")
             if mode != 0 or denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method: p_sample without denoised_fn (the reference's ddim_sample "
                                           "has no such option, gaussian_diffusion.py:597-634)")
             out = self._guided(model, x, t, clip_denoised, model_kwargs, noise2=noise, want_sample=True)
             return out["sample"], out["pred_xstart"]
         if denoised_fn is not None:
-            _refuse_known(model, "denoised_fn")
-            _refuse_measurement(model, "denoised_fn")
+            _refuse(model, "known_region", "denoised_fn")
+            _refuse(model, "measurement", "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise,
                                  cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
@@ -785,57 +831,43 @@ class GaussianDiffusion:
         return self._fused_step(mode, model, x, t, clip_denoised, model_kwargs, eta=eta, noise=noise,
                                 return_attn_weights=return_attn_weights, cfg_scale=cfg_scale)
 
-    # per sampler (the engine's numbering: 0 p_sample, 1 ddim_sample, 2 ddim_reverse_sample, 3 dpmpp_2m_sample, 4 dpmpp_2m_sde_sample): the fused step's
-    # entry, and the network-free one that finishes a step through denoised_fn
-    _ENTRIES = {0: ("vd_p_sample", "vd_posterior_from_xstart"), 1: ("vd_ddim_sample", "vd_posterior_from_xstart"),
-                2: ("vd_ddim_reverse_sample", "vd_ddim_reverse_from_xstart"), 3: ("vd_dpmpp_2m_sample", "vd_dpmpp_2m_from_xstart"),
-                4: ("vd_dpmpp_2m_sde_sample", "vd_dpmpp_2m_sde_from_xstart")}
-
     def _fused_step(self, mode, model, x, t, clip_denoised, model_kwargs, eta=0.0, noise=None, prev_xstart=None,
-                    return_attn_weights=None, cfg_scale=1.0, philox=None):
-        """One step of sampler `mode` as one engine call -> (sample, pred_xstart), fresh tensors.  Samplers 0, 1 and 4 read `noise`
-        (drawn from the global generator when None, even for eta = 0: gaussian_diffusion.py:438 / :628), samplers 3 and 4 their
-        `prev_xstart` or None; sampler 2 draws and reads nothing.  philox = (seed, offset), sampler 4 only: no noise tensor -- the pass
-        draws element i from the engine's Philox stream at that state, as a window graph does.  return_attn_weights True / False sets self._last_attn (None leaves it alone)."""
+                    return_attn_weights=None, cfg_scale=1.0, philox=None, state=None):
+        """One step of sampler `mode` (SAMPLERS' id) as one engine call -> (sample, pred_xstart), fresh tensors; sampler 5 (unipc_sample) ->
+        (sample, pred_xstart, state).  Samplers 0, 1 and 4 read `noise` (_step_noise), samplers 3 and 4 their `prev_xstart` or None, sampler 5
+        its `state` or None; sampler 2 draws and reads nothing.  philox = (seed, offset), sampler 4 only, in place of a noise tensor.
+        return_attn_weights True / False sets self._last_attn (None leaves it alone)."""
+        row = _BY_ID[mode]
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-        if mode in (0, 1, 4) and philox is None:
-            noise = th.randn_like(xs) if noise is None else _f32(noise, model.device)
-            assert noise.shape == xs.shape
-        assert philox is None or (mode == 4 and noise is None)
-        seed, offset = (0, 0) if philox is None else (int(philox[0]), int(philox[1]))
-        prev = None if prev_xstart is None else _f32(prev_xstart, model.device)
-        assert prev is None or prev.shape == xs.shape
-        region = _known(model)
+        noise = _step_noise(row, xs, noise, philox)
+        region = _scope(model, "known_region")
         if region is not None:
-            if mode == 2:
-                raise NotImplementedError("ddim_reverse_sample inside known_region_scope is not served")
+            if not row.known_region:
+                raise NotImplementedError(f"{row.step} inside known_region_scope is not served")
             if region["src"].shape != xs.shape:
                 raise ValueError(f"known_region_scope: known_src {tuple(region['src'].shape)} against a step on {tuple(xs.shape)}")
             known_noise = region["noise"] if region["noise"] is not None else th.randn_like(xs)    # behind the sampler's own draw
-        if mode == 2:
-            _refuse_measurement(model, "ddim_reverse_sample")
+        if row.up:
+            _refuse(model, "measurement", row.step)
         _check_step_measurement(model, xs.shape)
         sample, xstart = th.empty_like(xs), th.empty_like(xs)
         B, T = xs.shape[:2]
-        window = (model._handle, B, T, *model._window_ptrs(xs, kw), _lib.ptr(tt))
-        flags = (kw["obs_mode"], 1 if clip_denoised else 0)
-        own = {0: (*flags, _lib.ptr(noise), 0, 0), 1: (*flags, float(eta), _lib.ptr(noise), 0, 0), 2: flags, 3: (_lib.ptr(prev), *flags),
-               4: (_lib.ptr(prev), *flags, _lib.ptr(noise), seed, offset)}[mode]
+        args, state = _entry_args(row, (model._handle, B, T, *model._window_ptrs(xs, kw), tt), xs, (kw["obs_mode"], 1 if clip_denoised else 0),
+                                  (float(eta),) if row.eta else (), noise, (sample, xstart, None), prev_xstart, state)
         if return_attn_weights is not None:
             self._last_attn = model._attn_capture(B, T) if return_attn_weights else None     # unet.py:457-466 per block
         try:
             if region is not None:
                 _engine_region(model, region, known_noise)
             with _cfg_scope(model, cfg_scale):
-                rc = getattr(_lib.lib(), self._ENTRIES[mode][0])(*window, *own, _lib.ptr(sample), _lib.ptr(xstart), None,
-                                                                 _lib.current_stream())
+                rc = getattr(_lib.lib(), row.fused)(*_ptrs(args), _lib.current_stream())
         finally:
             if region is not None:
                 _engine_region(model, region)
             if return_attn_weights:
                 model._attn_release()
         _lib.check(rc)
-        return sample, xstart
+        return (sample, xstart) if state is None else (sample, xstart, state)
 
     def _guided(self, model, x, t, clip_denoised, model_kwargs, noise2=None, want_sample=False, _noise=None):
         """p_mean_variance(..., use_gradient_method=True) (+ p_sample's noise add) on the engine: one taped forward, the
@@ -861,14 +893,14 @@ class GaussianDiffusion:
         return {"mean": mean, "pred_xstart": xstart, "grad": grad, "sample": sample}
 
     def _denoised(self, model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode=None, eta=0.0, noise=None,
-                  prev_xstart=None, cfg_scale=1.0, philox=None):
+                  prev_xstart=None, cfg_scale=1.0, philox=None, state=None):
         """process_xstart with a caller's function (gaussian_diffusion.py:319-324): `denoised_fn` sees the UNCLIPPED x_0
         prediction, the clamp and the posterior run on what it returns.  Two launches around a host callback instead of
-        the fused step: forward + x_0 (vd_p_mean_variance, clip off), then vd_posterior_from_xstart -- the posterior mean
-        (p_mean_variance), or with a sampler `mode` (0 p_sample, 1 ddim_sample) its sample; mode 2 (ddim_reverse_sample) ends
-        in vd_ddim_reverse_from_xstart and draws no noise; mode 3 (dpmpp_2m_sample, with its `prev_xstart` or None) ends in
-        vd_dpmpp_2m_from_xstart and draws none either; mode 4 (dpmpp_2m_sde_sample) ends in vd_dpmpp_2m_sde_from_xstart with its
-        `prev_xstart` and `noise` (drawn here when None, behind the callback, as for modes 0 and 1).  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
+        the fused step: forward + x_0 (vd_p_mean_variance, clip off), then the sampler's network-free entry (SAMPLERS' from_xstart) --
+        vd_posterior_from_xstart gives the posterior mean (p_mean_variance, mode None), or with a sampler `mode` (0 p_sample, 1 ddim_sample)
+        its sample; the other samplers' entries take what the fused step takes: `prev_xstart` or None (3, 4), `state` or None (5, whose
+        new state comes back under 'state'), and the noise (4: `noise` or philox, as _step_noise; 0, 1: `noise`) is drawn here when None,
+        behind the callback; 2 and 3 draw none.  cfg_scale acts inside p_mean_variance: the x_0 prediction `denoised_fn` sees is
         the guided one, the passes behind it run no network.  dynamic_threshold (guidance_scope) would have to run between the
         callback and those passes: refused."""
         if clip_denoised and _lib.lib().vd_dynamic_threshold(self._bind(model)._handle) != 0.0:
@@ -883,25 +915,15 @@ class GaussianDiffusion:
         assert x0.shape == xs.shape
         tt = t.to(device=dev, dtype=th.int64).contiguous()
         out.update({"sample" if mode is not None else "mean": th.empty_like(xs), "pred_xstart": th.empty_like(xs)})
-        head = (base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0))
-        clip = 1 if clip_denoised else 0
-        if mode in (2, 3, 4):
-            prev = None if prev_xstart is None else _f32(prev_xstart, dev)
-            assert prev is None or prev.shape == xs.shape
-            own = (_lib.ptr(tt), clip) if mode == 2 else (_lib.ptr(prev), _lib.ptr(tt), clip)
-            if mode == 4 and philox is not None:                   # (seed, offset): the pass draws from the engine's Philox stream
-                own = (*own, None, int(philox[0]), int(philox[1]))
-            elif mode == 4:
-                noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
-                assert noise.shape == xs.shape
-                own = (*own, _lib.ptr(noise), 0, 0)
-            args = (*head, *own, _lib.ptr(out["sample"]), _lib.ptr(out["pred_xstart"]))
-        else:
-            if mode is not None:
-                noise = th.randn_like(xs) if noise is None else _f32(noise, dev)
-            args = (base._handle, mode or 0, *head[1:], _lib.ptr(tt), clip, float(eta), _lib.ptr(noise), 0, 0, _lib.ptr(out.get("sample")),
-                    _lib.ptr(out["pred_xstart"]), _lib.ptr(out["mean"] if mode is None else None))
-        _lib.check(getattr(_lib.lib(), self._ENTRIES[mode or 0][1])(*args, _lib.current_stream()))
+        row = _BY_ID[mode or 0]
+        posterior = row.id < 2                                     # vd_posterior_from_xstart: the sampler's number in front, eta whatever it is, the mean behind
+        lead = (base._handle, *((row.id,) if posterior else ()), xs.shape[0], xs[0].numel(), xs, x0)
+        outs = (out.get("sample"), out["pred_xstart"], *((out["mean"] if mode is None else None,) if posterior else ()))
+        args, state = _entry_args(row, lead, xs, (tt, 1 if clip_denoised else 0), (float(eta),) if posterior else (),
+                                  _step_noise(row, xs, noise, philox) if mode is not None else (None, 0, 0), outs, prev_xstart, state)
+        _lib.check(getattr(_lib.lib(), row.from_xstart)(*_ptrs(args), _lib.current_stream()))
+        if state is not None:
+            out["state"] = state
         return out
 
     def _variance(self, t, shape):
@@ -928,8 +950,8 @@ class GaussianDiffusion:
         if return_attn_weights and use_gradient_method:
             raise NotImplementedError("return_attn_weights together with use_gradient_method")
         if use_gradient_method:
-            _refuse_known(model, "use_gradient_method")
-            _refuse_measurement(model, "use_gradient_method")
+            _refuse(model, "known_region", "use_gradient_method")
+            _refuse(model, "measurement", "use_gradient_method")
             if denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method with denoised_fn")
             g = self._guided(model, x, t, clip_denoised, model_kwargs or {}, _noise=getattr(self, "_guidance_noise", None))
@@ -937,7 +959,7 @@ class GaussianDiffusion:
             return {"mean": g["mean"], **self._variance(tt, g["mean"].shape), "pred_xstart": g["pred_xstart"], "attn": None,
                     "grad": g["grad"]}
         if denoised_fn is not None:
-            _refuse_measurement(model, "denoised_fn")
+            _refuse(model, "measurement", "denoised_fn")
             return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, cfg_scale=cfg_scale)
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs or {})
         _check_step_measurement(model, xs.shape)
@@ -1037,8 +1059,8 @@ class GaussianDiffusion:
         """What eps_vjp and the ODE likelihood hand the engine: _prepare's tuple with observed_frames defaulting to 'x_0' and x0 to x (as
         video_nll does), `latent_mask` in place of the kwargs' when given, and the backward-data weights on the device.  The scopes that
         live on the Python side (a known region reaches the engine only for the length of a step) are refused here, by name."""
-        _refuse_known(model, what)
-        _refuse_dps(model, what)
+        _refuse(model, "known_region", what)
+        _refuse(model, "dps", what)
         kw_in = dict(model_kwargs or {})
         kw_in.setdefault("observed_frames", "x_0")
         kw_in.setdefault("x0", x)
@@ -1261,18 +1283,26 @@ class GaussianDiffusion:
     def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
         """gaussian_diffusion.py:636-668: x_{t+1} from x_t by the DDIM reverse ODE.  Deterministic: no noise is drawn."""
         assert eta == 0.0, 'Reverse ODE only for deterministic path'
+        return self._scope_step("ddim_reverse", model, x, t, clip_denoised, denoised_fn, model_kwargs)
+
+    def _scope_step(self, sampler, model, x, t, clip_denoised, denoised_fn, model_kwargs, noise=None, philox=None, **carry):
+        """One step of a sampler that takes its cfg_scale from the scope (every one but p_sample and ddim_sample, whose _step serves the
+        scopes these refuse) -> its dict.  `carry`: prev_xstart= or state=, what the row carries."""
+        row = SAMPLERS[sampler]
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
-        _refuse_known(model, "ddim_reverse_sample")
-        _refuse_measurement(model, "ddim_reverse_sample")
-        _refuse_dps(model, "ddim_reverse_sample")
-        _refuse_loss_guidance(model, "ddim_reverse_sample")
+        for scope in (_SCOPES if row.up else ("dps", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
+            _refuse(model, scope, row.step)
+        if not row.known_region:
+            _refuse(model, "known_region", row.step)
         if denoised_fn is not None:
-            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=2)
-            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-        sample, xstart = self._fused_step(2, model, x, t, clip_denoised, model_kwargs)
-        return {"sample": sample, "pred_xstart": xstart}
+            _refuse(model, "known_region", "denoised_fn")
+            _refuse(model, "measurement", "denoised_fn")
+            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=row.id, noise=noise, philox=philox, **carry)
+            return {k: out[k] for k in ("sample", "pred_xstart", "state") if k in out}
+        return dict(zip(("sample", "pred_xstart", "state"),
+                        self._fused_step(row.id, model, x, t, clip_denoised, model_kwargs, noise=noise, philox=philox, **carry)))
 
     def dpmpp_2m_sample(self, model, x, t, prev_xstart=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """This project's extension (the reference has no such sampler): one step x_t -> x_{t-1} of DPM-Solver++(2M), the
@@ -1281,18 +1311,7 @@ class GaussianDiffusion:
         D = pred_xstart + w[t] (pred_xstart - prev_xstart), without it (a chain's first step) on pred_xstart itself, and is
         then ddim_sample's with eta = 0 (_multistep_weights; include/vd_amd.h: vd_dpmpp_2m_sample).  No noise is drawn.  Meant for
         timestep_respacing='logsnrN'; with 'ddimN' at small N first-order ddim_sample can be the better choice."""
-        if model_kwargs is None:
-            model_kwargs = {}
-        self._refuse_learned(x)
-        _refuse_dps(model, "dpmpp_2m_sample")
-        _refuse_loss_guidance(model, "dpmpp_2m_sample")
-        if denoised_fn is not None:
-            _refuse_known(model, "denoised_fn")
-            _refuse_measurement(model, "denoised_fn")
-            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=3, prev_xstart=prev_xstart)
-            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-        sample, xstart = self._fused_step(3, model, x, t, clip_denoised, model_kwargs, prev_xstart=prev_xstart)
-        return {"sample": sample, "pred_xstart": xstart}
+        return self._scope_step("dpmpp_2m", model, x, t, clip_denoised, denoised_fn, model_kwargs, prev_xstart=prev_xstart)
 
     def dpmpp_2m_sde_sample(self, model, x, t, prev_xstart=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """This project's extension (the reference has no such sampler): one step x_t -> x_{t-1} of SDE-DPM-Solver++(2M) (Lu et al.
@@ -1309,19 +1328,7 @@ class GaussianDiffusion:
         """dpmpp_2m_sde_sample with the step's noise handed in: `noise` (None: drawn from the global generator), or philox =
         (seed, offset) -- the pass then draws from the engine's Philox stream at that state, which is how infer_video's eager loop
         repeats a window graph's draws."""
-        if model_kwargs is None:
-            model_kwargs = {}
-        self._refuse_learned(x)
-        _refuse_dps(model, "dpmpp_2m_sde_sample")
-        _refuse_loss_guidance(model, "dpmpp_2m_sde_sample")
-        if denoised_fn is not None:
-            _refuse_known(model, "denoised_fn")
-            _refuse_measurement(model, "denoised_fn")
-            out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=4, noise=noise, prev_xstart=prev_xstart,
-                                 philox=philox)
-            return {"sample": out["sample"], "pred_xstart": out["pred_xstart"]}
-        sample, xstart = self._fused_step(4, model, x, t, clip_denoised, model_kwargs, noise=noise, prev_xstart=prev_xstart, philox=philox)
-        return {"sample": sample, "pred_xstart": xstart}
+        return self._scope_step("dpmpp_2m_sde", model, x, t, clip_denoised, denoised_fn, model_kwargs, noise, philox, prev_xstart=prev_xstart)
 
     def unipc_sample(self, model, x, t, state=None, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """This project's extension (the reference has no such sampler): one step x~_t -> x~_{t-1} of UniPC (Zhao et al. 2023) in its
@@ -1336,44 +1343,7 @@ class GaussianDiffusion:
         its own, a merge behind the pass would be discarded), dps_scope and a learned variance.  Meant for
         timestep_respacing='logsnrN' with N of 20 or more: at logsnr10 (h near 1) dpmpp_2m_sample is the better choice.
         Returns {'sample', 'pred_xstart', 'state'}."""
-        if model_kwargs is None:
-            model_kwargs = {}
-        self._refuse_learned(x)
-        _refuse_dps(model, "unipc_sample")
-        _refuse_loss_guidance(model, "unipc_sample")
-        _refuse_known(model, "unipc_sample")
-        base = self._bind(model)
-        dev = base.device
-        if state is None:
-            tensors, count = (None, None, None), 0
-        else:
-            tensors, count = tuple(_f32(v, dev) for v in state[:3]), int(state[3])
-            assert all(v.shape == x.shape for v in tensors) and count >= 0
-        if denoised_fn is not None:
-            _refuse_measurement(model, "denoised_fn")
-            if clip_denoised and _lib.lib().vd_dynamic_threshold(base._handle) != 0.0:
-                raise NotImplementedError("denoised_fn together with dynamic_threshold (guidance_scope): the threshold replaces the clamp "
-                                          "of the fused step, which a step through denoised_fn does not run")
-            head = self.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=model_kwargs)
-            xs = _f32(x, dev)
-            x0 = _f32(denoised_fn(head["pred_xstart"]), dev)
-            assert x0.shape == xs.shape
-            tt = t.to(device=dev, dtype=th.int64).contiguous()
-            sample, xstart, new = th.empty_like(xs), th.empty_like(xs), tuple(th.empty_like(xs) for _ in range(3))
-            _lib.check(_lib.lib().vd_unipc_from_xstart(base._handle, xs.shape[0], xs[0].numel(), _lib.ptr(xs), _lib.ptr(x0),
-                                                       *(_lib.ptr(v) for v in tensors), count, _lib.ptr(tt), 1 if clip_denoised else 0,
-                                                       _lib.ptr(sample), _lib.ptr(xstart), *(_lib.ptr(v) for v in new),
-                                                       _lib.current_stream()))
-        else:
-            base, xs, tt, kw = self._prepare(model, x, t, model_kwargs)
-            _check_step_measurement(base, xs.shape)
-            sample, xstart, new = th.empty_like(xs), th.empty_like(xs), tuple(th.empty_like(xs) for _ in range(3))
-            B, T = xs.shape[:2]
-            _lib.check(_lib.lib().vd_unipc_sample(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt),
-                                                  *(_lib.ptr(v) for v in tensors), count, kw["obs_mode"], 1 if clip_denoised else 0,
-                                                  _lib.ptr(sample), _lib.ptr(xstart), *(_lib.ptr(v) for v in new), None,
-                                                  _lib.current_stream()))
-        return {"sample": sample, "pred_xstart": xstart, "state": (*new, count + 1)}
+        return self._scope_step("unipc", model, x, t, clip_denoised, denoised_fn, model_kwargs, state=state)
 
     def q_sample(self, x_start, t, noise=None, model=None):
         """gaussian_diffusion.py:190-206.  Needs an engine for its tables: pass `model` (or call after
@@ -1440,21 +1410,40 @@ class GaussianDiffusion:
                                   return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
         """gaussian_diffusion.py:528-595, including the per-step side draws that consume the global RNG
         (x_t_minus_1, random_t, x_random) so a seeded run walks the generator like the reference."""
-        cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)     # before the first side draw touches the engine
+        yield from self._sample_loop("p_sample", model, shape, noise, device, cfg_scale, side_draws=True, clip_denoised=clip_denoised,
+                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
+                                     use_gradient_method=use_gradient_method)
+
+    def _sample_loop(self, sampler, model, shape, noise, device, cfg_scale=1.0, eta=0.0, side_draws=False, indices=None, **step_kw):
+        """The steps of every *_sample_loop_progressive, one dict per index: sampler `sampler` from `noise` (None: drawn here) over
+        `indices` (default: the last index down to 0), each step handed what the row carries from the one before.  side_draws:
+        p_sample_loop_progressive's draws in front of every step, and the model remembered for q_sample.  step_kw: the step's keywords."""
+        cfg_scale = _check_cfg(cfg_scale, step_kw.get("return_attn_weights", False), step_kw.get("use_gradient_method", False))     # before the first side draw touches the engine
         base = getattr(model, "model", model)
         if device is None:
             device = base.device
         assert isinstance(shape, (tuple, list))
         img = noise if noise is not None else th.randn(*shape, device=device)
-        self._model_hint = base
-        for i in list(range(self.num_timesteps))[::-1]:
+        if side_draws:
+            self._model_hint = base
+        carry = None
+        for i in (list(range(self.num_timesteps))[::-1] if indices is None else indices):
             t = th.tensor([i] * shape[0], device=device)
-            self._loop_side_draws(base, model_kwargs, t, noise, device)
-            out = self.p_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                model_kwargs=model_kwargs, return_attn_weights=return_attn_weights,
-                                use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)
+            if side_draws:
+                self._loop_side_draws(base, step_kw["model_kwargs"], t, noise, device)
+            out, carry = _sampler_step(self, sampler, model, img, t, carry, cfg_scale, eta, **step_kw)
             yield out
             img = out["sample"]
+
+    @staticmethod
+    def _drain(model, steps):
+        """A loop's last step's sample, behind the wait for the device (every stream): a non-finite network output / bad index of ANY step
+        surfaces here, not in a later loop."""
+        final = None
+        for final in steps:
+            pass
+        getattr(model, "check_device_errors", lambda: None)()
+        return final["sample"]
 
     def _loop_side_draws(self, base, model_kwargs, t, noise, device):
         """What p_sample_loop_progressive does before each step (gaussian_diffusion.py:560-573): x_t_minus_1, random_t and x_random's draw."""
@@ -1470,152 +1459,81 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                          latent_mask=None, device=None, progress=False, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:670-700: returns the sample only."""
-        final = None
-        for sample in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                        denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                                                        device=device, progress=progress, eta=eta, cfg_scale=cfg_scale):
-            final = sample
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                    denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                                    device=device, progress=progress, eta=eta, cfg_scale=cfg_scale))
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      model_kwargs=None, latent_mask=None, device=None, progress=False, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:702-748."""
-        cfg_scale = _check_cfg(cfg_scale)
-        base = getattr(model, "model", model)
-        if device is None:
-            device = base.device
-        assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        for i in list(range(self.num_timesteps))[::-1]:
-            t = th.tensor([i] * shape[0], device=device)
-            out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                   model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
-            yield out
-            img = out["sample"]
+        yield from self._sample_loop("ddim", model, shape, noise, device, cfg_scale, eta, clip_denoised=clip_denoised,
+                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs)
 
     def ddim_reverse_sample_loop(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None, t_start=0,
                                  t_end=None, progress=False):
         """This project's extension (the reference has the step, :636-668, and no loop for it): encode `x_start`, taken as
         x_{t_start}, by one ddim_reverse_sample per index t_start..t_end (default: the last index); returns the last sample,
         x_{t_end + 1}.  Shaped like ddim_sample_loop."""
-        final = None
-        for sample in self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                                                model_kwargs=model_kwargs, t_start=t_start, t_end=t_end,
-                                                                progress=progress):
-            final = sample
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.ddim_reverse_sample_loop_progressive(model, x_start, clip_denoised=clip_denoised,
+                                                                            denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                                            t_start=t_start, t_end=t_end, progress=progress))
 
     def ddim_reverse_sample_loop_progressive(self, model, x_start, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                              t_start=0, t_end=None, progress=False):
         """This project's extension: the steps of ddim_reverse_sample_loop, one dict per index, driven from the host like
         ddim_sample_loop_progressive.  model_kwargs are handed to every step as they are: in 'x_t_minus_1' mode the caller's
         tensor is read unchanged (nothing is re-noised: the step draws no noise)."""
-        base = getattr(model, "model", model)
         if t_end is None:
             t_end = self.num_timesteps - 1
         if not 0 <= t_start <= t_end < self.num_timesteps:
             raise IndexError(f"t_start..t_end = {t_start}..{t_end} is outside the schedule of {self.num_timesteps} steps")
-        img = x_start
-        for i in range(t_start, t_end + 1):
-            t = th.tensor([i] * img.shape[0], device=base.device)
-            out = self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                           model_kwargs=model_kwargs)
-            yield out
-            img = out["sample"]
+        yield from self._sample_loop("ddim_reverse", model, tuple(x_start.shape), x_start, None, indices=range(t_start, t_end + 1),
+                                     clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs)
 
     def dpmpp_2m_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                              latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension, shaped like ddim_sample_loop: dpmpp_2m_sample from the last index down to 0, each step handed
         the x_0 prediction of the one before; returns the sample only."""
-        final = None
-        for sample in self.dpmpp_2m_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                            denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                                                            device=device, progress=progress, cfg_scale=cfg_scale):
-            final = sample
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.dpmpp_2m_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                        denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                                        device=device, progress=progress, cfg_scale=cfg_scale))
 
     def dpmpp_2m_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                          model_kwargs=None, latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension: the steps of dpmpp_2m_sample_loop, one dict per index, driven from the host like
         ddim_sample_loop_progressive.  The first step has no history and is first-order."""
-        cfg_scale = _check_cfg(cfg_scale)
-        base = getattr(model, "model", model)
-        if device is None:
-            device = base.device
-        assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        prev = None
-        for i in list(range(self.num_timesteps))[::-1]:
-            t = th.tensor([i] * shape[0], device=device)
-            with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                out = self.dpmpp_2m_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                           model_kwargs=model_kwargs)
-            yield out
-            img, prev = out["sample"], out["pred_xstart"]
+        yield from self._sample_loop("dpmpp_2m", model, shape, noise, device, cfg_scale, clip_denoised=clip_denoised,
+                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs)
 
     def unipc_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                           latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension, shaped like dpmpp_2m_sample_loop (ddim_sample_loop's parameters without eta): unipc_sample from the
         last index down to 0, each step handed the state of the one before; returns the sample only.  Deterministic."""
-        final = None
-        for sample in self.unipc_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                                         model_kwargs=model_kwargs, device=device, progress=progress, cfg_scale=cfg_scale):
-            final = sample
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.unipc_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs, device=device,
+                                                                     progress=progress, cfg_scale=cfg_scale))
 
     def unipc_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                       latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension: the steps of unipc_sample_loop, one dict per index ('sample', 'pred_xstart', 'state'), driven from
         the host like dpmpp_2m_sample_loop_progressive.  The first step has no state: no corrector, a first-order predictor."""
-        cfg_scale = _check_cfg(cfg_scale)
-        base = getattr(model, "model", model)
-        if device is None:
-            device = base.device
-        assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        state = None
-        for i in list(range(self.num_timesteps))[::-1]:
-            t = th.tensor([i] * shape[0], device=device)
-            with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                out = self.unipc_sample(model, img, t, state=state, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                        model_kwargs=model_kwargs)
-            yield out
-            img, state = out["sample"], out["state"]
+        yield from self._sample_loop("unipc", model, shape, noise, device, cfg_scale, clip_denoised=clip_denoised,
+                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs)
 
     def dpmpp_2m_sde_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
                                  latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension, shaped like dpmpp_2m_sample_loop: dpmpp_2m_sde_sample from the last index down to 0, each step
         handed the x_0 prediction of the one before and drawing its noise from the global generator; returns the sample only."""
-        final = None
-        for sample in self.dpmpp_2m_sde_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
-                                                                denoised_fn=denoised_fn, model_kwargs=model_kwargs,
-                                                                device=device, progress=progress, cfg_scale=cfg_scale):
-            final = sample
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.dpmpp_2m_sde_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
+                                                                            denoised_fn=denoised_fn, model_kwargs=model_kwargs,
+                                                                            device=device, progress=progress, cfg_scale=cfg_scale))
 
     def dpmpp_2m_sde_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                              model_kwargs=None, latent_mask=None, device=None, progress=False, cfg_scale=1.0):
         """This project's extension: the steps of dpmpp_2m_sde_sample_loop, one dict per index, driven from the host like
         dpmpp_2m_sample_loop_progressive.  The first step has no history: it is ddim_sample at eta = 1."""
-        cfg_scale = _check_cfg(cfg_scale)
-        base = getattr(model, "model", model)
-        if device is None:
-            device = base.device
-        assert isinstance(shape, (tuple, list))
-        img = noise if noise is not None else th.randn(*shape, device=device)
-        prev = None
-        for i in list(range(self.num_timesteps))[::-1]:
-            t = th.tensor([i] * shape[0], device=device)
-            with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                out = self.dpmpp_2m_sde_sample(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
-                                               model_kwargs=model_kwargs)
-            yield out
-            img, prev = out["sample"], out["pred_xstart"]
+        yield from self._sample_loop("dpmpp_2m_sde", model, shape, noise, device, cfg_scale, clip_denoised=clip_denoised,
+                                     denoised_fn=denoised_fn, model_kwargs=model_kwargs)
 
     def repaint_sample_loop(self, model, shape, known_src, known_mask, sampler="p_sample", jump_length=1, n_resample=1, noise=None,
                             clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
@@ -1625,13 +1543,10 @@ class GaussianDiffusion:
         whose known pixels on the latent frames are known_src to the bit.  sampler: 'p_sample' (with p_sample_loop's per-step side
         draws: n_resample = 1 is p_sample_loop inside the scope), 'ddim' (with `eta`), 'dpmpp_2m' or 'dpmpp_2m_sde' (both first-order
         after a jump)."""
-        final = None
-        for out in self.repaint_sample_loop_progressive(model, shape, known_src, known_mask, sampler=sampler, jump_length=jump_length,
-                                                        n_resample=n_resample, noise=noise, clip_denoised=clip_denoised,
-                                                        model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale, progress=progress):
-            final = out
-        getattr(model, "check_device_errors", lambda: None)()
-        return final["sample"]
+        return self._drain(model, self.repaint_sample_loop_progressive(model, shape, known_src, known_mask, sampler=sampler,
+                                                                       jump_length=jump_length, n_resample=n_resample, noise=noise,
+                                                                       clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta,
+                                                                       cfg_scale=cfg_scale, progress=progress))
 
     def repaint_sample_loop_progressive(self, model, shape, known_src, known_mask, sampler="p_sample", jump_length=1, n_resample=1,
                                         noise=None, clip_denoised=True, model_kwargs=None, eta=0.0, cfg_scale=1.0, progress=False):
@@ -1640,7 +1555,7 @@ class GaussianDiffusion:
         if sampler == "unipc":
             raise NotImplementedError("repaint_sample_loop with sampler='unipc' is not served: unipc_sample's corrector rebuilds the state "
                                       "from its own, the merge of a known region behind the pass would be discarded")
-        if sampler not in ("p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde"):
+        if sampler not in SAMPLERS or not SAMPLERS[sampler].known_region:
             raise ValueError(f"sampler={sampler!r}: 'p_sample', 'ddim', 'dpmpp_2m' or 'dpmpp_2m_sde'")
         ops = repaint_schedule(self.num_timesteps - 1, jump_length, n_resample)
         cfg_scale = _check_cfg(cfg_scale)
@@ -1659,12 +1574,7 @@ class GaussianDiffusion:
                     continue
                 if sampler == "p_sample":
                     self._loop_side_draws(base, model_kwargs, t, noise, device)
-                    out = self.p_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, cfg_scale=cfg_scale)
-                elif sampler == "ddim":
-                    out = self.ddim_sample(model, img, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
-                else:
-                    step = self.dpmpp_2m_sample if sampler == "dpmpp_2m" else self.dpmpp_2m_sde_sample
-                    with (self.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                        out = step(model, img, t, prev_xstart=prev, clip_denoised=clip_denoised, model_kwargs=model_kwargs)
-                img, prev = out["sample"], out["pred_xstart"]
-                yield {"op": op, "t": i, "sample": img, "pred_xstart": prev}
+                out, prev = _sampler_step(self, sampler, model, img, t, prev, cfg_scale, eta, clip_denoised=clip_denoised,
+                                          model_kwargs=model_kwargs)
+                img = out["sample"]
+                yield {"op": op, "t": i, "sample": img, "pred_xstart": out["pred_xstart"]}

@@ -23,7 +23,8 @@ import os
 import numpy as np
 import torch
 
-from . import inference_util
+from . import _lib, inference_util
+from .gaussian_diffusion import SAMPLERS, _check_guidance, _sampler_step, check_loss_guidance, check_measurement, check_zeta
 from .script_util import (args_to_dict, create_video_model_and_diffusion, str2bool,
                           video_model_and_diffusion_defaults)
 from .weights_init import synth_param
@@ -124,43 +125,33 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     executor='graph', prefix_cache, suffix_skip, the samplers 'dpmpp_2m', 'dpmpp_2m_sde' and 'unipc', use_gradient_method, known_mask,
     a measurement, cfg_scale != 1, cfg_rescale and dynamic_threshold.  Both None (default): no scope is entered."""
     loss_guided = loss_fn is not None or cotangent_fn is not None
+    # what a step that moves the latent frames behind the plain step (loss_guidance_scope, dps_scope) is not served with, in the order it is
+    # refused; the three that dps_zeta leaves to the checks of the measurement below are marked
+    moved_step = [("executor='graph'", executor == "graph", False), ("prefix_cache", prefix_cache, False), ("suffix_skip", suffix_skip, False),
+                  *((f"sampler='{s}'", sampler == s, False) for s, row in SAMPLERS.items() if row.carry),       # the multistep samplers
+                  ("use_gradient_method", use_gradient_method, True), ("known_mask", known_mask is not None, True),
+                  ("a measurement", measurement is not None, True), ("cfg_scale != 1", float(cfg_scale) != 1.0, False),
+                  ("cfg_rescale", float(cfg_rescale) != 0.0, False), ("dynamic_threshold", dynamic_threshold is not None, False)]
     if loss_guided or loss_scale is not None:
-        from . import _lib
-        from .gaussian_diffusion import check_loss_guidance
         if loss_scale is None:
             raise ValueError("loss_fn / cotangent_fn need a step size (loss_scale=)")
         loss_scale = check_loss_guidance(loss_fn, cotangent_fn, loss_scale)
-        for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
-                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("sampler='dpmpp_2m_sde'", sampler == "dpmpp_2m_sde"),
-                         ("sampler='unipc'", sampler == "unipc"), ("use_gradient_method", use_gradient_method),
-                         ("known_mask", known_mask is not None), ("a measurement", measurement is not None),
-                         ("cfg_scale != 1", float(cfg_scale) != 1.0),
-                         ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
+        for name, on, _ in moved_step:
             if on:
                 raise _lib.VdError(f"{name} together with loss_fn / cotangent_fn (loss_guidance_scope) is not served")
     if dps_zeta is not None:
-        from . import _lib
-        from .gaussian_diffusion import check_zeta
         dps_zeta = check_zeta(dps_zeta)
         if measurement is None:
             raise ValueError("dps_zeta needs a measurement (measurement=, sr_scale=, gray=)")
-        for name, on in (("executor='graph'", executor == "graph"), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip),
-                         ("sampler='dpmpp_2m'", sampler == "dpmpp_2m"), ("sampler='dpmpp_2m_sde'", sampler == "dpmpp_2m_sde"),
-                         ("sampler='unipc'", sampler == "unipc"),
-                         ("cfg_scale != 1", float(cfg_scale) != 1.0),
-                         ("cfg_rescale", float(cfg_rescale) != 0.0), ("dynamic_threshold", dynamic_threshold is not None)):
-            if on:
+        for name, on, left_to_measurement in moved_step:
+            if on and not left_to_measurement:
                 raise _lib.VdError(f"{name} together with dps_zeta is not served")
-    if sampler == "dpmpp_2m_sde" and use_gradient_method:
-        raise NotImplementedError("sampler='dpmpp_2m_sde' together with use_gradient_method")
-    if sampler == "unipc" and use_gradient_method:
-        raise NotImplementedError("sampler='unipc' together with use_gradient_method")
+    if sampler in ("dpmpp_2m_sde", "unipc") and use_gradient_method:
+        raise NotImplementedError(f"sampler='{sampler}' together with use_gradient_method")
     if sampler == "unipc" and known_mask is not None:
         raise NotImplementedError("sampler='unipc' together with known_mask: the corrector rebuilds the state from its own, the merge of a "
                                   "known region behind the pass would be discarded")
     if measurement is not None:
-        from . import _lib
-        from .gaussian_diffusion import check_measurement
         measurement_v = check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray).cpu()   # before anything touches the engine
         if known_mask is not None:
             raise _lib.VdError("a measurement together with a known region (known_mask) is not served")
@@ -176,7 +167,6 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         repaint_schedule(diffusion.num_timesteps - 1, jump_length, n_resample)     # the range checks, before anything touches the engine
         known_mask_v, known_video_v = video_known_region(batch, known_mask, known_video)
     if float(cfg_rescale) != 0.0 or dynamic_threshold is not None:
-        from .gaussian_diffusion import _check_guidance
         _check_guidance(cfg_rescale, dynamic_threshold)                     # before anything touches the engine
         for name, on in (("use_gradient_method", use_gradient_method), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
             if on:
@@ -187,6 +177,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                                executor=executor, adaptive_distance=adaptive_distance, prefix_cache=prefix_cache, suffix_skip=suffix_skip,
                                save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
                                jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray)
+    step_sampler = sampler if sampler in SAMPLERS and not SAMPLERS[sampler].up else "ddim"    # (the eager step: any other name is ddim_sample)
     adaptive = "adaptive" in mode
     B, T, C, H, W = batch.shape
     device = model.device
@@ -261,16 +252,17 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             model.check_device_errors()
             continue
         if known_mask is not None:
-            local_samples, trace = _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampler, eta, cfg_scale, jump_length,
+            local_samples, trace = _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, step_sampler, eta, cfg_scale, jump_length,
                                                        n_resample, save_all_timesteps)
             write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
             model.check_device_errors()
             continue
         local_samples = x0.clone()
         trace = [] if save_all_timesteps else None
-        prev_xstart = None                                  # dpmpp_2m, dpmpp_2m_sde: the history is the window's own
-        unipc_state = None                                  # ... and so is unipc's state
-        if sampler == "dpmpp_2m_sde":                       # ... and the noise what the window executor would draw (its seed, its ranges)
+        carry = None                                        # dpmpp_2m, dpmpp_2m_sde: the history is the window's own; and so is unipc's state
+        step_kw = dict(return_attn_weights=False, use_gradient_method=use_gradient_method) if sampler == "p_sample" else {}
+        sde_seed = None
+        if SAMPLERS[step_sampler].noise == "philox":        # ... and the noise what the window executor would draw (its seed, its ranges)
             sde_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         if loss_guided:
             scope = diffusion.loss_guidance_scope(model, loss_fn, cotangent_fn=cotangent_fn, scale=loss_scale, normalize=loss_normalize)
@@ -282,30 +274,10 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             scope = diffusion.measurement_scope(model, y_w, sr_scale, gray)
         with scope:
             for timestep in timesteps:
-                if sampler == "dpmpp_2m":
-                    # (the step keeps the parameter list it was introduced with: its scale comes from the scope)
-                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                        out = diffusion.dpmpp_2m_sample(model, local_samples, t=t_tensors[timestep], prev_xstart=prev_xstart, clip_denoised=True,
-                                                        model_kwargs=model_kwargs)
-                    local_samples, prev_xstart = out["sample"], out["pred_xstart"]
-                elif sampler == "dpmpp_2m_sde":
-                    k = diffusion.num_timesteps - 1 - timestep
-                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                        out = diffusion._dpmpp_2m_sde(model, local_samples, t_tensors[timestep], prev_xstart, True, None, model_kwargs,
-                                                      philox=(sde_seed, k * local_samples.numel()))
-                    local_samples, prev_xstart = out["sample"], out["pred_xstart"]
-                elif sampler == "unipc":
-                    with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                        out = diffusion.unipc_sample(model, local_samples, t_tensors[timestep], state=unipc_state, clip_denoised=True,
-                                                     model_kwargs=model_kwargs)
-                    local_samples, unipc_state = out["sample"], out["state"]
-                elif sampler == "p_sample":
-                    local_samples = diffusion.p_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
-                                                       model_kwargs=model_kwargs, return_attn_weights=False,
-                                                       use_gradient_method=use_gradient_method, cfg_scale=cfg_scale)["sample"]
-                else:
-                    local_samples = diffusion.ddim_sample(model, local_samples, t=t_tensors[timestep], clip_denoised=True,
-                                                          model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)["sample"]
+                philox = None if sde_seed is None else (sde_seed, (diffusion.num_timesteps - 1 - timestep) * local_samples.numel())
+                out, carry = _sampler_step(diffusion, step_sampler, model, local_samples, t_tensors[timestep], carry, cfg_scale, eta, philox,
+                                           clip_denoised=True, model_kwargs=model_kwargs, **step_kw)
+                local_samples = out["sample"]
                 if trace is not None:
                     trace.append(local_samples.clone())
         write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
@@ -338,7 +310,6 @@ def _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampl
     """One window of infer_video's eager executor with a known region: the walk of repaint_schedule through the step entry points inside
     known_region_scope.  The merge's and the jumps' noise is what the window executor would draw: vd_randn at (seed, k B per + B per / 4)
     for op k's merge and (seed, k B per) for a jump, the seed drawn as WindowExecutor.begin draws it."""
-    from . import _lib
     from .respace import repaint_schedule
     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     B = x0.shape[0]
@@ -352,17 +323,10 @@ def _eager_known_window(model, diffusion, x0, model_kwargs, k_src, k_mask, sampl
             local, prev = diffusion.q_jump(local, t, latent_mask=model_kwargs["latent_mask"], noise=z, model=model), None
             continue
         with diffusion.known_region_scope(model, k_src, k_mask, known_noise=z):
-            if sampler == "dpmpp_2m":
-                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):
-                    out = diffusion.dpmpp_2m_sample(model, local, t=t, prev_xstart=prev, clip_denoised=True, model_kwargs=model_kwargs)
-            elif sampler == "dpmpp_2m_sde":
-                with (diffusion.cfg_scale_scope(model, cfg_scale) if cfg_scale != 1.0 else contextlib.nullcontext()):    # the head of op k's range
-                    out = diffusion._dpmpp_2m_sde(model, local, t, prev, True, None, model_kwargs, philox=(seed, k * n))
-            elif sampler == "p_sample":
-                out = diffusion.p_sample(model, local, t=t, clip_denoised=True, model_kwargs=model_kwargs, cfg_scale=cfg_scale)
-            else:
-                out = diffusion.ddim_sample(model, local, t=t, clip_denoised=True, model_kwargs=model_kwargs, eta=eta, cfg_scale=cfg_scale)
-        local, prev = out["sample"], out["pred_xstart"]
+            philox = (seed, k * n) if SAMPLERS[sampler].noise == "philox" else None       # the head of op k's range
+            out, prev = _sampler_step(diffusion, sampler, model, local, t, prev, cfg_scale, eta, philox, clip_denoised=True,
+                                      model_kwargs=model_kwargs)
+        local = out["sample"]
         if trace is not None:
             trace.append(local.clone())
     return local, trace
@@ -581,7 +545,7 @@ def load_lpips_for(args, device):
 
 def build_parser():
     ap = add_job_arguments(argparse.ArgumentParser())
-    ap.add_argument("--sampler", default="p_sample", choices=["p_sample", "ddim", "dpmpp_2m", "dpmpp_2m_sde", "unipc"],
+    ap.add_argument("--sampler", default="p_sample", choices=[s for s, row in SAMPLERS.items() if not row.up],
                     help="the step: p_sample (default), ddim (ddim_sample with --eta), dpmpp_2m (the second-order multistep solver), dpmpp_2m_sde "
                          "(its stochastic form) or unipc (dpmpp_2m's predictor plus a corrector on the same forward: third order; all three "
                          "meant for --timestep_respacing logsnrN, unipc for N of 20 or more); a non-default sampler is named in the run directory")
