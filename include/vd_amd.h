@@ -629,6 +629,67 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, c
                    const float* y, const float* latent_mask, int scale, int gray, float* d_eps, float* d_x, float* rho,
                    float* pred_xstart, void* stream);
 
+/* Particle steering -- this project's extension (Feynman-Kac steering: Singhal et al. 2025; the twisted diffusion sampler of Wu et al.
+ * 2023 without its gradient proposal; the reference has nothing like it): guidance by a reward on the step's x_0 prediction WITHOUT a
+ * derivative of the UNet -- sequential Monte Carlo over the reverse chain.  The batch is G groups of K consecutive items ("particles"):
+ * item g K + k is particle k of group g, and a group's items share t, the masks, the frame indices and the observed content.  Every
+ * particle runs the ordinary stochastic step; behind it the caller computes one fp64 reward r per item and hands them to
+ * vd_particle_apply, which per group (particles.hip; every sum in index order in fp64, no floating-point atomics):
+ *   1. logw_k += lambda (r_k - rprev_k), rprev_k = r_k (a reward or a log-weight of -inf keeps the particle at -inf);  m = max_k logw_k;
+ *      p_k = exp(logw_k - m) / sum_j exp(logw_j - m);  ESS = 1 / sum_k p_k^2;
+ *   2. if the K log-weights are bit-equal nothing else happens (a constant reward leaves the plain step's bits);
+ *   3. else if ESS < ess_threshold K: systematic resampling at u = uniforms[2 g]: c_k = sum_{j <= k} p_j (1 from the last k with p_k > 0
+ *      on), a_i = min{k : c_k > (u + i) / K}; item g K + i of each of the n <= 4 `tensors` ([B][per] floats, in place) takes the content of
+ *      item g K + a_i, rprev_i = rprev_{a_i}, logw_i = 0, and the group's resample counter goes up;
+ *   4. at t[g K] == 0 step 3 is skipped and chosen[g] = min{k : c_k > u2}, u2 = uniforms[2 g + 1]; nothing is gathered.
+ * The increments telescope, so with the last reward taken on the final sample the chain targets p(x_0) exp(lambda r(x_0)) as K grows.
+ * A group whose log-weights are all -inf is left as it is and its `degenerate` counter goes up.  A NaN or +inf reward is the caller's error.
+ * vd_set_particles: engine state like the measurement.  K <= 1 or lambda == 0 clears it; K <= 256, lambda finite and not negative,
+ *   ess_threshold in [0, 1].  y == NULL: the rewards are the caller's, through vd_particle_apply behind every step (eager steps only).
+ *   y != NULL: the BUILT-IN reward of a noisy measurement, r_b = -rho_b^2 / (2 sigma_y^2), rho_b^2 the sum over the cells of item b's
+ *   frames with latent_mask == 1 of (y - A x_0)^2 for the cell-mean operators of vd_set_measurement (scale, gray; y the caller's device
+ *   tensor of that layout, kept alive), sigma_y > 0.  Every step whose sample is wanted (vd_p_sample, vd_ddim_sample,
+ *   vd_dpmpp_2m_sde_sample with `pred_xstart` non-NULL, and the captured step of vd_window_begin) then appends three launches behind the
+ *   sampler pass and behind nothing else: the residual pass of vd_dps_step's step 3 as it is, on the step's pred_xstart (at t == 0: on its
+ *   sample, so that the increments telescope to lambda r(x_0)) -- same residual, partial layout and fold order, so an item's reward does
+ *   not depend on B -- the weights from its partials, and the gather of `sample` and `pred_xstart` (dpmpp_2m_sde's history).  With the
+ *   target exp(lambda r) and lambda = 1 the chain samples the Bayesian posterior of y = A x_0 + N(0, sigma_y^2) as K grows.
+ *   While particles are set, a step whose sample is wanted fails by name for: a sampler that draws no noise (ddim_sample at eta = 0,
+ *   dpmpp_2m_sample, unipc_sample, ddim_reverse_sample: duplicates would never separate), B no multiple of K, a known region, a
+ *   measurement, an armed attention capture; so do the differentiated passes (vd_guided_step, vd_dps_step, vd_guide_begin, vd_eps_vjp,
+ *   vd_ode_nll_eval), and vd_window_begin for the caller's rewards (a callback cannot be captured), the window prefix cache and the
+ *   suffix skip.  cfg_scale, guidance rescale, dynamic thresholding, both mean types, every observed_frames mode and windows of 1..128
+ *   frames are served.  With the state clear no launch is added and every path keeps its bits.  vd_particles: K, or 0 when clear.
+ * The uniforms of the built-in reward: a window draws them from its own Philox stream -- group g's (u, u2) are the two 53-bit halves
+ *   (words 0, 1 and 2, 3; 27 bits of the first above 26 of the second, times 2^-53) of block offset + 3/4 B per + g of the step's range
+ *   of B per blocks: the sampler's noise uses the first quarter, the known-region merge the second, the re-noised observed frames the
+ *   third, nothing else the fourth.  An eager step takes what vd_particle_draws set: a device tensor [G][2], or (uniforms NULL) the
+ *   same Philox block at (seed, offset + 3/4 B per + g), offset being the head of the step's range -- how an eager loop repeats a
+ *   window's draws.  vd_window_begin resets the state (vd_particle_reset) itself; eager chains call it before their first step.
+ * vd_particle_reset: sizes the state for B items and zeroes it (logw, rprev, counters); waits for the device.  The state outlives
+ *   vd_set_particles -- it can be read behind a window after the setting was cleared -- and a step or an apply under another K fails by name.
+ * vd_particle_apply: two launches on `stream` (the weights, the gather), no host wait; rewards [B] fp64, t [B] the index of the step just
+ *   made, uniforms [G][2] fp64 in [0, 1), all on the device; `tensors` is a host array of n device pointers (n = 0: weights only).
+ * vd_particle_state: copies out logw [B], rprev [B], ancestors [B] (of the last apply: the item each item took, itself where nothing
+ *   moved), chosen [G] (-1 unless the last apply was at t == 0), ess [G] and counters [G][2] (resamplings, degenerate steps); any may be
+ *   NULL; host or device destinations; waits for the device.
+ * vd_op_particle_weights / vd_op_particle_gather: the two passes alone on a caller's device state, no engine.  The weights pass takes the
+ *   rewards, or (rewards NULL) nblk fp64 partial sums per item of a squared residual, folded in index order: r = -(sum / (2 sigma_y^2)).
+ *   uniforms NULL: group g's pair from Philox block (seed, offset + g), as above.
+ *   The gather serves ANY map `ancestors` over the B items, cycles included; it allocates its scratch, waits for `stream` and frees it.
+ *   16-byte accesses while per % 4 == 0 and the tensors are 16-byte aligned, else element by element: same bits. */
+int vd_set_particles(vd_engine* e, int K, double lambda, double ess_threshold, const float* y, int scale, int gray, double sigma_y);
+int vd_particles(vd_engine* e);
+int vd_particle_reset(vd_engine* e, int B);
+int vd_particle_draws(vd_engine* e, const double* uniforms, unsigned long long seed, unsigned long long offset);
+int vd_particle_apply(vd_engine* e, int B, long long per, const double* rewards, const long long* t, const double* uniforms,
+                      float* const* tensors, int n, void* stream);
+int vd_particle_state(vd_engine* e, int B, double* logw, double* rprev, int* ancestors, int* chosen, double* ess, long long* counters);
+int vd_op_particle_weights(int G, int K, double lambda, double ess_threshold, const double* rewards, const double* partials, int nblk,
+                           double sigma_y, const long long* t, const double* uniforms, unsigned long long seed, unsigned long long offset,
+                           double* logw, double* rprev, int* ancestors, int* chosen, double* ess, long long* counters, void* stream);
+int vd_op_particle_gather(int B, long long per, const int* ancestors, float* const* tensors, int n, void* stream);
+
 /* Loss-guided sampling -- this project's extension: a reverse step moved down the gradient, with respect to x_t, of ANY differentiable
  * function of the step's x_0 prediction.  The function is the caller's own code: vd_dps_step is split in two around the point where the
  * cotangent of x_0 is formed, and the taped forward survives between the two calls.  Per item b, with L_b its frames with

@@ -244,6 +244,30 @@ int launch_dps_seed(DpsArgs a, hipStream_t s) {
     return 0;
 }
 
+// The residual pass alone (particle steering's built-in reward: particles.hip): r and the per-item partials of sum r^2, no seed pass.
+// *nblk: partials per item of this launch.  deps, dxd, rho and err are not read.
+int launch_dps_residual(DpsArgs a, int* nblk, hipStream_t s) {
+    VD_REQUIRE(a.x && a.eps && a.y && a.lat && a.t && a.tab && a.num_timesteps > 0 && a.r && a.part && nblk, "dps_residual: null tensor");
+    VD_REQUIRE(a.B > 0 && a.B <= 65535 && a.T > 0 && a.H > 0 && a.W > 0, "dps_residual: shape");
+    VD_REQUIRE(measurement_served(a.scale, a.gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
+    VD_REQUIRE(a.H % a.scale == 0 && a.W % a.scale == 0, "measurement: H and W must be divisible by scale");
+    const bool vec = dps_vec(a);
+    const dim3 rg = dps_residual_grid(a);
+    a.nblk = (int)(rg.x * rg.y);
+    *nblk = a.nblk;
+    switch (a.scale * 2 + (a.gray ? 1 : 0)) {
+        case 3: launch_residual<1, true>(a, vec, s); break;
+        case 4: launch_residual<2, false>(a, vec, s); break;
+        case 5: launch_residual<2, true>(a, vec, s); break;
+        case 8: launch_residual<4, false>(a, vec, s); break;
+        case 9: launch_residual<4, true>(a, vec, s); break;
+        case 16: launch_residual<8, false>(a, vec, s); break;
+        default: launch_residual<8, true>(a, vec, s); break;
+    }
+    VD_HIP(hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------ dps_final_kernel
 // g = d_x + dx_net * (1 / s) on every element (1 / s a power of two: launch_grad_rescale), written to `grad` when given; on the frames with
 // lat == 1 sample = fmaf(-zeta, g, sample), every other frame keeps the bits the sampler pass wrote.

@@ -335,7 +335,33 @@ struct vd_engine {
     // pass reads it.  The caller's tensor; a window graph's key carries the address, the scale and the gray flag.
     const float* meas_y = nullptr;
     int meas_scale = 1, meas_gray = 0;
-    int mean_type = 0;                               // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
+    // particle steering (vd_set_particles; part_K <= 1 = off): the batch is G groups of part_K particles; behind a step the caller hands
+    // the items' rewards to vd_particle_apply, which updates the state below and resamples the caller's tensors (particles.hip).
+    // part_B, part_state_K: the batch and the group size vd_particle_reset (or vd_window_begin) last zeroed the state for; the state outlives
+    // vd_set_particles, so that it can be read behind a window whose begin() has restored the engine's setting.
+    int part_K = 0, part_B = 0, part_state_K = 0;
+    double part_lambda = 0.0, part_tau = 0.0;
+    // the built-in reward (null: the rewards come through vd_particle_apply): r_b = -||y - A x_0||^2 / (2 sigma^2) on item b's latent
+    // frames, for the cell-mean operators of measure.hip; the caller's tensor, like meas_y
+    const float* part_y = nullptr;
+    int part_scale = 1, part_gray = 0;
+    double part_sigma = 0.0;
+    double *d_part_logw = nullptr, *d_part_rprev = nullptr, *d_part_ess = nullptr;
+    int *d_part_anc = nullptr, *d_part_chosen = nullptr;
+    long long* d_part_counters = nullptr;
+    size_t part_state_cap = 0;
+    float* d_part_scratch = nullptr; size_t part_scratch_cap = 0;
+    // ... of the built-in reward: the residual pass's r and partials, the x_0 prediction of a window whose sampler keeps none, and the
+    // selector rows [2][num_timesteps] that make dps_residual_kernel's x_0 head read the sample at t == 0 and pred_xstart elsewhere
+    float* d_part_r = nullptr; size_t part_r_cap = 0;
+    double* d_part_partials = nullptr; size_t part_partials_cap = 0;
+    float* d_part_x0 = nullptr; size_t part_x0_cap = 0;
+    float* d_part_sel = nullptr; size_t part_sel_cap = 0; int part_sel_nt = 0;
+    // the uniforms of the eager steps (vd_particle_draws): a device tensor [G][2], or Philox at (part_seed, part_offset) like a window's
+    const double* part_uni = nullptr;
+    unsigned long long part_seed = 0, part_offset = 0;
+    bool part_draws_set = false;
+    int mean_type = 0;                              // what the network's output IS: 0 eps (ModelMeanType.EPSILON), 1 x_0 (START_X)
     int* d_err = nullptr;                            // sticky device flags: bit 0 = timestep index out of range, bit 1 = network output not finite
     int device = -1;
     double* d_part = nullptr; size_t part_cap = 0;   // NLL partial sums
@@ -351,6 +377,8 @@ struct vd_engine {
         float* x; const float *obs_src, *obs, *lat, *km; const long long* fidx;
         const float *known_src, *known_mask;                      // known region: the merge pass a graph ends in reads them (null: none)
         const float* meas_y; int meas_scale, meas_gray;           // measurement: the projection pass a graph holds reads y (null: none)
+        const float* part_y; int part_K, part_scale, part_gray;   // particle steering: the three passes a graph ends in and their constants (part_K 0: none)
+        double part_lambda, part_tau, part_sigma;
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -404,6 +432,10 @@ struct vd_engine {
         if (d_unipc) (void)hipFree(d_unipc);
         if (d_jump) (void)hipFree(d_jump);
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
+        for (void* p : {(void*)d_part_logw, (void*)d_part_rprev, (void*)d_part_ess, (void*)d_part_anc, (void*)d_part_chosen,
+                        (void*)d_part_counters, (void*)d_part_scratch, (void*)d_part_r, (void*)d_part_partials, (void*)d_part_x0,
+                        (void*)d_part_sel})
+            if (p) (void)hipFree(p);
         for (auto& g : win_graphs) g.release();
     }
 
@@ -2007,6 +2039,14 @@ struct StepReq {
     // measurement (null: none): the projection of the step's x_0 prediction onto y, in front of the sampler pass
     const float* meas_y = nullptr;
     int meas_scale = 1, meas_gray = 0;
+    // particle steering with the built-in reward (part_K 0: none): behind the sampler pass the residual pass on the step's x_0 prediction, the
+    // weights and the gather of `sample` and `xstart`; the uniforms are part_uni, or Philox at (part_seed, part_offset + 3/4 B per), or at
+    // the pair `rng` points to
+    int part_K = 0, part_scale = 1, part_gray = 0;
+    const float* part_y = nullptr;
+    double part_lambda = 0.0, part_tau = 0.0, part_sigma = 0.0;
+    const double* part_uni = nullptr;
+    unsigned long long part_seed = 0, part_offset = 0;
 };
 
 // The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
@@ -2034,6 +2074,31 @@ static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long lo
     return a;
 }
 
+// Particle steering with the built-in reward, behind the sampler pass (ensure_particle_ws has sized the buffers): the residual pass of
+// dps.hip as it is -- handed (sample, pred_xstart) as its (x_t, eps) and the selector rows as its tables, its x_0 head gives the sample
+// at t == 0 and pred_xstart elsewhere, exactly -- then the weights from its partials and the gather of both tensors (particles.hip).
+static int particle_launches(vd_engine* e, const StepReq& r, const int64_t* t, size_t per, hipStream_t st) {
+    const int B = r.B, T = r.T, S = e->cfg.image_size, K = r.part_K;
+    VD_REQUIRE(r.part_y && r.sample && r.xstart, "particle steering: a step hands out its sample and its pred_xstart");
+    VD_REQUIRE(!r.pp && !r.sp, "particle steering (vd_set_particles) together with the window prefix cache or suffix skip is not served");
+    VD_REQUIRE(e->part_B == B && e->part_state_K == K && e->d_part_sel && e->part_sel_nt == e->num_timesteps, "particle steering: no state for this batch (vd_particle_reset)");
+    DpsArgs da{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_scale, r.part_gray, 0,
+               e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int nblk = 0, rc;
+    {
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 2.0, st, "particle_residual");
+        if ((rc = launch_dps_residual(da, &nblk, st))) return rc;
+    }
+    ParticleArgs pa{B / K, K, r.part_lambda, r.part_tau, nullptr, e->d_part_partials, nblk, 1.0 / (2.0 * r.part_sigma * r.part_sigma), t, r.part_uni,
+                    e->d_part_logw, e->d_part_rprev, e->d_part_anc, e->d_part_chosen, e->d_part_ess, e->d_part_counters};
+    pa.seed = r.part_seed; pa.offset = r.part_offset; pa.dstate = r.rng;
+    pa.pos = (unsigned long long)B * per / 4 * 3;
+    if ((rc = launch_particle_weights(pa, st))) return rc;
+    GatherArgs ga{{r.sample, r.xstart, nullptr, nullptr}, 2, B, (long long)per, e->d_part_anc, e->d_part_scratch};
+    ProfScope ps(PC_ELEMENTWISE, 0.0, 4.0 * B * per * 4.0, st, "particle_gather");
+    return launch_particle_gather(ga, st);
+}
+
 // The launches of one step on `st`: t -> t_model, UNet forward, the sampler pass.  Nothing here allocates or waits, and `t`, `rng` and
 // `hist_on` are read on the device, so the same launch sequence serves every step of a window (executor).
 // cfg_w != 1 (cfg_scale): behind the forward a second one at the same batch size with the engine's all-zero observation mask (cfg_zero_mask
@@ -2049,6 +2114,7 @@ static SamplerPassArgs pass_args(const vd_engine* e, int sampler, int B, long lo
 // x_0 itself (pass_x0: the sampler pass's head, clamp included) and writes the projected one into the second output buffer.  Either way
 // the sampler pass then runs in its x0_given form with clip off, so pred_xstart, the mean and the 2M history are the projected x_0.
 // Null: no launch is added.
+// part_K > 1 (particle steering with the built-in reward): particle_launches behind the sampler pass.  0: no launch is added.
 static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     int rc;
     const int B = r.B, T = r.T;
@@ -2111,6 +2177,7 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
         ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st);
         rc = launch_sampler_pass(pa, st);
     }
+    if (!rc && r.part_K > 1) rc = particle_launches(e, r, pa.t, per, st);
     if (rc || !r.known_src || !r.sample) return rc;
     // known region: the known pixels of the latent frames of the sample, noised to the level the step just reached (known.hip)
     KnownMergeArgs ka{r.sample, r.known_src, r.known_mask, r.lat, pa.t, e->d_tab, e->num_timesteps, B, T, (long)(per / T / 3)};
@@ -2140,6 +2207,65 @@ static int refuse_with_measurement(const vd_engine* e, int sampler) {
     return 0;
 }
 
+// what particle steering (vd_set_particles) is refused together with, by name: a step whose sample is wanted asks this of the engine's state
+static int refuse_with_particles(const vd_engine* e, int sampler, int B, float eta) {
+    VD_REQUIRE(sampler_draws_noise(sampler) && (sampler != SAMPLER_DDIM || eta > 0.f), std::string(sampler_name(sampler)) + (sampler == SAMPLER_DDIM ? " at eta = 0" : "") +
+               " together with particle steering (vd_set_particles) is not served: the step draws no noise, duplicated particles would never separate");
+    VD_REQUIRE(B % e->part_K == 0, "particle steering (vd_set_particles): the batch of " + std::to_string(B) + " items is no multiple of the " + std::to_string(e->part_K) + " particles of a group");
+    VD_REQUIRE(!e->known_src, "particle steering (vd_set_particles) together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(!e->meas_y, "particle steering (vd_set_particles) together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "particle steering (vd_set_particles) together with return_attn_weights is not served");
+    return 0;
+}
+
+// the particle state for B items, zeroed (never inside a capture; waits for the device: the steps that follow may run on any stream)
+static int particle_state_reset(vd_engine* e, int B) {
+    const size_t n = (size_t)B;
+    if (n > e->part_state_cap) {
+        size_t c0 = e->part_state_cap, c1 = c0, c2 = c0, c3 = c0, c4 = c0, c5 = c0;      // (one capacity for the six buffers)
+        int rc = e->grow(e->d_part_logw, c0, n, true);
+        if (!rc) rc = e->grow(e->d_part_rprev, c1, n, true);
+        if (!rc) rc = e->grow(e->d_part_ess, c2, n, true);
+        if (!rc) rc = e->grow(e->d_part_anc, c3, n, true);
+        if (!rc) rc = e->grow(e->d_part_chosen, c4, n, true);
+        if (!rc) rc = e->grow(e->d_part_counters, c5, 2 * n, true);
+        if (rc) { e->part_state_cap = 0; return rc; }
+        e->part_state_cap = n;
+    }
+    VD_HIP(hipMemset(e->d_part_logw, 0, n * sizeof(double)));
+    VD_HIP(hipMemset(e->d_part_rprev, 0, n * sizeof(double)));
+    VD_HIP(hipMemset(e->d_part_ess, 0, n * sizeof(double)));
+    VD_HIP(hipMemset(e->d_part_anc, 0, n * sizeof(int)));
+    VD_HIP(hipMemset(e->d_part_chosen, 0xff, n * sizeof(int)));
+    VD_HIP(hipMemset(e->d_part_counters, 0, 2 * n * sizeof(long long)));
+    VD_HIP(hipDeviceSynchronize());
+    e->part_B = B; e->part_state_K = e->part_K;
+    return 0;
+}
+
+// the buffers of the built-in reward for a (B, T) step (never inside a capture); x0: also the x_0 prediction of a window without history
+static int ensure_particle_ws(vd_engine* e, int B, int T, bool x0) {
+    const int S = e->cfg.image_size, sc = e->part_scale;
+    const size_t per = (size_t)T * 3 * S * S;
+    int rc = e->grow(e->d_part_r, e->part_r_cap, (size_t)B * T * (e->part_gray ? 1 : 3) * (S / sc) * (S / sc), true);
+    if (!rc) rc = e->grow(e->d_part_partials, e->part_partials_cap, (size_t)B * dps_partials_per_item(), true);
+    if (!rc) rc = e->grow(e->d_part_scratch, e->part_scratch_cap, 2 * (size_t)B * per, true);
+    if (!rc && x0) rc = e->grow(e->d_part_x0, e->part_x0_cap, (size_t)B * per, true);
+    if (rc) return rc;
+    const int NT = e->num_timesteps;
+    if (e->part_sel_nt != NT || !e->d_part_sel) {
+        // rows TAB_SQRT_RECIP and TAB_SQRT_RECIPM1 as the residual pass reads them: x_0 = a x - b eps with (a, b) = (1, 0) at t == 0 -- the
+        // sample -- and (0, -1) elsewhere -- pred_xstart; both exact
+        if ((rc = e->grow(e->d_part_sel, e->part_sel_cap, 2 * (size_t)NT, true))) return rc;
+        std::vector<float> rows(2 * (size_t)NT, 0.f);
+        rows[0] = 1.f;
+        for (int t = 1; t < NT; ++t) rows[(size_t)NT + t] = -1.f;
+        VD_HIP(hipMemcpy(e->d_part_sel, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+        e->part_sel_nt = NT;
+    }
+    return 0;
+}
+
 // what a step needs sized before its launches (never inside a capture): the workspace, and the zero mask of a cfg_scale step
 static int step_workspace(vd_engine* e, int B, int T, hipStream_t st) {
     int rc = e->ensure_ws(B, T);
@@ -2155,6 +2281,7 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
                "null tensor");
     VD_REQUIRE(r.sampler != SAMPLER_DDIM || r.eta >= 0.f, "eta");
     if ((rc = require_history_rows(e, r.sampler, sampler_name(r.sampler)))) return rc;
+    if (want_sample && e->part_K > 1 && (rc = refuse_with_particles(e, r.sampler, r.B, r.eta))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
     r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
@@ -2166,6 +2293,14 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
     if (e->meas_y) {
         if ((rc = refuse_with_measurement(e, r.sampler))) return rc;
         r.meas_y = e->meas_y; r.meas_scale = e->meas_scale; r.meas_gray = e->meas_gray;
+    }
+    if (want_sample && e->part_K > 1 && e->part_y) {
+        VD_REQUIRE(e->part_B == r.B && e->part_state_K == e->part_K, "particle steering: the state holds " + std::to_string(e->part_B) + " items in groups of " + std::to_string(e->part_state_K) + " (vd_particle_reset), the step " + std::to_string(r.B) + " in groups of " + std::to_string(e->part_K));
+        VD_REQUIRE(e->part_draws_set, "particle steering: no uniforms for this step (vd_particle_draws)");
+        if ((rc = ensure_particle_ws(e, r.B, r.T, false))) return rc;
+        r.part_K = e->part_K; r.part_y = e->part_y; r.part_scale = e->part_scale; r.part_gray = e->part_gray;
+        r.part_lambda = e->part_lambda; r.part_tau = e->part_tau; r.part_sigma = e->part_sigma;
+        r.part_uni = e->part_uni; r.part_seed = e->part_seed; r.part_offset = e->part_offset;
     }
     return step_launches(e, r, st);
 }
@@ -2407,6 +2542,11 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
     r.known_src = k.known_src; r.known_mask = k.known_mask;      // the merge draws from the window's own Philox pair (r.rng)
     r.meas_y = k.meas_y; r.meas_scale = k.meas_scale; r.meas_gray = k.meas_gray;
+    if (k.part_K > 1) {                                          // the uniforms come from the window's own Philox pair (r.rng)
+        r.part_K = k.part_K; r.part_y = k.part_y; r.part_scale = k.part_scale; r.part_gray = k.part_gray;
+        r.part_lambda = k.part_lambda; r.part_tau = k.part_tau; r.part_sigma = k.part_sigma;
+        if (!r.xstart) r.xstart = e->d_part_x0;
+    }
     if (!rc) rc = step_launches(e, r, st);
     if (!rc) {
         // a step with a merge pass consumes its range whatever the sampler: the merge's quarter of it is drawn from
@@ -2452,6 +2592,12 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     if ((rc = require_history_rows(e, sampler, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ")"))) return rc;
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
+    if (e->part_K > 1) {
+        VD_REQUIRE(e->part_y, "particle steering (vd_set_particles) with the caller's rewards inside a window graph is not served: a callback between two steps cannot be captured (the built-in reward can)");
+        if ((rc = refuse_with_particles(e, sampler, B, eta))) return rc;
+        VD_REQUIRE(!e->prefix_cache_on, "particle steering (vd_set_particles) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+        VD_REQUIRE(!e->suffix_skip_on, "particle steering (vd_set_particles) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    }
     if (e->known_src) {
         VD_REQUIRE(!sampler_walks_up(sampler), "sampler 2 (ddim_reverse_sample) together with a known region (vd_set_known_region) is not served: the merge noises to t - 1");
         VD_REQUIRE(!e->known_noise, "a window draws the known region's noise from its own Philox stream: known_noise must be NULL (vd_set_known_region)");
@@ -2467,6 +2613,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = step_workspace(e, B, T, st))) return rc;
     if ((rc = window_buffers(e, B, obs_mode, sampler, (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size))) return rc;
+    if (e->part_K > 1 && ((rc = particle_state_reset(e, B)) || (rc = ensure_particle_ws(e, B, T, !sampler_has_history(sampler))))) return rc;
     hipLaunchKernelGGL(win_set_kernel, dim3((B + 63) / 64), dim3(64), 0, st, e->d_win_t, e->d_win_rng, B, t_start, seed, offset);
     VD_HIP(hipGetLastError());
     vd_engine::WinKey key;
@@ -2476,6 +2623,10 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     key.guid_phi = e->guid_phi; key.dyn_p = e->dyn_p;
     key.x = x; key.obs_src = obs_src; key.obs = obs; key.lat = lat; key.km = km; key.fidx = fidx;
     key.known_src = e->known_src; key.known_mask = e->known_mask;
+    if (e->part_K > 1) {
+        key.part_y = e->part_y; key.part_K = e->part_K; key.part_scale = e->part_scale; key.part_gray = e->part_gray;
+        key.part_lambda = e->part_lambda; key.part_tau = e->part_tau; key.part_sigma = e->part_sigma;
+    }
     if (e->meas_y) { key.meas_y = e->meas_y; key.meas_scale = e->meas_scale; key.meas_gray = e->meas_gray; }
     e->win_cur = -1;
     e->win_lost = false;
@@ -2644,6 +2795,96 @@ int vd_measurement_project(vd_engine* e, int B, int T, int H, int W, float* x0_i
     VD_REQUIRE(e, "null engine");
     MeasureArgs a{nullptr, x0_inout, x0_inout, y, lat, nullptr, nullptr, 0, B, T, H, W, scale, gray ? 1 : 0, 0};
     return launch_measurement_project(a, static_cast<hipStream_t>(stream));
+}
+
+// ---- particle steering (particles.hip): engine state like the measurement; the weights and counters live in the engine
+int vd_set_particles(vd_engine* e, int K, double lambda, double ess_threshold, const float* y, int scale, int gray, double sigma_y) {
+    VD_REQUIRE(e, "null engine");
+    if (K <= 1 || lambda == 0.0) {
+        e->part_K = 0; e->part_lambda = 0.0; e->part_tau = 0.0;
+        e->part_y = nullptr; e->part_scale = 1; e->part_gray = 0; e->part_sigma = 0.0;
+        e->part_uni = nullptr; e->part_draws_set = false;
+        return 0;
+    }
+    VD_REQUIRE(K <= kMaxParticles, "particle steering: at most " + std::to_string(kMaxParticles) + " particles per group, got " + std::to_string(K));
+    VD_REQUIRE(lambda > 0.0 && lambda <= 1.7976931348623157e308, "particle steering: the reward scale must be finite and not negative");
+    VD_REQUIRE(ess_threshold >= 0.0 && ess_threshold <= 1.0, "particle steering: ess_threshold must lie in [0, 1]");
+    if (y) {
+        VD_REQUIRE(sigma_y > 0.0 && sigma_y <= 1.7976931348623157e308, "particle steering: sigma_y must be positive and finite");
+        VD_REQUIRE(measurement_served(scale, gray), "measurement: scale is 2, 4 or 8, or 1 together with gray (scale 1 without gray is the identity)");
+        VD_REQUIRE(e->cfg.image_size % scale == 0, "measurement: H and W must be divisible by scale");
+    }
+    e->part_K = K; e->part_lambda = lambda; e->part_tau = ess_threshold;
+    e->part_y = y; e->part_scale = y ? scale : 1; e->part_gray = y && gray ? 1 : 0; e->part_sigma = y ? sigma_y : 0.0;
+    return 0;
+}
+
+int vd_particles(vd_engine* e) { return e && e->part_K > 1 ? e->part_K : 0; }
+
+int vd_particle_reset(vd_engine* e, int B) {
+    VD_REQUIRE(e && e->part_K > 1, "vd_particle_reset: no particles are set (vd_set_particles)");
+    VD_REQUIRE(B > 0 && B % e->part_K == 0, "particle steering (vd_set_particles): the batch of " + std::to_string(B) + " items is no multiple of the " + std::to_string(e->part_K) + " particles of a group");
+    return particle_state_reset(e, B);
+}
+
+int vd_particle_draws(vd_engine* e, const double* uniforms, unsigned long long seed, unsigned long long offset) {
+    VD_REQUIRE(e, "null engine");
+    e->part_uni = uniforms; e->part_seed = seed; e->part_offset = offset; e->part_draws_set = true;
+    return 0;
+}
+
+int vd_particle_apply(vd_engine* e, int B, long long per, const double* rewards, const long long* t, const double* u, float* const* tensors,
+                      int n, void* stream) {
+    VD_REQUIRE(e && e->part_K > 1, "vd_particle_apply: no particles are set (vd_set_particles)");
+    VD_REQUIRE(B > 0 && B == e->part_B && e->part_state_K == e->part_K, "vd_particle_apply: the state holds " + std::to_string(e->part_B) + " items in groups of " + std::to_string(e->part_state_K) + " (vd_particle_reset), got " + std::to_string(B) + " in groups of " + std::to_string(e->part_K));
+    VD_REQUIRE(!e->part_y, "vd_particle_apply: the built-in reward is set (vd_set_particles with y): the step applies it itself");
+    VD_REQUIRE(rewards && t && u && per > 0 && n >= 0 && n <= 4 && (n == 0 || tensors), "vd_particle_apply: arguments");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int K = e->part_K;
+    ParticleArgs pa{B / K, K, e->part_lambda, e->part_tau, rewards, nullptr, 0, 0.0, reinterpret_cast<const int64_t*>(t), u,
+                    e->d_part_logw, e->d_part_rprev, e->d_part_anc, e->d_part_chosen, e->d_part_ess, e->d_part_counters};
+    if (n > 0)
+        if (int rc = e->grow(e->d_part_scratch, e->part_scratch_cap, (size_t)n * B * per, true)) return rc;
+    if (int rc = launch_particle_weights(pa, st)) return rc;
+    if (n == 0) return 0;
+    GatherArgs ga{{nullptr, nullptr, nullptr, nullptr}, n, B, per, e->d_part_anc, e->d_part_scratch};
+    for (int k = 0; k < n; ++k) ga.x[k] = tensors[k];
+    ProfScope ps(PC_ELEMENTWISE, 0.0, 0.0, st, "particle_gather");
+    return launch_particle_gather(ga, st);
+}
+
+int vd_particle_state(vd_engine* e, int B, double* logw, double* rprev, int* ancestors, int* chosen, double* ess, long long* counters) {
+    VD_REQUIRE(e && e->part_state_K > 1 && B > 0 && B == e->part_B, "vd_particle_state: no state of this batch size is held (vd_particle_reset, vd_window_begin)");
+    const size_t G = (size_t)B / e->part_state_K;
+    VD_HIP(hipDeviceSynchronize());
+    if (logw) VD_HIP(hipMemcpy(logw, e->d_part_logw, B * sizeof(double), hipMemcpyDefault));
+    if (rprev) VD_HIP(hipMemcpy(rprev, e->d_part_rprev, B * sizeof(double), hipMemcpyDefault));
+    if (ancestors) VD_HIP(hipMemcpy(ancestors, e->d_part_anc, B * sizeof(int), hipMemcpyDefault));
+    if (chosen) VD_HIP(hipMemcpy(chosen, e->d_part_chosen, G * sizeof(int), hipMemcpyDefault));
+    if (ess) VD_HIP(hipMemcpy(ess, e->d_part_ess, G * sizeof(double), hipMemcpyDefault));
+    if (counters) VD_HIP(hipMemcpy(counters, e->d_part_counters, 2 * G * sizeof(long long), hipMemcpyDefault));
+    return 0;
+}
+
+// the two passes alone on a caller's state (tests): no engine state is read or written
+int vd_op_particle_weights(int G, int K, double lambda, double ess_threshold, const double* rewards, const double* partials, int nblk,
+                           double sigma_y, const long long* t, const double* u, unsigned long long seed, unsigned long long offset, double* logw,
+                           double* rprev, int* ancestors, int* chosen, double* ess, long long* counters, void* stream) {
+    VD_REQUIRE(rewards || sigma_y > 0.0, "particle steering: sigma_y must be positive");
+    ParticleArgs pa{G, K, lambda, ess_threshold, rewards, partials, nblk, rewards ? 0.0 : 1.0 / (2.0 * sigma_y * sigma_y),
+                    reinterpret_cast<const int64_t*>(t), u, logw, rprev, ancestors, chosen, ess, counters};
+    pa.seed = seed; pa.offset = offset;
+    return launch_particle_weights(pa, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_particle_gather(int B, long long per, const int* ancestors, float* const* tensors, int n, void* stream) {
+    VD_REQUIRE(B > 0 && per > 0 && ancestors && tensors && n >= 1 && n <= 4, "vd_op_particle_gather: arguments");
+    OpScratch sc(stream);
+    float* scratch;
+    if (int rc = sc.get(&scratch, (size_t)n * B * per)) return rc;
+    GatherArgs ga{{nullptr, nullptr, nullptr, nullptr}, n, B, per, ancestors, scratch};
+    for (int k = 0; k < n; ++k) ga.x[k] = tensors[k];
+    return launch_particle_gather(ga, static_cast<hipStream_t>(stream));
 }
 
 static const char* const kNoJumpRows = "q_jump: no jump rows for the bound schedule (vd_set_jump_rows, after vd_set_schedule)";
@@ -2900,6 +3141,7 @@ static int check_diff(vd_engine* e, int B, int T, const std::string& what, bool 
     VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only" + eps_note);
     VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, what + ": the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
     VD_REQUIRE(!e->meas_y, what + " together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(e->part_K <= 1, what + " together with particle steering (vd_set_particles) is not served");
     if (!plain_state) return 0;
     VD_REQUIRE(e->cfg_w == 1.f, what + " together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
     VD_REQUIRE(e->guid_phi == 0.f, what + " together with guidance_rescale (vd_set_guidance_rescale) is not served");

@@ -628,9 +628,44 @@ struct DpsArgs {
 };
 size_t dps_partials_per_item();
 int launch_dps_seed(DpsArgs a, hipStream_t s);
+// the residual pass of launch_dps_seed alone: r and part; *nblk = the partials per item it wrote
+int launch_dps_residual(DpsArgs a, int* nblk, hipStream_t s);
 // g = dxd + dx_net * gs[1] (launch_grad_rescale's 1 / s) -> grad (or null); sample = fmaf(-zeta, g, sample) on the frames with lat == 1
 int launch_dps_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, float zeta,
                      float* sample, float* grad, hipStream_t s);
+
+// Particle steering (particles.hip; this project's extension, Feynman-Kac steering: Singhal et al. 2025): B = G*K items, item g*K + k is
+// particle k of group g.  launch_particle_weights, one block per group: the weight update logw += lambda (r - rprev) from the items' rewards
+// (`rewards`, or r = -(sum_j part[b][j]) * inv_two_var, the partials folded in index order), p = softmax(logw), ess = 1 / sum p^2, and --
+// unless the group's logw are bit-equal, t[g*K] == 0 or ess >= tau K -- systematic resampling at uni[2g]: ancestors[g*K + i] = g*K + a_i,
+// rprev_i = rprev_{a_i}, logw_i = 0, counters[2g] += 1; otherwise identity ancestors.  t[g*K] == 0: chosen[g] = the inverse CDF at
+// uni[2g + 1], else -1.  A group whose logw are all -inf: left as it is, counters[2g + 1] += 1.  Sums in index order in fp64, no atomics.
+constexpr int kMaxParticles = 256;
+struct ParticleArgs {
+    int G, K;
+    double lambda, tau;
+    const double* rewards;  // [B], or null: from the partials
+    const double* part; int nblk; double inv_two_var;
+    const int64_t* t;       // [B] respaced index of the step just made (a group's items share it)
+    const double* uni;      // [G][2], each in [0, 1); or null: words 0..3 of Philox block (seed, offset + pos + g), 53 bits each pair,
+                            // the pair (seed, offset) read from `dstate` when given
+    double* logw; double* rprev;                     // [B], updated in place
+    int* ancestors; int* chosen; double* ess;        // [B], [G], [G]
+    long long* counters;                             // [G][2]: resamplings, degenerate steps
+    unsigned long long seed = 0, offset = 0, pos = 0;
+    const unsigned long long* dstate = nullptr;
+};
+int launch_particle_weights(const ParticleArgs& a, hipStream_t s);
+// launch_particle_gather, one launch: item i of each of the n <= 4 tensors x[k] ([B][per] floats) takes the content of item anc[i]; any map,
+// cycles included.  scratch: n*B*per floats.  Items with anc[i] == i are neither read nor written; nothing moved: no traffic but the indices.
+// 16-byte accesses while per % 4 == 0 and every pointer is 16-byte aligned, else element by element: same bits.
+struct GatherArgs {
+    float* x[4]; int n;
+    int B; long long per;
+    const int* anc;
+    float* scratch;
+};
+int launch_particle_gather(const GatherArgs& a, hipStream_t s);
 
 // Loss-guided sampling (guide.hip; this project's extension): a reverse step moved down the gradient of a caller's function of its x_0
 // prediction.  Tensors are [B][T][3][H][W], `lat` the [B*T] latent mask.  launch_guide_seed: on the frames with lat == 1, with cot the

@@ -23,14 +23,17 @@ on the window tensor, `jump(n)` walks the armed window n forward diffusion steps
 walk of `respace.repaint_schedule` over both; all noise stays on the window's Philox stream (include/vd_amd.h: vd_set_known_region).
 Zero-shot restoration (DDNM, this project's extension too): `begin(..., measurement=, sr_scale=, gray=)` captures a step whose x_0
 prediction is projected onto the measurement in front of the sampler pass (include/vd_amd.h: vd_set_measurement).
+Particle steering (this project's extension): `begin(..., particles=K, particle_measurement=, sigma_y=)` captures a step that ends in the
+residual pass, the weights and the gather of the built-in reward; the weights live in the engine, the uniforms on the window's Philox
+stream, and `particle_state()` reads them (include/vd_amd.h: vd_set_particles).
 """
 import math
 
 import torch as th
 
 from . import _lib
-from .gaussian_diffusion import (SAMPLERS, _engine_measurement, _engine_region, _refuse, _scope, check_known_region, check_measurement,
-                                 measurement_shape)
+from .gaussian_diffusion import (SAMPLERS, _check_operator, _engine_measurement, _engine_particles, _engine_region, _refuse, _scope,
+                                 check_known_region, check_measurement, check_steering, measurement_shape)
 
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
@@ -82,7 +85,8 @@ class WindowExecutor:
         return bufs[key]
 
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
-              known_src=None, known_mask=None, measurement=None, sr_scale=1, gray=False, cfg_scale=1.0):
+              known_src=None, known_mask=None, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
+              ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -112,6 +116,15 @@ class WindowExecutor:
         gray); the captured step projects its x_0 prediction onto it, and y's address, the scale and the flag are part of the graph's
         signature.  Without it, a begin() inside `diffusion.measurement_scope(...)` takes the scope's measurement.  The engine refuses it
         by name with 'ddim_reverse', prefix_cache, suffix_skip and a known region.
+        particles, reward_scale, ess_threshold, particle_measurement, particle_sr_scale, particle_gray, sigma_y (this project's extension;
+        gaussian_diffusion.py: steering_scope): particle steering with the BUILT-IN reward of a noisy measurement -- the batch is groups
+        of `particles` consecutive items, y = particle_measurement is checked and copied into a buffer of this object, and the captured
+        step ends in the residual pass, the weights and the gather of the window tensor and the x_0 prediction; K, the scale, the
+        threshold, y's address, the operator and sigma_y are part of the graph's signature.  The weights are reset by every begin();
+        the uniforms come from the window's Philox stream.  particle_state() reads the state behind any run().  Without them, a begin()
+        inside `diffusion.steering_scope(..., measurement=)` takes the scope's setting.  A reward_fn -- the keyword, or the scope's -- is
+        refused by name: a Python callback cannot be captured.  Refused by name too: a sampler that draws no noise ('ddim' at eta = 0,
+        'dpmpp_2m', 'unipc', 'ddim_reverse'), a known region, a measurement, prefix_cache, suffix_skip, B no multiple of particles.
         A begin() inside `diffusion.dps_scope(...)` is refused by name: a DPS step runs a backward pass and is eager only; so is one
         inside `diffusion.loss_guidance_scope(...)`, whose step runs the caller's Python between two launches."""
         cfg_scale = float(cfg_scale)
@@ -125,6 +138,9 @@ class WindowExecutor:
             raise ValueError("known_src and known_mask are given together")
         _refuse(self.model, "dps", "WindowExecutor.begin")               # before anything touches the engine
         _refuse(self.model, "loss_guidance", "WindowExecutor.begin")     # (a Python callback between two launches cannot be captured)
+        steer = self._steering(x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, particle_measurement, particle_sr_scale,
+                               particle_gray, sigma_y, known_src is not None or _scope(self.model, "known_region") is not None,
+                               measurement is not None or _scope(self.model, "measurement") is not None)
         scope = _scope(self.model, "known_region")
         if known_src is not None:
             known_src, known_mask = check_known_region(known_src, known_mask)
@@ -185,6 +201,13 @@ class WindowExecutor:
                     meas["y"].record_stream(self.stream)
                 yb.copy_(meas["y"])
                 meas = dict(meas, y=yb)
+            if steer is not None:
+                pm = steer["measurement"]
+                yb = self._measurement_buffer(B, T, pm["scale"], pm["gray"])
+                if pm["y"].is_cuda:
+                    pm["y"].record_stream(self.stream)
+                yb.copy_(pm["y"])
+                steer = dict(steer, measurement=dict(pm, y=yb))
             for k in ("obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"):
                 bufs[k].copy_(kw[k].view(bufs[k].shape))
             if mode == "x_0":
@@ -210,6 +233,10 @@ class WindowExecutor:
             # ... and the measurement: the signature keeps the buffer's address, the scale and the gray flag
             if meas is not None:
                 _engine_measurement(self.model, meas)
+            # ... and the particles: the signature keeps K, the scale, the threshold, y's address, the operator and sigma_y
+            s_scope = _scope(self.model, "steering")
+            if steer is not None:
+                _engine_particles(self.model, steer)
             try:
                 rc = _lib.lib().vd_window_begin(
                     self.model._handle, B, T, _lib.ptr(bufs["x"]), _lib.ptr(obs_src), _lib.ptr(bufs["obs_mask"]),
@@ -217,6 +244,8 @@ class WindowExecutor:
                     3 if (mode == "x_t_minus_1" and not renoise) else _OBS_MODES[mode], sid, 1 if clip_denoised else 0, float(eta), seed, 0,
                     int(t_start), self.stream.cuda_stream)
             finally:
+                if steer is not None:
+                    _engine_particles(self.model, s_scope)
                 if meas is not None:
                     _engine_measurement(self.model, m_scope)
                 if region is not None or scope is not None:
@@ -225,10 +254,60 @@ class WindowExecutor:
                     _lib.check(_lib.lib().vd_set_cfg_scale(self.model._handle, 1.0))
             _lib.check(rc)
         self.x = bufs["x"]
+        self._particles = None if steer is None else (B, steer["K"])
         self.seed = seed
         self._left = self.diffusion.num_timesteps - int(t_start) if up else int(t_start) + 1
         self._gen = int(_lib.lib().vd_window_generation(self.model._handle))
         return self
+
+    def _steering(self, x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, y, sr_scale, gray, sigma_y, region, meas):
+        """begin()'s particle keywords, or the enclosing steering_scope's setting, checked before anything touches the engine -> a steering
+        dict (gaussian_diffusion.py: _engine_particles) or None (the plain window)."""
+        scope = _scope(self.model, "steering")
+        if reward_fn is not None or (scope is not None and scope["measurement"] is None and particles == 1):
+            raise NotImplementedError("WindowExecutor.begin with a reward_fn is not served: a Python callback between two steps cannot be "
+                                      "captured in a graph (the built-in reward can: particle_measurement=, sigma_y=)")
+        if particles == 1 and y is None:
+            if scope is None:
+                return None
+            d = dict(scope)
+        else:
+            if y is None:
+                raise ValueError("WindowExecutor.begin: particles > 1 needs particle_measurement= and sigma_y= (the built-in reward)")
+            K, lam, tau, sig = check_steering(None, y, particles, reward_scale, ess_threshold, sigma_y)
+            sc, gr = _check_operator(sr_scale, gray)
+            if K == 1 or lam == 0.0:
+                return None
+            d = dict(K=K, scale=lam, tau=tau, measurement=dict(y=y, scale=sc, gray=gr, sigma_y=sig))
+        m = d["measurement"]
+        m = dict(m, y=check_measurement(m["y"], x_init.shape, m["scale"], m["gray"]))
+        row = SAMPLERS.get(sampler, SAMPLERS["ddim"])
+        if row.noise is None or (row.eta and float(eta) == 0.0):
+            raise NotImplementedError(f"sampler={sampler!r}{' at eta = 0' if row.noise is not None else ''} together with particles is not served: "
+                                      "the step draws no noise, duplicated particles would never separate")
+        for name, on in (("prefix_cache", self.prefix_cache), ("suffix_skip", self.suffix_skip), ("a known region", region), ("a measurement", meas)):
+            if on:
+                raise NotImplementedError(f"{name} together with particles is not served")
+        if x_init.shape[0] % d["K"]:
+            raise ValueError(f"WindowExecutor.begin: the batch of {x_init.shape[0]} items is no multiple of particles={d['K']}")
+        return dict(d, measurement=m)
+
+    def particle_state(self):
+        """The particle state of the armed window behind the steps run so far (waits for the device) -> dict log_weights (B,), rprev (B,)
+        float64, ancestors (B,) int32 (of the last step), chosen (G,) int32 (-1 before the step at t == 0), ess (G,) float64, resamples
+        (G,) and degenerate (G,) int64, as host tensors."""
+        if getattr(self, "_particles", None) is None:
+            raise RuntimeError("WindowExecutor.particle_state: the armed window has no particles (begin(..., particles=K, ...))")
+        self._check_gen("particle_state")
+        B, K = self._particles
+        G = B // K
+        out = dict(log_weights=th.empty(B, dtype=th.float64), rprev=th.empty(B, dtype=th.float64), ancestors=th.empty(B, dtype=th.int32),
+                   chosen=th.empty(G, dtype=th.int32), ess=th.empty(G, dtype=th.float64))
+        counters = th.empty(G, 2, dtype=th.int64)
+        _lib.check(_lib.lib().vd_particle_state(self.model._handle, B, *(_lib.ptr(out[k]) for k in ("log_weights", "rprev", "ancestors", "chosen", "ess")),
+                                                _lib.ptr(counters)))
+        out["resamples"], out["degenerate"] = counters[:, 0].clone(), counters[:, 1].clone()
+        return out
 
     def run(self, n_steps=None):
         """Replay the step graph n_steps times (default: down to t = 0; 'ddim_reverse': up to the last index).  Returns the
@@ -281,10 +360,13 @@ class WindowExecutor:
         return self.x
 
     def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, known_src=None, known_mask=None,
-                      jump_length=1, n_resample=1, measurement=None, sr_scale=1, gray=False, cfg_scale=1.0):
+                      jump_length=1, n_resample=1, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
+                      ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, cfg_scale=1.0):
         """All num_timesteps steps of one window (with a known region and n_resample > 1: the walk of run_repaint); returns a fresh tensor."""
         self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale, known_src=known_src,
-                   known_mask=known_mask, measurement=measurement, sr_scale=sr_scale, gray=gray)
+                   known_mask=known_mask, measurement=measurement, sr_scale=sr_scale, gray=gray, particles=particles, reward_fn=reward_fn,
+                   reward_scale=reward_scale, ess_threshold=ess_threshold, particle_measurement=particle_measurement,
+                   particle_sr_scale=particle_sr_scale, particle_gray=particle_gray, sigma_y=sigma_y)
         if int(n_resample) != 1:
             return self.run_repaint(jump_length, n_resample).clone()
         return self.run(self.diffusion.num_timesteps).clone()

@@ -232,12 +232,14 @@ def check_known_region(known_src, known_mask):
 
 # the scopes that keep their setting on the model, as attribute _<name> -- in the order a step inside a later one refuses the earlier
 # ones -- and what a refusal raises
-_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "loss_guidance": _lib.VdError}
+_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "loss_guidance": _lib.VdError,
+           "steering": NotImplementedError}
 
 
 def _scope(model, name):
     """What the innermost <name>_scope set on this model, or None: known_region (dict src, mask, noise), measurement (dict y, scale, gray),
-    dps (dict y, scale, gray, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize)."""
+    dps (dict y, scale, gray, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize), steering (dict reward_fn, K, scale, tau,
+    measurement, uniforms and the chain's bookkeeping)."""
     return getattr(getattr(model, "model", model), "_" + name, None)
 
 
@@ -377,6 +379,48 @@ def loss_guidance_step_scale(scale, t, B):
             raise ValueError(f"loss_guidance_scope: scale(t)={v.tolist()!r}: every step size must be finite and not negative")
         return v.contiguous()
     return th.full((B,), _scale_number(v, "scale(t)" if callable(scale) else "scale"), dtype=th.float32)
+
+
+MAX_PARTICLES = 256
+
+
+def check_steering(reward_fn, measurement, particles, scale, ess_threshold, sigma_y):
+    """The host checks of steering_scope's arguments (no engine) -> (K, scale, ess_threshold, sigma_y or None) as (int, float, float, float).
+    ValueError naming the rule otherwise."""
+    if isinstance(particles, bool) or not isinstance(particles, (int, np.integer)) or not 1 <= int(particles) <= MAX_PARTICLES:
+        raise ValueError(f"steering_scope: particles={particles!r}: the particles of a group are an integer in [1, {MAX_PARTICLES}]")
+    if (reward_fn is None) == (measurement is None):
+        raise ValueError("steering_scope: exactly one of reward_fn and measurement is given")
+    if reward_fn is not None and not callable(reward_fn):
+        raise ValueError("steering_scope: reward_fn must be callable: reward_fn(x0, t) -> (B,) tensor")
+    for name, v in (("scale", scale), ("ess_threshold", ess_threshold)) + ((("sigma_y", sigma_y),) if measurement is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"steering_scope: {name}={v!r} must be a number")
+    lam, tau = float(scale), float(ess_threshold)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"steering_scope: scale={scale!r}: the reward scale must be finite and not negative")
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError(f"steering_scope: ess_threshold={ess_threshold!r} must lie in [0, 1]")
+    if measurement is None:
+        return int(particles), lam, tau, None
+    sig = float(sigma_y)
+    if not (math.isfinite(sig) and sig > 0.0):
+        raise ValueError(f"steering_scope: sigma_y={sigma_y!r}: the measurement's noise level must be positive and finite (sigma_y <= 0 is not served)")
+    return int(particles), lam, tau, sig
+
+
+def _engine_particles(model, d):
+    """Engine state <- a steering dict or None (clear).  The next steered step inside starts a chain (vd_particle_reset)."""
+    L = _lib.lib()
+    if d is None:
+        _lib.check(L.vd_set_particles(model._handle, 0, 0.0, 0.0, None, 1, 0, 0.0))
+        return
+    m = d["measurement"]
+    d["B"] = None
+    if m is None:
+        _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], None, 1, 0, 0.0))
+    else:
+        _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0, m["sigma_y"]))
 
 
 def _cfg_scope_or_null(diffusion, model, cfg_scale):
@@ -757,6 +801,144 @@ class GaussianDiffusion:
             out["grad_norm"] = norm
         return out
 
+    def steering_scope(self, model, reward_fn=None, *, particles, scale=1.0, ess_threshold=0.5, measurement=None, sr_scale=1, gray=False,
+                       sigma_y=None, uniforms=None):
+        """This project's extension (Feynman-Kac steering: Singhal et al. 2025; the twisted diffusion sampler of Wu et al. 2023 without its
+        gradient proposal): `with diffusion.steering_scope(model, reward_fn, particles=K):` -- guidance towards a reward on the step's x_0
+        prediction WITHOUT a derivative of the UNet, so it reaches what the gradient scopes do not: windows of up to 128 frames,
+        predict_xstart models, and (built-in reward) the window executor.  The batch of every step inside is G groups of K consecutive
+        items, the particles of one video: items g K .. g K + K - 1 share t, the masks, frame_indices and the observed content (the
+        caller repeats them).  Every particle runs the ordinary step and draws its own noise; behind it each is weighted by
+        exp(scale * (r - r_previous)) of its reward, and when a group's effective sample size falls below ess_threshold * K its particles
+        are resampled (systematic resampling): good ones are duplicated, bad ones dropped, and the duplicates separate again at the next
+        step.  At t == 0 the reward is taken on the sample itself and nothing is resampled: the step returns all K samples and
+        'chosen' (G,), one particle per group drawn from the final weights.  The increments telescope, so the chain targets
+        p(x_0) exp(scale * r(x_0)) as K grows (include/vd_amd.h: vd_set_particles; tests/particle_restated.py is the arithmetic).
+        Exactly one of:
+          reward_fn(x0, t)   the caller's torch function of 'pred_xstart' (B, T, 3, H, W) (at t == 0: of 'sample'), t the step's (B,)
+                             indices, both on the device -> a (B,) tensor, converted to float64.  -inf removes a particle; NaN or +inf
+                             raise ValueError -- this check, like the callback itself, costs a device wait per step.  Eager steps only.
+          measurement=y      the built-in reward of a NOISY measurement y = measure(video, sr_scale, gray) + N(0, sigma_y^2):
+                             r = -||y - A x0||^2 / (2 sigma_y^2) over the item's frames with latent_mask == 1, computed on the device in
+                             the step's own launches; with scale = 1 the target is the Bayesian posterior, which dps_scope approximates
+                             with a gradient and a hand-tuned zeta.  y (B, T, Cy, H / sr_scale, W / sr_scale): a group's items carry the
+                             same y.  sigma_y is required.
+        Served inside: p_sample, ddim_sample with eta > 0, dpmpp_2m_sde_sample and the loops built on them; cfg_scale, guidance_scope with
+        any of its options, every observed_frames mode, both mean types.  A step returns its usual dict -- 'sample' and 'pred_xstart' are
+        the resampled tensors -- plus 'ancestors' (B,) int32 (the item each item took; itself where nothing moved), 'ess' (G,) and
+        'log_weights' (B,) float64, and at t == 0 'chosen' (G,) int32.  particles=1 or scale=0 is the plain step to the bit, and so is
+        a reward that is constant over a group.  The weights start at 0 at the first step inside the scope, when the batch size
+        changes, and behind a step at t == 0.  uniforms: None (torch's global generator), a torch.Generator, or a callable uniforms(t) ->
+        a (G, 2) tensor of values in [0, 1), or (built-in reward) a (seed, offset) pair naming the head of the step's Philox range.
+        Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name:
+        ddim_sample at eta = 0, dpmpp_2m_sample, unipc_sample, ddim_reverse_sample (they draw no noise: duplicates would never
+        separate), a learned variance, known_region_scope, measurement_scope, dps_scope, loss_guidance_scope, use_gradient_method,
+        return_attn_weights, a batch that is no multiple of `particles`, and with the built-in reward denoised_fn.  WindowExecutor.begin
+        takes the built-in reward through its own keywords and refuses a reward_fn.  No claim about sample quality is made."""
+        base = self._bind(model)
+        K, lam, tau, sig = check_steering(reward_fn, measurement, particles, scale, ess_threshold, sigma_y)
+        if uniforms is not None and not (isinstance(uniforms, th.Generator) or callable(uniforms)):
+            raise ValueError("steering_scope: uniforms is None, a torch.Generator or a callable uniforms(t)")
+        meas = None
+        if measurement is not None:
+            sc, gr = _check_operator(sr_scale, gray)
+            if not th.is_tensor(measurement) or measurement.dim() != 5:
+                raise ValueError(f"steering_scope: measurement must be a (B, T, Cy, H / sr_scale, W / sr_scale) tensor, got "
+                                 f"{tuple(getattr(measurement, 'shape', ()))}")
+            B, T, Cy, Hs, Ws = measurement.shape
+            meas = dict(y=_f32(check_measurement(measurement, (B, T, 3, Hs * sc, Ws * sc), sc, gr), base.device), scale=sc, gray=gr, sigma_y=sig)
+        d = None if K == 1 or lam == 0.0 else dict(reward_fn=reward_fn, K=K, scale=lam, tau=tau, measurement=meas, uniforms=uniforms,
+                                                   B=None, done=False)
+        return _scoped(base, "steering", d, _engine_particles)
+
+    def _check_steered(self, model, row, eta, x, denoised_fn=None, return_attn_weights=False, use_gradient_method=False):
+        """The refusals of a step of sampler `row` inside steering_scope, by name, before anything touches the engine -> the scope's
+        setting, or None outside a scope (and inside one that is the plain step)."""
+        d = _scope(model, "steering")
+        if d is None:
+            return None
+        if row.noise is None or (row.eta and float(eta) == 0.0):
+            raise NotImplementedError(f"{row.step}{' at eta = 0' if row.noise is not None else ''} inside steering_scope is not served: the step "
+                                      "draws no noise, duplicated particles would never separate")
+        self._refuse_learned(x)
+        for other in ("known_region", "measurement", "dps", "loss_guidance"):
+            if _scope(model, other) is not None:
+                raise NotImplementedError(f"{other}_scope together with steering_scope is not served")
+        for flag, what in ((use_gradient_method, "use_gradient_method"), (return_attn_weights, "return_attn_weights"),
+                           (denoised_fn is not None and d["measurement"] is not None, "denoised_fn together with the built-in reward")):
+            if flag:
+                raise NotImplementedError(f"{what} inside steering_scope is not served")
+        if x.shape[0] % d["K"]:
+            raise ValueError(f"steering_scope: the batch of {x.shape[0]} items is no multiple of particles={d['K']}")
+        m = d["measurement"]
+        if m is not None and tuple(m["y"].shape) != measurement_shape(x.shape, m["scale"], m["gray"]):
+            raise ValueError(f"steering_scope: measurement {tuple(m['y'].shape)} against a step on {tuple(x.shape)} at sr_scale={m['scale']}, "
+                             f"gray={m['gray']}")
+        return d
+
+    def _steer_uniforms(self, d, t, G, dev):
+        """The step's uniforms -> a (G, 2) float64 device tensor, or a (seed, offset) pair (the engine's Philox stream)."""
+        src = d["uniforms"]
+        if callable(src):
+            u = src(t)
+            if isinstance(u, tuple) and len(u) == 2 and not th.is_tensor(u[0]):
+                if d["measurement"] is None:
+                    raise ValueError("steering_scope: a (seed, offset) pair of uniforms serves the built-in reward only")
+                return int(u[0]), int(u[1])
+            u = th.as_tensor(u)
+        else:
+            u = th.rand(G, 2, dtype=th.float64, generator=src)
+        if tuple(u.shape) != (G, 2) or not bool(((u >= 0) & (u < 1)).all()):
+            raise ValueError(f"steering_scope: uniforms must be a ({G}, 2) tensor of values in [0, 1)")
+        return u.to(device=dev, dtype=th.float64).contiguous()
+
+    def _steer_before(self, d, model, x, t, philox=None):
+        """In front of a steered step: a new chain's state, and with the built-in reward the step's uniforms -> what _steer_after needs."""
+        base = self._bind(model)
+        L, B = _lib.lib(), x.shape[0]
+        if d["B"] != B or d["done"]:
+            _lib.check(L.vd_particle_reset(base._handle, B))
+            d["B"], d["done"] = B, False
+        u = philox if (philox is not None and d["uniforms"] is None and d["measurement"] is not None) \
+            else self._steer_uniforms(d, t, B // d["K"], base.device)
+        if d["measurement"] is not None:
+            if isinstance(u, tuple):
+                _lib.check(L.vd_particle_draws(base._handle, None, u[0], u[1]))
+            else:
+                _lib.check(L.vd_particle_draws(base._handle, _lib.ptr(u), 0, 0))
+        return base, u
+
+    def _steer_after(self, d, held, out, t):
+        """Behind a steered step: with a reward_fn its call and vd_particle_apply on the step's tensors (in place); either way the state the
+        step returns beside its own dict."""
+        base, u = held
+        L = _lib.lib()
+        sample, xstart = out["sample"], out["pred_xstart"]
+        B, G = sample.shape[0], sample.shape[0] // d["K"]
+        tt = t.to(device=base.device, dtype=th.int64).contiguous()
+        final = bool((t == 0).any())
+        if d["measurement"] is None:
+            x0 = th.where((tt == 0).view(B, 1, 1, 1, 1), sample, xstart) if final else xstart
+            r = d["reward_fn"](x0, tt)
+            if not th.is_tensor(r) or tuple(r.shape) != (B,):
+                raise ValueError(f"steering_scope: reward_fn must return a ({B},) tensor, got {tuple(getattr(r, 'shape', ()))}")
+            r = r.detach().to(device=base.device, dtype=th.float64).contiguous()
+            if bool((th.isnan(r) | (r == math.inf)).any()):
+                raise ValueError("steering_scope: reward_fn returned NaN or +inf (-inf removes a particle; every other value must be finite)")
+            moved = [v for v in (sample, xstart) if v is not None]
+            arr = (ctypes.c_void_p * len(moved))(*[v.data_ptr() for v in moved])
+            _lib.check(L.vd_particle_apply(base._handle, B, sample[0].numel(), _lib.ptr(r), _lib.ptr(tt), _lib.ptr(u), arr, len(moved),
+                                           _lib.current_stream()))
+        extra = {"ancestors": th.empty(B, dtype=th.int32, device=base.device), "ess": th.empty(G, dtype=th.float64, device=base.device),
+                 "log_weights": th.empty(B, dtype=th.float64, device=base.device)}
+        chosen = th.empty(G, dtype=th.int32, device=base.device)
+        _lib.check(L.vd_particle_state(base._handle, B, _lib.ptr(extra["log_weights"]), None, _lib.ptr(extra["ancestors"]), _lib.ptr(chosen),
+                                       _lib.ptr(extra["ess"]), None))
+        if final:
+            extra["chosen"] = chosen
+            d["done"] = True
+        return extra
+
     def q_jump(self, x, t, latent_mask=None, noise=None, model=None):
         """This project's extension: one forward diffusion step x_{t-1} -> x_t at index t, the move RePaint's resampling walks back up
         with: on the frames with latent_mask == 1 (None: every frame) sqrt(1 - beta_t) x + sqrt(beta_t) noise, the other frames unchanged;
@@ -801,6 +983,23 @@ class GaussianDiffusion:
 
     def _step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
               return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
+        """p_sample (mode 0) / ddim_sample (mode 1) -> (sample, pred_xstart); inside steering_scope the plain step, then the scope's
+        reweighting and resampling of both tensors (self._last_steer holds what the step returns beside them)."""
+        self._last_steer = None
+        self._refuse_learned(x)                                    # the plain step's own first refusals, in front of the scope's as of everything else
+        _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
+        d = self._check_steered(model, _BY_ID[mode], eta, x, denoised_fn, return_attn_weights, use_gradient_method)
+        if d is None:
+            return self._plain_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                                    use_gradient_method, cfg_scale)
+        held = self._steer_before(d, model, x, t)
+        sample, xstart = self._plain_step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                                          use_gradient_method, cfg_scale)
+        self._last_steer = self._steer_after(d, held, {"sample": sample, "pred_xstart": xstart}, t)
+        return sample, xstart
+
+    def _plain_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise,
+                    return_attn_weights=False, use_gradient_method=False, cfg_scale=1.0):
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
@@ -1273,7 +1472,8 @@ class GaussianDiffusion:
         """'grad' and 'residual_norm' of the step just made inside dps_scope, 'grad' and (normalize) 'grad_norm' of one inside
         loss_guidance_scope; nothing outside them."""
         d = getattr(self, "_last_dps", None)
-        return {} if d is None else {k: d[k] for k in ("grad", "residual_norm", "grad_norm") if k in d}
+        return {**({} if d is None else {k: d[k] for k in ("grad", "residual_norm", "grad_norm") if k in d}),
+                **(getattr(self, "_last_steer", None) or {})}
 
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0, cfg_scale=1.0):
         """gaussian_diffusion.py:597-634."""
@@ -1294,6 +1494,15 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         for scope in (_SCOPES if row.up else ("dps", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
             _refuse(model, scope, row.step)
+        d = self._check_steered(model, row, 1.0, x, denoised_fn)
+        if d is not None:                                                         # dpmpp_2m_sde_sample inside steering_scope
+            held = self._steer_before(d, model, x, t, philox)
+            out = self._plain_scope_step(row, model, x, t, clip_denoised, denoised_fn, model_kwargs, noise, philox, **carry)
+            out.update(self._steer_after(d, held, out, t))
+            return out
+        return self._plain_scope_step(row, model, x, t, clip_denoised, denoised_fn, model_kwargs, noise, philox, **carry)
+
+    def _plain_scope_step(self, row, model, x, t, clip_denoised, denoised_fn, model_kwargs, noise=None, philox=None, **carry):
         if not row.known_region:
             _refuse(model, "known_region", row.step)
         if denoised_fn is not None:

@@ -48,7 +48,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 adaptive_distance="lpips", prefix_cache=False, suffix_skip=False, save_all_timesteps=False, cfg_scale=1.0,
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
                 measurement=None, sr_scale=1, gray=False, dps_zeta=None, loss_fn=None, cotangent_fn=None, loss_scale=None,
-                loss_normalize=False):
+                loss_normalize=False, particles=1, reward_fn=None, reward_scale=1.0, ess_threshold=0.5, particle_measurement=None,
+                sigma_y=None):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -123,7 +124,24 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     prediction, through the whole UNet (windows of at most 32 frames).  The function sees a WINDOW (B, Tw, 3, H, W), observed frames
     first, not the whole video.  Refused by name before the engine is touched: both or a missing loss_scale (ValueError),
     executor='graph', prefix_cache, suffix_skip, the samplers 'dpmpp_2m', 'dpmpp_2m_sde' and 'unipc', use_gradient_method, known_mask,
-    a measurement, cfg_scale != 1, cfg_rescale and dynamic_threshold.  Both None (default): no scope is entered."""
+    a measurement, cfg_scale != 1, cfg_rescale and dynamic_threshold.  Both None (default): no scope is entered.
+
+    particles, reward_fn, reward_scale, ess_threshold, particle_measurement, sigma_y (this project's extension: particle steering,
+    gradient-free guidance by resampling; gaussian_diffusion.py: steering_scope): with particles = K > 1 every video of the batch runs
+    as K consecutive items, every window's step loop inside steering_scope -- reward_fn(x0, t) on the WINDOW's x_0 prediction
+    (B K, Tw, 3, H, W), eager executor only, or the built-in reward of a noisy measurement particle_measurement = y over the WHOLE
+    video (the layout of `measurement`, operator sr_scale / gray, noise level sigma_y), gathered per window like x0, on both executors.
+    Behind each window the particle 'chosen' at t == 0 becomes that window's result for all K particles of its video, so the next window
+    conditions on one history; the return shape is unchanged.  With the built-in reward and sampler='dpmpp_2m_sde' the two executors
+    give equal bits.  Every sampler that draws noise, cfg_scale, cfg_rescale and dynamic_threshold are served, and windows of up to 128
+    frames.  Refused by name before the engine is touched: use_gradient_method, known_mask, a measurement (the exact projection),
+    dps_zeta, loss_fn / cotangent_fn, prefix_cache, suffix_skip, save_all_timesteps, a sampler that draws no noise ('ddim' at eta = 0,
+    'dpmpp_2m', 'unipc'), and a reward_fn with executor='graph'.  particles=1 (default): nothing of this runs."""
+    steer = _check_particles(particles, reward_fn, reward_scale, ess_threshold, particle_measurement, sigma_y, batch, sr_scale, gray, sampler, eta,
+                             executor, [("use_gradient_method", use_gradient_method), ("known_mask", known_mask is not None),
+                                        ("a measurement", measurement is not None), ("dps_zeta", dps_zeta is not None),
+                                        ("loss_fn / cotangent_fn", loss_fn is not None or cotangent_fn is not None), ("prefix_cache", prefix_cache),
+                                        ("suffix_skip", suffix_skip), ("save_all_timesteps", save_all_timesteps)])
     loss_guided = loss_fn is not None or cotangent_fn is not None
     # what a step that moves the latent frames behind the plain step (loss_guidance_scope, dps_scope) is not served with, in the order it is
     # refused; the three that dps_zeta leaves to the checks of the measurement below are marked
@@ -176,9 +194,13 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                                use_gradient_method=use_gradient_method, observed_frames=observed_frames, sampler=sampler, eta=eta,
                                executor=executor, adaptive_distance=adaptive_distance, prefix_cache=prefix_cache, suffix_skip=suffix_skip,
                                save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
-                               jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray)
+                               jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray,
+                               particles=particles, reward_fn=reward_fn, reward_scale=reward_scale, ess_threshold=ess_threshold,
+                               particle_measurement=particle_measurement, sigma_y=sigma_y)
     step_sampler = sampler if sampler in SAMPLERS and not SAMPLERS[sampler].up else "ddim"    # (the eager step: any other name is ddim_sample)
     adaptive = "adaptive" in mode
+    if steer is not None:                  # every video as K consecutive items; the return takes one of each group again
+        batch = batch.repeat_interleave(steer["K"], dim=0)
     B, T, C, H, W = batch.shape
     device = model.device
     samples = torch.zeros_like(batch).cpu()
@@ -244,6 +266,20 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         y_w = None
         if measurement is not None:    # ... and so is the window's share of the measurement
             y_w = gather_window(measurement_v, frame_indices).to(device)
+        if steer is not None:
+            pm_w = None if steer["y"] is None else gather_window(steer["y"], frame_indices).to(device)
+            if use_graph:
+                wex.begin(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, particles=steer["K"],
+                          reward_scale=steer["scale"], ess_threshold=steer["tau"], particle_measurement=pm_w, particle_sr_scale=sr_scale,
+                          particle_gray=gray, sigma_y=sigma_y)
+                local_samples = wex.run(diffusion.num_timesteps).clone()
+                chosen = wex.particle_state()["chosen"]
+            else:
+                local_samples, chosen = _eager_particle_window(model, diffusion, x0, model_kwargs, step_sampler, eta, cfg_scale, steer, pm_w,
+                                                               sr_scale, gray, sigma_y, t_tensors, timesteps)
+            write_back(_chosen_for_all(local_samples, chosen, steer["K"]))
+            model.check_device_errors()
+            continue
         if use_graph:
             # renoise=False: like the eager loop below (and scripts/video_sample.py:149-166), every step reads x_t_minus_1 = x0 as it is
             write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, known_src=k_src,
@@ -282,7 +318,55 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                     trace.append(local_samples.clone())
         write_back(local_samples, None if trace is None else torch.stack(trace, dim=1))
         model.check_device_errors()    # once per window (write_back has synchronised): a non-finite network output of any of its steps raises here
-    return samples.numpy(), all_timestep_samples.numpy()
+    return (samples if steer is None else samples[::steer["K"]]).numpy(), all_timestep_samples.numpy()
+
+
+def _check_particles(particles, reward_fn, reward_scale, ess_threshold, y, sigma_y, batch, sr_scale, gray, sampler, eta, executor, others):
+    """infer_video's particle keywords, checked before anything touches the engine -> dict K, scale, tau, reward_fn, y (the whole video's
+    measurement repeated per particle, on the host, or None), or None for the plain run (particles=1 or reward_scale=0)."""
+    from .gaussian_diffusion import check_steering
+    if particles == 1 and reward_fn is None and y is None:
+        return None
+    K, lam, tau, _ = check_steering(reward_fn, y, particles, reward_scale, ess_threshold, sigma_y)
+    y_v = None
+    if y is not None:
+        y_v = check_measurement(torch.as_tensor(y), batch.shape, sr_scale, gray).cpu()
+    for name, on in others:
+        if on:
+            raise NotImplementedError(f"{name} together with particles is not served")
+    row = SAMPLERS[sampler if sampler in SAMPLERS else "ddim"]
+    if row.noise is None or (row.eta and float(eta) == 0.0):
+        raise NotImplementedError(f"sampler='{sampler}'{' at eta = 0' if row.noise is not None else ''} together with particles is not served: the "
+                                  "step draws no noise, duplicated particles would never separate")
+    if reward_fn is not None and executor == "graph":
+        raise NotImplementedError("executor='graph' together with a reward_fn is not served: a Python callback between two steps cannot be "
+                                  "captured in a graph (the built-in reward can: particle_measurement=, sigma_y=)")
+    if K == 1 or lam == 0.0:
+        return None
+    return dict(K=K, scale=lam, tau=tau, reward_fn=reward_fn, y=None if y_v is None else y_v.repeat_interleave(K, dim=0))
+
+
+def _chosen_for_all(local, chosen, K):
+    """A window's result for all K particles of every video: the particle chosen at t == 0, repeated."""
+    G = local.shape[0] // K
+    picked = local.view(G, K, *local.shape[1:])[torch.arange(G, device=local.device), chosen.to(device=local.device, dtype=torch.int64)]
+    return picked.repeat_interleave(K, dim=0)
+
+
+def _eager_particle_window(model, diffusion, x0, model_kwargs, sampler, eta, cfg_scale, steer, y_w, sr_scale, gray, sigma_y, t_tensors, timesteps):
+    """One window of infer_video's eager executor inside steering_scope -> (the window's K samples per video, chosen (G,)).  A sampler
+    whose noise is the engine's Philox stream draws it, and the uniforms of the built-in reward, where the window executor would."""
+    local, carry, out = x0.clone(), None, None
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if SAMPLERS[sampler].noise == "philox" else None
+    with diffusion.steering_scope(model, steer["reward_fn"], particles=steer["K"], scale=steer["scale"], ess_threshold=steer["tau"],
+                                  measurement=y_w, sr_scale=sr_scale if y_w is not None else 1, gray=gray if y_w is not None else False,
+                                  sigma_y=sigma_y):
+        for timestep in timesteps:
+            philox = None if seed is None else (seed, (diffusion.num_timesteps - 1 - timestep) * local.numel())
+            out, carry = _sampler_step(diffusion, sampler, model, local, t_tensors[timestep], carry, cfg_scale, eta, philox,
+                                       clip_denoised=True, model_kwargs=model_kwargs)
+            local = out["sample"]
+    return local, out["chosen"]
 
 
 def video_known_region(batch, known_mask, known_video=None):
@@ -590,6 +674,19 @@ def build_parser():
                     help="with --loss_guidance: the step is S / ||grad||_2 per video, the norm over the window's generated frames")
     ap.add_argument("--loss_guidance_cotangent", action="store_true",
                     help="with --loss_guidance: FUNCTION returns d loss / d x_0 itself (float32, x_0's shape, on the device), no autograd")
+    ap.add_argument("--particles", type=int, default=1, metavar="K",
+                    help="particle steering (gradient-free guidance by resampling): every video runs as K particles that are reweighted by a "
+                         "reward on each step's x_0 prediction and resampled when their weights degenerate; needs --reward, or --measurement "
+                         "with --measurement_sigma; every sampler that draws noise; named in the run directory ('_smc<K>') when above 1")
+    ap.add_argument("--reward", default=None, metavar="MODULE:FUNCTION",
+                    help="with --particles: FUNCTION(x0, t) of the importable MODULE (the current directory is searched too) returns one reward "
+                         "per item of each window's x_0 prediction (B, Tw, 3, H, W); eager executor")
+    ap.add_argument("--reward_scale", type=float, default=1.0, metavar="L", help="with --particles: the weight of the reward, finite and not negative")
+    ap.add_argument("--measurement_sigma", type=float, default=None, metavar="SIGMA",
+                    help="with --particles and --measurement: the measurement carries Gaussian noise of this standard deviation and is the "
+                         "built-in reward -||y - A x_0||^2 / (2 SIGMA^2) of the particles, in place of the exact projection; both executors")
+    ap.add_argument("--ess_threshold", type=float, default=0.5, metavar="TAU",
+                    help="with --particles: resample when the effective sample size falls below TAU * K; in [0, 1]")
     ap.add_argument("--adaptive_distance", default="l2", choices=["l2", "lpips"],
                     help="adaptive-* modes: frame embedding for the farthest-point selection (lpips needs --lpips_weights)")
     add_lpips_arguments(ap)
@@ -603,8 +700,29 @@ def build_parser():
     return ap
 
 
+def check_particle_arguments(ap, args):
+    """The rules between --particles and its companions, as argparse errors naming the options."""
+    K, sigma = getattr(args, "particles", 1), getattr(args, "measurement_sigma", None)
+    uses = [name for name, on in (("--dps_zeta", getattr(args, "dps_zeta", None) is not None), ("--measurement_sigma", sigma is not None)) if on]
+    if len(uses) > 1:
+        ap.error(f"{' and '.join(uses)} are two uses of --measurement (the gradient step of DPS, the reward of --particles; without either, the "
+                 "exact projection): give one")
+    if K < 1:
+        ap.error("--particles K: at least 1")
+    if sigma is not None and not getattr(args, "measurement", None):
+        ap.error("--measurement_sigma needs --measurement Y.npy")
+    if sigma is not None and getattr(args, "reward", None):
+        ap.error("--reward and --measurement_sigma are two rewards for --particles: give one")
+    if K > 1 and sigma is None and not getattr(args, "reward", None):
+        ap.error("--particles needs a reward: --reward MODULE:FUNCTION, or --measurement Y.npy with --measurement_sigma SIGMA")
+    if K == 1 and (sigma is not None or getattr(args, "reward", None)):
+        ap.error("--reward and --measurement_sigma need --particles K with K above 1")
+    return args
+
+
 def main(argv=None):
-    return run(parse_with_lpips(build_parser(), argv))
+    ap = build_parser()
+    return run(check_particle_arguments(ap, parse_with_lpips(ap, argv)))
 
 
 def _known_options(args, batch):
@@ -641,11 +759,25 @@ def _measurement_options(args, batch):
         raise ValueError(f"{path}: --measurement is (N, T, Cy, H / S, W / S), got {y.shape}")
     T = batch.shape[1]
     rows = np.stack([np.asarray(y[i][:T], dtype=np.float32) for i in args._batch_ids])
+    if getattr(args, "measurement_sigma", None) is not None:          # the reward of --particles, not the projection
+        return dict(particle_measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)),
+                    sigma_y=float(args.measurement_sigma))
     return dict(measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)),
                 **({} if zeta is None else dict(dps_zeta=float(zeta))))
 
 
-def import_function(spec):
+def _particle_options(args):
+    """--particles and its companions -> infer_video's keywords ({} at the default K = 1); the measurement's share comes from
+    _measurement_options."""
+    K = int(getattr(args, "particles", 1))
+    if K == 1:
+        return {}
+    spec = getattr(args, "reward", None)
+    return dict(particles=K, reward_fn=import_function(spec, "--reward") if spec else None, reward_scale=float(getattr(args, "reward_scale", 1.0)),
+                ess_threshold=float(getattr(args, "ess_threshold", 0.5)))
+
+
+def import_function(spec, option="--loss_guidance"):
     """'MODULE:FUNCTION' -> the callable FUNCTION of the module importlib finds under the name MODULE; the current directory is searched
     like the rest of sys.path (a script run as `python -m` does not have it there).  ValueError for a spec of another form, a module that
     cannot be imported, or a name that is missing or not callable."""
@@ -653,16 +785,16 @@ def import_function(spec):
     import sys
     mod, sep, fn = str(spec).partition(":")
     if not (sep and mod and fn):
-        raise ValueError(f"--loss_guidance {spec!r}: expected MODULE:FUNCTION")
+        raise ValueError(f"{option} {spec!r}: expected MODULE:FUNCTION")
     if os.getcwd() not in sys.path and "" not in sys.path:
         sys.path.append(os.getcwd())
     try:
         module = importlib.import_module(mod)
     except ImportError as e:
-        raise ValueError(f"--loss_guidance {spec!r}: cannot import module {mod!r}: {e}") from e
+        raise ValueError(f"{option} {spec!r}: cannot import module {mod!r}: {e}") from e
     f = getattr(module, fn, None)
     if not callable(f):
-        raise ValueError(f"--loss_guidance {spec!r}: module {mod!r} has no callable {fn!r}")
+        raise ValueError(f"{option} {spec!r}: module {mod!r} has no callable {fn!r}")
     return f
 
 
@@ -692,13 +824,15 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        prefix_cache=getattr(args, "prefix_cache", False), suffix_skip=getattr(args, "suffix_skip", False),
                        save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
                        cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None),
-                       **_known_options(args, batch), **_measurement_options(args, batch), **_loss_guidance_options(args))
+                       **_known_options(args, batch), **_measurement_options(args, batch), **_loss_guidance_options(args),
+                       **_particle_options(args))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
-    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'), and a --loss_guidance ('_lg0.5': its scale) -- samples of different samplers or guidance settings never share a directory, and a run
+    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'), a --loss_guidance ('_lg0.5': its scale) and --particles
+    above 1 ('_smc8') -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
@@ -717,8 +851,9 @@ def run_postfix(args):
     lg = ""
     if getattr(args, "loss_guidance", None):      # '_lg0.5' (the function is not named: a run directory is one function's)
         lg = "_lg" + ("None" if getattr(args, "loss_guidance_scale", None) is None else f"{float(args.loss_guidance_scale):g}")
+    smc = f"_smc{int(args.particles)}" if int(getattr(args, "particles", 1) or 1) > 1 else ""      # '_smc8': the particles of a video
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
-        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas + lg
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas + lg + smc
 
 
 def run(args, create=None, device=None, infer=None):
