@@ -1013,6 +1013,41 @@ int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W,
 /* Stem backward: dcols [nfr][H*W][64] (k = tap * stem channels + channel) -> dx [nfr][3][H][W]; cond_mode 0 channel, 1 duplicate / all, 2 t=0. */
 int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, const float* km, int nfr, int H, int W,
                       int cond_mode, float* dx, void* stream);
+/* What lies between those kernels in the backward-data pass.
+ * The backward image of a forward weight -- the operator d out / d in of the layer as a forward layer of its own -- by the one function
+ * vd_load_weight_bwd packs with.  host_w: [O][I] (linear layer, 1x1 conv) or OIHW (3x3), O and I the FORWARD's outputs and inputs.  kind:
+ *   0 linear        W^T [I][O] as vd_pack_linear_split(N = I, K = O)
+ *   1 stem          the matrix [k = tap * I + i][o], rows 9 I .. 63 zero, as vd_pack_linear_split(N = 64, K = O)
+ *   2 Winograd conv w'[i][o][t] = w[o][i][8 - t] (transposed, rotated by 180 degrees) as vd_pack_conv3_wino_split(O' = I, I' = O)
+ *   3 generic conv  the same kernel as [tap][I][O] floats
+ * vd_bwd_image_floats: floats of the image (-1: no such kind or shape).  Host only. */
+long long vd_bwd_image_floats(int kind, int O, int I);
+int vd_pack_weight_bwd(const float* host_w, int kind, int O, int I, float* host_out);
+/* The two matrix-product calls of the pass, with the engine's own argument setup, in the process' arithmetic; VD_MATH=fp32 is refused
+ * as vd_set_bwd_weight_storage refuses it.  out[nfr][H][H][cout_bwd] = conv3x3 (stride 1, padding 1) of dy [nfr][H][H][cin_bwd] with
+ * the image w_bwd (kind 2 | 3, on the device; cin_bwd = the forward's O, cout_bwd = its I) + res (or NULL; res == out is allowed: the
+ * Downsample branch accumulates in place).  Kind 2 is offered split-K scratch by the engine's rule (allocated for the call, which then
+ * waits for the stream).  vd_op_linear_bwd_data: out[M][N] = dy[M][K] * image (kind 0: K = O, N = I; kind 1: N = 64) + res. */
+int vd_op_conv3_bwd_data(const float* dy, int nfr, int H, int cin_bwd, const void* w_bwd, int kind, int cout_bwd, const float* res, float* out,
+                         void* stream);
+int vd_op_linear_bwd_data(const float* dy, int M, int K, const void* w_bwd, const float* res, float* out, int N, void* stream);
+/* y[n][2oy][2ox][c] = x[n][oy][ox][c], zero elsewhere (x [nfr][Ho][Wo][C], y [nfr][2Ho][2Wo][C]): the Downsample conv's backward is a
+ * stride-1 conv of this.  sumpool2: y[n][oy][ox][c] (+)= ((b00 + b01) + b10) + b11 of the 2x2 block of x [nfr][2Ho][2Wo][C]: the
+ * nearest x2 upsample's backward.  add: y (+)= x, n % 4 == 0.  C % 4 == 0; enqueued only. */
+int vd_op_zero_stuff2(const float* x, int nfr, int Ho, int Wo, int C, float* y, void* stream);
+int vd_op_sumpool2(const float* x, int nfr, int Ho, int Wo, int C, int accumulate, float* y, void* stream);
+int vd_op_add(const float* x, long long n, int accumulate, float* y, void* stream);
+/* g *= s in place, s = 2^k with max |g| s in [1, 2) (k clamped to +-100; s = 1 when the maximum is 0 or not below 3e38; a NaN does not
+ * enter the maximum and stays); gs (4 floats on the device) receives {s, 1 / s, the bits of max |g|, 0}.  Enqueued only. */
+int vd_op_grad_rescale(float* g, long long n, float* gs, void* stream);
+/* The two guidance passes of vd_guided_step on caller's tensors [B][per] (per = T frames of per / T elements), the engine's schedule
+ * table; no network.  guided_grad: d loss / d eps, the direct part of d loss / d x, the unguided mean and pred_xstart (the last two
+ * may be NULL).  guided_final: g = dxd + dx_net * gs[1], mean_out = mean - 10 alpha_t g / 2, sample = mean_out + [t != 0] sigma_t
+ * noise2; grad, mean_out and sample may be NULL.  A t[b] outside the schedule writes NaN rows; a non-finite x_0 sets VD_ERR_NONFINITE. */
+int vd_op_guided_grad(vd_engine* e, int B, int T, long long per, const float* x, const float* eps, const float* noise, const float* x_t_minus_1,
+                      const float* obs, const long long* t, int clip_denoised, float* deps, float* dxd, float* mean, float* xstart, void* stream);
+int vd_op_guided_final(vd_engine* e, int B, int T, long long per, const long long* t, const float* dxd, const float* mean, const float* dx_net,
+                       const float* gs, const float* noise2, float* grad, float* mean_out, float* sample, void* stream);
 /* The kernels that build what the network is conditioned on (csrc/misc.hip), each through the launcher the forward pass calls and
  * with the arguments in the forward pass' form.  Enqueued only.
  * out[i] = [cos(t[i] f_j) | sin(t[i] f_j)], j < dim / 2, and a zero last column when dim is odd (timestep_embedding / frame_embedding,

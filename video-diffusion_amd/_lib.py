@@ -294,7 +294,17 @@ SIGNATURES = {
     "vd_op_attn_spatial_bwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "vd_op_out_conv_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_stem_col2im": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "vd_op_sinus_embed": (_I, [_P, _I, _I, _P, _P, _P]),
+    "vd_bwd_image_floats": (_L, [_I, _I, _I]),
+    "vd_pack_weight_bwd": (_I, [_P, _I, _I, _I, _P]),
+    "vd_op_conv3_bwd_data": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "vd_op_linear_bwd_data": (_I, [_P, _I, _I, _P, _P, _P, _I, _P]),
+    "vd_op_zero_stuff2": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "vd_op_sumpool2": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "vd_op_add": (_I, [_P, _L, _I, _P, _P]),
+    "vd_op_grad_rescale": (_I, [_P, _L, _P, _P]),
+    "vd_op_guided_grad": (_I, [_P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "vd_op_guided_final": (_I, [_P, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vd_op_sinus_embed":(_I, [_P, _I, _I, _P, _P, _P]),
     "vd_op_frame_t": (_I, [_P, _I, _I, _I, _P, _P]),
     "vd_op_rpe_hidden": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _L, _P]),
     "vd_op_rpe_table": (_I, [_P, _P, _I, _I, _I, _F, _F, _F, _P, _P]),

@@ -86,6 +86,50 @@ static bool split_math() { return math_mode() != MATH_FP32; }
 
 constexpr int STEM_KPAD = 64;          // im2col width of the 5-channel 3x3 stem (45 real columns)
 
+// ---- the backward-data image of one forward weight (vd_load_weight_bwd, vd_pack_weight_bwd): the operator d out / d in of a layer as
+// a forward layer of its own.  O, I: the FORWARD's outputs and inputs.
+enum BwdKind { BWD_LINEAR = 0, BWD_STEM = 1, BWD_CONV3_WINO = 2, BWD_CONV3_GENERIC = 3 };
+
+// floats of the image
+static size_t bwd_image_floats(int kind, size_t O, size_t I) {
+    if (kind == BWD_STEM) return (size_t)STEM_KPAD * O * 3 / 2 + 2 * STEM_KPAD;      // split image of [STEM_KPAD][O]
+    if (kind == BWD_LINEAR) return I * O * 3 / 2 + 2 * I;                            // split image of W^T [I][O]
+    if (kind == BWD_CONV3_WINO) return 16 * I * O * 3 / 2 + 2 * I;                   // Winograd-split image of I kernels over O channels
+    return 9 * I * O;                                                                // [tap][I][O]
+}
+
+// host: forward weight ([O][I] linear / 1x1, OIHW 3x3) -> out[bwd_image_floats()]
+static void pack_weight_bwd(const float* host, int kind, int O, int I, float* out) {
+    if (kind == BWD_STEM) {                            // forward lin[o][k = tap*I + i]; backward matrix [k][o], rows 9 I .. STEM_KPAD - 1 zero
+        std::vector<float> lt((size_t)STEM_KPAD * O, 0.f);
+        for (int o = 0; o < O; ++o)
+            for (int i = 0; i < I; ++i)
+                for (int t = 0; t < 9; ++t) lt[(size_t)(t * I + i) * O + o] = host[((size_t)o * I + i) * 9 + t];
+        pack_linear_split(lt.data(), reinterpret_cast<unsigned short*>(out), STEM_KPAD, O, STEM_KPAD, 0);
+    } else if (kind == BWD_LINEAR) {                   // W[O][I] -> W^T[I][O]
+        std::vector<float> wt((size_t)O * I);
+        for (int o = 0; o < O; ++o)
+            for (int i = 0; i < I; ++i) wt[(size_t)i * O + o] = host[(size_t)o * I + i];
+        pack_linear_split(wt.data(), reinterpret_cast<unsigned short*>(out), I, O, I, 0);
+    } else {                                           // w'[i][o][ky][kx] = w[o][i][2-ky][2-kx]
+        std::vector<float> wr((size_t)O * I * 9);
+        for (int o = 0; o < O; ++o)
+            for (int i = 0; i < I; ++i)
+                for (int t = 0; t < 9; ++t) wr[((size_t)i * O + o) * 9 + t] = host[((size_t)o * I + i) * 9 + (8 - t)];
+        if (kind == BWD_CONV3_WINO) {
+            pack_conv3_wino_split(wr.data(), reinterpret_cast<unsigned short*>(out), I, O);
+        } else {                                       // generic kernel: [tap][Cout' = I][Cin' = O]
+            for (int i = 0; i < I; ++i)
+                for (int o = 0; o < O; ++o)
+                    for (int t = 0; t < 9; ++t) out[((size_t)t * I + i) * O + o] = wr[((size_t)i * O + o) * 9 + t];
+        }
+    }
+}
+
+static int bwd_kind_of(const Param& p) {
+    return p.kind == PK_STEM ? BWD_STEM : p.kind_bwd == PK_LINF ? BWD_LINEAR : p.kind_bwd == PK_CONV3W ? BWD_CONV3_WINO : BWD_CONV3_GENERIC;
+}
+
 struct Arena {
     char* base = nullptr;
     size_t cap = 0, used = 0, peak = 0;     // cap: bytes this arena may hand out (the workspace up to its tail; 0 = unchecked)
@@ -714,11 +758,7 @@ int vd_engine::build() {
     size_t offb = 0;
     for (auto& p : params) {
         if (p.kind_bwd < 0) continue;
-        const size_t O = (size_t)p.shape[1], I = (size_t)p.shape[0];          // outputs / inputs of the BACKWARD operator
-        if (p.kind == PK_STEM) p.packed_bwd = (size_t)STEM_KPAD * I * 3 / 2 + 2 * STEM_KPAD;
-        else if (p.kind_bwd == PK_LINF) p.packed_bwd = O * I * 3 / 2 + 2 * O;
-        else if (p.kind_bwd == PK_CONV3W) p.packed_bwd = 16 * O * I * 3 / 2 + 2 * O;
-        else p.packed_bwd = 9 * O * I;
+        p.packed_bwd = bwd_image_floats(bwd_kind_of(p), (size_t)p.shape[0], (size_t)p.shape[1]);
         p.off_bwd = offb;
         offb += (p.packed_bwd + 3) & ~(size_t)3;
     }
@@ -1418,12 +1458,33 @@ struct GradMap {
 };
 }  // namespace
 
+// The argument setup of bwd_linear / bwd_conv3, shared with vd_op_linear_bwd_data / vd_op_conv3_bwd_data: w_bwd is the backward image
+// (vd_pack_weight_bwd)
+static IgemmArgs bwd_linear_args(const float* dy, int M, int Kb, int Nb, const float* w_bwd, const float* resid, float* out) {
+    IgemmArgs g = linear_args(M, Kb, Nb);
+    g.src0 = dy; g.wfrag = w_bwd; g.wsplit = 1; g.res = resid; g.out = out;
+    return g;
+}
+
+// floats of split-K scratch a backward 3x3 conv is offered (the Winograd-split image only)
+static size_t bwd_conv3_scratch(const Arena& ar, int kind_bwd, Tens dy, int N, int cout_bwd) {
+    return kind_bwd == PK_CONV3W ? ksplit_scratch(ar, N, dy.H, dy.C, cout_bwd) : 0;
+}
+
+static IgemmArgs bwd_conv3_args(Tens dy, int N, int kind_bwd, const float* w_bwd, int cout_bwd, const float* resid, float* out, float* ksplit_ws,
+                                size_t ksplit_ws_floats) {
+    IgemmArgs g = conv_args(dy, nullptr, N, 3, 1, 0);
+    g.ksplit_ws = ksplit_ws; g.ksplit_ws_floats = ksplit_ws_floats;
+    if (kind_bwd == PK_CONV3W) { g.wwino = w_bwd; g.wsplit = 2; } else { g.w = w_bwd; g.wsplit = 0; }
+    g.res = resid; g.res_ld = cout_bwd; g.out = out; g.ldo = cout_bwd; g.Cout = cout_bwd;
+    return g;
+}
+
 // out[M][K_fwd] = dy[M][N_fwd] * W  (+ res): the forward's split GEMM over the transposed image of parameter pw
 int vd_engine::bwd_linear(const float* dy, int M, int pw, const float* resid, float* out, hipStream_t st) {
     const Param& p = params[pw];
     const int Kb = (int)p.shape[0], Nb = p.kind == PK_STEM ? STEM_KPAD : (int)p.shape[1];
-    IgemmArgs g = linear_args(M, Kb, Nb);
-    g.src0 = dy; g.wfrag = WB(pw); g.wsplit = 1; g.res = resid; g.out = out;
+    const IgemmArgs g = bwd_linear_args(dy, M, Kb, Nb, WB(pw), resid, out);
     VD_REQUIRE(gemm_split_supported(g), "backward linear layer: shape not covered by gemm_split.hip");
     return launch_igemm(g, st);
 }
@@ -1431,15 +1492,12 @@ int vd_engine::bwd_linear(const float* dy, int M, int pw, const float* resid, fl
 // out[N][H][H][cout_bwd] = conv3x3_s1(dy, rotated transposed kernel of parameter pw) (+ res, in place allowed)
 int vd_engine::bwd_conv3(Tens dy, int N, int pw, int cout_bwd, const float* resid, float* out, hipStream_t st, Arena& ar) {
     const Param& p = params[pw];
-    IgemmArgs g = conv_args(dy, nullptr, N, 3, 1, 0);
     const size_t mk = ar.mark();
-    const size_t ksf = p.kind_bwd == PK_CONV3W ? ksplit_scratch(ar, N, dy.H, dy.C, cout_bwd) : 0;
-    g.ksplit_ws = ksf ? ar.get<float>(ksf) : nullptr; g.ksplit_ws_floats = ksf;
+    const size_t ksf = bwd_conv3_scratch(ar, p.kind_bwd, dy, N, cout_bwd);
+    float* ksw = ksf ? ar.get<float>(ksf) : nullptr;
     ar.release(mk);
     if (ar.dry) return 0;
-    if (p.kind_bwd == PK_CONV3W) { g.wwino = WB(pw); g.wsplit = 2; } else { g.w = WB(pw); g.wsplit = 0; }
-    g.res = resid; g.res_ld = cout_bwd; g.out = out; g.ldo = cout_bwd; g.Cout = cout_bwd;
-    return launch_igemm(g, st);
+    return launch_igemm(bwd_conv3_args(dy, N, p.kind_bwd, WB(pw), cout_bwd, resid, out, ksw, ksf), st);
 }
 
 int vd_engine::backward(const FwdIn& in, const float* deps, float* dx, hipStream_t st, Arena& ar) {
@@ -3101,31 +3159,7 @@ int vd_load_weight_bwd(vd_engine* e, const char* name, const float* host, long l
     if (p.kind_bwd < 0) return 0;
     VD_REQUIRE((long long)p.numel == numel, "size mismatch");
     std::vector<float> tmp((size_t)p.packed_bwd, 0.f);
-    const int O = (int)p.shape[0], I = (int)p.shape[1];
-    if (p.kind == PK_STEM) {                           // forward lin[o][k = tap*I + i]; backward matrix [k][o]
-        std::vector<float> lt((size_t)STEM_KPAD * O, 0.f);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i)
-                for (int t = 0; t < 9; ++t) lt[(size_t)(t * I + i) * O + o] = host[((size_t)o * I + i) * 9 + t];
-        pack_linear_split(lt.data(), reinterpret_cast<unsigned short*>(tmp.data()), STEM_KPAD, O, STEM_KPAD, 0);
-    } else if (p.kind_bwd == PK_LINF) {                // W[O][I] -> W^T[I][O]
-        std::vector<float> wt((size_t)O * I);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i) wt[(size_t)i * O + o] = host[(size_t)o * I + i];
-        pack_linear_split(wt.data(), reinterpret_cast<unsigned short*>(tmp.data()), I, O, I, 0);
-    } else {                                           // w'[i][o][ky][kx] = w[o][i][2-ky][2-kx]
-        std::vector<float> wr((size_t)O * I * 9);
-        for (int o = 0; o < O; ++o)
-            for (int i = 0; i < I; ++i)
-                for (int t = 0; t < 9; ++t) wr[((size_t)i * O + o) * 9 + t] = host[((size_t)o * I + i) * 9 + (8 - t)];
-        if (p.kind_bwd == PK_CONV3W) {
-            pack_conv3_wino_split(wr.data(), reinterpret_cast<unsigned short*>(tmp.data()), I, O);
-        } else {                                       // generic kernel: [tap][Cout' = I][Cin' = O]
-            for (int i = 0; i < I; ++i)
-                for (int o = 0; o < O; ++o)
-                    for (int t = 0; t < 9; ++t) tmp[((size_t)t * I + i) * O + o] = wr[((size_t)i * O + o) * 9 + t];
-        }
-    }
+    pack_weight_bwd(host, bwd_kind_of(p), (int)p.shape[0], (int)p.shape[1], tmp.data());
     float* dst = e->wbuf_bwd + p.off_bwd;
     if (e->wbuf_bwd_on_host) std::memcpy(dst, tmp.data(), p.packed_bwd * sizeof(float));
     else VD_HIP(hipMemcpy(dst, tmp.data(), p.packed_bwd * sizeof(float), hipMemcpyHostToDevice));
@@ -3924,6 +3958,86 @@ int vd_op_out_conv_bwd(const float* deps, const float* w, int nfr, int H, int W,
 int vd_op_stem_col2im(const float* dcols, const float* obs, const float* lat, const float* km, int nfr, int H, int W,
                       int cond_mode, float* dx, void* stream) {
     return launch_stem_col2im(dcols, obs, lat, km, nfr, H, W, STEM_KPAD, cond_mode, dx, static_cast<hipStream_t>(stream));
+}
+
+// ---- what lies between those kernels in backward(): the weight images, the two matrix-product calls, resampling, rescale, guidance
+static const char* kBwdSplitOnly = "use_gradient_method runs on the split arithmetic only (VD_MATH=f16x3 | bf16x6)";
+
+long long vd_bwd_image_floats(int kind, int O, int I) {
+    if (kind < BWD_LINEAR || kind > BWD_CONV3_GENERIC || O <= 0 || I <= 0) return -1;
+    return (long long)bwd_image_floats(kind, (size_t)O, (size_t)I);
+}
+
+int vd_pack_weight_bwd(const float* host_w, int kind, int O, int I, float* host_out) {
+    VD_REQUIRE(host_w && host_out && kind >= BWD_LINEAR && kind <= BWD_CONV3_GENERIC && O > 0 && I > 0, "vd_pack_weight_bwd: weight, image, kind 0..3 and a positive shape");
+    VD_REQUIRE(kind != BWD_STEM || 9 * I <= STEM_KPAD, "vd_pack_weight_bwd: a stem of at most 7 input channels");
+    VD_REQUIRE(kind == BWD_CONV3_GENERIC || (O % 32 == 0 && (kind == BWD_STEM || I % 32 == 0)), "vd_pack_weight_bwd: split images need multiples of 32");
+    VD_REQUIRE(kind != BWD_CONV3_WINO || I % 64 == 0, "vd_pack_weight_bwd: the Winograd-split image needs a multiple of 64 forward inputs");
+    std::fill(host_out, host_out + bwd_image_floats(kind, (size_t)O, (size_t)I), 0.f);
+    pack_weight_bwd(host_w, kind, O, I, host_out);
+    return 0;
+}
+
+int vd_op_conv3_bwd_data(const float* dy, int nfr, int H, int cin_bwd, const void* w_bwd, int kind, int cout_bwd, const float* res, float* out,
+                         void* stream) {
+    VD_REQUIRE(split_math(), kBwdSplitOnly);
+    VD_REQUIRE(dy && w_bwd && out && nfr > 0 && H > 0 && cin_bwd > 0 && cout_bwd > 0, "vd_op_conv3_bwd_data: tensors and a positive shape");
+    VD_REQUIRE(kind == BWD_CONV3_WINO || kind == BWD_CONV3_GENERIC, "vd_op_conv3_bwd_data: kind 2 (Winograd-split image) or 3 ([tap][Cout'][Cin'])");
+    const int pk = kind == BWD_CONV3_WINO ? (int)PK_CONV3W : (int)PK_CONV3;
+    const Tens t{const_cast<float*>(dy), cin_bwd, H};
+    OpScratch ws(stream);
+    float* ksw = nullptr;
+    const size_t ksf = bwd_conv3_scratch(Arena{}, pk, t, nfr, cout_bwd);
+    if (ksf)
+        if (int rc = ws.get(&ksw, ksf)) return rc;
+    return launch_igemm(bwd_conv3_args(t, nfr, pk, static_cast<const float*>(w_bwd), cout_bwd, res, out, ksw, ksf), ws.st);
+}
+
+int vd_op_linear_bwd_data(const float* dy, int M, int K, const void* w_bwd, const float* res, float* out, int N, void* stream) {
+    VD_REQUIRE(split_math(), kBwdSplitOnly);
+    VD_REQUIRE(dy && w_bwd && out && M > 0 && K > 0 && N > 0, "vd_op_linear_bwd_data: tensors and a positive shape");
+    const IgemmArgs g = bwd_linear_args(dy, M, K, N, static_cast<const float*>(w_bwd), res, out);
+    VD_REQUIRE(gemm_split_supported(g), "backward linear layer: shape not covered by gemm_split.hip");
+    return launch_igemm(g, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_zero_stuff2(const float* x, int nfr, int Ho, int Wo, int C, float* y, void* stream) {
+    VD_REQUIRE(x && y && nfr > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "vd_op_zero_stuff2: channels in 16-byte units");
+    return launch_zero_stuff2(x, nfr, Ho, Wo, C, y, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_sumpool2(const float* x, int nfr, int Ho, int Wo, int C, int accumulate, float* y, void* stream) {
+    VD_REQUIRE(x && y && nfr > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "vd_op_sumpool2: channels in 16-byte units");
+    return launch_sumpool2(x, nfr, Ho, Wo, C, accumulate, y, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_add(const float* x, long long n, int accumulate, float* y, void* stream) {
+    VD_REQUIRE(x && y && n > 0, "vd_op_add: tensors and a positive count");
+    return launch_add(x, (size_t)n, accumulate, y, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_grad_rescale(float* g, long long n, float* gs, void* stream) {
+    VD_REQUIRE(g && gs && n > 0, "vd_op_grad_rescale: the gradient, four words and a positive count");
+    return launch_grad_rescale(g, (size_t)n, gs, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_guided_grad(vd_engine* e, int B, int T, long long per, const float* x, const float* eps, const float* noise, const float* x_t_minus_1,
+                      const float* obs, const long long* t, int clip, float* deps, float* dxd, float* mean, float* xstart, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && per > 0 && per % T == 0 && x && eps && noise && x_t_minus_1 && obs && t && deps && dxd, "vd_op_guided_grad: arguments");
+    GuidedArgs ga{x, eps, noise, x_t_minus_1, obs, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)per, clip, deps, dxd, mean, xstart};
+    ga.err = e->d_err;
+    return launch_guided_grad(ga, static_cast<hipStream_t>(stream));
+}
+
+int vd_op_guided_final(vd_engine* e, int B, int T, long long per, const long long* t, const float* dxd, const float* mean, const float* dx_net,
+                       const float* gs, const float* noise2, float* grad, float* mean_out, float* sample, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && per > 0 && per % T == 0 && t && dxd && mean && dx_net && gs && (!sample || noise2), "vd_op_guided_final: arguments");
+    GuidedArgs ga{nullptr, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, (long)per, 0,
+                  nullptr, const_cast<float*>(dxd), const_cast<float*>(mean), nullptr};
+    ga.gscale = gs;
+    return launch_guided_final(ga, dx_net, noise2, grad, mean_out, sample, static_cast<hipStream_t>(stream));
 }
 
 // ---- the kernels that build what the network is conditioned on (misc.hip), through the launchers forward() calls
