@@ -690,6 +690,40 @@ int vd_op_particle_weights(int G, int K, double lambda, double ess_threshold, co
                            double* logw, double* rprev, int* ancestors, int* chosen, double* ess, long long* counters, void* stream);
 int vd_op_particle_gather(int B, long long per, const int* ancestors, float* const* tensors, int n, void* stream);
 
+/* Deblurring -- this project's extension: DPS (vd_dps_step) and the built-in reward of particle steering (vd_set_particles) for a
+ * convolution measurement y = w * x_0 + noise (blur.hip).  w is ONE real k x k kernel, k odd, 1 <= k <= 15, applied to every channel plane
+ * of every frame; the output has the plane's size, with zeros outside the plane; the orientation is torch's conv2d (correlation), c = k / 2:
+ *   (A x)[i][j]   = sum_{a,b} w[a][b] x[i + a - c][j + b - c]
+ *   (A^T r)[p][q] = sum_{a,b} w[a][b] r[p - a + c][q - b + c]      (the exact adjoint, which is why the padding is zeros)
+ * y has the video's shape [B][T][3][H][W].  w need not be symmetric, normalised or non-negative.  Every sum over the taps runs in fp32 in one
+ * fixed order -- a ascending, inside it b ascending, acc = acc + w[a][b] v with the product and the sum each rounded, never fused.
+ * vd_set_blur_kernel: engine state.  k == 0 clears it (refused while vd_set_particle_blur is on); otherwise k*k finite taps on the HOST,
+ *   row-major, not all zero, copied into an engine-owned device buffer whose address never changes; waits for the device.
+ *   vd_blur_kernel: 1 and *k when a kernel is installed, else 0.
+ * vd_deblur_step: vd_dps_step on the installed kernel -- its argument list without scale and gray, its seven steps with
+ *   3. r = y - A x_0 on the frames in L_b, rho_b = sqrt(sum r^2) folded as there (fp64, fixed order, independent of B, no atomics);
+ *   4. q = -(A^T r) / rho_b (0 where rho_b == 0 or L_b is empty), then q_r, d eps and d_x as there;
+ *   its outputs, its workspace and its refusals under the name "deblur"; it also fails while no kernel is installed.  Eager steps only.
+ * vd_op_deblur_seed: steps 2-4 alone on a caller's (x_t, eps) and taps ON THE DEVICE, on frames of H x W (any size), no network; outputs as
+ *   vd_op_dps_seed.  vd_op_blur: out = A x (adjoint == 0) or A^T x of a [B][T][3][H][W] tensor, out != x; no engine.
+ *   16-byte accesses while W % 4 == 0 and the tensors are 16-byte aligned, else element by element: same bits.
+ * vd_set_particle_blur: on != 0 (a kernel must be installed) makes the installed kernel the operator of the built-in reward of
+ *   vd_set_particles: y then has the video's shape and the scale and gray handed to vd_set_particles are not read (hand scale 1 with
+ *   gray).  The residual pass runs inside the step's launches and is captured into a window graph; the graph's key carries k, and taps
+ *   changed between two windows at equal k act without a new capture.  vd_particle_blur: the switch. */
+int vd_set_blur_kernel(vd_engine* e, const float* taps_host, int k);
+int vd_blur_kernel(vd_engine* e, int* k);
+int vd_deblur_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                   const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, int clip_denoised,
+                   int sampler, float eta, const float* noise, const float* y, float zeta, float* sample, float* pred_xstart,
+                   float* grad, float* residual_norm, void* stream);
+int vd_op_deblur_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, const float* eps, const long long* t, int clip_denoised,
+                      const float* y, const float* latent_mask, const float* taps_dev, int k, float* d_eps, float* d_x, float* rho,
+                      float* pred_xstart, void* stream);
+int vd_op_blur(int B, int T, int H, int W, const float* x, const float* taps_dev, int k, int adjoint, float* out, void* stream);
+int vd_set_particle_blur(vd_engine* e, int on);
+int vd_particle_blur(vd_engine* e);
+
 /* Loss-guided sampling -- this project's extension: a reverse step moved down the gradient, with respect to x_t, of ANY differentiable
  * function of the step's x_0 prediction.  The function is the caller's own code: vd_dps_step is split in two around the point where the
  * cotangent of x_0 is formed, and the taped forward survives between the two calls.  Per item b, with L_b its frames with

@@ -390,6 +390,11 @@ struct vd_engine {
     const float* part_y = nullptr;
     int part_scale = 1, part_gray = 0;
     double part_sigma = 0.0;
+    // the blur kernel (vd_set_blur_kernel; blur_k 0: none): k x k taps in an engine-owned buffer of kMaxBlurTaps^2 floats whose address never
+    // changes, so a window graph that reads it follows a change of taps at equal k.  part_blur (vd_set_particle_blur): the built-in
+    // reward's operator is this kernel (blur.hip), y has the video's shape, and part_scale / part_gray are not read.
+    float* d_blur_taps = nullptr;
+    int blur_k = 0, part_blur = 0;
     double *d_part_logw = nullptr, *d_part_rprev = nullptr, *d_part_ess = nullptr;
     int *d_part_anc = nullptr, *d_part_chosen = nullptr;
     long long* d_part_counters = nullptr;
@@ -423,6 +428,7 @@ struct vd_engine {
         const float* meas_y; int meas_scale, meas_gray;           // measurement: the projection pass a graph holds reads y (null: none)
         const float* part_y; int part_K, part_scale, part_gray;   // particle steering: the three passes a graph ends in and their constants (part_K 0: none)
         double part_lambda, part_tau, part_sigma;
+        int part_blur_k;                                          // ... with the blur kernel as the reward's operator: its size (0: the cell mean); the taps' address is fixed
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -478,7 +484,7 @@ struct vd_engine {
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
         for (void* p : {(void*)d_part_logw, (void*)d_part_rprev, (void*)d_part_ess, (void*)d_part_anc, (void*)d_part_chosen,
                         (void*)d_part_counters, (void*)d_part_scratch, (void*)d_part_r, (void*)d_part_partials, (void*)d_part_x0,
-                        (void*)d_part_sel})
+                        (void*)d_part_sel, (void*)d_blur_taps})
             if (p) (void)hipFree(p);
         for (auto& g : win_graphs) g.release();
     }
@@ -2105,6 +2111,9 @@ struct StepReq {
     double part_lambda = 0.0, part_tau = 0.0, part_sigma = 0.0;
     const double* part_uni = nullptr;
     unsigned long long part_seed = 0, part_offset = 0;
+    // ... with the blur kernel as the reward's operator (part_blur_k 0: the cell mean at part_scale, part_gray)
+    const float* part_taps = nullptr;
+    int part_blur_k = 0;
 };
 
 // The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
@@ -2140,10 +2149,15 @@ static int particle_launches(vd_engine* e, const StepReq& r, const int64_t* t, s
     VD_REQUIRE(r.part_y && r.sample && r.xstart, "particle steering: a step hands out its sample and its pred_xstart");
     VD_REQUIRE(!r.pp && !r.sp, "particle steering (vd_set_particles) together with the window prefix cache or suffix skip is not served");
     VD_REQUIRE(e->part_B == B && e->part_state_K == K && e->d_part_sel && e->part_sel_nt == e->num_timesteps, "particle steering: no state for this batch (vd_particle_reset)");
-    DpsArgs da{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_scale, r.part_gray, 0,
-               e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
     int nblk = 0, rc;
-    {
+    if (r.part_blur_k) {                                         // blur.hip's residual pass, handed the same tensors and rows
+        BlurArgs ba{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_taps, r.part_blur_k, 0,
+                    e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * r.part_blur_k * r.part_blur_k * B * per, 4.0 * B * per * 4.0, st, "particle_blur_residual");
+        if ((rc = launch_blur_residual(ba, &nblk, st))) return rc;
+    } else {
+        DpsArgs da{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_scale, r.part_gray, 0,
+                   e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
         ProfScope ps(PC_ELEMENTWISE, 2.0 * B * per, 4.0 * B * per * 2.0, st, "particle_residual");
         if ((rc = launch_dps_residual(da, &nblk, st))) return rc;
     }
@@ -2305,7 +2319,7 @@ static int particle_state_reset(vd_engine* e, int B) {
 static int ensure_particle_ws(vd_engine* e, int B, int T, bool x0) {
     const int S = e->cfg.image_size, sc = e->part_scale;
     const size_t per = (size_t)T * 3 * S * S;
-    int rc = e->grow(e->d_part_r, e->part_r_cap, (size_t)B * T * (e->part_gray ? 1 : 3) * (S / sc) * (S / sc), true);
+    int rc = e->grow(e->d_part_r, e->part_r_cap, e->part_blur ? (size_t)B * per : (size_t)B * T * (e->part_gray ? 1 : 3) * (S / sc) * (S / sc), true);
     if (!rc) rc = e->grow(e->d_part_partials, e->part_partials_cap, (size_t)B * dps_partials_per_item(), true);
     if (!rc) rc = e->grow(e->d_part_scratch, e->part_scratch_cap, 2 * (size_t)B * per, true);
     if (!rc && x0) rc = e->grow(e->d_part_x0, e->part_x0_cap, (size_t)B * per, true);
@@ -2359,6 +2373,7 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
         r.part_K = e->part_K; r.part_y = e->part_y; r.part_scale = e->part_scale; r.part_gray = e->part_gray;
         r.part_lambda = e->part_lambda; r.part_tau = e->part_tau; r.part_sigma = e->part_sigma;
         r.part_uni = e->part_uni; r.part_seed = e->part_seed; r.part_offset = e->part_offset;
+        if (e->part_blur) { r.part_taps = e->d_blur_taps; r.part_blur_k = e->blur_k; }
     }
     return step_launches(e, r, st);
 }
@@ -2603,6 +2618,7 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     if (k.part_K > 1) {                                          // the uniforms come from the window's own Philox pair (r.rng)
         r.part_K = k.part_K; r.part_y = k.part_y; r.part_scale = k.part_scale; r.part_gray = k.part_gray;
         r.part_lambda = k.part_lambda; r.part_tau = k.part_tau; r.part_sigma = k.part_sigma;
+        r.part_taps = e->d_blur_taps; r.part_blur_k = k.part_blur_k;
         if (!r.xstart) r.xstart = e->d_part_x0;
     }
     if (!rc) rc = step_launches(e, r, st);
@@ -2684,6 +2700,7 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     if (e->part_K > 1) {
         key.part_y = e->part_y; key.part_K = e->part_K; key.part_scale = e->part_scale; key.part_gray = e->part_gray;
         key.part_lambda = e->part_lambda; key.part_tau = e->part_tau; key.part_sigma = e->part_sigma;
+        key.part_blur_k = e->part_blur ? e->blur_k : 0;
     }
     if (e->meas_y) { key.meas_y = e->meas_y; key.meas_scale = e->meas_scale; key.meas_gray = e->meas_gray; }
     e->win_cur = -1;
@@ -2878,6 +2895,46 @@ int vd_set_particles(vd_engine* e, int K, double lambda, double ess_threshold, c
 }
 
 int vd_particles(vd_engine* e) { return e && e->part_K > 1 ? e->part_K : 0; }
+
+// ---- the blur kernel (blur.hip): engine state; the taps live in the engine, at an address that never changes
+int vd_set_blur_kernel(vd_engine* e, const float* taps_host, int k) {
+    VD_REQUIRE(e, "null engine");
+    if (k == 0) {
+        VD_REQUIRE(!e->part_blur, "vd_set_blur_kernel: the built-in reward of particle steering reads the kernel (vd_set_particle_blur): switch that off first");
+        e->blur_k = 0;
+        return 0;
+    }
+    VD_REQUIRE(blur_served(k), "blur: the kernel is k x k with k odd and 1 <= k <= 15");
+    VD_REQUIRE(taps_host, "vd_set_blur_kernel: null taps");
+    bool nonzero = false;
+    for (int i = 0; i < k * k; ++i) {
+        VD_REQUIRE(std::isfinite(taps_host[i]), "blur: the taps must be finite");
+        nonzero |= taps_host[i] != 0.f;
+    }
+    VD_REQUIRE(nonzero, "blur: the taps must not all be zero");
+    if (!e->d_blur_taps) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_blur_taps), kMaxBlurTaps * kMaxBlurTaps * sizeof(float)));
+    VD_HIP(hipDeviceSynchronize());                  // a step that reads the taps may still run, on any stream
+    VD_HIP(hipMemcpy(e->d_blur_taps, taps_host, (size_t)k * k * sizeof(float), hipMemcpyHostToDevice));
+    e->blur_k = k;
+    return 0;
+}
+
+int vd_blur_kernel(vd_engine* e, int* k) {
+    if (k) *k = e ? e->blur_k : 0;
+    return e && e->blur_k ? 1 : 0;
+}
+
+// The built-in reward of particle steering on the installed blur kernel in place of the cell mean: y (vd_set_particles) then has the
+// video's shape, and the scale and gray handed to vd_set_particles are not read.  Runs inside the step's launches and is captured into a
+// window graph, whose key carries k.
+int vd_set_particle_blur(vd_engine* e, int on) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(!on || e->blur_k, "vd_set_particle_blur: no kernel is installed (vd_set_blur_kernel)");
+    e->part_blur = on ? 1 : 0;
+    return 0;
+}
+
+int vd_particle_blur(vd_engine* e) { return e && e->part_blur ? 1 : 0; }
 
 int vd_particle_reset(vd_engine* e, int B) {
     VD_REQUIRE(e && e->part_K > 1, "vd_particle_reset: no particles are set (vd_set_particles)");
@@ -3304,6 +3361,69 @@ int vd_op_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, con
     DpsArgs da{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, scale, gray ? 1 : 0, clip,
                rbuf, part, deps, dxd, xstart, rho, e->d_err};
     return launch_dps_seed(da, static_cast<hipStream_t>(stream));
+}
+
+// vd_dps_step on the installed blur kernel (vd_set_blur_kernel): y has the video's shape, the residual and seed passes are blur.hip's, and
+// everything else -- the taped forward, the sampler pass, the backward-data pass, the final pass and the outputs -- is that entry's.
+int vd_deblur_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                   const long long* fidx, const long long* t, int obs_mode, int clip, int sampler, float eta, const float* noise,
+                   const float* y, float zeta, float* sample, float* xstart, float* grad, float* residual_norm, void* stream) {
+    if (int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes)) return rc;
+    if (int rc = check_diff(e, B, T, "deblur")) return rc;
+    VD_REQUIRE(sampler == SAMPLER_P || sampler == SAMPLER_DDIM, "deblur: p_sample (0) or ddim_sample (1), got sampler " + std::to_string(sampler));
+    VD_REQUIRE(sampler == SAMPLER_P || eta >= 0.f, "eta");
+    VD_REQUIRE(zeta >= 0.f && zeta <= 3.4028234e38f, "deblur: zeta must be finite and not negative");
+    VD_REQUIRE(e->blur_k, "deblur: no kernel is installed (vd_set_blur_kernel)");
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && noise && y && sample && xstart, "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = e->cfg.image_size, k = e->blur_k;
+    const size_t per = (size_t)T * 3 * S * S;
+    const DiffWs w(e, B, T);
+    VD_REQUIRE(w.partials_fit((size_t)B * dps_partials_per_item()), "deblur: window too small for its partial sums");
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, nullptr};
+    return taped_pass(e, w, in, t, st, no_pre, [&](const FwdIn& fi, Arena& ar) {
+        SamplerPassArgs pa = pass_args(e, sampler, B, (long long)per, x, t, clip, sample, xstart);
+        pa.eps = fi.eps; pa.eta = eta; pa.noise = noise;
+        int rc;
+        { ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st); rc = launch_sampler_pass(pa, st); }
+        if (!rc) {
+            BlurArgs ba{x, fi.eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, S, S, e->d_blur_taps, k, clip,
+                        w.r(), w.partials(), w.deps(), w.dxd(), nullptr, residual_norm, e->d_err};
+            ProfScope ps(PC_ELEMENTWISE, 4.0 * k * k * B * per, 4.0 * B * per * 9.0, st, "deblur_seed");
+            rc = launch_blur_seed(ba, st);
+        }
+        if (!rc) rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+        if (!rc) rc = e->backward(fi, w.deps(), w.dx_net(), st, ar);
+        if (!rc) {
+            ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "dps_final");
+            rc = launch_dps_final(w.dxd(), w.dx_net(), w.gscale(), lat, B, T, (long)(per / T), zeta, sample, grad, st);
+        }
+        return rc;
+    });
+}
+
+// The residual and seed passes of vd_deblur_step alone, on a caller's (x_t, eps) and taps on the device: no network, no workspace of the
+// engine (tests).
+int vd_op_deblur_seed(vd_engine* e, int B, int T, int H, int W, const float* x, const float* eps, const long long* t, int clip,
+                      const float* y, const float* lat, const float* taps_dev, int k, float* deps, float* dxd, float* rho, float* xstart,
+                      void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0 && x && eps && t && y && lat && taps_dev && deps && dxd, "arguments");
+    VD_REQUIRE(blur_served(k), "blur: the kernel is k x k with k odd and 1 <= k <= 15");
+    OpScratch sc(stream);
+    float* rbuf; double* part;
+    int rc = sc.get(&rbuf, (size_t)B * T * 3 * H * W);
+    if (!rc) rc = sc.get(&part, (size_t)B * dps_partials_per_item());
+    if (rc) return rc;
+    BlurArgs ba{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, taps_dev, k, clip,
+                rbuf, part, deps, dxd, xstart, rho, e->d_err};
+    return launch_blur_seed(ba, static_cast<hipStream_t>(stream));
+}
+
+// out = A x (adjoint == 0) or A^T x of a [B][T][3][H][W] tensor for taps on the device; out != x.  No engine.
+int vd_op_blur(int B, int T, int H, int W, const float* x, const float* taps_dev, int k, int adjoint, float* out, void* stream) {
+    VD_REQUIRE(B > 0 && T > 0, "blur: shape");
+    return launch_blur_apply(x, taps_dev, k, adjoint, (size_t)B * T * 3, H, W, out, static_cast<hipStream_t>(stream));
 }
 
 // ---- loss guidance: vd_dps_step split where the cotangent is formed, the caller's own code running between the two halves

@@ -634,6 +634,37 @@ int launch_dps_residual(DpsArgs a, int* nblk, hipStream_t s);
 int launch_dps_final(const float* dxd, const float* dx_net, const float* gs, const float* lat, int B, int T, long frame_elems, float zeta,
                      float* sample, float* grad, hipStream_t s);
 
+// Deblurring (blur.hip; this project's extension): DPS and the built-in reward of particle steering on the measurement y = w * x_0 + noise
+// of one real k x k kernel w (k odd, 1 <= k <= kMaxBlurTaps), applied to every channel plane of every frame at "same" size with zeros
+// outside the plane, oriented as torch's conv2d.  Tensors and y are [B][T][3][H][W].  launch_blur_seed is launch_dps_seed for this
+// operator -- r = y - A x_0, rho_b, and q = -(A^T r) / rho_b in place of -r_cell / (rho_b n_c); everything else, the poisoning of an item
+// whose t[b] lies outside the schedule included, as DpsArgs states it.  `taps`: k*k floats on the device, row-major.
+constexpr int kMaxBlurTaps = 15;
+inline bool blur_served(int k) { return k >= 1 && k <= kMaxBlurTaps && (k & 1); }
+struct BlurArgs {
+    const float* x;         // x_t
+    const float* eps;       // the network output
+    const float* y;
+    const float* lat;
+    const int64_t* t;       // [B] respaced index
+    const float* tab; int num_timesteps;
+    int B, T, H, W;
+    const float* taps; int k;
+    int clip;
+    float* r;               // scratch: y's shape
+    double* part;           // scratch: [B][dps_partials_per_item()]
+    float* deps; float* dxd;
+    float* xstart;          // the x_0 prediction of every frame (the sampler pass's bits), or null
+    float* rho;             // [B], or null
+    int* err;               // the engine's sticky error word, or null
+    int nblk = 0;           // set by launch_blur_seed: partials per item of this launch
+};
+int launch_blur_seed(BlurArgs a, hipStream_t s);
+// the residual pass of launch_blur_seed alone: r and part; *nblk = the partials per item it wrote
+int launch_blur_residual(BlurArgs a, int* nblk, hipStream_t s);
+// out = A x (adjoint == 0) or A^T x of `planes` planes of H x W; out != x
+int launch_blur_apply(const float* x, const float* taps, int k, int adjoint, size_t planes, int H, int W, float* out, hipStream_t s);
+
 // Particle steering (particles.hip; this project's extension, Feynman-Kac steering: Singhal et al. 2025): B = G*K items, item g*K + k is
 // particle k of group g.  launch_particle_weights, one block per group: the weight update logw += lambda (r - rprev) from the items' rewards
 // (`rewards`, or r = -(sum_j part[b][j]) * inv_two_var, the partials folded in index order), p = softmax(logw), ess = 1 / sum p^2, and --

@@ -33,7 +33,8 @@ import torch as th
 
 from . import _lib
 from .gaussian_diffusion import (SAMPLERS, _check_operator, _engine_measurement, _engine_particles, _engine_region, _refuse, _scope,
-                                 check_known_region, check_measurement, check_steering, measurement_shape)
+                                 check_blur_kernel, check_blur_measurement, check_known_region, check_measurement, check_steering,
+                                 measurement_shape)
 
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
@@ -76,17 +77,20 @@ class WindowExecutor:
             bufs["known_mask"] = th.zeros(B, T, S, S, dtype=th.float32, device=self.model.device)
         return bufs["known_src"], bufs["known_mask"]
 
-    def _measurement_buffer(self, B, T, scale, gray):
-        """The window's measurement, one buffer per (B, T, scale, gray): a stable address, so one graph per shape and operator."""
-        bufs, key = self._buffers(B, T), f"measurement_s{scale}_g{int(gray)}"
+    def _measurement_buffer(self, B, T, scale, gray, blur=False):
+        """The window's measurement, one buffer per (B, T, scale, gray) and one for a blurred one (the video's shape): a stable address, so
+        one graph per shape and operator."""
+        bufs, key = self._buffers(B, T), "measurement_blur" if blur else f"measurement_s{scale}_g{int(gray)}"
         if key not in bufs:
             S = self.model.image_size
-            bufs[key] = th.zeros(*measurement_shape((B, T, 3, S, S), scale, gray), dtype=th.float32, device=self.model.device)
+            shape = (B, T, 3, S, S) if blur else measurement_shape((B, T, 3, S, S), scale, gray)
+            bufs[key] = th.zeros(*shape, dtype=th.float32, device=self.model.device)
         return bufs[key]
 
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
               known_src=None, known_mask=None, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
-              ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, cfg_scale=1.0):
+              ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, blur_kernel=None,
+              cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -125,6 +129,12 @@ class WindowExecutor:
         inside `diffusion.steering_scope(..., measurement=)` takes the scope's setting.  A reward_fn -- the keyword, or the scope's -- is
         refused by name: a Python callback cannot be captured.  Refused by name too: a sampler that draws no noise ('ddim' at eta = 0,
         'dpmpp_2m', 'unipc', 'ddim_reverse'), a known region, a measurement, prefix_cache, suffix_skip, B no multiple of particles.
+        blur_kernel (this project's extension; gaussian_diffusion.py: deblur_scope): with particle_measurement, the built-in reward's
+        operator is this (k, k) blur in place of the cell mean -- particle_measurement then has the window's own shape, and
+        particle_sr_scale and particle_gray stay at their defaults.  The taps are copied into the engine's own buffer, whose address never
+        changes: the graph's signature carries k alone, and a begin() with other taps of the same size replays the same graph on the new
+        taps.  They stay there until the next kernel is installed (another begin() with a blur, a deblur_scope, a steering_scope with a
+        blur), so run() the window before that.
         A begin() inside `diffusion.dps_scope(...)` is refused by name: a DPS step runs a backward pass and is eager only; so is one
         inside `diffusion.loss_guidance_scope(...)`, whose step runs the caller's Python between two launches."""
         cfg_scale = float(cfg_scale)
@@ -137,9 +147,10 @@ class WindowExecutor:
         if (known_src is None) != (known_mask is None):
             raise ValueError("known_src and known_mask are given together")
         _refuse(self.model, "dps", "WindowExecutor.begin")               # before anything touches the engine
+        _refuse(self.model, "deblur", "WindowExecutor.begin")
         _refuse(self.model, "loss_guidance", "WindowExecutor.begin")     # (a Python callback between two launches cannot be captured)
         steer = self._steering(x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, particle_measurement, particle_sr_scale,
-                               particle_gray, sigma_y, known_src is not None or _scope(self.model, "known_region") is not None,
+                               particle_gray, sigma_y, blur_kernel, known_src is not None or _scope(self.model, "known_region") is not None,
                                measurement is not None or _scope(self.model, "measurement") is not None)
         scope = _scope(self.model, "known_region")
         if known_src is not None:
@@ -203,7 +214,7 @@ class WindowExecutor:
                 meas = dict(meas, y=yb)
             if steer is not None:
                 pm = steer["measurement"]
-                yb = self._measurement_buffer(B, T, pm["scale"], pm["gray"])
+                yb = self._measurement_buffer(B, T, pm["scale"], pm["gray"], pm.get("kernel") is not None)
                 if pm["y"].is_cuda:
                     pm["y"].record_stream(self.stream)
                 yb.copy_(pm["y"])
@@ -260,13 +271,16 @@ class WindowExecutor:
         self._gen = int(_lib.lib().vd_window_generation(self.model._handle))
         return self
 
-    def _steering(self, x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, y, sr_scale, gray, sigma_y, region, meas):
+    def _steering(self, x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, y, sr_scale, gray, sigma_y, blur_kernel, region,
+                  meas):
         """begin()'s particle keywords, or the enclosing steering_scope's setting, checked before anything touches the engine -> a steering
         dict (gaussian_diffusion.py: _engine_particles) or None (the plain window)."""
         scope = _scope(self.model, "steering")
         if reward_fn is not None or (scope is not None and scope["measurement"] is None and particles == 1):
             raise NotImplementedError("WindowExecutor.begin with a reward_fn is not served: a Python callback between two steps cannot be "
                                       "captured in a graph (the built-in reward can: particle_measurement=, sigma_y=)")
+        if blur_kernel is not None and y is None:
+            raise ValueError("WindowExecutor.begin: blur_kernel is the operator of the built-in reward: it needs particle_measurement= and sigma_y=")
         if particles == 1 and y is None:
             if scope is None:
                 return None
@@ -275,12 +289,21 @@ class WindowExecutor:
             if y is None:
                 raise ValueError("WindowExecutor.begin: particles > 1 needs particle_measurement= and sigma_y= (the built-in reward)")
             K, lam, tau, sig = check_steering(None, y, particles, reward_scale, ess_threshold, sigma_y)
-            sc, gr = _check_operator(sr_scale, gray)
+            if blur_kernel is not None:
+                if not (sr_scale == 1 and gray is False):
+                    raise ValueError("WindowExecutor.begin: blur_kernel together with particle_sr_scale or particle_gray is not served: "
+                                     "leave them at their defaults")
+                sc, gr, w = 1, False, check_blur_kernel(blur_kernel)
+            else:
+                (sc, gr), w = _check_operator(sr_scale, gray), None
             if K == 1 or lam == 0.0:
                 return None
-            d = dict(K=K, scale=lam, tau=tau, measurement=dict(y=y, scale=sc, gray=gr, sigma_y=sig))
+            d = dict(K=K, scale=lam, tau=tau, measurement=dict(y=y, scale=sc, gray=gr, sigma_y=sig, kernel=w))
         m = d["measurement"]
-        m = dict(m, y=check_measurement(m["y"], x_init.shape, m["scale"], m["gray"]))
+        if m.get("kernel") is not None:
+            m = dict(m, y=check_blur_measurement(m["y"], x_init.shape))
+        else:
+            m = dict(m, y=check_measurement(m["y"], x_init.shape, m["scale"], m["gray"]))
         row = SAMPLERS.get(sampler, SAMPLERS["ddim"])
         if row.noise is None or (row.eta and float(eta) == 0.0):
             raise NotImplementedError(f"sampler={sampler!r}{' at eta = 0' if row.noise is not None else ''} together with particles is not served: "
@@ -361,12 +384,13 @@ class WindowExecutor:
 
     def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, known_src=None, known_mask=None,
                       jump_length=1, n_resample=1, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
-                      ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, cfg_scale=1.0):
+                      ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, blur_kernel=None,
+                      cfg_scale=1.0):
         """All num_timesteps steps of one window (with a known region and n_resample > 1: the walk of run_repaint); returns a fresh tensor."""
         self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale, known_src=known_src,
                    known_mask=known_mask, measurement=measurement, sr_scale=sr_scale, gray=gray, particles=particles, reward_fn=reward_fn,
                    reward_scale=reward_scale, ess_threshold=ess_threshold, particle_measurement=particle_measurement,
-                   particle_sr_scale=particle_sr_scale, particle_gray=particle_gray, sigma_y=sigma_y)
+                   particle_sr_scale=particle_sr_scale, particle_gray=particle_gray, sigma_y=sigma_y, blur_kernel=blur_kernel)
         if int(n_resample) != 1:
             return self.run_repaint(jump_length, n_resample).clone()
         return self.run(self.diffusion.num_timesteps).clone()

@@ -30,6 +30,8 @@ that overwrites the known pixels of the latent frames with the known content noi
 is the forward step of its resampling walk and `repaint_sample_loop` the loop around both.  Zero-shot restoration is the last one
 (DDNM): inside `GaussianDiffusion.measurement_scope` the x_0 prediction of every step is projected onto a degraded copy y of the video,
 x_0 + A^+(y - A x_0), for the cell-mean operators A of `measure` -- super-resolution, colourisation, or both (csrc/measure.hip).
+Deblurring (this project's extension too): `GaussianDiffusion.deblur_scope` is DPS, and `steering_scope(..., blur_kernel=)` the built-in
+reward of particle steering, for a measurement y = blur(video, w) + noise under one real k x k kernel w (csrc/blur.hip).
 Training losses are out of scope.
 """
 import contextlib
@@ -232,13 +234,13 @@ def check_known_region(known_src, known_mask):
 
 # the scopes that keep their setting on the model, as attribute _<name> -- in the order a step inside a later one refuses the earlier
 # ones -- and what a refusal raises
-_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "loss_guidance": _lib.VdError,
-           "steering": NotImplementedError}
+_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "deblur": _lib.VdError,
+           "loss_guidance": _lib.VdError, "steering": NotImplementedError}
 
 
 def _scope(model, name):
     """What the innermost <name>_scope set on this model, or None: known_region (dict src, mask, noise), measurement (dict y, scale, gray),
-    dps (dict y, scale, gray, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize), steering (dict reward_fn, K, scale, tau,
+    dps (dict y, scale, gray, zeta), deblur (dict y, kernel, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize), steering (dict reward_fn, K, scale, tau,
     measurement, uniforms and the chain's bookkeeping)."""
     return getattr(getattr(model, "model", model), "_" + name, None)
 
@@ -346,6 +348,88 @@ def check_zeta(zeta):
     return z
 
 
+MAX_BLUR_SIZE = 15
+
+
+def check_blur_kernel(kernel):
+    """The checks of a blur kernel (no engine): a 2-D square tensor or array of odd size <= 15, every tap finite, not all of them zero --
+    ValueError naming the rule otherwise.  Returns the taps as a contiguous float32 host tensor (k, k)."""
+    try:
+        w = kernel.detach().cpu() if th.is_tensor(kernel) else th.as_tensor(np.asarray(kernel))
+    except Exception as exc:
+        raise ValueError(f"blur_kernel must be a 2-D square tensor or array, got {type(kernel).__name__}") from exc
+    if w.dim() != 2 or w.shape[0] != w.shape[1] or w.shape[0] == 0:
+        raise ValueError(f"blur_kernel must be 2-D and square (k, k), got {tuple(w.shape)}")
+    k = int(w.shape[0])
+    if k % 2 == 0:
+        raise ValueError(f"blur_kernel: the size k={k} must be odd (the kernel has a centre tap)")
+    if k > MAX_BLUR_SIZE:
+        raise ValueError(f"blur_kernel: the size k={k} must be at most {MAX_BLUR_SIZE}")
+    if w.dtype == th.bool or not (w.dtype.is_floating_point or w.dtype in (th.int8, th.int16, th.int32, th.int64, th.uint8)):
+        raise ValueError(f"blur_kernel must hold real numbers, got {w.dtype}")
+    w = w.to(th.float32).contiguous()
+    if not bool(th.isfinite(w).all()):
+        raise ValueError("blur_kernel must be finite: a tap is NaN or Inf (or beyond float32)")
+    if not bool((w != 0).any()):
+        raise ValueError("blur_kernel must not be all zero: the measurement would carry nothing")
+    return w
+
+
+def gaussian_kernel(size, sigma):
+    """The (size, size) Gaussian blur kernel exp(-(i^2 + j^2) / (2 sigma^2)) around the centre tap, normalised to sum 1 in float64 and
+    rounded once to float32.  size odd, 1 <= size <= 15; sigma positive and finite; ValueError otherwise."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= int(size) <= MAX_BLUR_SIZE or int(size) % 2 == 0:
+        raise ValueError(f"gaussian_kernel: size={size!r} must be an odd integer in [1, {MAX_BLUR_SIZE}]")
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not (math.isfinite(float(sigma)) and float(sigma) > 0.0):
+        raise ValueError(f"gaussian_kernel: sigma={sigma!r} must be positive and finite")
+    ax = th.arange(int(size), dtype=th.float64) - int(size) // 2
+    g = th.exp(-(ax * ax) / (2.0 * float(sigma) ** 2))
+    w = g[:, None] * g[None, :]
+    return (w / w.sum()).to(th.float32)
+
+
+def blur(video, kernel):
+    """A on the host, in torch: video (B, T, 3, H, W) -> y of the same shape, every channel plane of every frame correlated with the
+    (k, k) kernel as torch.nn.functional.conv2d does it, at "same" size with zeros outside the plane.  How a caller makes the y of
+    `deblur_scope` from a video; float64 in, float64 out (the taps are taken as given when they are float64 too), anything else float32."""
+    if not th.is_tensor(video) or video.dim() != 5 or video.shape[2] != 3:
+        raise ValueError(f"blur: a (B, T, 3, H, W) tensor, got {tuple(getattr(video, 'shape', ()))}")
+    w32 = check_blur_kernel(kernel)
+    dt = th.float64 if video.dtype == th.float64 else th.float32
+    w = kernel.detach().to(device=video.device, dtype=dt) if (th.is_tensor(kernel) and kernel.dtype == th.float64 and dt == th.float64) \
+        else w32.to(device=video.device, dtype=dt)
+    B, T, C, H, W = video.shape
+    k = int(w.shape[0])
+    out = th.nn.functional.conv2d(video.to(dt).reshape(B * T * C, 1, H, W), w.reshape(1, 1, k, k), padding=k // 2)
+    return out.reshape(B, T, C, H, W).contiguous()
+
+
+def check_blur_measurement(y, shape):
+    """The checks of a blurred measurement against the video `shape` (B, T, 3, H, W) it constrains: y is a tensor of that very shape and
+    every value of it is finite -- ValueError naming the rule otherwise.  Returns y as contiguous float32, on the device it came on."""
+    if len(shape) != 5 or shape[2] != 3:
+        raise ValueError(f"a video is (B, T, 3, H, W), got {tuple(shape)}")
+    if not th.is_tensor(y) or tuple(y.shape) != tuple(int(v) for v in shape):
+        raise ValueError(f"y must have the video's shape {tuple(int(v) for v in shape)} under a blur, got {tuple(getattr(y, 'shape', ()))}")
+    y = y.to(th.float32).contiguous()
+    if not bool(th.isfinite(y).all()):
+        raise ValueError("y must be finite: a measurement holds no NaN and no Inf")
+    return y
+
+
+def _engine_blur(model, _=None):
+    """Engine state <- the blur kernel the scopes on this model hold: the steering scope's when its built-in reward runs on one, else the
+    deblur scope's, else none.  Both scopes call this on the way in and on the way out, so whatever order they nest in the engine holds
+    what the innermost step needs.  Clearing leaves the taps in the engine's buffer: a window graph armed before keeps reading them."""
+    s, d = _scope(model, "steering"), _scope(model, "deblur")
+    m = None if s is None else s["measurement"]
+    w = m["kernel"] if (m is not None and m.get("kernel") is not None) else (None if d is None else d["kernel"])
+    if w is None:
+        _lib.check(_lib.lib().vd_set_blur_kernel(model._handle, None, 0))
+    else:
+        _lib.check(_lib.lib().vd_set_blur_kernel(model._handle, _lib.ptr(w), int(w.shape[0])))
+
+
 def _scale_number(v, what="scale"):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
         raise ValueError(f"loss_guidance_scope: {what}={v!r}: the step size must be a number, or a callable scale(t) returning one or a (B,) tensor")
@@ -410,17 +494,33 @@ def check_steering(reward_fn, measurement, particles, scale, ess_threshold, sigm
 
 
 def _engine_particles(model, d):
-    """Engine state <- a steering dict or None (clear).  The next steered step inside starts a chain (vd_particle_reset)."""
+    """Engine state <- a steering dict or None (clear).  The next steered step inside starts a chain (vd_particle_reset).  A built-in
+    reward on a blur (measurement['kernel']) also installs the kernel and switches the reward's operator (vd_set_particle_blur); the
+    switch is taken back, and the kernel an enclosing deblur_scope holds put back, by the next call here -- model._particle_blur keeps
+    whether it is on, so that a setting without a blur makes the calls it always made."""
     L = _lib.lib()
+    m = None if d is None else d["measurement"]
+    blurred = m is not None and m.get("kernel") is not None
+    was = getattr(model, "_particle_blur", False)
+    if was:
+        _lib.check(L.vd_set_particle_blur(model._handle, 0))
+        model._particle_blur = False
     if d is None:
         _lib.check(L.vd_set_particles(model._handle, 0, 0.0, 0.0, None, 1, 0, 0.0))
-        return
-    m = d["measurement"]
-    d["B"] = None
-    if m is None:
-        _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], None, 1, 0, 0.0))
     else:
-        _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0, m["sigma_y"]))
+        d["B"] = None
+        if m is None:
+            _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], None, 1, 0, 0.0))
+        elif blurred:                      # y has the video's shape; the engine reads neither scale nor gray (vd_set_particle_blur)
+            _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), 1, 1, m["sigma_y"]))
+        else:
+            _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0, m["sigma_y"]))
+    if blurred:
+        _lib.check(L.vd_set_blur_kernel(model._handle, _lib.ptr(m["kernel"]), int(m["kernel"].shape[0])))
+        _lib.check(L.vd_set_particle_blur(model._handle, 1))
+        model._particle_blur = True
+    elif was:
+        _engine_blur(model)
 
 
 def _cfg_scope_or_null(diffusion, model, cfg_scale):
@@ -452,6 +552,8 @@ class GaussianDiffusion:
     """gaussian_diffusion.py:107-172 (tables) + the sampling methods."""
 
     measure = staticmethod(measure)          # diffusion.measure(video, scale, gray): the y of measurement_scope from a video
+    blur = staticmethod(blur)                # diffusion.blur(video, kernel): the y of deblur_scope from a video
+    gaussian_kernel = staticmethod(gaussian_kernel)
 
     def __init__(self, *, betas, model_mean_type, model_var_type, loss_type, rescale_timesteps=False):
         self.model_mean_type = model_mean_type
@@ -684,7 +786,7 @@ class GaussianDiffusion:
         return _scoped(base, "dps", d)
 
     def _moved_step_window(self, scope, model, x, t, denoised_fn, model_kwargs, return_attn_weights, use_gradient_method, cfg_scale):
-        """The opening of a step inside dps_scope / loss_guidance_scope (`scope`: 'dps' / 'loss_guidance'), which runs the plain step and then
+        """The opening of a step inside dps_scope / deblur_scope / loss_guidance_scope (`scope`: 'dps' / 'deblur' / 'loss_guidance'), which runs the plain step and then
         moves the latent frames: every refusal by name, around _prepare -> (the scope's setting, base, xs, tt, kw)."""
         if self.model_mean_type != ModelMeanType.EPSILON:
             raise NotImplementedError(f"{scope}_scope with predict_xstart=True: epsilon-prediction models only")
@@ -726,6 +828,45 @@ class GaussianDiffusion:
         _lib.check(L.vd_dps_step(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0,
                                  mode, float(eta), _lib.ptr(noise), _lib.ptr(d["y"]), d["scale"], 1 if d["gray"] else 0, d["zeta"],
                                  _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
+        return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
+
+    def deblur_scope(self, model, y, kernel, *, zeta):
+        """This project's extension: `with diffusion.deblur_scope(model, y, kernel, zeta=0.5):` -- dps_scope for a blurred, NOISY copy of
+        the video: y = blur(video, kernel) plus whatever noise the footage carries, of the video's own shape (B, T, 3, H, W).  `kernel`
+        is one real (k, k) tensor or array, k odd and at most 15, applied to every channel plane of every frame as
+        torch.nn.functional.conv2d applies it, at "same" size with zeros outside the plane; it need not be symmetric, normalised or
+        non-negative (gaussian_kernel(size, sigma) makes the usual one; check_blur_kernel states the rules).  Every p_sample and
+        ddim_sample call inside, and every loop built on them, runs the plain step and then moves the frames with latent_mask == 1 down
+        the gradient of rho = ||y - k * x_0(x_t)||_2 with respect to x_t, per batch item: sample = fmaf(-zeta, grad, sample_plain)
+        (include/vd_amd.h: vd_deblur_step; csrc/blur.hip).  In every other respect this is dps_scope: the cost of a step, windows of at
+        most 32 frames, epsilon-prediction models, the returned 'residual_norm' (B,) and 'grad', 'pred_xstart' the plain step's, zeta = 0
+        the plain step to the bit, the sampler noise drawn once where the plain step draws it, zeta required.
+        Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name:
+        dpmpp_2m_sample, dpmpp_2m_sde_sample, unipc_sample, ddim_reverse_sample, denoised_fn, use_gradient_method, cfg_scale != 1, guidance_scope with either option set,
+        known_region_scope, measurement_scope and dps_scope on the same model, return_attn_weights, and WindowExecutor.begin.  Not
+        honoured by model(...) itself, p_mean_variance, score_windows and the NLL path.  No claim about restoration quality is made."""
+        base = self._bind(model)
+        w = check_blur_kernel(kernel)
+        zeta = check_zeta(zeta)
+        if not th.is_tensor(y) or y.dim() != 5:
+            raise ValueError(f"y must be a (B, T, 3, H, W) tensor, got {tuple(getattr(y, 'shape', ()))}")
+        d = dict(y=_f32(check_blur_measurement(y, y.shape), base.device), kernel=w, zeta=zeta)
+        return _scoped(base, "deblur", d, _engine_blur)
+
+    def _deblur_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                     use_gradient_method, cfg_scale):
+        """One p_sample (mode 0) / ddim_sample (mode 1) step inside deblur_scope -> dict sample, pred_xstart, grad, residual_norm."""
+        d, base, xs, tt, kw = self._moved_step_window("deblur", model, x, t, denoised_fn, model_kwargs, return_attn_weights, use_gradient_method,
+                                                      cfg_scale)
+        if tuple(d["y"].shape) != tuple(xs.shape):
+            raise ValueError(f"deblur_scope: y {tuple(d['y'].shape)} against a step on {tuple(xs.shape)}")
+        noise, sample, xstart, grad = self._moved_step_tensors(base, xs, noise)
+        B, T = xs.shape[:2]
+        L = _lib.lib()
+        rho = th.empty(B, dtype=th.float32, device=base.device)
+        _lib.check(L.vd_deblur_step(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"], 1 if clip_denoised else 0,
+                                    mode, float(eta), _lib.ptr(noise), _lib.ptr(d["y"]), d["zeta"],
+                                    _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
         return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
 
     def loss_guidance_scope(self, model, loss_fn=None, *, cotangent_fn=None, scale, normalize=False):
@@ -802,7 +943,7 @@ class GaussianDiffusion:
         return out
 
     def steering_scope(self, model, reward_fn=None, *, particles, scale=1.0, ess_threshold=0.5, measurement=None, sr_scale=1, gray=False,
-                       sigma_y=None, uniforms=None):
+                       sigma_y=None, uniforms=None, blur_kernel=None):
         """This project's extension (Feynman-Kac steering: Singhal et al. 2025; the twisted diffusion sampler of Wu et al. 2023 without its
         gradient proposal): `with diffusion.steering_scope(model, reward_fn, particles=K):` -- guidance towards a reward on the step's x_0
         prediction WITHOUT a derivative of the UNet, so it reaches what the gradient scopes do not: windows of up to 128 frames,
@@ -822,7 +963,9 @@ class GaussianDiffusion:
                              r = -||y - A x0||^2 / (2 sigma_y^2) over the item's frames with latent_mask == 1, computed on the device in
                              the step's own launches; with scale = 1 the target is the Bayesian posterior, which dps_scope approximates
                              with a gradient and a hand-tuned zeta.  y (B, T, Cy, H / sr_scale, W / sr_scale): a group's items carry the
-                             same y.  sigma_y is required.
+                             same y.  sigma_y is required.  With blur_kernel=w (deblur_scope's kernel) the operator is the blur
+                             instead: y = blur(video, w) + N(0, sigma_y^2) has the video's shape, and sr_scale and gray stay at
+                             their defaults (ValueError otherwise; so is a blur_kernel without a measurement).
         Served inside: p_sample, ddim_sample with eta > 0, dpmpp_2m_sde_sample and the loops built on them; cfg_scale, guidance_scope with
         any of its options, every observed_frames mode, both mean types.  A step returns its usual dict -- 'sample' and 'pred_xstart' are
         the resampled tensors -- plus 'ancestors' (B,) int32 (the item each item took; itself where nothing moved), 'ess' (G,) and
@@ -832,7 +975,7 @@ class GaussianDiffusion:
         a (G, 2) tensor of values in [0, 1), or (built-in reward) a (seed, offset) pair naming the head of the step's Philox range.
         Scopes nest; the setting found before is back when the block ends, whatever it raised.  Refused inside, by name:
         ddim_sample at eta = 0, dpmpp_2m_sample, unipc_sample, ddim_reverse_sample (they draw no noise: duplicates would never
-        separate), a learned variance, known_region_scope, measurement_scope, dps_scope, loss_guidance_scope, use_gradient_method,
+        separate), a learned variance, known_region_scope, measurement_scope, dps_scope, deblur_scope, loss_guidance_scope, use_gradient_method,
         return_attn_weights, a batch that is no multiple of `particles`, and with the built-in reward denoised_fn.  WindowExecutor.begin
         takes the built-in reward through its own keywords and refuses a reward_fn.  No claim about sample quality is made."""
         base = self._bind(model)
@@ -840,7 +983,17 @@ class GaussianDiffusion:
         if uniforms is not None and not (isinstance(uniforms, th.Generator) or callable(uniforms)):
             raise ValueError("steering_scope: uniforms is None, a torch.Generator or a callable uniforms(t)")
         meas = None
-        if measurement is not None:
+        if blur_kernel is not None:
+            if measurement is None:
+                raise ValueError("steering_scope: blur_kernel is the operator of the built-in reward: it needs measurement= and sigma_y=")
+            if not (sr_scale == 1 and gray is False):
+                raise ValueError("steering_scope: blur_kernel together with sr_scale or gray is not served: leave them at their defaults")
+            if not th.is_tensor(measurement) or measurement.dim() != 5:
+                raise ValueError(f"steering_scope: measurement must be a (B, T, 3, H, W) tensor under a blur, got "
+                                 f"{tuple(getattr(measurement, 'shape', ()))}")
+            meas = dict(y=_f32(check_blur_measurement(measurement, measurement.shape), base.device), scale=1, gray=False, sigma_y=sig,
+                        kernel=check_blur_kernel(blur_kernel))
+        elif measurement is not None:
             sc, gr = _check_operator(sr_scale, gray)
             if not th.is_tensor(measurement) or measurement.dim() != 5:
                 raise ValueError(f"steering_scope: measurement must be a (B, T, Cy, H / sr_scale, W / sr_scale) tensor, got "
@@ -861,7 +1014,7 @@ class GaussianDiffusion:
             raise NotImplementedError(f"{row.step}{' at eta = 0' if row.noise is not None else ''} inside steering_scope is not served: the step "
                                       "draws no noise, duplicated particles would never separate")
         self._refuse_learned(x)
-        for other in ("known_region", "measurement", "dps", "loss_guidance"):
+        for other in ("known_region", "measurement", "dps", "deblur", "loss_guidance"):
             if _scope(model, other) is not None:
                 raise NotImplementedError(f"{other}_scope together with steering_scope is not served")
         for flag, what in ((use_gradient_method, "use_gradient_method"), (return_attn_weights, "return_attn_weights"),
@@ -871,7 +1024,10 @@ class GaussianDiffusion:
         if x.shape[0] % d["K"]:
             raise ValueError(f"steering_scope: the batch of {x.shape[0]} items is no multiple of particles={d['K']}")
         m = d["measurement"]
-        if m is not None and tuple(m["y"].shape) != measurement_shape(x.shape, m["scale"], m["gray"]):
+        if m is not None and m.get("kernel") is not None:
+            if tuple(m["y"].shape) != tuple(x.shape):
+                raise ValueError(f"steering_scope: measurement {tuple(m['y'].shape)} against a step on {tuple(x.shape)} under a blur")
+        elif m is not None and tuple(m["y"].shape) != measurement_shape(x.shape, m["scale"], m["gray"]):
             raise ValueError(f"steering_scope: measurement {tuple(m['y'].shape)} against a step on {tuple(x.shape)} at sr_scale={m['scale']}, "
                              f"gray={m['gray']}")
         return d
@@ -1005,7 +1161,7 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         self._last_dps = None
-        for scope, step in (("loss_guidance", self._loss_guidance_step), ("dps", self._dps_step)):
+        for scope, step in (("loss_guidance", self._loss_guidance_step), ("deblur", self._deblur_step), ("dps", self._dps_step)):
             if _scope(model, scope) is not None:                   # p_sample / ddim_sample inside the scope: the plain step, then the scope's move
                 self._last_dps = step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
                                       use_gradient_method, cfg_scale)
@@ -1260,6 +1416,7 @@ class GaussianDiffusion:
         live on the Python side (a known region reaches the engine only for the length of a step) are refused here, by name."""
         _refuse(model, "known_region", what)
         _refuse(model, "dps", what)
+        _refuse(model, "deblur", what)
         kw_in = dict(model_kwargs or {})
         kw_in.setdefault("observed_frames", "x_0")
         kw_in.setdefault("x0", x)
@@ -1492,7 +1649,7 @@ class GaussianDiffusion:
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
-        for scope in (_SCOPES if row.up else ("dps", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
+        for scope in (_SCOPES if row.up else ("dps", "deblur", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
             _refuse(model, scope, row.step)
         d = self._check_steered(model, row, 1.0, x, denoised_fn)
         if d is not None:                                                         # dpmpp_2m_sde_sample inside steering_scope

@@ -18,13 +18,15 @@ step runs -- follows scripts/video_sample.py:192-239,570-640; `run()` is that bo
 import argparse
 import contextlib
 import logging
+import math
 import os
 
 import numpy as np
 import torch
 
 from . import _lib, inference_util
-from .gaussian_diffusion import SAMPLERS, _check_guidance, _sampler_step, check_loss_guidance, check_measurement, check_zeta
+from .gaussian_diffusion import (SAMPLERS, _check_guidance, _sampler_step, check_blur_kernel, check_blur_measurement, check_loss_guidance,
+                                 check_measurement, check_zeta, gaussian_kernel)
 from .script_util import (args_to_dict, create_video_model_and_diffusion, str2bool,
                           video_model_and_diffusion_defaults)
 from .weights_init import synth_param
@@ -49,7 +51,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
                 measurement=None, sr_scale=1, gray=False, dps_zeta=None, loss_fn=None, cotangent_fn=None, loss_scale=None,
                 loss_normalize=False, particles=1, reward_fn=None, reward_scale=1.0, ess_threshold=0.5, particle_measurement=None,
-                sigma_y=None):
+                sigma_y=None, blur_kernel=None):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -136,9 +138,29 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     give equal bits.  Every sampler that draws noise, cfg_scale, cfg_rescale and dynamic_threshold are served, and windows of up to 128
     frames.  Refused by name before the engine is touched: use_gradient_method, known_mask, a measurement (the exact projection),
     dps_zeta, loss_fn / cotangent_fn, prefix_cache, suffix_skip, save_all_timesteps, a sampler that draws no noise ('ddim' at eta = 0,
-    'dpmpp_2m', 'unipc'), and a reward_fn with executor='graph'.  particles=1 (default): nothing of this runs."""
+    'dpmpp_2m', 'unipc'), and a reward_fn with executor='graph'.  particles=1 (default): nothing of this runs.
+
+    blur_kernel (this project's extension: deblurring; gaussian_diffusion.py: deblur_scope): the measurement is a blurred, noisy copy of
+    the WHOLE video, of the video's own shape -- what diffusion.blur(video, blur_kernel) returns, plus noise -- and blur_kernel one real
+    (k, k) kernel, k odd and at most 15 (check_blur_kernel); sr_scale and gray stay at their defaults.  It takes one of the two paths that
+    accept a noisy measurement, each with its own rules above: dps_zeta= (deblur_scope in place of dps_scope), or particles=K, sigma_y=
+    (the built-in reward on the blur; `measurement` is then read as particle_measurement when that is not given).  With neither it is
+    refused by name: the exact projection of measurement_scope has no pseudo-inverse for a blur."""
+    blur_w = None
+    if blur_kernel is not None:
+        blur_w = check_blur_kernel(blur_kernel)                             # before anything touches the engine
+        if not (sr_scale == 1 and gray is False):
+            raise ValueError("blur_kernel together with sr_scale or gray is not served: leave them at their defaults")
+        if measurement is None and particle_measurement is None:
+            raise ValueError("blur_kernel needs a measurement (measurement=: the blurred copy of the video)")
+        steered = particles != 1 or sigma_y is not None or particle_measurement is not None
+        if dps_zeta is None and not steered:
+            raise _lib.VdError("blur_kernel without dps_zeta or particles is not served: measurement_scope together with a blur is refused, "
+                               "the exact projection has no pseudo-inverse for this operator")
+        if steered and dps_zeta is None and particle_measurement is None:
+            measurement, particle_measurement = None, measurement
     steer = _check_particles(particles, reward_fn, reward_scale, ess_threshold, particle_measurement, sigma_y, batch, sr_scale, gray, sampler, eta,
-                             executor, [("use_gradient_method", use_gradient_method), ("known_mask", known_mask is not None),
+                             executor, blur_w, [("use_gradient_method", use_gradient_method), ("known_mask", known_mask is not None),
                                         ("a measurement", measurement is not None), ("dps_zeta", dps_zeta is not None),
                                         ("loss_fn / cotangent_fn", loss_fn is not None or cotangent_fn is not None), ("prefix_cache", prefix_cache),
                                         ("suffix_skip", suffix_skip), ("save_all_timesteps", save_all_timesteps)])
@@ -170,7 +192,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         raise NotImplementedError("sampler='unipc' together with known_mask: the corrector rebuilds the state from its own, the merge of a "
                                   "known region behind the pass would be discarded")
     if measurement is not None:
-        measurement_v = check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray).cpu()   # before anything touches the engine
+        measurement_v = (check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray) if blur_w is None     # before anything touches the engine
+                         else check_blur_measurement(torch.as_tensor(measurement), batch.shape)).cpu()
         if known_mask is not None:
             raise _lib.VdError("a measurement together with a known region (known_mask) is not served")
         if use_gradient_method:
@@ -196,7 +219,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                                save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
                                jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray,
                                particles=particles, reward_fn=reward_fn, reward_scale=reward_scale, ess_threshold=ess_threshold,
-                               particle_measurement=particle_measurement, sigma_y=sigma_y)
+                               particle_measurement=particle_measurement, sigma_y=sigma_y, blur_kernel=blur_kernel)
     step_sampler = sampler if sampler in SAMPLERS and not SAMPLERS[sampler].up else "ddim"    # (the eager step: any other name is ddim_sample)
     adaptive = "adaptive" in mode
     if steer is not None:                  # every video as K consecutive items; the return takes one of each group again
@@ -271,12 +294,12 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             if use_graph:
                 wex.begin(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, particles=steer["K"],
                           reward_scale=steer["scale"], ess_threshold=steer["tau"], particle_measurement=pm_w, particle_sr_scale=sr_scale,
-                          particle_gray=gray, sigma_y=sigma_y)
+                          particle_gray=gray, sigma_y=sigma_y, blur_kernel=None if pm_w is None else blur_w)
                 local_samples = wex.run(diffusion.num_timesteps).clone()
                 chosen = wex.particle_state()["chosen"]
             else:
                 local_samples, chosen = _eager_particle_window(model, diffusion, x0, model_kwargs, step_sampler, eta, cfg_scale, steer, pm_w,
-                                                               sr_scale, gray, sigma_y, t_tensors, timesteps)
+                                                               sr_scale, gray, sigma_y, t_tensors, timesteps, blur_w)
             write_back(_chosen_for_all(local_samples, chosen, steer["K"]))
             model.check_device_errors()
             continue
@@ -304,6 +327,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             scope = diffusion.loss_guidance_scope(model, loss_fn, cotangent_fn=cotangent_fn, scale=loss_scale, normalize=loss_normalize)
         elif y_w is None:
             scope = contextlib.nullcontext()
+        elif dps_zeta is not None and blur_w is not None:
+            scope = diffusion.deblur_scope(model, y_w, blur_w, zeta=dps_zeta)
         elif dps_zeta is not None:
             scope = diffusion.dps_scope(model, y_w, sr_scale, gray, zeta=dps_zeta)
         else:
@@ -321,7 +346,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     return (samples if steer is None else samples[::steer["K"]]).numpy(), all_timestep_samples.numpy()
 
 
-def _check_particles(particles, reward_fn, reward_scale, ess_threshold, y, sigma_y, batch, sr_scale, gray, sampler, eta, executor, others):
+def _check_particles(particles, reward_fn, reward_scale, ess_threshold, y, sigma_y, batch, sr_scale, gray, sampler, eta, executor, blur_w, others):
     """infer_video's particle keywords, checked before anything touches the engine -> dict K, scale, tau, reward_fn, y (the whole video's
     measurement repeated per particle, on the host, or None), or None for the plain run (particles=1 or reward_scale=0)."""
     from .gaussian_diffusion import check_steering
@@ -330,7 +355,8 @@ def _check_particles(particles, reward_fn, reward_scale, ess_threshold, y, sigma
     K, lam, tau, _ = check_steering(reward_fn, y, particles, reward_scale, ess_threshold, sigma_y)
     y_v = None
     if y is not None:
-        y_v = check_measurement(torch.as_tensor(y), batch.shape, sr_scale, gray).cpu()
+        y_v = (check_measurement(torch.as_tensor(y), batch.shape, sr_scale, gray) if blur_w is None
+               else check_blur_measurement(torch.as_tensor(y), batch.shape)).cpu()
     for name, on in others:
         if on:
             raise NotImplementedError(f"{name} together with particles is not served")
@@ -353,14 +379,15 @@ def _chosen_for_all(local, chosen, K):
     return picked.repeat_interleave(K, dim=0)
 
 
-def _eager_particle_window(model, diffusion, x0, model_kwargs, sampler, eta, cfg_scale, steer, y_w, sr_scale, gray, sigma_y, t_tensors, timesteps):
+def _eager_particle_window(model, diffusion, x0, model_kwargs, sampler, eta, cfg_scale, steer, y_w, sr_scale, gray, sigma_y, t_tensors, timesteps,
+                           blur_w=None):
     """One window of infer_video's eager executor inside steering_scope -> (the window's K samples per video, chosen (G,)).  A sampler
     whose noise is the engine's Philox stream draws it, and the uniforms of the built-in reward, where the window executor would."""
     local, carry, out = x0.clone(), None, None
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if SAMPLERS[sampler].noise == "philox" else None
     with diffusion.steering_scope(model, steer["reward_fn"], particles=steer["K"], scale=steer["scale"], ess_threshold=steer["tau"],
                                   measurement=y_w, sr_scale=sr_scale if y_w is not None else 1, gray=gray if y_w is not None else False,
-                                  sigma_y=sigma_y):
+                                  sigma_y=sigma_y, blur_kernel=None if y_w is None else blur_w):
         for timestep in timesteps:
             philox = None if seed is None else (seed, (diffusion.num_timesteps - 1 - timestep) * local.numel())
             out, carry = _sampler_step(diffusion, sampler, model, local, t_tensors[timestep], carry, cfg_scale, eta, philox,
@@ -664,6 +691,14 @@ def build_parser():
                     help="with --measurement: diffusion posterior sampling (DPS) for a measurement that carries noise -- every step moves the "
                          "generated frames down the gradient of ||y - A x_0||_2 through the network with step size Z, in place of the exact "
                          "projection; eager executor, samplers p_sample and ddim; named in the run directory when set")
+    ap.add_argument("--blur_kernel", default=None, metavar="K.npy",
+                    help="with --measurement: deblurring -- the measurement is a blurred, noisy copy of the test videos, (N, T, 3, H, W), and "
+                         "K.npy the (k, k) kernel it was blurred with (k odd, at most 15; applied as torch's conv2d, zeros outside the frame); "
+                         "needs --dps_zeta, or --particles with --measurement_sigma; named in the run directory ('_blur<k>')")
+    ap.add_argument("--blur_sigma", type=float, default=None, metavar="S",
+                    help="in place of --blur_kernel: a normalised Gaussian kernel of standard deviation S pixels")
+    ap.add_argument("--blur_size", type=int, default=None, metavar="N",
+                    help="with --blur_sigma: the kernel is N x N (odd, at most 15; default: the odd size that covers 3 S, at most 15)")
     ap.add_argument("--loss_guidance", default=None, metavar="MODULE:FUNCTION",
                     help="loss-guided sampling: FUNCTION(x0, t) of the importable MODULE (the current directory is searched too) is a loss on "
                          "each window's x_0 prediction (B, Tw, 3, H, W), differentiated by torch; every step moves the generated frames down "
@@ -709,6 +744,23 @@ def check_particle_arguments(ap, args):
                  "exact projection): give one")
     if K < 1:
         ap.error("--particles K: at least 1")
+    kern, bsig, bsize = (getattr(args, n, None) for n in ("blur_kernel", "blur_sigma", "blur_size"))
+    if kern and bsig is not None:
+        ap.error("--blur_kernel and --blur_sigma are two kernels: give one")
+    if bsize is not None and bsig is None:
+        ap.error("--blur_size needs --blur_sigma S")
+    if bsig is not None and not bsig > 0.0:
+        ap.error("--blur_sigma S: positive")
+    if bsize is not None and not (1 <= bsize <= 15 and bsize % 2 == 1):
+        ap.error("--blur_size N: odd, from 1 to 15")
+    if kern or bsig is not None:
+        if not getattr(args, "measurement", None):
+            ap.error("--blur_kernel / --blur_sigma need --measurement Y.npy")
+        if not uses:
+            ap.error("--blur_kernel / --blur_sigma need --dps_zeta Z, or --particles K with --measurement_sigma SIGMA: the exact projection has "
+                     "no pseudo-inverse for a blur")
+        if int(getattr(args, "sr_scale", 1)) != 1 or getattr(args, "gray", False):
+            ap.error("--blur_kernel / --blur_sigma together with --sr_scale or --gray are not served")
     if sigma is not None and not getattr(args, "measurement", None):
         ap.error("--measurement_sigma needs --measurement Y.npy")
     if sigma is not None and getattr(args, "reward", None):
@@ -745,6 +797,19 @@ def _known_options(args, batch):
     return kw
 
 
+def blur_kernel_of(args):
+    """--blur_kernel K.npy / --blur_sigma S [--blur_size N] -> the (k, k) float32 taps, checked, or None without either."""
+    path, sigma = getattr(args, "blur_kernel", None), getattr(args, "blur_sigma", None)
+    if path:
+        return check_blur_kernel(np.load(path))
+    if sigma is None:
+        return None
+    size = getattr(args, "blur_size", None)
+    if size is None:
+        size = min(15, 2 * int(math.ceil(3.0 * float(sigma))) + 1)
+    return gaussian_kernel(int(size), float(sigma))
+
+
 def _measurement_options(args, batch):
     """--measurement / --sr_scale / --gray of the job -> infer_video's keywords for this batch ({} without a measurement).  The
     batch's dataset items are args._batch_ids (run() sets it)."""
@@ -759,6 +824,11 @@ def _measurement_options(args, batch):
         raise ValueError(f"{path}: --measurement is (N, T, Cy, H / S, W / S), got {y.shape}")
     T = batch.shape[1]
     rows = np.stack([np.asarray(y[i][:T], dtype=np.float32) for i in args._batch_ids])
+    blur_w = blur_kernel_of(args)
+    if blur_w is not None:                                            # a blurred copy: the video's shape, and one of the two noisy paths
+        if getattr(args, "measurement_sigma", None) is not None:
+            return dict(particle_measurement=torch.from_numpy(rows), sigma_y=float(args.measurement_sigma), blur_kernel=blur_w)
+        return dict(measurement=torch.from_numpy(rows), blur_kernel=blur_w, **({} if zeta is None else dict(dps_zeta=float(zeta))))
     if getattr(args, "measurement_sigma", None) is not None:          # the reward of --particles, not the projection
         return dict(particle_measurement=torch.from_numpy(rows), sr_scale=int(getattr(args, "sr_scale", 1)), gray=bool(getattr(args, "gray", False)),
                     sigma_y=float(args.measurement_sigma))
@@ -831,7 +901,7 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
-    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'), a --loss_guidance ('_lg0.5': its scale) and --particles
+    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'; under --blur_kernel / --blur_sigma '_blur9' in their place), a --loss_guidance ('_lg0.5': its scale) and --particles
     above 1 ('_smc8') -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
@@ -843,9 +913,10 @@ def run_postfix(args):
         r = int(getattr(args, "n_resample", 1))
         known = "_known" + ("" if r == 1 else f"_j{int(getattr(args, 'jump_length', 1))}r{r}")
     meas = ""
-    if getattr(args, "measurement", None):        # '_sr4', '_gray', '_sr4gray'
+    if getattr(args, "measurement", None):        # '_sr4', '_gray', '_sr4gray'; under a blur '_blur9'
         S = int(getattr(args, "sr_scale", 1))
-        meas = "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
+        blur_w = blur_kernel_of(args)
+        meas = f"_blur{int(blur_w.shape[0])}" if blur_w is not None else "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
         if getattr(args, "dps_zeta", None) is not None:
             meas += f"_dps{float(args.dps_zeta):g}"
     lg = ""
