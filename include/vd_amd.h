@@ -724,6 +724,55 @@ int vd_op_blur(int B, int T, int H, int W, const float* x, const float* taps_dev
 int vd_set_particle_blur(vd_engine* e, int on);
 int vd_particle_blur(vd_engine* e);
 
+/* Separable linear measurements -- this project's extension: the exact projection (vd_set_measurement's), DPS (vd_dps_step's) and the
+ * built-in reward of particle steering for a measurement that acts on every channel plane of every frame alike as
+ *   y[b][t][c] = A_h x_0[b][t][c] A_w^T,   A_h: Mh x H,  A_w: Mw x W,  1 <= Mh <= H <= 128,  1 <= Mw <= W <= 128   (linop.hip)
+ * -- bicubic or bilinear down-sampling, a separable blur with any padding and stride, the cell mean.  y is [B][T][3][Mh][Mw].  The adjoint
+ * is A_h^T r A_w, the back-projection P_h r P_w^T with P_h (H x Mh) and P_w (W x Mw), the caller's (truncated) pseudo-inverses.  All
+ * matrices are dense, row-major fp32.  Every product is Z = L X R^T (L: P x Q, X: Q x U, R: S x U), the right factor first:
+ *   tmp[q][s] = sum_u X[q][u] R[s][u], then Z[p][s] = sum_q L[p][q] tmp[q][s]
+ * each sum from 0 in ascending index order, acc = acc + a * b with the product and the sum each rounded to fp32, never fused; tmp is fp32.
+ * Forward: L = A_h, R = A_w.  Adjoint: L = A_h^T, R = A_w^T.  Back-projection: L = P_h, R = P_w.
+ * vd_set_linear_operator: engine state, H = W = the model's image size.  Matrices on the HOST, finite, A_h and A_w not all zero, copied
+ *   into engine-owned device buffers whose addresses never change; waits for the device.  P_h and P_w come together or are both NULL (the
+ *   projection is then refused by name).  A_h or A_w NULL clears the operator (refused while vd_set_linear_measurement or
+ *   vd_set_particle_linear reads it; while one does, new matrices keep the shape).  vd_linear_operator: 0 none, 1 installed, 2 with a
+ *   back-projection; *Mh, *Mw.
+ * vd_set_linear_measurement: y on the device (the caller's; NULL: off).  Every step then projects its x_0 prediction,
+ *   x_0 <- x_0 + P_h (y - A_h x_0 A_w^T) P_w^T on the frames with latent_mask == 1, in the place and under the rules of vd_set_measurement:
+ *   in front of the sampler pass, behind the dynamic threshold, the sampler pass in its x0_given form with the clamp off; composes with
+ *   cfg_scale and guidance rescale; two launches per step.  Refused, by name, together with a known region, the window prefix cache or
+ *   suffix skip, a sampler that walks up, vd_set_particles, the differentiated passes, and vd_set_measurement itself.  A window graph's
+ *   key carries (y, Mh, Mw): new matrices of equal shape between two windows act without a new capture.  vd_linear_measurement: the switch.
+ * vd_linear_dps_step: vd_deblur_step on the installed operator -- r = y - A x_0, rho_b, q = -(A_h^T r A_w) / rho_b; its outputs, its
+ *   workspace and its refusals under the name "linear_dps"; it also fails while no operator is installed.  Eager steps only.
+ * vd_set_particle_linear: on != 0 (an operator must be installed; refused together with vd_set_particle_blur) makes the installed operator
+ *   the operator of the built-in reward of vd_set_particles: y is then [B][T][3][Mh][Mw] and the scale and gray handed there are not read
+ *   (hand scale 1 with gray).  Captured into a window graph, whose key carries (Mh, Mw).  vd_particle_linear: the switch.
+ * vd_op_linop: out = L x R^T of `planes` planes of Q x U, matrices ON THE DEVICE, out != x; no engine.
+ * vd_op_linear_project: the projection alone on an x_0 handed in (through the clamp when clip_denoised), in place, on frames of H x W, no
+ *   network; frames with latent_mask != 1 keep their bits unless clip_denoised.  vd_op_linear_dps_seed: the residual and seed passes alone
+ *   on a caller's (x_t, eps); outputs as vd_op_dps_seed.  16-byte loads while the row length is a multiple of 4 and the tensors are 16-byte
+ *   aligned, else element by element: same bits. */
+int vd_set_linear_operator(vd_engine* e, const float* A_h_host, int Mh, const float* A_w_host, int Mw, const float* P_h_host,
+                           const float* P_w_host);
+int vd_linear_operator(vd_engine* e, int* Mh, int* Mw);
+int vd_set_linear_measurement(vd_engine* e, const float* y);
+int vd_linear_measurement(vd_engine* e);
+int vd_linear_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs_mask, const float* latent_mask,
+                       const float* kinda_marg_mask, const long long* frame_indices, const long long* t, int obs_mode, int clip_denoised,
+                       int sampler, float eta, const float* noise, const float* y, float zeta, float* sample, float* pred_xstart,
+                       float* grad, float* residual_norm, void* stream);
+int vd_set_particle_linear(vd_engine* e, int on);
+int vd_particle_linear(vd_engine* e);
+int vd_op_linop(long long planes, int Q, int U, const float* x, const float* L_dev, int P, const float* R_dev, int S, float* out, void* stream);
+int vd_op_linear_project(vd_engine* e, int B, int T, int H, int W, float* x0_inout, const float* y, const float* latent_mask,
+                         const float* A_h_dev, int Mh, const float* A_w_dev, int Mw, const float* P_h_dev, const float* P_w_dev,
+                         int clip_denoised, void* stream);
+int vd_op_linear_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x_t, const float* eps, const long long* t, int clip_denoised,
+                          const float* y, const float* latent_mask, const float* A_h_dev, int Mh, const float* A_w_dev, int Mw, float* d_eps,
+                          float* d_x, float* rho, float* pred_xstart, void* stream);
+
 /* Loss-guided sampling -- this project's extension: a reverse step moved down the gradient, with respect to x_t, of ANY differentiable
  * function of the step's x_0 prediction.  The function is the caller's own code: vd_dps_step is split in two around the point where the
  * cotangent of x_0 is formed, and the taped forward survives between the two calls.  Per item b, with L_b its frames with

@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "guidance.hip", "known.hip", "measure.hip", "dps.hip", "blur.hip", "particles.hip", "guide.hip", "ode_nll.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip", "hallway.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "guidance.hip", "known.hip", "measure.hip", "dps.hip", "blur.hip", "linop.hip", "particles.hip", "guide.hip", "ode_nll.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip", "hallway.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # every header a source may include: part of the library's identity and of each object's build stamp
 HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), os.path.join(_CSRC, "igemm_tile.h"), HEADER]
@@ -224,6 +224,16 @@ SIGNATURES = {
     "vd_op_blur": (_I, [_I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "vd_set_particle_blur": (_I, [_P, _I]),
     "vd_particle_blur": (_I, [_P]),
+    "vd_set_linear_operator": (_I, [_P, _P, _I, _P, _I, _P, _P]),
+    "vd_linear_operator": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "vd_set_linear_measurement": (_I, [_P, _P]),
+    "vd_linear_measurement": (_I, [_P]),
+    "vd_linear_dps_step": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _F, _P, _P, _P, _P, _P]),
+    "vd_set_particle_linear": (_I, [_P, _I]),
+    "vd_particle_linear": (_I, [_P]),
+    "vd_op_linop": (_I, [ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _I, _P, _P]),
+    "vd_op_linear_project": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "vd_op_linear_dps_seed": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "vd_set_particles": (_I, [_P, _I, _D, _D, _P, _I, _I, _D]),
     "vd_particles": (_I, [_P]),
     "vd_particle_reset": (_I, [_P, _I]),

@@ -395,6 +395,16 @@ struct vd_engine {
     // reward's operator is this kernel (blur.hip), y has the video's shape, and part_scale / part_gray are not read.
     float* d_blur_taps = nullptr;
     int blur_k = 0, part_blur = 0;
+    // the separable linear operator (vd_set_linear_operator; lin_Mh 0: none): A_h, A_w, P_h, P_w in four engine-owned slots of
+    // kMaxLinopSide^2 floats whose addresses never change, so a window graph that reads them follows new matrices of equal shape.
+    // lin_back: P_h and P_w were handed in.  lin_y (vd_set_linear_measurement; null = off): the x_0 prediction of every step is projected
+    // onto it (linop.hip) in the place of meas_y; the caller's tensor.  d_lin_r: the residual between the projection's two passes.
+    // part_lin (vd_set_particle_linear): the built-in reward's operator is this one, y is [B][T][3][Mh][Mw].
+    float* d_lin_mats = nullptr;
+    int lin_Mh = 0, lin_Mw = 0, lin_back = 0, part_lin = 0;
+    const float* lin_y = nullptr;
+    float* d_lin_r = nullptr; size_t lin_r_cap = 0;
+    const float* lin_mat(int i) const { return d_lin_mats + (size_t)i * kMaxLinopSide * kMaxLinopSide; }      // 0 A_h, 1 A_w, 2 P_h, 3 P_w
     double *d_part_logw = nullptr, *d_part_rprev = nullptr, *d_part_ess = nullptr;
     int *d_part_anc = nullptr, *d_part_chosen = nullptr;
     long long* d_part_counters = nullptr;
@@ -429,6 +439,8 @@ struct vd_engine {
         const float* part_y; int part_K, part_scale, part_gray;   // particle steering: the three passes a graph ends in and their constants (part_K 0: none)
         double part_lambda, part_tau, part_sigma;
         int part_blur_k;                                          // ... with the blur kernel as the reward's operator: its size (0: the cell mean); the taps' address is fixed
+        int part_lin_Mh, part_lin_Mw;                             // ... with the linear operator as the reward's operator: y's sides (0: not); the matrices' addresses are fixed
+        const float* lin_y; int lin_Mh, lin_Mw;                   // linear measurement: the two projection passes a graph holds read y (null: none)
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -484,7 +496,7 @@ struct vd_engine {
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
         for (void* p : {(void*)d_part_logw, (void*)d_part_rprev, (void*)d_part_ess, (void*)d_part_anc, (void*)d_part_chosen,
                         (void*)d_part_counters, (void*)d_part_scratch, (void*)d_part_r, (void*)d_part_partials, (void*)d_part_x0,
-                        (void*)d_part_sel, (void*)d_blur_taps})
+                        (void*)d_part_sel, (void*)d_blur_taps, (void*)d_lin_mats, (void*)d_lin_r})
             if (p) (void)hipFree(p);
         for (auto& g : win_graphs) g.release();
     }
@@ -2114,6 +2126,11 @@ struct StepReq {
     // ... with the blur kernel as the reward's operator (part_blur_k 0: the cell mean at part_scale, part_gray)
     const float* part_taps = nullptr;
     int part_blur_k = 0;
+    // ... with the linear operator as the reward's operator (part_lin_Mh 0: not)
+    int part_lin_Mh = 0, part_lin_Mw = 0;
+    // linear measurement (null: none): the projection of the step's x_0 prediction onto y under the engine's operator, in meas_y's place
+    const float* lin_y = nullptr;
+    int lin_Mh = 0, lin_Mw = 0;
 };
 
 // The window prefix cache and suffix skip cut a step short on the observed frames; two options need all of them.  cfg_scale != 1: in the
@@ -2150,7 +2167,12 @@ static int particle_launches(vd_engine* e, const StepReq& r, const int64_t* t, s
     VD_REQUIRE(!r.pp && !r.sp, "particle steering (vd_set_particles) together with the window prefix cache or suffix skip is not served");
     VD_REQUIRE(e->part_B == B && e->part_state_K == K && e->d_part_sel && e->part_sel_nt == e->num_timesteps, "particle steering: no state for this batch (vd_particle_reset)");
     int nblk = 0, rc;
-    if (r.part_blur_k) {                                         // blur.hip's residual pass, handed the same tensors and rows
+    if (r.part_lin_Mh) {                                         // linop.hip's residual pass, handed the same tensors and rows
+        LinopArgs la{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_lin_Mh, r.part_lin_Mw,
+                     e->lin_mat(0), e->lin_mat(1), 0, e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * (r.part_lin_Mw + r.part_lin_Mh) * B * per, 4.0 * B * per * 3.0, st, "particle_linop_residual");
+        if ((rc = launch_linop_residual(la, &nblk, st))) return rc;
+    } else if (r.part_blur_k) {                                         // blur.hip's residual pass, handed the same tensors and rows
         BlurArgs ba{r.sample, r.xstart, r.part_y, r.lat, t, e->d_part_sel, e->num_timesteps, B, T, S, S, r.part_taps, r.part_blur_k, 0,
                     e->d_part_r, e->d_part_partials, nullptr, nullptr, nullptr, nullptr, nullptr};
         ProfScope ps(PC_ELEMENTWISE, 2.0 * r.part_blur_k * r.part_blur_k * B * per, 4.0 * B * per * 4.0, st, "particle_blur_residual");
@@ -2186,6 +2208,8 @@ static int particle_launches(vd_engine* e, const StepReq& r, const int64_t* t, s
 // x_0 itself (pass_x0: the sampler pass's head, clamp included) and writes the projected one into the second output buffer.  Either way
 // the sampler pass then runs in its x0_given form with clip off, so pred_xstart, the mean and the 2M history are the projected x_0.
 // Null: no launch is added.
+// lin_y (a linear measurement; the same place, rules and refusals, and refused together with meas_y): two passes in front of the sampler
+// pass, launch_linop_residual (x_0 and r = y - A x_0) and launch_linop_project (x_0 += P_h r P_w^T).  Null: no launch is added.
 // part_K > 1 (particle steering with the built-in reward): particle_launches behind the sampler pass.  0: no launch is added.
 static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     int rc;
@@ -2238,6 +2262,23 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
         pa.eps = nullptr; pa.x0_given = out;
         pa.clip = 0;
     }
+    if (r.lin_y) {
+        VD_REQUIRE(!r.pp && !r.sp, "a linear measurement (vd_set_linear_measurement) together with the window prefix cache or suffix skip is not served");
+        const int S = e->cfg.image_size;
+        float* out = e->step_eps_u(B, T);
+        // the residual pass forms x_0 as launch_measurement_project does -- behind the threshold its output, in place, as it is; else the
+        // network output through pass_x0 with the step's clamp -- and hands it out beside r; the second pass adds P_h r P_w^T in place
+        LinopArgs la{thresh || e->mean_type == 1 ? nullptr : r.x, thresh ? out : eps, r.lin_y, r.lat, pa.t, e->d_tab, e->num_timesteps, B, T, S, S,
+                     r.lin_Mh, r.lin_Mw, e->lin_mat(0), e->lin_mat(1), thresh ? 0 : r.clip, e->d_lin_r, nullptr, nullptr, nullptr, out, nullptr, nullptr};
+        {
+            ProfScope ps(PC_ELEMENTWISE, 2.0 * (r.lin_Mw + r.lin_Mh) * B * per, 4.0 * B * per * (la.x ? 3.0 : 2.0), st, "linop_residual");
+            if ((rc = launch_linop_residual(la, nullptr, st))) return rc;
+        }
+        ProfScope ps(PC_ELEMENTWISE, 2.0 * (r.lin_Mw + r.lin_Mh) * B * per, 4.0 * B * per * 2.0, st, "linop_project");
+        if ((rc = launch_linop_project(out, e->d_lin_r, r.lat, e->lin_mat(2), e->lin_mat(3), B, T, S, S, r.lin_Mh, r.lin_Mw, st))) return rc;
+        pa.eps = nullptr; pa.x0_given = out;
+        pa.clip = 0;
+    }
     pa.mean = r.mean; pa.eta = r.eta; pa.noise = r.noise; pa.seed = r.seed; pa.offset = r.offset; pa.dstate = r.rng;
     pa.hist = r.hist; pa.hist_on = r.hist_on;
     if (sampler_is_unipc(r.sampler)) {
@@ -2279,6 +2320,15 @@ static int refuse_with_measurement(const vd_engine* e, int sampler) {
     return 0;
 }
 
+// ... and a linear measurement, the same set under its own name, and the measurement itself
+static int refuse_with_linear_measurement(const vd_engine* e, int sampler) {
+    VD_REQUIRE(!sampler_walks_up(sampler), std::string(sampler_name(sampler)) + " together with a linear measurement (vd_set_linear_measurement) is not served: the projection constrains x_0 of a reverse step");
+    VD_REQUIRE(!e->known_src, "a linear measurement (vd_set_linear_measurement) together with a known region (vd_set_known_region) is not served");
+    VD_REQUIRE(!e->meas_y, "a linear measurement (vd_set_linear_measurement) together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(e->lin_Mh && e->lin_back, "linear measurement: the installed operator has no back-projection (vd_set_linear_operator with P_h and P_w)");
+    return 0;
+}
+
 // what particle steering (vd_set_particles) is refused together with, by name: a step whose sample is wanted asks this of the engine's state
 static int refuse_with_particles(const vd_engine* e, int sampler, int B, float eta) {
     VD_REQUIRE(sampler_draws_noise(sampler) && (sampler != SAMPLER_DDIM || eta > 0.f), std::string(sampler_name(sampler)) + (sampler == SAMPLER_DDIM ? " at eta = 0" : "") +
@@ -2286,6 +2336,7 @@ static int refuse_with_particles(const vd_engine* e, int sampler, int B, float e
     VD_REQUIRE(B % e->part_K == 0, "particle steering (vd_set_particles): the batch of " + std::to_string(B) + " items is no multiple of the " + std::to_string(e->part_K) + " particles of a group");
     VD_REQUIRE(!e->known_src, "particle steering (vd_set_particles) together with a known region (vd_set_known_region) is not served");
     VD_REQUIRE(!e->meas_y, "particle steering (vd_set_particles) together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(!e->lin_y, "particle steering (vd_set_particles) together with a linear measurement (vd_set_linear_measurement) is not served");
     VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "particle steering (vd_set_particles) together with return_attn_weights is not served");
     return 0;
 }
@@ -2319,7 +2370,7 @@ static int particle_state_reset(vd_engine* e, int B) {
 static int ensure_particle_ws(vd_engine* e, int B, int T, bool x0) {
     const int S = e->cfg.image_size, sc = e->part_scale;
     const size_t per = (size_t)T * 3 * S * S;
-    int rc = e->grow(e->d_part_r, e->part_r_cap, e->part_blur ? (size_t)B * per : (size_t)B * T * (e->part_gray ? 1 : 3) * (S / sc) * (S / sc), true);
+    int rc = e->grow(e->d_part_r, e->part_r_cap, e->part_lin ? (size_t)B * T * 3 * e->lin_Mh * e->lin_Mw : e->part_blur ? (size_t)B * per : (size_t)B * T * (e->part_gray ? 1 : 3) * (S / sc) * (S / sc), true);
     if (!rc) rc = e->grow(e->d_part_partials, e->part_partials_cap, (size_t)B * dps_partials_per_item(), true);
     if (!rc) rc = e->grow(e->d_part_scratch, e->part_scratch_cap, 2 * (size_t)B * per, true);
     if (!rc && x0) rc = e->grow(e->d_part_x0, e->part_x0_cap, (size_t)B * per, true);
@@ -2342,6 +2393,7 @@ static int ensure_particle_ws(vd_engine* e, int B, int T, bool x0) {
 static int step_workspace(vd_engine* e, int B, int T, hipStream_t st) {
     int rc = e->ensure_ws(B, T);
     if (!rc && e->cfg_w != 1.f) rc = cfg_zero_mask(e, B, T, st);
+    if (!rc && e->lin_y) rc = e->grow(e->d_lin_r, e->lin_r_cap, (size_t)B * T * 3 * e->lin_Mh * e->lin_Mw, true);
     return rc;
 }
 
@@ -2366,6 +2418,10 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
         if ((rc = refuse_with_measurement(e, r.sampler))) return rc;
         r.meas_y = e->meas_y; r.meas_scale = e->meas_scale; r.meas_gray = e->meas_gray;
     }
+    if (e->lin_y) {
+        if ((rc = refuse_with_linear_measurement(e, r.sampler))) return rc;
+        r.lin_y = e->lin_y; r.lin_Mh = e->lin_Mh; r.lin_Mw = e->lin_Mw;
+    }
     if (want_sample && e->part_K > 1 && e->part_y) {
         VD_REQUIRE(e->part_B == r.B && e->part_state_K == e->part_K, "particle steering: the state holds " + std::to_string(e->part_B) + " items in groups of " + std::to_string(e->part_state_K) + " (vd_particle_reset), the step " + std::to_string(r.B) + " in groups of " + std::to_string(e->part_K));
         VD_REQUIRE(e->part_draws_set, "particle steering: no uniforms for this step (vd_particle_draws)");
@@ -2374,6 +2430,7 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
         r.part_lambda = e->part_lambda; r.part_tau = e->part_tau; r.part_sigma = e->part_sigma;
         r.part_uni = e->part_uni; r.part_seed = e->part_seed; r.part_offset = e->part_offset;
         if (e->part_blur) { r.part_taps = e->d_blur_taps; r.part_blur_k = e->blur_k; }
+        if (e->part_lin) { r.part_lin_Mh = e->lin_Mh; r.part_lin_Mw = e->lin_Mw; }
     }
     return step_launches(e, r, st);
 }
@@ -2615,10 +2672,12 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
     r.known_src = k.known_src; r.known_mask = k.known_mask;      // the merge draws from the window's own Philox pair (r.rng)
     r.meas_y = k.meas_y; r.meas_scale = k.meas_scale; r.meas_gray = k.meas_gray;
+    r.lin_y = k.lin_y; r.lin_Mh = k.lin_Mh; r.lin_Mw = k.lin_Mw;
     if (k.part_K > 1) {                                          // the uniforms come from the window's own Philox pair (r.rng)
         r.part_K = k.part_K; r.part_y = k.part_y; r.part_scale = k.part_scale; r.part_gray = k.part_gray;
         r.part_lambda = k.part_lambda; r.part_tau = k.part_tau; r.part_sigma = k.part_sigma;
         r.part_taps = e->d_blur_taps; r.part_blur_k = k.part_blur_k;
+        r.part_lin_Mh = k.part_lin_Mh; r.part_lin_Mw = k.part_lin_Mw;
         if (!r.xstart) r.xstart = e->d_part_x0;
     }
     if (!rc) rc = step_launches(e, r, st);
@@ -2683,6 +2742,11 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
         VD_REQUIRE(!e->prefix_cache_on, "a measurement (vd_set_measurement) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
         VD_REQUIRE(!e->suffix_skip_on, "a measurement (vd_set_measurement) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
     }
+    if (e->lin_y) {
+        if ((rc = refuse_with_linear_measurement(e, sampler))) return rc;
+        VD_REQUIRE(!e->prefix_cache_on, "a linear measurement (vd_set_linear_measurement) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+        VD_REQUIRE(!e->suffix_skip_on, "a linear measurement (vd_set_linear_measurement) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     VD_REQUIRE(st != nullptr, "the window executor captures a hipGraph: it needs a non-default stream");
     if ((rc = step_workspace(e, B, T, st))) return rc;
@@ -2701,7 +2765,9 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
         key.part_y = e->part_y; key.part_K = e->part_K; key.part_scale = e->part_scale; key.part_gray = e->part_gray;
         key.part_lambda = e->part_lambda; key.part_tau = e->part_tau; key.part_sigma = e->part_sigma;
         key.part_blur_k = e->part_blur ? e->blur_k : 0;
+        if (e->part_lin) { key.part_lin_Mh = e->lin_Mh; key.part_lin_Mw = e->lin_Mw; }
     }
+    if (e->lin_y) { key.lin_y = e->lin_y; key.lin_Mh = e->lin_Mh; key.lin_Mw = e->lin_Mw; }
     if (e->meas_y) { key.meas_y = e->meas_y; key.meas_scale = e->meas_scale; key.meas_gray = e->meas_gray; }
     e->win_cur = -1;
     e->win_lost = false;
@@ -2930,11 +2996,94 @@ int vd_blur_kernel(vd_engine* e, int* k) {
 int vd_set_particle_blur(vd_engine* e, int on) {
     VD_REQUIRE(e, "null engine");
     VD_REQUIRE(!on || e->blur_k, "vd_set_particle_blur: no kernel is installed (vd_set_blur_kernel)");
+    VD_REQUIRE(!on || !e->part_lin, "vd_set_particle_blur together with vd_set_particle_linear is not served: the built-in reward has one operator");
     e->part_blur = on ? 1 : 0;
     return 0;
 }
 
 int vd_particle_blur(vd_engine* e) { return e && e->part_blur ? 1 : 0; }
+
+// ---- the separable linear operator (linop.hip): engine state; the four matrices live in the engine, at addresses that never change
+int vd_set_linear_operator(vd_engine* e, const float* A_h_host, int Mh, const float* A_w_host, int Mw, const float* P_h_host, const float* P_w_host) {
+    VD_REQUIRE(e, "null engine");
+    if (!A_h_host || !A_w_host) {
+        VD_REQUIRE(!e->part_lin, "vd_set_linear_operator: the built-in reward of particle steering reads the operator (vd_set_particle_linear): switch that off first");
+        VD_REQUIRE(!e->lin_y, "vd_set_linear_operator: a linear measurement reads the operator (vd_set_linear_measurement): clear that first");
+        e->lin_Mh = e->lin_Mw = e->lin_back = 0;
+        return 0;
+    }
+    const int S = e->cfg.image_size;
+    VD_REQUIRE(linop_served(S, Mh) && linop_served(S, Mw), "linear operator: A_h is Mh x H and A_w is Mw x W with 1 <= Mh <= H <= 128 and 1 <= Mw <= W <= 128");
+    VD_REQUIRE((P_h_host == nullptr) == (P_w_host == nullptr), "linear operator: P_h and P_w come together, or neither");
+    VD_REQUIRE((!e->lin_y && !e->part_lin) || (Mh == e->lin_Mh && Mw == e->lin_Mw && (!e->lin_y || P_h_host)),
+               "vd_set_linear_operator: a linear measurement or the built-in reward reads the operator: new matrices keep its shape and its back-projection");
+    const float* mats[4] = {A_h_host, A_w_host, P_h_host, P_w_host};
+    const size_t counts[4] = {(size_t)Mh * S, (size_t)Mw * S, (size_t)S * Mh, (size_t)S * Mw};
+    for (int m = 0; m < 4; ++m) {
+        if (!mats[m]) continue;
+        bool nonzero = false;
+        for (size_t i = 0; i < counts[m]; ++i) {
+            VD_REQUIRE(std::isfinite(mats[m][i]), "linear operator: the matrices must be finite");
+            nonzero |= mats[m][i] != 0.f;
+        }
+        VD_REQUIRE(nonzero || m >= 2, "linear operator: A_h and A_w must not be all zero");
+    }
+    const size_t slot = (size_t)kMaxLinopSide * kMaxLinopSide;
+    if (!e->d_lin_mats) VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_lin_mats), 4 * slot * sizeof(float)));
+    VD_HIP(hipDeviceSynchronize());                  // a step that reads the matrices may still run, on any stream
+    for (int m = 0; m < 4; ++m)
+        if (mats[m]) VD_HIP(hipMemcpy(e->d_lin_mats + m * slot, mats[m], counts[m] * sizeof(float), hipMemcpyHostToDevice));
+    e->lin_Mh = Mh; e->lin_Mw = Mw; e->lin_back = P_h_host ? 1 : 0;
+    return 0;
+}
+
+int vd_linear_operator(vd_engine* e, int* Mh, int* Mw) {
+    if (Mh) *Mh = e ? e->lin_Mh : 0;
+    if (Mw) *Mw = e ? e->lin_Mw : 0;
+    return e && e->lin_Mh ? (e->lin_back ? 2 : 1) : 0;
+}
+
+// the projection onto y [B][T][3][Mh][Mw] (device; the caller's) under the installed operator, in every step; a window graph's key
+// carries y and the two sides.  NULL: off.
+int vd_set_linear_measurement(vd_engine* e, const float* y) {
+    VD_REQUIRE(e, "null engine");
+    if (!y) { e->lin_y = nullptr; return 0; }
+    VD_REQUIRE(e->lin_Mh, "linear measurement: no operator is installed (vd_set_linear_operator)");
+    VD_REQUIRE(e->lin_back, "linear measurement: the installed operator has no back-projection (vd_set_linear_operator with P_h and P_w)");
+    VD_REQUIRE(!e->meas_y, "a linear measurement (vd_set_linear_measurement) together with a measurement (vd_set_measurement) is not served");
+    e->lin_y = y;
+    return 0;
+}
+
+int vd_linear_measurement(vd_engine* e) { return e && e->lin_y ? 1 : 0; }
+
+// The built-in reward of particle steering on the installed linear operator in place of the cell mean: y (vd_set_particles) is then
+// [B][T][3][Mh][Mw], and the scale and gray handed to vd_set_particles are not read.  Runs inside the step's launches and is captured into
+// a window graph, whose key carries (Mh, Mw).
+int vd_set_particle_linear(vd_engine* e, int on) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(!on || e->lin_Mh, "vd_set_particle_linear: no operator is installed (vd_set_linear_operator)");
+    VD_REQUIRE(!on || !e->part_blur, "vd_set_particle_linear together with vd_set_particle_blur is not served: the built-in reward has one operator");
+    e->part_lin = on ? 1 : 0;
+    return 0;
+}
+
+int vd_particle_linear(vd_engine* e) { return e && e->part_lin ? 1 : 0; }
+
+// the projection alone on an x_0 handed in, in place, on frames of H x W under matrices on the device (the engine's are not read), no
+// network: the analogue of vd_measurement_project
+int vd_op_linear_project(vd_engine* e, int B, int T, int H, int W, float* x0_inout, const float* y, const float* lat, const float* A_h, int Mh,
+                         const float* A_w, int Mw, const float* P_h, const float* P_w, int clip, void* stream) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(B > 0 && T > 0 && x0_inout && y && lat && A_h && A_w && P_h && P_w, "arguments");
+    VD_REQUIRE(linop_served(H, Mh) && linop_served(W, Mw), "linear operator: A_h is Mh x H and A_w is Mw x W with 1 <= Mh <= H <= 128 and 1 <= Mw <= W <= 128");
+    OpScratch sc(stream);
+    float* rbuf;
+    if (int rc = sc.get(&rbuf, (size_t)B * T * 3 * Mh * Mw)) return rc;
+    LinopArgs la{nullptr, x0_inout, y, lat, nullptr, nullptr, 0, B, T, H, W, Mh, Mw, A_h, A_w, clip, rbuf, nullptr, nullptr, nullptr, x0_inout, nullptr, nullptr};
+    if (int rc = launch_linop_residual(la, nullptr, static_cast<hipStream_t>(stream))) return rc;
+    return launch_linop_project(x0_inout, rbuf, lat, P_h, P_w, B, T, H, W, Mh, Mw, static_cast<hipStream_t>(stream));
+}
 
 int vd_particle_reset(vd_engine* e, int B) {
     VD_REQUIRE(e && e->part_K > 1, "vd_particle_reset: no particles are set (vd_set_particles)");
@@ -3232,6 +3381,7 @@ static int check_diff(vd_engine* e, int B, int T, const std::string& what, bool 
     VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only" + eps_note);
     VD_REQUIRE(e->wbuf_bwd && !e->wbuf_bwd_on_host, what + ": the backward-data weight image is not on the device (vd_set_bwd_weight_storage / vd_load_weight_bwd)");
     VD_REQUIRE(!e->meas_y, what + " together with a measurement (vd_set_measurement) is not served");
+    VD_REQUIRE(!e->lin_y, what + " together with a linear measurement (vd_set_linear_measurement) is not served");
     VD_REQUIRE(e->part_K <= 1, what + " together with particle steering (vd_set_particles) is not served");
     if (!plain_state) return 0;
     VD_REQUIRE(e->cfg_w == 1.f, what + " together with cfg_scale != 1 (vd_set_cfg_scale) is not served");
@@ -3424,6 +3574,69 @@ int vd_op_deblur_seed(vd_engine* e, int B, int T, int H, int W, const float* x, 
 int vd_op_blur(int B, int T, int H, int W, const float* x, const float* taps_dev, int k, int adjoint, float* out, void* stream) {
     VD_REQUIRE(B > 0 && T > 0, "blur: shape");
     return launch_blur_apply(x, taps_dev, k, adjoint, (size_t)B * T * 3, H, W, out, static_cast<hipStream_t>(stream));
+}
+
+// vd_deblur_step on the installed linear operator (vd_set_linear_operator): y is [B][T][3][Mh][Mw], the residual and seed passes are
+// linop.hip's, and everything else is that entry's.
+int vd_linear_dps_step(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs, const float* lat, const float* km,
+                       const long long* fidx, const long long* t, int obs_mode, int clip, int sampler, float eta, const float* noise,
+                       const float* y, float zeta, float* sample, float* xstart, float* grad, float* residual_norm, void* stream) {
+    if (int rc = check_sampler(e, B, T, obs_mode, 2, kObsModes)) return rc;
+    if (int rc = check_diff(e, B, T, "linear_dps")) return rc;
+    VD_REQUIRE(sampler == SAMPLER_P || sampler == SAMPLER_DDIM, "linear_dps: p_sample (0) or ddim_sample (1), got sampler " + std::to_string(sampler));
+    VD_REQUIRE(sampler == SAMPLER_P || eta >= 0.f, "eta");
+    VD_REQUIRE(zeta >= 0.f && zeta <= 3.4028234e38f, "linear_dps: zeta must be finite and not negative");
+    VD_REQUIRE(e->lin_Mh, "linear_dps: no operator is installed (vd_set_linear_operator)");
+    VD_REQUIRE(x && obs_src && obs && lat && km && fidx && t && noise && y && sample && xstart, "null tensor");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int S = e->cfg.image_size, Mh = e->lin_Mh, Mw = e->lin_Mw;
+    const size_t per = (size_t)T * 3 * S * S;
+    const DiffWs w(e, B, T);
+    VD_REQUIRE(w.partials_fit((size_t)B * dps_partials_per_item()), "linear_dps: window too small for its partial sums");
+    FwdIn in{B, T, x, obs_src, obs, lat, km, nullptr, reinterpret_cast<const int64_t*>(fidx), obs_mode, nullptr};
+    return taped_pass(e, w, in, t, st, no_pre, [&](const FwdIn& fi, Arena& ar) {
+        SamplerPassArgs pa = pass_args(e, sampler, B, (long long)per, x, t, clip, sample, xstart);
+        pa.eps = fi.eps; pa.eta = eta; pa.noise = noise;
+        int rc;
+        { ProfScope ps(PC_POSTERIOR, 0.0, 4.0 * B * per * 5.0, st); rc = launch_sampler_pass(pa, st); }
+        if (!rc) {
+            LinopArgs la{x, fi.eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, S, S, Mh, Mw, e->lin_mat(0), e->lin_mat(1),
+                         clip, w.r(), w.partials(), w.deps(), w.dxd(), nullptr, residual_norm, e->d_err};
+            ProfScope ps(PC_ELEMENTWISE, 4.0 * (Mh + Mw) * B * per, 4.0 * B * per * 9.0, st, "linear_dps_seed");
+            rc = launch_linop_seed(la, st);
+        }
+        if (!rc) rc = launch_grad_rescale(w.deps(), w.tot, w.gscale(), st);
+        if (!rc) rc = e->backward(fi, w.deps(), w.dx_net(), st, ar);
+        if (!rc) {
+            ProfScope ps(PC_ELEMENTWISE, 3.0 * B * per, 4.0 * B * per * 5.0, st, "dps_final");
+            rc = launch_dps_final(w.dxd(), w.dx_net(), w.gscale(), lat, B, T, (long)(per / T), zeta, sample, grad, st);
+        }
+        return rc;
+    });
+}
+
+// The residual and seed passes of vd_linear_dps_step alone, on a caller's (x_t, eps) and matrices on the device: no network, no workspace
+// of the engine (tests).
+int vd_op_linear_dps_seed(vd_engine* e, int B, int T, int H, int W, const float* x, const float* eps, const long long* t, int clip,
+                          const float* y, const float* lat, const float* A_h, int Mh, const float* A_w, int Mw, float* deps, float* dxd,
+                          float* rho, float* xstart, void* stream) {
+    VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(B > 0 && T > 0 && x && eps && t && y && lat && A_h && A_w && deps && dxd, "arguments");
+    VD_REQUIRE(linop_served(H, Mh) && linop_served(W, Mw), "linear operator: A_h is Mh x H and A_w is Mw x W with 1 <= Mh <= H <= 128 and 1 <= Mw <= W <= 128");
+    OpScratch sc(stream);
+    float* rbuf; double* part;
+    int rc = sc.get(&rbuf, (size_t)B * T * 3 * Mh * Mw);
+    if (!rc) rc = sc.get(&part, (size_t)B * dps_partials_per_item());
+    if (rc) return rc;
+    LinopArgs la{x, eps, y, lat, reinterpret_cast<const int64_t*>(t), e->d_tab, e->num_timesteps, B, T, H, W, Mh, Mw, A_h, A_w, clip,
+                 rbuf, part, deps, dxd, xstart, rho, e->d_err};
+    return launch_linop_seed(la, static_cast<hipStream_t>(stream));
+}
+
+// out = L x R^T of `planes` planes of Q x U for matrices on the device (L: P x Q, R: S x U; out planes of P x S); out != x.  No engine.
+int vd_op_linop(long long planes, int Q, int U, const float* x, const float* L, int P, const float* R, int S, float* out, void* stream) {
+    VD_REQUIRE(planes > 0, "linop: shape");
+    return launch_linop_apply(x, L, P, Q, R, S, U, (size_t)planes, out, static_cast<hipStream_t>(stream));
 }
 
 // ---- loss guidance: vd_dps_step split where the cotangent is formed, the caller's own code running between the two halves

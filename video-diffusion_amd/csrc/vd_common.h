@@ -665,6 +665,42 @@ int launch_blur_residual(BlurArgs a, int* nblk, hipStream_t s);
 // out = A x (adjoint == 0) or A^T x of `planes` planes of H x W; out != x
 int launch_blur_apply(const float* x, const float* taps, int k, int adjoint, size_t planes, int H, int W, float* out, hipStream_t s);
 
+// Separable linear measurements (linop.hip; this project's extension): the projection of measure.hip, DPS and the built-in reward of
+// particle steering on a measurement y[b][t][c] = A_h x_0[b][t][c] A_w^T of two dense row-major matrices on the device, A_h (Mh x H) and
+// A_w (Mw x W), 1 <= Mh <= H <= kMaxLinopSide, 1 <= Mw <= W <= kMaxLinopSide.  Tensors are [B][T][3][H][W], y and r [B][T][3][Mh][Mw].
+// Every product is Z = L X R^T, the right factor first, each sum from 0 in ascending index order, product and sum each rounded to fp32.
+// launch_linop_seed is launch_blur_seed for this operator -- r = y - A x_0, rho_b, and q = -(A_h^T r A_w) / rho_b; everything else, the
+// poisoning of an item whose t[b] lies outside the schedule included, as DpsArgs states it.  x null (residual pass only): src is the x_0
+// prediction itself, t and the tables are not read, and xstart may alias src.
+constexpr int kMaxLinopSide = 128;
+inline bool linop_served(int n, int m) { return m >= 1 && m <= n && n <= kMaxLinopSide; }
+struct LinopArgs {
+    const float* x;         // x_t, or null (residual pass): src is the x_0 prediction
+    const float* src;       // the network output (eps), or the x_0 prediction
+    const float* y;
+    const float* lat;
+    const int64_t* t;       // [B] respaced index (read with x only)
+    const float* tab; int num_timesteps;
+    int B, T, H, W, Mh, Mw;
+    const float* A_h; const float* A_w;
+    int clip;
+    float* r;               // y's shape: the residual on the latent frames
+    double* part;           // scratch: [B][dps_partials_per_item()]; null (residual pass only): sum r^2 is not kept
+    float* deps; float* dxd;
+    float* xstart;          // the x_0 prediction of every frame (the sampler pass's bits), or null
+    float* rho;             // [B], or null
+    int* err;               // the engine's sticky error word, or null
+    int nblk = 0;           // set by the launchers: partials per item of this launch
+};
+int launch_linop_seed(LinopArgs a, hipStream_t s);
+// the residual pass of launch_linop_seed alone: r, part and xstart where given; *nblk (or null) = the partials per item it wrote
+int launch_linop_residual(LinopArgs a, int* nblk, hipStream_t s);
+// x0 <- x0 + P_h r P_w^T on the frames with lat == 1, in place (P_h: H x Mh, P_w: W x Mw, on the device); other frames keep their bits
+int launch_linop_project(float* x0, const float* r, const float* lat, const float* P_h, const float* P_w, int B, int T, int H, int W, int Mh,
+                         int Mw, hipStream_t s);
+// out = L x R^T of `planes` planes of Q x U (L: P x Q, R: S x U, on the device; out planes of P x S); out != x
+int launch_linop_apply(const float* x, const float* L, int P, int Q, const float* R, int S, int U, size_t planes, float* out, hipStream_t s);
+
 // Particle steering (particles.hip; this project's extension, Feynman-Kac steering: Singhal et al. 2025): B = G*K items, item g*K + k is
 // particle k of group g.  launch_particle_weights, one block per group: the weight update logw += lambda (r - rprev) from the items' rewards
 // (`rewards`, or r = -(sum_j part[b][j]) * inv_two_var, the partials folded in index order), p = softmax(logw), ess = 1 / sum p^2, and --

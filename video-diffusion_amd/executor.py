@@ -23,6 +23,9 @@ on the window tensor, `jump(n)` walks the armed window n forward diffusion steps
 walk of `respace.repaint_schedule` over both; all noise stays on the window's Philox stream (include/vd_amd.h: vd_set_known_region).
 Zero-shot restoration (DDNM, this project's extension too): `begin(..., measurement=, sr_scale=, gray=)` captures a step whose x_0
 prediction is projected onto the measurement in front of the sampler pass (include/vd_amd.h: vd_set_measurement).
+Separable linear measurements (this project's extension): `begin(..., measurement=, operator=(A_h, A_w))` captures the two projection passes
+of csrc/linop.hip in the same place, `begin(..., particle_measurement=, operator=, sigma_y=)` the built-in reward on that operator; the
+matrices live in the engine at fixed addresses (include/vd_amd.h: vd_set_linear_operator).
 Particle steering (this project's extension): `begin(..., particles=K, particle_measurement=, sigma_y=)` captures a step that ends in the
 residual pass, the weights and the gather of the built-in reward; the weights live in the engine, the uniforms on the window's Philox
 stream, and `particle_state()` reads them (include/vd_amd.h: vd_set_particles).
@@ -32,9 +35,9 @@ import math
 import torch as th
 
 from . import _lib
-from .gaussian_diffusion import (SAMPLERS, _check_operator, _engine_measurement, _engine_particles, _engine_region, _refuse, _scope,
-                                 check_blur_kernel, check_blur_measurement, check_known_region, check_measurement, check_steering,
-                                 measurement_shape)
+from .gaussian_diffusion import (SAMPLERS, _check_operator, _engine_linear, _engine_measurement, _engine_particles, _engine_region, _refuse,
+                                 _scope, check_blur_kernel, check_blur_measurement, check_known_region, check_linear_measurement,
+                                 check_measurement, check_separable_operator, check_steering, measurement_shape, separable_pinv)
 
 _OBS_MODES = {"x_0": 0, "x_t": 1, "x_t_minus_1": 2}
 
@@ -87,10 +90,17 @@ class WindowExecutor:
             bufs[key] = th.zeros(*shape, dtype=th.float32, device=self.model.device)
         return bufs[key]
 
+    def _linear_buffer(self, B, T, Mh, Mw, use):
+        """The window's measurement under a separable operator, one buffer per (B, T, Mh, Mw) and use: a stable address."""
+        bufs, key = self._buffers(B, T), f"linear_{use}_{Mh}x{Mw}"
+        if key not in bufs:
+            bufs[key] = th.zeros(B, T, 3, Mh, Mw, dtype=th.float32, device=self.model.device)
+        return bufs[key]
+
     def begin(self, x_init, model_kwargs, t_start=None, seed=None, sampler="p_sample", eta=0.0, clip_denoised=True, renoise=True,
               known_src=None, known_mask=None, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
               ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, blur_kernel=None,
-              cfg_scale=1.0):
+              operator=None, operator_rtol=1e-3, cfg_scale=1.0):
         """Arm a window: copy its tensors into the executor's buffers, set the device counters, capture if new.
         renoise ('x_t_minus_1' only): True = p_sample_loop's form, the clean model_kwargs['x0'] frames re-noised to t - 1 inside
         every step; False = model_kwargs['x_t_minus_1'] read as it is at every step (a direct p_sample caller).
@@ -135,6 +145,14 @@ class WindowExecutor:
         changes: the graph's signature carries k alone, and a begin() with other taps of the same size replays the same graph on the new
         taps.  They stay there until the next kernel is installed (another begin() with a blur, a deblur_scope, a steering_scope with a
         blur), so run() the window before that.
+        operator, operator_rtol (this project's extension; gaussian_diffusion.py: linear_measurement_scope): operator=(A_h, A_w) makes the
+        measurement -- `measurement` or `particle_measurement`, one of them -- one under that separable operator, (B, T, 3, Mh, Mw), and
+        sr_scale, gray and blur_kernel stay at their defaults.  With `measurement` the captured step holds the two projection passes, with
+        the truncated pseudo-inverses separable_pinv(A, operator_rtol) as the back-projection; with `particle_measurement` the built-in
+        reward runs on the operator.  The matrices are copied into the engine's own buffers, whose addresses never change: the graph's
+        signature carries y's address and (Mh, Mw), and a begin() with other matrices of the same shape replays the same graph on them.
+        Without the keyword, a begin() inside `diffusion.linear_measurement_scope(...)` takes the scope's measurement, matrices and
+        back-projection.  A begin() inside `diffusion.linear_dps_scope(...)` is refused by name.
         A begin() inside `diffusion.dps_scope(...)` is refused by name: a DPS step runs a backward pass and is eager only; so is one
         inside `diffusion.loss_guidance_scope(...)`, whose step runs the caller's Python between two launches."""
         cfg_scale = float(cfg_scale)
@@ -148,10 +166,31 @@ class WindowExecutor:
             raise ValueError("known_src and known_mask are given together")
         _refuse(self.model, "dps", "WindowExecutor.begin")               # before anything touches the engine
         _refuse(self.model, "deblur", "WindowExecutor.begin")
+        _refuse(self.model, "linear_dps", "WindowExecutor.begin")
+        lin, lm_scope = None, _scope(self.model, "linear_measurement")
+        if operator is not None:
+            if (measurement is None) == (particle_measurement is None):
+                raise ValueError("WindowExecutor.begin: operator is the operator of measurement= or of particle_measurement=: give one of them")
+            if blur_kernel is not None or not (sr_scale == 1 and gray is False and particle_sr_scale == 1 and particle_gray is False):
+                raise ValueError("WindowExecutor.begin: operator together with blur_kernel, sr_scale or gray is not served: leave them at their defaults")
+            if not isinstance(operator, (tuple, list)) or len(operator) != 2:
+                raise ValueError("WindowExecutor.begin: operator is a pair (A_h, A_w)")
+            a_h, a_w = check_separable_operator(*operator)
+            if measurement is not None:
+                lin = dict(y=check_linear_measurement(measurement, x_init.shape, a_h, a_w), A_h=a_h, A_w=a_w,
+                           P_h=separable_pinv(a_h, operator_rtol)[0], P_w=separable_pinv(a_w, operator_rtol)[0])
+                measurement = None
+            else:
+                operator = (a_h, a_w)
+        elif lm_scope is not None:
+            lin = dict(lm_scope, y=check_linear_measurement(lm_scope["y"], x_init.shape, lm_scope["A_h"], lm_scope["A_w"]))
+        if lin is not None and (measurement is not None or _scope(self.model, "measurement") is not None):
+            raise _lib.VdError("a linear measurement together with a measurement is not served")
         _refuse(self.model, "loss_guidance", "WindowExecutor.begin")     # (a Python callback between two launches cannot be captured)
         steer = self._steering(x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, particle_measurement, particle_sr_scale,
                                particle_gray, sigma_y, blur_kernel, known_src is not None or _scope(self.model, "known_region") is not None,
-                               measurement is not None or _scope(self.model, "measurement") is not None)
+                               measurement is not None or _scope(self.model, "measurement") is not None or lin is not None,
+                               operator if lin is None else None)
         scope = _scope(self.model, "known_region")
         if known_src is not None:
             known_src, known_mask = check_known_region(known_src, known_mask)
@@ -212,9 +251,16 @@ class WindowExecutor:
                     meas["y"].record_stream(self.stream)
                 yb.copy_(meas["y"])
                 meas = dict(meas, y=yb)
+            if lin is not None:
+                yb = self._linear_buffer(B, T, lin["A_h"].shape[0], lin["A_w"].shape[0], "projection")
+                if lin["y"].is_cuda:
+                    lin["y"].record_stream(self.stream)
+                yb.copy_(lin["y"])
+                lin = dict(lin, y=yb)
             if steer is not None:
                 pm = steer["measurement"]
-                yb = self._measurement_buffer(B, T, pm["scale"], pm["gray"], pm.get("kernel") is not None)
+                yb = self._linear_buffer(B, T, pm["A_h"].shape[0], pm["A_w"].shape[0], "reward") if pm.get("A_h") is not None \
+                    else self._measurement_buffer(B, T, pm["scale"], pm["gray"], pm.get("kernel") is not None)
                 if pm["y"].is_cuda:
                     pm["y"].record_stream(self.stream)
                 yb.copy_(pm["y"])
@@ -244,6 +290,9 @@ class WindowExecutor:
             # ... and the measurement: the signature keeps the buffer's address, the scale and the gray flag
             if meas is not None:
                 _engine_measurement(self.model, meas)
+            # ... and the linear measurement: the signature keeps the buffer's address and (Mh, Mw); the matrices' addresses are the engine's
+            if lin is not None:
+                _engine_linear(self.model, op=lin)
             # ... and the particles: the signature keeps K, the scale, the threshold, y's address, the operator and sigma_y
             s_scope = _scope(self.model, "steering")
             if steer is not None:
@@ -257,6 +306,8 @@ class WindowExecutor:
             finally:
                 if steer is not None:
                     _engine_particles(self.model, s_scope)
+                if lin is not None:
+                    _engine_linear(self.model)
                 if meas is not None:
                     _engine_measurement(self.model, m_scope)
                 if region is not None or scope is not None:
@@ -272,7 +323,7 @@ class WindowExecutor:
         return self
 
     def _steering(self, x_init, sampler, eta, particles, reward_fn, reward_scale, ess_threshold, y, sr_scale, gray, sigma_y, blur_kernel, region,
-                  meas):
+                  meas, operator=None):
         """begin()'s particle keywords, or the enclosing steering_scope's setting, checked before anything touches the engine -> a steering
         dict (gaussian_diffusion.py: _engine_particles) or None (the plain window)."""
         scope = _scope(self.model, "steering")
@@ -289,7 +340,10 @@ class WindowExecutor:
             if y is None:
                 raise ValueError("WindowExecutor.begin: particles > 1 needs particle_measurement= and sigma_y= (the built-in reward)")
             K, lam, tau, sig = check_steering(None, y, particles, reward_scale, ess_threshold, sigma_y)
-            if blur_kernel is not None:
+            lin_op = {}
+            if operator is not None:
+                sc, gr, w, lin_op = 1, False, None, dict(A_h=operator[0], A_w=operator[1])
+            elif blur_kernel is not None:
                 if not (sr_scale == 1 and gray is False):
                     raise ValueError("WindowExecutor.begin: blur_kernel together with particle_sr_scale or particle_gray is not served: "
                                      "leave them at their defaults")
@@ -298,9 +352,11 @@ class WindowExecutor:
                 (sc, gr), w = _check_operator(sr_scale, gray), None
             if K == 1 or lam == 0.0:
                 return None
-            d = dict(K=K, scale=lam, tau=tau, measurement=dict(y=y, scale=sc, gray=gr, sigma_y=sig, kernel=w))
+            d = dict(K=K, scale=lam, tau=tau, measurement=dict(y=y, scale=sc, gray=gr, sigma_y=sig, kernel=w, **lin_op))
         m = d["measurement"]
-        if m.get("kernel") is not None:
+        if m.get("A_h") is not None:
+            m = dict(m, y=check_linear_measurement(m["y"], x_init.shape, m["A_h"], m["A_w"]))
+        elif m.get("kernel") is not None:
             m = dict(m, y=check_blur_measurement(m["y"], x_init.shape))
         else:
             m = dict(m, y=check_measurement(m["y"], x_init.shape, m["scale"], m["gray"]))
@@ -385,12 +441,13 @@ class WindowExecutor:
     def sample_window(self, x_init, model_kwargs, sampler="p_sample", eta=0.0, seed=None, renoise=True, known_src=None, known_mask=None,
                       jump_length=1, n_resample=1, measurement=None, sr_scale=1, gray=False, particles=1, reward_fn=None, reward_scale=1.0,
                       ess_threshold=0.5, particle_measurement=None, particle_sr_scale=1, particle_gray=False, sigma_y=None, blur_kernel=None,
-                      cfg_scale=1.0):
+                      operator=None, operator_rtol=1e-3, cfg_scale=1.0):
         """All num_timesteps steps of one window (with a known region and n_resample > 1: the walk of run_repaint); returns a fresh tensor."""
         self.begin(x_init, model_kwargs, seed=seed, sampler=sampler, eta=eta, renoise=renoise, cfg_scale=cfg_scale, known_src=known_src,
                    known_mask=known_mask, measurement=measurement, sr_scale=sr_scale, gray=gray, particles=particles, reward_fn=reward_fn,
                    reward_scale=reward_scale, ess_threshold=ess_threshold, particle_measurement=particle_measurement,
-                   particle_sr_scale=particle_sr_scale, particle_gray=particle_gray, sigma_y=sigma_y, blur_kernel=blur_kernel)
+                   particle_sr_scale=particle_sr_scale, particle_gray=particle_gray, sigma_y=sigma_y, blur_kernel=blur_kernel,
+                   operator=operator, operator_rtol=operator_rtol)
         if int(n_resample) != 1:
             return self.run_repaint(jump_length, n_resample).clone()
         return self.run(self.diffusion.num_timesteps).clone()

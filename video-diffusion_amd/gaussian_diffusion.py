@@ -32,6 +32,10 @@ is the forward step of its resampling walk and `repaint_sample_loop` the loop ar
 x_0 + A^+(y - A x_0), for the cell-mean operators A of `measure` -- super-resolution, colourisation, or both (csrc/measure.hip).
 Deblurring (this project's extension too): `GaussianDiffusion.deblur_scope` is DPS, and `steering_scope(..., blur_kernel=)` the built-in
 reward of particle steering, for a measurement y = blur(video, w) + noise under one real k x k kernel w (csrc/blur.hip).
+Separable linear measurements (this project's extension too): `GaussianDiffusion.linear_measurement_scope` is the exact projection,
+`linear_dps_scope` DPS and `steering_scope(..., operator=)` the built-in reward for any measurement y = A_h x A_w^T of two dense matrices
+per channel plane -- bicubic super-resolution (`resize_matrix`), a separable blur with any padding and stride (`blur_matrix`), the cell
+mean (`box_matrix`) -- with the truncated pseudo-inverse of `separable_pinv` as the back-projection (csrc/linop.hip).
 Training losses are out of scope.
 """
 import contextlib
@@ -234,13 +238,14 @@ def check_known_region(known_src, known_mask):
 
 # the scopes that keep their setting on the model, as attribute _<name> -- in the order a step inside a later one refuses the earlier
 # ones -- and what a refusal raises
-_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "dps": _lib.VdError, "deblur": _lib.VdError,
-           "loss_guidance": _lib.VdError, "steering": NotImplementedError}
+_SCOPES = {"known_region": NotImplementedError, "measurement": _lib.VdError, "linear_measurement": _lib.VdError, "dps": _lib.VdError,
+           "deblur": _lib.VdError, "linear_dps": _lib.VdError, "loss_guidance": _lib.VdError, "steering": NotImplementedError}
 
 
 def _scope(model, name):
     """What the innermost <name>_scope set on this model, or None: known_region (dict src, mask, noise), measurement (dict y, scale, gray),
-    dps (dict y, scale, gray, zeta), deblur (dict y, kernel, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize), steering (dict reward_fn, K, scale, tau,
+    dps (dict y, scale, gray, zeta), deblur (dict y, kernel, zeta), linear_measurement (dict y, A_h, A_w, P_h, P_w), linear_dps (dict y,
+    A_h, A_w, zeta), loss_guidance (dict loss_fn, cotangent_fn, scale, normalize), steering (dict reward_fn, K, scale, tau,
     measurement, uniforms and the chain's bookkeeping)."""
     return getattr(getattr(model, "model", model), "_" + name, None)
 
@@ -333,6 +338,12 @@ def _engine_measurement(model, m):
 
 
 def _check_step_measurement(model, shape):
+    lm = _scope(model, "linear_measurement")
+    if lm is not None:
+        try:
+            check_linear_measurement(lm["y"], shape, lm["A_h"], lm["A_w"])
+        except ValueError as exc:
+            raise ValueError(f"linear_measurement_scope: {exc}") from None
     m = _scope(model, "measurement")
     if m is not None and tuple(m["y"].shape) != measurement_shape(shape, m["scale"], m["gray"]):
         raise ValueError(f"measurement_scope: y {tuple(m['y'].shape)} against a step on {tuple(shape)} at scale={m['scale']}, gray={m['gray']}")
@@ -430,6 +441,199 @@ def _engine_blur(model, _=None):
         _lib.check(_lib.lib().vd_set_blur_kernel(model._handle, _lib.ptr(w), int(w.shape[0])))
 
 
+MAX_OPERATOR_SIDE = 128
+
+
+def _host_matrix(A, name):
+    try:
+        a = A.detach().cpu() if th.is_tensor(A) else th.as_tensor(np.asarray(A))
+    except Exception as exc:
+        raise ValueError(f"{name} must be a 2-D tensor or array, got {type(A).__name__}") from exc
+    if a.dim() != 2 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError(f"{name} must be 2-D (M, n), got {tuple(a.shape)}")
+    if a.dtype == th.bool or not (a.dtype.is_floating_point or a.dtype in (th.int8, th.int16, th.int32, th.int64, th.uint8)):
+        raise ValueError(f"{name} must hold real numbers, got {a.dtype}")
+    return a
+
+
+def check_separable_operator(A_h, A_w):
+    """The checks of a separable linear operator y = A_h x A_w^T on every channel plane (no engine): each matrix a 2-D real tensor or
+    array (M, n) with 1 <= M <= n <= 128, every entry finite, not all of them zero -- ValueError naming the rule otherwise.  Returns
+    (A_h, A_w) as contiguous float32 host tensors: the values the engine is handed."""
+    out = []
+    for name, A in (("A_h", A_h), ("A_w", A_w)):
+        a = _host_matrix(A, name)
+        M, n = int(a.shape[0]), int(a.shape[1])
+        if n > MAX_OPERATOR_SIDE:
+            raise ValueError(f"{name}: the side n={n} must be at most {MAX_OPERATOR_SIDE}")
+        if M > n:
+            raise ValueError(f"{name} is (M, n) with M <= n: a measurement has no more rows than the plane, got {(M, n)}")
+        a = a.to(th.float32).contiguous()
+        if not bool(th.isfinite(a).all()):
+            raise ValueError(f"{name} must be finite: an entry is NaN or Inf (or beyond float32)")
+        if not bool((a != 0).any()):
+            raise ValueError(f"{name} must not be all zero: the measurement would carry nothing")
+        out.append(a)
+    return tuple(out)
+
+
+def separable_pinv(A, rtol=1e-3):
+    """The truncated pseudo-inverse of one factor of a separable operator -> (P, rank): a float64 SVD on the host, the singular values at
+    or below rtol * sigma_max dropped, P = V_k diag(1 / sigma_k) U_k^T (n, M) rounded once to float32.  (A_w (x) A_h)^+ = A_w^+ (x) A_h^+,
+    so the two factors' P are the back-projection of the whole operator.  rtol: a number in [0, 1); ValueError otherwise."""
+    if isinstance(rtol, bool) or not isinstance(rtol, (int, float, np.integer, np.floating)) or not 0.0 <= float(rtol) < 1.0:
+        raise ValueError(f"separable_pinv: rtol={rtol!r} must be a number in [0, 1)")
+    a = _host_matrix(A, "A").to(th.float64)
+    if not bool(th.isfinite(a).all()) or not bool((a != 0).any()):
+        raise ValueError("separable_pinv: A must be finite and not all zero")
+    U, S, Vh = th.linalg.svd(a, full_matrices=False)
+    k = int((S > float(rtol) * S[0]).sum())
+    P = (Vh[:k].T / S[:k]) @ U[:, :k].T
+    return P.to(th.float32).contiguous(), k
+
+
+def _check_side(n, what):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_OPERATOR_SIDE:
+        raise ValueError(f"{what}={n!r} must be an integer in [1, {MAX_OPERATOR_SIDE}]")
+    return int(n)
+
+
+def resize_matrix(n, m, mode="bicubic", antialias=True):
+    """The (m, n) float64 matrix of torch.nn.functional.interpolate(mode=..., antialias=..., align_corners=False) along one axis, n -> m
+    samples, 1 <= m <= n <= 128: the n x n identity resized as one 2-D image to (m, n).  mode: 'bicubic' or 'bilinear'."""
+    n, m = _check_side(n, "resize_matrix: n"), _check_side(m, "resize_matrix: m")
+    if m > n:
+        raise ValueError(f"resize_matrix: m={m} must be at most n={n}: the operator down-samples")
+    if mode not in ("bicubic", "bilinear"):
+        raise ValueError(f"resize_matrix: mode={mode!r} must be 'bicubic' or 'bilinear'")
+    eye = th.eye(n, dtype=th.float64).reshape(1, 1, n, n)
+    return th.nn.functional.interpolate(eye, size=(m, n), mode=mode, antialias=bool(antialias), align_corners=False).reshape(m, n).contiguous()
+
+
+BLUR_PADDINGS = ("zeros", "reflect", "circular")
+
+
+def blur_matrix(n, taps, stride=1, padding="zeros"):
+    """The float64 matrix of a 1-D correlation with `taps` (k of them, k odd, centre c = k // 2) along an axis of n samples, in the
+    orientation `blur` uses, (A x)[i] = sum_a taps[a] x[i + a - c], keeping every stride-th row: (ceil(n / stride), n).  padding: 'zeros'
+    (a tap outside the axis reads 0), 'reflect' (torch's: -1 -> 1, n -> n - 2; needs c < n) or 'circular'."""
+    n = _check_side(n, "blur_matrix: n")
+    try:
+        w = (taps.detach().cpu() if th.is_tensor(taps) else th.as_tensor(np.asarray(taps))).to(th.float64)
+    except Exception as exc:
+        raise ValueError(f"blur_matrix: taps must be a 1-D tensor or array, got {type(taps).__name__}") from exc
+    if w.dim() != 1 or w.numel() == 0 or w.numel() % 2 == 0:
+        raise ValueError(f"blur_matrix: taps must be 1-D with an odd number of entries (a centre tap), got {tuple(w.shape)}")
+    if not bool(th.isfinite(w).all()):
+        raise ValueError("blur_matrix: taps must be finite")
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= int(stride) <= n:
+        raise ValueError(f"blur_matrix: stride={stride!r} must be an integer in [1, n]")
+    if padding not in BLUR_PADDINGS:
+        raise ValueError(f"blur_matrix: padding={padding!r} must be one of {', '.join(BLUR_PADDINGS)}")
+    k, c = int(w.numel()), int(w.numel()) // 2
+    if padding == "reflect" and c >= n:
+        raise ValueError(f"blur_matrix: reflect padding needs k // 2 < n, got k={k}, n={n}")
+    A = th.zeros(n, n, dtype=th.float64)
+    for i in range(n):
+        for a in range(k):
+            j = i + a - c
+            if padding == "circular":
+                j %= n
+            elif padding == "reflect":
+                j = -j if j < 0 else (2 * (n - 1) - j if j >= n else j)
+            elif j < 0 or j >= n:
+                continue
+            A[i, j] += w[a]
+    return A[::int(stride)].contiguous()
+
+
+def box_matrix(n, scale):
+    """The (n / scale, n) float64 matrix of the mean over every cell of `scale` samples: measure(video, scale) is this matrix on both axes."""
+    n = _check_side(n, "box_matrix: n")
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) < 1 or n % int(scale):
+        raise ValueError(f"box_matrix: scale={scale!r} must be a positive integer that divides n={n}")
+    s = int(scale)
+    return th.kron(th.eye(n // s, dtype=th.float64), th.full((1, s), 1.0 / s, dtype=th.float64)).contiguous()
+
+
+def measure_separable(video, A_h, A_w):
+    """A on the host, in torch: video (B, T, 3, H, W) -> y (B, T, 3, Mh, Mw), y[b, t, c] = A_h video[b, t, c] A_w^T.  How a caller makes
+    the y of `linear_measurement_scope` from a video; float64 in, float64 out (float64 matrices are then taken as given), anything else
+    float32 on the matrices check_separable_operator returns."""
+    if not th.is_tensor(video) or video.dim() != 5 or video.shape[2] != 3:
+        raise ValueError(f"measure_separable: a (B, T, 3, H, W) tensor, got {tuple(getattr(video, 'shape', ()))}")
+    a32 = check_separable_operator(A_h, A_w)
+    H, W = int(video.shape[3]), int(video.shape[4])
+    if a32[0].shape[1] != H or a32[1].shape[1] != W:
+        raise ValueError(f"measure_separable: A_h (Mh, {a32[0].shape[1]}) and A_w (Mw, {a32[1].shape[1]}) against planes of {(H, W)}")
+    dt = th.float64 if video.dtype == th.float64 else th.float32
+    mats = [A.detach().to(device=video.device, dtype=dt) if (th.is_tensor(A) and A.dtype == th.float64 and dt == th.float64)
+            else a.to(device=video.device, dtype=dt) for A, a in zip((A_h, A_w), a32)]
+    return (mats[0] @ video.to(dt) @ mats[1].T).contiguous()
+
+
+def check_linear_measurement(y, shape, A_h, A_w):
+    """The checks of a measurement under a separable operator against the video `shape` (B, T, 3, H, W): the matrices' columns are H and
+    W, y is a tensor (B, T, 3, Mh, Mw) and every value of it is finite -- ValueError naming the rule otherwise.  Returns y as contiguous
+    float32, on the device it came on."""
+    if len(shape) != 5 or shape[2] != 3:
+        raise ValueError(f"a video is (B, T, 3, H, W), got {tuple(shape)}")
+    B, T, _, H, W = (int(v) for v in shape)
+    if int(A_h.shape[1]) != H or int(A_w.shape[1]) != W:
+        raise ValueError(f"A_h (Mh, {int(A_h.shape[1])}) and A_w (Mw, {int(A_w.shape[1])}) against a video of {tuple(shape)}: the columns are H and W")
+    want = (B, T, 3, int(A_h.shape[0]), int(A_w.shape[0]))
+    if not th.is_tensor(y) or tuple(y.shape) != want:
+        raise ValueError(f"y must be {want} for a video of {tuple(shape)} under A_h {tuple(A_h.shape)} and A_w {tuple(A_w.shape)}, got "
+                         f"{tuple(getattr(y, 'shape', ()))}")
+    y = y.to(th.float32).contiguous()
+    if not bool(th.isfinite(y).all()):
+        raise ValueError("y must be finite: a measurement holds no NaN and no Inf")
+    return y
+
+
+def _linear_y(y, A_h, A_w, who):
+    """y of a linear scope: (B, T, 3, Mh, Mw) for the matrices' rows; the video's H and W are the matrices' columns."""
+    if not th.is_tensor(y) or y.dim() != 5:
+        raise ValueError(f"{who}: y must be a (B, T, 3, Mh, Mw) tensor, got {tuple(getattr(y, 'shape', ()))}")
+    return check_linear_measurement(y, (y.shape[0], y.shape[1], 3, A_h.shape[1], A_w.shape[1]), A_h, A_w)
+
+
+def _engine_linear(model, _=None, op=None):
+    """Engine state <- the separable operator `op` (a dict A_h, A_w, and with P_h, P_w and y the projection's), or without one what the
+    scopes on this model hold: the linear_measurement scope's (with its back-projection and y), else the linear_dps scope's, else the
+    steering scope's when its built-in reward runs on one, else none.  Every such scope calls this on the way in and on the way out.
+    Clearing leaves the matrices in the engine's buffers: a window graph armed before keeps reading them."""
+    L, h = _lib.lib(), model._handle
+    if op is None:
+        s = _scope(model, "steering")
+        sm = None if s is None else s["measurement"]
+        op = _scope(model, "linear_measurement") or _scope(model, "linear_dps") or (sm if (sm is not None and sm.get("A_h") is not None) else None)
+    _lib.check(L.vd_set_linear_measurement(h, None))
+    if op is None:
+        if not getattr(model, "_particle_linear", False):
+            _lib.check(L.vd_set_linear_operator(h, None, 0, None, 0, None, None))
+        return
+    P_h, P_w = op.get("P_h"), op.get("P_w")
+    _lib.check(L.vd_set_linear_operator(h, _lib.ptr(op["A_h"]), int(op["A_h"].shape[0]), _lib.ptr(op["A_w"]), int(op["A_w"].shape[0]),
+                                        _lib.ptr(P_h), _lib.ptr(P_w)))
+    if P_h is not None:
+        _lib.check(L.vd_set_linear_measurement(h, _lib.ptr(op["y"])))
+
+
+class _LinearScope:
+    """The context manager linear_measurement_scope returns: the scope, and the ranks its pseudo-inverses kept (None with back=)."""
+
+    def __init__(self, cm, rank_h, rank_w):
+        self._cm, self.rank_h, self.rank_w = cm, rank_h, rank_w
+
+    def __enter__(self):
+        self._cm.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        return self._cm.__exit__(*exc)
+
+
 def _scale_number(v, what="scale"):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
         raise ValueError(f"loss_guidance_scope: {what}={v!r}: the step size must be a number, or a callable scale(t) returning one or a (B,) tensor")
@@ -505,13 +709,18 @@ def _engine_particles(model, d):
     if was:
         _lib.check(L.vd_set_particle_blur(model._handle, 0))
         model._particle_blur = False
+    linear = m is not None and m.get("A_h") is not None
+    was_linear = getattr(model, "_particle_linear", False)
+    if was_linear:
+        _lib.check(L.vd_set_particle_linear(model._handle, 0))
+        model._particle_linear = False
     if d is None:
         _lib.check(L.vd_set_particles(model._handle, 0, 0.0, 0.0, None, 1, 0, 0.0))
     else:
         d["B"] = None
         if m is None:
             _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], None, 1, 0, 0.0))
-        elif blurred:                      # y has the video's shape; the engine reads neither scale nor gray (vd_set_particle_blur)
+        elif blurred or linear:            # y has the operator's shape; the engine reads neither scale nor gray (vd_set_particle_blur / _linear)
             _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), 1, 1, m["sigma_y"]))
         else:
             _lib.check(L.vd_set_particles(model._handle, d["K"], d["scale"], d["tau"], _lib.ptr(m["y"]), m["scale"], 1 if m["gray"] else 0, m["sigma_y"]))
@@ -521,6 +730,11 @@ def _engine_particles(model, d):
         model._particle_blur = True
     elif was:
         _engine_blur(model)
+    if linear or was_linear:
+        _engine_linear(model, op=m if linear else None)
+    if linear:
+        _lib.check(L.vd_set_particle_linear(model._handle, 1))
+        model._particle_linear = True
 
 
 def _cfg_scope_or_null(diffusion, model, cfg_scale):
@@ -759,6 +973,71 @@ class GaussianDiffusion:
         m = dict(y=_f32(check_measurement(y, (B, T, 3, Hs * scale, Ws * scale), scale, gray), base.device), scale=scale, gray=gray)
         return _scoped(base, "measurement", m, _engine_measurement)
 
+    measure_separable = staticmethod(measure_separable)
+
+    def linear_measurement_scope(self, model, y, A_h, A_w, *, rtol=1e-3, back=None):
+        """This project's extension: `with diffusion.linear_measurement_scope(model, y, A_h, A_w):` -- measurement_scope for ANY separable
+        linear measurement y[b, t, c] = A_h x[b, t, c] A_w^T of two dense matrices, A_h (Mh, H) and A_w (Mw, W) with 1 <= M <= n <= 128
+        (check_separable_operator): bicubic or bilinear down-sampling (resize_matrix), a separable blur with any padding and stride
+        (blur_matrix), the cell mean (box_matrix).  y = measure_separable(video, A_h, A_w), (B, T, 3, Mh, Mw).  Every step and loop
+        measurement_scope covers, p_mean_variance included, projects the x_0 prediction of the step on the frames with latent_mask == 1:
+        x_0 + P_h (y - A_h x_0 A_w^T) P_w^T, in the place and under the rules of that scope (include/vd_amd.h:
+        vd_set_linear_measurement; csrc/linop.hip).  P_h, P_w = separable_pinv(A, rtol)[0] of the two matrices -- the truncated
+        pseudo-inverse: singular values at or below rtol * sigma_max are dropped, and the scope object's rank_h and rank_w say how many
+        were kept -- or the pair back=(P_h, P_w), (H, Mh) and (W, Mw), as given (rank_h and rank_w are then None).  For a full-rank
+        operator A P = I and measure_separable(pred_xstart) == y up to rounding on the latent frames; for a truncated one the
+        projection is exact on the kept subspace only.
+        Scopes nest; the setting found before is back when the block ends, whatever it raised.  Composes with cfg_scale and
+        guidance_scope.  Refused inside, by name: what measurement_scope refuses, and measurement_scope itself on the same model (the
+        engine refuses the step).  No claim about restoration quality is made."""
+        base = self._bind(model)
+        a_h, a_w = check_separable_operator(A_h, A_w)
+        if back is None:
+            (p_h, rank_h), (p_w, rank_w) = separable_pinv(a_h, rtol), separable_pinv(a_w, rtol)
+        else:
+            if not isinstance(back, (tuple, list)) or len(back) != 2:
+                raise ValueError("linear_measurement_scope: back is a pair (P_h, P_w)")
+            p_h, p_w = (_host_matrix(P, name).to(th.float32).contiguous() for P, name in zip(back, ("P_h", "P_w")))
+            for P, A, name in ((p_h, a_h, "P_h"), (p_w, a_w, "P_w")):
+                if tuple(P.shape) != (A.shape[1], A.shape[0]):
+                    raise ValueError(f"linear_measurement_scope: {name} must be {(int(A.shape[1]), int(A.shape[0]))}, got {tuple(P.shape)}")
+                if not bool(th.isfinite(P).all()):
+                    raise ValueError(f"linear_measurement_scope: {name} must be finite")
+            rank_h = rank_w = None
+        m = dict(y=_f32(_linear_y(y, a_h, a_w, "linear_measurement_scope"), base.device), A_h=a_h, A_w=a_w, P_h=p_h, P_w=p_w)
+        return _LinearScope(_scoped(base, "linear_measurement", m, _engine_linear), rank_h, rank_w)
+
+    def linear_dps_scope(self, model, y, A_h, A_w, *, zeta):
+        """This project's extension: `with diffusion.linear_dps_scope(model, y, A_h, A_w, zeta=0.5):` -- deblur_scope for a NOISY
+        measurement under the separable operator of linear_measurement_scope: y = measure_separable(video, A_h, A_w) plus whatever
+        noise the footage carries, (B, T, 3, Mh, Mw).  Every p_sample and ddim_sample call inside, and every loop built on them, runs the
+        plain step and then moves the frames with latent_mask == 1 down the gradient of rho = ||y - A_h x_0(x_t) A_w^T||_2 with respect
+        to x_t, per batch item: sample = fmaf(-zeta, grad, sample_plain) (include/vd_amd.h: vd_linear_dps_step; csrc/linop.hip).  In
+        every other respect this is deblur_scope under its own name: the cost of a step, windows of at most 32 frames,
+        epsilon-prediction models, the returned 'residual_norm' and 'grad', zeta = 0 the plain step to the bit, its refusals."""
+        base = self._bind(model)
+        a_h, a_w = check_separable_operator(A_h, A_w)
+        zeta = check_zeta(zeta)
+        d = dict(y=_f32(_linear_y(y, a_h, a_w, "linear_dps_scope"), base.device), A_h=a_h, A_w=a_w, zeta=zeta)
+        return _scoped(base, "linear_dps", d, _engine_linear)
+
+    def _linear_dps_step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
+                         use_gradient_method, cfg_scale):
+        """One p_sample (mode 0) / ddim_sample (mode 1) step inside linear_dps_scope -> dict sample, pred_xstart, grad, residual_norm."""
+        d, base, xs, tt, kw = self._moved_step_window("linear_dps", model, x, t, denoised_fn, model_kwargs, return_attn_weights,
+                                                      use_gradient_method, cfg_scale)
+        try:
+            check_linear_measurement(d["y"], xs.shape, d["A_h"], d["A_w"])
+        except ValueError as exc:
+            raise ValueError(f"linear_dps_scope: {exc}") from None
+        noise, sample, xstart, grad = self._moved_step_tensors(base, xs, noise)
+        B, T = xs.shape[:2]
+        rho = th.empty(B, dtype=th.float32, device=base.device)
+        _lib.check(_lib.lib().vd_linear_dps_step(base._handle, B, T, *base._window_ptrs(xs, kw), _lib.ptr(tt), kw["obs_mode"],
+                                                 1 if clip_denoised else 0, mode, float(eta), _lib.ptr(noise), _lib.ptr(d["y"]), d["zeta"],
+                                                 _lib.ptr(sample), _lib.ptr(xstart), _lib.ptr(grad), _lib.ptr(rho), _lib.current_stream()))
+        return {"sample": sample, "pred_xstart": xstart, "grad": grad, "residual_norm": rho}
+
     def dps_scope(self, model, y, scale=1, gray=False, *, zeta):
         """This project's extension (DPS: Chung, Kim, McCann, Klasky, Ye, ICLR 2023): `with diffusion.dps_scope(model, y, scale=4,
         zeta=0.5):` -- restoration from a NOISY degraded copy of the video.  y, scale and gray are measurement_scope's (y =
@@ -786,7 +1065,7 @@ class GaussianDiffusion:
         return _scoped(base, "dps", d)
 
     def _moved_step_window(self, scope, model, x, t, denoised_fn, model_kwargs, return_attn_weights, use_gradient_method, cfg_scale):
-        """The opening of a step inside dps_scope / deblur_scope / loss_guidance_scope (`scope`: 'dps' / 'deblur' / 'loss_guidance'), which runs the plain step and then
+        """The opening of a step inside dps_scope / deblur_scope / linear_dps_scope / loss_guidance_scope (`scope`: its name), which runs the plain step and then
         moves the latent frames: every refusal by name, around _prepare -> (the scope's setting, base, xs, tt, kw)."""
         if self.model_mean_type != ModelMeanType.EPSILON:
             raise NotImplementedError(f"{scope}_scope with predict_xstart=True: epsilon-prediction models only")
@@ -943,7 +1222,7 @@ class GaussianDiffusion:
         return out
 
     def steering_scope(self, model, reward_fn=None, *, particles, scale=1.0, ess_threshold=0.5, measurement=None, sr_scale=1, gray=False,
-                       sigma_y=None, uniforms=None, blur_kernel=None):
+                       sigma_y=None, uniforms=None, blur_kernel=None, operator=None):
         """This project's extension (Feynman-Kac steering: Singhal et al. 2025; the twisted diffusion sampler of Wu et al. 2023 without its
         gradient proposal): `with diffusion.steering_scope(model, reward_fn, particles=K):` -- guidance towards a reward on the step's x_0
         prediction WITHOUT a derivative of the UNet, so it reaches what the gradient scopes do not: windows of up to 128 frames,
@@ -965,7 +1244,9 @@ class GaussianDiffusion:
                              with a gradient and a hand-tuned zeta.  y (B, T, Cy, H / sr_scale, W / sr_scale): a group's items carry the
                              same y.  sigma_y is required.  With blur_kernel=w (deblur_scope's kernel) the operator is the blur
                              instead: y = blur(video, w) + N(0, sigma_y^2) has the video's shape, and sr_scale and gray stay at
-                             their defaults (ValueError otherwise; so is a blur_kernel without a measurement).
+                             their defaults (ValueError otherwise; so is a blur_kernel without a measurement).  With
+                             operator=(A_h, A_w) (linear_measurement_scope's matrices) the operator is that separable one:
+                             y = measure_separable(video, A_h, A_w) + N(0, sigma_y^2) is (B, T, 3, Mh, Mw), under the same rules.
         Served inside: p_sample, ddim_sample with eta > 0, dpmpp_2m_sde_sample and the loops built on them; cfg_scale, guidance_scope with
         any of its options, every observed_frames mode, both mean types.  A step returns its usual dict -- 'sample' and 'pred_xstart' are
         the resampled tensors -- plus 'ancestors' (B,) int32 (the item each item took; itself where nothing moved), 'ess' (G,) and
@@ -983,7 +1264,16 @@ class GaussianDiffusion:
         if uniforms is not None and not (isinstance(uniforms, th.Generator) or callable(uniforms)):
             raise ValueError("steering_scope: uniforms is None, a torch.Generator or a callable uniforms(t)")
         meas = None
-        if blur_kernel is not None:
+        if operator is not None:
+            if measurement is None:
+                raise ValueError("steering_scope: operator is the operator of the built-in reward: it needs measurement= and sigma_y=")
+            if blur_kernel is not None or not (sr_scale == 1 and gray is False):
+                raise ValueError("steering_scope: operator together with blur_kernel, sr_scale or gray is not served: leave them at their defaults")
+            if not isinstance(operator, (tuple, list)) or len(operator) != 2:
+                raise ValueError("steering_scope: operator is a pair (A_h, A_w)")
+            a_h, a_w = check_separable_operator(*operator)
+            meas = dict(y=_f32(_linear_y(measurement, a_h, a_w, "steering_scope"), base.device), scale=1, gray=False, sigma_y=sig, A_h=a_h, A_w=a_w)
+        elif blur_kernel is not None:
             if measurement is None:
                 raise ValueError("steering_scope: blur_kernel is the operator of the built-in reward: it needs measurement= and sigma_y=")
             if not (sr_scale == 1 and gray is False):
@@ -1014,7 +1304,7 @@ class GaussianDiffusion:
             raise NotImplementedError(f"{row.step}{' at eta = 0' if row.noise is not None else ''} inside steering_scope is not served: the step "
                                       "draws no noise, duplicated particles would never separate")
         self._refuse_learned(x)
-        for other in ("known_region", "measurement", "dps", "deblur", "loss_guidance"):
+        for other in ("known_region", "measurement", "linear_measurement", "dps", "deblur", "linear_dps", "loss_guidance"):
             if _scope(model, other) is not None:
                 raise NotImplementedError(f"{other}_scope together with steering_scope is not served")
         for flag, what in ((use_gradient_method, "use_gradient_method"), (return_attn_weights, "return_attn_weights"),
@@ -1024,7 +1314,12 @@ class GaussianDiffusion:
         if x.shape[0] % d["K"]:
             raise ValueError(f"steering_scope: the batch of {x.shape[0]} items is no multiple of particles={d['K']}")
         m = d["measurement"]
-        if m is not None and m.get("kernel") is not None:
+        if m is not None and m.get("A_h") is not None:
+            try:
+                check_linear_measurement(m["y"], x.shape, m["A_h"], m["A_w"])
+            except ValueError as exc:
+                raise ValueError(f"steering_scope: {exc}") from None
+        elif m is not None and m.get("kernel") is not None:
             if tuple(m["y"].shape) != tuple(x.shape):
                 raise ValueError(f"steering_scope: measurement {tuple(m['y'].shape)} against a step on {tuple(x.shape)} under a blur")
         elif m is not None and tuple(m["y"].shape) != measurement_shape(x.shape, m["scale"], m["gray"]):
@@ -1161,7 +1456,8 @@ class GaussianDiffusion:
         self._refuse_learned(x)
         cfg_scale = _check_cfg(cfg_scale, return_attn_weights, use_gradient_method)
         self._last_dps = None
-        for scope, step in (("loss_guidance", self._loss_guidance_step), ("deblur", self._deblur_step), ("dps", self._dps_step)):
+        for scope, step in (("loss_guidance", self._loss_guidance_step), ("linear_dps", self._linear_dps_step), ("deblur", self._deblur_step),
+                            ("dps", self._dps_step)):
             if _scope(model, scope) is not None:                   # p_sample / ddim_sample inside the scope: the plain step, then the scope's move
                 self._last_dps = step(mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta, noise, return_attn_weights,
                                       use_gradient_method, cfg_scale)
@@ -1171,6 +1467,7 @@ class GaussianDiffusion:
         if use_gradient_method:
             _refuse(model, "known_region", "use_gradient_method")
             _refuse(model, "measurement", "use_gradient_method")
+            _refuse(model, "linear_measurement", "use_gradient_method")
             if mode != 0 or denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method: p_sample without denoised_fn (the reference's ddim_sample "
                                           "has no such option, gaussian_diffusion.py:597-634)")
@@ -1179,6 +1476,7 @@ class GaussianDiffusion:
         if denoised_fn is not None:
             _refuse(model, "known_region", "denoised_fn")
             _refuse(model, "measurement", "denoised_fn")
+            _refuse(model, "linear_measurement", "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, mode, eta, noise,
                                  cfg_scale=cfg_scale)
             self._last_attn = out["attn"]                          # the maps of the one forward this step makes (gaussian_diffusion.py:274-324)
@@ -1204,6 +1502,7 @@ class GaussianDiffusion:
             known_noise = region["noise"] if region["noise"] is not None else th.randn_like(xs)    # behind the sampler's own draw
         if row.up:
             _refuse(model, "measurement", row.step)
+            _refuse(model, "linear_measurement", row.step)
         _check_step_measurement(model, xs.shape)
         sample, xstart = th.empty_like(xs), th.empty_like(xs)
         B, T = xs.shape[:2]
@@ -1307,6 +1606,7 @@ class GaussianDiffusion:
         if use_gradient_method:
             _refuse(model, "known_region", "use_gradient_method")
             _refuse(model, "measurement", "use_gradient_method")
+            _refuse(model, "linear_measurement", "use_gradient_method")
             if denoised_fn is not None:
                 raise NotImplementedError("use_gradient_method with denoised_fn")
             g = self._guided(model, x, t, clip_denoised, model_kwargs or {}, _noise=getattr(self, "_guidance_noise", None))
@@ -1315,6 +1615,7 @@ class GaussianDiffusion:
                     "grad": g["grad"]}
         if denoised_fn is not None:
             _refuse(model, "measurement", "denoised_fn")
+            _refuse(model, "linear_measurement", "denoised_fn")
             return self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, return_attn_weights, cfg_scale=cfg_scale)
         model, xs, tt, kw = self._prepare(model, x, t, model_kwargs or {})
         _check_step_measurement(model, xs.shape)
@@ -1417,6 +1718,7 @@ class GaussianDiffusion:
         _refuse(model, "known_region", what)
         _refuse(model, "dps", what)
         _refuse(model, "deblur", what)
+        _refuse(model, "linear_dps", what)
         kw_in = dict(model_kwargs or {})
         kw_in.setdefault("observed_frames", "x_0")
         kw_in.setdefault("x0", x)
@@ -1649,7 +1951,7 @@ class GaussianDiffusion:
         if model_kwargs is None:
             model_kwargs = {}
         self._refuse_learned(x)
-        for scope in (_SCOPES if row.up else ("dps", "deblur", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
+        for scope in (_SCOPES if row.up else ("dps", "deblur", "linear_dps", "loss_guidance")):           # (ddim_reverse_sample is served inside none of the scopes)
             _refuse(model, scope, row.step)
         d = self._check_steered(model, row, 1.0, x, denoised_fn)
         if d is not None:                                                         # dpmpp_2m_sde_sample inside steering_scope
@@ -1665,6 +1967,7 @@ class GaussianDiffusion:
         if denoised_fn is not None:
             _refuse(model, "known_region", "denoised_fn")
             _refuse(model, "measurement", "denoised_fn")
+            _refuse(model, "linear_measurement", "denoised_fn")
             out = self._denoised(model, x, t, clip_denoised, denoised_fn, model_kwargs, False, mode=row.id, noise=noise, philox=philox, **carry)
             return {k: out[k] for k in ("sample", "pred_xstart", "state") if k in out}
         return dict(zip(("sample", "pred_xstart", "state"),

@@ -25,8 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib, inference_util
-from .gaussian_diffusion import (SAMPLERS, _check_guidance, _sampler_step, check_blur_kernel, check_blur_measurement, check_loss_guidance,
-                                 check_measurement, check_zeta, gaussian_kernel)
+from .gaussian_diffusion import (SAMPLERS, _check_guidance, _sampler_step, check_blur_kernel, check_blur_measurement,
+                                 check_linear_measurement, check_loss_guidance, check_measurement, check_separable_operator, check_zeta,
+                                 gaussian_kernel, resize_matrix, separable_pinv)
 from .script_util import (args_to_dict, create_video_model_and_diffusion, str2bool,
                           video_model_and_diffusion_defaults)
 from .weights_init import synth_param
@@ -51,7 +52,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
                 measurement=None, sr_scale=1, gray=False, dps_zeta=None, loss_fn=None, cotangent_fn=None, loss_scale=None,
                 loss_normalize=False, particles=1, reward_fn=None, reward_scale=1.0, ess_threshold=0.5, particle_measurement=None,
-                sigma_y=None, blur_kernel=None):
+                sigma_y=None, blur_kernel=None, operator=None, operator_rtol=1e-3):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -145,7 +146,28 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     (k, k) kernel, k odd and at most 15 (check_blur_kernel); sr_scale and gray stay at their defaults.  It takes one of the two paths that
     accept a noisy measurement, each with its own rules above: dps_zeta= (deblur_scope in place of dps_scope), or particles=K, sigma_y=
     (the built-in reward on the blur; `measurement` is then read as particle_measurement when that is not given).  With neither it is
-    refused by name: the exact projection of measurement_scope has no pseudo-inverse for a blur."""
+    refused by name: the exact projection of measurement_scope has no pseudo-inverse for a blur.
+
+    operator, operator_rtol (this project's extension: separable linear measurements; gaussian_diffusion.py: linear_measurement_scope):
+    operator=(A_h, A_w), A_h (Mh, H) and A_w (Mw, W), makes the measurement one under y[b, t, c] = A_h x[b, t, c] A_w^T over the WHOLE
+    video, (B, T, 3, Mh, Mw) -- what diffusion.measure_separable(video, A_h, A_w) returns; sr_scale, gray and blur_kernel stay at their
+    defaults.  It takes any of the three paths, each with its own rules above: neither option (the exact projection, with the truncated
+    pseudo-inverses separable_pinv(A, operator_rtol); both executors, every sampler a measurement is served with), dps_zeta=
+    (linear_dps_scope), or particles=K, sigma_y= (the built-in reward on the operator; `measurement` is then read as
+    particle_measurement when that is not given; both executors)."""
+    lin = None
+    if operator is not None:
+        if not isinstance(operator, (tuple, list)) or len(operator) != 2:     # before anything touches the engine
+            raise ValueError("operator is a pair (A_h, A_w)")
+        lin = check_separable_operator(*operator)
+        if blur_kernel is not None or not (sr_scale == 1 and gray is False):
+            raise ValueError("operator together with blur_kernel, sr_scale or gray is not served: leave them at their defaults")
+        if measurement is None and particle_measurement is None:
+            raise ValueError("operator needs a measurement (measurement=: measure_separable(video, A_h, A_w))")
+        separable_pinv(lin[0], operator_rtol)                               # (the check of operator_rtol)
+        steered = particles != 1 or sigma_y is not None or particle_measurement is not None
+        if steered and dps_zeta is None and particle_measurement is None:
+            measurement, particle_measurement = None, measurement
     blur_w = None
     if blur_kernel is not None:
         blur_w = check_blur_kernel(blur_kernel)                             # before anything touches the engine
@@ -160,7 +182,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         if steered and dps_zeta is None and particle_measurement is None:
             measurement, particle_measurement = None, measurement
     steer = _check_particles(particles, reward_fn, reward_scale, ess_threshold, particle_measurement, sigma_y, batch, sr_scale, gray, sampler, eta,
-                             executor, blur_w, [("use_gradient_method", use_gradient_method), ("known_mask", known_mask is not None),
+                             executor, blur_w if lin is None else lin, [("use_gradient_method", use_gradient_method), ("known_mask", known_mask is not None),
                                         ("a measurement", measurement is not None), ("dps_zeta", dps_zeta is not None),
                                         ("loss_fn / cotangent_fn", loss_fn is not None or cotangent_fn is not None), ("prefix_cache", prefix_cache),
                                         ("suffix_skip", suffix_skip), ("save_all_timesteps", save_all_timesteps)])
@@ -192,7 +214,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         raise NotImplementedError("sampler='unipc' together with known_mask: the corrector rebuilds the state from its own, the merge of a "
                                   "known region behind the pass would be discarded")
     if measurement is not None:
-        measurement_v = (check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray) if blur_w is None     # before anything touches the engine
+        measurement_v = (check_linear_measurement(torch.as_tensor(measurement), batch.shape, *lin) if lin is not None
+                         else check_measurement(torch.as_tensor(measurement), batch.shape, sr_scale, gray) if blur_w is None     # before anything touches the engine
                          else check_blur_measurement(torch.as_tensor(measurement), batch.shape)).cpu()
         if known_mask is not None:
             raise _lib.VdError("a measurement together with a known region (known_mask) is not served")
@@ -219,7 +242,8 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                                save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, known_mask=known_mask, known_video=known_video,
                                jump_length=jump_length, n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray,
                                particles=particles, reward_fn=reward_fn, reward_scale=reward_scale, ess_threshold=ess_threshold,
-                               particle_measurement=particle_measurement, sigma_y=sigma_y, blur_kernel=blur_kernel)
+                               particle_measurement=particle_measurement, sigma_y=sigma_y, blur_kernel=blur_kernel,
+                               operator=operator, operator_rtol=operator_rtol)
     step_sampler = sampler if sampler in SAMPLERS and not SAMPLERS[sampler].up else "ddim"    # (the eager step: any other name is ddim_sample)
     adaptive = "adaptive" in mode
     if steer is not None:                  # every video as K consecutive items; the return takes one of each group again
@@ -294,12 +318,13 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             if use_graph:
                 wex.begin(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, particles=steer["K"],
                           reward_scale=steer["scale"], ess_threshold=steer["tau"], particle_measurement=pm_w, particle_sr_scale=sr_scale,
-                          particle_gray=gray, sigma_y=sigma_y, blur_kernel=None if pm_w is None else blur_w)
+                          particle_gray=gray, sigma_y=sigma_y, blur_kernel=None if pm_w is None else blur_w,
+                          operator=None if pm_w is None else lin)
                 local_samples = wex.run(diffusion.num_timesteps).clone()
                 chosen = wex.particle_state()["chosen"]
             else:
                 local_samples, chosen = _eager_particle_window(model, diffusion, x0, model_kwargs, step_sampler, eta, cfg_scale, steer, pm_w,
-                                                               sr_scale, gray, sigma_y, t_tensors, timesteps, blur_w)
+                                                               sr_scale, gray, sigma_y, t_tensors, timesteps, blur_w, lin)
             write_back(_chosen_for_all(local_samples, chosen, steer["K"]))
             model.check_device_errors()
             continue
@@ -307,7 +332,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             # renoise=False: like the eager loop below (and scripts/video_sample.py:149-166), every step reads x_t_minus_1 = x0 as it is
             write_back(wex.sample_window(x0, model_kwargs, sampler=sampler, eta=eta, renoise=False, cfg_scale=cfg_scale, known_src=k_src,
                                          known_mask=k_mask, jump_length=jump_length, n_resample=n_resample, measurement=y_w,
-                                         sr_scale=sr_scale, gray=gray))
+                                         sr_scale=sr_scale, gray=gray, operator=None if y_w is None else lin, operator_rtol=operator_rtol))
             model.check_device_errors()
             continue
         if known_mask is not None:
@@ -327,6 +352,9 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
             scope = diffusion.loss_guidance_scope(model, loss_fn, cotangent_fn=cotangent_fn, scale=loss_scale, normalize=loss_normalize)
         elif y_w is None:
             scope = contextlib.nullcontext()
+        elif lin is not None:
+            scope = diffusion.linear_dps_scope(model, y_w, *lin, zeta=dps_zeta) if dps_zeta is not None \
+                else diffusion.linear_measurement_scope(model, y_w, *lin, rtol=operator_rtol)
         elif dps_zeta is not None and blur_w is not None:
             scope = diffusion.deblur_scope(model, y_w, blur_w, zeta=dps_zeta)
         elif dps_zeta is not None:
@@ -355,7 +383,8 @@ def _check_particles(particles, reward_fn, reward_scale, ess_threshold, y, sigma
     K, lam, tau, _ = check_steering(reward_fn, y, particles, reward_scale, ess_threshold, sigma_y)
     y_v = None
     if y is not None:
-        y_v = (check_measurement(torch.as_tensor(y), batch.shape, sr_scale, gray) if blur_w is None
+        y_v = (check_linear_measurement(torch.as_tensor(y), batch.shape, *blur_w) if isinstance(blur_w, tuple)          # (a separable operator)
+               else check_measurement(torch.as_tensor(y), batch.shape, sr_scale, gray) if blur_w is None
                else check_blur_measurement(torch.as_tensor(y), batch.shape)).cpu()
     for name, on in others:
         if on:
@@ -380,14 +409,15 @@ def _chosen_for_all(local, chosen, K):
 
 
 def _eager_particle_window(model, diffusion, x0, model_kwargs, sampler, eta, cfg_scale, steer, y_w, sr_scale, gray, sigma_y, t_tensors, timesteps,
-                           blur_w=None):
+                           blur_w=None, lin=None):
     """One window of infer_video's eager executor inside steering_scope -> (the window's K samples per video, chosen (G,)).  A sampler
     whose noise is the engine's Philox stream draws it, and the uniforms of the built-in reward, where the window executor would."""
     local, carry, out = x0.clone(), None, None
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if SAMPLERS[sampler].noise == "philox" else None
     with diffusion.steering_scope(model, steer["reward_fn"], particles=steer["K"], scale=steer["scale"], ess_threshold=steer["tau"],
                                   measurement=y_w, sr_scale=sr_scale if y_w is not None else 1, gray=gray if y_w is not None else False,
-                                  sigma_y=sigma_y, blur_kernel=None if y_w is None else blur_w):
+                                  sigma_y=sigma_y, blur_kernel=None if y_w is None else blur_w,
+                                  operator=None if y_w is None else lin):
         for timestep in timesteps:
             philox = None if seed is None else (seed, (diffusion.num_timesteps - 1 - timestep) * local.numel())
             out, carry = _sampler_step(diffusion, sampler, model, local, t_tensors[timestep], carry, cfg_scale, eta, philox,
@@ -691,6 +721,17 @@ def build_parser():
                     help="with --measurement: diffusion posterior sampling (DPS) for a measurement that carries noise -- every step moves the "
                          "generated frames down the gradient of ||y - A x_0||_2 through the network with step size Z, in place of the exact "
                          "projection; eager executor, samplers p_sample and ddim; named in the run directory when set")
+    ap.add_argument("--sr_kernel", default="box", choices=["box", "bicubic", "bilinear"],
+                    help="with --measurement and --sr_scale S: how the measurement was down-sampled -- 'box' (default): the S x S cell mean; "
+                         "'bicubic' / 'bilinear': torch's antialiased resampler, (N, T, 3, H / S, W / S), through the separable linear "
+                         "operator (named in the run directory: '_lin<Mh>x<Mw>')")
+    ap.add_argument("--operator_h", default=None, metavar="AH.npy",
+                    help="with --measurement and --operator_w: the measurement is A_h x A_w^T of every channel plane, (N, T, 3, Mh, Mw); AH.npy "
+                         "is the (Mh, H) matrix, Mh <= H <= 128; alone: the exact projection, or with --dps_zeta, or with --particles and "
+                         "--measurement_sigma")
+    ap.add_argument("--operator_w", default=None, metavar="AW.npy", help="with --operator_h: the (Mw, W) matrix")
+    ap.add_argument("--operator_rtol", type=float, default=1e-3, metavar="R",
+                    help="with --operator_h / --sr_kernel: the exact projection drops singular values at or below R times the largest")
     ap.add_argument("--blur_kernel", default=None, metavar="K.npy",
                     help="with --measurement: deblurring -- the measurement is a blurred, noisy copy of the test videos, (N, T, 3, H, W), and "
                          "K.npy the (k, k) kernel it was blurred with (k odd, at most 15; applied as torch's conv2d, zeros outside the frame); "
@@ -761,6 +802,18 @@ def check_particle_arguments(ap, args):
                      "no pseudo-inverse for a blur")
         if int(getattr(args, "sr_scale", 1)) != 1 or getattr(args, "gray", False):
             ap.error("--blur_kernel / --blur_sigma together with --sr_scale or --gray are not served")
+    oh, ow, srk = getattr(args, "operator_h", None), getattr(args, "operator_w", None), getattr(args, "sr_kernel", "box")
+    if bool(oh) != bool(ow):
+        ap.error("--operator_h and --operator_w come together")
+    if oh or srk != "box":
+        if not getattr(args, "measurement", None):
+            ap.error("--operator_h / --operator_w / --sr_kernel need --measurement Y.npy")
+        if kern or bsig is not None or getattr(args, "gray", False):
+            ap.error("--operator_h / --operator_w / --sr_kernel together with --blur_kernel, --blur_sigma or --gray are not served")
+        if oh and (srk != "box" or int(getattr(args, "sr_scale", 1)) != 1):
+            ap.error("--operator_h / --operator_w and --sr_scale / --sr_kernel are two operators: give one")
+        if srk != "box" and int(getattr(args, "sr_scale", 1)) == 1:
+            ap.error("--sr_kernel bicubic / bilinear needs --sr_scale S with S above 1")
     if sigma is not None and not getattr(args, "measurement", None):
         ap.error("--measurement_sigma needs --measurement Y.npy")
     if sigma is not None and getattr(args, "reward", None):
@@ -810,6 +863,21 @@ def blur_kernel_of(args):
     return gaussian_kernel(int(size), float(sigma))
 
 
+def operator_of(args):
+    """--operator_h AH.npy --operator_w AW.npy, or --sr_scale S --sr_kernel bicubic|bilinear on frames of --image_size -> (A_h, A_w),
+    checked float32 host tensors, or None without either (the default --sr_kernel box is the cell-mean path)."""
+    oh, ow, srk = getattr(args, "operator_h", None), getattr(args, "operator_w", None), getattr(args, "sr_kernel", "box")
+    if oh and ow:
+        return check_separable_operator(np.load(oh), np.load(ow))
+    if srk in ("bicubic", "bilinear"):
+        n, S = int(args.image_size), int(getattr(args, "sr_scale", 1))
+        if S < 2 or n % S:
+            raise ValueError(f"--sr_kernel {srk}: --sr_scale S above 1 that divides --image_size {n}")
+        A = resize_matrix(n, n // S, srk)
+        return check_separable_operator(A, A)
+    return None
+
+
 def _measurement_options(args, batch):
     """--measurement / --sr_scale / --gray of the job -> infer_video's keywords for this batch ({} without a measurement).  The
     batch's dataset items are args._batch_ids (run() sets it)."""
@@ -824,6 +892,12 @@ def _measurement_options(args, batch):
         raise ValueError(f"{path}: --measurement is (N, T, Cy, H / S, W / S), got {y.shape}")
     T = batch.shape[1]
     rows = np.stack([np.asarray(y[i][:T], dtype=np.float32) for i in args._batch_ids])
+    lin = operator_of(args)
+    if lin is not None:                                               # a separable operator: any of the three paths
+        kw = dict(operator=lin, operator_rtol=float(getattr(args, "operator_rtol", 1e-3)))
+        if getattr(args, "measurement_sigma", None) is not None:
+            return dict(particle_measurement=torch.from_numpy(rows), sigma_y=float(args.measurement_sigma), **kw)
+        return dict(measurement=torch.from_numpy(rows), **kw, **({} if zeta is None else dict(dps_zeta=float(zeta))))
     blur_w = blur_kernel_of(args)
     if blur_w is not None:                                            # a blurred copy: the video's shape, and one of the two noisy paths
         if getattr(args, "measurement_sigma", None) is not None:
@@ -901,7 +975,7 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
-    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'; under --blur_kernel / --blur_sigma '_blur9' in their place), a --loss_guidance ('_lg0.5': its scale) and --particles
+    --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'; under --blur_kernel / --blur_sigma '_blur9' in their place, under --operator_h / --sr_kernel bicubic '_lin8x8'), a --loss_guidance ('_lg0.5': its scale) and --particles
     above 1 ('_smc8') -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
@@ -915,8 +989,8 @@ def run_postfix(args):
     meas = ""
     if getattr(args, "measurement", None):        # '_sr4', '_gray', '_sr4gray'; under a blur '_blur9'
         S = int(getattr(args, "sr_scale", 1))
-        blur_w = blur_kernel_of(args)
-        meas = f"_blur{int(blur_w.shape[0])}" if blur_w is not None else "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
+        blur_w, lin = blur_kernel_of(args), operator_of(args)
+        meas = f"_lin{int(lin[0].shape[0])}x{int(lin[1].shape[0])}" if lin is not None else f"_blur{int(blur_w.shape[0])}" if blur_w is not None else "_" + ("" if S == 1 else f"sr{S}") + ("gray" if getattr(args, "gray", False) else "")
         if getattr(args, "dps_zeta", None) is not None:
             meas += f"_dps{float(args.dps_zeta):g}"
     lg = ""
