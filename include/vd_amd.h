@@ -130,6 +130,17 @@ int vd_device_errors(vd_engine* e, int* flags);
  * softmax).  vd_guided_step (use_gradient_method), vd_dps_step, vd_eps_vjp and vd_ode_nll_eval are limited to T <= 32.  Larger T fails with a message naming the limit. */
 int vd_max_window_frames(void);
 
+/* The envelope of a model, checked by vd_create (host only) with the launchers' own constants and predicates, so that a model
+ * that cannot be served fails there and not at its first forward.  The message names the parameter, the layer and the limit:
+ *   num_channels           a GroupNorm32 over more than vd_gn_max_channels() = 1024 channels, the two halves of a decoder concat
+ *                          counted together (num_channels 160 at 64 x 64: output_blocks.0 normalises 640 + 640)
+ *   num_heads              a head dim the attention kernels do not serve: vd_attn_temporal_variant / vd_attn_spatial_variant refuse it
+ *                          (multiples of 8; spatial: 8..64, 72, 80, 96, 112, 128), or heads that do not divide a layer's width
+ * The spatial attention's forward has no token ceiling (attention_resolutions is free); the backward-data pass serves 1024 tokens
+ * per frame and says so when it is asked.  The temporal attention's LDS ceiling moves with T and stays at the forward; no head dim
+ * that the spatial attention serves reaches it at T <= 128. */
+int vd_gn_max_channels(void);
+
 /* Bytes of engine-owned workspace a (B, T) window needs; allocated lazily by the first call.  The relative-position tensors
  * grow with B*T^2 (about 60 KB per (b, t, s) pair for the default 64x64 model: ~1 GB at B = 1, T = 128).  The figure is the
  * activation arena of one forward plus the step's tail: t_model, the two network-output buffers (the second one is out_u of a
@@ -1024,7 +1035,7 @@ int vd_op_attn_spatial_weights(const float* qkv, int nfr, int L, int C, int head
 int vd_attn_temporal_variant(int T, int HW, int C, int heads, int rpe, char* name, int cap);
 /* The same for vd_op_attn_spatial (and the engine), in the process' own VD_MATH: "attn_spatial_split_kernel<F,F16,NW>" (f16x3: F16 =
  * true, bf16x6: false; NW = 2 for L <= 64, 4 for L <= 128, 8 above), "attn_spatial_kernel<F>" (fp32), or "refused: <reason>" -- C not
- * divisible by heads, a head dim F = C / heads outside {8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128}, a non-positive L, C or
+ * divisible by heads, a head dim F = C / heads outside {8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128}, a non-positive L, C or
  * heads.  Same return values; host only; the launcher dispatches through the same table and vd_op_attn_spatial returns -1 for a
  * refused shape before any launch.  The frame count is no argument: it never changes the choice. */
 int vd_attn_spatial_variant(int L, int C, int heads, char* name, int cap);

@@ -15,7 +15,7 @@ from attn_spatial_restated import attn_ref, row_scale, scaled_errors
 from video_diffusion_amd import _lib
 
 MODES = {0: "f16x3", 1: "bf16x6", 2: "fp32"}
-HEAD_DIMS = (8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128)
+HEAD_DIMS = (8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128)
 SENTINEL = -7777.25
 FACTOR, FLOOR = 4.0, 2e-6            # e_got <= max(FACTOR e_f32, FLOOR): test_attention_spatial_accuracy_over_magnitudes / test_attention_temporal_per_element
 
@@ -55,7 +55,7 @@ def label(c):
 
 
 # ---- one row per head dim: (F, heads, L at NW = 2 with one key tile, L at NW = 2 with two key tiles, L at NW = 4, L at NW = 8).
-# One and two key tiles both need L <= 64, i.e. NW = 2: 48 cases for the 36 (F, NW) pairs.  Per row: one tile (no second prefetch,
+# One and two key tiles both need L <= 64, i.e. NW = 2: 52 cases for the 39 (F, NW) pairs.  Per row: one tile (no second prefetch,
 # no double buffering), exactly two (stage without prefetch), three or more, and L % 32 = 0, 1 and 31.  Over the rows every L of
 #   NW 2: 1, 16, 31, 32, 33, 64    NW 4: 65, 96, 100, 127, 128    NW 8: 129, 255, 256, 257, 290
 # L = 257, 290: two blocks along x at NW = 8, the second with seven or more wholly invalid waves.  heads = 2: head 1 starts at F in each third.
@@ -63,6 +63,7 @@ VARIANT_ROWS = [
     (8, 2, 1, 64, 127, 257), (16, 1, 16, 33, 128, 255), (24, 2, 31, 64, 65, 290), (32, 1, 32, 33, 127, 256),
     (40, 2, 31, 33, 96, 129), (48, 1, 32, 64, 65, 255), (56, 2, 16, 33, 127, 256), (64, 1, 31, 64, 100, 257),
     (80, 2, 32, 33, 96, 255), (96, 1, 1, 64, 127, 290), (112, 2, 31, 33, 128, 129), (128, 2, 1, 64, 127, 256),
+    (72, 2, 31, 33, 100, 257),           # 288 channels on 4 heads: num_channels 96 at its third level
 ]
 VARIANT_CASES = [Case(2, L, F * heads, heads, nw=nw) for F, heads, *Ls in VARIANT_ROWS for L, nw in zip(Ls, (2, 2, 4, 8))]
 

@@ -1,5 +1,5 @@
-"""GPU: every instantiation behind launch_attn_spatial (csrc/attn_spatial.hip) -- attn_spatial_split_kernel<F,F16,NW> for the twelve head
-dims, NW = 2, 4, 8 and f16x3 | bf16x6 (72), attn_spatial_kernel<F> for VD_MATH=fp32 (12) -- element by element against float64, in all
+"""GPU: every instantiation behind launch_attn_spatial (csrc/attn_spatial.hip) -- attn_spatial_split_kernel<F,F16,NW> for the thirteen head
+dims, NW = 2, 4, 8 and f16x3 | bf16x6 (78), attn_spatial_kernel<F> for VD_MATH=fp32 (13) -- element by element against float64, in all
 three arithmetic modes: the test process' own here, the other two through tools/attn_spatial_check.py as a child process each.
 
 The cases (tests/attn_spatial_cases.py) are compared with tests/attn_spatial_restated.py (checked against explicit loops in
@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 def test_every_instantiation_is_run_and_every_case_runs_the_one_it_names():
     mode = process_mode()
     names = all_variants(mode)
-    assert len(names) == len(set(names)) == (12 if mode == "fp32" else 36)
+    assert len(names) == len(set(names)) == (13 if mode == "fp32" else 39)
     seen = set()
     for c in CASES:
         rc, name = variant_of(c.L, c.C, c.heads)
@@ -78,10 +78,10 @@ def test_attention_spatial_per_element(c):
 
 
 # ---------------------------------------------------------------------------------------------------- the envelope
-@pytest.mark.parametrize("L,C,heads,text", [(64, 8, 2, "head dim one of"), (64, 12, 1, "head dim one of"), (64, 144, 2, "head dim one of"),
+@pytest.mark.parametrize("L,C,heads,text", [(64, 8, 2, "head dim one of"), (64, 12, 1, "head dim one of"), (64, 176, 2, "head dim one of"),
                                             (64, 136, 1, "head dim one of"), (64, 20, 3, "divisible by heads"), (0, 64, 2, "positive")])
 def test_shapes_outside_the_envelope_are_refused_without_a_launch(L, C, heads, text):
-    """Head dims 4, 12, 72 and 136, channels that the heads do not divide and L = 0."""
+    """Head dims 4, 12, 88 and 136, channels that the heads do not divide and L = 0."""
     rc, name = variant_of(L, C, heads)
     assert rc == 0 and name.startswith("refused: ") and text in name, name
     qkv = torch.zeros(max(L, 1) * 3 * C + 64, device="cuda")
@@ -106,7 +106,7 @@ CHILD_TIMEOUT = 300      # library load and device start (some 15 s) + the cases
 def test_every_case_in_every_other_arithmetic_mode(mode):
     """VD_MATH is read once per process: tools/attn_spatial_check.py runs the same table through the same run_case() as a fresh child
     process per mode, and every line is held to the assertions of test_attention_spatial_per_element; the variants the child reports
-    are exactly that mode's 36 (fp32: 12).  The process' own mode is covered above and skipped here."""
+    are exactly that mode's 39 (fp32: 13).  The process' own mode is covered above and skipped here."""
     if mode == process_mode():
         pytest.skip("the test process' own mode: the tests above run in it")
     assert not CHILD_DIED, f"the {CHILD_DIED[0]} child ended by signal or timeout: no further child is started"
@@ -128,6 +128,6 @@ def test_every_case_in_every_other_arithmetic_mode(mode):
         assert row["label"] == label(c) and row["mode"] == mode and row["expected_variant"] == variant_name(c, mode)
         assert not failures(row), (row["label"], failures(row), row)
     names = all_variants(mode)
-    assert sorted({row["variant"] for row in rows}) == sorted(names) and len(names) == (12 if mode == "fp32" else 36)
+    assert sorted({row["variant"] for row in rows}) == sorted(names) and len(names) == (13 if mode == "fp32" else 39)
     print(f"spatial attention, {mode}: {len(names)} of {len(names)} instantiations run at op level")
     assert summary["failed"] == [] and summary["variants"] == len(names)

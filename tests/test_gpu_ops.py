@@ -804,7 +804,7 @@ def test_every_arithmetic_mode_end_to_end(mode):
     """Every VD_MATH mode the library ships is held to the SAME bar as the default one: the mode is read once per process, so
     tools/mode_check.py runs as a child process per mode -- a linear layer and a 3x3 conv against fp64 next to the fp32-MFMA
     kernel, and the whole network against the reference's goldens (tiny config: 10 eps cases + p_sample at four timesteps;
-    the default 116 M model) at the tier's tolerance 1e-4 + 1e-4 |ref|.  The process' own mode is covered by the rest of
+    the default 116 M model; the 96- and 160-channel configurations of the sweep) at the tier's tolerance 1e-4 + 1e-4 |ref|.  The process' own mode is covered by the rest of
     this suite and skipped here."""
     import json
     import subprocess
@@ -812,13 +812,18 @@ def test_every_arithmetic_mode_end_to_end(mode):
     if mode == math_mode():
         pytest.skip("the test process' own mode: the whole suite runs in it")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "mode_check.py")], env={**os.environ, "VD_MATH": mode},
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "mode_check.py"), "--configs"], env={**os.environ, "VD_MATH": mode},
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     rep = json.loads(r.stdout.strip().splitlines()[-1])
     assert rep["mode"] == mode and mode in rep["version"]
     for net in ("eps_tiny", "psample_tiny", "eps_full64"):
         assert rep[net]["outside_tol"] == 0, (net, rep[net])
+    from config_sweep_cases import MODE_TAGS
+    assert sorted(rep["eps_configs"]) == sorted(MODE_TAGS)                  # 96 and 160 channels (tests/test_gpu_config_sweep.py)
+    for tag, fig in rep["eps_configs"].items():
+        print(f"{mode} {tag}: max |d eps| = {fig['max_err']:.3e} over {fig['compared']} elements, |eps| up to {fig['eps_max']:.2f}")
+        assert fig["outside_tol"] == 0 and fig["compared"] > 0, (tag, fig)
     fmax, fmean = (1.5, 1.25) if mode == "f16x3" else (1.5, 1.5)
     for op in ("linear", "conv"):
         k = rep[op]["fp32_kernel"]

@@ -8,7 +8,7 @@ Importing this package does not touch the reference: the producers load it when 
 Every producer takes the output directory, returns the paths it wrote, and gives the same output whether it runs alone
 or after any other producer: inputs come from explicit generators, and a producer that lets the reference draw from
 torch's global generator (loops, nll*, full_sampler) seeds it right before the call."""
-from . import full_size, guidance, jobs, long_window, loops_nll, optimal_schedule, room_seq, schedules, steps
+from . import configs, full_size, guidance, jobs, long_window, loops_nll, optimal_schedule, room_seq, schedules, steps
 
 # fixture file -> (producer, rough CPU seconds of the producer on 8 threads, needs a full-size model?)
 MANIFEST = {
@@ -49,6 +49,7 @@ MANIFEST = {
     "script_imports.json": (jobs.script_imports, 1, False),
     "optimal_schedule_search.json": (optimal_schedule.search, 3, False),
     "room_seq_acc.json": (room_seq.room_seq, 1, False),
+    "unet_configs.npz": (configs.unet_configs, 30, False),
 }
 
 # JSON keys that hold wall-clock seconds: `check` does not compare them, and `write` leaves an existing file alone when

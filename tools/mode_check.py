@@ -6,7 +6,10 @@ bench.py for the modes it reports beside the headline).  One JSON line:
                             figures of the fp32-MFMA kernel (gemm_frag.hip / conv_wino.hip / the generic kernel) on the same inputs
   eps_tiny, eps_full64    : elements outside 1e-4 + 1e-4 |ref| and max |eps - golden| on tests/golden/unet_tiny.npz (10 cases) and
                             unet_full64.npz (the default 116 M model), both minted from the imported reference
-  psample_tiny            : the same for p_sample at t = 249, 248, 1, 0 on tests/golden/psample_tiny.npz"""
+  psample_tiny            : the same for p_sample at t = 249, 248, 1, 0 on tests/golden/psample_tiny.npz
+  eps_configs             : with --configs only (the per-mode test passes it): the same per configuration of
+                            tests/config_sweep_cases.py's MODE_TAGS on tests/golden/unet_configs.npz (96 and 160 channels: generic and
+                            Winograd convs alternate, and the backward image's kernel follows the mode)"""
 import json
 import os
 import sys
@@ -110,7 +113,28 @@ def main():
             scale = float(np.abs(rec["eps"]).max())
         out[tag] = {"outside_tol": bad, "max_err": worst, "eps_max": scale}
         del model
+    if "--configs" in sys.argv[1:]:
+        out["eps_configs"] = eps_configs()
     print(json.dumps(out))
+
+
+def eps_configs():
+    from config_sweep_cases import MODE_TAGS, case
+    rep = {}
+    for tag in MODE_TAGS:
+        k = case(tag)
+        cfg, c, s = k["cfg"], k["c"], k["stride"]
+        model, diff = vda.create_video_model_and_diffusion(**{key: cfg[key] for key in vda.video_model_and_diffusion_defaults()})
+        model.load_state_dict(synth_sd(model.param_specs()))
+        model.to("cuda").eval()
+        kw = dict(frame_indices=c["frame_indices"].cuda(), x0=c["x0"].cuda(), obs_mask=c["obs_mask"].cuda(), latent_mask=c["latent_mask"].cuda(),
+                  kinda_marg_mask=c["kinda_marg_mask"].cuda(), x_t_minus_1=c["x0"].cuda(), observed_frames="x_0")
+        eps, _ = diff._wrap_model(model)(c["x"].cuda(), k["t"].cuda(), **kw)
+        bad, worst = outside(eps.cpu()[..., ::s, ::s], k["eps"])
+        model.check_device_errors()
+        rep[tag] = {"outside_tol": bad, "max_err": worst, "eps_max": float(k["eps"].abs().max()), "compared": k["eps"].numel()}
+        del model
+    return rep
 
 
 if __name__ == "__main__":

@@ -145,6 +145,7 @@ SIGNATURES = {
     "vd_version": (ctypes.c_char_p, []),
     "vd_source_sha": (ctypes.c_char_p, []),
     "vd_max_window_frames": (_I, []),
+    "vd_gn_max_channels": (_I, []),
     "vd_create": (_I, [ctypes.POINTER(VdConfig), ctypes.POINTER(_P)]),
     "vd_destroy": (None, [_P]),
     "vd_param_count": (_I, [_P]),

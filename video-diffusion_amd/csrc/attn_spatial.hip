@@ -436,7 +436,7 @@ struct AttnSpatialRow {
                     {FV, 2, true, launch_attn_spatial_split<FV, true, 2>}, {FV, 4, true, launch_attn_spatial_split<FV, true, 4>}, {FV, 8, true, launch_attn_spatial_split<FV, true, 8>},    \
                     {FV, 2, false, launch_attn_spatial_split<FV, false, 2>}, {FV, 4, false, launch_attn_spatial_split<FV, false, 4>}, {FV, 8, false, launch_attn_spatial_split<FV, false, 8>}
 static const AttnSpatialRow kAttnSpatialRows[] = {VD_ROWS(8), VD_ROWS(16), VD_ROWS(24), VD_ROWS(32), VD_ROWS(40), VD_ROWS(48),
-                                                  VD_ROWS(56), VD_ROWS(64), VD_ROWS(80), VD_ROWS(96), VD_ROWS(112), VD_ROWS(128)};
+                                                  VD_ROWS(56), VD_ROWS(64), VD_ROWS(72), VD_ROWS(80), VD_ROWS(96), VD_ROWS(112), VD_ROWS(128)};
 #undef VD_ROWS
 
 AttnSpatialVariant attn_spatial_variant(int L, int C, int heads) {
@@ -451,7 +451,7 @@ AttnSpatialVariant attn_spatial_variant(int L, int C, int heads) {
         const AttnSpatialRow& r = kAttnSpatialRows[i];
         if (r.F == F && r.NW == NW && r.f16 == f16) return AttnSpatialVariant{i, F, NW, f16, nullptr};
     }
-    v.why = "head dim one of 8, 16, 24, 32, 40, 48, 56, 64, 80, 96, 112, 128";
+    v.why = "head dim one of 8, 16, 24, 32, 40, 48, 56, 64, 72, 80, 96, 112, 128";
     return v;
 }
 

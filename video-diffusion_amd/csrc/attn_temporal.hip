@@ -540,7 +540,11 @@ static int launch_variant(const AttnTemporalVariant& v, const AttnTemporalArgs& 
 int launch_attn_temporal(const AttnTemporalArgs& a, hipStream_t s) {
     const bool rpe = a.Rk != nullptr;
     const AttnTemporalVariant v = attn_temporal_variant(a.T, a.HW, a.C, a.heads, rpe);
-    VD_REQUIRE(v.family != AttnTemporalVariant::kRefused, v.why);
+    if (v.family == AttnTemporalVariant::kRefused) {
+        set_error(std::string("temporal attention: ") + v.why + " (head dim " + std::to_string(a.heads > 0 ? a.C / a.heads : 0) + " = " + std::to_string(a.C) +
+                  " channels on " + std::to_string(a.heads) + " heads, T = " + std::to_string(a.T) + ")");
+        return -1;
+    }
     VD_REQUIRE((a.Rk == nullptr) == (a.Rq == nullptr) && (a.Rk == nullptr) == (a.Rv == nullptr), "all or no RPE terms");
     if (v.family == AttnTemporalVariant::kLongMfma || v.family == AttnTemporalVariant::kLongGeneric) return launch_attn_temporal_long(a, s);
     return rpe ? launch_variant<true>(v, a, s) : launch_variant<false>(v, a, s);

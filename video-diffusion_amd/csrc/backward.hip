@@ -120,6 +120,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GnBwdArgs a, int per)
 
 int gn_bwd_split(int nfr, int HW, int C) { return gn_stats_split(nfr, HW, C); }
 
+VD_GN_LIMIT_IS_1024;
+
 int launch_gn_bwd(const GnBwdArgs& a, hipStream_t s) {
     VD_REQUIRE(a.C % 32 == 0 && a.C <= 1024 && a.C0 % 4 == 0 && (a.x1 != nullptr || a.C0 == a.C), "GroupNorm backward: channel counts");
     VD_REQUIRE(a.part && a.K && a.mr && a.dx0 && (a.dx1 || a.C0 == a.C), "GroupNorm backward: buffers");

@@ -623,7 +623,18 @@ int vd_engine::build() {
     };
     auto bwd3 = [&](int p, int rs) { params[p].kind_bwd = k3b(rs, (int)params[p].shape[1], (int)params[p].shape[0]); };
     auto bwdl = [&](int p) { params[p].kind_bwd = PK_LINF; };
-    auto add_res = [&](const std::string& pre, int cin, int cout, int rs) {
+    // The envelope: what no launch could serve is refused at the end of build(), by parameter, layer and limit, with the launchers'
+    // own constant (kGnMaxChannels) and predicates (attn_temporal_variant at T = 1, attn_spatial_variant) -- not at the first
+    // forward.  The first offending layer per parameter is named; the layout goes on so that both are found.
+    std::string bad_width, bad_heads;
+    auto gn_fits = [&](const std::string& layer, int C, int skip) {
+        if (C <= kGnMaxChannels || !bad_width.empty()) return;
+        bad_width = "num_channels=" + std::to_string(mc) + ": " + layer + " normalises " + std::to_string(C) + " channels" +
+                    (skip ? " (" + std::to_string(C - skip) + " + " + std::to_string(skip) + " of the skip connection)" : std::string()) +
+                    "; GroupNorm32 serves at most " + std::to_string(kGnMaxChannels) + " (vd_gn_max_channels)";
+    };
+    auto add_res = [&](const std::string& pre, int cin, int cout, int rs, int skip = 0) {
+        gn_fits(pre + ".in_layers.0", cin, skip); gn_fits(pre + ".out_layers.0", cout, 0);
         ResP r; r.cin = cin; r.cout = cout;
         r.gn1w = add(pre + ".in_layers.0.weight", {cin}); r.gn1b = add(pre + ".in_layers.0.bias", {cin});
         r.c1w = add(pre + ".in_layers.2.weight", {cout, cin, 3, 3}, k3(rs, cout)); r.c1b = add(pre + ".in_layers.2.bias", {cout});
@@ -658,8 +669,19 @@ int vd_engine::build() {
         }
         return r;
     };
-    auto add_attn = [&](const std::string& pre, int C) {
-        VD_REQUIRE(C % cfg.num_heads == 0 && (C / cfg.num_heads) % 8 == 0, "head dim must be a multiple of 8");
+    auto add_attn = [&](const std::string& pre, int C, int rs) {
+        const int heads = cfg.num_heads, L = rs * rs;
+        const std::string where = "num_heads=" + std::to_string(heads) + ": " + pre + " (" + std::to_string(C) + " channels at " + std::to_string(rs) + " x " +
+                                  std::to_string(rs) + ", attention_resolutions " + std::to_string(rs) + ")";
+        const AttnTemporalVariant tv = attn_temporal_variant(1, L, C, heads, true);
+        const AttnSpatialVariant sv = attn_spatial_variant(L, C, heads);
+        const bool t_no = tv.family == AttnTemporalVariant::kRefused;
+        if (bad_heads.empty() && C % heads != 0)
+            bad_heads = where + ": " + std::to_string(C) + " channels do not divide into " + std::to_string(heads) + " heads";
+        else if (bad_heads.empty() && (t_no || sv.row < 0))
+            bad_heads = where + " has head dim " + std::to_string(C / heads) + "; " +
+                        (t_no ? std::string("temporal attention: ") + tv.why : std::string("spatial attention: ") + sv.why);
+        gn_fits(pre + ".norm", C, 0);
         AttnP a; a.C = C;
         a.sp = add_att(pre + ".spatial_attention", C);
         a.tp = add_att(pre + ".temporal_attention", C);
@@ -693,7 +715,7 @@ int vd_engine::build() {
             int ri = add_res(pre + ".0", ch, mult[lvl] * mc, cfg.image_size / ds);
             blk.push_back(Layer{1, ri});
             ch = mult[lvl] * mc;
-            if (in_att(ds)) { int ai = add_attn(pre + ".1", ch); if (ai < 0) return ai; blk.push_back(Layer{2, ai}); }
+            if (in_att(ds)) { int ai = add_attn(pre + ".1", ch, cfg.image_size / ds); if (ai < 0) return ai; blk.push_back(Layer{2, ai}); }
             input_blocks.push_back(blk);
             chans.push_back(ch);
         }
@@ -714,7 +736,7 @@ int vd_engine::build() {
     }
     {
         int r0 = add_res("middle_block.0", ch, ch, cfg.image_size / ds);
-        int a0 = add_attn("middle_block.1", ch); if (a0 < 0) return a0;
+        int a0 = add_attn("middle_block.1", ch, cfg.image_size / ds); if (a0 < 0) return a0;
         int r1 = add_res("middle_block.2", ch, ch, cfg.image_size / ds);
         middle = {Layer{1, r0}, Layer{2, a0}, Layer{1, r1}};
     }
@@ -723,10 +745,10 @@ int vd_engine::build() {
             const std::string pre = "output_blocks." + std::to_string(output_blocks.size());
             std::vector<Layer> blk;
             const int skip = chans.back(); chans.pop_back();
-            blk.push_back(Layer{1, add_res(pre + ".0", ch + skip, mc * mult[lvl], cfg.image_size / ds)});
+            blk.push_back(Layer{1, add_res(pre + ".0", ch + skip, mc * mult[lvl], cfg.image_size / ds, skip)});
             ch = mc * mult[lvl];
             int li = 1;
-            if (in_att(ds)) { int ai = add_attn(pre + "." + std::to_string(li++), ch); if (ai < 0) return ai; blk.push_back(Layer{2, ai}); }
+            if (in_att(ds)) { int ai = add_attn(pre + "." + std::to_string(li++), ch, cfg.image_size / ds); if (ai < 0) return ai; blk.push_back(Layer{2, ai}); }
             if (lvl && i == nrb) {
                 // Upsample + conv: the sub-pixel form where the split Winograd kernel serves the SOURCE map
                 const int rs_src = cfg.image_size / ds;
@@ -742,6 +764,10 @@ int vd_engine::build() {
     for (size_t i = 0; i < output_blocks.size(); ++i)
         for (size_t l = 0; l < output_blocks[i].size(); ++l)
             if (output_blocks[i][l].type == 2) { suf_blk = (int)i; suf_layer = (int)l; }
+    if (!bad_width.empty() || !bad_heads.empty()) {
+        set_error(bad_width + (!bad_width.empty() && !bad_heads.empty() ? ";  " : "") + bad_heads);
+        return -1;
+    }
     final_ch = ch;
     p_outgw = add("out.0.weight", {ch}); p_outgb = add("out.0.bias", {ch});
     const int oc = cfg.learn_sigma ? 6 : 3;                                                    // script_util.py:129-131
@@ -2033,6 +2059,7 @@ static int check_sampler(vd_engine* e, int B, int T, int obs_mode, int max_obs_m
 static const char* const kObsModes = "observed_frames must be x_0 / x_t / x_t_minus_1";
 
 int vd_max_window_frames(void) { return kMaxWindowFrames; }
+int vd_gn_max_channels(void) { return kGnMaxChannels; }
 
 int vd_unet_forward(vd_engine* e, int B, int T, const float* x, const float* obs_src, const float* obs,
                     const float* lat, const float* km, const long long* fidx, const float* t_model, int obs_mode,

@@ -71,6 +71,8 @@ int gn_stats_split(int nfr, int HW, int C) {
     return split;
 }
 
+VD_GN_LIMIT_IS_1024;
+
 int launch_gn_stats(const float* src0, const float* src1, int C0, int C, int nfr, int HW, double* part, int split,
                     hipStream_t s) {
     VD_REQUIRE(C >= 32 && C % 32 == 0 && C <= 1024 && C0 % 4 == 0 && C0 > 0 && C0 <= C, "GroupNorm32 channel constraints");

@@ -15,6 +15,13 @@ namespace vd {
 // (attn_temporal.hip, norm.hip) and for 33..128 (attn_temporal_long.hip, norm.hip's long form).  The guided step's backward
 // kernels (use_gradient_method, backward.hip) stay at kMaxGuidedWindowFrames.
 constexpr int kMaxWindowFrames = 128;
+// Widest tensor the GroupNorm32 launchers serve, the two halves of a decoder concat counted together: a thread per channel quad and
+// whole pixels in a block of 256 threads (norm.hip, backward.hip).  The launchers spell the number out in their requirements
+// (`C <= 1024`, so that their messages do) beside a static_assert against this constant; vd_create refuses a model that would need
+// more, by layer (engine.hip).
+constexpr int kGnThreadsPerBlock = 256;
+constexpr int kGnMaxChannels = 4 * kGnThreadsPerBlock;
+#define VD_GN_LIMIT_IS_1024 static_assert(vd::kGnMaxChannels == 1024, "the GroupNorm launchers' `C <= 1024` is kGnMaxChannels")
 constexpr int kMaxGuidedWindowFrames = 32;
 
 // Error plumbing: every C-ABI entry returns 0 or a negative code; text via vd_last_error().
