@@ -439,6 +439,47 @@ int vd_set_cfg_scale(vd_engine* e, float w);
 float vd_cfg_scale(vd_engine* e);
 int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream);
 
+/* FreeU -- this project's extension (Si, Huang, Jiang, Liu: "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024): the one option that acts
+ * INSIDE the UNet forward.  Decoder levels count from the bottom: stage 1 is the first num_res_blocks + 1 output blocks (lowest
+ * resolution) with the constants (b1, s1), stage 2 the next num_res_blocks + 1 with (b2, s2).  Every model vd_create builds has both:
+ * the level count follows the image size, four to six levels (vd_freeu_stages() == 2; a topology of one level, which cannot be created
+ * today, would have stage 1 alone).  Every output block of a stage reads cat([h', skip']) in the place of
+ * cat([h, skip]), h and skip being N frames of S x S pixels, channels-last:
+ *   skip' (the skip filter): per frame and channel, with theta = 2 pi / S and x the S x S plane,
+ *     x'[i,j] = x[i,j] + (s - 1)/S^2 (m0 + ci cos(theta i) + si sin(theta i) + cj cos(theta j) + sj sin(theta j)
+ *                                        + cd cos(theta (i+j)) + sd sin(theta (i+j))),
+ *     m0 = sum x, (ci, si) = sum x[i',j'] (cos, sin)(theta i'), (cj, sj) the same in j', (cd, sd) the same in i' + j'
+ *     = Re ifft2(M . fft2(x)) with M = s on the four bins (u, v) in {0, S-1}^2 and 1 elsewhere: the published code's fftshift box
+ *     [S/2 - 1 : S/2 + 1]^2 at threshold 1 with .real taken.  The threshold is fixed at 1.
+ *   h' (the backbone scale): with H = C_h / 2, channels c >= H are copied; for c < H
+ *     plain:    h' = (float)b * h, one fp32 multiply;
+ *     adaptive: h' = h ((b - 1) g + 1), g = (m - lo)/(hi - lo), m[n,p] the mean of h[n,p,:] over ALL C_h channels, lo and hi its
+ *               minimum and maximum over the pixels of frame n (the paper's structure-aware form).  hi == lo gives g = 0, where the
+ *               published code divides 0 by 0.
+ * The seven sums, the mean, min / max, g, the factor and the update are fp64 in a fixed order without atomics, the result is rounded once
+ * to fp32: two runs on equal inputs give equal bits.  The cos / sin tables of the two sides are computed on the host in double and
+ * uploaded by the first vd_set_freeu that switches the option on.  h' and skip' go to engine-owned buffers (one pair, reused block after
+ * block; never in place: a skip tensor may outlive the step), and so do their GroupNorm partial sums, one statistics pass over each
+ * modified half: FreeU takes nothing from the step's workspace, whose size does not depend on it.
+ * vd_set_freeu: all four constants must be finite and > 0; all four equal to 1 = off (the default): no launch is added and every entry
+ * is the one it was, to the bit.  Otherwise a stage with b == 1 adds no backbone launch and one with s == 1 no filter launch; per block
+ * the plain form adds up to 2 launches, the adaptive form up to 3 (the structure map is a launch of its own).
+ * Honoured by every untaped forward: vd_unet_forward, vd_p_mean_variance, the step entries (vd_p_sample, vd_ddim_sample,
+ * vd_ddim_reverse_sample, vd_dpmpp_2m_sample, vd_dpmpp_2m_sde_sample, vd_unipc_sample) -- both forwards of a cfg_scale step -- and
+ * vd_window_begin / vd_window_run, where the constants are part of a captured graph's signature.  Refused by name while it is on:
+ * vd_guided_step, vd_dps_step, vd_deblur_step, vd_linear_dps_step, vd_guide_begin, vd_eps_vjp and vd_ode_nll_eval (the taped forward
+ * does not run the passes), vd_score_windows and vd_vb_terms (the search and the NLL score the model as trained), and vd_window_begin
+ * while the prefix cache or the suffix skip is switched on.
+ * vd_freeu: returns 1 while on, 0 while off; consts (4 doubles: b1, b2, s1, s2) and adaptive may be NULL.
+ * vd_op_freeu_filter / vd_op_freeu_backbone: the passes alone on [N][S*S][C] tensors, C % 4 == 0, 16-byte aligned, y != input, no
+ * engine; they allocate their table / scratch, wait for `stream` and free it.  s == 1 copies the input bits; the filter needs S >= 2
+ * (at one pixel the four bins coincide, and the published box is empty). */
+int vd_set_freeu(vd_engine* e, double b1, double b2, double s1, double s2, int adaptive);
+int vd_freeu(vd_engine* e, double* consts, int* adaptive);
+int vd_freeu_stages(vd_engine* e);
+int vd_op_freeu_filter(const float* x, int N, int S, int C, double s, float* y, void* stream);
+int vd_op_freeu_backbone(const float* h, int N, int S, int C, double b, int adaptive, float* y, void* stream);
+
 /* Guidance rescale and dynamic thresholding -- this project's extensions; the two standard remedies for the over-saturation of
  * cfg_scale > 1 under the static clamp of x_0 to [-1, 1].  "Item" is one batch element, and each statistic below runs over the elements of
  * the item's LATENT frames only (latent_mask == 1); observed and padding frames keep the bits of the step without the option.

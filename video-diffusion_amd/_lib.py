@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(_HERE, "libvdamd.so")
-SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "guidance.hip", "known.hip", "measure.hip", "dps.hip", "blur.hip", "linop.hip", "particles.hip", "guide.hip", "ode_nll.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip", "hallway.hip"]
+SOURCES = ["igemm.hip", "conv_wino.hip", "conv_wino_r64.hip", "conv_wino_z128.hip", "gemm_frag.hip", "gemm_split.hip", "split_pack.hip", "norm.hip", "backward.hip", "attn_spatial.hip", "attn_temporal.hip", "attn_temporal_long.hip", "misc.hip", "guidance.hip", "known.hip", "measure.hip", "dps.hip", "blur.hip", "linop.hip", "particles.hip", "freeu.hip", "guide.hip", "ode_nll.hip", "engine.hip", "lpips.hip", "metrics.hip", "i3d.hip", "conv_cl.hip", "hallway.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vd_amd.h")
 # every header a source may include: part of the library's identity and of each object's build stamp
 HEADERS = [os.path.join(_CSRC, "vd_common.h"), os.path.join(_CSRC, "wino_common.h"), os.path.join(_CSRC, "igemm_tile.h"), HEADER]
@@ -189,6 +189,11 @@ SIGNATURES = {
     "vd_set_cfg_scale": (_I, [_P, _F]),
     "vd_cfg_scale": (_F, [_P]),
     "vd_op_cfg_combine": (_I, [_P, _P, _F, _L, _P, _P]),
+    "vd_set_freeu": (_I, [_P, _D, _D, _D, _D, _I]),
+    "vd_freeu": (_I, [_P, _P, ctypes.POINTER(_I)]),
+    "vd_freeu_stages": (_I, [_P]),
+    "vd_op_freeu_filter": (_I, [_P, _I, _I, _I, _D, _P, _P]),
+    "vd_op_freeu_backbone": (_I, [_P, _I, _I, _I, _D, _I, _P, _P]),
     "vd_set_guidance_rescale": (_I, [_P, _F]),
     "vd_guidance_rescale": (_F, [_P]),
     "vd_set_dynamic_threshold": (_I, [_P, _F]),

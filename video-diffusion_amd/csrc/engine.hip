@@ -244,12 +244,25 @@ static int affine_act(const float* src0, const float* src1, int C0, int C, const
     return launch_affine_act(src0, src1, C0, C, A, B, N, HW, 1, y, st);
 }
 
+// FreeU for one forward (vd_set_freeu): the constants of the two stages, the cos / sin table of each stage's side, and the engine's
+// buffers the modified halves of a concat go to -- one pair for every block: a block's kernels have read them before the next block's
+// FreeU passes write them (one stream)
+struct FreeUReq {
+    double b[2], s[2];
+    int adaptive;
+    const double* trig[2];
+    float *yh, *ys;                  // h' and skip'
+    double* map;                     // the adaptive form's structure map, [N][S*S]
+    double *ph, *ps;                 // GroupNorm partial sums of h' and skip' ([N][gn_stats_split][C][2]): handed on as Tens::part
+};
+
 struct FwdIn {
     int B, T;
     const float *x, *obs_src, *obs, *lat, *km, *t_model;
     const int64_t* fidx;
     int obs_mode;
     float* eps;
+    const FreeUReq* fu = nullptr;    // null: the plain forward
 };
 
 // Window prefix cache (vd_window_begin, opt-in).  The input blocks before the first attention layer treat frames as
@@ -371,6 +384,46 @@ struct vd_engine {
     // guidance rescale (vd_set_guidance_rescale; 0 = off; acts with cfg_w != 1) and dynamic thresholding (vd_set_dynamic_threshold; 0 = off;
     // acts with clip_denoised, whose clamp it replaces): engine state like cfg_w, part of a window graph's key
     float guid_phi = 0.f, dyn_p = 0.f;
+    // FreeU (vd_set_freeu; all four constants 1 = off): in front of every output block of the two lowest-resolution decoder levels the
+    // backbone half of the concat is scaled by b and the skip half filtered by s (freeu.hip), stage 1 = level 0.  fu_blk: per such block
+    // the side and the channels of h and of the skip (build()); d_fu_trig: the cos / sin tables of the two sides, uploaded once by the
+    // first vd_set_freeu that switches it on; d_fu: h', skip' and the structure map of one block (freeu_workspace), whose addresses a
+    // captured window graph holds.  Engine state like cfg_w, part of a window graph's key.
+    double fu_b[2] = {1.0, 1.0}, fu_s[2] = {1.0, 1.0};
+    int fu_adaptive = 0;
+    struct FuBlk { int S, Ch, Cs; };
+    std::vector<FuBlk> fu_blk;
+    int fu_per_stage = 0;
+    double* d_fu_trig = nullptr;
+    float* d_fu = nullptr; size_t fu_cap = 0;
+    bool freeu_on() const { return fu_b[0] != 1.0 || fu_b[1] != 1.0 || fu_s[0] != 1.0 || fu_s[1] != 1.0; }
+    // floats of d_fu's five parts for N frames, each the largest any block of the two stages needs, rounded to 256 bytes: h', skip', the
+    // map, and the two statistics tables (doubles: two floats each)
+    struct FuSizes { size_t nh = 0, ns = 0, nm = 0, nph = 0, nps = 0; size_t total() const { return nh + ns + nm + nph + nps; } };
+    FuSizes freeu_floats(int N) const {
+        FuSizes z;
+        for (const FuBlk& k : fu_blk) {
+            const int hw = k.S * k.S;
+            z.nh = std::max(z.nh, (size_t)N * hw * k.Ch); z.ns = std::max(z.ns, (size_t)N * hw * k.Cs); z.nm = std::max(z.nm, 2 * (size_t)N * hw);
+            z.nph = std::max(z.nph, 4 * (size_t)N * gn_stats_split(N, hw, k.Ch) * k.Ch);
+            z.nps = std::max(z.nps, 4 * (size_t)N * gn_stats_split(N, hw, k.Cs) * k.Cs);
+        }
+        for (size_t* v : {&z.nh, &z.ns, &z.nm, &z.nph, &z.nps}) *v = (*v + 63) & ~(size_t)63;
+        return z;
+    }
+    int freeu_workspace(int B, int T) {              // never inside a capture
+        return grow(d_fu, fu_cap, freeu_floats(B * T).total(), true);
+    }
+    // the request of a (B, T) forward under the constants handed in (the engine's, or a window graph's key)
+    int freeu_request(int B, int T, const double* b, const double* s, int adaptive, FreeUReq* q) const {
+        const FuSizes z = freeu_floats(B * T);
+        VD_REQUIRE(d_fu && fu_cap >= z.total() && d_fu_trig, "FreeU: buffers not sized (vd_set_freeu, then a step entry or vd_window_begin)");
+        float* p = d_fu + z.nh + z.ns;
+        *q = FreeUReq{{b[0], b[1]}, {s[0], s[1]}, adaptive, {d_fu_trig, d_fu_trig + 2 * (size_t)fu_blk.front().S},
+                      d_fu, d_fu + z.nh, reinterpret_cast<double*>(p), reinterpret_cast<double*>(p + z.nm),
+                      reinterpret_cast<double*>(p + z.nm + z.nph)};
+        return 0;
+    }
     // known region (vd_set_known_region; null = off): every sampling step ends in the merge pass of known.hip on its sample.  The caller's
     // tensors; a window graph's key carries the two addresses.  known_noise / seed / offset: the draws of the eager entries.
     const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
@@ -441,6 +494,7 @@ struct vd_engine {
         int part_blur_k;                                          // ... with the blur kernel as the reward's operator: its size (0: the cell mean); the taps' address is fixed
         int part_lin_Mh, part_lin_Mw;                             // ... with the linear operator as the reward's operator: y's sides (0: not); the matrices' addresses are fixed
         const float* lin_y; int lin_Mh, lin_Mw;                   // linear measurement: the two projection passes a graph holds read y (null: none)
+        double fu_b[2], fu_s[2]; int fu_on, fu_adaptive;          // FreeU: the passes a graph's forwards hold and their constants (fu_on 0: none, all zero)
         bool operator==(const WinKey& o) const { return std::memcmp(this, &o, sizeof(WinKey)) == 0; }
     };
     struct WinGraph {
@@ -494,6 +548,8 @@ struct vd_engine {
         if (d_unipc) (void)hipFree(d_unipc);
         if (d_jump) (void)hipFree(d_jump);
         if (d_cfg_zero) (void)hipFree(d_cfg_zero);
+        if (d_fu_trig) (void)hipFree(d_fu_trig);
+        if (d_fu) (void)hipFree(d_fu);
         for (void* p : {(void*)d_part_logw, (void*)d_part_rprev, (void*)d_part_ess, (void*)d_part_anc, (void*)d_part_chosen,
                         (void*)d_part_counters, (void*)d_part_scratch, (void*)d_part_r, (void*)d_part_partials, (void*)d_part_x0,
                         (void*)d_part_sel, (void*)d_blur_taps, (void*)d_lin_mats, (void*)d_lin_r})
@@ -740,11 +796,13 @@ int vd_engine::build() {
         int r1 = add_res("middle_block.2", ch, ch, cfg.image_size / ds);
         middle = {Layer{1, r0}, Layer{2, a0}, Layer{1, r1}};
     }
+    fu_blk.clear(); fu_per_stage = nrb + 1;
     for (int lvl = nlev - 1; lvl >= 0; --lvl) {
         for (int i = 0; i <= nrb; ++i) {
             const std::string pre = "output_blocks." + std::to_string(output_blocks.size());
             std::vector<Layer> blk;
             const int skip = chans.back(); chans.pop_back();
+            if (lvl >= nlev - 2) fu_blk.push_back(FuBlk{cfg.image_size / ds, ch, skip});      // FreeU's two stages: the lowest two levels
             blk.push_back(Layer{1, add_res(pre + ".0", ch + skip, mc * mult[lvl], cfg.image_size / ds, skip)});
             ch = mc * mult[lvl];
             int li = 1;
@@ -1258,6 +1316,8 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
     drop_held();
     VD_REQUIRE(!pp || (!tape && !ar.dry && pp->store && n_before_attn > 0), "prefix plan: executor steps only");
     VD_REQUIRE(!sp || (!tape && sp->n > 0 && sp->n <= N && (ar.dry || sp->list)), "suffix plan: executor steps only, at least one frame");
+    const FreeUReq* fu = in.fu;
+    VD_REQUIRE(!fu || (!tape && !pp && !sp), "FreeU (vd_set_freeu): untaped forwards over all frames only");
     struct SelGuard { ~SelGuard() { g_sel_nfr = 0; } } sel_guard;      // (every return path leaves the selection hint cleared)
     const int Npre = pp ? pp->n : N;                                 // frames the blocks before the first attention layer run on
     float* x8 = ar.get<float>((size_t)Npre * S * S * STEM_KPAD);    // im2col of the network input
@@ -1435,6 +1495,36 @@ int vd_engine::forward(const FwdIn& in, hipStream_t st, Arena& ar, const PrefixP
             continue;
         }
         if (compact) { skip = gather_t(skip); VD_REQUIRE(ar.dry || skip.p, "suffix skip: gather"); }
+        if (fu && i < fu_blk.size() && !ar.dry) {
+            // FreeU: the block reads cat([h', skip']) -- both in the engine's buffers, never in place.  The producers' statistics tables do
+            // not describe the modified values: one statistics pass over each modified half, here, into the engine's buffers as well --
+            // left to gn_partials the tables would come out of the step arena, whose dry run sees the unmodified halves and sizes none
+            const int sg = (int)i / fu_per_stage;
+            auto stats = [&](Tens* t, double* part) -> int {
+                t->split = gn_stats_split(N, t->H * t->H, t->C);
+                t->part = part;
+                ProfScope ps(PC_GN_STATS, 0.0, 4.0 * N * t->H * t->H * t->C, st);
+                return launch_gn_stats(t->p, nullptr, t->C, t->C, N, t->H * t->H, part, t->split, st);
+            };
+            VD_REQUIRE(h.H == fu_blk[i].S && h.C == fu_blk[i].Ch && skip.H == h.H && skip.C == fu_blk[i].Cs, "FreeU: decoder block shape");
+            const double bytes = 8.0 * N * h.H * h.H;
+            if (fu->b[sg] != 1.0) {
+                {   // (a profiler record closes before the next one opens)
+                    ProfScope ps(PC_ELEMENTWISE, 1.0 * N * h.H * h.H * h.C, bytes * h.C * (fu->adaptive ? 1.5 : 1.0), st, "freeu_backbone");
+                    if ((rc = launch_freeu_backbone(h.p, N, h.H, h.C, fu->b[sg], fu->adaptive, fu->map, fu->yh, st))) return rc;
+                }
+                h = Tens{fu->yh, h.C, h.H};
+                if ((rc = stats(&h, fu->ph))) return rc;
+            }
+            if (fu->s[sg] != 1.0) {
+                {
+                    ProfScope ps(PC_ELEMENTWISE, 26.0 * N * h.H * h.H * skip.C, bytes * skip.C, st, "freeu_filter");
+                    if ((rc = launch_freeu_filter(skip.p, N, skip.H, skip.C, fu->s[sg], fu->trig[sg], fu->ys, st))) return rc;
+                }
+                skip = Tens{fu->ys, skip.C, skip.H};
+                if ((rc = stats(&skip, fu->ps))) return rc;
+            }
+        }
         if ((rc = run(output_blocks[i], h, &skip, &h))) return rc;
     }
     float *A, *Bf, *mrh = nullptr;
@@ -2071,6 +2161,11 @@ int vd_unet_forward(vd_engine* e, int B, int T, const float* x, const float* obs
     if ((rc = e->ensure_ws(B, T))) return rc;
     Arena ar = e->step_arena();
     FwdIn fi{B, T, x, obs_src, obs, lat, km, t_model, reinterpret_cast<const int64_t*>(fidx), obs_mode, eps};
+    FreeUReq fq;
+    if (e->freeu_on()) {                             // FreeU acts inside the network: the bare forward runs it too
+        if ((rc = e->freeu_workspace(B, T)) || (rc = e->freeu_request(B, T, e->fu_b, e->fu_s, e->fu_adaptive, &fq))) return rc;
+        fi.fu = &fq;
+    }
     return e->forward(fi, static_cast<hipStream_t>(stream), ar);
 }
 
@@ -2135,6 +2230,10 @@ struct StepReq {
     const SuffixPlan* sp = nullptr;
     // the guidance constants of this step: the engine's switches (eager entries) or a window graph's key
     float cfg_w = 1.f, guid_phi = 0.f, dyn_p = 0.f;
+    // FreeU (all four 1: off): the constants of the two decoder stages every forward of this step runs under, and the backbone form
+    double fu_b[2] = {1.0, 1.0}, fu_s[2] = {1.0, 1.0};
+    int fu_adaptive = 0;
+    bool freeu() const { return fu_b[0] != 1.0 || fu_b[1] != 1.0 || fu_s[0] != 1.0 || fu_s[1] != 1.0; }
     // known region (null: none): the merge pass behind the sampler pass, in place on `sample`; its draws are known_noise, or Philox at
     // (known_seed, known_offset + B*per/4), or at the pair `rng` points to
     const float *known_src = nullptr, *known_mask = nullptr, *known_noise = nullptr;
@@ -2253,6 +2352,12 @@ static int step_launches(vd_engine* e, const StepReq& r, hipStream_t st) {
     map_t(e, r.t, B, tm, st);
     Arena ar = e->step_arena();
     FwdIn fi{B, T, r.x, r.obs_src, r.obs, r.lat, r.km, tm, reinterpret_cast<const int64_t*>(r.fidx), r.obs_mode, eps};
+    FreeUReq fq;
+    if (r.freeu()) {                                 // both forwards of a cfg_scale step run it (fu = fi below)
+        VD_REQUIRE(!r.pp && !r.sp, "FreeU (vd_set_freeu) together with the window prefix cache or suffix skip is not served");
+        if ((rc = e->freeu_request(B, T, r.fu_b, r.fu_s, r.fu_adaptive, &fq))) return rc;
+        fi.fu = &fq;
+    }
     if ((rc = e->forward(fi, st, ar, r.pp, r.sp))) return rc;
     if (r.cfg_w != 1.f) {
         Arena au = e->step_arena();                  // the first forward's activations are dead: its output lives in the tail
@@ -2420,6 +2525,7 @@ static int ensure_particle_ws(vd_engine* e, int B, int T, bool x0) {
 static int step_workspace(vd_engine* e, int B, int T, hipStream_t st) {
     int rc = e->ensure_ws(B, T);
     if (!rc && e->cfg_w != 1.f) rc = cfg_zero_mask(e, B, T, st);
+    if (!rc && e->freeu_on()) rc = e->freeu_workspace(B, T);
     if (!rc && e->lin_y) rc = e->grow(e->d_lin_r, e->lin_r_cap, (size_t)B * T * 3 * e->lin_Mh * e->lin_Mw, true);
     return rc;
 }
@@ -2436,6 +2542,8 @@ static int run_step(vd_engine* e, StepReq r, bool want_sample, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if ((rc = step_workspace(e, r.B, r.T, st))) return rc;
     r.cfg_w = e->cfg_w; r.guid_phi = e->guid_phi; r.dyn_p = e->dyn_p;
+    for (int i = 0; i < 2; ++i) { r.fu_b[i] = e->fu_b[i]; r.fu_s[i] = e->fu_s[i]; }
+    r.fu_adaptive = e->fu_adaptive;
     if (want_sample && e->known_src) {
         VD_REQUIRE(!sampler_walks_up(r.sampler), std::string(sampler_name(r.sampler)) + " together with a known region (vd_set_known_region) is not served: the merge noises to t - 1");
         r.known_src = e->known_src; r.known_mask = e->known_mask; r.known_noise = e->known_noise;
@@ -2474,6 +2582,7 @@ int vd_vb_terms(vd_engine* e, int B, int T, const float* x_start, const float* x
                 const long long* t, int clip, const float* latent_mask, float* vb, float* xstart_mse, float* mse,
                 float* pred_xstart, void* stream) {
     VD_REQUIRE(e && e->d_tab, "vd_set_schedule not called");
+    VD_REQUIRE(!e->freeu_on(), "vb_terms (the NLL path) together with FreeU (vd_set_freeu) is not served: a likelihood is the trained model's");
     VD_REQUIRE(B > 0 && T > 0 && x_start && x_t && eps && t && vb, "arguments");
     VD_REQUIRE(mse == nullptr || noise != nullptr, "mse needs the noise x_t was drawn with");
     const long per = (long)T * 3 * e->cfg.image_size * e->cfg.image_size;
@@ -2530,6 +2639,7 @@ int vd_score_windows(vd_engine* e, int B, int T, const float* x_start, const flo
     int rc = check_sampler(e, B, T, 0, 0, kObsModes);
     if (rc) return rc;
     VD_REQUIRE(x_start && obs && lat && km && fidx && t && mse_out && (noise || item_offset), "null tensor");
+    VD_REQUIRE(!e->freeu_on(), "score_windows together with FreeU (vd_set_freeu) is not served: the search scores the model as trained");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = B * T;
     const size_t per = (size_t)T * 3 * e->cfg.image_size * e->cfg.image_size;
@@ -2642,6 +2752,11 @@ static int warmup_forward(vd_engine* e, const vd_engine::WinKey& k, const float*
     int rc = renoise_observed(e, k, st);
     if (rc) return rc;
     FwdIn fi{k.B, k.T, k.x, net_obs_src, k.obs, k.lat, k.km, tm, reinterpret_cast<const int64_t*>(k.fidx), net_mode, e->step_eps(k.B)};
+    FreeUReq fq;
+    if (k.fu_on) {                                   // the graph's own passes, once outside the capture
+        if ((rc = e->freeu_request(k.B, k.T, k.fu_b, k.fu_s, k.fu_adaptive, &fq))) return rc;
+        fi.fu = &fq;
+    }
     if ((rc = e->forward(fi, st, ar))) return rc;
     VD_HIP(hipStreamSynchronize(st));
     return 0;
@@ -2697,6 +2812,7 @@ static int capture_window(vd_engine* e, const vd_engine::WinKey& k, const std::v
     if (pre_on) r.pp = &plan;
     if (suf_on) r.sp = &splan;
     r.cfg_w = k.cfg_w; r.guid_phi = k.guid_phi; r.dyn_p = k.dyn_p;
+    if (k.fu_on) { for (int i = 0; i < 2; ++i) { r.fu_b[i] = k.fu_b[i]; r.fu_s[i] = k.fu_s[i]; } r.fu_adaptive = k.fu_adaptive; }
     r.known_src = k.known_src; r.known_mask = k.known_mask;      // the merge draws from the window's own Philox pair (r.rng)
     r.meas_y = k.meas_y; r.meas_scale = k.meas_scale; r.meas_gray = k.meas_gray;
     r.lin_y = k.lin_y; r.lin_Mh = k.lin_Mh; r.lin_Mw = k.lin_Mw;
@@ -2752,6 +2868,10 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     if ((rc = require_history_rows(e, sampler, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ")"))) return rc;
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
+    if (e->freeu_on()) {
+        VD_REQUIRE(!e->prefix_cache_on, "FreeU (vd_set_freeu) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
+        VD_REQUIRE(!e->suffix_skip_on, "FreeU (vd_set_freeu) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
+    }
     if (e->part_K > 1) {
         VD_REQUIRE(e->part_y, "particle steering (vd_set_particles) with the caller's rewards inside a window graph is not served: a callback between two steps cannot be captured (the built-in reward can)");
         if ((rc = refuse_with_particles(e, sampler, B, eta))) return rc;
@@ -2796,6 +2916,10 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     }
     if (e->lin_y) { key.lin_y = e->lin_y; key.lin_Mh = e->lin_Mh; key.lin_Mw = e->lin_Mw; }
     if (e->meas_y) { key.meas_y = e->meas_y; key.meas_scale = e->meas_scale; key.meas_gray = e->meas_gray; }
+    if (e->freeu_on()) {
+        key.fu_on = 1; key.fu_adaptive = e->fu_adaptive;
+        for (int i = 0; i < 2; ++i) { key.fu_b[i] = e->fu_b[i]; key.fu_s[i] = e->fu_s[i]; }
+    }
     e->win_cur = -1;
     e->win_lost = false;
     ++e->win_gen;
@@ -2841,6 +2965,56 @@ int vd_set_cfg_scale(vd_engine* e, float w) {
 }
 
 float vd_cfg_scale(vd_engine* e) { return e ? e->cfg_w : 1.f; }
+
+// FreeU, engine state like cfg_scale: all four constants 1 = off.  A captured window graph carries the constants in its key.  The first
+// call that switches it on uploads the cos / sin tables of the two stages' sides (double, host-computed): never inside a capture.
+int vd_set_freeu(vd_engine* e, double b1, double b2, double s1, double s2, int adaptive) {
+    VD_REQUIRE(e, "null engine");
+    const double v[4] = {b1, b2, s1, s2};
+    for (double x : v) VD_REQUIRE(x > 0.0 && x <= 1.7976931348623157e308, "freeu: b1, b2, s1 and s2 must be finite and > 0");
+    VD_REQUIRE(!e->fu_blk.empty(), "freeu: engine not built");
+    const bool on = b1 != 1.0 || b2 != 1.0 || s1 != 1.0 || s2 != 1.0;
+    if (on && !e->d_fu_trig) {
+        const int S0 = e->fu_blk.front().S, S1 = e->fu_blk.back().S;
+        std::vector<double> tab(2 * (size_t)(S0 + S1));
+        freeu_trig_table(S0, tab.data());
+        freeu_trig_table(S1, tab.data() + 2 * S0);
+        VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_fu_trig), tab.size() * sizeof(double)));
+        VD_HIP(hipMemcpy(e->d_fu_trig, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    e->fu_b[0] = b1; e->fu_b[1] = b2; e->fu_s[0] = s1; e->fu_s[1] = s2;
+    e->fu_adaptive = on && adaptive != 0;
+    return 0;
+}
+
+int vd_freeu(vd_engine* e, double* consts, int* adaptive) {
+    VD_REQUIRE(e, "null engine");
+    if (consts) { consts[0] = e->fu_b[0]; consts[1] = e->fu_b[1]; consts[2] = e->fu_s[0]; consts[3] = e->fu_s[1]; }
+    if (adaptive) *adaptive = e->fu_adaptive;
+    return e->freeu_on() ? 1 : 0;
+}
+
+int vd_freeu_stages(vd_engine* e) { return e && e->fu_per_stage ? (int)e->fu_blk.size() / e->fu_per_stage : 0; }
+
+int vd_op_freeu_filter(const float* x, int N, int S, int C, double s, float* y, void* stream) {
+    VD_REQUIRE(S >= 2 && S <= 4096, "vd_op_freeu_filter: S >= 2 (at one pixel the four bins coincide and the published box is empty), at most 4096");
+    OpScratch ws(stream);
+    double* trig = nullptr;
+    int rc = ws.get(&trig, 2 * (size_t)S);
+    if (rc) return rc;
+    std::vector<double> tab(2 * (size_t)S);
+    freeu_trig_table(S, tab.data());
+    VD_HIP(hipMemcpy(trig, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    return launch_freeu_filter(x, N, S, C, s, trig, y, ws.st);
+}
+
+int vd_op_freeu_backbone(const float* h, int N, int S, int C, double b, int adaptive, float* y, void* stream) {
+    VD_REQUIRE(N > 0 && S > 0 && S <= 4096, "vd_op_freeu_backbone: shape");
+    OpScratch ws(stream);
+    double* map = nullptr;
+    if (adaptive) { int rc = ws.get(&map, (size_t)N * S * S); if (rc) return rc; }
+    return launch_freeu_backbone(h, N, S, C, b, adaptive, map, y, ws.st);
+}
 
 int vd_op_cfg_combine(const float* out_c, const float* out_u, float w, long long n, float* out, void* stream) {
     return launch_cfg_combine(out_c, out_u, w, n, out, static_cast<hipStream_t>(stream));
@@ -3403,6 +3577,7 @@ int vd_load_weight_bwd(vd_engine* e, const char* name, const float* host, long l
 // Their shared refusals under the entry's name.  plain_state: also the engine state that would act on a plain step, and the item limit
 // (the guided step leaves those switches to its Python caller and has its own limit); eps_note: what the vjp entries add on a START_X model.
 static int check_diff(vd_engine* e, int B, int T, const std::string& what, bool plain_state = true, const char* eps_note = "") {
+    VD_REQUIRE(!e->freeu_on(), what + " together with FreeU (vd_set_freeu) is not served: the taped forward does not run its passes");
     VD_REQUIRE(T <= kMaxGuidedWindowFrames, what + ": windows of at most " + std::to_string(kMaxGuidedWindowFrames) +
                                             " frames (the temporal attention and GroupNorm backward kernels), got " + std::to_string(T));
     VD_REQUIRE(e->mean_type == 0, what + ": epsilon-prediction models only" + eps_note);

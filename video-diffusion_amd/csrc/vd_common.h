@@ -585,6 +585,16 @@ struct QJumpArgs {
 };
 int launch_q_jump(const QJumpArgs& a, hipStream_t s);
 
+// FreeU (freeu.hip; this project's extension, Si, Huang, Jiang, Liu 2024): the two operators on the halves of a decoder concat.
+// Tensors are channels-last [N][S*S][C], C % 4 == 0, 16-byte aligned; never in place.  Sums in fp64, fixed order, no atomics.
+// freeu_trig_table: cos(2 pi k / S) | sin(2 pi k / S), k < S, into 2 S host doubles; the launchers read its device copy (`trig`).
+// launch_freeu_filter: per (frame, channel) plane y = Re ifft2(M . fft2(x)), M = s on the bins {0, S-1}^2 and 1 elsewhere (closed form,
+// a rank-7 update); s == 1 copies.  launch_freeu_backbone: channels c < C/2 times (float)b (plain), or times (b - 1) g + 1 with g the
+// per-frame min-max normalised channel mean (adaptive; `map`: N * S * S doubles of scratch; hi == lo: g = 0); the others copied.
+void freeu_trig_table(int S, double* out);
+int launch_freeu_filter(const float* x, int N, int S, int C, double s, const double* trig, float* y, hipStream_t st);
+int launch_freeu_backbone(const float* h, int N, int S, int C, double b, int adaptive, double* map, float* y, hipStream_t st);
+
 // Zero-shot restoration (measure.hip; this project's extension, DDNM: Wang, Yu, Zhang 2022): the projection of a step's x_0 prediction onto
 // a measurement, x_0 <- x_0 + A^+(y - A x_0), for the "cell mean" operators.  Tensors are [B][T][3][H][W], `lat` the [B*T] latent mask.
 // A cell is scale x scale pixels of one channel plane (gray: of the three planes of its frame); A is the mean over every cell,

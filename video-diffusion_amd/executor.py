@@ -121,6 +121,9 @@ class WindowExecutor:
         Guidance rescale and dynamic thresholding are not parameters: a begin() inside `diffusion.guidance_scope(...)` captures (or finds)
         the graph of the scope's values -- they are part of the signature like the weight -- and run() may be called outside the scope.
         The engine refuses either of them together with prefix_cache or suffix_skip.
+        FreeU is not a parameter either: a begin() inside `diffusion.freeu_scope(...)` captures (or finds) the graph whose forwards hold
+        the scope's passes -- the four constants and the form are part of the signature, and going back to off finds the plain graph
+        again.  Refused together with prefix_cache or suffix_skip.
         known_src, known_mask (this project's extension; gaussian_diffusion.py: known_region_scope): pixel-mask inpainting -- both are
         copied into buffers of this object, the captured step ends in the merge pass, and the merge's noise comes from the window's own
         Philox stream (the step's range at + B*per/4; every sampler's step then advances the counter by B*per).  Without them, a begin()
@@ -217,6 +220,8 @@ class WindowExecutor:
                 raise NotImplementedError(f"{which} together with cfg_rescale != 0")
             if float(L.vd_dynamic_threshold(h)) != 0.0 and clip_denoised:
                 raise NotImplementedError(f"{which} together with dynamic_threshold")
+            if L.vd_freeu(h, None, None):                             # an enclosing freeu_scope
+                raise NotImplementedError(f"{which} together with FreeU (freeu_scope)")
         mode = model_kwargs.get("observed_frames", "x_0")
         if mode not in _OBS_MODES:
             raise NotImplementedError(f"observed_frames={mode!r}: the window executor handles 'x_0', 'x_t' and 'x_t_minus_1'")

@@ -36,6 +36,9 @@ Separable linear measurements (this project's extension too): `GaussianDiffusion
 `linear_dps_scope` DPS and `steering_scope(..., operator=)` the built-in reward for any measurement y = A_h x A_w^T of two dense matrices
 per channel plane -- bicubic super-resolution (`resize_matrix`), a separable blur with any padding and stride (`blur_matrix`), the cell
 mean (`box_matrix`) -- with the truncated pseudo-inverse of `separable_pinv` as the back-projection (csrc/linop.hip).
+FreeU (this project's extension too) is the one option that acts inside the network: within `GaussianDiffusion.freeu_scope` every
+untaped forward scales the backbone half and damps the lowest frequencies of the skip half of the decoder's concats at its two
+lowest-resolution levels (csrc/freeu.hip).
 Training losses are out of scope.
 """
 import contextlib
@@ -216,6 +219,39 @@ def _guidance_scope(model, phi, p):
     finally:
         _lib.check(L.vd_set_guidance_rescale(model._handle, before[0]))
         _lib.check(L.vd_set_dynamic_threshold(model._handle, before[1]))
+
+
+def check_freeu(b1, b2, s1, s2):
+    """The range check of FreeU's four constants (no engine): each finite and > 0; returns them as floats."""
+    vals = []
+    for name, v in (("b1", b1), ("b2", b2), ("s1", s1), ("s2", s2)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"freeu {name}={v!r}: a number, finite and > 0") from None
+        if not (math.isfinite(f) and f > 0.0):
+            raise ValueError(f"freeu {name}={v!r}: the constant must be finite and > 0")
+        vals.append(f)
+    return tuple(vals)
+
+
+def freeu_state(model):
+    """The engine's FreeU setting: ((b1, b2, s1, s2), adaptive), all four 1.0 while it is off."""
+    c, a = (ctypes.c_double * 4)(), ctypes.c_int(0)
+    _lib.lib().vd_freeu(getattr(model, "model", model)._handle, c, ctypes.byref(a))
+    return tuple(c), bool(a.value)
+
+
+@contextlib.contextmanager
+def _freeu_scope(model, consts, adaptive):
+    """The engine's FreeU constants for the calls inside; behind them, whatever they raise, the setting found before (as _cfg_scope)."""
+    L = _lib.lib()
+    before, was = freeu_state(model)
+    _lib.check(L.vd_set_freeu(model._handle, *consts, 1 if adaptive else 0))
+    try:
+        yield
+    finally:
+        _lib.check(L.vd_set_freeu(model._handle, *before, 1 if was else 0))
 
 
 def check_known_region(known_src, known_mask):
@@ -927,6 +963,25 @@ class GaussianDiffusion:
         inside dps_scope refuses either option by name."""
         phi, p = _check_guidance(cfg_rescale, dynamic_threshold)
         return _guidance_scope(self._bind(model), phi, p)
+
+    def freeu_scope(self, model, b1=1.0, b2=1.0, s1=1.0, s2=1.0, adaptive=False):
+        """This project's extension (FreeU; Si, Huang, Jiang, Liu, CVPR 2024): `with diffusion.freeu_scope(model, b1=1.4, b2=1.2, s1=0.6,
+        s2=0.8):` -- the one option that acts INSIDE the UNet forward.  At the two lowest-resolution decoder levels (stage 1: the lowest,
+        constants b1 and s1; stage 2: the next, b2 and s2) every output block reads the backbone half of its concat with its first
+        C_h / 2 channels scaled by b, and the skip half with its lowest spatial frequencies -- the four FFT bins (u, v) in {0, S-1}^2, the
+        published code's box at threshold 1 -- scaled by s (include/vd_amd.h: vd_set_freeu states the arithmetic).  adaptive=True is
+        the paper's structure-aware form: the factor is (b - 1) g + 1 with g the frame's min-max normalised channel mean; a frame whose
+        mean is constant gets g = 0, where the published code divides 0 by 0.  Every model that can be created has both stages (four to
+        six levels, by image size).  All four constants 1 (the defaults) is the forward as it was, to the bit, with no added launch.
+        Every step entry point, loop, p_mean_variance, model(...) and WindowExecutor.begin called inside runs under it -- both forwards
+        of a cfg_scale step -- and it composes with cfg_scale, guidance_scope, known_region_scope, the measurement scopes and
+        steering_scope, none of which touches the forward.  The setting found before is back when the block ends, whatever it raised,
+        and scopes nest.  Refused by name inside: use_gradient_method, the steps of dps_scope, deblur_scope, linear_dps_scope and
+        loss_guidance_scope, eps_vjp and ode_nll_loop (their taped forward does not run the passes), score_windows and the NLL loop (a
+        likelihood is the trained model's), and a WindowExecutor with prefix_cache or suffix_skip.  A constant that is not finite and
+        > 0 raises ValueError.  No claim about sample quality is made."""
+        consts = check_freeu(b1, b2, s1, s2)
+        return _freeu_scope(self._bind(model), consts, bool(adaptive))
 
     def known_region_scope(self, model, known_src, known_mask, known_noise=None):
         """This project's extension (RePaint, Lugmayr et al. 2022): `with diffusion.known_region_scope(model, known_src, known_mask):`
@@ -1652,6 +1707,8 @@ class GaussianDiffusion:
         calc_bpd_loop_subsampled when the noise x_t was drawn with is passed)."""
         model = self._bind(model)          # (predict_xstart=True: the engine takes the network output handed to vd_vb_terms as the x_0 prediction)
         dev = model.device
+        if _lib.lib().vd_freeu(model._handle, None, None):
+            raise _lib.VdError("the NLL loop (calc_bpd_loop) together with FreeU (freeu_scope) is not served: a likelihood is the trained model's")
         xs, xt = _f32(x_start, dev), _f32(x_t, dev)
         B, T = xs.shape[:2]
         out = self.p_mean_variance(model, xt, t, clip_denoised=clip_denoised, model_kwargs=model_kwargs)

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, inference_util
-from .gaussian_diffusion import (SAMPLERS, _check_guidance, _sampler_step, check_blur_kernel, check_blur_measurement,
+from .gaussian_diffusion import (SAMPLERS, _check_guidance, _sampler_step, check_blur_kernel, check_blur_measurement, check_freeu,
                                  check_linear_measurement, check_loss_guidance, check_measurement, check_separable_operator, check_zeta,
                                  gaussian_kernel, resize_matrix, separable_pinv)
 from .script_util import (args_to_dict, create_video_model_and_diffusion, str2bool,
@@ -52,7 +52,7 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
                 cfg_rescale=0.0, dynamic_threshold=None, known_mask=None, known_video=None, jump_length=1, n_resample=1,
                 measurement=None, sr_scale=1, gray=False, dps_zeta=None, loss_fn=None, cotangent_fn=None, loss_scale=None,
                 loss_normalize=False, particles=1, reward_fn=None, reward_scale=1.0, ess_threshold=0.5, particle_measurement=None,
-                sigma_y=None, blur_kernel=None, operator=None, operator_rtol=1e-3):
+                sigma_y=None, blur_kernel=None, operator=None, operator_rtol=1e-3, freeu=None, freeu_adaptive=False):
     """video_sample.py:50-190.  Returns (samples ndarray (B,T,C,H,W), all_timestep_samples): the second is the
     (B, num_timesteps, T, C, H, W) record of every step's output when `save_all_timesteps` (the reference's
     `args.save_all_timesteps`, :84-91,168-186; eager executor only -- the graph keeps a window on the device), else
@@ -154,7 +154,15 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
     defaults.  It takes any of the three paths, each with its own rules above: neither option (the exact projection, with the truncated
     pseudo-inverses separable_pinv(A, operator_rtol); both executors, every sampler a measurement is served with), dps_zeta=
     (linear_dps_scope), or particles=K, sigma_y= (the built-in reward on the operator; `measurement` is then read as
-    particle_measurement when that is not given; both executors)."""
+    particle_measurement when that is not given; both executors).
+
+    freeu, freeu_adaptive (this project's extension: FreeU; both executors, every sampler): freeu=(b1, b2, s1, s2) runs the whole of this
+    function's work inside `diffusion.freeu_scope(model, b1, b2, s1, s2, adaptive=freeu_adaptive)` -- in every forward the backbone half
+    of the concat at the two lowest-resolution decoder levels is scaled and the lowest frequencies of the skip half are damped
+    (gaussian_diffusion.py: freeu_scope).  Under a sampler that draws no noise the two executors agree to the bit.  Composes with
+    cfg_scale, cfg_rescale, dynamic_threshold, known_mask, a measurement and particles; refused by name before the engine is touched
+    with use_gradient_method, dps_zeta, loss_fn / cotangent_fn, prefix_cache and suffix_skip.  None (default): no scope is entered and
+    the engine is not touched."""
     lin = None
     if operator is not None:
         if not isinstance(operator, (tuple, list)) or len(operator) != 2:     # before anything touches the engine
@@ -230,6 +238,23 @@ def infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size
         from .respace import repaint_schedule
         repaint_schedule(diffusion.num_timesteps - 1, jump_length, n_resample)     # the range checks, before anything touches the engine
         known_mask_v, known_video_v = video_known_region(batch, known_mask, known_video)
+    if freeu is not None:
+        if not isinstance(freeu, (tuple, list)) or len(freeu) != 4:          # before anything touches the engine
+            raise ValueError("freeu is four numbers (b1, b2, s1, s2)")
+        consts = check_freeu(*freeu)
+        for name, on in (("use_gradient_method", use_gradient_method), ("dps_zeta", dps_zeta is not None), ("loss_fn / cotangent_fn", loss_guided),
+                         ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
+            if on:
+                raise NotImplementedError(f"{name} together with freeu")
+        with diffusion.freeu_scope(model, *consts, adaptive=freeu_adaptive):
+            return infer_video(mode, model, diffusion, batch, max_frames, obs_length, step_size, optimal_schedule_path,
+                               observed_frames=observed_frames, sampler=sampler, eta=eta, executor=executor, adaptive_distance=adaptive_distance,
+                               save_all_timesteps=save_all_timesteps, cfg_scale=cfg_scale, cfg_rescale=cfg_rescale,
+                               dynamic_threshold=dynamic_threshold, known_mask=known_mask, known_video=known_video, jump_length=jump_length,
+                               n_resample=n_resample, measurement=measurement, sr_scale=sr_scale, gray=gray, particles=particles,
+                               reward_fn=reward_fn, reward_scale=reward_scale, ess_threshold=ess_threshold,
+                               particle_measurement=particle_measurement, sigma_y=sigma_y, blur_kernel=blur_kernel, operator=operator,
+                               operator_rtol=operator_rtol)
     if float(cfg_rescale) != 0.0 or dynamic_threshold is not None:
         _check_guidance(cfg_rescale, dynamic_threshold)                     # before anything touches the engine
         for name, on in (("use_gradient_method", use_gradient_method), ("prefix_cache", prefix_cache), ("suffix_skip", suffix_skip)):
@@ -702,6 +727,12 @@ def build_parser():
     ap.add_argument("--dynamic_threshold", type=float, default=None,
                     help="dynamic thresholding: the percentile P in (0, 1] of |x_0| over each item's latent frames that replaces the 1 of the "
                          "clamp of x_0 (never below 1); off by default; named in the run directory when set")
+    ap.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("B1", "B2", "S1", "S2"),
+                    help="FreeU: in every forward the backbone half of the decoder's concat at the two lowest-resolution levels is scaled by "
+                         "B1 / B2 and the lowest frequencies of the skip half by S1 / S2 (e.g. 1.4 1.2 0.6 0.8); all four finite and > 0; off "
+                         "by default; named in the run directory when set")
+    ap.add_argument("--freeu_adaptive", action="store_true",
+                    help="with --freeu: the structure-aware backbone factor (b - 1) g + 1, g the frame's min-max normalised channel mean")
     ap.add_argument("--known_mask", default=None, metavar="MASK.npy",
                     help="pixel-mask inpainting: a (T, H, W) or (H, W) array, nonzero = known, one mask for all videos; the known pixels of every "
                          "generated frame are kept from the source (--known_videos, default: the test videos themselves)")
@@ -959,6 +990,16 @@ def _loss_guidance_options(args):
                 loss_normalize=bool(getattr(args, "loss_guidance_normalize", False)))
 
 
+def _freeu_options(args):
+    """--freeu B1 B2 S1 S2 [--freeu_adaptive] -> infer_video's keywords ({} without the option)."""
+    fu = getattr(args, "freeu", None)
+    if fu is None:
+        if getattr(args, "freeu_adaptive", False):
+            raise ValueError("--freeu_adaptive needs --freeu B1 B2 S1 S2")
+        return {}
+    return dict(freeu=check_freeu(*fu), freeu_adaptive=bool(getattr(args, "freeu_adaptive", False)))
+
+
 def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
     return infer_video(args.inference_mode, model, diffusion, batch, args.max_frames, args.obs_length, args.step_size,
                        optimal_schedule_path, use_gradient_method=getattr(args, "use_gradient_method", False),
@@ -969,14 +1010,14 @@ def _default_infer(args, model, diffusion, batch, optimal_schedule_path):
                        save_all_timesteps=getattr(args, "save_all_timesteps", False), cfg_scale=getattr(args, "cfg_scale", 1.0),
                        cfg_rescale=getattr(args, "cfg_rescale", 0.0), dynamic_threshold=getattr(args, "dynamic_threshold", None),
                        **_known_options(args, batch), **_measurement_options(args, batch), **_loss_guidance_options(args),
-                       **_particle_options(args))
+                       **_particle_options(args), **_freeu_options(args))
 
 
 def run_postfix(args):
     """What the options add to the run directory's name: a sampler other than the default, then a cfg_scale other than 1
     ('_cfg2', '_cfg1.5', '_cfg-0.5'), a cfg_rescale other than 0 ('_resc0.7'), a dynamic_threshold ('_dt0.995'), a --known_mask and a
     --measurement ('_sr4', '_gray', '_sr4gray', with --dps_zeta '_sr4_dps0.5'; under --blur_kernel / --blur_sigma '_blur9' in their place, under --operator_h / --sr_kernel bicubic '_lin8x8'), a --loss_guidance ('_lg0.5': its scale) and --particles
-    above 1 ('_smc8') -- samples of different samplers or guidance settings never share a directory, and a run
+    above 1 ('_smc8') and a --freeu ('_freeu1.4-1.2-0.6-0.8', with --freeu_adaptive '_freeu1.4-1.2-0.6-0.8a') -- samples of different samplers or guidance settings never share a directory, and a run
     without the options keeps its name."""
     sampler = getattr(args, "sampler", "p_sample")
     w = float(getattr(args, "cfg_scale", 1.0))
@@ -997,8 +1038,10 @@ def run_postfix(args):
     if getattr(args, "loss_guidance", None):      # '_lg0.5' (the function is not named: a run directory is one function's)
         lg = "_lg" + ("None" if getattr(args, "loss_guidance_scale", None) is None else f"{float(args.loss_guidance_scale):g}")
     smc = f"_smc{int(args.particles)}" if int(getattr(args, "particles", 1) or 1) > 1 else ""      # '_smc8': the particles of a video
+    fu = getattr(args, "freeu", None)
+    freeu = "" if fu is None else "_freeu" + "-".join(f"{float(v):g}" for v in fu) + ("a" if getattr(args, "freeu_adaptive", False) else "")
     return ("" if sampler == "p_sample" else f"_{sampler}") + ("" if w == 1.0 else f"_cfg{w:g}") + \
-        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas + lg + smc
+        ("" if phi == 0.0 else f"_resc{phi:g}") + ("" if p is None else f"_dt{float(p):g}") + known + meas + lg + smc + freeu
 
 
 def run(args, create=None, device=None, infer=None):
