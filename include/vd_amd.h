@@ -383,6 +383,11 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream);
  * "window graphs invalidated" when the armed window's graph was dropped (workspace growth, vd_set_schedule). */
 unsigned long long vd_window_generation(vd_engine* e);
 int vd_window_graphs(vd_engine* e);            /* captured graphs held by the engine */
+/* What the armed window carries from step to step, copied out on `stream` (device to device, B*T*3*H*W floats each; every pointer
+ * optional): `hist` -- the previous step's x_0 prediction of samplers 3 and 4, UniPC's D_{t+1} -- and UniPC's corrected state
+ * x^c_{t+1} (`ubase`) and D_{t+2} (`ud2`).  Meaningful behind the window's first step; B and T are the armed window's; a sampler
+ * without history, and `ubase` / `ud2` for any sampler but 5, are refused by name.  Reads only: nothing of the window changes. */
+int vd_window_history(vd_engine* e, int B, int T, float* hist, float* ubase, float* ud2, void* stream);
 
 /* Window prefix cache (opt-in, off by default; a host-side choice like the executor itself).  The reference recomputes the
  * whole UNet for every frame at every step (unet.py:838-846).  Before the first attention layer the network treats frames as

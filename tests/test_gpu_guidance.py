@@ -11,6 +11,7 @@ import torch
 import video_diffusion_amd as vda
 from guidance_restated import rescale_factor_fp64, threshold_fp64
 from helpers import synth_sd
+from step_compose import _combine, _compose, _kw, _rescale, _threshold
 from video_diffusion_amd import _lib
 from video_diffusion_amd.executor import WindowExecutor
 
@@ -47,21 +48,6 @@ def _dev(a):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rescale op
-def _combine(c, u, w):
-    out = torch.empty_like(c)
-    _lib.check(_lib.lib().vd_op_cfg_combine(_lib.ptr(c), _lib.ptr(u), float(w), c.numel(), _lib.ptr(out), _lib.current_stream()))
-    return out
-
-
-def _rescale(c, u, w, lat, phi, out=None):
-    b, t, fe = c.shape
-    out = torch.empty_like(c) if out is None else out
-    f = torch.empty(b, device="cuda")
-    _lib.check(_lib.lib().vd_op_cfg_rescale(_lib.ptr(c), _lib.ptr(u), float(w), _lib.ptr(lat), b, t, fe, float(phi), _lib.ptr(out), _lib.ptr(f),
-                                            _lib.current_stream()))
-    return out, f
-
-
 def _rescale_inputs(shape, data):
     g = np.random.default_rng(sum(shape))
     if data == "normal":
@@ -115,14 +101,6 @@ def test_rescale_op_against_float64(shape, kind, data):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the threshold op
-def _threshold(x, lat, p, out=None):
-    b, t, fe = x.shape
-    out = torch.empty_like(x) if out is None else out
-    s = torch.empty(b, device="cuda")
-    _lib.check(_lib.lib().vd_op_dynamic_threshold(_lib.ptr(x), _lib.ptr(lat), b, t, fe, float(p), _lib.ptr(out), _lib.ptr(s), _lib.current_stream()))
-    return out, s
-
-
 def _threshold_input(shape, lat, data):
     g = np.random.default_rng(sum(shape) + 1)
     if data in ("gauss3", "nan_latent", "nan_observed"):
@@ -225,13 +203,6 @@ def _window(seed):
                 xtm1=(0.5 * x0 + 0.1 * torch.randn(B, T, 3, S, S, generator=g) * obs).cuda())
 
 
-def _kw(c, zero_obs=False):
-    d = {k: c[k] for k in ["x0", "obs_mask", "latent_mask", "kinda_marg_mask", "frame_indices"]}
-    if zero_obs:
-        d["obs_mask"] = torch.zeros_like(d["obs_mask"])
-    return dict(d, x_t_minus_1=c["xtm1"], observed_frames="x_0")
-
-
 def _t(v):
     return torch.tensor([v] * B, device="cuda")
 
@@ -243,43 +214,6 @@ def _noise(seed):
 def _state(model):
     L = _lib.lib()
     return float(L.vd_cfg_scale(model._handle)), float(L.vd_guidance_rescale(model._handle)), float(L.vd_dynamic_threshold(model._handle))
-
-
-def _compose(model, diff, c, tv, w, phi, p, mode, eta, nz, start_x, prev=None):
-    """The step from existing entries: p_mean_variance(clip off, cfg_scale) for the network outputs, the two op entries on them, then the
-    *_from_xstart pass with its clamp off behind the threshold (on, as in the plain step, without it).  Called outside any scope.
-    -> (sample, pred_xstart, per-item thresholds or None)."""
-    L = _lib.lib()
-    kw, t = _kw(c), _t(tv)
-    x, per = c["x"], c["x"][0].numel()
-    lat = c["latent_mask"].reshape(B, T).contiguous()
-    out = diff.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=kw, cfg_scale=w)["eps"]
-    if phi != 0.0 and w != 1.0:
-        out_c = diff.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=kw)["eps"]
-        out_u = diff.p_mean_variance(model, x, t, clip_denoised=False, model_kwargs=_kw(c, zero_obs=True))["eps"]
-        assert torch.equal(_bits(_combine(out_c, out_u, w)), _bits(out))
-        out = _rescale(out_c.view(B, T, FE), out_u.view(B, T, FE), w, lat, phi)[0].view_as(x)
-    if start_x:
-        x0 = out
-    else:                                                                        # x_0 as the posterior pass forms it from eps
-        x0, dummy = torch.empty_like(x), torch.empty_like(x)
-        _lib.check(L.vd_posterior_update(model._handle, 0, B, per, _lib.ptr(x), _lib.ptr(out), _lib.ptr(t), 0, 0.0, _lib.ptr(nz), 0, 0,
-                                         _lib.ptr(dummy), _lib.ptr(x0), _lib.current_stream()))
-    s, clip = None, 1
-    if p:
-        x0, s = _threshold(x0.view(B, T, FE), lat, p)
-        x0, clip = x0.view_as(x), 0
-    sample, xstart = torch.empty_like(x), torch.empty_like(x)
-    if mode == 2:
-        _lib.check(L.vd_ddim_reverse_from_xstart(model._handle, B, per, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(t), clip, _lib.ptr(sample),
-                                                 _lib.ptr(xstart), _lib.current_stream()))
-    elif mode == 3:
-        _lib.check(L.vd_dpmpp_2m_from_xstart(model._handle, B, per, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(prev), _lib.ptr(t), clip,
-                                             _lib.ptr(sample), _lib.ptr(xstart), _lib.current_stream()))
-    else:
-        _lib.check(L.vd_posterior_from_xstart(model._handle, mode, B, per, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(t), clip, eta, _lib.ptr(nz), 0, 0,
-                                              _lib.ptr(sample), _lib.ptr(xstart), None, _lib.current_stream()))
-    return sample, xstart, s
 
 
 @pytest.mark.parametrize("start_x", [False, True], ids=["eps", "predict_xstart"])

@@ -9,6 +9,7 @@ import torch
 
 from known_region_restated import (jump_noise_f32, jump_rows, known_merge_bound, known_merge_f32, merge_noise_f32, merged,
                                    q_jump_bound, q_jump_f32)
+from step_compose import MODES, _eager_chain, _randn
 from step_nll_restated import normal_bound, normal_fp64, ratio, tables
 from test_gpu_dpmpp_2m import _rand_window, _t, _window_kw, tiny
 from video_diffusion_amd import _lib
@@ -16,7 +17,6 @@ from video_diffusion_amd.executor import WindowExecutor
 from video_diffusion_amd.respace import repaint_schedule
 
 pytestmark = pytest.mark.gpu
-MODES = {"p_sample": 0, "ddim": 1, "dpmpp_2m": 3}
 
 
 def _np(v):
@@ -304,40 +304,6 @@ def test_the_step_under_guidance_and_the_refusals():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4, 5
-def _randn(shape, seed, offset):
-    out = torch.empty(shape, device="cuda")
-    _lib.check(_lib.lib().vd_randn(_lib.ptr(out), out.numel(), seed, offset, _lib.current_stream()))
-    return out
-
-
-def _eager_chain(model, diff, sampler, eta, x_init, kw, src, mask, seed, ops, keep=()):
-    """The window's documented arithmetic from the eager entries: op k owns the Philox range [k n, (k + 1) n), n = B per; a step draws
-    its sampler noise at k n and its merge noise at k n + n // 4 (vd_known_merge on the plain step's sample); a jump draws at k n and
-    drops dpmpp_2m's history."""
-    L = _lib.lib()
-    B, T, _, S, _ = x_init.shape
-    n = x_init.numel()
-    lat = kw["latent_mask"].reshape(-1).float().contiguous()
-    x, prev, kept = x_init.clone(), None, {}
-    for k, (op, tv) in enumerate(ops):
-        tt = _t(B, tv)
-        if op == "jump":
-            out = torch.empty_like(x)
-            _lib.check(L.vd_q_jump(model._handle, B, T, S * S, _lib.ptr(x), _lib.ptr(lat), _lib.ptr(tt), _lib.ptr(_randn(x.shape, seed, k * n)), 0, 0,
-                                   _lib.ptr(out), _lib.current_stream()))
-            x, prev = out, None
-        else:
-            noise = _randn(x.shape, seed, k * n) if sampler != "dpmpp_2m" else None
-            x, prev = diff._fused_step(MODES[sampler], model, x, tt, True, kw, eta=eta, noise=noise, prev_xstart=prev)
-            if src is not None:
-                z = _randn(x.shape, seed, k * n + n // 4)
-                _lib.check(L.vd_known_merge(model._handle, B, T, S * S, _lib.ptr(x), _lib.ptr(src), _lib.ptr(mask), _lib.ptr(lat), _lib.ptr(tt),
-                                            _lib.ptr(z), 0, 0, _lib.current_stream()))
-        if k + 1 in keep:
-            kept[k + 1] = x.clone()
-    return x, kept
-
-
 @pytest.mark.parametrize("sampler,eta", [("p_sample", 0.0), ("ddim", 0.5), ("dpmpp_2m", 0.0)])
 def test_window_graph_with_a_region_and_jumps(sampler, eta):
     """begin(known...), run(3), jump(2), run(): to the bit the eager chain; a second window reuses the graph; a window without a

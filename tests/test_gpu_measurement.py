@@ -7,32 +7,16 @@ import pytest
 import torch
 
 from measurement_restated import cell_mean_of, measure_fp64, project_bound, project_f32, second_application_bound
+from step_compose import MODES, _eager_chain, _from_xstart, _project
 from step_nll_restated import U, ratio
 from test_gpu_dpmpp_2m import _rand_window, _t, _window_kw, tiny
-from test_gpu_known_region import _bits, _eager_chain, _np, _same_bits
+from test_gpu_known_region import _bits, _np, _same_bits
 from video_diffusion_amd import _lib
 from video_diffusion_amd.executor import WindowExecutor
 from video_diffusion_amd.gaussian_diffusion import measure
 
 pytestmark = pytest.mark.gpu
-MODES = {"p_sample": 0, "ddim": 1, "dpmpp_2m": 3}
 STEP_OPERATORS = [(4, False), (1, True)]                                         # "at s = 4 and at gray"
-
-
-def _project(model, x0, y, lat, s, gray, misalign=False):
-    """vd_measurement_project on device copies -> the projected x_0 (a device tensor).  misalign: x_0 at an address 4 bytes off."""
-    B, T, _, H, W = x0.shape
-    if misalign:
-        buf = torch.empty(x0.numel() + 1, device="cuda")
-        out = buf[1:].view(x0.shape)
-        out.copy_(x0)
-        assert out.data_ptr() % 16 == 4
-    else:
-        out = x0.cuda().clone()
-    yd, ld = y.cuda().float().contiguous(), lat.cuda().float().reshape(-1).contiguous()
-    _lib.check(_lib.lib().vd_measurement_project(model._handle, B, T, H, W, _lib.ptr(out), _lib.ptr(yd), _lib.ptr(ld), s, 1 if gray else 0,
-                                                 _lib.current_stream()))
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
@@ -96,21 +80,6 @@ def test_projection_entry_refusals():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2
-def _from_xstart(model, mode, x, x0, t, eta, noise, prev, want_mean=False):
-    """The sampler pass alone on an x_0 handed in, clip off -> (sample, pred_xstart) or the posterior mean."""
-    L = _lib.lib()
-    B, per = x.shape[0], x[0].numel()
-    sample, xs, mean = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-    if mode == 3:
-        _lib.check(L.vd_dpmpp_2m_from_xstart(model._handle, B, per, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(prev), _lib.ptr(t), 0, _lib.ptr(sample),
-                                             _lib.ptr(xs), _lib.current_stream()))
-    else:
-        _lib.check(L.vd_posterior_from_xstart(model._handle, mode, B, per, _lib.ptr(x), _lib.ptr(x0), _lib.ptr(t), 0, float(eta), _lib.ptr(noise),
-                                              0, 0, None if want_mean else _lib.ptr(sample), _lib.ptr(xs), _lib.ptr(mean) if want_mean else None,
-                                              _lib.current_stream()))
-    return mean if want_mean else (sample, xs)
-
-
 def _window_measurement(c, s, gray, seed):
     """A measurement for the window `c`: A of a random video, so every frame's cells get a target of their own."""
     g = torch.Generator().manual_seed(seed)

@@ -212,6 +212,7 @@ SIGNATURES = {
     "vd_window_begin": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _U, _U, _L, _P]),
     "vd_window_run": (_I, [_P, _I, _P]),
     "vd_window_graphs": (_I, [_P]),
+    "vd_window_history": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "vd_posterior_update": (_I, [_P, _I, _I, _L, _P, _P, _P, _I, _F, _P, _U, _U, _P, _P, _P]),
     "vd_posterior_from_xstart": (_I, [_P, _I, _I, _L, _P, _P, _P, _I, _F, _P, _U, _U, _P, _P, _P, _P]),
     "vd_attn_blocks": (_I, [_P]),

@@ -3094,6 +3094,23 @@ int vd_window_run(vd_engine* e, int n_steps, void* stream) {
 
 int vd_window_graphs(vd_engine* e) { return e ? (int)e->win_graphs.size() : -1; }
 
+// what the armed window carries from step to step, copied out on `stream` (device to device; each pointer optional): the history of
+// samplers 3 and 4 / UniPC's D_{t+1} (`hist`), and UniPC's x^c_{t+1} and D_{t+2}.  Meaningful behind the window's first step.
+int vd_window_history(vd_engine* e, int B, int T, float* hist, float* ubase, float* ud2, void* stream) {
+    VD_REQUIRE(e, "null engine");
+    VD_REQUIRE(!e->win_lost && e->win_cur >= 0, "vd_window_history: no window is armed (vd_window_begin first)");
+    const vd_engine::WinKey& k = e->win_graphs[e->win_cur].key;
+    VD_REQUIRE(B == k.B && T == k.T, "vd_window_history: B and T are the armed window's");
+    VD_REQUIRE(sampler_has_history(k.sampler), std::string("vd_window_history: ") + sampler_name(k.sampler) + " carries no history");
+    VD_REQUIRE((!ubase && !ud2) || sampler_is_unipc(k.sampler), std::string("vd_window_history: ") + sampler_name(k.sampler) + " carries one tensor, not UniPC's three");
+    const size_t bytes = (size_t)B * T * 3 * e->cfg.image_size * e->cfg.image_size * sizeof(float);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hist) VD_HIP(hipMemcpyAsync(hist, e->d_win_hist, bytes, hipMemcpyDeviceToDevice, st));
+    if (ubase) VD_HIP(hipMemcpyAsync(ubase, e->d_win_ubase, bytes, hipMemcpyDeviceToDevice, st));
+    if (ud2) VD_HIP(hipMemcpyAsync(ud2, e->d_win_ud2, bytes, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
 // ---- known region (pixel-mask inpainting): engine state like cfg_scale; a window graph's key carries the two addresses
 int vd_set_known_region(vd_engine* e, const float* known_src, const float* known_mask, const float* known_noise, unsigned long long seed,
                         unsigned long long offset) {

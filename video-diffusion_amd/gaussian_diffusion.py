@@ -1313,7 +1313,8 @@ class GaussianDiffusion:
         ddim_sample at eta = 0, dpmpp_2m_sample, unipc_sample, ddim_reverse_sample (they draw no noise: duplicates would never
         separate), a learned variance, known_region_scope, measurement_scope, dps_scope, deblur_scope, loss_guidance_scope, use_gradient_method,
         return_attn_weights, a batch that is no multiple of `particles`, and with the built-in reward denoised_fn.  WindowExecutor.begin
-        takes the built-in reward through its own keywords and refuses a reward_fn.  No claim about sample quality is made."""
+        takes the built-in reward through its own keywords and refuses a reward_fn.  Not honoured by model(...) itself, p_mean_variance
+        (it runs no sampler pass, and the scope acts behind one), score_windows and the NLL path.  No claim about sample quality is made."""
         base = self._bind(model)
         K, lam, tau, sig = check_steering(reward_fn, measurement, particles, scale, ess_threshold, sigma_y)
         if uniforms is not None and not (isinstance(uniforms, th.Generator) or callable(uniforms)):
