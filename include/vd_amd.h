@@ -1237,6 +1237,10 @@ long long vd_lpips_dim(int H, int W);
 /* frames [N][3][H][W] in the model's [-1, 1] space (no remapping, as LpipsEmbedder.forward) -> out [N][D].  Workspace owned by
  * the handle (grown on demand, bounded: frames are processed in chunks). */
 int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float* out, void* stream);
+/* Frames of H x W that vd_lpips_embed puts through the feature stack per pass when N is larger (the workspace bound of 2^26 floats over
+ * the per-frame activations, at most 65535), or -1 where vd_lpips_dim gives -1.  vd_lpips_embed runs min(N, this) frames at a time.
+ * Host only. */
+int vd_lpips_embed_chunk(int H, int W);
 /* Farthest-point selection on embs [B][n_cand][D] (inference_util.py:157-185): out [B*n + 1] ints receives per item the n picked
  * CANDIDATE indices (pick 0 and every pick i < n_always is always_host[i]; the others the argmax of the squared distance to the
  * nearest earlier pick, lowest index on ties; repicks possible), and out[B*n] an error word (bit 0: a distance was not finite).
@@ -1259,6 +1263,11 @@ int vd_fps_select(int B, int n_cand, long long D, const float* embs, int n, cons
  * Device pointers; enqueued only.  The partial-sum table is owned by the library (per device, grown on demand). */
 int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pred, int pred_is_u8, double ssim_data_range,
                      double* ssim_out, double* psnr_out, void* stream);
+/* What vd_frame_metrics launches with for H x W planes, from the function it calls itself: the input rows of a full LDS strip
+ * (32, fewer once two planes of 32 rows pass the tile: W >= 240, down to 7 at W = 1024), the strips per plane, and the row runs a
+ * strip's output rows are cut into (1 once W - 6 > 256: every thread then walks several columns).  Returns 0, or vd_frame_metrics'
+ * refusal of the size.  Host only. */
+int vd_frame_metrics_plan(int H, int W, int* rows_tile, int* nstrips, int* groups);
 /* out[n] = sum over d of (a[n][d] - b[n][d])^2 for rows of D floats, differences and sum in float64, fixed order. */
 int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream);
 

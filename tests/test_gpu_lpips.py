@@ -6,18 +6,30 @@ distance='lpips' end to end.  Weights are synthetic (seeded, He-scaled convs, no
 Error bound (fp32 operands and accumulation against fp64): every embedding element within 2e-5 * max|e| + 1e-5 * |e| of its tap, and every
 pairwise squared distance within 1e-5 relative.  Measured on the MI355X: largest relative distance error 1.9e-7 (32x32),
 8.8e-8 (64x64), 5.7e-8 (128x128), 1.6e-7 (48x40); largest absolute embedding error 6.9e-8.  The smallest relative margin of an
-argmax pick in the samplers' test videos: 2.2e-3 (asserted > 100x the distance bound)."""
+argmax pick in the samplers' test videos: 2.2e-3 (asserted > 100x the distance bound).
+
+Launch regimes only large inputs select (inputs in tests/eval_regime_cases.py, kept honest on the CPU by tests/test_eval_regimes_cpu.py):
+  * the chunk loop of vd_lpips_embed: 23 frames of 512 x 512 where `vd_lpips_embed_chunk` says 21 fit one pass; rows 0, 20, 21, 22 per element
+    (measured: largest absolute embedding error 8.9e-9), every row equal to the bit to its frame embedded alone, no two rows equal, guard
+    pads intact;
+  * pixels whose feature vector is all zero (den = 0 + 1e-10): exactly 0, nothing non-finite; measured largest absolute embedding error
+    on the non-zero rest 5.2e-8 (64 x 64) and 3.2e-8 (64 x 192);
+  * farthest-point selection over 257, 600 and 1000 candidates (each thread of fps_pick_kernel sees up to four values before the tree),
+    on integer embeddings whose distances are exact in float32: picks equal to the fp64 loop's, exact ties broken to the lowest index in
+    the strided pre-pass (f + 256 duplicates f) and in the tree (f + 300 duplicates f), a NaN beyond index 256 reported."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import eval_regime_cases as rc
 import video_diffusion_amd as vda
-from helpers import close, synth_sd
+from helpers import Guarded, close, synth_sd
 from lpips_restated import class_embedder, embed_parts_restated, embed_restated, select_restated, synth_weights
+from video_diffusion_amd import _lib
 from video_diffusion_amd import inference_util as iu
-from video_diffusion_amd.lpips import LpipsAlex, embedding_dim
+from video_diffusion_amd.lpips import LpipsAlex, embed_chunk, embedding_dim
 
 pytestmark = pytest.mark.gpu
 DIST_RTOL = 1e-5
@@ -293,3 +305,117 @@ def test_sampling_cli_adaptive_lpips(tmp_path, monkeypatch):
     for i in range(2):
         got = np.load(tmp_path / out / "samples" / f"sample_{i:04d}-0.npy")
         assert np.array_equal(got, want[i])
+
+
+# ---------------------------------------------------------------- launch regimes only large inputs select
+def _check_taps(got, parts, what):
+    """got (n, D) float64 against the restated per-tap pieces under the file's bound; the largest error."""
+    off, worst = 0, 0.0
+    for k, p in enumerate(parts):
+        g = got[:, off:off + p.shape[1]]
+        off += p.shape[1]
+        err = (g - p).abs()
+        bound = 2e-5 * p.abs().max() + 1e-5 * p.abs()
+        assert bool((err <= bound).all()), f"{what}, tap {k + 1}: max err {err.max().item():.3e}, max|e| {p.abs().max().item():.3e}"
+        assert p.abs().max() > 0
+        worst = max(worst, err.max().item())
+    assert off == got.shape[1]
+    return worst
+
+
+def test_embed_chunk_loop():
+    """More frames than one pass takes (vd_lpips_embed_chunk(512, 512) + 2 = 23 frames of 512 x 512: a pass of 21 and a short one of 2),
+    through the C entry into a guarded buffer.  Rows 0, chunk - 1, chunk and N - 1 per element and per tap against the restatement; every row
+    equal to the bit to that frame embedded alone (its sums have a fixed order that no neighbour enters); no two rows equal, so a row
+    written to another's place cannot pass; the pads untouched.  Measured on the MI355X: largest absolute embedding error 8.9e-9."""
+    emb, w = embedder()
+    H = W = 512
+    chunk = embed_chunk(H, W)
+    N = chunk + 2
+    assert N > chunk > 1
+    D = embedding_dim(H, W)
+    x = _frames(N, H, W, seed=512)
+    xd = x.cuda()
+    g = Guarded(N, D)
+    with torch.cuda.device(emb.device):
+        _lib.check(_lib.lib().vd_lpips_embed(emb._h, N, H, W, _lib.ptr(xd), _lib.ptr(g.t), _lib.current_stream()))
+    assert g.pads_intact(), "a pad was written"
+    got = g.t
+    assert bool(torch.isfinite(got).all()), "a row was not written (or is not finite)"
+    for n in range(N):
+        alone = emb(xd[n:n + 1]).reshape(-1)
+        assert torch.equal(alone, got[n]), f"row {n} differs from frame {n} embedded alone"
+        for m in range(n):
+            assert not torch.equal(got[m], got[n]), f"rows {m} and {n} are equal"
+    rows = [0, chunk - 1, chunk, N - 1]
+    worst = _check_taps(got[rows].cpu().to(torch.float64), embed_parts_restated(x[rows], w), f"rows {rows} of {N}")
+    print(f"LPIPS chunk loop {H}x{W}, N = {N}, chunk = {chunk}: max abs embedding error {worst:.3e}")
+
+
+_zero_emb = {}
+
+
+@pytest.mark.parametrize("W,flat,zero_taps", rc.ZERO_NORM_CASES)
+def test_zero_norm_pixels(W, flat, zero_taps):
+    """A pixel whose feature vector is all zero: den = sqrt(0) + 1e-10, the embedding there is exactly 0 and nothing is NaN.  Conv biases
+    -|bias|, frame 0 the ScalingLayer's shift colour in its first columns and noise in the rest, frame 1 the shift colour everywhere (64 x 64
+    with 40 flat columns: zero vectors at taps 1 and 2; 64 x 192 with 100: at every tap -- eval_regime_cases.ZERO_NORM_CASES)."""
+    w = rc.zero_norm_weights()
+    if not _zero_emb:
+        _zero_emb[0] = LpipsAlex.from_state_dict(_state_dict(w), "cuda:0")
+    emb = _zero_emb[0]
+    x = rc.zero_norm_frames(W, flat)
+    masks, finite = rc.zero_vector_masks(x, w)
+    assert finite
+    for k, m in enumerate(masks):
+        assert bool(m[0].any()) == (k + 1 in zero_taps) and not bool(m[0].all()) and bool(m[1].all()), f"tap {k + 1}"
+    got = emb(x).reshape(2, -1).cpu()
+    assert got.shape[1] == embedding_dim(64, W) and bool(torch.isfinite(got).all())
+    assert bool((got[1] == 0.0).all())
+    parts = embed_parts_restated(x[:1], w)
+    worst = _check_taps(got[:1].to(torch.float64), parts, f"zero-norm frame 0 at 64x{W}")
+    off = 0
+    for k, (p, m) in enumerate(zip(parts, masks)):                             # the zero vectors themselves: exactly 0, not merely small
+        g = got[0, off:off + p.shape[1]].view(-1, m.shape[1])
+        off += p.shape[1]
+        assert bool((g[:, m[0]] == 0.0).all()), f"tap {k + 1}"
+        assert bool((g[:, ~m[0]] != 0.0).any()), f"tap {k + 1}"
+    print(f"LPIPS zero-norm 64x{W}: zero vectors per tap {[int(m[0].sum()) for m in masks]}, max abs embedding error {worst:.3e}")
+    assert np.array_equal(emb.distance(x, x.clone()), np.zeros(2))
+
+
+@pytest.mark.parametrize("ncand", [257, 600, 1000])
+def test_select_many_candidates(ncand):
+    """More than 256 candidates: every thread of fps_pick_kernel sees several values before the tree.  Integer embeddings make every
+    squared distance exact in float32, so the picks equal the fp64 loop's with no margin to argue -- ties included (lowest index)."""
+    e = rc.int_embeddings(ncand, seed=ncand)
+    for always in ((0,), [5, 256, 3, ncand - 2]):
+        got = _check_select(e, 12, always)
+        assert got[0] != got[1] and all(len(set(row)) == 12 for row in got)
+        if ncand >= 600:
+            assert any(p >= 256 for row in got for p in row[len(always):])      # an argmax beyond a thread's first value
+
+
+def test_select_many_candidates_ties():
+    """Exactly equal maxima among more than 256 candidates: f + 256 duplicates f (the same thread meets both in its strided pre-pass),
+    f + 300 duplicates f (another thread of another wave: the tree's tie-break), and 600 equal candidates."""
+    for ndist in (256, 300):
+        base = rc.int_embeddings(ndist, seed=ndist, B=1)
+        assert len({tuple(r.tolist()) for r in base[0]}) == ndist
+        got = _check_select(torch.cat([base, base], dim=1), 12, (0,))
+        assert len(set(got[0])) == 12 and all(p < ndist for p in got[0]), got     # no duplicate's higher index is ever picked
+    same = torch.ones(1, 600, 32, dtype=torch.float64)
+    assert _check_select(same, 4, (3,)) == [[3, 0, 0, 0]]
+
+
+def test_select_many_candidates_nan_raises():
+    emb, _ = embedder()
+    e = rc.int_embeddings(600, seed=3).to(torch.float32)
+    want = select_restated(e.to(torch.float64), 3, (0,))
+    e[1, 431, 10] = float("nan")
+    with pytest.raises(FloatingPointError):
+        emb.select(e.cuda(), 3, (0,))
+    e[1, 431, 10] = 0.0
+    assert emb.select(e.cuda(), 3, (0,)) == select_restated(e.to(torch.float64), 3, (0,))
+    e = rc.int_embeddings(600, seed=3).to(torch.float32)
+    assert emb.select(e.cuda(), 3, (0,)) == want

@@ -22,7 +22,16 @@ bound applies.  It cannot hold as d -> 0: with ea' = ea + ua, eb' = eb + ub, d' 
 with sqrt(d) and is what the relative bound covers for well-separated pairs; the second does not shrink with d.  Its size from the
 per-element bound: |ua_i - ub_i| <= e_i := (2e-5 max|ea_tap| + 1e-5 |ea_i|) + (2e-5 max|eb_tap| + 1e-5 |eb_i|), so ||ua - ub||^2 <= sum_i e_i^2 =: ATOL
 (about 1e-7 at 64 x 64), computed per pair from the restated embeddings.  Tolerance: DIST_RTOL * d + ATOL.  The regular pairs are asserted
-to lie at least 1000 x above ATOL; one pair is deliberately near-identical."""
+to lie at least 1000 x above ATOL; one pair is deliberately near-identical.
+
+Wide frames.  SHAPES stops at 200 x 160: a full 32-row strip, one pass of the column loop.  tests/eval_regime_cases.py: WIDE_CASES are the frames
+on the other side of those branches -- W = 239 | 240 (the last full strip, the first shrunken one), 263 and 300 (W - 6 > 256: one row run per strip,
+threads walking two columns; a short last strip; planes and owned rows of no multiple of 4 floats), 1023 and 1024 (7-row strips, one per output
+row; four columns per thread) -- and `vd_frame_metrics_plan`, which the launcher itself calls, proves each case's regime.  The bound is the same
+scheme with these inputs' own pool: max(GAP_wide, FLOOR_wide), GAP_wide computed here, FLOOR_wide = 3 x MEASURED_WIDE.  Measured on the MI355X
+over the wide inputs: SSIM, kernel against float64, 9.68e-14 absolute at R = 2 and 2.68e-13 at R = 1, where the float32 gap of the restatement is
+3.63e-7 and 6.55e-7; PSNR 1.64e-8 relative, which again IS the float32 gap (1.636e-8).  Batched calls equal single frames to the bit at 12 x 1024
+and 70 x 300; views that start one float (gt) or one byte (uint8 prediction) into their buffers equal the aligned call to the bit."""
 import functools
 import os
 import pickle
@@ -32,11 +41,12 @@ import pytest
 import torch
 
 import metrics_restated as mr
+from eval_regime_cases import WIDE_CASES, check_wide_plan
 from lpips_restated import embed_parts_restated, synth_weights
 from video_diffusion_amd import _lib
 from video_diffusion_amd import video_eval as ve
 from video_diffusion_amd.lpips import LpipsAlex, embedding_dim
-from video_diffusion_amd.metrics import frame_ssim_psnr
+from video_diffusion_amd.metrics import frame_ssim_psnr, launch_plan
 from video_diffusion_amd.video_sample import to_uint8
 
 pytestmark = pytest.mark.gpu
@@ -45,6 +55,11 @@ DIST_RTOL = 1e-5                              # tests/test_gpu_lpips.py
 MEASURED = {"ssim_abs": 2.7e-13, "psnr_rel": 2.27e-8}
 SSIM_FLOOR = 3 * MEASURED["ssim_abs"]
 PSNR_FLOOR = 3 * MEASURED["psnr_rel"]
+
+# the same over the wide frames (WIDE_CASES) alone: measured on the MI355X by test_wide_frame_metrics_vs_restated, which prints them
+MEASURED_WIDE = {"ssim_abs": 2.68e-13, "psnr_rel": 1.64e-8}
+SSIM_FLOOR_WIDE = 3 * MEASURED_WIDE["ssim_abs"]
+PSNR_FLOOR_WIDE = 3 * MEASURED_WIDE["psnr_rel"]
 
 SHAPES = [(7, 7), (9, 33), (64, 64), (100, 70), (128, 128), (200, 160)]     # 200 x 160: several row strips per plane
 KINDS = ["noise", "outliers", "ramp", "quantised", "identical"]
@@ -296,3 +311,115 @@ def test_video_eval_cli_end_to_end(tmp_path, capsys):
     assert ve.main(argv) == path
     assert "No metrics to compute." in capsys.readouterr().out
     assert os.path.getmtime(path) == before
+
+
+# ---------------------------------------------------------------- frames 240 pixels or wider: shrunken strips, the column loop
+def _wide_cases():
+    for (H, W) in WIDE_CASES:
+        for C in (1, 3):
+            for kind in KINDS:
+                for u8 in (False, True):
+                    yield (H, W, C, kind, u8)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated_wide(R):
+    """`_restated` over the wide inputs alone: their own float64 values and their own float32 gap."""
+    out, gap_s, gap_p = {}, 0.0, 0.0
+    for key in _wide_cases():
+        H, W, C, kind, u8 = key
+        gt, pred = _case(kind, C, H, W, u8)
+        s64, p64 = mr.frame_ssim_psnr(gt, pred, R, np.float64)
+        s32, p32 = mr.frame_ssim_psnr(gt, pred, R, np.float32)
+        out[key] = (s64, p64)
+        gap_s = max(gap_s, float(np.abs(s32 - s64).max()))
+        fin = np.isfinite(p64)
+        assert np.array_equal(fin, np.isfinite(p32))
+        if fin.any():
+            gap_p = max(gap_p, float((np.abs(p32 - p64)[fin] / np.abs(p64[fin])).max()))
+    return out, gap_s, gap_p
+
+
+@pytest.mark.parametrize("R", [2.0, 1.0])
+def test_wide_frame_metrics_vs_restated(R):
+    """W >= 240: `tile_rows` leaves 32 (down to one strip per output row at W >= 1023) and, past W - 6 = 256, every thread walks several
+    columns.  The plan query proves the regime of each case; the values are held to the float64 restatement as the narrow ones are, with
+    the float32 gap and the measured floor of these inputs alone."""
+    for (H, W) in WIDE_CASES:
+        check_wide_plan(H, W, *launch_plan(H, W))
+    want, gap_s, gap_p = _restated_wide(R)
+    tol_s, tol_p = max(gap_s, SSIM_FLOOR_WIDE), max(gap_p, PSNR_FLOOR_WIDE)
+    worst_s, worst_p, n_inf = 0.0, 0.0, 0
+    failures = []
+    for key in _wide_cases():
+        H, W, C, kind, u8 = key
+        gt, pred = _case(kind, C, H, W, u8)
+        ssim, psnr = frame_ssim_psnr(gt, pred, R, device="cuda:0")
+        assert ssim.shape == (N_FRAMES,) and ssim.dtype == np.float64 and psnr.dtype == np.float64
+        s64, p64 = want[key]
+        es = float(np.abs(ssim - s64).max())
+        fin = np.isfinite(p64)
+        if not np.array_equal(psnr[~fin], p64[~fin]):                        # +inf stays +inf
+            failures.append((key, "psnr inf", psnr, p64))
+        n_inf += int((~fin).sum())
+        ep = float((np.abs(psnr - p64)[fin] / np.abs(p64[fin])).max()) if fin.any() else 0.0
+        worst_s, worst_p = max(worst_s, es), max(worst_p, ep)
+        if not (es <= tol_s and ep <= tol_p):
+            failures.append((key, es, ep))
+        if kind == "identical":
+            assert np.abs(ssim - 1.0).max() <= tol_s and not fin.any() and (psnr == np.inf).all()
+    print(f"wide frame metrics R={R}: float32 gap of the restatement ssim {gap_s:.3e} abs, psnr {gap_p:.3e} rel; "
+          f"kernel vs float64: ssim {worst_s:.3e} abs, psnr {worst_p:.3e} rel; {n_inf} +inf frames; MEASURED_WIDE {MEASURED_WIDE}")
+    assert n_inf > 0
+    assert not failures, failures[:5]
+    # the file's finding assert: the kernel is no worse than 10 x the reference's own float32 arithmetic
+    assert worst_s <= 10 * gap_s and worst_p <= 10 * gap_p
+
+
+@pytest.mark.parametrize("H,W", [(12, 1024), (70, 300)])
+@pytest.mark.parametrize("u8", [False, True])
+def test_wide_batched_call_is_bit_equal_to_single_frames(H, W, u8):
+    g = np.random.default_rng(6)
+    gt = g.random((5, 3, H, W)).astype(np.float32)
+    pred = (g.random((5, 3, H, W)) * 255).astype(np.uint8) if u8 else g.random((5, 3, H, W)).astype(np.float32)
+    s, p = frame_ssim_psnr(gt, pred, device="cuda:0")
+    assert np.isfinite(s).all() and np.isfinite(p).all() and len(set(s)) == 5 and len(set(p)) == 5
+    for n in range(5):
+        s1, p1 = frame_ssim_psnr(gt[n:n + 1], pred[n:n + 1], device="cuda:0")
+        assert s1[0] == s[n] and p1[0] == p[n]
+
+
+@pytest.mark.parametrize("shift_gt,shift_pred", [(1, 1), (1, 0), (0, 1)])
+def test_wide_misaligned_views_take_the_scalar_path_bit_equal(shift_gt, shift_pred):
+    """12 x 1024 looks aligned (W % 4 == 0, every strip a multiple of 4 floats), so the aligned call stages with 16-byte loads; a gt that
+    starts one float into its buffer, or a uint8 prediction that starts one byte into its own, must fall to the scalar loop.  That loop
+    adds a thread's squared errors in another order, so the inputs are chosen to make every order exact: gt and prediction are both
+    k / 255 in float32, a non-zero difference is at least 1 / 255 - 2^-24, its float32 square at least 2^-16 with a last bit of 2^-39 or
+    more, and a plane's sum is at most H W = 12288 < 2^14 -- 53 bits hold every partial sum.  The result equals the aligned call's bits."""
+    N, C, H, W = 2, 3, 12, 1024
+    g = np.random.default_rng(8)
+    gt = mr.u8_to_float(g.integers(0, 256, (N, C, H, W), dtype=np.uint8))
+    pred = g.integers(0, 256, (N, C, H, W), dtype=np.uint8)
+    d2 = (gt - mr.u8_to_float(pred)) ** 2
+    assert d2.dtype == np.float32 and d2[d2 > 0].min() >= 2.0 ** -16 and d2.max() <= 1.0 and H * W <= 2 ** 14
+    rows_tile, nstrips, _ = launch_plan(H, W)
+    assert W % 4 == 0 and (rows_tile * W) % 4 == 0 and nstrips > 1
+    n = N * C * H * W
+    L = _lib.lib()
+
+    def run(gt_t, pred_t):
+        assert gt_t.is_contiguous() and pred_t.is_contiguous()
+        out = torch.full((2 * N,), float("nan"), dtype=torch.float64, device="cuda:0")
+        _lib.check(L.vd_frame_metrics(N, C, H, W, _lib.ptr(gt_t), _lib.ptr(pred_t), 1, 2.0, _lib.ptr(out), _lib.ptr(out[N:]),
+                                      _lib.current_stream()))
+        return out.cpu().numpy()
+    gt_buf = torch.zeros(n + 4, dtype=torch.float32, device="cuda:0")
+    pred_buf = torch.zeros(n + 4, dtype=torch.uint8, device="cuda:0")
+    assert gt_buf.data_ptr() % 16 == 0 and pred_buf.data_ptr() % 16 == 0
+    gt_v, pred_v = gt_buf[shift_gt:shift_gt + n], pred_buf[shift_pred:shift_pred + n]
+    gt_v.copy_(torch.from_numpy(gt).reshape(-1))
+    pred_v.copy_(torch.from_numpy(pred).reshape(-1))
+    assert gt_v.data_ptr() % 16 == 4 * shift_gt and pred_v.data_ptr() % 4 == shift_pred
+    want = run(torch.from_numpy(gt).cuda().reshape(-1), torch.from_numpy(pred).cuda().reshape(-1))     # fresh allocations: aligned
+    got = run(gt_v, pred_v)
+    assert np.isfinite(want).all() and len(set(want)) == 2 * N and np.array_equal(got, want), (got, want)

@@ -341,9 +341,11 @@ SIGNATURES = {
     "vd_lpips_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),
     "vd_lpips_dim": (_L, [_I, _I]),
     "vd_lpips_embed": (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    "vd_fps_select": (_I, [_I, _I, _L, _P, _I, _P, _I, _P, _P, _P]),
+    "vd_lpips_embed_chunk": (_I, [_I, _I]),
+    "vd_fps_select":(_I, [_I, _I, _L, _P, _I, _P, _I, _P, _P, _P]),
     "vd_frame_metrics": (_I, [_I, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P]),
-    "vd_pair_sqdist": (_I, [_I, _L, _P, _P, _P, _P]),
+    "vd_frame_metrics_plan": (_I, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "vd_pair_sqdist":(_I, [_I, _L, _P, _P, _P, _P]),
     "vd_i3d_create": (_I, [ctypes.POINTER(_P)]),
     "vd_i3d_destroy": (None, [_P]),
     "vd_i3d_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),

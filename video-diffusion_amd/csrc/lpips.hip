@@ -161,6 +161,21 @@ long long lp_dim(int hs[5], int ws[5]) {
     return d;
 }
 
+// workspace floats per frame, a1 | p1 | a2 | p2 | a3 | a4 | a5 (NHWC)
+void lp_ws_sizes(const int hs[5], const int ws[5], size_t sz[7]) {
+    const size_t HW1 = (size_t)hs[0] * ws[0], HW2 = (size_t)hs[1] * ws[1], HW3 = (size_t)hs[2] * ws[2];
+    const size_t v[7] = {HW1 * 64, HW2 * 64, HW2 * 192, HW3 * 192, HW3 * 384, HW3 * 256, HW3 * 256};
+    for (int k = 0; k < 7; ++k) sz[k] = v[k];
+}
+
+// frames per pass: the workspace is bounded by 2^26 floats (256 MiB), the tap kernel's grid.y by 65535; at least one frame
+int lp_chunk(const size_t sz[7]) {
+    size_t per = 0;
+    for (int k = 0; k < 7; ++k) per += sz[k];
+    const size_t cap = (size_t)1 << 26;
+    return (int)std::max<size_t>(1, std::min<size_t>(65535, cap / per));
+}
+
 }  // namespace
 }  // namespace vd
 
@@ -244,6 +259,14 @@ long long vd_lpips_dim(int H, int W) {
     return lp_dim(hs, ws);
 }
 
+int vd_lpips_embed_chunk(int H, int W) {
+    int hs[5], ws[5];
+    if (!lp_dims(H, W, hs, ws)) return -1;
+    size_t sz[7];
+    lp_ws_sizes(hs, ws, sz);
+    return lp_chunk(sz);
+}
+
 int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float* out, void* stream) {
     VD_REQUIRE(h && frames && out, "null argument");
     VD_REQUIRE(h->loaded == (1u << 15) - 1, "LPIPS weights incomplete: conv1..5 weight/bias and lin1..5 are required");
@@ -254,13 +277,10 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
     if (N == 0) return 0;
     const long long D = lp_dim(hs, wds);
     const int hp1 = hs[1], wp1 = wds[1];                  // pool1 output = conv2 input/output size
-    const size_t HW1 = (size_t)hs[0] * wds[0], HW2 = (size_t)hs[1] * wds[1], HW3 = (size_t)hs[2] * wds[2];
-    // per frame: a1 | p1 | a2 | p2 | a3 | a4 | a5
-    const size_t sz[7] = {HW1 * 64, HW2 * 64, HW2 * 192, HW3 * 192, HW3 * 384, HW3 * 256, HW3 * 256};
-    size_t per = 0;
+    size_t sz[7], per = 0;
+    lp_ws_sizes(hs, wds, sz);
     for (size_t v : sz) per += v;
-    const size_t cap = (size_t)1 << 26;                   // workspace bound: 256 MiB
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((size_t)N, 65535), cap / per));   // grid.y of the tap kernel
+    const int chunk = std::min(N, lp_chunk(sz));          // what vd_lpips_embed_chunk answers, or all N frames
     if (int rc = grow_ws(&h->ws, &h->ws_floats, per * chunk)) return rc;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     long long offs[5];

@@ -245,24 +245,30 @@ using namespace vd;
 
 extern "C" {
 
+int vd_frame_metrics_plan(int H, int W, int* rows_tile, int* nstrips, int* groups) {
+    VD_REQUIRE(H >= MT_WIN && W >= MT_WIN, "frame metrics: SSIM's 7 x 7 window needs H >= 7 and W >= 7");
+    VD_REQUIRE(W <= MT_MAX_W, "frame metrics: frames are at most 1024 pixels wide (7 rows of both planes must fit the LDS tile)");
+    VD_REQUIRE(rows_tile && nstrips && groups, "null argument");
+    *rows_tile = tile_rows(W);
+    const int out_step = *rows_tile - (MT_WIN - 1);
+    *nstrips = (H - (MT_WIN - 1) + out_step - 1) / out_step;
+    const int ncols = W - (MT_WIN - 1);
+    *groups = std::max(1, std::min(MT_THREADS / ncols, std::min(*rows_tile, H) - (MT_WIN - 1)));
+    return 0;
+}
+
 int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pred, int pred_is_u8, double ssim_data_range,
                      double* ssim_out, double* psnr_out, void* stream) {
     VD_REQUIRE(N >= 0 && C >= 1, "frame metrics: N >= 0 frames of C >= 1 channel planes");
-    VD_REQUIRE(H >= MT_WIN && W >= MT_WIN, "frame metrics: SSIM's 7 x 7 window needs H >= 7 and W >= 7");
-    VD_REQUIRE(W <= MT_MAX_W, "frame metrics: frames are at most 1024 pixels wide (7 rows of both planes must fit the LDS tile)");
+    MetricsArgs a{};
+    if (int rc = vd_frame_metrics_plan(H, W, &a.rows_tile, &a.nstrips, &a.groups)) return rc;
     VD_REQUIRE(gt && pred && ssim_out && psnr_out, "null argument");
     VD_REQUIRE(ssim_data_range > 0.0, "frame metrics: ssim_data_range must be positive");
     VD_REQUIRE((reinterpret_cast<uintptr_t>(gt) & 3) == 0 && (pred_is_u8 || (reinterpret_cast<uintptr_t>(pred) & 3) == 0),
                "frame metrics: float planes must be 4-byte aligned");
     if (N == 0) return 0;
-    MetricsArgs a{};
     a.gt = gt; a.pred = pred; a.pred_u8 = pred_is_u8 ? 1 : 0;
     a.H = H; a.W = W;
-    a.rows_tile = tile_rows(W);
-    const int out_step = a.rows_tile - (MT_WIN - 1);
-    a.nstrips = (H - (MT_WIN - 1) + out_step - 1) / out_step;
-    const int ncols = W - (MT_WIN - 1);
-    a.groups = std::max(1, std::min(MT_THREADS / ncols, std::min(a.rows_tile, H) - (MT_WIN - 1)));
     a.C1 = (0.01 * ssim_data_range) * (0.01 * ssim_data_range);
     a.C2 = (0.03 * ssim_data_range) * (0.03 * ssim_data_range);
     const long long blocks = (long long)N * C * a.nstrips;

@@ -47,6 +47,15 @@ def embedding_dim(H, W):
     return sum(c * h * w for c, (h, w) in zip(CHANNELS, layer_sizes(H, W)))
 
 
+def embed_chunk(H, W):
+    """Frames of H x W that one pass of `vd_lpips_embed` takes (its workspace is bounded); a longer batch runs in several passes.
+    Host only.  ValueError where the frame is too small for the feature stack."""
+    n = int(_lib.lib().vd_lpips_embed_chunk(H, W))
+    if n < 0:
+        layer_sizes(H, W)
+    return n
+
+
 def _load_dict(path):
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):

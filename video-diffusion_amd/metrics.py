@@ -23,6 +23,15 @@ def check_frame_size(H, W):
         raise ValueError(f"win_size exceeds image extent: SSIM's {WIN}x{WIN} window does not fit a {H}x{W} frame")
 
 
+def launch_plan(H, W):
+    """(rows_tile, nstrips, groups) that `vd_frame_metrics` launches with for H x W planes: the input rows of a full LDS strip, the strips
+    per plane and the row runs per strip.  Host only; VdError where the size is refused."""
+    import ctypes
+    r, s, g = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().vd_frame_metrics_plan(H, W, ctypes.byref(r), ctypes.byref(s), ctypes.byref(g)))
+    return r.value, s.value, g.value
+
+
 def _device_tensor(a, device):
     t = a if isinstance(a, torch.Tensor) else torch.as_tensor(a)
     if t.dtype != torch.uint8:
