@@ -68,7 +68,11 @@ int vd_param_info(vd_engine* e, int index, char* name, int name_cap, int* ndim, 
  * [K/16][N/32][3][64][8], each image followed by its per-output scales; spatial_encoding -> [HW][C]) so that a
  * single RCCL broadcast replaces dist_util.sync_params' per-tensor broadcasts (dist_util.py:139-143).  The layout depends on
  * VD_MATH: vd_weights_layout_id() identifies it, and ranks compare it before accepting a broadcast buffer.
- * The buffer is caller-owned (e.g. a torch tensor) and must outlive the engine. */
+ * The buffer is caller-owned (e.g. a torch tensor) and must outlive the engine.
+ * vd_set_weight_storage / vd_set_weight_storage_host with another buffer than the bound one drop every captured window graph first
+ * (the graphs hold addresses inside the image; a window in flight is lost: vd_window_run reports "window graphs invalidated").
+ * vd_load_weight / vd_load_weight_bwd into device storage of an engine that has run wait for the whole device before they
+ * overwrite the image in place: captured graphs keep reading it, and the next window sees the new weights. */
 long long vd_weights_bytes(vd_engine* e);
 int vd_set_weight_storage(vd_engine* e, void* dev_buffer, long long bytes);
 /* The same packed image assembled in HOST memory (no GPU needed): pack once, then ship it -- a broadcast, a file, one
@@ -85,7 +89,8 @@ int vd_pos_channels(vd_engine* e);
 int vd_pos_resolution(vd_engine* e);
 
 /* Frequency tables of timestep_embedding / frame_embedding (nn.py:89-122), built by the host with
- * the reference's own float32 expression so the angles agree bit for bit. */
+ * the reference's own float32 expression so the angles agree bit for bit.  A call that replaces tables already uploaded drops
+ * every captured window graph first, like vd_set_schedule: each captured forward holds the tables' addresses. */
 int vd_set_freqs(vd_engine* e, const float* host_time_freqs, int n_time, const float* host_frame_freqs, int n_frame);
 
 /* SpacedDiffusion tables (respace.py:68-82, gaussian_diffusion.py:123-172,299-317).
@@ -623,7 +628,8 @@ int vd_posterior_from_xstart(vd_engine* e, int mode, int B, long long per_sample
 /* return_attn_weights (unet.py:457-466,799-836; gaussian_diffusion.py:277,496): per attention block the softmax weights
  * averaged over the heads, absolute value -- temporal (B*HW, T, T) and spatial (B*T, HW, HW) -- in execution order (input
  * blocks, middle, output blocks).  vd_attn_blocks / vd_attn_block_info size the buffers; vd_set_attn_capture arms the
- * capture for the following forwards (n = 0 clears it).  Two extra passes over q, k per block: the logging path. */
+ * capture for the following forwards (n = 0 clears it).  Two extra passes over q, k per block: the logging path.
+ * vd_window_begin refuses by name while a capture is armed: a captured step would bake the buffers' addresses in. */
 int vd_attn_blocks(vd_engine* e);
 int vd_attn_block_info(vd_engine* e, int i, int* resolution, int* channels);
 int vd_set_attn_capture(vd_engine* e, float* const* temporal, float* const* spatial, int n);

@@ -1880,6 +1880,8 @@ int vd_set_weight_storage(vd_engine* e, void* buf, long long bytes) {
     if (g_bound_device < 0) g_bound_device = dev;
     VD_REQUIRE(dev == g_bound_device, "libvdamd drives ONE device per process (one process per GPU); this process is already bound to another device");
     e->device = dev;
+    // every captured forward holds addresses inside the image it was captured on: graphs go before another buffer takes its place
+    if (e->wbuf && e->wbuf != static_cast<float*>(buf)) { if (e->win_cur >= 0) e->win_lost = true; e->drop_window_graphs(); }
     e->wbuf_on_host = false;
     e->wbuf = static_cast<float*>(buf);
     return 0;
@@ -1888,6 +1890,8 @@ int vd_set_weight_storage(vd_engine* e, void* buf, long long bytes) {
 int vd_set_weight_storage_host(vd_engine* e, void* host_buf, long long bytes) {
     VD_REQUIRE(e && host_buf, "null argument");
     VD_REQUIRE(bytes >= (long long)(e->packed_total * sizeof(float)), "weight buffer too small");
+    // (as vd_set_weight_storage: the engine stops tracking the device image the captured graphs read)
+    if (e->wbuf && e->wbuf != static_cast<float*>(host_buf)) { if (e->win_cur >= 0) e->win_lost = true; e->drop_window_graphs(); }
     e->wbuf = static_cast<float*>(host_buf);
     e->wbuf_on_host = true;
     return 0;
@@ -1906,6 +1910,10 @@ int vd_load_weight(vd_engine* e, const char* name, const float* host, long long 
     std::vector<float> tmp;
     const float* src = host;
     int rc_put = 0;
+    // a reload on a live model overwrites the image in place (captured graphs keep reading it: nothing is dropped); a step that reads the
+    // weights may still run, on any stream, and a NULL-stream copy is not ordered behind torch's side streams.  Nothing has run before
+    // the workspace exists.
+    if (!e->wbuf_on_host && e->ws) VD_HIP(hipDeviceSynchronize());
     if (p.kind == PK_LINF && split_math()) {
         // rows [row0, row0+rows) of a [frag_rows][K] matrix -> K/16 contiguous pieces of its bf16-split fragment image
         const int rows = (int)p.shape[0], K = (int)p.shape[1];
@@ -2005,6 +2013,8 @@ int vd_pos_resolution(vd_engine* e) { return e ? e->pos_res : -1; }
 
 int vd_set_freqs(vd_engine* e, const float* tf, int nt, const float* ff, int nf) {
     VD_REQUIRE(e && tf && nt > 0, "time frequencies");
+    // every captured forward reads the two tables: the graphs are dropped before a table they hold the address of is freed
+    if (e->d_freq_time || (ff && nf > 0 && e->d_freq_frame)) { if (e->win_cur >= 0) e->win_lost = true; e->drop_window_graphs(); }
     if (e->d_freq_time) VD_HIP(hipFree(e->d_freq_time));
     VD_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_freq_time), nt * sizeof(float)));
     VD_HIP(hipMemcpy(e->d_freq_time, tf, nt * sizeof(float), hipMemcpyHostToDevice));
@@ -2868,6 +2878,9 @@ int vd_window_begin(vd_engine* e, int B, int T, float* x, const float* obs_src, 
     if ((rc = require_history_rows(e, sampler, "sampler " + std::to_string(sampler) + " (" + sampler_name(sampler) + ")"))) return rc;
     VD_REQUIRE(t_start >= 0 && t_start < e->num_timesteps, "t_start outside the schedule");
     if ((rc = refuse_cut_step(e->cfg_w, e->dyn_p != 0.f && clip, e->prefix_cache_on, e->suffix_skip_on))) return rc;
+    // forward() launches the weight passes wherever the capture's pointers are set: a graph captured now would bake them in, and a graph
+    // found would not write them.  return_attn_weights is served by the bare forward alone (armed for one call)
+    VD_REQUIRE(e->attn_cap_t.empty() && e->attn_cap_s.empty(), "a window graph together with return_attn_weights (vd_set_attn_capture) is not served: clear the capture (n = 0) first");
     if (e->freeu_on()) {
         VD_REQUIRE(!e->prefix_cache_on, "FreeU (vd_set_freeu) together with the window prefix cache (vd_set_window_prefix_cache) is not served");
         VD_REQUIRE(!e->suffix_skip_on, "FreeU (vd_set_freeu) together with the window suffix skip (vd_set_window_suffix_skip) is not served");
@@ -3585,6 +3598,7 @@ int vd_load_weight_bwd(vd_engine* e, const char* name, const float* host, long l
     std::vector<float> tmp((size_t)p.packed_bwd, 0.f);
     pack_weight_bwd(host, bwd_kind_of(p), (int)p.shape[0], (int)p.shape[1], tmp.data());
     float* dst = e->wbuf_bwd + p.off_bwd;
+    if (!e->wbuf_bwd_on_host && e->ws) VD_HIP(hipDeviceSynchronize());      // (as vd_load_weight: a differentiated pass may still read the image)
     if (e->wbuf_bwd_on_host) std::memcpy(dst, tmp.data(), p.packed_bwd * sizeof(float));
     else VD_HIP(hipMemcpy(dst, tmp.data(), p.packed_bwd * sizeof(float), hipMemcpyHostToDevice));
     return 0;
