@@ -129,6 +129,19 @@ int vd_set_model_mean_type(vd_engine* e, int type);
  * The host mirror raises FloatingPointError. */
 int vd_device_errors(vd_engine* e, int* flags);
 
+/* Test hook: what the engine's scratch memory holds when the next call begins.  A call's bits must not depend on it -- every range a
+ * kernel reads is written by the same call first -- and tests/test_gpu_scratch_history.py checks that by comparing a call behind a fill
+ * with the same call on a freshly created engine.  In order: requires the engine's device; ends a held loss-guidance pass (its tape lives
+ * in the workspace: vd_guide_finish then fails on the stale ticket with this call's reason); waits for the whole device; hipMemset's
+ * every byte of the workspace (all of its capacity, the tail and what a larger window grew included) and of every engine-owned buffer
+ * that is scratch -- the list, with the rule and the buffers that are state, stands above the entry in csrc/engine.hip -- to `byte`
+ * (0..255); reports the bytes written (0 on an engine that has not run).
+ * Left alone: every address (nothing grows, nothing is freed, captured window graphs stay valid and are not dropped, the window generation
+ * does not move) and every piece of state: weights and their backward image, the schedule and coefficient tables, the device flags, the
+ * particle state, the armed window's counters, Philox triple and carried history, prefix stores, blur taps, operator matrices, FreeU's
+ * trig tables, the zero mask of cfg_scale.  No existing path calls it. */
+int vd_scratch_fill(vd_engine* e, int byte, long long* bytes_filled);
+
 /* Longest window, in frames per batch item, that every forward / step / window entry point accepts: 128.  A window is any
  * T in 1..vd_max_window_frames() (the reference's UNet takes any T; --max_frames picks it at sampling time).  T <= 32 runs
  * on the original temporal attention / GroupNorm kernels, 33..128 on their long-window forms (key tiles with an online
@@ -1247,6 +1260,9 @@ int vd_lpips_embed(vd_lpips* h, int N, int H, int W, const float* frames, float*
  * the per-frame activations, at most 65535), or -1 where vd_lpips_dim gives -1.  vd_lpips_embed runs min(N, this) frames at a time.
  * Host only. */
 int vd_lpips_embed_chunk(int H, int W);
+/* Test hook, as vd_scratch_fill: waits for the device and sets every byte of the handle's workspace to `byte`; the weights and the
+ * workspace's address stay.  bytes_filled: 0 on a handle that has not embedded. */
+int vd_lpips_scratch_fill(vd_lpips* h, int byte, long long* bytes_filled);
 /* Farthest-point selection on embs [B][n_cand][D] (inference_util.py:157-185): out [B*n + 1] ints receives per item the n picked
  * CANDIDATE indices (pick 0 and every pick i < n_always is always_host[i]; the others the argmax of the squared distance to the
  * nearest earlier pick, lowest index on ties; repicks possible), and out[B*n] an error word (bit 0: a distance was not finite).
@@ -1274,6 +1290,9 @@ int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pr
  * strip's output rows are cut into (1 once W - 6 > 256: every thread then walks several columns).  Returns 0, or vd_frame_metrics'
  * refusal of the size.  Host only. */
 int vd_frame_metrics_plan(int H, int W, int* rows_tile, int* nstrips, int* groups);
+/* Test hook, as vd_scratch_fill: waits for the device and sets every byte of the current device's partial-sum table to `byte`; its
+ * address stays.  bytes_filled: 0 before the first vd_frame_metrics. */
+int vd_frame_metrics_scratch_fill(int byte, long long* bytes_filled);
 /* out[n] = sum over d of (a[n][d] - b[n][d])^2 for rows of D floats, differences and sum in float64, fixed order. */
 int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream);
 
@@ -1317,6 +1336,9 @@ int vd_i3d_max_frames(void);
 /* videos [N][T][3][H][W] uint8 (device) -> out [N][400] (device).  Workspace owned by the handle, grown on demand for T; the videos
  * are processed one after another on `stream`.  A T outside 9 .. vd_i3d_max_frames() is refused before anything is allocated. */
 int vd_i3d_embed(vd_i3d* h, int N, int T, int H, int W, const unsigned char* videos, float* out, void* stream);
+/* Test hook, as vd_scratch_fill: waits for the device and sets every byte of the handle's workspace to `byte`; the weights and the
+ * workspace's address stay.  bytes_filled: 0 on a handle that has not embedded. */
+int vd_i3d_scratch_fill(vd_i3d* h, int byte, long long* bytes_filled);
 /* One convolution of that network on its own: x [T][H][W][Cin] channels-last, w [Cout][Cin][kt][kh][kw] and bias [Cout] (or NULL) on
  * the device, SAME padding, optional ReLU; output row (ot, oy, ox) at out + ((ot*Ho + oy)*Wo + ox) * out_stride, Cout floats
  * (out may point into a wider tensor).  Packs w on every call and waits for the stream: an entry for tests. */

@@ -812,7 +812,7 @@ def test_every_arithmetic_mode_end_to_end(mode):
     if mode == math_mode():
         pytest.skip("the test process' own mode: the whole suite runs in it")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "mode_check.py"), "--configs"], env={**os.environ, "VD_MATH": mode},
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "mode_check.py"), "--configs", "--scratch"], env={**os.environ, "VD_MATH": mode},
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     rep = json.loads(r.stdout.strip().splitlines()[-1])
@@ -824,6 +824,11 @@ def test_every_arithmetic_mode_end_to_end(mode):
     for tag, fig in rep["eps_configs"].items():
         print(f"{mode} {tag}: max |d eps| = {fig['max_err']:.3e} over {fig['compared']} elements, |eps| up to {fig['eps_max']:.2f}")
         assert fig["outside_tol"] == 0 and fig["compared"] > 0, (tag, fig)
+    # no output's bits depend on what the engine's scratch memory held (tests/test_gpu_scratch_history.py, history 1, in this mode)
+    assert sorted(rep["scratch"]) == sorted(["tiny"] + MODE_TAGS)
+    for name, fig in rep["scratch"].items():
+        print(f"{mode} {name}: {fig['differing']} of {fig['compared']} outputs differ behind a filled scratch")
+        assert fig["differing"] == 0 and fig["compared"] == (9 if mode == "fp32" else 15), (name, fig)      # (fp32 does not serve eps_vjp)
     fmax, fmean = (1.5, 1.25) if mode == "f16x3" else (1.5, 1.5)
     for op in ("linear", "conv"):
         k = rep[op]["fp32_kernel"]

@@ -9,7 +9,11 @@ bench.py for the modes it reports beside the headline).  One JSON line:
   psample_tiny            : the same for p_sample at t = 249, 248, 1, 0 on tests/golden/psample_tiny.npz
   eps_configs             : with --configs only (the per-mode test passes it): the same per configuration of
                             tests/config_sweep_cases.py's MODE_TAGS on tests/golden/unet_configs.npz (96 and 160 channels: generic and
-                            Winograd convs alternate, and the backward image's kernel follows the mode)"""
+                            Winograd convs alternate, and the backward image's kernel follows the mode)
+  scratch                 : with --scratch only (the per-mode test passes it): per configuration -- the tiny model of
+                            tests/test_gpu_scratch_history.py and MODE_TAGS -- the number of outputs of forward, p_sample and eps_vjp whose
+                            bits differ from a freshly created engine's (eps_vjp in the split modes only: fp32 does not serve it) when the engine's scratch memory was filled with 0x00, 0x7F and
+                            0xFF bytes in front of the call (vd_scratch_fill; the split kernels and their padded images differ per mode)"""
 import json
 import os
 import sys
@@ -115,7 +119,58 @@ def main():
         del model
     if "--configs" in sys.argv[1:]:
         out["eps_configs"] = eps_configs()
+    if "--scratch" in sys.argv[1:]:
+        out["scratch"] = scratch_history()
     print(json.dumps(out))
+
+
+def scratch_history():
+    """History 1 of tests/test_gpu_scratch_history.py in this process' mode -> {configuration: {'differing': n, 'compared': m}}."""
+    from config_sweep_cases import MODE_TAGS, case
+    defaults = vda.video_model_and_diffusion_defaults()
+    tiny = {**defaults, **dict(T=6, image_size=32, num_channels=32, num_res_blocks=1, rp_alpha=6, rp_beta=6, rp_gamma=6, timestep_respacing="ddim10")}
+    g = torch.Generator().manual_seed(77)
+    obs = torch.zeros(2, 3, 1, 1, 1)
+    obs[0, 0] = 1
+    tiny_c = dict(x=1.5 * torch.randn(2, 3, 3, 32, 32, generator=g), x0=(torch.rand(2, 3, 3, 32, 32, generator=g) * 2 - 1) * obs, obs_mask=obs,
+                  latent_mask=1 - obs, kinda_marg_mask=torch.zeros(2, 3, 1, 1, 1), frame_indices=torch.arange(3).view(1, 3).repeat(2, 1))
+    jobs = [("tiny", tiny, tiny_c, torch.tensor([5, 5]))] + [(tag, case(tag)["cfg"], case(tag)["c"], case(tag)["t"]) for tag in MODE_TAGS]
+    rep = {}
+    split = _lib.lib().vd_math_mode() != 2
+    for name, cfg, c, t in jobs:
+        kw = dict(frame_indices=c["frame_indices"].cuda(), x0=c["x0"].cuda(), obs_mask=c["obs_mask"].cuda(), latent_mask=c["latent_mask"].cuda(),
+                  kinda_marg_mask=c["kinda_marg_mask"].cuda(), x_t_minus_1=c["x0"].cuda(), observed_frames="x_0")
+        x, tt = c["x"].cuda(), t.cuda()
+        gg = torch.Generator().manual_seed(5)
+        noise, cot = torch.randn(x.shape, generator=gg).cuda(), torch.randn(x.shape, generator=gg).cuda()
+
+        def calls(model, diff):
+            eps = diff._wrap_model(model)(x, tt, **kw)[0]
+            sample, xstart = diff._step(0, model, x, tt, True, None, kw, 0.0, noise)
+            outs = [eps, sample, xstart]
+            if split:                                                            # the backward-data pass runs on the split arithmetic only: VD_MATH=fp32 refuses it by name
+                v = diff.eps_vjp(model, x, tt, cot, kw)
+                outs += [v["eps"], v["vjp"]]
+            model.check_device_errors()
+            return outs
+
+        def engine():
+            model, diff = vda.create_video_model_and_diffusion(**{k: cfg[k] for k in defaults})
+            model.load_state_dict(synth_sd(model.param_specs()))
+            model.to("cuda").eval()
+            return model, diff
+        want = calls(*engine())
+        model, diff = engine()
+        calls(model, diff)
+        differing = compared = 0
+        for byte in (0x00, 0x7F, 0xFF):
+            assert model.scratch_fill(byte) > 0
+            for got, ref in zip(calls(model, diff), want):
+                compared += 1
+                differing += int(not torch.equal(got.view(torch.int32), ref.view(torch.int32)))
+        rep[name] = {"differing": differing, "compared": compared}
+        del model
+    return rep
 
 
 def eps_configs():

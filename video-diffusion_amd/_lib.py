@@ -158,6 +158,7 @@ SIGNATURES = {
     "vd_mark_weights_loaded": (_I, [_P]),
     "vd_weights_layout_id": (_U, [_P]),
     "vd_device_errors": (_I, [_P, ctypes.POINTER(_I)]),
+    "vd_scratch_fill": (_I, [_P, _I, ctypes.POINTER(_L)]),
     "vd_pos_channels": (_I, [_P]),
     "vd_pos_resolution": (_I, [_P]),
     "vd_set_freqs": (_I, [_P, _P, _I, _P, _I]),
@@ -342,15 +343,18 @@ SIGNATURES = {
     "vd_lpips_dim": (_L, [_I, _I]),
     "vd_lpips_embed": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "vd_lpips_embed_chunk": (_I, [_I, _I]),
+    "vd_lpips_scratch_fill": (_I, [_P, _I, ctypes.POINTER(_L)]),
     "vd_fps_select":(_I, [_I, _I, _L, _P, _I, _P, _I, _P, _P, _P]),
     "vd_frame_metrics": (_I, [_I, _I, _I, _I, _P, _P, _I, _D, _P, _P, _P]),
     "vd_frame_metrics_plan": (_I, [_I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "vd_frame_metrics_scratch_fill": (_I, [_I, ctypes.POINTER(_L)]),
     "vd_pair_sqdist":(_I, [_I, _L, _P, _P, _P, _P]),
     "vd_i3d_create": (_I, [ctypes.POINTER(_P)]),
     "vd_i3d_destroy": (None, [_P]),
     "vd_i3d_load_weight": (_I, [_P, ctypes.c_char_p, _P, _L]),
     "vd_i3d_max_frames": (_I, []),
     "vd_i3d_embed": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "vd_i3d_scratch_fill": (_I, [_P, _I, ctypes.POINTER(_L)]),
     "vd_op_conv3d_same": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "vd_op_maxpool3d_same": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "vd_op_resize_bilinear_tf1": (_I, [_P, _I, _I, _I, _P, _P]),

@@ -2124,6 +2124,65 @@ int vd_device_errors(vd_engine* e, int* flags) {
     return 0;
 }
 
+// Test hook (include/vd_amd.h): every engine-owned SCRATCH buffer set to `byte` over its whole capacity, so that a test can say what
+// a call finds in memory it has not written yet.  The rule: a buffer is scratch when no call reads it before that same call has
+// written it; everything else is state and is not touched.  Every device pointer of struct vd_engine, once:
+//
+//   SCRATCH  ws                the activation arena and the step's tail (t_model, the two network outputs, the guidance scratch, DiffWs's
+//                              tail): each forward, backward and step writes what it reads.  A held loss-guidance pass keeps its tape
+//                              and eps there across two C calls: the fill ends it first, by name
+//            d_fu              h', skip', the structure map and the two statistics tables of one FreeU block
+//            d_lin_r           the residual between the linear projection's two passes
+//            d_part_scratch    the gather's copy of the tensors it permutes
+//            d_part_r          the built-in reward's residual
+//            d_part_partials   ... and its per-block sums, folded by particle_weights_kernel in the same step
+//            d_part_x0         the x_0 prediction of a steered window whose sampler keeps none, written by the step that reads it
+//            d_part            the NLL entries' per-block sums
+//            d_score_xt        vd_score_windows' x_t
+//            d_score_list      ... and its suffix list, uploaded by the call that reads it (its first n entries, n of that call)
+//   STATE    d_freq_time, d_freq_frame, d_tab, d_tmap, d_w2m, d_unipc, d_jump     the tables of the setters
+//            d_hid, d_out      the relative-position nets' offset tables (rpe_tables)
+//            d_cfg_zero        zeroed when it grows, read by every cfg_scale step after that
+//            d_fu_trig         FreeU's cos / sin tables
+//            d_blur_taps, d_lin_mats, d_part_sel                                  taps, operator matrices, the reward's selector rows
+//            d_part_logw, d_part_rprev, d_part_ess, d_part_anc, d_part_chosen, d_part_counters    the particle state
+//            d_err             the sticky flags
+//            d_win_t, d_win_rng                                                   the armed window's counters and Philox triple
+//            d_win_hist, d_win_ubase, d_win_ud2                                   ... and its carried history (the first step of a window does not
+//                              read them: state from the second step on)
+//            d_win_xtm1        redrawn by every step of an 'x_t_minus_1' window before the forward reads it: scratch in effect, kept as
+//                              state because it belongs to the armed window
+//            d_lists           a window graph's frame lists (WinGraph, beside its prefix store: state as well)
+// The weights (wbuf, wbuf_bwd) are the caller's.  No address changes: nothing grows, nothing is freed, and the captured window graphs stay.
+int vd_scratch_fill(vd_engine* e, int byte, long long* bytes_filled) {
+    VD_REQUIRE(e && bytes_filled && byte >= 0 && byte <= 255, "scratch_fill: an engine, a byte 0..255 and where to report the bytes");
+    *bytes_filled = 0;
+    if (e->device >= 0) if (int rc = require_device(e->device, "engine")) return rc;
+    e->end_held("dropped by vd_scratch_fill: the workspace the pass lives in was overwritten");
+    VD_HIP(hipDeviceSynchronize());
+    long long total = 0;
+    auto fill = [&](void* p, size_t bytes) -> int {
+        if (!p || !bytes) return 0;
+        VD_HIP(hipMemset(p, byte, bytes));
+        total += (long long)bytes;
+        return 0;
+    };
+    int rc = fill(e->ws, e->ws_cap);
+    if (!rc) rc = fill(e->d_fu, e->fu_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_lin_r, e->lin_r_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_part_scratch, e->part_scratch_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_part_r, e->part_r_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_part_partials, e->part_partials_cap * sizeof(double));
+    if (!rc) rc = fill(e->d_part_x0, e->part_x0_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_part, e->part_cap * sizeof(double));
+    if (!rc) rc = fill(e->d_score_xt, e->score_xt_cap * sizeof(float));
+    if (!rc) rc = fill(e->d_score_list, e->score_list_cap * sizeof(int));
+    if (rc) return rc;
+    VD_HIP(hipDeviceSynchronize());
+    *bytes_filled = total;
+    return 0;
+}
+
 int vd_workspace_bytes(vd_engine* e, int B, int T, long long* bytes) {
     VD_REQUIRE(e && bytes && B > 0 && T > 0, "arguments");
     Arena dry; dry.dry = true;

@@ -337,6 +337,19 @@ int vd_i3d_embed(vd_i3d* h, int N, int T, int H, int W, const uint8_t* videos, f
     return 0;
 }
 
+// Test hook, as vd_scratch_fill: the handle's workspace -- the six regions of i3d_plan and the pooled features, each written by the
+// embed that reads it -- set to `byte`.  The weights and the buffer's address stay.
+int vd_i3d_scratch_fill(vd_i3d* h, int byte, long long* bytes_filled) {
+    VD_REQUIRE(h && bytes_filled && byte >= 0 && byte <= 255, "scratch_fill: a handle, a byte 0..255 and where to report the bytes");
+    *bytes_filled = 0;
+    if (int rc = require_device(h->dev, "I3D")) return rc;
+    VD_HIP(hipDeviceSynchronize());
+    if (h->ws && h->ws_floats) VD_HIP(hipMemset(h->ws, byte, h->ws_floats * sizeof(float)));
+    VD_HIP(hipDeviceSynchronize());
+    *bytes_filled = h->ws ? (long long)(h->ws_floats * sizeof(float)) : 0;
+    return 0;
+}
+
 int vd_op_conv3d_same(const float* x, const float* w, const float* bias, int T, int H, int W, int Cin, int Cout, int kt, int kh,
                       int kw, int st, int sh, int sw, int relu, float* out, long long out_stride, void* stream) {
     VD_REQUIRE(x && w && out, "null argument");

@@ -253,6 +253,19 @@ int vd_lpips_load_weight(vd_lpips* h, const char* name, const float* host, long 
     return -1;
 }
 
+// Test hook, as vd_scratch_fill: the handle's workspace -- activations each embed writes before it reads them -- set to `byte`.  The
+// weights and the buffer's address stay.
+int vd_lpips_scratch_fill(vd_lpips* h, int byte, long long* bytes_filled) {
+    VD_REQUIRE(h && bytes_filled && byte >= 0 && byte <= 255, "scratch_fill: a handle, a byte 0..255 and where to report the bytes");
+    *bytes_filled = 0;
+    if (int rc = require_device(h->dev, "LPIPS")) return rc;
+    VD_HIP(hipDeviceSynchronize());
+    if (h->ws && h->ws_floats) VD_HIP(hipMemset(h->ws, byte, h->ws_floats * sizeof(float)));
+    VD_HIP(hipDeviceSynchronize());
+    *bytes_filled = h->ws ? (long long)(h->ws_floats * sizeof(float)) : 0;
+    return 0;
+}
+
 long long vd_lpips_dim(int H, int W) {
     int hs[5], ws[5];
     if (!lp_dims(H, W, hs, ws)) return -1;

@@ -292,6 +292,23 @@ int vd_frame_metrics(int N, int C, int H, int W, const float* gt, const void* pr
     return 0;
 }
 
+// Test hook, as vd_scratch_fill: the current device's partials table -- one pair per block, stored by ssim_strip_kernel and folded by
+// metrics_final_kernel in the same call -- set to `byte`.  The table's address stays.
+int vd_frame_metrics_scratch_fill(int byte, long long* bytes_filled) {
+    VD_REQUIRE(bytes_filled && byte >= 0 && byte <= 255, "scratch_fill: a byte 0..255 and where to report the bytes");
+    *bytes_filled = 0;
+    int dev = 0;
+    VD_HIP(hipGetDevice(&dev));
+    VD_REQUIRE(dev >= 0 && dev < 64, "device ordinal beyond the per-device workspace table");
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    MetricsWs& ws = g_ws[dev];
+    VD_HIP(hipDeviceSynchronize());
+    if (ws.part && ws.doubles) VD_HIP(hipMemset(ws.part, byte, ws.doubles * sizeof(double)));
+    VD_HIP(hipDeviceSynchronize());
+    *bytes_filled = ws.part ? (long long)(ws.doubles * sizeof(double)) : 0;
+    return 0;
+}
+
 int vd_pair_sqdist(int N, long long D, const float* a, const float* b, double* out, void* stream) {
     VD_REQUIRE(N >= 0 && D >= 1, "pair distance: N >= 0 rows of D >= 1 values");
     if (N == 0) return 0;

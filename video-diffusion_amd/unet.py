@@ -293,6 +293,13 @@ class CondMargVideoModel:
                 "an operand beyond the split's range (|x| >= 2^15; inputs of a 3x3 conv: 2^13) overflows -- set VD_MATH=bf16x6 (exact three-piece split, full "
                 "fp32 exponent range) on every rank and reload the weights")
 
+    def scratch_fill(self, byte):
+        """Test hook (vd_scratch_fill): every byte of the engine's workspace and of its scratch buffers set to `byte` -> the bytes written.
+        Waits for the device; ends a held loss-guidance pass; changes no address and no state, so captured window graphs stay."""
+        n = ctypes.c_longlong(0)
+        _lib.check(_lib.lib().vd_scratch_fill(self._handle, int(byte), ctypes.byref(n)))
+        return n.value
+
     # -- forward ---------------------------------------------------------------------------------------
     def _pack_kwargs(self, x, kw):
         """model_kwargs of video_sample.py:157-165 -> contiguous device buffers for the C ABI."""
